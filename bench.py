@@ -14,10 +14,18 @@ overlap the kernels of the others, and every kernel of the pipeline covers the -
 All stages run (census, cost, 8-path aggregation, WTA, LR check, speckle removal, median = the options of the reference's
 main.c).  Frames are independent units, so with N GPUs every rank processes its own K batches -- its share
 (sharding.frames_of_rank) of the 32-frame KITTI pool, cycled -- (weak scaling, no data-path collective); `value` is the
-whole-job aggregate.  Beside it in the same JSON line (N = 1): `device_resident` (the same frames already in HBM: kernels
-only), `sustained` (the headline loop for >= 2 s), `host_boundary` (the blocking one-frame-per-call contract, pageable
-buffers), `workloads` (the other single-GPU BASELINE configs: cone 8 / 4 paths, 2880x1988 D=256, 1762x800 D=192, each with
-its own roofline), `stream` (config 5 as a stream of 256 distinct frames), `cpu_baseline`.
+whole-job aggregate.  A plain run does only that: set-up, W warm-up steps, K timed steps, the result line.
+
+--full adds the other legs (--legs picks among them) to the same JSON line (N = 1): `device_resident` (the same frames already
+in HBM: kernels only), `sustained` (the headline loop for >= 2 s), `latency` (one frame alone), `host_boundary` (the blocking
+one-frame-per-call contract, pageable buffers), `workloads` (the other single-GPU BASELINE configs: cone 8 / 4 paths,
+2880x1988 D=256, 1762x800 D=192, each with its own roofline), `stream` (config 5 as a stream of 256 distinct frames),
+`cpu_baseline`, and the verification of the headline's frames below.
+
+--dump-outputs DIR writes what the timed path computed in its last step: DIR/disparity.npy, float32 [frames][H][W], the
+disparity maps of rank 0's last step in instance order (instance k's sub-batch of B frames at rows k*B .. k*B + B-1), with
+the library's invalid marker (+INF) written as min_disparity - 1 so that every value is finite; a fixed, seeded choice of
+whole frames where they exceed 64 MB.  The inputs depend on the arguments only.
 
 --mode tiles.  Every frame is cut into N row tiles, one per GPU (soc_project_stereo_matching_amd/tiling.py): boundary
 path costs are handed from rank to rank, several frames are in flight so that the ranks work as a pipeline, the rows are
@@ -25,7 +33,7 @@ gathered on the frame's owner rank, which runs speckle removal + median.  A step
 frames per launch and per hand-over); strong scaling.  On ONE GPU: --tile-ranks-in-process N runs N ranks as threads (device copies
 for the hand-overs), --tile-rank-alone r/N one rank's share with the exchanges skipped (tools/tiles_schedule_cost.py).
 
-Every leg hashes what it timed against the digests the reference's own C produced for the same seeds
+With --full every leg hashes what it timed against the digests the reference's own C produced for the same seeds
 (tests/golden/bench_frames.json): the headline the last 4 batches of every instance (`frames_verified`: 128 frames at the
 defaults), the other legs their last batches, the stream its first and last four frames.
 
@@ -554,9 +562,37 @@ class HostPipeline:
                         bad += 1
         return ok, bad, unp
 
+    def last_step_maps(self):
+        """Copies of the disparity maps of the last step, instance after instance: [n x B][H][W] float32."""
+        return np.concatenate([self.outs[k][(self.done[k] - 1) % self.keep] for k in range(len(self.insts))])
+
     def close(self):
         for i in self.insts:
             i.close()
+
+
+DUMP_LIMIT = 64_000_000        # --dump-outputs: bytes written at most
+
+
+def dump_outputs(path, maps, invalid_as):
+    """--dump-outputs: DIR/disparity.npy, float32, every value finite: invalid disparities (+INF) become `invalid_as`, which lies
+    below every valid one; any other non-finite value is refused.  Above DUMP_LIMIT a fixed, seeded choice of whole frames, kept in
+    order."""
+    maps = np.asarray(maps, dtype=np.float32)
+    invalid = np.isposinf(maps)                      # the library's one invalid marker; NaN or -INF would be a bug, not hidden here
+    bad = ~invalid & ~np.isfinite(maps)
+    if bad.any():
+        raise SystemExit(f"--dump-outputs: {int(bad.sum())} disparities are NaN or -INF")
+    if (maps[~invalid] <= invalid_as).any():
+        raise SystemExit(f"--dump-outputs: a valid disparity is <= {invalid_as}, the value invalid ones are written as")
+    maps = np.ascontiguousarray(np.where(invalid, np.float32(invalid_as), maps), dtype=np.float32)
+    if maps.nbytes > DUMP_LIMIT:
+        n = DUMP_LIMIT // maps[0].nbytes
+        if n < 1:
+            raise SystemExit(f"--dump-outputs: one frame is {maps[0].nbytes} bytes, more than {DUMP_LIMIT}")
+        maps = maps[np.sort(np.random.default_rng(0x5EED).choice(len(maps), n, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "disparity.npy"), maps)
 
 
 def device_resident_leg(S, torch, device, workload, B, n_inst, steps, warmup, overlap_post=False, cu_split="", honor4=False, alone=False):
@@ -822,7 +858,10 @@ def run_frames(args):
     B = max(1, args.batch)
     n_host = max(1, args.host_instances)
     digests = golden_digests(args.workload)
-    legs = set(args.legs.split(",")) if args.legs else {"headline", "sustained", "device", "latency", "host", "workloads", "stream", "cpu"}
+    if args.full:
+        legs = set(args.legs.split(",")) if args.legs else {"headline", "sustained", "device", "latency", "host", "workloads", "stream", "cpu"}
+    else:
+        legs = {"headline"}                              # a plain run: the headline figure and nothing else
     if world > 1:
         legs &= {"headline", "device"}
     if args.no_host_boundary:
@@ -862,7 +901,11 @@ def run_frames(args):
     torch.cuda.synchronize()
     barrier()
     stage_ms, stage_min, launches = merge_timing(hp.insts)
-    n_ok, n_bad, n_unp = hp.verify(batch_seeds, digests)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hp.last_step_maps(), opt.min_disparity - 1)
+    n_ok = n_bad = n_unp = None
+    if args.full:
+        n_ok, n_bad, n_unp = hp.verify(batch_seeds, digests)
     sustained = None
     if "sustained" in legs:
         el2, steps2 = hp.run_for(max(2.0, args.sustain_seconds), first_step=args.warmup + args.steps)
@@ -873,12 +916,14 @@ def run_frames(args):
                      "note": "the headline loop run for a fixed time instead of a fixed number of steps"}
     hp.close()
     if world > 1:
-        t = torch.tensor([elapsed, float(n_ok), float(n_bad), float(n_unp)], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+        t = torch.tensor([elapsed, float(n_ok or 0), float(n_bad or 0), float(n_unp or 0)], dtype=torch.float64,
+                         device="cuda" if backend == "nccl" else "cpu")
         tmax = t.clone()
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         elapsed = float(tmax[0].item())
-        n_ok, n_bad, n_unp = int(t[1].item()), int(t[2].item()), int(t[3].item())
+        if args.full:
+            n_ok, n_bad, n_unp = int(t[1].item()), int(t[2].item()), int(t[3].item())
 
     # ---- the same frames already resident in HBM (kernels only), this rank ------------------------------------------------
     dev = None
@@ -915,12 +960,14 @@ def run_frames(args):
                        "rank0_host_threads_pinned_to_numa_node": numa_node},
             "ms_per_frame": round(elapsed / (args.steps * B * n_host) * 1e3, 4),
             "stage_ms_per_batch_launch": {k: round(v, 4) for k, v in stage_ms.items()},
-            "frames_verified": n_ok, "frames_mismatched": n_bad, "frames_without_reference_digest": n_unp,
-            "verified_against_golden": (n_bad == 0 and n_ok > 0 and n_unp == 0),
-            "verification": "sha256 of every frame of the last 4 batches of each instance (all ranks), copied back by the timed calls "
-                            "themselves, vs the reference's own C for the same seeds (tests/golden/bench_frames.json)",
             "source_id": source_id(),
         }
+        if args.full:
+            line.update({
+                "frames_verified": n_ok, "frames_mismatched": n_bad, "frames_without_reference_digest": n_unp,
+                "verified_against_golden": (n_bad == 0 and n_ok > 0 and n_unp == 0),
+                "verification": "sha256 of every frame of the last 4 batches of each instance (all ranks), copied back by the timed "
+                                "calls themselves, vs the reference's own C for the same seeds (tests/golden/bench_frames.json)"})
         dp = -(-d // 16) * 16
         line.update(rooflines(args.workload, w, h, d, B, stage_ms, stage_min, launches, fused=dp <= 256))
         for key in ("roofline", "roofline_sum_wta"):
@@ -1039,9 +1086,15 @@ def main():
                          "tiles mode: frames in flight through the rank pipeline (default 2 x ranks)")
     ap.add_argument("--host-instances", type=int, default=int(os.environ.get("SGM_BENCH_HOST_INSTANCES", "4")),
                     help="frames mode: instances (one host thread each) the headline's host-pointer pipeline round-robins steps over")
+    ap.add_argument("--full", action="store_true",
+                    help="frames mode: beside the headline run the other legs (--legs, default all at --gpus 1) and verify the "
+                         "headline's frames against the reference digests; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="frames mode: after the timed steps write the disparity maps of the last step to DIR/disparity.npy (float32; "
+                         "invalid disparities, +INF in the library's maps, as min_disparity - 1)")
     ap.add_argument("--legs", default=None,
-                    help="comma list of the legs to run (default all at --gpus 1): headline is always run; sustained, device, latency, "
-                         "host, workloads, stream, cpu")
+                    help="with --full: comma list of the legs to run (default all at --gpus 1): headline is always run; sustained, "
+                         "device, latency, host, workloads, stream, cpu")
     ap.add_argument("--sustain-seconds", type=float, default=2.0)
     ap.add_argument("--stream-frames", type=int, default=256)
     ap.add_argument("--tile-ranks-in-process", type=int, default=0,
@@ -1067,9 +1120,11 @@ def main():
     ap.add_argument("--alone", type=int, default=1, choices=[0, 1], nargs="?", const=1,
                     help="device-resident leg: after its timed region also time the batches with ONE instance and nothing else on the GPU -> "
                          "device_resident.roofline.alone (the kernel's own quality; in the timed regions other batches share the chip).  "
-                         "On by default; the kernel-trace profile of tools/refresh_profiles.sh runs --legs headline, which has no such launches")
+                         "On by default; the kernel-trace profile of tools/refresh_profiles.sh is a plain run (headline only), which has no such launches")
     args = ap.parse_args()
     if args.mode == "tiles":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs is a frames-mode option")
         # a rank of the tile pipeline keeps ~N + 3 HIP streams busy, some with millisecond-long serial kernels (tile_begin's
         # horizontal lines); on HIP's default of 4 hardware queues short kernels queue up behind those (measured, NOTES.md
         # section 7: 1.9 -> 1.45 ms per frame for one rank of eight at 3840x2160).  Read by the runtime when it starts.
@@ -1084,6 +1139,8 @@ def main():
         return (tb.run_tiles if python_host else tb.run_tiles_c)(args, init_dist, WORKLOADS, golden_digests)
     if args.cu_split or os.environ.get("SGM_BENCH_CU_SPLIT"):
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # up to three streams per instance in flight: no two of them on one hardware queue
+    if args.legs and not args.full:
+        raise SystemExit("--legs picks among the legs of --full")
     args.workload = args.workload or "kitti_1242x375_d128_p8"
     args.batch = args.batch or 8
     args.in_flight = args.in_flight or 2

@@ -10,14 +10,28 @@
 #      there = undefined behaviour, Q6);
 #   2. the uint8_t loop counter at SemiGlobalMatching.c:272 is widened so D >= 256 terminates (Q2).
 # Each edit must match exactly one source line or the build fails.
+#
+# build_ref.sh main -- the reference's own driver (SemiGlobalMatching/main.c, read in place with its own headers) linked against
+#   libsgm_mi355x.so instead of SemiGlobalMatching.c, into oracle/_ref/sgm_ref_main (tests/test_reference_main_links.py).
 set -euo pipefail
-W=${1:?width} H=${2:?height} D=${3:?disparity range}
+W=${1:?"width, or main"} H=${2:-} D=${3:-}
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 REF="${SGM_REFERENCE_DIR:-/root/reference}/SemiGlobalMatching/SemiGlobalMatching"
 SRC="$REF/SemiGlobalMatching.c"
 [ -f "$SRC" ] || { echo "build_ref.sh: reference not present at $SRC (nothing built)"; exit 3; }
 OUT="$HERE/_ref"
 mkdir -p "$OUT"
+
+if [ "$W" = main ]; then
+  PKG="$HERE/../soc_project_stereo_matching_amd"
+  [ -f "$PKG/libsgm_mi355x.so" ] || { echo "build_ref.sh main: build libsgm_mi355x.so first"; exit 5; }
+  # found at run time next to the package, wherever the tree lies
+  gcc -O2 -w -I"$REF" "$REF/main.c" -o "$OUT/sgm_ref_main" -L"$PKG" -lsgm_mi355x \
+      -Wl,-rpath,'$ORIGIN/../../soc_project_stereo_matching_amd' -lm
+  echo "built $OUT/sgm_ref_main"
+  exit 0
+fi
+: "${H:?height}" "${D:?disparity range}"
 
 # the reference's buffers are static arrays: past 2 GB of .bss the default code model cannot address them
 MODEL=""

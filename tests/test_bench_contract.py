@@ -170,3 +170,51 @@ def test_bench_prints_exactly_one_stdout_line():
         assert json.load(f)["value"] == full["value"]
     if not had:
         os.remove(detail)
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: the maps with invalid disparities (+INF) written as the given finite value; above the limit the same seeded
+    choice of whole frames every time, in order."""
+    import numpy as np
+    maps = np.random.default_rng(1).random((8, 5, 7), dtype=np.float32) * 60
+    maps[maps < 6] = np.inf
+    want = np.where(np.isfinite(maps), maps, np.float32(-1))
+    bench.dump_outputs(str(tmp_path / "all"), maps, -1)
+    got = np.load(tmp_path / "all" / "disparity.npy")
+    assert got.dtype == np.float32 and np.isfinite(got).all() and np.array_equal(got, want) and (got == -1).any()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 3 * maps[0].nbytes)
+    bench.dump_outputs(str(tmp_path / "a"), maps, -1)
+    bench.dump_outputs(str(tmp_path / "b"), maps, -1)
+    a, b = np.load(tmp_path / "a" / "disparity.npy"), np.load(tmp_path / "b" / "disparity.npy")
+    assert a.dtype == np.float32 and a.nbytes <= bench.DUMP_LIMIT and len(a) == 3 and np.array_equal(a, b) and np.isfinite(a).all()
+    rows = [next(k for k in range(len(want)) if np.array_equal(f, want[k])) for f in a]
+    assert rows == sorted(rows)
+    with pytest.raises(SystemExit):                               # the marker must not collide with a valid disparity
+        bench.dump_outputs(str(tmp_path / "c"), maps, 10)
+    for v in (np.nan, -np.inf):                                   # only +INF means invalid: anything else non-finite is a bug
+        m = maps.copy()
+        m[3, 2, 1] = v
+        with pytest.raises(SystemExit):
+            bench.dump_outputs(str(tmp_path / "d"), m, -1)
+
+
+def test_last_step_maps_are_the_last_ring_slot_of_every_instance():
+    """HostPipeline.last_step_maps: instance k's newest output buffer (slot (done[k] - 1) % keep of its ring), instances in order."""
+    import numpy as np
+    hp = object.__new__(bench.HostPipeline)
+    hp.insts, hp.keep, B, h, w = [None] * 3, 4, 2, 3, 5
+    hp.outs = [[np.full((B, h, w), 10 * k + s, np.float32) for s in range(hp.keep)] for k in range(3)]
+    for done in (1, 4, 6, 9):
+        hp.done = [done] * 3
+        got = hp.last_step_maps()
+        assert got.shape == (3 * B, h, w)
+        assert [float(got[k * B + j, 0, 0]) for k in range(3) for j in range(B)] == [10 * k + (done - 1) % 4 for k in range(3) for _ in range(B)]
+        got[...] = -5                                              # a copy: the ring itself is untouched
+        assert all((o >= 0).all() for ring in hp.outs for o in ring)
+
+
+def test_legs_need_full():
+    """--legs only picks among the legs of --full: a plain run with --legs is refused before anything starts."""
+    import subprocess
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--legs", "device"], capture_output=True, text=True, timeout=120)
+    assert p.returncode != 0 and "--legs picks among the legs of --full" in p.stderr

@@ -1,12 +1,44 @@
-"""Our CPU restatement against the reference's own C (oracle/_ref, built by oracle/build_ref.sh) on seeded
-random shapes and options -- every stage.  Skipped where the reference build is absent (the golden
-fixtures of test_oracle_golden.py carry the same pin without it)."""
+"""Our CPU restatement against the reference's own C on seeded random shapes and options -- every stage.  The expected values
+are the sha256 digests of what the reference's own C (oracle/_ref, built by oracle/build_ref.sh) computed for these very cases,
+stored in tests/golden/reference_stages.json by tests/golden/make_golden_reference_stages.py: nothing here needs the reference."""
+import functools
+import json
+import os
+
 import numpy as np
 import pytest
 
-from oracle.pyoracle import DIRECTIONS, STAGE_NAMES, Reference, default_option, ref_path
+from conftest import GOLDEN
+from oracle.pyoracle import DIRECTIONS, STAGE_NAMES, default_option, sha
 
-pytestmark = pytest.mark.skipif(ref_path(24, 16, 8) is None, reason="oracle/_ref not built (needs /root/reference)")
+# (w, h, d, seed) of the per-direction aggregation comparison
+AGG_CASES = [(23, 17, 6, 1), (17, 23, 6, 2), (64, 9, 20, 3)]
+
+
+@functools.lru_cache(maxsize=None)
+def _golden():
+    with open(os.path.join(GOLDEN, "reference_stages.json")) as f:
+        return json.load(f)
+
+
+def case_id(c):
+    return f"{c[0]}x{c[1]}_d{c[2]}-{c[3]}_s{c[4]}"
+
+
+def agg_id(c):
+    return f"{c[0]}x{c[1]}_d{c[2]}_s{c[3]}"
+
+
+def _same(a, want):
+    """a holds the values of the reference's array `want` was made from (float32 maps: the same bit patterns)."""
+    if list(a.shape) != want["shape"]:
+        return False
+    if str(a.dtype) != want["dtype"]:
+        b = a.astype(want["dtype"])
+        if not np.array_equal(b, a):
+            return False
+        a = b
+    return sha(a) == want["sha256"]
 
 
 def _cases():
@@ -46,28 +78,29 @@ def _cases():
     return out
 
 
-@pytest.mark.parametrize("case", _cases(), ids=lambda c: f"{c[0]}x{c[1]}_d{c[2]}-{c[3]}_s{c[4]}")
+@pytest.mark.parametrize("case", _cases(), ids=case_id)
 def test_all_stages_equal_reference(oracle, case):
     w, h, dmin, dmax, seed, kw = case
+    want = _golden()["cases"][case_id(case)]
+    assert want["options"] == kw                                # the fixture was made for this very case
     left, right = oracle.synth_pair(w, h, dmax - dmin, seed)
+    assert sha(left) == want["sha256_inputs"]["left"] and sha(right) == want["sha256_inputs"]["right"]
     opt = default_option(dmax, dmin, **kw)
-    ref = Reference.for_shape(w, h, dmax - dmin)
-    want = ref.run(left, right, opt)
     got = oracle.run(left, right, opt)
     if not opt.is_check_lr:
         got["disp_r"][:] = 0
     for n in STAGE_NAMES:
-        a, b = got[n], want[n]
-        same = np.array_equal(a.view(np.uint32), b.view(np.uint32)) if a.dtype == np.float32 else np.array_equal(a, b)
-        assert same, f"{case}: stage {n} differs"
+        assert _same(got[n], want["stages"][n]), f"{case}: stage {n} differs"
 
 
 def test_per_direction_aggregation_equal_reference(oracle):
-    for (w, h, d, seed) in [(23, 17, 6, 1), (17, 23, 6, 2), (64, 9, 20, 3)]:
+    for (w, h, d, seed) in AGG_CASES:
+        want = _golden()["aggregate_dir"][agg_id((w, h, d, seed))]
         left, right = oracle.synth_pair(w, h, d, seed)
+        assert sha(left) == want["sha256_inputs"]["left"] and sha(right) == want["sha256_inputs"]["right"]
         opt = default_option(d)
-        ref = Reference.for_shape(w, h, d)
-        cost = ref.run(left, right, opt)["cost"]
+        cost = oracle.run(left, right, opt)["cost"]
+        assert _same(cost, want["cost"]), f"{(w, h)}: cost differs"
         for dx, dy in DIRECTIONS:
             S, _, _ = oracle.aggregate_dir(left, cost, opt.p1, opt.p2_init, dx, dy)
-            np.testing.assert_array_equal(S, ref.aggregate_dir(left, cost, opt, dx, dy), err_msg=f"{(w, h, dx, dy)}")
+            assert _same(S, want["directions"][f"{dx},{dy}"]), f"{(w, h, dx, dy)}"

@@ -1,21 +1,21 @@
-"""Build-container-only: the REFERENCE's own driver (SemiGlobalMatching/main.c:72,83) compiled in place -- nothing is
-copied into the repo -- and linked against libsgm_mi355x.so instead of the reference's SemiGlobalMatching.c, exactly
-the command INTEGRATION.md section 2 gives a maintainer.  Proves the drop-in claim at link level: the three entry
-points and the SGMOption layout the reference's caller was compiled against resolve to this library.
+"""The REFERENCE's own driver (SemiGlobalMatching/main.c:72,83) linked against libsgm_mi355x.so instead of the reference's
+SemiGlobalMatching.c, exactly the command INTEGRATION.md section 2 gives a maintainer: oracle/build_ref.sh main compiles it in place
+(nothing is copied into the repo) into oracle/_ref/sgm_ref_main when build() runs where the reference is present.  Proves the
+drop-in claim at link level: the three entry points and the SGMOption layout the reference's caller was compiled against resolve
+to this library.  Its inputs and the PNG the reference committed are data fixtures under tests/golden/ (cone_im2.png, cone_im6.png,
+cone_im2.d.png).
 
-Skips where /root/reference is absent (the GPU box): the reference does not travel."""
+Skips where oracle/_ref/sgm_ref_main was not built (no reference where build() ran)."""
 import os
 import subprocess
 
 import pytest
 
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
-REF = os.path.join(os.environ.get("SGM_REFERENCE_DIR", "/root/reference"), "SemiGlobalMatching")
-SRC = os.path.join(REF, "SemiGlobalMatching")
-PKG = os.path.join(ROOT, "soc_project_stereo_matching_amd")
+EXE = os.path.join(ROOT, "oracle", "_ref", "sgm_ref_main")
 
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(SRC, "main.c")), reason="reference sources not present")
+pytestmark = pytest.mark.skipif(not os.path.isfile(EXE), reason="oracle/_ref/sgm_ref_main not built (needs the reference)")
 
 
 @pytest.fixture(scope="module")
@@ -23,25 +23,21 @@ def exe(tmp_path_factory):
     import soc_project_stereo_matching_amd as S
     assert os.path.exists(S.library_path())
     d = tmp_path_factory.mktemp("refmain")
-    out = d / "bin" / "sgm_ref_main"
     (d / "bin").mkdir()
-    # main.c with the reference's own headers (SemiGlobalMatching.h, stb_image*.h) from where they lie; only OUR library
-    subprocess.check_call(["gcc", "-O2", "-w", "-I", SRC, os.path.join(SRC, "main.c"), "-o", str(out),
-                           "-L", PKG, "-lsgm_mi355x", f"-Wl,-rpath,{PKG}", "-lm"])
-    # the driver's paths are relative ("../Data/cone/..."): give it a private Data/cone with links to the two inputs,
-    # so that its output PNG is written next to them in the temporary directory and never under /root/reference
+    # the driver's paths are relative ("../Data/cone/..."): run it from a private bin/ beside a Data/cone with links to the two
+    # inputs, so that its output PNG is written next to them in the temporary directory
     cone = d / "Data" / "cone"
     cone.mkdir(parents=True)
     for f in ("im2.png", "im6.png"):
-        os.symlink(os.path.join(REF, "Data", "cone", f), cone / f)
-    return out
+        os.symlink(os.path.join(GOLDEN, f"cone_{f}"), cone / f)
+    return d / "bin"
 
 
 def test_reference_main_links_against_the_library(exe):
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", str(exe)], text=True)
+    und = subprocess.check_output(["nm", "-D", "--undefined-only", EXE], text=True)
     for sym in ("SGM_Initialize", "SGM_Match"):
         assert sym in und                                           # resolved at run time ...
-    ldd = subprocess.check_output(["ldd", str(exe)], text=True)
+    ldd = subprocess.check_output(["ldd", EXE], text=True)
     assert "libsgm_mi355x.so" in ldd and "not found" not in ldd     # ... by this library
     assert "sgm" not in [l.split()[-1] for l in und.splitlines()]  # the reference's global instance is not needed
 
@@ -50,7 +46,7 @@ def test_reference_main_runs_to_the_library(exe):
     """Without a GPU the run must end where the library says 'no device' (exit code -2 = main.c:74-78), with a GPU it
     must write the PNG the reference committed (all but the one undefined-behaviour pixel)."""
     import torch
-    p = subprocess.run([str(exe)], cwd=str(exe.parent), capture_output=True, text=True, timeout=120)
+    p = subprocess.run([EXE], cwd=str(exe), capture_output=True, text=True, timeout=120)
     if not torch.cuda.is_available():
         assert p.returncode == 254 and "SGM initialization failed" in p.stdout
         assert "no HIP device" in p.stderr
@@ -58,6 +54,6 @@ def test_reference_main_runs_to_the_library(exe):
     assert p.returncode == 0, p.stdout + p.stderr
     import numpy as np
     from PIL import Image
-    got = np.asarray(Image.open(exe.parent.parent / "Data" / "cone" / "im2.d.png"))
-    want = np.asarray(Image.open(os.path.join(REF, "Data", "cone", "im2.d.png")))
+    got = np.asarray(Image.open(exe.parent / "Data" / "cone" / "im2.d.png"))
+    want = np.asarray(Image.open(os.path.join(GOLDEN, "cone_im2.d.png")))
     assert np.argwhere(got != want).tolist() == [[374, 153]]

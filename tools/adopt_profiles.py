@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""After `gpurun -- 'bash tools/refresh_profiles.sh'`: copy what that run left under gpurun_out/ into profiles/ as round N's files
-(counters.json, rNN_bench.json = stdout, rNN_bench_detail.json, kernel trace summary, kernel stats) and rewrite the numbers
-paragraph of profiles/README.md from them.  Refuses files measured on other kernel sources.   python tools/adopt_profiles.py 04"""
+"""python tools/adopt_profiles.py NN OUTDIR -- after `bash tools/refresh_profiles.sh OUTDIR` on an MI355X: copy what that run left
+in OUTDIR into profiles/ as round NN's files (counters.json, rNN_bench.json = stdout, rNN_bench_detail.json, kernel trace summary,
+kernel stats) and rewrite the numbers paragraph of profiles/README.md from them.  Refuses files measured on other kernel sources."""
 import json
 import os
 import re
@@ -13,8 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
-r = sys.argv[1] if len(sys.argv) > 1 else "04"
-g, p = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+if len(sys.argv) != 3:
+    raise SystemExit(__doc__)
+r, g, p = sys.argv[1], os.path.abspath(sys.argv[2]), os.path.join(ROOT, "profiles")
 c = json.load(open(os.path.join(g, "counters.json")))
 d = json.load(open(os.path.join(g, "bench_detail.json")))
 line = open(os.path.join(g, "bench.json")).read()

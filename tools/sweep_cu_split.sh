@@ -8,7 +8,7 @@ mkdir -p "$(dirname "$out")"
 run() {   # label, in-flight, env..., then spec
     local label=$1 inflight=$2 spec=$3; shift 3
     local line
-    line=$(env "$@" python bench.py --steps 100 --warmup 20 --host-instances "$inflight" --legs sustained ${spec:+--cu-split "$spec"} 2>>"$out.err" | tail -1)
+    line=$(env "$@" python bench.py --steps 100 --warmup 20 --host-instances "$inflight" --full --legs sustained ${spec:+--cu-split "$spec"} 2>>"$out.err" | tail -1)
     python - "$label" "$inflight" "$spec" "$*" "$line" >> "$out" <<'PY'
 import json, sys
 label, inflight, spec, env, line = sys.argv[1:6]

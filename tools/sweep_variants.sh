@@ -5,7 +5,7 @@ cd "$(dirname "${BASH_SOURCE[0]}")/.."
 for lib in intree variants/*/libsgm_mi355x.so; do
     if [ "$lib" = intree ]; then unset SGM_LIBRARY_PATH; name=intree; else export SGM_LIBRARY_PATH="$PWD/$lib"; name=$(basename "$(dirname "$lib")"); fi
     out=gpurun_out/sweep_${name}.json
-    timeout -k 10 300 python bench.py --steps 40 --warmup 8 --legs device,sustained --alone "$@" > "$out" 2>> gpurun_out/sweep.err || { echo "$name FAILED"; continue; }
+    timeout -k 10 300 python bench.py --steps 40 --warmup 8 --full --legs device,sustained --alone "$@" > "$out" 2>> "${out%/*}/sweep.err" || { echo "$name FAILED"; continue; }
     python - "$out" "$name" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
