@@ -96,6 +96,28 @@ void SGM_SetHonorNumPaths(int honor);
 bool SGM_SetCensusWindow(int width, int height);
 void SGM_SetReferenceView(int right);
 
+/* Hole filling (extension, "parity unpinned by the reference": SemiGlobalMatching.h:24-40 has no such option; defined here
+ * and restated by tests/fill_holes_ref.py).  The discontinuity-preserving interpolation of Hirschmueller's SGM paper: the
+ * pixels the LR check, the uniqueness test and speckle removal leave +INF get a disparity from their neighbourhood, occluded
+ * pixels from the background.  Off by default (every launch, buffer and result is then the reference's); takes effect at the
+ * next SGM_Initialize / sgm_initialize / SGM_Reset / sgm_reset, which return false in row-tile mode (sgm_set_rows) with it on.
+ * INF = +INFINITY; ref = the reference view's map after WTA (stage 4, or 5 with the right view), oth = the other view's; R =
+ * option.max_disparity.
+ *   1. Classes (stage 18, u8 [H][W]), from ref and oth BEFORE the LR check: 0 valid, 1 occluded, 2 mismatched; all 0 when
+ *      is_check_lr is off.  Left view, pixel x of row y, d = ref[y][x]: d == INF -> 2; else xr = (int)((double)((float)x - d)
+ *      + 0.5) (the LR check's own rounding); xr outside [0, W) -> 2; else r = oth[y][xr]: r == INF -> 0; |d - r| >
+ *      lrcheck_thres -> xl = (int)((double)((float)xr + r) + 0.5), class 1 if 0 <= xl < W and ref[y][xl] > d (INF included),
+ *      else 2; otherwise 0.  Right view: the mirror image (x + d, then xl - l).  Class != 0 exactly where the LR check
+ *      leaves +INF.
+ *   2. Filling, on the map after speckle removal, before the median: three Jacobi passes (each reads the map as it was when
+ *      the pass started) -- pass 1 the INF pixels of class 1, pass 2 the INF pixels of class 2, pass 3 every pixel still INF.
+ *      A target walks each of the 8 directions (+-1,0), (0,+-1), (+-1,+-1) for m = 1..R steps, stopping at the frame edge
+ *      or at the first finite value, which it collects.  k <= 8 candidates sorted ascending s[]: k == 0 stays INF; pass 1
+ *      takes s[1] if k >= 2 else s[0] (the background), passes 2 and 3 take s[k/2].  Compares and selects only: exact.
+ *   3. The median runs unchanged on the filled map.
+ * Timing: the classification counts toward "lrcheck", the three passes toward "speckle". */
+bool SGM_SetFillHoles(int enable);
+
 /* Same as SGM_Match but all three pointers are DEVICE pointers (HBM-resident frames) on the
  * instance's device.  Asynchronous on the instance's stream; SGM_Synchronize waits. */
 bool SGM_MatchDevice(const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left);
@@ -119,6 +141,7 @@ void          sgm_destroy(sgm_instance* s);
 void          sgm_set_honor_num_paths(sgm_instance* s, int honor);
 bool          sgm_set_census_window(sgm_instance* s, int width, int height);   /* see SGM_SetCensusWindow */
 void          sgm_set_reference_view(sgm_instance* s, int right);              /* see SGM_SetReferenceView */
+bool          sgm_set_fill_holes(sgm_instance* s, int enable);                 /* see SGM_SetFillHoles */
 bool          sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMOption* option);
 bool          sgm_reset(sgm_instance* s, uint16_t width, uint16_t height, const SGMOption* option);
 bool          sgm_match(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left);
@@ -219,6 +242,12 @@ bool   sgm_disparity_to_depth(sgm_instance* s, const float* d_disparity, size_t 
 bool   sgm_compare_depth(sgm_instance* s, const float* d_ground_truth, const float* d_test, size_t count, float abs_thresh,
                          double* rmse, double* bad_pixel_rate, uint64_t* n_valid);
 
+/* The filling of SGM_SetFillHoles (step 2) on any device map: d_disp, the instance's B frames of its shape, is filled in
+ * place with R = the option's max_disparity; d_class (u8 [B][H][W], classes 0/1/2) drives passes 1 and 2, NULL runs pass 3
+ * alone.  Asynchronous on sgm_stream(s), behind the last match.  Works whether or not filling is on for matches; the filled
+ * map of a match (stage 9) is overwritten. */
+bool   sgm_fill_holes(sgm_instance* s, float* d_disp, const uint8_t* d_class);
+
 /* ---- a test-platform frame end to end (the data formats either side of the path) ----
  * The server hands the board six byte planes per frame -- left B, G, R, right B, G, R, each h rows of w bytes
  * (HostScript_Server/server.py:105-131; received into frame_buffer.h:16-51 by tcp_perf_client.c:181-189) -- and expects h rows
@@ -239,6 +268,8 @@ bool   sgm_match_planes(sgm_instance* s, const uint8_t* planes, float fx, float 
  *        2 matching cost (u8 [H][W][D])   3 aggregated cost S (u16 [H][W][D])
  *        4 left disparity after WTA       5 right-view disparity
  *        6 after LR check                 7 after speckle removal        8 final (all f32 [H][W])
+ *        9 after hole filling (f32 [H][W]; needs sgm_keep_stages and filling on, SGM_SetFillHoles)
+ *        18 hole-filling classes (u8 [H][W]; after any match with filling on)
  *        10..17 per-direction path cost L_r of direction (which-10) (u8 [H][W][D]; cells the
  *               direction never visits read 0, cells visited twice hold the last-but-one visit)
  * Returns the number of bytes written, 0 on error or if `capacity` is too small. */
@@ -253,7 +284,8 @@ void   SGM_KeepStages(int enable);
 
 /* Per-kernel device time (ms) of the last match of the instance, measured with HIP events on
  * the instance's stream when timing is enabled.  names[i] points to static strings.
- * Returns the number of entries written (<= max_entries). */
+ * Returns the number of entries written (<= max_entries).  With hole filling on (SGM_SetFillHoles) the same eight entries:
+ * the classification is part of "lrcheck", the three filling passes are part of "speckle". */
 void   sgm_enable_timing(sgm_instance* s, int enable);
 int    sgm_last_timing(sgm_instance* s, const char** names, float* ms, int max_entries);
 /* Mean and minimum per-kernel time over every match since timing was (re-)enabled and collected by

@@ -173,6 +173,15 @@ int sgmd_lrcheck_right(int ord, void* stream, const sgmd_geom* g, const void* di
 int sgmd_speckle(int ord, void* stream, const sgmd_geom* g, void* disp, float diff, unsigned min_area,
                  void* labels, void* sizes, void* totals);
 
+/* Extension (parity unpinned by the reference), the hole filling of include/sgm_mi355x.h (sgm_set_fill_holes); sgm_fill.hip.
+ * classify: one byte per pixel of all B frames, 0 valid / 1 occluded / 2 mismatched, from the reference view's WTA map `ref` and
+ * the other view's `oth` as they are BEFORE the LR check (right != 0: the right view is the reference view); all 0 if !do_check.
+ * pass: one Jacobi pass (1 occluded, 2 mismatched, 3 every INF pixel; cls may be NULL for pass 3) of the 8-ray fill, walks of at
+ * most R steps, `in` -> `out` (distinct buffers).  sgm_host.c references both weakly (a host built without them has no filling). */
+int sgmd_fill_classify(int ord, void* stream, const sgmd_geom* g, const void* ref, const void* oth, float thres, int right,
+                       int do_check, void* cls);
+int sgmd_fill_pass(int ord, void* stream, const sgmd_geom* g, int R, const void* in, void* out, const void* cls, int pass);
+
 /* in-place raster-order 3x3 median (the reference calls MedianFilter with in == out, .c:120).
  * scratch: sgmd_median_scratch_bytes(g) bytes for the pre-sorted neighbourhoods. */
 /* status: NULL, or an int in page-locked host memory (sgmd_alloc_pinned) that the chained kernel of tall frames sets to 1 when a

@@ -64,6 +64,8 @@ struct sgm_instance {
     int honor_num_paths;
     int census_w, census_h;      /* census window (sgm_set_census_window); 0 = the reference's 5x5 */
     int reference_view;          /* 0 = left (reference), 1 = right (sgm_set_reference_view) */
+    int fill_req;                /* hole filling asked for (sgm_set_fill_holes); takes effect at the next initialize */
+    bool fill_on;                /* ... and in effect for this shape: the class map and the ping-pong map exist */
     int reference_statics;       /* the default instance behind SGM_Initialize / SGM_Reset / SGM_Match: its census buffers behave like
                                     the reference's static arrays (SemiGlobalMatching.h:67-68) -- zero at first, never cleared, the words
                                     census_transform_5x5 does not write (.c:136,140-141) keep what an earlier frame of another shape left
@@ -108,6 +110,8 @@ struct sgm_instance {
     size_t cap_census_need;
     int need_key[7];                     /* W, H, rows, dmin, Dp, ndirs the map was built for */
     void *d_bgr, *d_depth, *h_bgr;       /* a test-platform frame's six colour planes, its depth map, pinned staging (first use) */
+    void *d_fill_class, *d_fill_map;     /* hole filling: u8 class map and the f32 ping-pong map ([B][H][W] each; only when asked for) */
+    size_t cap_fill;
     size_t cap_bgr;
     size_t plane_bytes;
     /* pinned staging for the host-pointer entry point */
@@ -263,6 +267,10 @@ static void free_device_buffers(sgm_instance* s)
         sgmd_free(s->device, *all[i]);
         *all[i] = NULL;
     }
+    if (s->d_fill_class) sgmd_free(s->device, s->d_fill_class);
+    if (s->d_fill_map) sgmd_free(s->device, s->d_fill_map);
+    s->d_fill_class = s->d_fill_map = NULL;
+    s->cap_fill = 0;
     sgmd_free_pinned(s->device, s->h_left);
     sgmd_free_pinned(s->device, s->h_right);
     sgmd_free_pinned(s->device, s->h_disp);
@@ -372,6 +380,20 @@ bool sgm_set_census_window(sgm_instance* s, int width, int height)
 }
 
 void sgm_set_reference_view(sgm_instance* s, int right) { if (s) s->reference_view = right ? 1 : 0; }
+
+/* The hole-filling launchers live in sgm_fill.hip; the host is also built without any HIP (tests link it against a stand-in
+ * device), where they are absent: weak references, and no filling there. */
+#pragma weak sgmd_fill_classify
+#pragma weak sgmd_fill_pass
+static bool fill_available(void) { return sgmd_fill_classify != NULL && sgmd_fill_pass != NULL; }
+
+bool sgm_set_fill_holes(sgm_instance* s, int enable)
+{
+    if (!s) return false;
+    if (enable && !fill_available()) FAIL("hole filling is not part of this build");
+    s->fill_req = enable ? 1 : 0;                                /* takes effect at the next initialize */
+    return true;
+}
 void sgm_keep_stages(sgm_instance* s, int enable) { if (s) s->keep_stages = enable; }
 
 bool sgm_set_batch(sgm_instance* s, int frames)
@@ -628,6 +650,40 @@ static int ensure_cost(sgm_instance* s)
     return rc;
 }
 
+/* the class map and the ping-pong map of the hole filling, [B][H][W] each */
+static int ensure_fill(sgm_instance* s)
+{
+    const size_t px = (size_t)s->g.B * s->g.W * s->g.H;
+    if (s->d_fill_map && px <= s->cap_fill) return 0;
+    sync_streams(s);
+    sgmd_free(s->device, s->d_fill_class);
+    sgmd_free(s->device, s->d_fill_map);
+    s->d_fill_class = s->d_fill_map = NULL;
+    s->cap_fill = 0;
+    if (sgmd_alloc(s->device, &s->d_fill_class, px) != 0 || sgmd_alloc(s->device, &s->d_fill_map, px * sizeof(float)) != 0) {
+        fprintf(stderr, "sgm_mi355x: device allocation failed for the hole-filling maps (%zu pixels)\n", px);
+        return -1;
+    }
+    s->cap_fill = px;
+    return 0;
+}
+
+/* the three Jacobi passes of the hole filling on `disp` (in place, through d_fill_map, which keeps the filled map: stage 9);
+ * cls == NULL: pass 3 alone */
+static int fill_passes(sgm_instance* s, void* st, void* disp, const void* cls)
+{
+    const int R = s->opt.max_disparity;
+    const size_t bytes = (size_t)s->g.B * s->g.W * s->g.H * sizeof(float);
+    int rc = 0;
+    if (cls) {
+        rc = sgmd_fill_pass(s->device, st, &s->g, R, disp, s->d_fill_map, cls, 1);                  /* occluded */
+        if (rc == 0) rc = sgmd_fill_pass(s->device, st, &s->g, R, s->d_fill_map, disp, cls, 2);     /* mismatched */
+    }
+    if (rc == 0) rc = sgmd_fill_pass(s->device, st, &s->g, R, disp, s->d_fill_map, NULL, 3);        /* every hole left */
+    if (rc == 0) rc = sgmd_d2d_async(s->device, st, disp, s->d_fill_map, bytes);
+    return rc;
+}
+
 bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMOption* option)
 {
     if (!s || !option) return false;
@@ -703,7 +759,14 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
     s->paths.run_anom = 1;
     s->need_plane_memset = !s->paths.ghost_zero;
 
+    s->fill_on = false;
+    if (s->fill_req && s->tile_end != 0)
+        FAIL("hole filling (sgm_set_fill_holes) works on whole frames: not available in row-tile mode (sgm_set_rows)");
     if (!ensure_buffers(s)) return false;
+    if (s->fill_req) {
+        if (ensure_fill(s) != 0) return false;
+        s->fill_on = true;
+    }
     /* extras: 4 anomalous lines x H steps x Dp bytes */
     const size_t extras_bytes = (size_t)s->g.B * 4 * height * s->g.Dp;
     if (extras_bytes > s->cap_extras || !s->d_extras) {
@@ -991,12 +1054,16 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
         st2 = s->post_stream;
         s->post_pending = true;                                  /* from here on the post stream has work of this match */
     }
+    if (s->fill_on)                  /* hole filling (extension): classes from both WTA maps, before the LR check rewrites them */
+        LAUNCH(sgmd_fill_classify(dev, st2, g, s->reference_view ? s->d_disp_r : d_out, s->reference_view ? d_out : s->d_disp_r,
+                                  o->lrcheck_thres, s->reference_view, o->is_check_lr ? 1 : 0, s->d_fill_class));
     LAUNCH(lr_stage(s, st2, d_out));                                                                /* .c:109 */
     if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_lr, d_out, px_bytes));
     mark_on(s, st2, 6);
     if (o->is_remove_speckles)                                                                      /* .c:115 */
         LAUNCH(sgmd_speckle(dev, st2, g, d_out, 1.0f, o->min_speckle_area, s->d_labels, s->d_sizes, s->d_totals));
     if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_speckle, d_out, px_bytes));
+    if (s->fill_on) LAUNCH(fill_passes(s, st2, d_out, s->d_fill_class));                           /* extension; timed as "speckle" */
     mark_on(s, st2, 7);
     LAUNCH(sgmd_median(dev, st2, g, d_out, s->d_median_scratch, s->h_status));                                   /* .c:120 */
     mark_on(s, st2, 8);
@@ -1303,6 +1370,19 @@ bool sgm_disparity_to_depth(sgm_instance* s, const float* d_disparity, size_t co
     return sgmd_depth(s->device, s->stream, d_disparity, count, fx, baseline, doffs, d_depth) == 0;
 }
 
+/* ------------------------------------------------------------------ hole filling of any map (extension) */
+
+bool sgm_fill_holes(sgm_instance* s, float* d_disp, const uint8_t* d_class)
+{
+    if (!s || !s->initialized || !d_disp) return false;
+    if (!fill_available()) FAIL("hole filling is not part of this build");
+    if (ensure_fill(s) != 0) return false;
+    /* the ping-pong map may still be in use by the post pass of the last match on a stream of its own */
+    if (wait_for_result(s, s->stream) != 0) return false;
+    if (fill_passes(s, s->stream, d_disp, d_class) != 0) FAIL("a kernel launch failed");
+    return true;
+}
+
 /* ------------------------------------------------------------------ a test-platform frame end to end (8f-2) */
 
 bool sgm_gray_from_planes(sgm_instance* s, const uint8_t* d_bgr, size_t count, int weight_r, uint8_t* d_gray)
@@ -1404,7 +1484,8 @@ size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacit
     size_t elem = 0;
     bool volume = false;
     int row_a = 0, row_b = s->g.H;                                /* rows the device holds of a volume stage */
-    if ((which == 4 || which == 6 || which == 7 || (which == 2 && !s->census_w)) && !s->keep_stages) return 0;
+    if ((which == 4 || which == 6 || which == 7 || which == 9 || (which == 2 && !s->census_w)) && !s->keep_stages) return 0;
+    if ((which == 9 || which == 18) && !s->fill_on) return 0;
     if (which == 2 && !s->d_cost) return 0;
     if (which == 3 && (ensure_S(s) != 0 || materialize_S(s) != 0)) return 0;
     switch (which) {
@@ -1417,6 +1498,8 @@ size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacit
     case 6: src = (const char*)s->d_snap_lr + f * px * 4; elem = 4; break;
     case 7: src = (const char*)s->d_snap_speckle + f * px * 4; elem = 4; break;
     case 8: src = (const char*)s->d_disp + f * px * 4; elem = 4; break;
+    case 9: src = (const char*)s->d_fill_map + f * px * 4; elem = 4; break;
+    case 18: src = (const char*)s->d_fill_class + f * px; elem = 1; break;
     default:
         if (which >= 10 && which < 10 + s->paths.ndirs) {
             /* frame-addressed base of the plane; only rows [plane_row_lo, plane_row_lo + plane_rows) have storage */
@@ -1470,7 +1553,14 @@ bool SGM_SetDevice(int device_ordinal)
     return true;
 }
 
-static int g_default_census_w, g_default_census_h, g_default_view;
+static int g_default_census_w, g_default_census_h, g_default_view, g_default_fill;
+
+bool SGM_SetFillHoles(int enable)
+{
+    if (enable && !fill_available()) FAIL("hole filling is not part of this build");
+    g_default_fill = enable ? 1 : 0;
+    return g_default ? sgm_set_fill_holes(g_default, enable) : true;
+}
 
 bool SGM_SetCensusWindow(int width, int height)
 {
@@ -1504,6 +1594,7 @@ bool SGM_Initialize(uint16_t width, uint16_t height, const SGMOption* option)
         g_default->reference_statics = 1;
         if (g_default_census_w) sgm_set_census_window(g_default, g_default_census_w, g_default_census_h);
         sgm_set_reference_view(g_default, g_default_view);
+        if (g_default_fill) sgm_set_fill_holes(g_default, 1);
     }
     return sgm_initialize(g_default, width, height, option);
 }

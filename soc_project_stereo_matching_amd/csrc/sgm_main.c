@@ -10,6 +10,7 @@
  *            [--paths 4|8] [--census WxH] [--right-reference]      extensions of the boundary: 4-path
  *            aggregation (the reference stores num_paths and ignores it), census windows other than 5x5, the right image
  *            as reference view; the defaults are the reference's behaviour
+ *            [--fill-holes]   extension: occlusion-aware hole filling of the invalid disparities (SGM_SetFillHoles)
  *   sgm_main --convert IN OUT.png        (image I/O only, no GPU: used by the CPU tests)
  */
 #define _POSIX_C_SOURCE 200809L
@@ -63,7 +64,7 @@ int main(int argc, char** argv)
     opt.p1 = 10;
     opt.p2_init = 150;
     const char* raw_path = NULL;
-    int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0;
+    int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0;
     for (int i = 4; i < argc; ++i) {
         const char* a = argv[i];
         const char* v = (i + 1 < argc) ? argv[i + 1] : NULL;
@@ -86,6 +87,7 @@ int main(int argc, char** argv)
             ++i;
         }
         else if (!strcmp(a, "--right-reference")) right_ref = 1;
+        else if (!strcmp(a, "--fill-holes")) fill_holes = 1;
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
     }
 
@@ -100,6 +102,7 @@ int main(int argc, char** argv)
     if (device >= 0) SGM_SetDevice(device);
     if (census_w && !SGM_SetCensusWindow(census_w, census_h)) { printf("unsupported census window %dx%d\n", census_w, census_h); return -2; }
     if (right_ref) SGM_SetReferenceView(1);
+    if (fill_holes && !SGM_SetFillHoles(1)) { printf("hole filling unavailable\n"); return -2; }
     if (!SGM_Initialize((uint16_t)w1, (uint16_t)h1, &opt)) { printf("SGM initialization failed\n"); return -2; }
     float* disp = (float*)malloc(sizeof(float) * (size_t)w1 * h1);
     double best = 1e30;

@@ -19,6 +19,8 @@ _LOAD_LOCK = threading.Lock()
 
 STAGE_NAMES = ["census_l", "census_r", "cost", "aggr", "disp_l", "disp_r", "after_lr", "after_speckle", "final"]
 _STAGE_DTYPE = [np.uint32, np.uint32, np.uint8, np.uint16] + [np.float32] * 5
+# stages outside STAGE_NAMES (read_stages() leaves them out: they exist only with hole filling on, set_fill_holes)
+STAGE_FILLED, STAGE_FILL_CLASS = 9, 18
 
 
 class SGMOption(C.Structure):
@@ -117,6 +119,13 @@ def _load() -> C.CDLL:
     L.SGM_SetCensusWindow.restype = C.c_bool
     L.SGM_SetReferenceView.argtypes = [C.c_int]
     L.sgm_keep_stages.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "sgm_set_fill_holes"):      # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_set_fill_holes.argtypes = [C.c_void_p, C.c_int]
+        L.sgm_set_fill_holes.restype = C.c_bool
+        L.SGM_SetFillHoles.argtypes = [C.c_int]
+        L.SGM_SetFillHoles.restype = C.c_bool
+        L.sgm_fill_holes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sgm_fill_holes.restype = C.c_bool
     L.sgm_set_batch.argtypes = [C.c_void_p, C.c_int]
     L.sgm_set_batch.restype = C.c_bool
     L.sgm_select_frame.argtypes = [C.c_void_p, C.c_int]
@@ -219,6 +228,10 @@ class _StageReader:
         h, w, d = self.shape
         if idx < 2 and getattr(self, "wide_census", False):
             dt, shp = np.uint64, (h, w)
+        elif idx == STAGE_FILLED:
+            dt, shp = np.float32, (h, w)
+        elif idx == STAGE_FILL_CLASS:
+            dt, shp = np.uint8, (h, w)
         elif idx >= 10:
             dt, shp = np.uint8, (h, w, d)
         else:
@@ -231,6 +244,14 @@ class _StageReader:
 
     def read_stages(self):
         return {n: self.read_stage(n) for n in STAGE_NAMES}
+
+    def read_filled(self):
+        """Stage 9: the map after hole filling, before the median (needs keep_stages and fill on)."""
+        return self.read_stage(STAGE_FILLED)
+
+    def read_fill_classes(self):
+        """Stage 18: the hole-filling classes, 0 valid / 1 occluded / 2 mismatched (after any match with fill on)."""
+        return self.read_stage(STAGE_FILL_CLASS)
 
 
 class SGM(_StageReader):
@@ -254,6 +275,10 @@ class SGM(_StageReader):
 
     def set_reference_view(self, right: bool):
         self.lib.SGM_SetReferenceView(int(right))
+
+    def set_fill_holes(self, enable: bool = True) -> bool:
+        """Extension: occlusion-aware hole filling of the +INF pixels (include/sgm_mi355x.h); next initialize/reset."""
+        return bool(self.lib.SGM_SetFillHoles(int(enable)))
 
     def keep_stages(self, enable=True):
         self.lib.SGM_KeepStages(int(enable))
@@ -387,6 +412,15 @@ class SGMInstance(_StageReader):
     def set_reference_view(self, right: bool):
         """Extension: True = the result is the right image's disparity map (mirrored LR check)."""
         self.lib.sgm_set_reference_view(self.handle, int(right))
+
+    def set_fill_holes(self, enable: bool = True) -> bool:
+        """Extension: occlusion-aware hole filling of the +INF pixels (include/sgm_mi355x.h); next initialize/reset."""
+        return bool(self.lib.sgm_set_fill_holes(self.handle, int(enable)))
+
+    def fill_holes(self, d_disp: int, d_class: int = None) -> bool:
+        """sgm_fill_holes: fill the +INF pixels of a device map of the instance's batch and shape in place (passes 1 and 2 need
+        the u8 class map d_class, None runs pass 3 alone); asynchronous on `stream`."""
+        return bool(self.lib.sgm_fill_holes(self.handle, d_disp, d_class or None))
 
     def keep_stages(self, enable=True):
         self.lib.sgm_keep_stages(self.handle, int(enable))
