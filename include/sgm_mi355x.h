@@ -118,6 +118,24 @@ void SGM_SetReferenceView(int right);
  * Timing: the classification counts toward "lrcheck", the three passes toward "speckle". */
 bool SGM_SetFillHoles(int enable);
 
+/* Matching confidence (extension, "parity unpinned by the reference": SemiGlobalMatching.c:380-426 computes min_cost and
+ * sec_min_cost of every pixel but never exposes them; defined here and restated by tests/confidence_ref.py).
+ * For each pixel of the REFERENCE view take the aggregated costs S after this match's cost sum (the Q14 accumulation of a
+ * Match without Reset included), index k = d - min_disparity in [0, D):
+ *   left view:  S[y][x][k];   right view (SGM_SetReferenceView(1)): S[y][x + min_disparity + k][k], columns outside the
+ *   image counting as 65535 (.c:397-407).
+ *   m1 = the smallest of these costs; d1 = the first index that reaches it (strict '>', .c:390 / .c:401);
+ *   m2 = the smallest cost over every index k != d1, 65535 if there is none (.c:381).
+ *   conf = (m2 == 0) ? 0 : (uint16_t)(((uint32_t)(m2 - m1) * 65535u) / m2)       (unsigned 32-bit, floor)
+ * So a pixel without any candidate (m1 = m2 = 65535) and a tie for the best cost both give 0.  The value describes the
+ * winner-take-all result: the LR check, the uniqueness test, speckle removal, hole filling and the median do not change it
+ * (mask it with the disparity map's +INF where needed), and it does not depend on is_check_unique / uniqueness_ratio.
+ * Layout u16 [B][H][W] like the disparity map.  disp is bit-identical to what the plain match returns for the same instance
+ * state.  The sgm_match_confidence* forms mirror sgm_match / sgm_match_async (+ sgm_match_wait) / sgm_match_device;
+ * SGM_MatchConfidence is SGM_Match on the default instance.  A NULL conf returns false and queues nothing; so does row-tile
+ * mode (sgm_set_rows), and a build without the confidence kernels.  Timing: the store counts toward "sum" / "wta". */
+bool SGM_MatchConfidence(const uint8_t* img_left, const uint8_t* img_right, float* disp_left, uint16_t* conf);
+
 /* Same as SGM_Match but all three pointers are DEVICE pointers (HBM-resident frames) on the
  * instance's device.  Asynchronous on the instance's stream; SGM_Synchronize waits. */
 bool SGM_MatchDevice(const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left);
@@ -156,6 +174,13 @@ bool          sgm_synchronize(sgm_instance* s);
  * staging copy on either side; any other host pointer is staged through the instance's own pinned buffers. */
 bool          sgm_match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left);
 bool          sgm_match_wait(sgm_instance* s);
+/* the matching confidence beside the disparity map (see SGM_MatchConfidence): host blocking, host pipelined (+ sgm_match_wait;
+ * buffers from sgm_host_alloc are used in place), device pointers (asynchronous, as sgm_match_device) */
+bool          sgm_match_confidence(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left, uint16_t* conf);
+bool          sgm_match_confidence_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left,
+                                         uint16_t* conf);
+bool          sgm_match_confidence_device(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left,
+                                          uint16_t* d_conf);
 void*         sgm_host_alloc(sgm_instance* s, size_t bytes);   /* page-locked host memory on the instance's device; NULL on failure */
 void          sgm_host_free(sgm_instance* s, void* p);
 /* Throughput option for a stream of matches on ONE instance: with sgm_set_overlap_post(s, 1) the post pass of a match (LR

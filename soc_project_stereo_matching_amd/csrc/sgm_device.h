@@ -160,6 +160,21 @@ int sgmd_upsum(int ord, void* stream, const sgmd_geom* g, const sgmd_paths* path
 int sgmd_wta_right(int ord, void* stream, const sgmd_geom* g, const void* S, int check_unique, float one_minus_ratio,
                    void* disp_r);
 
+/* Extension (parity unpinned by the reference), the matching confidence of include/sgm_mi355x.h (sgm_match_confidence): the
+ * launchers above that also store the reference view's confidence of every pixel to conf, u16 [B][H][W].  sgmd_sum_wta_conf: the
+ * left view; sgmd_wta_right_conf: the right view; sgmd_sum_wta_lr_conf: the left view, or the right one if conf_right (needs
+ * do_right).  conf == NULL: exactly the plain launcher.  sgm_host.c references them weakly (a host built without them answers
+ * false to the confidence entry points). */
+int sgmd_sum_wta_conf(int ord, void* stream, const sgmd_geom* g, int ndirs, const void* planes, size_t plane_bytes,
+                      const void* extras, const void* row_extras, const void* row_extra_count, int row_cap, int accumulate,
+                      void* S, int check_unique, float one_minus_ratio, void* disp_l, void* conf);
+int sgmd_sum_wta_lr_conf(int ord, void* stream, const sgmd_geom* g, int ndirs, const void* planes, size_t plane_bytes,
+                         const void* extras, const void* row_extras, const void* row_extra_count, int row_cap, int accumulate,
+                         int store_S, int do_right, void* S, int check_unique, float one_minus_ratio, void* disp_l, void* disp_r,
+                         void* conf, int conf_right);
+int sgmd_wta_right_conf(int ord, void* stream, const sgmd_geom* g, const void* S, int check_unique, float one_minus_ratio,
+                        void* disp_r, void* conf);
+
 /* SemiGlobalMatching.c:445-470 */
 int sgmd_lrcheck(int ord, void* stream, const sgmd_geom* g, void* disp_l, const void* disp_r, float thres);
 

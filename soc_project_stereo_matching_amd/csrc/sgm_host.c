@@ -112,6 +112,9 @@ struct sgm_instance {
     void *d_bgr, *d_depth, *h_bgr;       /* a test-platform frame's six colour planes, its depth map, pinned staging (first use) */
     void *d_fill_class, *d_fill_map;     /* hole filling: u8 class map and the f32 ping-pong map ([B][H][W] each; only when asked for) */
     size_t cap_fill;
+    void* conf_dst;                      /* matching confidence (extension): where the running match's cost sum stores it, NULL: nowhere */
+    void *d_conf, *h_conf;               /* device / page-locked staging of the host-pointer confidence entry points (first use) */
+    size_t cap_conf, cap_h_conf;
     size_t cap_bgr;
     size_t plane_bytes;
     /* pinned staging for the host-pointer entry point */
@@ -121,6 +124,7 @@ struct sgm_instance {
     float* async_out;            /* caller's buffer the staged result still has to be copied to (NULL: it was pinned, the
                                     device wrote it directly) */
     size_t async_bytes;
+    uint16_t* async_conf_out;    /* caller's confidence buffer the staged map still has to be copied to (NULL: none, or pinned) */
     /* a staged result (pageable caller buffer) comes back in RESULT_CHUNKS pieces, an event behind each: sgm_match_wait copies piece i
      * to the caller while piece i + 1 is still on the bus (a 1242x375 map: 1.86 MB, ~40 us of DMA + ~90 us of memcpy in sequence otherwise) */
     void* ev_chunk[4];
@@ -271,6 +275,10 @@ static void free_device_buffers(sgm_instance* s)
     if (s->d_fill_map) sgmd_free(s->device, s->d_fill_map);
     s->d_fill_class = s->d_fill_map = NULL;
     s->cap_fill = 0;
+    if (s->d_conf) sgmd_free(s->device, s->d_conf);
+    if (s->h_conf) sgmd_free_pinned(s->device, s->h_conf);
+    s->d_conf = s->h_conf = NULL;
+    s->cap_conf = s->cap_h_conf = 0;
     sgmd_free_pinned(s->device, s->h_left);
     sgmd_free_pinned(s->device, s->h_right);
     sgmd_free_pinned(s->device, s->h_disp);
@@ -395,6 +403,13 @@ bool sgm_set_fill_holes(sgm_instance* s, int enable)
     return true;
 }
 void sgm_keep_stages(sgm_instance* s, int enable) { if (s) s->keep_stages = enable; }
+
+/* The confidence launchers (sgm_sum_wta.hip): weak references as for the hole filling -- a host built without them (the
+ * stand-in device of the tests) answers false to the confidence entry points. */
+#pragma weak sgmd_sum_wta_conf
+#pragma weak sgmd_sum_wta_lr_conf
+#pragma weak sgmd_wta_right_conf
+static bool conf_available(void) { return sgmd_sum_wta_conf != NULL && sgmd_sum_wta_lr_conf != NULL && sgmd_wta_right_conf != NULL; }
 
 bool sgm_set_batch(sgm_instance* s, int frames)
 {
@@ -872,25 +887,37 @@ static int sum_and_wta(sgm_instance* s, void* st, void* d_out, bool with_marks)
     const int uniq = o->is_check_unique ? 1 : 0;
     const float keep = 1 - o->uniqueness_ratio;
     int rc;
+    const bool want_right = o->is_check_lr || s->reference_view;
+    void* const conf = s->conf_dst;                              /* the reference view's confidence (extension), or NULL */
     if ((!s->fused_wta || accumulate || s->keep_stages) && ensure_S(s) != 0) return -1;
     if (s->fused_wta) {
         const int store = s->keep_stages ? 1 : 0;
-        rc = sgmd_sum_wta_lr(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras,
-                             s->d_row_extras, s->d_row_count, s->row_cap, accumulate, store, (o->is_check_lr || s->reference_view) ? 1 : 0, s->d_S,
-                             uniq, keep, d_out, s->d_disp_r);
+        if (conf)
+            rc = sgmd_sum_wta_lr_conf(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras, s->d_row_extras,
+                                      s->d_row_count, s->row_cap, accumulate, store, want_right ? 1 : 0, s->d_S, uniq, keep, d_out,
+                                      s->d_disp_r, conf, s->reference_view);
+        else
+            rc = sgmd_sum_wta_lr(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras,
+                                 s->d_row_extras, s->d_row_count, s->row_cap, accumulate, store, want_right ? 1 : 0, s->d_S,
+                                 uniq, keep, d_out, s->d_disp_r);
         if (rc != 0) return rc;
         s->s_pending = !store;
         s->s_pending_accumulate = accumulate != 0;
         if (with_marks) mark_on(s, st, 4);
     } else {
-        rc = sgmd_sum_wta(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras,
-                          s->d_row_extras, s->d_row_count, s->row_cap, accumulate, s->d_S, uniq, keep, d_out);
+        if (conf && !s->reference_view)
+            rc = sgmd_sum_wta_conf(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras,
+                                   s->d_row_extras, s->d_row_count, s->row_cap, accumulate, s->d_S, uniq, keep, d_out, conf);
+        else
+            rc = sgmd_sum_wta(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras,
+                              s->d_row_extras, s->d_row_count, s->row_cap, accumulate, s->d_S, uniq, keep, d_out);
         if (rc != 0) return rc;
         /* d_S now holds this frame's sum whatever happens next */
         s->s_pending = false;
         s->s_is_zero = false;
         if (with_marks) mark_on(s, st, 4);
-        if (o->is_check_lr || s->reference_view) rc = sgmd_wta_right(s->device, st, &s->g, s->d_S, uniq, keep, s->d_disp_r);
+        if (conf && s->reference_view) rc = sgmd_wta_right_conf(s->device, st, &s->g, s->d_S, uniq, keep, s->d_disp_r, conf);
+        else if (want_right) rc = sgmd_wta_right(s->device, st, &s->g, s->d_S, uniq, keep, s->d_disp_r);
         if (rc != 0) return rc;
     }
     s->s_is_zero = false;
@@ -1012,8 +1039,8 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
         for (int f = 0; f < g->B; ++f)
             LAUNCH(sgmd_memset_async(dev, st, (char*)s->d_planes_alloc + ((size_t)f * 8 + 4) * s->plane_bytes, 0, 4 * s->plane_bytes));
     /* the last vertical sweep fused with the cost sum (sgmd_upsum): whenever this match neither adds to an earlier S (Q14) nor has
-     * to leave S behind for a test */
-    const bool use_up = s->up_rows > 0 && !s->keep_stages && s->s_is_zero && s->fused_wta;
+     * to leave S behind for a test, nor asks for the matching confidence (written by the cost-sum kernels) */
+    const bool use_up = s->up_rows > 0 && !s->keep_stages && s->s_is_zero && s->fused_wta && !s->conf_dst;
     s->last_up_rows = use_up ? s->up_rows : 0;
     if (use_up) {
         LAUNCH(ensure_upsum(s));
@@ -1290,15 +1317,62 @@ bool sgm_match_wait(sgm_instance* s)
     }
     if (!sgm_synchronize(s)) return false;
     if (s->async_out) memcpy((char*)s->async_out + done, (const char*)s->h_disp + done, s->async_bytes - done);   /* .c:122 */
+    if (s->async_conf_out) memcpy(s->async_conf_out, s->h_conf, s->async_bytes / sizeof(float) * sizeof(uint16_t));
     s->async_out = NULL;
+    s->async_conf_out = NULL;
     s->async_chunks = 1;
     return true;
+}
+
+/* the confidence staging: a device map for the host-pointer forms, and a page-locked one for callers whose buffer is not */
+static int ensure_conf(sgm_instance* s, bool host_staging)
+{
+    const size_t need = (size_t)s->g.B * s->g.W * s->g.H * sizeof(uint16_t);
+    if (!s->d_conf || need > s->cap_conf) {
+        sync_streams(s);
+        sgmd_free(s->device, s->d_conf);
+        s->d_conf = NULL; s->cap_conf = 0;
+        if (sgmd_alloc(s->device, &s->d_conf, need) != 0) return -1;
+        s->cap_conf = need;
+    }
+    if (host_staging && (!s->h_conf || need > s->cap_h_conf)) {
+        sgmd_free_pinned(s->device, s->h_conf);
+        s->h_conf = NULL; s->cap_h_conf = 0;
+        if (sgmd_alloc_pinned(s->device, &s->h_conf, need) != 0) return -1;
+        s->cap_h_conf = need;
+    }
+    return 0;
+}
+
+/* a match whose cost sum also stores the reference view's confidence to the device map d_conf */
+static bool run_pipeline_conf(sgm_instance* s, const void* d_left, const void* d_right, void* d_out, void* d_conf)
+{
+    s->conf_dst = d_conf;
+    const bool ok = run_pipeline(s, d_left, d_right, d_out);
+    s->conf_dst = NULL;
+    return ok;
+}
+
+/* what every confidence entry point checks before it queues anything */
+static bool conf_ready(sgm_instance* s, const void* l, const void* r, const void* disp, const void* conf)
+{
+    if (!s || !s->initialized || !l || !r || !disp || !conf) return false;
+    if (s->tile_end != 0) FAIL("the matching confidence works on whole frames: not available in row-tile mode (sgm_set_rows)");
+    if (!conf_available()) FAIL("the matching confidence is not part of this build");
+    return true;
+}
+
+bool sgm_match_confidence_device(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, float* d_disp, uint16_t* d_conf)
+{
+    if (!conf_ready(s, d_left, d_right, d_disp, d_conf)) return false;
+    return run_pipeline_conf(s, d_left, d_right, d_disp, d_conf);
 }
 
 /* The host-pointer match without the final wait: stages the images (not at all when the caller's buffers are pinned,
  * sgm_host_alloc), queues H2D, the pipeline and D2H on the instance's stream and returns.  With a few instances
  * round-robined by the caller, the copies of one overlap the kernels of the others (separate DMA engines). */
-bool sgm_match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left)
+/* conf != NULL (sgm_match_confidence_async): the confidence map comes back behind the disparity map, through s->d_conf */
+static bool match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left, uint16_t* conf)
 {
     if (!s || !s->initialized) return false;                     /* .c:70 */
     if (!img_left || !img_right) return false;                   /* .c:73 */
@@ -1306,6 +1380,8 @@ bool sgm_match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* im
     if (s->tile_end != 0) FAIL("the instance is in row-tile mode (sgm_set_rows): use the sgm_tile_* sequence");
     if (!sgm_match_wait(s)) return false;                        /* the staging buffers are free again */
     const size_t px = (size_t)s->g.B * s->g.W * s->g.H;           /* batch > 1: B consecutive frames */
+    const bool conf_pinned = conf && sgmd_host_is_pinned(s->device, conf, px * sizeof(uint16_t)) != 0;
+    if (conf && ensure_conf(s, !conf_pinned) != 0) FAIL("device allocation failed for the confidence map");
     const void *src_l = img_left, *src_r = img_right;
     /* the left image is on the bus while the right one is staged */
     if (!sgmd_host_is_pinned(s->device, img_left, px)) { memcpy(s->h_left, img_left, px); src_l = s->h_left; }
@@ -1314,7 +1390,7 @@ bool sgm_match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* im
     const bool out_pinned = sgmd_host_is_pinned(s->device, disp_left, px * sizeof(float)) != 0;
     const size_t bytes = px * sizeof(float);
     ok = ok && sgmd_h2d_async(s->device, s->stream, s->d_right, src_r, px) == 0 &&
-         run_pipeline(s, s->d_left, s->d_right, s->d_disp);
+         (conf ? run_pipeline_conf(s, s->d_left, s->d_right, s->d_disp, s->d_conf) : run_pipeline(s, s->d_left, s->d_right, s->d_disp));
     int chunks = 1;
     if (ok && !out_pinned && bytes >= RESULT_CHUNK_MIN) {        /* a single frame: 0.92 -> 0.88 ms per blocking call; batches of 8 through
                                                                    four pipelined instances on pageable buffers: 3500 -> 3640 fps */
@@ -1335,20 +1411,39 @@ bool sgm_match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* im
         }
     } else if (ok)
         ok = queue_result_copy(s, out_pinned ? (void*)disp_left : s->h_disp, s->d_disp, bytes);
+    if (ok && conf)                       /* the confidence behind the map: written by the cost sum, long done by then */
+        ok = queue_result_copy(s, conf_pinned ? (void*)conf : s->h_conf, s->d_conf, px * sizeof(uint16_t));
     if (!ok) {
         sync_streams(s);                  /* queued copies may still read the caller's / staging buffers */
         return false;
     }
     s->async_pending = true;
     s->async_out = out_pinned ? NULL : disp_left;
+    s->async_conf_out = (conf && !conf_pinned) ? conf : NULL;
     s->async_bytes = bytes;
     s->async_chunks = chunks;
     return true;
 }
 
+bool sgm_match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left)
+{
+    return match_async(s, img_left, img_right, disp_left, NULL);
+}
+
 bool sgm_match(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left)
 {
     return sgm_match_async(s, img_left, img_right, disp_left) && sgm_match_wait(s);
+}
+
+bool sgm_match_confidence_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left, uint16_t* conf)
+{
+    if (!conf_ready(s, img_left, img_right, disp_left, conf)) return false;
+    return match_async(s, img_left, img_right, disp_left, conf);
+}
+
+bool sgm_match_confidence(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left, uint16_t* conf)
+{
+    return sgm_match_confidence_async(s, img_left, img_right, disp_left, conf) && sgm_match_wait(s);
 }
 
 void* sgm_host_alloc(sgm_instance* s, size_t bytes)
@@ -1616,6 +1711,12 @@ bool sgm_compute(const uint8_t* img_left, const uint8_t* img_right, uint16_t wid
                  float* disp_left)
 {
     return SGM_Reset(width, height, option) && SGM_Match(img_left, img_right, disp_left);
+}
+
+bool SGM_MatchConfidence(const uint8_t* img_left, const uint8_t* img_right, float* disp_left, uint16_t* conf)
+{
+    if (!g_default) return false;
+    return sgm_match_confidence(g_default, img_left, img_right, disp_left, conf);
 }
 
 bool SGM_MatchDevice(const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left)

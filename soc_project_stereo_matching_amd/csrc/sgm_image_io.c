@@ -211,3 +211,20 @@ int sgm_write_pgm(const char* path, const uint8_t* data, int w, int h)
     fwrite(data, 1, (size_t)w * h, f);
     return fclose(f) == 0 ? 0 : -1;
 }
+
+int sgm_write_pgm16(const char* path, const uint16_t* data, int w, int h)
+{
+    FILE* f = fopen(path, "wb");
+    if (!f) return -1;
+    fprintf(f, "P5\n%d %d\n65535\n", w, h);
+    const size_t n = (size_t)w * h;
+    uint8_t* be = (uint8_t*)malloc(2 * n);
+    int rc = be ? 0 : -1;
+    if (be) {
+        for (size_t i = 0; i < n; ++i) { be[2 * i] = (uint8_t)(data[i] >> 8); be[2 * i + 1] = (uint8_t)data[i]; }
+        if (fwrite(be, 1, 2 * n, f) != 2 * n) rc = -1;
+        free(be);
+    }
+    if (fclose(f) != 0) rc = -1;
+    return rc;
+}

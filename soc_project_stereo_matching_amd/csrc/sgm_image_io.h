@@ -12,4 +12,6 @@ uint8_t* sgm_load_gray(const char* path, int* w, int* h);
 /* 8-bit grey writers; return 0 on success. */
 int sgm_write_png_gray(const char* path, const uint8_t* data, int w, int h);
 int sgm_write_pgm(const char* path, const uint8_t* data, int w, int h);
+/* 16-bit binary PGM (maxval 65535, most significant byte first); 0 on success */
+int sgm_write_pgm16(const char* path, const uint16_t* data, int w, int h);
 #endif

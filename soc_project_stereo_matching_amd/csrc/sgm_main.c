@@ -11,6 +11,7 @@
  *            aggregation (the reference stores num_paths and ignores it), census windows other than 5x5, the right image
  *            as reference view; the defaults are the reference's behaviour
  *            [--fill-holes]   extension: occlusion-aware hole filling of the invalid disparities (SGM_SetFillHoles)
+ *            [--confidence OUT.pgm]   extension: the matching confidence (SGM_MatchConfidence) as a 16-bit PGM
  *   sgm_main --convert IN OUT.png        (image I/O only, no GPU: used by the CPU tests)
  */
 #define _POSIX_C_SOURCE 200809L
@@ -64,6 +65,7 @@ int main(int argc, char** argv)
     opt.p1 = 10;
     opt.p2_init = 150;
     const char* raw_path = NULL;
+    const char* conf_path = NULL;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0;
     for (int i = 4; i < argc; ++i) {
         const char* a = argv[i];
@@ -79,6 +81,7 @@ int main(int argc, char** argv)
         else if (v && !strcmp(a, "--unique-ratio")) { opt.uniqueness_ratio = (float)atof(v); ++i; }
         else if (v && !strcmp(a, "--speckle-area")) { opt.min_speckle_area = (uint16_t)atoi(v); ++i; }
         else if (v && !strcmp(a, "--raw")) { raw_path = v; ++i; }
+        else if (v && !strcmp(a, "--confidence")) { conf_path = v; ++i; }
         else if (v && !strcmp(a, "--repeat")) { repeat = atoi(v); ++i; }
         else if (v && !strcmp(a, "--device")) { device = atoi(v); ++i; }
         else if (v && !strcmp(a, "--paths")) { opt.num_paths = (uint8_t)atoi(v); SGM_SetHonorNumPaths(1); ++i; }
@@ -105,11 +108,12 @@ int main(int argc, char** argv)
     if (fill_holes && !SGM_SetFillHoles(1)) { printf("hole filling unavailable\n"); return -2; }
     if (!SGM_Initialize((uint16_t)w1, (uint16_t)h1, &opt)) { printf("SGM initialization failed\n"); return -2; }
     float* disp = (float*)malloc(sizeof(float) * (size_t)w1 * h1);
+    uint16_t* conf = conf_path ? (uint16_t*)malloc(sizeof(uint16_t) * (size_t)w1 * h1) : NULL;
     double best = 1e30;
     for (int r = 0; r < repeat; ++r) {
         const double t0 = now_ms();
         if (r > 0 && !SGM_Reset((uint16_t)w1, (uint16_t)h1, &opt)) { printf("SGM reset failed\n"); return -2; }
-        if (!SGM_Match(left, right, disp)) { printf("SGM matching failed\n"); return -2; }
+        if (!(conf ? SGM_MatchConfidence(left, right, disp, conf) : SGM_Match(left, right, disp))) { printf("SGM matching failed\n"); return -2; }
         const double t = now_ms() - t0;
         if (t < best) best = t;
     }
@@ -136,12 +140,13 @@ int main(int argc, char** argv)
     }
     printf("valid %zu of %zu, disparity range [%g, %g]\n", valid, px, lo, hi);
     int rc = ends_with(argv[3], ".pgm") ? sgm_write_pgm(argv[3], u8, w1, h1) : sgm_write_png_gray(argv[3], u8, w1, h1);
+    if (conf_path && sgm_write_pgm16(conf_path, conf, w1, h1) != 0) rc = -1;
     if (raw_path) {
         FILE* f = fopen(raw_path, "wb");
         if (!f || fwrite(disp, sizeof(float), px, f) != px) rc = -1;
         if (f) fclose(f);
     }
     SGM_Shutdown();
-    free(u8); free(disp); free(left); free(right);
+    free(u8); free(disp); free(conf); free(left); free(right);
     return rc ? 1 : 0;
 }

@@ -6,13 +6,23 @@
 // inverse == 0).  16 lanes per pixel, DPL disparities per lane; the kernel is HBM-bound (it streams the 8
 // planes once), so the WTA arithmetic rides along for free.
 //   key = S << 16 | d: the row-wide minimum key is the first minimum the reference's strict '>' finds.
-template <int DPL>
+// CONF (extension, sgm_match_confidence): the lane that finishes a pixel also stores its matching confidence to conf
+// (u16 [B][H][W]); the CONF = false instantiations never touch conf.
+
+// matching confidence from the best and runner-up cost (include/sgm_mi355x.h): 0 for a tie or no candidate; one u32 divide
+static __device__ __forceinline__ uint16_t conf_value(unsigned m1, unsigned m2)
+{
+    return m2 == 0u ? (uint16_t)0 : (uint16_t)(((m2 - m1) * 65535u) / m2);
+}
+
+template <int DPL, bool CONF = false>
 __global__ __launch_bounds__(256) void sgm_sum_wta_k(const uint8_t* __restrict__ planes, size_t plane_bytes, int ndirs,
                                                      const uint8_t* __restrict__ extras,
                                                      const sgmd_row_extra* __restrict__ row_extras,
                                                      const int* __restrict__ row_extra_count, int row_cap, int accumulate,
                                                      uint16_t* __restrict__ S, float* __restrict__ disp_l, int W, int H, int D,
-                                                     int Dp, int dmin, int check_unique, float one_minus_ratio, int row0)
+                                                     int Dp, int dmin, int check_unique, float one_minus_ratio, int row0,
+                                                     uint16_t* __restrict__ conf)
 {
     const int sub = threadIdx.x & 15;
     const int xr = blockIdx.x * 16 + (threadIdx.x >> 4);
@@ -87,6 +97,7 @@ __global__ __launch_bounds__(256) void sgm_sum_wta_k(const uint8_t* __restrict__
         st.c2 = nb >> 16;
         st.pv = 0; st.want_next = false;
         disp_l[(size_t)row * W + x] = wta_finish(st, D, dmin, check_unique, one_minus_ratio);
+        if constexpr (CONF) conf[(size_t)blockIdx.z * W * H + (size_t)row * W + x] = conf_value(st.m1, st.m2);
     }
 }
 
@@ -124,8 +135,9 @@ static __device__ __forceinline__ void sumlr_prefetch(CellVec<DPL> (&pre)[2][8],
 // write the next iteration's columns while another still reads this one's oldest): for Dp = 256 that is what lets the ring
 // (288 x 258 u16 = 145 KB either way) serve 32 columns = 8 waves per iteration instead of 16 columns = 4 waves -- the kernel
 // is alone on its CU there, so its waves are all the latency hiding it has.
+// CONF: the finishing lane of the reference view (the right one if conf_right) also stores the pixel's confidence.
 #define SUMLR_MAX_EXTRA 8
-template <int DPL, bool SLOW, int THREADS, bool TIGHT = false>
+template <int DPL, bool SLOW, int THREADS, bool TIGHT = false, bool CONF = false>
 __global__ __launch_bounds__(THREADS) void sgm_sum_wta_lr_k(const uint8_t* __restrict__ planes, size_t plane_bytes, int ndirs,
                                                         const uint8_t* __restrict__ extras,
                                                         const sgmd_row_extra* __restrict__ row_extras,
@@ -133,7 +145,8 @@ __global__ __launch_bounds__(THREADS) void sgm_sum_wta_lr_k(const uint8_t* __res
                                                         int accumulate, int store_S, int do_right,
                                                         uint16_t* __restrict__ S, float* __restrict__ disp_l,
                                                         float* __restrict__ disp_r, int W, int H, int D, int dmin,
-                                                        int check_unique, float one_minus_ratio, int row0, int seg_len)
+                                                        int check_unique, float one_minus_ratio, int row0, int seg_len,
+                                                        uint16_t* __restrict__ conf, int conf_right)
 {
     constexpr int Dp = 16 * DPL;
     constexpr int LD = Dp + 2;
@@ -158,6 +171,7 @@ __global__ __launch_bounds__(THREADS) void sgm_sum_wta_lr_k(const uint8_t* __res
     S += (size_t)blockIdx.y * W * H * Dp;
     disp_l += (size_t)blockIdx.y * W * H;
     disp_r += (size_t)blockIdx.y * W * H;
+    if constexpr (CONF) conf += (size_t)blockIdx.y * W * H;
     const unsigned row_cells = (unsigned)row * (unsigned)W * Dp;      // 32-bit cell offsets: the host guarantees W*H*Dp < 2^32
     const int n_extra = (ndirs > 4) ? min(row_extra_count[row], SUMLR_MAX_EXTRA) : 0;    // host: row_cap <= SUMLR_MAX_EXTRA
     for (int t = threadIdx.x; t < n_extra * (Dp / 4); t += THREADS) {
@@ -259,6 +273,9 @@ __global__ __launch_bounds__(THREADS) void sgm_sum_wta_lr_k(const uint8_t* __res
             st.pv = 0; st.want_next = false;
             float* const out = is_r ? disp_r + xr : disp_l + x;
             out[(size_t)row * W] = wta_finish(st, D, dmin, check_unique, one_minus_ratio);
+            if constexpr (CONF) {
+                if (is_r == (conf_right != 0)) conf[(size_t)row * W + (is_r ? xr : x)] = conf_value(st.m1, st.m2);
+            }
         }
         if (TIGHT && do_right) __syncthreads();                          // every diagonal of this iteration has been read
     };
@@ -411,9 +428,10 @@ __global__ __launch_bounds__(THREADS) void sgm_sum_wta_lr_k(const uint8_t* __res
 #define WTA_DC 64
 #define WTA_LD (WTA_DC + 2)       // u16 row stride (33 dwords: odd, conflict-free lane stride)
 
+template <bool CONF = false>
 __global__ __launch_bounds__(WTA_T) void sgm_wta_right_k(const uint16_t* __restrict__ S, float* __restrict__ disp_r, int W,
                                                          int H, int D, int Dp, int dmin, int check_unique,
-                                                         float one_minus_ratio, int row0)
+                                                         float one_minus_ratio, int row0, uint16_t* __restrict__ conf)
 {
     __shared__ unsigned short tr[(WTA_T + WTA_DC) * WTA_LD];
     const int row = row0 + blockIdx.y;
@@ -458,7 +476,10 @@ __global__ __launch_bounds__(WTA_T) void sgm_wta_right_k(const uint16_t* __restr
             for (int k = 0; k < 8; ++k) wta_feed(sr, v[k], dc + e0 + k);
         }
     }
-    if (x < W) disp_r[(size_t)row * W + x] = wta_finish(sr, D, dmin, check_unique, one_minus_ratio);
+    if (x < W) {
+        disp_r[(size_t)row * W + x] = wta_finish(sr, D, dmin, check_unique, one_minus_ratio);
+        if constexpr (CONF) conf[frame_px + (size_t)row * W + x] = conf_value(sr.m1, sr.m2);
+    }
 }
 
 // ============================================================================================
@@ -515,40 +536,49 @@ template <int DPL, int THREADS, bool TIGHT = false>
 static void launch_sum_wta_lr(dim3 grid, hipStream_t st, const void* planes, size_t plane_bytes, int ndirs, const void* extras,
                               const void* row_extras, const void* row_extra_count, int row_cap, int accumulate, int store_S,
                               int do_right, void* S, void* disp_l, void* disp_r, const sgmd_geom* g, int check_unique,
-                              float one_minus_ratio, int seg_len)
+                              float one_minus_ratio, int seg_len, void* conf, int conf_right)
 {
-#define SUMLR_CALL(SLOW)                                                                                              \
-    hipLaunchKernelGGL((sgm_sum_wta_lr_k<DPL, SLOW, THREADS, TIGHT>), grid, dim3(THREADS), 0, st, (const uint8_t*)planes, plane_bytes, ndirs, \
-                       (const uint8_t*)extras, (const sgmd_row_extra*)row_extras, (const int*)row_extra_count, row_cap,  \
+#define SUMLR_CALL(SLOW, CONF)                                                                                        \
+    hipLaunchKernelGGL((sgm_sum_wta_lr_k<DPL, SLOW, THREADS, TIGHT, CONF>), grid, dim3(THREADS), 0, st, (const uint8_t*)planes, plane_bytes, \
+                       ndirs, (const uint8_t*)extras, (const sgmd_row_extra*)row_extras, (const int*)row_extra_count, row_cap, \
                        accumulate, store_S, do_right, (uint16_t*)S, (float*)disp_l, (float*)disp_r, g->W, g->H, g->D,    \
-                       g->dmin, check_unique, one_minus_ratio, g->row_begin, seg_len)
-    if (accumulate || store_S) SUMLR_CALL(true);
-    else SUMLR_CALL(false);
+                       g->dmin, check_unique, one_minus_ratio, g->row_begin, seg_len, (uint16_t*)conf, conf_right)
+    if (conf) {
+        if (accumulate || store_S) SUMLR_CALL(true, true);
+        else SUMLR_CALL(false, true);
+    } else {
+        if (accumulate || store_S) SUMLR_CALL(true, false);
+        else SUMLR_CALL(false, false);
+    }
 #undef SUMLR_CALL
 }
 
 template <int DPL>
 static void launch_sum_wta(dim3 grid, hipStream_t st, const void* planes, size_t plane_bytes, int ndirs, const void* extras,
                            const void* row_extras, const void* row_extra_count, int row_cap, int accumulate, void* S,
-                           void* disp_l, const sgmd_geom* g, int check_unique, float one_minus_ratio)
+                           void* disp_l, const sgmd_geom* g, int check_unique, float one_minus_ratio, void* conf)
 {
-    hipLaunchKernelGGL((sgm_sum_wta_k<DPL>), grid, dim3(256), 0, st, (const uint8_t*)planes, plane_bytes, ndirs,
-                       (const uint8_t*)extras, (const sgmd_row_extra*)row_extras, (const int*)row_extra_count, row_cap,
-                       accumulate, (uint16_t*)S, (float*)disp_l, g->W, g->H, g->D, g->Dp, g->dmin, check_unique,
-                       one_minus_ratio, g->row_begin);
+#define SUM_CALL(CONF)                                                                                                \
+    hipLaunchKernelGGL((sgm_sum_wta_k<DPL, CONF>), grid, dim3(256), 0, st, (const uint8_t*)planes, plane_bytes, ndirs,  \
+                       (const uint8_t*)extras, (const sgmd_row_extra*)row_extras, (const int*)row_extra_count, row_cap, \
+                       accumulate, (uint16_t*)S, (float*)disp_l, g->W, g->H, g->D, g->Dp, g->dmin, check_unique,      \
+                       one_minus_ratio, g->row_begin, (uint16_t*)conf)
+    if (conf) SUM_CALL(true);
+    else SUM_CALL(false);
+#undef SUM_CALL
 }
 
 
 extern "C" {
 
-int sgmd_sum_wta(int ord, void* stream, const sgmd_geom* g, int ndirs, const void* planes, size_t plane_bytes,
-                 const void* extras, const void* row_extras, const void* row_extra_count, int row_cap, int accumulate,
-                 void* S, int check_unique, float one_minus_ratio, void* disp_l)
+int sgmd_sum_wta_conf(int ord, void* stream, const sgmd_geom* g, int ndirs, const void* planes, size_t plane_bytes,
+                      const void* extras, const void* row_extras, const void* row_extra_count, int row_cap, int accumulate,
+                      void* S, int check_unique, float one_minus_ratio, void* disp_l, void* conf)
 {
     HIP_TRY(hipSetDevice(ord));
     const dim3 grid((g->W + 15) / 16, g->row_end - g->row_begin, g->B);
     hipStream_t st = (hipStream_t)stream;
-#define SUM_ARGS grid, st, planes, plane_bytes, ndirs, extras, row_extras, row_extra_count, row_cap, accumulate, S, disp_l, g, check_unique, one_minus_ratio
+#define SUM_ARGS grid, st, planes, plane_bytes, ndirs, extras, row_extras, row_extra_count, row_cap, accumulate, S, disp_l, g, check_unique, one_minus_ratio, conf
     switch (g->Dp / 16) {                                // 16 lanes per pixel here, whatever the aggregation used
     case 2:  launch_sum_wta<2>(SUM_ARGS); break;
     case 4:  launch_sum_wta<4>(SUM_ARGS); break;
@@ -565,16 +595,29 @@ int sgmd_sum_wta(int ord, void* stream, const sgmd_geom* g, int ndirs, const voi
     return 0;
 }
 
+int sgmd_sum_wta(int ord, void* stream, const sgmd_geom* g, int ndirs, const void* planes, size_t plane_bytes,
+                 const void* extras, const void* row_extras, const void* row_extra_count, int row_cap, int accumulate,
+                 void* S, int check_unique, float one_minus_ratio, void* disp_l)
+{
+    return sgmd_sum_wta_conf(ord, stream, g, ndirs, planes, plane_bytes, extras, row_extras, row_extra_count, row_cap, accumulate, S,
+                             check_unique, one_minus_ratio, disp_l, nullptr);
+}
+
 int sgmd_sum_wta_lr_supported(const sgmd_geom* g, int row_cap)
 {
     return (g->Dp == 32 || g->Dp == 64 || g->Dp == 128 || g->Dp == 192 || g->Dp == 256) && row_cap <= SUMLR_MAX_EXTRA;
 }
 
-int sgmd_sum_wta_lr(int ord, void* stream, const sgmd_geom* g, int ndirs, const void* planes, size_t plane_bytes,
-                    const void* extras, const void* row_extras, const void* row_extra_count, int row_cap, int accumulate,
-                    int store_S, int do_right, void* S, int check_unique, float one_minus_ratio, void* disp_l, void* disp_r)
+int sgmd_sum_wta_lr_conf(int ord, void* stream, const sgmd_geom* g, int ndirs, const void* planes, size_t plane_bytes,
+                         const void* extras, const void* row_extras, const void* row_extra_count, int row_cap, int accumulate,
+                         int store_S, int do_right, void* S, int check_unique, float one_minus_ratio, void* disp_l, void* disp_r,
+                         void* conf, int conf_right)
 {
     HIP_TRY(hipSetDevice(ord));
+    if (conf && conf_right && !do_right) {
+        fprintf(stderr, "sgm_mi355x: the right view's confidence needs the right-view WTA (do_right)\n");
+        return -1;
+    }
     // segments per row: enough workgroups for ~4 per CU when a launch has few rows (one frame), but never segments
     // shorter than 2 Dp columns (each re-sums dmin + D - 1 columns of its right neighbour), and one segment whenever S
     // is read or written (the overlap would be accumulated twice)
@@ -604,7 +647,7 @@ int sgmd_sum_wta_lr(int ord, void* stream, const sgmd_geom* g, int ndirs, const 
     const int seg_len = (((g->W + segs - 1) / segs) + 15) / 16 * 16;
     const dim3 grid(g->row_end - g->row_begin, g->B, (g->W + seg_len - 1) / seg_len);
     hipStream_t st = (hipStream_t)stream;
-#define SUMLR_ARGS grid, st, planes, plane_bytes, ndirs, extras, row_extras, row_extra_count, row_cap, accumulate, store_S, do_right, S, disp_l, disp_r, g, check_unique, one_minus_ratio, seg_len
+#define SUMLR_ARGS grid, st, planes, plane_bytes, ndirs, extras, row_extras, row_extra_count, row_cap, accumulate, store_S, do_right, S, disp_l, disp_r, g, check_unique, one_minus_ratio, seg_len, conf, conf_right
     switch (g->Dp / 16) {
     case 2: launch_sum_wta_lr<2, 256>(SUMLR_ARGS); break;
     case 4: launch_sum_wta_lr<4, 256>(SUMLR_ARGS); break;
@@ -627,15 +670,33 @@ int sgmd_sum_wta_lr(int ord, void* stream, const sgmd_geom* g, int ndirs, const 
     return 0;
 }
 
-int sgmd_wta_right(int ord, void* stream, const sgmd_geom* g, const void* S, int check_unique, float one_minus_ratio,
-                   void* disp_r)
+int sgmd_sum_wta_lr(int ord, void* stream, const sgmd_geom* g, int ndirs, const void* planes, size_t plane_bytes,
+                    const void* extras, const void* row_extras, const void* row_extra_count, int row_cap, int accumulate,
+                    int store_S, int do_right, void* S, int check_unique, float one_minus_ratio, void* disp_l, void* disp_r)
+{
+    return sgmd_sum_wta_lr_conf(ord, stream, g, ndirs, planes, plane_bytes, extras, row_extras, row_extra_count, row_cap, accumulate,
+                                store_S, do_right, S, check_unique, one_minus_ratio, disp_l, disp_r, nullptr, 0);
+}
+
+int sgmd_wta_right_conf(int ord, void* stream, const sgmd_geom* g, const void* S, int check_unique, float one_minus_ratio,
+                        void* disp_r, void* conf)
 {
     HIP_TRY(hipSetDevice(ord));
     dim3 grid((g->W + WTA_T - 1) / WTA_T, g->row_end - g->row_begin, g->B);
-    hipLaunchKernelGGL(sgm_wta_right_k, grid, dim3(WTA_T), 0, (hipStream_t)stream, (const uint16_t*)S, (float*)disp_r,
-                       g->W, g->H, g->D, g->Dp, g->dmin, check_unique, one_minus_ratio, g->row_begin);
+    if (conf)
+        hipLaunchKernelGGL(sgm_wta_right_k<true>, grid, dim3(WTA_T), 0, (hipStream_t)stream, (const uint16_t*)S, (float*)disp_r,
+                           g->W, g->H, g->D, g->Dp, g->dmin, check_unique, one_minus_ratio, g->row_begin, (uint16_t*)conf);
+    else
+        hipLaunchKernelGGL(sgm_wta_right_k<false>, grid, dim3(WTA_T), 0, (hipStream_t)stream, (const uint16_t*)S, (float*)disp_r,
+                           g->W, g->H, g->D, g->Dp, g->dmin, check_unique, one_minus_ratio, g->row_begin, (uint16_t*)nullptr);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int sgmd_wta_right(int ord, void* stream, const sgmd_geom* g, const void* S, int check_unique, float one_minus_ratio,
+                   void* disp_r)
+{
+    return sgmd_wta_right_conf(ord, stream, g, S, check_unique, one_minus_ratio, disp_r, nullptr);
 }
 
 int sgmd_lrcheck_right(int ord, void* stream, const sgmd_geom* g, const void* disp_r, const void* disp_l, float thres,

@@ -126,6 +126,12 @@ def _load() -> C.CDLL:
         L.SGM_SetFillHoles.restype = C.c_bool
         L.sgm_fill_holes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.sgm_fill_holes.restype = C.c_bool
+    if hasattr(L, "sgm_match_confidence"):    # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        for f in (L.sgm_match_confidence, L.sgm_match_confidence_async, L.sgm_match_confidence_device):
+            f.argtypes = [C.c_void_p] * 5
+            f.restype = C.c_bool
+        L.SGM_MatchConfidence.argtypes = [C.c_void_p] * 4
+        L.SGM_MatchConfidence.restype = C.c_bool
     L.sgm_set_batch.argtypes = [C.c_void_p, C.c_int]
     L.sgm_set_batch.restype = C.c_bool
     L.sgm_select_frame.argtypes = [C.c_void_p, C.c_int]
@@ -304,6 +310,15 @@ class SGM(_StageReader):
         out = np.empty(left.shape, np.float32)
         ok = self.lib.SGM_Match(left.ctypes.data, right.ctypes.data, out.ctypes.data)
         return out if ok else None
+
+    def match_confidence(self, left, right):
+        """SGM_MatchConfidence: (disparity float32, confidence uint16) of the default instance, or None where the C call returns
+        false.  The confidence contract is in include/sgm_mi355x.h."""
+        left, right = _u8(left), _u8(right)
+        out = np.empty(left.shape, np.float32)
+        conf = np.empty(left.shape, np.uint16)
+        ok = self.lib.SGM_MatchConfidence(left.ctypes.data, right.ctypes.data, out.ctypes.data, conf.ctypes.data)
+        return (out, conf) if ok else None
 
     def compute(self, left, right, option, out=None):
         """sgm_compute: SGM_Reset + SGM_Match in one call (north_star's entry point).  None where it returns false.  `out`: a
@@ -490,6 +505,36 @@ class SGMInstance(_StageReader):
             if tuple(a.shape) != want:
                 raise ValueError(f"match_async: {name} has shape {tuple(a.shape)}, the instance expects {want}")
         return bool(self.lib.sgm_match_async(self.handle, left.ctypes.data, right.ctypes.data, out.ctypes.data))
+
+    def match_confidence(self, left, right):
+        """sgm_match_confidence: (disparity float32, confidence uint16), each of the instance's shape, or None where the C call
+        returns false.  The confidence contract is in include/sgm_mi355x.h."""
+        if self.shape is None:
+            return None
+        left, right = _u8(left), _u8(right)
+        want = self._frame_shape()
+        if tuple(left.shape) != want or tuple(right.shape) != want:
+            raise ValueError(f"expected images of shape {want}, got {left.shape}")
+        out = np.empty(want, np.float32)
+        conf = np.empty(want, np.uint16)
+        ok = self.lib.sgm_match_confidence(self.handle, left.ctypes.data, right.ctypes.data, out.ctypes.data, conf.ctypes.data)
+        return (out, conf) if ok else None
+
+    def match_confidence_async(self, left, right, out, conf) -> bool:
+        """sgm_match_confidence_async: as match_async, plus `conf` (uint16, the instance's shape) which stays borrowed until
+        match_wait() as well."""
+        if self.shape is None:
+            return False
+        want = self._frame_shape()
+        for name, a, dt in (("left", left, np.uint8), ("right", right, np.uint8), ("out", out, np.float32), ("conf", conf, np.uint16)):
+            if not a.flags["C_CONTIGUOUS"] or a.dtype != dt or tuple(a.shape) != want:
+                raise ValueError(f"match_confidence_async: {name} must be a C-contiguous {np.dtype(dt).name} array of shape {want}")
+        return bool(self.lib.sgm_match_confidence_async(self.handle, left.ctypes.data, right.ctypes.data, out.ctypes.data,
+                                                        conf.ctypes.data))
+
+    def match_confidence_device(self, d_left: int, d_right: int, d_out: int, d_conf: int) -> bool:
+        """sgm_match_confidence_device: device pointers (d_conf: uint16 [batch][H][W]); asynchronous on the instance stream."""
+        return bool(self.lib.sgm_match_confidence_device(self.handle, d_left, d_right, d_out, d_conf))
 
     def _frame_shape(self):
         h, w = self.shape[:2]
