@@ -136,6 +136,46 @@ bool SGM_SetFillHoles(int enable);
  * mode (sgm_set_rows), and a build without the confidence kernels.  Timing: the store counts toward "sum" / "wta". */
 bool SGM_MatchConfidence(const uint8_t* img_left, const uint8_t* img_right, float* disp_left, uint16_t* conf);
 
+/* Refinement (extension, "parity unpinned by the reference": SemiGlobalMatching.h:24-40 has no such option; defined here and
+ * restated by tests/refine_ref.py).  A confidence-weighted, edge-aware smoother after the median: the Fast Global Smoother of
+ * Min et al. (2014), the weighted-least-squares filter behind OpenCV's DisparityWLSFilter, solved with separable 1-D tridiagonal
+ * systems.  Low-confidence and invalid pixels take their value from confident neighbours on the same surface of the grey image;
+ * depth edges stay where the image edges are.  Off by default (every launch, buffer and result is then the reference's); takes
+ * effect at the next SGM_Initialize / sgm_initialize / SGM_Reset / sgm_reset, which return false with it on in row-tile mode
+ * (sgm_set_rows) or together with hole filling (SGM_SetFillHoles: the refinement fills by itself, and a filled pixel would carry
+ * the confidence of a disparity the LR check rejected).  Returns false and changes nothing for enable or keep_invalid other than
+ * 0 / 1 and, with enable = 1, for a lambda or sigma that is not finite and > 0 or iterations outside 1..SGM_REFINE_MAX_ITERS
+ * (with enable = 0 the other arguments are not looked at), or in a build without the kernels.
+ * Per frame: D = the map after the median (f32 [H][W], +INF invalid); K = the reference view's confidence exactly as
+ * SGM_MatchConfidence defines it (u16); G = the reference view's grey image, the one the census saw (the left image, the right
+ * one with SGM_SetReferenceView(1)).  All arithmetic float32, every operation rounded on its own (no contraction, correctly
+ * rounded divide, subnormals kept):
+ *   1. c = isfinite(D) ? (float)K / 65535.0f : 0;  U = isfinite(D) ? c * D : 0;  V = c.
+ *   2. For iteration t = 0..T-1: lam_t = lambda * 1.5 * 4^(T-1-t) / (4^T - 1) and L_t[k] = (float)(lam_t * exp(-k / sigma)),
+ *      k = 0..255, in double, rounded once (sgm_refine_table).
+ *   3. A line of n samples with guide values g: e_i = L_t[|g[i+1] - g[i]|]; a_i = e_{i-1} (0 at i = 0), c_i = e_i (0 at i = n-1),
+ *      b_i = (1 + a_i) + c_i.  Thomas algorithm in this order: m_0 = b_0, m_i = b_i - a_i * q_{i-1}; q_i = c_i / m_i; for U and for
+ *      V: r'_0 = r_0 / m_0, r'_i = (r_i + a_i * r'_{i-1}) / m_i; x_{n-1} = r'_{n-1}, x_i = r'_i + q_i * x_{i+1}  (m_i >= 1).
+ *   4. Iteration t solves every row (horizontal pass), then every column (vertical pass), each on U and V.  Lines end at the
+ *      frame edges; the frames of a batch are independent.
+ *   5. out = V > 0 ? U / V : +INF; with keep_invalid the pixels that were +INF in D stay +INF, without it the map is dense
+ *      wherever V > 0 (V is 0 where a small sigma makes the weights underflow and cuts a line into pieces without a confident pixel).
+ * The result is a weighted average of the valid input disparities of the frame: it never leaves their [min, max] range.
+ * Every match of the instance then computes the confidence (into the caller's map for sgm_match_confidence*, else into one of its
+ * own; the fused last sweep is not used), and every entry point returns the refined map: SGM_Match, sgm_match*, sgm_compute,
+ * the device and pipelined forms, sgm_match_planes* (whose depth is computed from it).  The passes run behind the median on the
+ * post-pass stream (sgm_set_overlap_post, sgm_set_stage_cus and batches carry over) and read a private copy of G.
+ * Timing: the refinement counts toward "median".  Defaults of the drivers (the best of a sweep on the four image pairs the
+ * reference ships, NOTES.md): SGM_REFINE_DEFAULT_*. */
+#define SGM_REFINE_MAX_ITERS 8
+#define SGM_REFINE_DEFAULT_LAMBDA 16.0f
+#define SGM_REFINE_DEFAULT_SIGMA 1.5f
+#define SGM_REFINE_DEFAULT_ITERS 1
+bool SGM_SetRefine(int enable, float lambda, float sigma, int iterations, int keep_invalid);
+/* L_t of step 2 for (lambda, sigma, T = iterations, t) into out[256]; host only, no device needed.  false for arguments outside
+ * the ranges of SGM_SetRefine or t outside [0, T). */
+bool sgm_refine_table(float lambda, float sigma, int iterations, int t, float* out);
+
 /* Same as SGM_Match but all three pointers are DEVICE pointers (HBM-resident frames) on the
  * instance's device.  Asynchronous on the instance's stream; SGM_Synchronize waits. */
 bool SGM_MatchDevice(const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left);
@@ -160,6 +200,7 @@ void          sgm_set_honor_num_paths(sgm_instance* s, int honor);
 bool          sgm_set_census_window(sgm_instance* s, int width, int height);   /* see SGM_SetCensusWindow */
 void          sgm_set_reference_view(sgm_instance* s, int right);              /* see SGM_SetReferenceView */
 bool          sgm_set_fill_holes(sgm_instance* s, int enable);                 /* see SGM_SetFillHoles */
+bool          sgm_set_refine(sgm_instance* s, int enable, float lambda, float sigma, int iterations, int keep_invalid);  /* see SGM_SetRefine */
 bool          sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMOption* option);
 bool          sgm_reset(sgm_instance* s, uint16_t width, uint16_t height, const SGMOption* option);
 bool          sgm_match(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left);
@@ -272,6 +313,12 @@ bool   sgm_compare_depth(sgm_instance* s, const float* d_ground_truth, const flo
  * alone.  Asynchronous on sgm_stream(s), behind the last match.  Works whether or not filling is on for matches; the filled
  * map of a match (stage 9) is overwritten. */
 bool   sgm_fill_holes(sgm_instance* s, float* d_disp, const uint8_t* d_class);
+
+/* The refinement of SGM_SetRefine (steps 1-5) on any device map: d_disp, the instance's B frames of its shape, is refined in place
+ * with the parameters of the last sgm_set_refine(s, 1, ...) (false if there was none), from the u16 confidence d_conf and the u8
+ * grey image d_guide ([B][H][W] each).  Asynchronous on sgm_stream(s), behind the last match.  Works whether or not the refinement
+ * is on for matches. */
+bool   sgm_refine_disparity(sgm_instance* s, float* d_disp, const uint16_t* d_conf, const uint8_t* d_guide);
 
 /* ---- a test-platform frame end to end (the data formats either side of the path) ----
  * The server hands the board six byte planes per frame -- left B, G, R, right B, G, R, each h rows of w bytes

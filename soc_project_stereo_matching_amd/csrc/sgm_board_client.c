@@ -12,10 +12,11 @@
  * Depth follows the platform's own client simulator (client.py:40-45): NaN for invalid disparities,
  * float32(fx * baseline) / (disparity + doffs) otherwise.
  *
- *   sgm_board_client HOST PORT [--max-frames N] [--max-disparity D] [--min-disparity D] [--placeholder-gray] [--fill-holes]
+ *   sgm_board_client HOST PORT [--max-frames N] [--max-disparity D] [--min-disparity D] [--placeholder-gray] [--fill-holes] [--refine]
  * --placeholder-gray reproduces what the firmware does today (main.c:227-233: the "depth" it returns is the grey
  * value of the left image) and needs no GPU; the CPU tests use it to check the framing.
  * --fill-holes (extension) fills the invalid disparities before the depth conversion (sgm_set_fill_holes): dense maps.
+ * --refine (extension) refines the map before the depth conversion with the default parameters (sgm_set_refine): dense, edge-aware.
  */
 #define _POSIX_C_SOURCE 200809L
 #include "../../include/sgm_mi355x.h"
@@ -66,8 +67,8 @@ static float le_f32(const uint8_t* p)
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s HOST PORT [--max-frames N] [--max-disparity D] [--min-disparity D] [--placeholder-gray] [--fill-holes]\n", argv[0]); return 2; }
-    int max_frames = 1 << 30, placeholder = 0, fill_holes = 0;
+    if (argc < 3) { fprintf(stderr, "usage: %s HOST PORT [--max-frames N] [--max-disparity D] [--min-disparity D] [--placeholder-gray] [--fill-holes] [--refine]\n", argv[0]); return 2; }
+    int max_frames = 1 << 30, placeholder = 0, fill_holes = 0, refine = 0;
     SGMOption opt;
     memset(&opt, 0, sizeof opt);                           /* the reference driver's defaults, main.c:48-65 */
     opt.num_paths = 8; opt.min_disparity = 0; opt.max_disparity = 128;
@@ -79,6 +80,7 @@ int main(int argc, char** argv)
         const char* v = (i + 1 < argc) ? argv[i + 1] : NULL;
         if (!strcmp(argv[i], "--placeholder-gray")) placeholder = 1;
         else if (!strcmp(argv[i], "--fill-holes")) fill_holes = 1;      /* extension: dense depth maps (sgm_set_fill_holes) */
+        else if (!strcmp(argv[i], "--refine")) refine = 1;              /* extension: refined maps (sgm_set_refine) */
         else if (v && !strcmp(argv[i], "--max-frames")) { max_frames = atoi(v); ++i; }
         else if (v && !strcmp(argv[i], "--max-disparity")) { opt.max_disparity = (uint16_t)atoi(v); ++i; }
         else if (v && !strcmp(argv[i], "--min-disparity")) { opt.min_disparity = (uint16_t)atoi(v); ++i; }
@@ -103,6 +105,10 @@ int main(int argc, char** argv)
     sgm_instance* sgm = placeholder ? NULL : sgm_create(0);
     if (!placeholder && !sgm) { fprintf(stderr, "no usable GPU\n"); close(fd); return 1; }
     if (sgm && fill_holes && !sgm_set_fill_holes(sgm, 1)) { sgm_destroy(sgm); close(fd); return 1; }
+    if (sgm && refine &&
+        !sgm_set_refine(sgm, 1, SGM_REFINE_DEFAULT_LAMBDA, SGM_REFINE_DEFAULT_SIGMA, SGM_REFINE_DEFAULT_ITERS, 0)) {
+        sgm_destroy(sgm); close(fd); return 1;
+    }
     const double t_start = now_s();
 
     while (frames < max_frames) {

@@ -197,6 +197,16 @@ int sgmd_fill_classify(int ord, void* stream, const sgmd_geom* g, const void* re
                        int do_check, void* cls);
 int sgmd_fill_pass(int ord, void* stream, const sgmd_geom* g, int R, const void* in, void* out, const void* cls, int pass);
 
+/* Extension (parity unpinned by the reference), the refinement of include/sgm_mi355x.h (sgm_set_refine); sgm_refine.hip.
+ * One pass of one iteration over all B frames: vertical == 0 solves every row, else every column, of both right-hand sides U and V
+ * in place (f32 [B][H][W] each), with Q (f32 [B][H][W]) as scratch for q_i.  table: the iteration's L_t[256] (host memory, passed by
+ * value).  first (horizontal only): U and V are built from disp (f32, +INF invalid) and conf (u16) instead of read.  last (vertical
+ * only): out = V > 0 ? U / V : +INF, and with keep_invalid +INF where out itself was +INF before (out may be disp).
+ * sgm_host.c references it weakly (a host built without it has no refinement). */
+int sgmd_refine_pass(int ord, void* stream, const sgmd_geom* g, int vertical, const float* table, const void* guide,
+                     const void* disp, const void* conf, void* U, void* V, void* Q, int first, int last, int keep_invalid,
+                     void* out);
+
 /* in-place raster-order 3x3 median (the reference calls MedianFilter with in == out, .c:120).
  * scratch: sgmd_median_scratch_bytes(g) bytes for the pre-sorted neighbourhoods. */
 /* status: NULL, or an int in page-locked host memory (sgmd_alloc_pinned) that the chained kernel of tall frames sets to 1 when a

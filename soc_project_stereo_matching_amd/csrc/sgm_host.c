@@ -33,6 +33,13 @@ static const char* const k_stage_names[T_COUNT] = {"census", "cost", "aggregate"
 static const int k_dir_dx[8] = {1, -1, 0, 0, 1, -1, 1, -1};
 static const int k_dir_dy[8] = {0, 0, 1, -1, 1, -1, -1, 1};
 
+/* refinement parameters (sgm_set_refine) and the weight tables L_t of their iterations */
+typedef struct {
+    float lambda, sigma;
+    int iters, keep_invalid;
+    float tab[SGM_REFINE_MAX_ITERS][256];
+} refine_params;
+
 struct sgm_instance {
     int device;
     void* stream;                /* census and aggregation; and every other stage unless it has a stream of its own (sgm_set_stage_cus) */
@@ -66,6 +73,8 @@ struct sgm_instance {
     int reference_view;          /* 0 = left (reference), 1 = right (sgm_set_reference_view) */
     int fill_req;                /* hole filling asked for (sgm_set_fill_holes); takes effect at the next initialize */
     bool fill_on;                /* ... and in effect for this shape: the class map and the ping-pong map exist */
+    int refine_req;              /* refinement asked for (sgm_set_refine); takes effect at the next initialize */
+    bool refine_on;              /* ... and in effect for this shape: its maps exist */
     int reference_statics;       /* the default instance behind SGM_Initialize / SGM_Reset / SGM_Match: its census buffers behave like
                                     the reference's static arrays (SemiGlobalMatching.h:67-68) -- zero at first, never cleared, the words
                                     census_transform_5x5 does not write (.c:136,140-141) keep what an earlier frame of another shape left
@@ -115,6 +124,12 @@ struct sgm_instance {
     void* conf_dst;                      /* matching confidence (extension): where the running match's cost sum stores it, NULL: nowhere */
     void *d_conf, *h_conf;               /* device / page-locked staging of the host-pointer confidence entry points (first use) */
     size_t cap_conf, cap_h_conf;
+    refine_params rf_req, rf_eff;        /* refinement: the parameters last set (sgm_refine_disparity) and those of the matches */
+    void *d_rf_u, *d_rf_v, *d_rf_q;      /* its right-hand sides / solutions and the q_i of the line solves, f32 [B][H][W] each */
+    void* d_rf_conf;                     /* the confidence of a match whose caller did not ask for it, u16 [B][H][W] */
+    void* d_rf_guide[2];                 /* private copies of the reference image, used by turns (u8 [B][H][W] each) */
+    int rf_turn;
+    size_t cap_refine;
     size_t cap_bgr;
     size_t plane_bytes;
     /* pinned staging for the host-pointer entry point */
@@ -279,6 +294,12 @@ static void free_device_buffers(sgm_instance* s)
     if (s->h_conf) sgmd_free_pinned(s->device, s->h_conf);
     s->d_conf = s->h_conf = NULL;
     s->cap_conf = s->cap_h_conf = 0;
+    void** rf[] = {&s->d_rf_u, &s->d_rf_v, &s->d_rf_q, &s->d_rf_conf, &s->d_rf_guide[0], &s->d_rf_guide[1]};
+    for (size_t i = 0; i < sizeof rf / sizeof rf[0]; ++i) {
+        if (*rf[i]) sgmd_free(s->device, *rf[i]);
+        *rf[i] = NULL;
+    }
+    s->cap_refine = 0;
     sgmd_free_pinned(s->device, s->h_left);
     sgmd_free_pinned(s->device, s->h_right);
     sgmd_free_pinned(s->device, s->h_disp);
@@ -410,6 +431,48 @@ void sgm_keep_stages(sgm_instance* s, int enable) { if (s) s->keep_stages = enab
 #pragma weak sgmd_sum_wta_lr_conf
 #pragma weak sgmd_wta_right_conf
 static bool conf_available(void) { return sgmd_sum_wta_conf != NULL && sgmd_sum_wta_lr_conf != NULL && sgmd_wta_right_conf != NULL; }
+
+/* The refinement launcher (sgm_refine.hip), weakly referenced as well; a match with refinement needs the confidence kernels too */
+#pragma weak sgmd_refine_pass
+static bool refine_available(void) { return sgmd_refine_pass != NULL && conf_available(); }
+
+bool sgm_refine_table(float lambda, float sigma, int iterations, int t, float* out)
+{
+    if (!out || !isfinite(lambda) || !isfinite(sigma) || lambda <= 0 || sigma <= 0 || iterations < 1 ||
+        iterations > SGM_REFINE_MAX_ITERS || t < 0 || t >= iterations)
+        return false;
+    const double lam = (double)lambda * 1.5 * ldexp(1.0, 2 * (iterations - 1 - t)) / (ldexp(1.0, 2 * iterations) - 1.0);
+    for (int k = 0; k < 256; ++k) out[k] = (float)(lam * exp(-(double)k / (double)sigma));
+    return true;
+}
+
+static bool refine_params_set(refine_params* p, float lambda, float sigma, int iterations, int keep_invalid)
+{
+    if (keep_invalid != 0 && keep_invalid != 1) return false;
+    for (int t = 0; t < iterations; ++t)
+        if (!sgm_refine_table(lambda, sigma, iterations, t, p->tab[t])) return false;
+    if (iterations < 1) return false;
+    p->lambda = lambda;
+    p->sigma = sigma;
+    p->iters = iterations;
+    p->keep_invalid = keep_invalid;
+    return true;
+}
+
+bool sgm_set_refine(sgm_instance* s, int enable, float lambda, float sigma, int iterations, int keep_invalid)
+{
+    if (!s || (enable != 0 && enable != 1)) return false;
+    if (!enable) {
+        s->refine_req = 0;                                       /* takes effect at the next initialize */
+        return true;
+    }
+    if (!refine_available()) FAIL("the refinement is not part of this build");
+    refine_params p;
+    if (!refine_params_set(&p, lambda, sigma, iterations, keep_invalid)) return false;
+    s->rf_req = p;
+    s->refine_req = 1;
+    return true;
+}
 
 bool sgm_set_batch(sgm_instance* s, int frames)
 {
@@ -683,6 +746,42 @@ static int ensure_fill(sgm_instance* s)
     return 0;
 }
 
+/* the maps of the refinement, [B][H][W] each: U, V, Q (f32), the internal confidence (u16), two guide copies (u8) */
+static int ensure_refine(sgm_instance* s)
+{
+    const size_t px = (size_t)s->g.B * s->g.W * s->g.H;
+    if (s->d_rf_q && px <= s->cap_refine) return 0;
+    sync_streams(s);
+    void** rf[] = {&s->d_rf_u, &s->d_rf_v, &s->d_rf_q, &s->d_rf_conf, &s->d_rf_guide[0], &s->d_rf_guide[1]};
+    const size_t elem[] = {4, 4, 4, 2, 1, 1};
+    s->cap_refine = 0;
+    for (size_t i = 0; i < sizeof rf / sizeof rf[0]; ++i) {
+        sgmd_free(s->device, *rf[i]);
+        *rf[i] = NULL;
+    }
+    for (size_t i = 0; i < sizeof rf / sizeof rf[0]; ++i)
+        if (sgmd_alloc(s->device, rf[i], px * elem[i]) != 0) {
+            fprintf(stderr, "sgm_mi355x: device allocation failed for the refinement maps (%zu pixels)\n", px);
+            return -1;
+        }
+    s->cap_refine = px;
+    return 0;
+}
+
+/* the 2 T passes of the refinement on `disp`, in place (include/sgm_mi355x.h, sgm_set_refine) */
+static int refine_passes(sgm_instance* s, void* st, void* disp, const void* conf, const void* guide, const refine_params* p)
+{
+    int rc = 0;
+    for (int t = 0; rc == 0 && t < p->iters; ++t) {
+        rc = sgmd_refine_pass(s->device, st, &s->g, 0, p->tab[t], guide, t == 0 ? disp : NULL, t == 0 ? conf : NULL, s->d_rf_u,
+                              s->d_rf_v, s->d_rf_q, t == 0, 0, 0, NULL);
+        if (rc == 0)
+            rc = sgmd_refine_pass(s->device, st, &s->g, 1, p->tab[t], guide, NULL, NULL, s->d_rf_u, s->d_rf_v, s->d_rf_q, 0,
+                                  t == p->iters - 1, t == p->iters - 1 ? p->keep_invalid : 0, disp);
+    }
+    return rc;
+}
+
 /* the three Jacobi passes of the hole filling on `disp` (in place, through d_fill_map, which keeps the filled map: stage 9);
  * cls == NULL: pass 3 alone */
 static int fill_passes(sgm_instance* s, void* st, void* disp, const void* cls)
@@ -777,10 +876,21 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
     s->fill_on = false;
     if (s->fill_req && s->tile_end != 0)
         FAIL("hole filling (sgm_set_fill_holes) works on whole frames: not available in row-tile mode (sgm_set_rows)");
+    s->refine_on = false;
+    if (s->refine_req && s->tile_end != 0)
+        FAIL("the refinement (sgm_set_refine) works on whole frames: not available in row-tile mode (sgm_set_rows)");
+    if (s->refine_req && s->fill_req)
+        FAIL("the refinement (sgm_set_refine) and hole filling (sgm_set_fill_holes) do not combine: the refinement fills by itself, "
+             "and a filled pixel would carry the confidence of a disparity the LR check rejected");
     if (!ensure_buffers(s)) return false;
     if (s->fill_req) {
         if (ensure_fill(s) != 0) return false;
         s->fill_on = true;
+    }
+    if (s->refine_req) {
+        if (ensure_refine(s) != 0) return false;
+        s->rf_eff = s->rf_req;
+        s->refine_on = true;
     }
     /* extras: 4 anomalous lines x H steps x Dp bytes */
     const size_t extras_bytes = (size_t)s->g.B * 4 * height * s->g.Dp;
@@ -1010,7 +1120,7 @@ static int ensure_upsum(sgm_instance* s)
     return 0;
 }
 
-static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_right, void* d_out)
+static bool run_pipeline_body(sgm_instance* s, const void* d_left, const void* d_right, void* d_out)
 {
     const int dev = s->device;
     void* st = s->stream;
@@ -1025,6 +1135,15 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
     /* the aggregation rewrites the planes the previous match's cost sum may still be reading on its own stream */
     if (s->sum_pending) LAUNCH(sgmd_stream_wait_event(dev, st, s->ev_sum));
     if (!s->s_is_zero) LAUNCH(materialize_S(s));             /* Match without Reset: S of the previous frame is needed now */
+    /* the refinement's guide: the caller (or the next match's upload) may rewrite the images while the post pass of this match
+     * still runs on a stream of its own, so it reads a private copy.  Two copies by turns: the copy of match n + 2 is queued behind
+     * what waited for the post pass of match n (the cost sum of match n + 1 waits for it, and this stream waits for that sum) */
+    const void* guide = NULL;
+    if (s->refine_on) {
+        guide = s->d_rf_guide[s->rf_turn];
+        s->rf_turn ^= 1;
+        LAUNCH(sgmd_d2d_async(dev, st, (void*)guide, s->reference_view ? d_right : d_left, (size_t)g->B * g->W * g->H));
+    }
     mark(s, 0);
     LAUNCH(prepare_costs(s, d_left, d_right));                                                      /* .c:82-83 */
     mark(s, 1);
@@ -1093,6 +1212,7 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
     if (s->fill_on) LAUNCH(fill_passes(s, st2, d_out, s->d_fill_class));                           /* extension; timed as "speckle" */
     mark_on(s, st2, 7);
     LAUNCH(sgmd_median(dev, st2, g, d_out, s->d_median_scratch, s->h_status));                                   /* .c:120 */
+    if (s->refine_on) LAUNCH(refine_passes(s, st2, d_out, s->conf_dst, guide, &s->rf_eff));    /* extension; timed as "median" */
     mark_on(s, st2, 8);
     if (overlap) LAUNCH(sgmd_event_record(dev, s->ev_post, st2));
     else if (own_sum) LAUNCH(sgmd_event_record(dev, s->ev_sum, st2));   /* the post pass ran on the sum stream: "sum done" = all of it */
@@ -1109,6 +1229,17 @@ failed:
     if (s->sum_stream || s->post_stream) sync_streams(s);
     s->tail_stream = st;
     FAIL("a kernel launch failed; the match was abandoned");
+}
+
+/* every match: with the refinement on, the cost sum stores the confidence it needs -- to the caller's map (sgm_match_confidence*) or to
+ * an internal one */
+static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_right, void* d_out)
+{
+    const bool own_conf = s->refine_on && !s->conf_dst;
+    if (own_conf) s->conf_dst = s->d_rf_conf;
+    const bool ok = run_pipeline_body(s, d_left, d_right, d_out);
+    if (own_conf) s->conf_dst = NULL;
+    return ok;
 }
 
 /* ------------------------------------------------------------------ row tiles (one frame over several GPUs)
@@ -1478,6 +1609,20 @@ bool sgm_fill_holes(sgm_instance* s, float* d_disp, const uint8_t* d_class)
     return true;
 }
 
+/* ------------------------------------------------------------------ refinement of any map (extension) */
+
+bool sgm_refine_disparity(sgm_instance* s, float* d_disp, const uint16_t* d_conf, const uint8_t* d_guide)
+{
+    if (!s || !s->initialized || !d_disp || !d_conf || !d_guide) return false;
+    if (!refine_available()) FAIL("the refinement is not part of this build");
+    if (s->rf_req.iters < 1) FAIL("no refinement parameters: call sgm_set_refine first");
+    if (ensure_refine(s) != 0) return false;
+    /* U, V and Q may still be in use by the post pass of the last match on a stream of its own */
+    if (wait_for_result(s, s->stream) != 0) return false;
+    if (refine_passes(s, s->stream, d_disp, d_conf, d_guide, &s->rf_req) != 0) FAIL("a kernel launch failed");
+    return true;
+}
+
 /* ------------------------------------------------------------------ a test-platform frame end to end (8f-2) */
 
 bool sgm_gray_from_planes(sgm_instance* s, const uint8_t* d_bgr, size_t count, int weight_r, uint8_t* d_gray)
@@ -1657,6 +1802,27 @@ bool SGM_SetFillHoles(int enable)
     return g_default ? sgm_set_fill_holes(g_default, enable) : true;
 }
 
+static struct { int enable, iters, keep_invalid; float lambda, sigma; } g_default_refine;
+
+bool SGM_SetRefine(int enable, float lambda, float sigma, int iterations, int keep_invalid)
+{
+    if (enable != 0 && enable != 1) return false;
+    if (enable) {
+        if (!refine_available()) FAIL("the refinement is not part of this build");
+        refine_params p;
+        if (!refine_params_set(&p, lambda, sigma, iterations, keep_invalid)) return false;
+    }
+    if (g_default && !sgm_set_refine(g_default, enable, lambda, sigma, iterations, keep_invalid)) return false;
+    g_default_refine.enable = enable;
+    if (enable) {
+        g_default_refine.lambda = lambda;
+        g_default_refine.sigma = sigma;
+        g_default_refine.iters = iterations;
+        g_default_refine.keep_invalid = keep_invalid;
+    }
+    return true;
+}
+
 bool SGM_SetCensusWindow(int width, int height)
 {
     if (width < 1 || height < 1 || !(width & 1) || !(height & 1) || width * height > 64) return false;
@@ -1690,6 +1856,9 @@ bool SGM_Initialize(uint16_t width, uint16_t height, const SGMOption* option)
         if (g_default_census_w) sgm_set_census_window(g_default, g_default_census_w, g_default_census_h);
         sgm_set_reference_view(g_default, g_default_view);
         if (g_default_fill) sgm_set_fill_holes(g_default, 1);
+        if (g_default_refine.enable)
+            sgm_set_refine(g_default, 1, g_default_refine.lambda, g_default_refine.sigma, g_default_refine.iters,
+                           g_default_refine.keep_invalid);
     }
     return sgm_initialize(g_default, width, height, option);
 }

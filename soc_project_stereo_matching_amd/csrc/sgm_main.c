@@ -12,6 +12,8 @@
  *            as reference view; the defaults are the reference's behaviour
  *            [--fill-holes]   extension: occlusion-aware hole filling of the invalid disparities (SGM_SetFillHoles)
  *            [--confidence OUT.pgm]   extension: the matching confidence (SGM_MatchConfidence) as a 16-bit PGM
+ *            [--refine[=LAMBDA,SIGMA,ITERS]]   extension: confidence-guided edge-aware refinement of the map (SGM_SetRefine;
+ *                             defaults SGM_REFINE_DEFAULT_*)
  *   sgm_main --convert IN OUT.png        (image I/O only, no GPU: used by the CPU tests)
  */
 #define _POSIX_C_SOURCE 200809L
@@ -66,7 +68,9 @@ int main(int argc, char** argv)
     opt.p2_init = 150;
     const char* raw_path = NULL;
     const char* conf_path = NULL;
-    int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0;
+    int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
+    float refine_lambda = SGM_REFINE_DEFAULT_LAMBDA, refine_sigma = SGM_REFINE_DEFAULT_SIGMA;
+    int refine_iters = SGM_REFINE_DEFAULT_ITERS;
     for (int i = 4; i < argc; ++i) {
         const char* a = argv[i];
         const char* v = (i + 1 < argc) ? argv[i + 1] : NULL;
@@ -91,6 +95,15 @@ int main(int argc, char** argv)
         }
         else if (!strcmp(a, "--right-reference")) right_ref = 1;
         else if (!strcmp(a, "--fill-holes")) fill_holes = 1;
+        else if (!strcmp(a, "--refine")) refine = 1;
+        else if (!strncmp(a, "--refine=", 9)) {
+            if (sscanf(a + 9, "%f,%f,%d", &refine_lambda, &refine_sigma, &refine_iters) != 3) {
+                fprintf(stderr, "--refine= wants LAMBDA,SIGMA,ITERS, e.g. --refine=%g,%g,%d\n", SGM_REFINE_DEFAULT_LAMBDA,
+                        SGM_REFINE_DEFAULT_SIGMA, SGM_REFINE_DEFAULT_ITERS);
+                return 2;
+            }
+            refine = 1;
+        }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
     }
 
@@ -106,6 +119,10 @@ int main(int argc, char** argv)
     if (census_w && !SGM_SetCensusWindow(census_w, census_h)) { printf("unsupported census window %dx%d\n", census_w, census_h); return -2; }
     if (right_ref) SGM_SetReferenceView(1);
     if (fill_holes && !SGM_SetFillHoles(1)) { printf("hole filling unavailable\n"); return -2; }
+    if (refine && !SGM_SetRefine(1, refine_lambda, refine_sigma, refine_iters, 0)) {
+        printf("refinement unavailable or parameters out of range (%g, %g, %d)\n", refine_lambda, refine_sigma, refine_iters);
+        return -2;
+    }
     if (!SGM_Initialize((uint16_t)w1, (uint16_t)h1, &opt)) { printf("SGM initialization failed\n"); return -2; }
     float* disp = (float*)malloc(sizeof(float) * (size_t)w1 * h1);
     uint16_t* conf = conf_path ? (uint16_t*)malloc(sizeof(uint16_t) * (size_t)w1 * h1) : NULL;

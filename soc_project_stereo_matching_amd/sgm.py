@@ -21,6 +21,8 @@ STAGE_NAMES = ["census_l", "census_r", "cost", "aggr", "disp_l", "disp_r", "afte
 _STAGE_DTYPE = [np.uint32, np.uint32, np.uint8, np.uint16] + [np.float32] * 5
 # stages outside STAGE_NAMES (read_stages() leaves them out: they exist only with hole filling on, set_fill_holes)
 STAGE_FILLED, STAGE_FILL_CLASS = 9, 18
+# the refinement's default parameters (SGM_REFINE_DEFAULT_* of include/sgm_mi355x.h)
+REFINE_LAMBDA, REFINE_SIGMA, REFINE_ITERS = 16.0, 1.5, 1
 
 
 class SGMOption(C.Structure):
@@ -126,6 +128,15 @@ def _load() -> C.CDLL:
         L.SGM_SetFillHoles.restype = C.c_bool
         L.sgm_fill_holes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.sgm_fill_holes.restype = C.c_bool
+    if hasattr(L, "sgm_set_refine"):          # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_set_refine.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]
+        L.sgm_set_refine.restype = C.c_bool
+        L.SGM_SetRefine.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]
+        L.SGM_SetRefine.restype = C.c_bool
+        L.sgm_refine_table.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p]
+        L.sgm_refine_table.restype = C.c_bool
+        L.sgm_refine_disparity.argtypes = [C.c_void_p] * 4
+        L.sgm_refine_disparity.restype = C.c_bool
     if hasattr(L, "sgm_match_confidence"):    # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         for f in (L.sgm_match_confidence, L.sgm_match_confidence_async, L.sgm_match_confidence_device):
             f.argtypes = [C.c_void_p] * 5
@@ -217,6 +228,33 @@ def synth_pair(width, height, disparity_range, seed):
     return left, right
 
 
+def set_refine(enable=True, lam=REFINE_LAMBDA, sigma=REFINE_SIGMA, iterations=REFINE_ITERS, keep_invalid=False) -> bool:
+    """SGM_SetRefine: the refinement of the default instance (SGM_Initialize / SGM_Reset / SGM_Match); include/sgm_mi355x.h has the
+    contract.  Takes effect at the next initialize / reset; False for parameters out of range."""
+    return bool(load_library().SGM_SetRefine(int(enable), lam, sigma, int(iterations), int(keep_invalid)))
+
+
+def refine_table(lam, sigma, iterations, t):
+    """sgm_refine_table: the float32 weight table L_t[256] of iteration t (host only)."""
+    out = np.zeros(256, np.float32)
+    if not load_library().sgm_refine_table(lam, sigma, int(iterations), int(t), out.ctypes.data):
+        raise ValueError(f"sgm_refine_table: arguments out of range ({lam}, {sigma}, {iterations}, {t})")
+    return out
+
+
+def _device_ptr(x, dtype, count, name):
+    """A device pointer from an int or a torch tensor (checked: contiguous, dtype, number of elements)."""
+    if isinstance(x, int):
+        return x
+    import torch
+    want = {np.float32: torch.float32, np.uint16: torch.uint16 if hasattr(torch, "uint16") else torch.int16,
+            np.uint8: torch.uint8}[dtype]
+    ok_dtype = x.dtype == want or (dtype is np.uint16 and x.dtype in (torch.int16,))
+    if not (x.is_cuda and x.is_contiguous() and ok_dtype and x.numel() == count):
+        raise ValueError(f"{name}: a contiguous device tensor of {count} {np.dtype(dtype).name} elements is needed")
+    return x.data_ptr()
+
+
 def _u8(a):
     a = np.ascontiguousarray(a)
     if a.dtype != np.uint8:
@@ -285,6 +323,10 @@ class SGM(_StageReader):
     def set_fill_holes(self, enable: bool = True) -> bool:
         """Extension: occlusion-aware hole filling of the +INF pixels (include/sgm_mi355x.h); next initialize/reset."""
         return bool(self.lib.SGM_SetFillHoles(int(enable)))
+
+    def set_refine(self, enable=True, lam=REFINE_LAMBDA, sigma=REFINE_SIGMA, iterations=REFINE_ITERS, keep_invalid=False) -> bool:
+        """Extension: confidence-guided edge-aware refinement of the map (include/sgm_mi355x.h); next initialize/reset."""
+        return set_refine(enable, lam, sigma, iterations, keep_invalid)
 
     def keep_stages(self, enable=True):
         self.lib.SGM_KeepStages(int(enable))
@@ -436,6 +478,20 @@ class SGMInstance(_StageReader):
         """sgm_fill_holes: fill the +INF pixels of a device map of the instance's batch and shape in place (passes 1 and 2 need
         the u8 class map d_class, None runs pass 3 alone); asynchronous on `stream`."""
         return bool(self.lib.sgm_fill_holes(self.handle, d_disp, d_class or None))
+
+    def set_refine(self, enable=True, lam=REFINE_LAMBDA, sigma=REFINE_SIGMA, iterations=REFINE_ITERS, keep_invalid=False) -> bool:
+        """Extension: confidence-guided edge-aware refinement of the map (include/sgm_mi355x.h); next initialize/reset.  False for
+        parameters out of range."""
+        return bool(self.lib.sgm_set_refine(self.handle, int(enable), lam, sigma, int(iterations), int(keep_invalid)))
+
+    def refine_disparity(self, d_disp, d_conf, d_guide) -> bool:
+        """sgm_refine_disparity: refine a device map of the instance's batch and shape in place with the parameters of the last
+        set_refine(True, ...), from the confidence (uint16) and the grey image (uint8); device pointers or torch tensors.
+        Asynchronous on `stream`."""
+        n = self.batch * self.shape[0] * self.shape[1] if self.shape else 0
+        return bool(self.lib.sgm_refine_disparity(self.handle, _device_ptr(d_disp, np.float32, n, "d_disp"),
+                                                  _device_ptr(d_conf, np.uint16, n, "d_conf"),
+                                                  _device_ptr(d_guide, np.uint8, n, "d_guide")))
 
     def keep_stages(self, enable=True):
         self.lib.sgm_keep_stages(self.handle, int(enable))

@@ -1,0 +1,503 @@
+"""Refinement (include/sgm_mi355x.h, SGM_SetRefine) on the CPU: the numpy restatement tests/refine_ref.py against a dense solver and
+the properties the header promises, the library's weight tables, the exported interface, the host logic on the stand-in device, and
+the accuracy on the reference's four image pairs against their ground truth (tests/golden/gt_disparity.npz).  Parity unpinned by
+the reference: the reference has no such stage."""
+import ctypes as C
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import confidence_ref as CR
+import fill_holes_ref as FH
+import refine_ref as R
+from conftest import GOLDEN, ROOT, case_inputs, load_npz, option_from_dict
+
+CSRC = os.path.join(ROOT, "soc_project_stereo_matching_amd", "csrc")
+F = np.float32
+INF = F(np.inf)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+def lib_or_none():
+    import soc_project_stereo_matching_amd as S
+    return S.load_library() if os.path.exists(S.library_path()) else None
+
+
+def defaults():
+    import soc_project_stereo_matching_amd as S
+    return S.REFINE_LAMBDA, S.REFINE_SIGMA, S.REFINE_ITERS
+
+
+# ---- the line solve --------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n", [1, 2, 3, 17, 200])
+def test_line_solve_satisfies_the_tridiagonal_system(n):
+    """x of the float32 Thomas recurrence solves (1 + a + c) x_i - a x_{i-1} - c x_{i+1} = r_i to float32 rounding level, and agrees
+    with a float64 dense solve."""
+    rng = np.random.default_rng(n)
+    N = 6
+    g = rng.integers(0, 256, (N, n)).astype(np.uint8)
+    g[:, n // 2:] = g[:, n // 2:] // 8                        # some flat stretches: large weights
+    L = R.table_numpy(40.0, 6.0, 1, 0)
+    U = (rng.random((N, n)) * 60).astype(F)
+    V = rng.random((N, n)).astype(F)
+    xu, xv = R.solve_lines(g, U, V, L)
+    for k in range(N):
+        e = L[np.abs(g[k, 1:].astype(int) - g[k, :-1].astype(int))].astype(np.float64)
+        A = np.zeros((n, n))
+        for i in range(n):
+            a = e[i - 1] if i > 0 else 0.0
+            c = e[i] if i < n - 1 else 0.0
+            A[i, i] = 1 + a + c
+            if i > 0:
+                A[i, i - 1] = -a
+            if i < n - 1:
+                A[i, i + 1] = -c
+        for r, x in ((U[k], xu[k]), (V[k], xv[k])):
+            r64 = r.astype(np.float64)
+            want = np.linalg.solve(A, r64)
+            res = np.abs(A @ x.astype(np.float64) - r64).max()
+            scale = np.abs(A).sum(axis=1).max() * max(np.abs(x).max(), 1e-30)
+            assert res <= 1e-5 * scale, (n, k, res, scale)
+            assert np.allclose(x, want, rtol=2e-4, atol=1e-5 * max(np.abs(want).max(), 1e-30)), (n, k)
+
+
+def random_frame(h, w, seed, invalid=0.3):
+    rng = np.random.default_rng(seed)
+    D = (rng.random((h, w)) * 50 + 3).astype(F)
+    D[rng.random((h, w)) < invalid] = INF
+    K = rng.integers(0, 65536, (h, w)).astype(np.uint16)
+    G = rng.integers(0, 256, (h, w)).astype(np.uint8)
+    return D, K, G
+
+
+def test_result_stays_within_the_range_of_the_valid_inputs():
+    for seed, (lam, sigma, T) in enumerate(((64.0, 8.0, 3), (4.0, 4.0, 1), (1000.0, 40.0, 4), (0.5, 1.0, 2))):
+        D, K, G = random_frame(23, 31, seed)
+        out = R.refine(D, K, G, R.tables(lam, sigma, T))
+        lo, hi = D[np.isfinite(D)].min(), D[np.isfinite(D)].max()
+        fin = np.isfinite(out)
+        assert fin.any()
+        assert out[fin].min() >= lo and out[fin].max() <= hi, (seed, out[fin].min(), out[fin].max(), lo, hi)
+
+
+def test_a_step_in_guide_and_disparity_stays_a_step():
+    """A wall of 255 grey levels: exp(-255 / 2) underflows in float32, the edge weight is 0 and nothing crosses it."""
+    h, w = 12, 20
+    G = np.zeros((h, w), np.uint8)
+    G[:, 9:] = 255
+    D = np.where(np.arange(w) < 9, F(10), F(40)).astype(F)[None, :].repeat(h, 0)
+    D[3, 2] = INF
+    D[7, 15] = INF
+    K = np.full((h, w), 30000, np.uint16)
+    K[5, 4] = 9
+    tabs = R.tables(500.0, 2.0, 3)
+    assert tabs[0][255] == 0
+    out = R.refine(D, K, G, tabs)
+    assert np.isfinite(out).all()
+    assert np.allclose(out[:, :9], 10, atol=1e-4) and np.allclose(out[:, 9:], 40, atol=1e-4)
+
+
+def test_all_inf_stays_inf():
+    D = np.full((2, 9, 13), INF, F)
+    K = np.full(D.shape, 65535, np.uint16)
+    G = np.random.default_rng(3).integers(0, 256, D.shape).astype(np.uint8)
+    for keep in (False, True):
+        assert np.all(R.refine(D, K, G, R.tables(64.0, 8.0, 3), keep) == INF)
+
+
+def test_underflowing_weights_cut_segments_and_an_unconfident_segment_stays_inf():
+    h, w = 8, 24
+    G = np.zeros((h, w), np.uint8)
+    G[:, 8:16] = 255                                           # three vertical bands, walls between them
+    D = np.full((h, w), INF, F)
+    D[:, :8] = 5.0
+    D[2, 20] = 30.0
+    K = np.full((h, w), 65535, np.uint16)
+    out = R.refine(D, K, G, R.tables(100.0, 1.0, 2))
+    assert np.all(out[:, 8:16] == INF)                         # no confident pixel in the middle band
+    assert np.allclose(out[:, :8], 5.0, atol=1e-5)
+    assert np.isfinite(out[:, 16:]).all() and np.allclose(out[:, 16:], 30.0, atol=1e-4)   # filled from its one valid pixel
+    K0 = K.copy()
+    K0[:, :8] = 0                                              # valid but zero confidence: V = 0 there too
+    out0 = R.refine(D, K0, G, R.tables(100.0, 1.0, 2))
+    assert np.all(out0[:, :16] == INF)
+
+
+def test_keep_invalid_masks_exactly_the_inf_pixels():
+    D, K, G = random_frame(2 * 17, 29, 11)
+    D = D.reshape(2, 17, 29)
+    K = K.reshape(2, 17, 29)
+    G = G.reshape(2, 17, 29)
+    tabs = R.tables(64.0, 8.0, 2)
+    dense = R.refine(D, K, G, tabs, False)
+    kept = R.refine(D, K, G, tabs, True)
+    assert np.isfinite(dense).all()
+    assert np.array_equal(bits(kept), bits(np.where(np.isfinite(D), dense, INF)))
+
+
+def test_frames_of_a_batch_are_independent():
+    D, K, G = random_frame(3 * 10, 14, 5)
+    D, K, G = (a.reshape(3, 10, 14) for a in (D, K, G))
+    tabs = R.tables(30.0, 5.0, 3)
+    got = R.refine(D, K, G, tabs)
+    for f in range(3):
+        assert np.array_equal(bits(got[f]), bits(R.refine(D[f], K[f], G[f], tabs)))
+
+
+# ---- the library's tables and interface -------------------------------------------------------------------------------
+
+def ulp_distance(a, b):
+    ia = a.view(np.int32).astype(np.int64)
+    ib = b.view(np.int32).astype(np.int64)
+    return np.abs(ia - ib)
+
+
+@pytest.mark.parametrize("lam,sigma,T", [(64.0, 8.0, 3), (4.0, 4.0, 1), (8000.0, 1.5, 8), (0.25, 100.0, 2), (1.0, 0.3, 4)])
+def test_library_tables_agree_with_numpy(lam, sigma, T):
+    lib = lib_or_none()
+    assert lib is not None, "libsgm_mi355x.so is not built"
+    for t in range(T):
+        got = R.table_lib(lib, lam, sigma, T, t)
+        want = R.table_numpy(lam, sigma, T, t)
+        assert ulp_distance(got, want).max() <= 1, (lam, sigma, T, t)
+        assert got[0] == F(float(F(lam)) * 1.5 * 4.0 ** (T - 1 - t) / (4.0 ** T - 1.0))
+        assert np.all(np.diff(got.astype(np.float64)) <= 0)
+
+
+def test_library_table_refuses_bad_arguments():
+    lib = lib_or_none()
+    assert lib is not None
+    f = lib.sgm_refine_table
+    f.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p]
+    f.restype = C.c_bool
+    out = np.zeros(256, F)
+    for args in ((0.0, 8.0, 3, 0), (-1.0, 8.0, 3, 0), (float("inf"), 8.0, 3, 0), (float("nan"), 8.0, 3, 0), (64.0, 0.0, 3, 0),
+                 (64.0, float("inf"), 3, 0), (64.0, 8.0, 0, 0), (64.0, 8.0, 9, 0), (64.0, 8.0, 3, 3), (64.0, 8.0, 3, -1)):
+        assert not f(*args, out.ctypes.data), args
+    assert f(64.0, 8.0, 3, 2, out.ctypes.data)
+
+
+def test_header_declares_the_entry_points():
+    with open(os.path.join(ROOT, "include", "sgm_mi355x.h")) as fh:
+        h = fh.read()
+    for decl in (r"bool\s+SGM_SetRefine\(int enable, float lambda, float sigma, int iterations, int keep_invalid\)",
+                 r"bool\s+sgm_set_refine\(sgm_instance\* s, int enable, float lambda, float sigma, int iterations, int keep_invalid\)",
+                 r"bool\s+sgm_refine_table\(float lambda, float sigma, int iterations, int t, float\* out\)",
+                 r"bool\s+sgm_refine_disparity\(sgm_instance\* s, float\* d_disp, const uint16_t\* d_conf, const uint8_t\* d_guide\)"):
+        assert re.search(decl, h), decl
+    assert "never leaves" in h and "m_i = b_i - a_i * q_{i-1}" in h
+
+
+def test_library_exports_the_refinement():
+    import soc_project_stereo_matching_amd as S
+    lib = lib_or_none()
+    assert lib is not None
+    for sym in ("SGM_SetRefine", "sgm_set_refine", "sgm_refine_table", "sgm_refine_disparity", "sgmd_refine_pass"):
+        assert hasattr(lib, sym), sym
+    assert callable(S.sgm.set_refine) and callable(getattr(S.SGM, "set_refine", None))
+    for m in ("set_refine", "refine_disparity"):
+        assert callable(getattr(S.SGMInstance, m, None)), m
+    assert np.array_equal(S.sgm.refine_table(64.0, 8.0, 3, 1), R.table_lib(lib, 64.0, 8.0, 3, 1))
+
+
+# ---- host logic on the stand-in device ---------------------------------------------------------------------------------
+
+def _build(tmp_path_factory, with_refine):
+    out = tmp_path_factory.mktemp("refinestub") / ("librefine%d.so" % with_refine)
+    srcs = [os.path.join(CSRC, "sgm_host.c"), os.path.join(ROOT, "tests", "stub_device.c"),
+            os.path.join(ROOT, "tests", "stub_device_conf.c")]
+    if with_refine:
+        srcs.append(os.path.join(ROOT, "tests", "stub_device_refine.c"))
+    subprocess.check_call(["gcc", "-O1", "-std=c11", "-fPIC", "-shared", "-I", CSRC, "-o", str(out)] + srcs + ["-lm"])
+    L = C.CDLL(str(out))
+    L.sgm_create.restype = C.c_void_p
+    L.sgm_create.argtypes = [C.c_int]
+    L.sgm_destroy.argtypes = [C.c_void_p]
+    for f in (L.sgm_initialize, L.sgm_reset):
+        f.argtypes = [C.c_void_p, C.c_uint16, C.c_uint16, C.c_void_p]
+        f.restype = C.c_bool
+    for f in (L.sgm_match, L.sgm_match_async, L.sgm_match_device):
+        f.argtypes = [C.c_void_p] * 4
+        f.restype = C.c_bool
+    L.sgm_match_confidence_device.argtypes = [C.c_void_p] * 5
+    L.sgm_match_confidence_device.restype = C.c_bool
+    L.sgm_match_wait.argtypes = [C.c_void_p]
+    L.sgm_match_wait.restype = C.c_bool
+    L.sgm_set_refine.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]
+    L.sgm_set_refine.restype = C.c_bool
+    L.SGM_SetRefine.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]
+    L.SGM_SetRefine.restype = C.c_bool
+    L.sgm_refine_disparity.argtypes = [C.c_void_p] * 4
+    L.sgm_refine_disparity.restype = C.c_bool
+    L.sgm_set_fill_holes.argtypes = [C.c_void_p, C.c_int]
+    L.sgm_set_fill_holes.restype = C.c_bool
+    L.sgm_set_overlap_post.argtypes = [C.c_void_p, C.c_int]
+    L.sgm_set_overlap_post.restype = C.c_bool
+    L.sgm_set_reference_view.argtypes = [C.c_void_p, C.c_int]
+    L.sgm_set_rows.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.sgm_set_rows.restype = C.c_bool
+    L.sgm_fused_sweep_rows.argtypes = [C.c_void_p]
+    L.stub_log_name.restype = C.c_char_p
+    L.stub_log_name.argtypes = [C.c_int]
+    L.stub_log_arg.argtypes = [C.c_int]
+    L.stubc_log_dst.restype = C.c_void_p
+    L.stubc_log_dst.argtypes = [C.c_int]
+    if with_refine:
+        for n in ("flags", "pos"):
+            getattr(L, "stubr_log_" + n).argtypes = [C.c_int]
+        for n in ("guide", "conf"):
+            getattr(L, "stubr_log_" + n).argtypes = [C.c_int]
+            getattr(L, "stubr_log_" + n).restype = C.c_void_p
+        L.stubr_log_l0.argtypes = [C.c_int]
+        L.stubr_log_l0.restype = C.c_float
+    return L
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    return _build(tmp_path_factory, True)
+
+
+@pytest.fixture(scope="module")
+def host_old(tmp_path_factory):
+    return _build(tmp_path_factory, False)
+
+
+def clear(L):
+    L.stub_clear()
+    L.stubc_clear()
+    if hasattr(L, "stubr_clear"):
+        L.stubr_clear()
+
+
+def names(L):
+    return [L.stub_log_name(i).decode() for i in range(L.stub_log_size())]
+
+
+class Frame:
+    def __init__(self, w=48, h=20):
+        self.left = np.zeros((h, w), np.uint8)
+        self.right = np.zeros((h, w), np.uint8)
+        self.out = np.zeros((h, w), np.float32)
+        self.conf = np.zeros((h, w), np.uint16)
+
+    def args(self):
+        return self.left.ctypes.data, self.right.ctypes.data, self.out.ctypes.data
+
+
+def make(L, refine=True, rows=None, fill=False, **kw):
+    import soc_project_stereo_matching_amd as S
+    s = L.sgm_create(0)
+    assert s
+    if rows:
+        assert L.sgm_set_rows(s, *rows)
+    if fill:
+        assert L.sgm_set_fill_holes(s, 1)
+    if refine:
+        assert L.sgm_set_refine(s, 1, *kw.get("params", (64.0, 8.0, 3)), kw.get("keep", 0))
+    return s, S.default_option(16)
+
+
+def test_parameter_validation(host):
+    L = host
+    s = L.sgm_create(0)
+    good = (64.0, 8.0, 3, 0)
+    for enable, lam, sigma, it, keep in ((2, *good), (-1, *good), (1, 0.0, 8.0, 3, 0), (1, -2.0, 8.0, 3, 0),
+                                         (1, float("inf"), 8.0, 3, 0), (1, float("nan"), 8.0, 3, 0), (1, 64.0, 0.0, 3, 0),
+                                         (1, 64.0, -1.0, 3, 0), (1, 64.0, float("nan"), 3, 0), (1, 64.0, 8.0, 0, 0),
+                                         (1, 64.0, 8.0, 9, 0), (1, 64.0, 8.0, 3, 2), (1, 64.0, 8.0, 3, -1)):
+        assert not L.sgm_set_refine(s, enable, lam, sigma, it, keep), (enable, lam, sigma, it, keep)
+        assert not L.SGM_SetRefine(enable, lam, sigma, it, keep)
+    assert L.sgm_set_refine(s, 1, 64.0, 8.0, 1, 1) and L.sgm_set_refine(s, 1, 64.0, 8.0, 8, 0)
+    assert L.sgm_set_refine(s, 0, 0.0, 0.0, 0, 0)                 # disabling looks at nothing else
+    assert not L.sgm_set_refine(None, 1, *good)
+    L.sgm_destroy(s)
+
+
+def test_refused_params_change_nothing(host):
+    L = host
+    s, opt = make(L, params=(20.0, 5.0, 2))
+    assert not L.sgm_set_refine(s, 1, 20.0, 5.0, 99, 0)
+    assert L.sgm_reset(s, 48, 20, C.byref(opt))
+    clear(L)
+    f = Frame()
+    assert L.sgm_match(s, *f.args())
+    assert L.stubr_log_size() == 4                               # still T = 2
+    L.sgm_destroy(s)
+
+
+def test_initialize_refuses_refinement_with_hole_filling(host):
+    L = host
+    s, opt = make(L, fill=True)
+    assert not L.sgm_reset(s, 48, 20, C.byref(opt))
+    assert L.sgm_set_fill_holes(s, 0)
+    assert L.sgm_reset(s, 48, 20, C.byref(opt))
+    L.sgm_destroy(s)
+
+
+def test_initialize_refuses_refinement_in_row_tile_mode(host):
+    L = host
+    s, opt = make(L, rows=(0, 10))
+    assert not L.sgm_reset(s, 48, 20, C.byref(opt))
+    assert L.sgm_set_refine(s, 0, 0.0, 0.0, 0, 0)
+    assert L.sgm_reset(s, 48, 20, C.byref(opt))
+    L.sgm_destroy(s)
+
+
+@pytest.mark.parametrize("T", [1, 3])
+@pytest.mark.parametrize("right_view", [False, True], ids=["left", "right"])
+def test_match_runs_2T_passes_after_the_median(host, T, right_view):
+    L = host
+    s, opt = make(L, params=(64.0, 8.0, T), keep=1)
+    L.sgm_set_reference_view(s, 1 if right_view else 0)
+    assert L.sgm_reset(s, 48, 20, C.byref(opt))
+    clear(L)
+    f = Frame()
+    assert L.sgm_match(s, *f.args())
+    log = names(L)
+    med = log.index("median")
+    assert L.stubr_log_size() == 2 * T
+    flags = [L.stubr_log_flags(i) for i in range(2 * T)]
+    want = []
+    for t in range(T):
+        want += [(2 if t == 0 else 0), 1 | ((4 | 8) if t == T - 1 else 0)]
+    assert flags == want
+    assert all(L.stubr_log_pos(i) == med + 1 for i in range(2 * T))        # right behind the median, nothing between
+    # the confidence went to an internal map, the guide is a private copy (a d2d of W*H bytes before the census)
+    conf = L.stubr_log_conf(0)
+    assert conf and conf == L.stubc_log_dst(0) and conf != f.conf.ctypes.data
+    assert all(L.stubr_log_conf(i) is None for i in range(1, 2 * T))    # read by the first pass only
+    assert log[:log.index("census")].count("d2d") == 1 and L.stub_log_arg(log.index("d2d")) == 48 * 20
+    assert len({L.stubr_log_guide(i) for i in range(2 * T)}) == 1
+    assert L.sgm_fused_sweep_rows(s) == 0
+    L.sgm_destroy(s)
+
+
+def test_guide_copies_alternate_between_matches(host):
+    L = host
+    s, opt = make(L, params=(64.0, 8.0, 1))
+    assert L.sgm_set_overlap_post(s, 1)
+    assert L.sgm_reset(s, 48, 20, C.byref(opt))
+    f = Frame()
+    guides = []
+    for _ in range(3):
+        clear(L)
+        assert L.sgm_match_async(s, *f.args())
+        guides.append(L.stubr_log_guide(0))
+    assert L.sgm_match_wait(s)
+    assert guides[0] != guides[1] and guides[0] == guides[2]
+    L.sgm_destroy(s)
+
+
+def test_confidence_match_refines_from_the_callers_map(host):
+    L = host
+    s, opt = make(L)
+    assert L.sgm_reset(s, 48, 20, C.byref(opt))
+    clear(L)
+    f = Frame()
+    assert L.sgm_match_confidence_device(s, *f.args(), f.conf.ctypes.data)
+    assert L.stubc_log_dst(0) == f.conf.ctypes.data and L.stubr_log_conf(0) == f.conf.ctypes.data
+    L.sgm_destroy(s)
+
+
+def test_switching_refinement_off_restores_the_plain_launches(host):
+    L = host
+    f = Frame()
+    s, opt = make(L, refine=False)
+    assert L.sgm_reset(s, 48, 20, C.byref(opt))
+    clear(L)
+    assert L.sgm_match(s, *f.args())
+    plain = [n for n in names(L) if n not in ("alloc", "sync")]
+    assert L.stubc_log_size() == 0
+    L.sgm_destroy(s)
+    s, opt = make(L)
+    assert L.sgm_reset(s, 48, 20, C.byref(opt))
+    assert L.sgm_match(s, *f.args())
+    assert L.sgm_set_refine(s, 0, 0.0, 0.0, 0, 0)
+    assert L.sgm_reset(s, 48, 20, C.byref(opt))
+    clear(L)
+    assert L.sgm_match(s, *f.args())
+    assert [n for n in names(L) if n not in ("alloc", "sync")] == plain
+    assert L.stubc_log_size() == 0 and L.stubr_log_size() == 0
+    L.sgm_destroy(s)
+
+
+def test_standalone_refinement(host):
+    L = host
+    s, opt = make(L, refine=False)
+    assert L.sgm_reset(s, 48, 20, C.byref(opt))
+    f = Frame()
+    assert not L.sgm_refine_disparity(s, f.out.ctypes.data, f.conf.ctypes.data, f.left.ctypes.data)   # no parameters yet
+    assert L.sgm_set_refine(s, 1, 64.0, 8.0, 2, 0)
+    clear(L)
+    assert L.sgm_refine_disparity(s, f.out.ctypes.data, f.conf.ctypes.data, f.left.ctypes.data)
+    assert L.stubr_log_size() == 4 and L.stubr_log_guide(0) == f.left.ctypes.data and L.stubr_log_conf(0) == f.conf.ctypes.data
+    for args in ((None, f.conf.ctypes.data, f.left.ctypes.data), (f.out.ctypes.data, None, f.left.ctypes.data),
+                 (f.out.ctypes.data, f.conf.ctypes.data, None)):
+        assert not L.sgm_refine_disparity(s, *args)
+    L.sgm_destroy(s)
+
+
+def test_host_without_the_launcher_links_and_refuses(host_old):
+    L = host_old
+    s = L.sgm_create(0)
+    assert not L.sgm_set_refine(s, 1, 64.0, 8.0, 3, 0)
+    assert not L.SGM_SetRefine(1, 64.0, 8.0, 3, 0)
+    assert L.sgm_set_refine(s, 0, 0.0, 0.0, 0, 0)
+    import soc_project_stereo_matching_amd as S
+    opt = S.default_option(16)
+    assert L.sgm_reset(s, 48, 20, C.byref(opt))
+    f = Frame()
+    assert not L.sgm_refine_disparity(s, f.out.ctypes.data, f.conf.ctypes.data, f.left.ctypes.data)
+    assert L.sgm_match(s, *f.args())
+    L.sgm_destroy(s)
+
+
+# ---- accuracy on the reference's image pairs ---------------------------------------------------------------------------
+
+SCENES = [("cone", "cone"), ("cloth3", "scene_cloth3"), ("reindeer", "scene_reindeer"), ("wood2", "scene_wood2")]
+
+
+def bad_rate(d, gt, known):
+    """share of the pixels with known ground truth whose disparity is +INF or off by more than 1 px"""
+    bad = ~np.isfinite(d) | (np.abs(d - gt) > 1)
+    return float(bad[known].mean())
+
+
+def test_ground_truth_fixture():
+    z = load_npz("gt_disparity.npz")
+    assert float(z["cone_scale"]) == 4.0
+    for name in ("cloth3", "reindeer", "wood2"):
+        assert float(z[name + "_scale"]) == 2.0 and abs(float(z[name + "_scale_measured"]) - 2.0) < 0.02
+    for name, _ in SCENES:
+        assert z[name].dtype == np.uint8 and (z[name] > 0).mean() > 0.95
+
+
+@pytest.mark.parametrize("scene,case", SCENES)
+def test_refinement_lowers_the_bad_pixel_rate(oracle, golden_cases, scene, case):
+    """The oracle's final map refined with the defaults, from the confidence of its stage-3 costs and the left image: fewer bad
+    pixels (> 1 px off, +INF counted bad) against the ground truth than the map itself.  Hole filling beside it for comparison."""
+    c = golden_cases[case]
+    left, right = case_inputs(c, oracle)
+    opt = option_from_dict(c["option"])
+    st = oracle.run(left, right, opt)
+    conf = CR.confidence(st["aggr"], opt.min_disparity, False)[3]
+    z = load_npz("gt_disparity.npz")
+    gt = z[scene].astype(F) / z[scene + "_scale"]
+    known = z[scene] > 0
+    assert gt.shape == st["final"].shape
+    lam, sigma, T = defaults()
+    refined = R.refine(st["final"], conf, left, R.tables(lam, sigma, T, lib_or_none()))
+    filled = oracle.median(FH.fill(st["after_speckle"], FH.classify(st["disp_l"], st["disp_r"], opt.lrcheck_thres),
+                                   opt.max_disparity))
+    before, after, fill = (bad_rate(m, gt, known) for m in (st["final"], refined, filled))
+    print(f"{scene}: bad > 1 px {100 * before:.2f} % -> refined {100 * after:.2f} % (hole filling {100 * fill:.2f} %)")
+    assert after < before
