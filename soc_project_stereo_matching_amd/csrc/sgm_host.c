@@ -14,6 +14,7 @@
 #include "sgm_device.h"
 
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,6 +26,7 @@
 enum { T_CENSUS, T_COST, T_AGGREGATE, T_SUM, T_WTA, T_LRCHECK, T_SPECKLE, T_MEDIAN, T_COUNT };
 /* event marks of a match: 0 .. T_COUNT bracket the stages in order; one more, M_SUM_BEGIN, sits right in front of the cost sum
  * BEHIND its waits for other streams' events, so that "sum" is the kernel's time and not the wait for the previous post pass */
+#define M_END T_COUNT
 #define M_SUM_BEGIN (T_COUNT + 1)
 #define MARKS_PER_MATCH (T_COUNT + 2)
 static const char* const k_stage_names[T_COUNT] = {"census", "cost", "aggregate", "sum", "wta", "lrcheck", "speckle", "median"};
@@ -32,6 +34,10 @@ static const char* const k_stage_names[T_COUNT] = {"census", "cost", "aggregate"
 /* reference direction order, SemiGlobalMatching.c:213-220 */
 static const int k_dir_dx[8] = {1, -1, 0, 0, 1, -1, 1, -1};
 static const int k_dir_dy[8] = {0, 0, 1, -1, 1, -1, -1, 1};
+
+/* A device or page-locked buffer the instance owns, its capacity in bytes beside it: buffers only grow, so a Reset with the same
+ * shape allocates nothing.  reserve() sizes them, free_device_buffers() walks k_buffers, nothing else allocates or frees one. */
+typedef struct { void* p; size_t cap; } sgm_buf;
 
 /* refinement parameters (sgm_set_refine) and the weight tables L_t of their iterations */
 typedef struct {
@@ -53,10 +59,8 @@ struct sgm_instance {
     int cu_first[3], cu_count[3];/* CUs per XCD of the main / sum / post stream (count 0: all CUs) */
     int up_rows;                 /* > 0: the last vertical sweep (directions (0,-1), (-1,-1), (1,-1)) runs fused with the cost sum and both WTAs
                                     (sgmd_upsum) wherever a match allows it: image rows per workgroup of that kernel */
-    void* d_up_scratch;          /* its hand-over rows, progress words and tickets */
-    size_t cap_up_scratch;
-    void* d_left_keep;           /* copy of the last fused match's left image(s): what re-creating the three planes needs (Q14, stage read-back) */
-    size_t cap_left_keep;
+    sgm_buf d_up_scratch;        /* its hand-over rows, progress words and tickets */
+    sgm_buf d_left_keep;         /* copy of the last fused match's left image(s): what re-creating the three planes needs (Q14, stage read-back) */
     unsigned up_gen;             /* launch counter of the fused kernel (its progress words carry it) */
     int last_up_rows;            /* rows per workgroup of the fused sweep in the LAST match, 0 if it ran the separate kernels */
     bool planes_partial;         /* the planes of the last frame lack the upward directions: materialize_S re-creates them first */
@@ -102,38 +106,30 @@ struct sgm_instance {
     double sum_ms[T_COUNT], min_ms[T_COUNT];
     long n_timed;
 
-    /* device buffers (capacity tracked so a Reset with the same shape allocates nothing) */
-    size_t cap_px, cap_planes, cap_S, cap_cost, cap_extras, cap_median;
+    /* device buffers (every sgm_buf of the instance is listed in k_buffers below) */
     int plane_row_lo, plane_rows;        /* image rows a direction plane has storage for: [plane_row_lo, plane_row_lo + plane_rows) --
                                             the whole frame normally, the tile's rows + one hand-over row either side in row-tile mode */
-    int cap_H, cap_row_cap;
     int tab_W, tab_H, tab_ndirs, tab_p1, tab_p2;   /* what the uploaded tables were built for */
-    void *d_left, *d_right, *d_census_l, *d_census_r, *d_census_r_alloc, *d_cost, *d_planes, *d_planes_alloc, *d_extras, *d_S;
-                                 /* d_planes = d_planes_alloc - plane_row_lo rows: kernels address cells by their frame
+    sgm_buf d_left, d_right, d_census_l, d_census_r_alloc, d_cost, d_planes_alloc, d_extras, d_S;
+    void *d_census_r, *d_planes; /* d_census_r = d_census_r_alloc + CENSUS_FRONT_SLACK;
+                                    d_planes = d_planes_alloc - plane_row_lo rows: kernels address cells by their frame
                                     position; d_cost and d_S exist only once somebody needs them (stage read-back, Q14, D > 256) */
-    void *d_disp, *d_disp_r, *d_labels, *d_sizes, *d_lut, *d_row_extras, *d_row_count;
-    void *d_snap_wta, *d_snap_lr, *d_snap_speckle, *d_totals, *d_median_scratch;
-    void *d_census64_l, *d_census64_r;   /* u64 census words of the wide windows (allocated on first use) */
-    size_t cap_census64;
-    void* d_census_need;                 /* row tiles: which 64 x 16 blocks of the census this instance reads (sgmd_census) */
-    size_t cap_census_need;
+    sgm_buf d_disp, d_disp_r, d_labels, d_sizes, d_lut, d_row_extras, d_row_count;
+    sgm_buf d_snap_wta, d_snap_lr, d_snap_speckle, d_totals, d_median_scratch;
+    sgm_buf d_census64_l, d_census64_r;  /* u64 census words of the wide windows (allocated on first use) */
+    sgm_buf d_census_need;               /* row tiles: which 64 x 16 blocks of the census this instance reads (sgmd_census) */
     int need_key[7];                     /* W, H, rows, dmin, Dp, ndirs the map was built for */
-    void *d_bgr, *d_depth, *h_bgr;       /* a test-platform frame's six colour planes, its depth map, pinned staging (first use) */
-    void *d_fill_class, *d_fill_map;     /* hole filling: u8 class map and the f32 ping-pong map ([B][H][W] each; only when asked for) */
-    size_t cap_fill;
-    void* conf_dst;                      /* matching confidence (extension): where the running match's cost sum stores it, NULL: nowhere */
-    void *d_conf, *h_conf;               /* device / page-locked staging of the host-pointer confidence entry points (first use) */
-    size_t cap_conf, cap_h_conf;
+    sgm_buf d_bgr, d_depth, h_bgr;       /* a test-platform frame's six colour planes, its depth map, pinned staging (first use) */
+    sgm_buf d_fill_class, d_fill_map;    /* hole filling: u8 class map and the f32 ping-pong map ([B][H][W] each; only when asked for) */
+    sgm_buf d_conf, h_conf;              /* device / page-locked staging of the host-pointer confidence entry points (first use) */
     refine_params rf_req, rf_eff;        /* refinement: the parameters last set (sgm_refine_disparity) and those of the matches */
-    void *d_rf_u, *d_rf_v, *d_rf_q;      /* its right-hand sides / solutions and the q_i of the line solves, f32 [B][H][W] each */
-    void* d_rf_conf;                     /* the confidence of a match whose caller did not ask for it, u16 [B][H][W] */
-    void* d_rf_guide[2];                 /* private copies of the reference image, used by turns (u8 [B][H][W] each) */
+    sgm_buf d_rf_u, d_rf_v, d_rf_q;      /* its right-hand sides / solutions and the q_i of the line solves, f32 [B][H][W] each */
+    sgm_buf d_rf_conf;                   /* the confidence of a match whose caller did not ask for it, u16 [B][H][W] */
+    sgm_buf d_rf_guide[2];               /* private copies of the reference image, used by turns (u8 [B][H][W] each) */
     int rf_turn;
-    size_t cap_refine;
-    size_t cap_bgr;
     size_t plane_bytes;
     /* pinned staging for the host-pointer entry point */
-    void *h_left, *h_right, *h_disp;
+    sgm_buf h_left, h_right, h_disp;
     /* sgm_match_async: a match whose result has been queued on the stream and not yet handed to the caller */
     bool async_pending;
     float* async_out;            /* caller's buffer the staged result still has to be copied to (NULL: it was pinned, the
@@ -144,6 +140,19 @@ struct sgm_instance {
      * to the caller while piece i + 1 is still on the bus (a 1242x375 map: 1.86 MB, ~40 us of DMA + ~90 us of memcpy in sequence otherwise) */
     void* ev_chunk[4];
     int async_chunks;
+};
+/* every buffer of the instance, for free_device_buffers: a new sgm_buf member gets its line here */
+#define DEVICE_BUF(member) {offsetof(struct sgm_instance, member), false}
+#define PINNED_BUF(member) {offsetof(struct sgm_instance, member), true}
+static const struct { size_t offset; bool pinned; } k_buffers[] = {
+    DEVICE_BUF(d_left), DEVICE_BUF(d_right), DEVICE_BUF(d_census_l), DEVICE_BUF(d_census_r_alloc), DEVICE_BUF(d_cost),
+    DEVICE_BUF(d_planes_alloc), DEVICE_BUF(d_extras), DEVICE_BUF(d_S), DEVICE_BUF(d_disp), DEVICE_BUF(d_disp_r), DEVICE_BUF(d_labels),
+    DEVICE_BUF(d_sizes), DEVICE_BUF(d_lut), DEVICE_BUF(d_row_extras), DEVICE_BUF(d_row_count), DEVICE_BUF(d_snap_wta),
+    DEVICE_BUF(d_snap_lr), DEVICE_BUF(d_snap_speckle), DEVICE_BUF(d_totals), DEVICE_BUF(d_median_scratch), DEVICE_BUF(d_census64_l),
+    DEVICE_BUF(d_census64_r), DEVICE_BUF(d_census_need), DEVICE_BUF(d_bgr), DEVICE_BUF(d_depth), PINNED_BUF(h_bgr),
+    DEVICE_BUF(d_up_scratch), DEVICE_BUF(d_left_keep), DEVICE_BUF(d_fill_class), DEVICE_BUF(d_fill_map), DEVICE_BUF(d_conf),
+    PINNED_BUF(h_conf), DEVICE_BUF(d_rf_u), DEVICE_BUF(d_rf_v), DEVICE_BUF(d_rf_q), DEVICE_BUF(d_rf_conf), DEVICE_BUF(d_rf_guide[0]),
+    DEVICE_BUF(d_rf_guide[1]), PINNED_BUF(h_left), PINNED_BUF(h_right), PINNED_BUF(h_disp),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -156,6 +165,9 @@ struct sgm_instance {
         fputc('\n', stderr);                       \
         return false;                              \
     } while (0)
+
+/* row-tile mode (sgm_set_rows): the instance computes rows [tile_begin, tile_end) of every frame */
+static bool row_tiled(const sgm_instance* s) { return s->tile_end != 0; }
 
 /* wait for everything the instance has queued (its stream and, with sgm_set_overlap_post, the post-pass stream) */
 static int sync_streams(sgm_instance* s)
@@ -273,43 +285,68 @@ sgm_instance* sgm_create(int device)
     return s;
 }
 
+/* ------------------------------------------------------------------ the instance's buffers */
+
+enum {
+    BUF_PINNED = 1,          /* page-locked host memory (a device buffer otherwise) */
+    BUF_ZERO = 2,            /* zero-filled on s->stream when (re-)allocated */
+    BUF_LAZY_DRAIN = 4       /* no drain in front of a first allocation, where there is nothing to free (every other buffer drains
+                                there too, as its hand-written block always did) */
+};
+typedef struct { sgm_buf* buf; size_t bytes; int flags; } buf_request;
+
+static bool buf_holds(const sgm_buf* b, size_t bytes) { return b->p && bytes <= b->cap; }
+
+static void buf_release(sgm_instance* s, sgm_buf* b, bool pinned)
+{
+    if (pinned) sgmd_free_pinned(s->device, b->p);
+    else sgmd_free(s->device, b->p);
+    b->p = NULL;
+    b->cap = 0;
+}
+
+/* The grow-only idiom, for n buffers that are sized together: nothing to do when all of them exist and are large enough.  Otherwise
+ * the instance's streams are drained once (queued work may use what is freed here) and each buffer that is missing or too small
+ * is freed and allocated anew; its capacity is recorded only once it is usable, a failure leaves it {NULL, 0} and ends the call. */
+static bool reserve_all(sgm_instance* s, const buf_request* req, int n, int flags)
+{
+    bool grow = false, drain = false;
+    for (int i = 0; i < n; ++i)
+        if (!buf_holds(req[i].buf, req[i].bytes)) {
+            grow = true;
+            if (req[i].buf->p || !((req[i].flags | flags) & BUF_LAZY_DRAIN)) drain = true;
+        }
+    if (!grow) return true;
+    if (drain) sync_streams(s);
+    for (int i = 0; i < n; ++i) {
+        sgm_buf* b = req[i].buf;
+        const int f = req[i].flags | flags;
+        if (buf_holds(b, req[i].bytes)) continue;
+        buf_release(s, b, f & BUF_PINNED);
+        const int rc = (f & BUF_PINNED) ? sgmd_alloc_pinned(s->device, &b->p, req[i].bytes) : sgmd_alloc(s->device, &b->p, req[i].bytes);
+        if (rc != 0) { b->p = NULL; return false; }
+        if ((f & BUF_ZERO) && sgmd_memset_async(s->device, s->stream, b->p, 0, req[i].bytes) != 0) {
+            buf_release(s, b, f & BUF_PINNED);
+            return false;
+        }
+        b->cap = req[i].bytes;
+    }
+    return true;
+}
+
+static bool reserve(sgm_instance* s, sgm_buf* b, size_t bytes, int flags)
+{
+    const buf_request one = {b, bytes, flags};
+    return reserve_all(s, &one, 1, 0);
+}
+
 static void free_device_buffers(sgm_instance* s)
 {
     s->d_census_r = NULL;                                        /* points into d_census_r_alloc */
     s->d_planes = NULL;                                          /* points into (or in front of) d_planes_alloc */
-    void** all[] = {&s->d_left, &s->d_right, &s->d_census_l, &s->d_census_r_alloc, &s->d_cost, &s->d_planes_alloc, &s->d_extras,
-                    &s->d_S, &s->d_disp, &s->d_disp_r, &s->d_labels, &s->d_sizes, &s->d_lut, &s->d_row_extras,
-                    &s->d_row_count, &s->d_snap_wta, &s->d_snap_lr, &s->d_snap_speckle, &s->d_totals,
-                    &s->d_median_scratch, &s->d_census64_l, &s->d_census64_r, &s->d_bgr, &s->d_depth, &s->d_census_need,
-                    &s->d_up_scratch, &s->d_left_keep};
-    for (size_t i = 0; i < sizeof all / sizeof all[0]; ++i) {
-        sgmd_free(s->device, *all[i]);
-        *all[i] = NULL;
-    }
-    if (s->d_fill_class) sgmd_free(s->device, s->d_fill_class);
-    if (s->d_fill_map) sgmd_free(s->device, s->d_fill_map);
-    s->d_fill_class = s->d_fill_map = NULL;
-    s->cap_fill = 0;
-    if (s->d_conf) sgmd_free(s->device, s->d_conf);
-    if (s->h_conf) sgmd_free_pinned(s->device, s->h_conf);
-    s->d_conf = s->h_conf = NULL;
-    s->cap_conf = s->cap_h_conf = 0;
-    void** rf[] = {&s->d_rf_u, &s->d_rf_v, &s->d_rf_q, &s->d_rf_conf, &s->d_rf_guide[0], &s->d_rf_guide[1]};
-    for (size_t i = 0; i < sizeof rf / sizeof rf[0]; ++i) {
-        if (*rf[i]) sgmd_free(s->device, *rf[i]);
-        *rf[i] = NULL;
-    }
-    s->cap_refine = 0;
-    sgmd_free_pinned(s->device, s->h_left);
-    sgmd_free_pinned(s->device, s->h_right);
-    sgmd_free_pinned(s->device, s->h_disp);
-    sgmd_free_pinned(s->device, s->h_bgr);
-    s->h_left = s->h_right = s->h_disp = s->h_bgr = NULL;
-    s->cap_px = s->cap_planes = s->cap_S = s->cap_cost = s->cap_extras = s->cap_median = s->cap_census64 = s->cap_bgr = 0;
-    s->cap_census_need = 0;
-    s->cap_up_scratch = s->cap_left_keep = 0;
+    for (size_t i = 0; i < sizeof k_buffers / sizeof k_buffers[0]; ++i)
+        buf_release(s, (sgm_buf*)((char*)s + k_buffers[i].offset), k_buffers[i].pinned);
     s->need_key[0] = 0;
-    s->cap_H = s->cap_row_cap = 0;
     s->tab_W = s->tab_H = 0;
 }
 
@@ -533,7 +570,7 @@ static bool upload_census_need(sgm_instance* s)
 {
     const int W = s->g.W, H = s->g.H;
     const int key[7] = {W, H, s->g.row_begin, s->g.row_end, s->g.dmin, s->g.Dp, s->paths.ndirs};
-    if (s->d_census_need && memcmp(key, s->need_key, sizeof key) == 0) return true;
+    if (s->d_census_need.p && memcmp(key, s->need_key, sizeof key) == 0) return true;
     int bx, by;
     sgmd_census_blocks(&s->g, &bx, &by);
     const size_t n = (size_t)bx * by;
@@ -556,15 +593,7 @@ static bool upload_census_need(sgm_instance* s)
         }
     }
     free(pix);
-    bool ok = true;
-    if (n > s->cap_census_need || !s->d_census_need) {
-        sync_streams(s);
-        sgmd_free(s->device, s->d_census_need);
-        s->d_census_need = NULL;
-        ok = sgmd_alloc(s->device, &s->d_census_need, n) == 0;
-        s->cap_census_need = ok ? n : 0;
-    }
-    ok = ok && sgmd_h2d_async(s->device, s->stream, s->d_census_need, need, n) == 0 && sync_streams(s) == 0;
+    const bool ok = reserve(s, &s->d_census_need, n, 0) && sgmd_h2d_async(s->device, s->stream, s->d_census_need.p, need, n) == 0 && sync_streams(s) == 0;
     free(need);
     if (!ok) FAIL("uploading the census block map failed");
     memcpy(s->need_key, key, sizeof key);
@@ -608,21 +637,13 @@ static bool upload_tables(sgm_instance* s)
             count[r]++;
         }
 
-    bool ok = true;
-    if (cap > s->cap_row_cap || H > s->cap_H || !s->d_row_extras) {
-        sgmd_free(s->device, s->d_row_extras);
-        sgmd_free(s->device, s->d_row_count);
-        s->d_row_extras = s->d_row_count = NULL;
-        ok = sgmd_alloc(s->device, &s->d_row_extras, sizeof *table * (size_t)H * cap) == 0 &&
-             sgmd_alloc(s->device, &s->d_row_count, sizeof(int) * (size_t)H) == 0;
-        s->cap_row_cap = cap;
-        s->cap_H = H;
-    }
+    /* tables that are replaced may still be read by queued work; the first ones are not */
+    const buf_request tables[] = {{&s->d_row_extras, sizeof *table * (size_t)H * cap, 0}, {&s->d_row_count, sizeof(int) * (size_t)H, 0}};
     s->row_cap = cap;
     /* plain blocking-safe uploads: the tables live on the host stack/heap only until the sync below */
-    ok = ok && sgmd_h2d_async(s->device, s->stream, s->d_row_extras, table, sizeof *table * (size_t)H * cap) == 0 &&
-         sgmd_h2d_async(s->device, s->stream, s->d_row_count, count, sizeof(int) * (size_t)H) == 0 &&
-         sgmd_h2d_async(s->device, s->stream, s->d_lut, lut, sizeof lut) == 0 &&
+    const bool ok = reserve_all(s, tables, 2, BUF_LAZY_DRAIN) && sgmd_h2d_async(s->device, s->stream, s->d_row_extras.p, table, sizeof *table * (size_t)H * cap) == 0 &&
+         sgmd_h2d_async(s->device, s->stream, s->d_row_count.p, count, sizeof(int) * (size_t)H) == 0 &&
+         sgmd_h2d_async(s->device, s->stream, s->d_lut.p, lut, sizeof lut) == 0 &&
          sync_streams(s) == 0;
     free(table); free(visits); free(count); free(pix);
     if (!ok) FAIL("uploading path tables failed");
@@ -636,62 +657,48 @@ static bool ensure_buffers(sgm_instance* s)
 {
     const int dev = s->device;
     const size_t px = (size_t)s->g.B * s->g.W * s->g.H;          /* all frames of the batch, frame-major */
-    int rc = 0;
-    if (px > s->cap_px || !s->d_disp) {
+    if (!buf_holds(&s->d_disp, px * 4)) {
+        /* the per-pixel set grows: everything the instance owns goes (the buffers sized below and in sgm_initialize come back at
+         * once, S, the cost volume and the others on their first use).
+         * The aggregation kernel reads census-right up to dmin + Dp - 1 words left of a row start (masked to 127
+         * afterwards); give the buffer that much readable slack in front, sized for the largest options */
+        const buf_request images[] = {{&s->d_left, px, 0}, {&s->d_right, px, 0}, {&s->d_census_l, px * 4, 0},
+                                      {&s->d_census_r_alloc, CENSUS_FRONT_SLACK + px * 4, 0}};
+        const buf_request maps[] = {{&s->d_disp, px * 4, 0}, {&s->d_disp_r, px * 4, 0}, {&s->d_labels, px * 4, 0}, {&s->d_sizes, px * 4, 0},
+                                    {&s->d_totals, px * 4, 0}, {&s->d_lut, 512, 0}, {&s->d_snap_wta, px * 4, 0}, {&s->d_snap_lr, px * 4, 0},
+                                    {&s->d_snap_speckle, px * 4, 0}, {&s->h_left, px, BUF_PINNED}, {&s->h_right, px, BUF_PINNED},
+                                    {&s->h_disp, px * 4, BUF_PINNED}};
         sync_streams(s);
         /* the census words of earlier frames outlive a re-allocation (reference_statics): set the old buffers aside */
-        void *old_l = s->d_census_l, *old_r_alloc = s->d_census_r_alloc;
-        const size_t old_px = s->cap_px;
-        s->d_census_l = s->d_census_r_alloc = NULL;
+        const sgm_buf old_l = s->d_census_l, old_r = s->d_census_r_alloc;
+        s->d_census_l = s->d_census_r_alloc = (sgm_buf){NULL, 0};
         free_device_buffers(s);
-        rc |= sgmd_alloc(dev, &s->d_left, px);
-        rc |= sgmd_alloc(dev, &s->d_right, px);
-        rc |= sgmd_alloc(dev, &s->d_census_l, px * 4);
-        /* the aggregation kernel reads census-right up to dmin + Dp - 1 words left of a row start (masked to 127
-         * afterwards); give the buffer that much readable slack in front, sized for the largest options */
-        rc |= sgmd_alloc(dev, &s->d_census_r_alloc, CENSUS_FRONT_SLACK + px * 4);
-        if (rc == 0) s->d_census_r = (char*)s->d_census_r_alloc + CENSUS_FRONT_SLACK;
+        int rc = reserve_all(s, images, 4, BUF_LAZY_DRAIN) ? 0 : -1;
+        if (rc == 0) s->d_census_r = (char*)s->d_census_r_alloc.p + CENSUS_FRONT_SLACK;
         /* zero like the reference's statics; then the words earlier frames left, at their linear indices */
-        if (rc == 0) rc |= sgmd_memset_async(dev, s->stream, s->d_census_l, 0, px * 4);
-        if (rc == 0) rc |= sgmd_memset_async(dev, s->stream, s->d_census_r_alloc, 0, CENSUS_FRONT_SLACK + px * 4);
-        if (rc == 0 && s->reference_statics && old_l && old_r_alloc && old_px) {
-            rc |= sgmd_d2d_async(dev, s->stream, s->d_census_l, old_l, old_px * 4);
-            rc |= sgmd_d2d_async(dev, s->stream, s->d_census_r, (char*)old_r_alloc + CENSUS_FRONT_SLACK, old_px * 4);
+        if (rc == 0) rc |= sgmd_memset_async(dev, s->stream, s->d_census_l.p, 0, px * 4);
+        if (rc == 0) rc |= sgmd_memset_async(dev, s->stream, s->d_census_r_alloc.p, 0, CENSUS_FRONT_SLACK + px * 4);
+        if (rc == 0 && s->reference_statics && old_l.p && old_r.p) {
+            rc |= sgmd_d2d_async(dev, s->stream, s->d_census_l.p, old_l.p, old_l.cap);
+            rc |= sgmd_d2d_async(dev, s->stream, s->d_census_r, (char*)old_r.p + CENSUS_FRONT_SLACK, old_l.cap);
         }
         if (rc == 0) rc |= sgmd_stream_sync(dev, s->stream);
-        sgmd_free(dev, old_l);
-        sgmd_free(dev, old_r_alloc);
-        rc |= sgmd_alloc(dev, &s->d_disp, px * 4);
-        rc |= sgmd_alloc(dev, &s->d_disp_r, px * 4);
-        rc |= sgmd_alloc(dev, &s->d_labels, px * 4);
-        rc |= sgmd_alloc(dev, &s->d_sizes, px * 4);
-        rc |= sgmd_alloc(dev, &s->d_totals, px * 4);
-        rc |= sgmd_alloc(dev, &s->d_lut, 512);
-        rc |= sgmd_alloc(dev, &s->d_snap_wta, px * 4);
-        rc |= sgmd_alloc(dev, &s->d_snap_lr, px * 4);
-        rc |= sgmd_alloc(dev, &s->d_snap_speckle, px * 4);
-        rc |= sgmd_alloc_pinned(dev, &s->h_left, px);
-        rc |= sgmd_alloc_pinned(dev, &s->h_right, px);
-        rc |= sgmd_alloc_pinned(dev, &s->h_disp, px * 4);
-        if (rc != 0) { free_device_buffers(s); FAIL("device allocation failed for %dx%dx%d", s->g.W, s->g.H, s->g.D); }
-        s->cap_px = px;
+        sgmd_free(dev, old_l.p);
+        sgmd_free(dev, old_r.p);
+        if (rc != 0 || !reserve_all(s, maps, 12, BUF_LAZY_DRAIN)) {
+            free_device_buffers(s);
+            FAIL("device allocation failed for %dx%dx%d", s->g.W, s->g.H, s->g.D);
+        }
     }
-    const bool tiled = s->tile_end != 0;
+    const bool tiled = row_tiled(s);
     s->plane_row_lo = tiled && s->g.row_begin > 0 ? s->g.row_begin - 1 : 0;
     const int row_hi = tiled && s->g.row_end < s->g.H ? s->g.row_end + 1 : s->g.H;
     s->plane_rows = row_hi - s->plane_row_lo;
     s->plane_bytes = (size_t)s->plane_rows * s->g.W * s->g.Dp;
     const size_t need = (size_t)s->g.B * 8 * s->plane_bytes;
-    if (need > s->cap_planes || !s->d_planes_alloc) {
-        sync_streams(s);
-        sgmd_free(dev, s->d_planes_alloc);
-        s->d_planes_alloc = NULL;
-        s->cap_planes = 0;
-        if (sgmd_alloc(dev, &s->d_planes_alloc, need) != 0)
-            FAIL("device allocation failed for the path-cost planes of %dx%dx%d (%zu bytes)", s->g.W, s->g.H, s->g.D, need);
-        s->cap_planes = need;
-    }
-    s->d_planes = (void*)((uintptr_t)s->d_planes_alloc - (uintptr_t)s->plane_row_lo * s->g.W * s->g.Dp);
+    if (!reserve(s, &s->d_planes_alloc, need, 0))
+        FAIL("device allocation failed for the path-cost planes of %dx%dx%d (%zu bytes)", s->g.W, s->g.H, s->g.D, need);
+    s->d_planes = (void*)((uintptr_t)s->d_planes_alloc.p - (uintptr_t)s->plane_row_lo * s->g.W * s->g.Dp);
     return true;
 }
 
@@ -701,71 +708,41 @@ static bool ensure_buffers(sgm_instance* s)
 static int ensure_S(sgm_instance* s)
 {
     const size_t need = (size_t)s->g.B * s->g.W * s->g.H * s->g.Dp * 2;
-    if (s->d_S && need <= s->cap_S) return 0;
-    sync_streams(s);
-    sgmd_free(s->device, s->d_S);
-    s->d_S = NULL;
-    s->cap_S = 0;
-    int rc = sgmd_alloc(s->device, &s->d_S, need);
-    if (rc == 0) rc = sgmd_memset_async(s->device, s->stream, s->d_S, 0, need);
-    if (rc == 0 && s->sum_stream) rc = sgmd_stream_sync(s->device, s->stream);   /* the cost sum may run on another stream */
-    if (rc == 0) s->cap_S = need;
-    else fprintf(stderr, "sgm_mi355x: device allocation failed for the aggregated-cost volume (%zu bytes)\n", need);
-    return rc;
+    if (buf_holds(&s->d_S, need)) return 0;
+    if (reserve(s, &s->d_S, need, BUF_ZERO) &&
+        (!s->sum_stream || sgmd_stream_sync(s->device, s->stream) == 0))   /* the cost sum may run on another stream */
+        return 0;
+    fprintf(stderr, "sgm_mi355x: device allocation failed for the aggregated-cost volume (%zu bytes)\n", need);
+    return -1;
 }
 
 static int ensure_cost(sgm_instance* s)
 {
     const size_t need = (size_t)s->g.B * s->g.W * s->g.H * s->g.Dp;
-    if (s->d_cost && need <= s->cap_cost) return 0;
-    sync_streams(s);
-    sgmd_free(s->device, s->d_cost);
-    s->d_cost = NULL;
-    s->cap_cost = 0;
-    const int rc = sgmd_alloc(s->device, &s->d_cost, need);
-    if (rc == 0) s->cap_cost = need;
-    else fprintf(stderr, "sgm_mi355x: device allocation failed for the cost volume (%zu bytes)\n", need);
-    return rc;
+    if (reserve(s, &s->d_cost, need, 0)) return 0;
+    fprintf(stderr, "sgm_mi355x: device allocation failed for the cost volume (%zu bytes)\n", need);
+    return -1;
 }
 
 /* the class map and the ping-pong map of the hole filling, [B][H][W] each */
 static int ensure_fill(sgm_instance* s)
 {
     const size_t px = (size_t)s->g.B * s->g.W * s->g.H;
-    if (s->d_fill_map && px <= s->cap_fill) return 0;
-    sync_streams(s);
-    sgmd_free(s->device, s->d_fill_class);
-    sgmd_free(s->device, s->d_fill_map);
-    s->d_fill_class = s->d_fill_map = NULL;
-    s->cap_fill = 0;
-    if (sgmd_alloc(s->device, &s->d_fill_class, px) != 0 || sgmd_alloc(s->device, &s->d_fill_map, px * sizeof(float)) != 0) {
-        fprintf(stderr, "sgm_mi355x: device allocation failed for the hole-filling maps (%zu pixels)\n", px);
-        return -1;
-    }
-    s->cap_fill = px;
-    return 0;
+    const buf_request maps[] = {{&s->d_fill_class, px, 0}, {&s->d_fill_map, px * sizeof(float), 0}};
+    if (reserve_all(s, maps, 2, 0)) return 0;
+    fprintf(stderr, "sgm_mi355x: device allocation failed for the hole-filling maps (%zu pixels)\n", px);
+    return -1;
 }
 
 /* the maps of the refinement, [B][H][W] each: U, V, Q (f32), the internal confidence (u16), two guide copies (u8) */
 static int ensure_refine(sgm_instance* s)
 {
     const size_t px = (size_t)s->g.B * s->g.W * s->g.H;
-    if (s->d_rf_q && px <= s->cap_refine) return 0;
-    sync_streams(s);
-    void** rf[] = {&s->d_rf_u, &s->d_rf_v, &s->d_rf_q, &s->d_rf_conf, &s->d_rf_guide[0], &s->d_rf_guide[1]};
-    const size_t elem[] = {4, 4, 4, 2, 1, 1};
-    s->cap_refine = 0;
-    for (size_t i = 0; i < sizeof rf / sizeof rf[0]; ++i) {
-        sgmd_free(s->device, *rf[i]);
-        *rf[i] = NULL;
-    }
-    for (size_t i = 0; i < sizeof rf / sizeof rf[0]; ++i)
-        if (sgmd_alloc(s->device, rf[i], px * elem[i]) != 0) {
-            fprintf(stderr, "sgm_mi355x: device allocation failed for the refinement maps (%zu pixels)\n", px);
-            return -1;
-        }
-    s->cap_refine = px;
-    return 0;
+    const buf_request maps[] = {{&s->d_rf_u, px * 4, 0}, {&s->d_rf_v, px * 4, 0}, {&s->d_rf_q, px * 4, 0}, {&s->d_rf_conf, px * 2, 0},
+                                {&s->d_rf_guide[0], px, 0}, {&s->d_rf_guide[1], px, 0}};
+    if (reserve_all(s, maps, 6, 0)) return 0;
+    fprintf(stderr, "sgm_mi355x: device allocation failed for the refinement maps (%zu pixels)\n", px);
+    return -1;
 }
 
 /* the 2 T passes of the refinement on `disp`, in place (include/sgm_mi355x.h, sgm_set_refine) */
@@ -773,10 +750,10 @@ static int refine_passes(sgm_instance* s, void* st, void* disp, const void* conf
 {
     int rc = 0;
     for (int t = 0; rc == 0 && t < p->iters; ++t) {
-        rc = sgmd_refine_pass(s->device, st, &s->g, 0, p->tab[t], guide, t == 0 ? disp : NULL, t == 0 ? conf : NULL, s->d_rf_u,
-                              s->d_rf_v, s->d_rf_q, t == 0, 0, 0, NULL);
+        rc = sgmd_refine_pass(s->device, st, &s->g, 0, p->tab[t], guide, t == 0 ? disp : NULL, t == 0 ? conf : NULL, s->d_rf_u.p,
+                              s->d_rf_v.p, s->d_rf_q.p, t == 0, 0, 0, NULL);
         if (rc == 0)
-            rc = sgmd_refine_pass(s->device, st, &s->g, 1, p->tab[t], guide, NULL, NULL, s->d_rf_u, s->d_rf_v, s->d_rf_q, 0,
+            rc = sgmd_refine_pass(s->device, st, &s->g, 1, p->tab[t], guide, NULL, NULL, s->d_rf_u.p, s->d_rf_v.p, s->d_rf_q.p, 0,
                                   t == p->iters - 1, t == p->iters - 1 ? p->keep_invalid : 0, disp);
     }
     return rc;
@@ -790,11 +767,11 @@ static int fill_passes(sgm_instance* s, void* st, void* disp, const void* cls)
     const size_t bytes = (size_t)s->g.B * s->g.W * s->g.H * sizeof(float);
     int rc = 0;
     if (cls) {
-        rc = sgmd_fill_pass(s->device, st, &s->g, R, disp, s->d_fill_map, cls, 1);                  /* occluded */
-        if (rc == 0) rc = sgmd_fill_pass(s->device, st, &s->g, R, s->d_fill_map, disp, cls, 2);     /* mismatched */
+        rc = sgmd_fill_pass(s->device, st, &s->g, R, disp, s->d_fill_map.p, cls, 1);                  /* occluded */
+        if (rc == 0) rc = sgmd_fill_pass(s->device, st, &s->g, R, s->d_fill_map.p, disp, cls, 2);     /* mismatched */
     }
-    if (rc == 0) rc = sgmd_fill_pass(s->device, st, &s->g, R, disp, s->d_fill_map, NULL, 3);        /* every hole left */
-    if (rc == 0) rc = sgmd_d2d_async(s->device, st, disp, s->d_fill_map, bytes);
+    if (rc == 0) rc = sgmd_fill_pass(s->device, st, &s->g, R, disp, s->d_fill_map.p, NULL, 3);        /* every hole left */
+    if (rc == 0) rc = sgmd_d2d_async(s->device, st, disp, s->d_fill_map.p, bytes);
     return rc;
 }
 
@@ -844,7 +821,7 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
     s->g.dmin = option->min_disparity;
     s->g.B = s->batch;
     s->g.row_begin = 0; s->g.row_end = height;
-    if (s->tile_end != 0) {
+    if (row_tiled(s)) {
         if (s->tile_begin < 0 || s->tile_begin >= s->tile_end || s->tile_end > height)
             FAIL("row tile [%d,%d) does not fit a frame of %d rows", s->tile_begin, s->tile_end, height);
         s->g.row_begin = s->tile_begin; s->g.row_end = s->tile_end;
@@ -874,10 +851,10 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
     s->need_plane_memset = !s->paths.ghost_zero;
 
     s->fill_on = false;
-    if (s->fill_req && s->tile_end != 0)
+    if (s->fill_req && row_tiled(s))
         FAIL("hole filling (sgm_set_fill_holes) works on whole frames: not available in row-tile mode (sgm_set_rows)");
     s->refine_on = false;
-    if (s->refine_req && s->tile_end != 0)
+    if (s->refine_req && row_tiled(s))
         FAIL("the refinement (sgm_set_refine) works on whole frames: not available in row-tile mode (sgm_set_rows)");
     if (s->refine_req && s->fill_req)
         FAIL("the refinement (sgm_set_refine) and hole filling (sgm_set_fill_holes) do not combine: the refinement fills by itself, "
@@ -894,24 +871,10 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
     }
     /* extras: 4 anomalous lines x H steps x Dp bytes */
     const size_t extras_bytes = (size_t)s->g.B * 4 * height * s->g.Dp;
-    if (extras_bytes > s->cap_extras || !s->d_extras) {
-        sync_streams(s);
-        sgmd_free(s->device, s->d_extras);
-        s->d_extras = NULL;
-        if (sgmd_alloc(s->device, &s->d_extras, extras_bytes) != 0) FAIL("device allocation failed (extras)");
-        s->cap_extras = extras_bytes;
-    }
-    /* median scratch depends on W and H separately (64-row groups x time slots) */
-    const size_t median_bytes = sgmd_median_scratch_bytes(&s->g);
-    if (median_bytes > s->cap_median || !s->d_median_scratch) {
-        sync_streams(s);
-        sgmd_free(s->device, s->d_median_scratch);
-        s->d_median_scratch = NULL;
-        if (sgmd_alloc(s->device, &s->d_median_scratch, median_bytes) != 0) FAIL("device allocation failed (median scratch)");
-        /* the granule rows between the bands of a tall frame carry a generation tag: start from "never written" */
-        if (sgmd_memset_async(s->device, s->stream, s->d_median_scratch, 0, median_bytes) != 0) FAIL("clearing the median scratch failed");
-        s->cap_median = median_bytes;
-    }
+    if (!reserve(s, &s->d_extras, extras_bytes, 0)) FAIL("device allocation failed (extras)");
+    /* median scratch depends on W and H separately (64-row groups x time slots); the granule rows between the bands of a tall
+     * frame carry a generation tag: start from "never written" */
+    if (!reserve(s, &s->d_median_scratch, sgmd_median_scratch_bytes(&s->g), BUF_ZERO)) FAIL("device allocation failed (median scratch)");
     /* a Reset with unchanged shape and penalties (the per-frame case, Q14) re-uploads nothing */
     if (s->tab_W != width || s->tab_H != height || s->tab_ndirs != s->paths.ndirs || s->tab_p1 != option->p1 ||
         s->tab_p2 != option->p2_init) {
@@ -920,7 +883,7 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
         s->tab_p1 = option->p1; s->tab_p2 = option->p2_init;
     }
 
-    if (s->tile_end != 0 && !s->census_w && !upload_census_need(s)) return false;
+    if (row_tiled(s) && !s->census_w && !upload_census_need(s)) return false;
 
     s->s_is_zero = true;                                         /* .c:57: memset of cost_aggr, done lazily */
     s->s_pending = false;
@@ -936,7 +899,7 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
      * costs latency) */
     s->up_rows = 0;
     s->planes_partial = false;
-    if (s->fused_wta && s->tile_end == 0 && !s->census_w && s->paths.ndirs == 8 && option->p1 >= 0 && s->row_cap <= 8 &&
+    if (s->fused_wta && !row_tiled(s) && !s->census_w && s->paths.ndirs == 8 && option->p1 >= 0 && s->row_cap <= 8 &&
         (s->env_upsum >= 0 ? s->env_upsum != 0 : UPSUM_DEFAULT && s->batch >= 2))
         s->up_rows = sgmd_upsum_rows(&s->g);
     if (s->up_rows > 0 && s->env_upsum_rows >= 1 && s->env_upsum_rows < s->up_rows) s->up_rows = s->env_upsum_rows;
@@ -952,14 +915,31 @@ bool sgm_reset(sgm_instance* s, uint16_t width, uint16_t height, const SGMOption
     return sgm_initialize(s, width, height, option);
 }
 
+/* mark T_x: stage x begins (and the one before it has ended); M_END: the match is queued to its end */
 static void mark_on(sgm_instance* s, void* stream, int idx)
 {
     if (s->timing && s->timer) sgmd_timer_mark(s->device, s->timer, stream, s->ring_next * MARKS_PER_MATCH + idx);
 }
 static void mark(sgm_instance* s, int idx) { mark_on(s, s->stream, idx); }
 
-static int sweep_mask(const sgm_instance* s, int forward);
-static int launch_aggregation(sgm_instance* s, const sgmd_paths* paths, const void* d_left);
+/* .c:94: the path aggregation, from the census images or (wide windows) from the cost volume */
+static int launch_aggregation(sgm_instance* s, const sgmd_paths* paths, const void* d_left)
+{
+    if (s->census_w)
+        return sgmd_aggregate_volume(s->device, s->stream, &s->g, paths, d_left, s->d_cost.p, s->d_lut.p, s->d_planes, s->plane_bytes,
+                                     s->d_extras.p);
+    return sgmd_aggregate(s->device, s->stream, &s->g, paths, d_left, s->d_census_l.p, s->d_census_r, s->d_lut.p, s->d_planes,
+                          s->plane_bytes, s->d_extras.p);
+}
+
+/* the directions of one vertical sense (forward: downwards) */
+static int sweep_mask(const sgm_instance* s, int forward)
+{
+    int m = 0;
+    for (int d = 0; d < s->paths.ndirs; ++d)
+        if (s->paths.dy[d] == (forward ? 1 : -1)) m |= 1 << d;
+    return m;
+}
 
 /* d_S <- [d_S +] sum of the planes of the last frame, if the fused kernel skipped that store */
 static int materialize_S(sgm_instance* s)
@@ -977,20 +957,21 @@ static int materialize_S(sgm_instance* s)
         p.dir_mask = sweep_mask(s, 0);
         p.run_anom = 0;
         p.up_fused = 0;
-        if (launch_aggregation(s, &p, s->d_left_keep) != 0) return -1;
+        if (launch_aggregation(s, &p, s->d_left_keep.p) != 0) return -1;
         s->planes_partial = false;
     }
     /* the left-view WTA this kernel also produces goes to a dead scratch map (speckle labels) */
-    const int rc = sgmd_sum_wta(s->device, s->stream, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras,
-                                s->d_row_extras, s->d_row_count, s->row_cap, s->s_pending_accumulate ? 1 : 0, s->d_S, 0, 0.0f,
-                                s->d_labels);
+    const int rc = sgmd_sum_wta(s->device, s->stream, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras.p,
+                                s->d_row_extras.p, s->d_row_count.p, s->row_cap, s->s_pending_accumulate ? 1 : 0, s->d_S.p, 0, 0.0f,
+                                s->d_labels.p);
     if (rc == 0) s->s_pending = false;                           /* a failed launch leaves the sum pending */
     return rc;
 }
 
-/* .c:94 (sum over the directions), .c:99 and .c:105 (both ComputeDisparity calls).  The Q14 bookkeeping (s_is_zero,
+/* .c:94 (sum over the directions), .c:99 and .c:105 (both ComputeDisparity calls); conf: where the reference view's matching
+ * confidence goes (extension), NULL: nowhere.  The Q14 bookkeeping (s_is_zero,
  * s_pending) changes only when every launch of the stage was accepted. */
-static int sum_and_wta(sgm_instance* s, void* st, void* d_out, bool with_marks)
+static int sum_and_wta(sgm_instance* s, void* st, void* d_out, void* conf, bool with_marks)
 {
     const SGMOption* o = &s->opt;
     const int accumulate = s->s_is_zero ? 0 : 1;                 /* Q14 */
@@ -998,36 +979,35 @@ static int sum_and_wta(sgm_instance* s, void* st, void* d_out, bool with_marks)
     const float keep = 1 - o->uniqueness_ratio;
     int rc;
     const bool want_right = o->is_check_lr || s->reference_view;
-    void* const conf = s->conf_dst;                              /* the reference view's confidence (extension), or NULL */
     if ((!s->fused_wta || accumulate || s->keep_stages) && ensure_S(s) != 0) return -1;
     if (s->fused_wta) {
         const int store = s->keep_stages ? 1 : 0;
         if (conf)
-            rc = sgmd_sum_wta_lr_conf(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras, s->d_row_extras,
-                                      s->d_row_count, s->row_cap, accumulate, store, want_right ? 1 : 0, s->d_S, uniq, keep, d_out,
-                                      s->d_disp_r, conf, s->reference_view);
+            rc = sgmd_sum_wta_lr_conf(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras.p, s->d_row_extras.p,
+                                      s->d_row_count.p, s->row_cap, accumulate, store, want_right ? 1 : 0, s->d_S.p, uniq, keep, d_out,
+                                      s->d_disp_r.p, conf, s->reference_view);
         else
-            rc = sgmd_sum_wta_lr(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras,
-                                 s->d_row_extras, s->d_row_count, s->row_cap, accumulate, store, want_right ? 1 : 0, s->d_S,
-                                 uniq, keep, d_out, s->d_disp_r);
+            rc = sgmd_sum_wta_lr(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras.p,
+                                 s->d_row_extras.p, s->d_row_count.p, s->row_cap, accumulate, store, want_right ? 1 : 0, s->d_S.p,
+                                 uniq, keep, d_out, s->d_disp_r.p);
         if (rc != 0) return rc;
         s->s_pending = !store;
         s->s_pending_accumulate = accumulate != 0;
-        if (with_marks) mark_on(s, st, 4);
+        if (with_marks) mark_on(s, st, T_WTA);
     } else {
         if (conf && !s->reference_view)
-            rc = sgmd_sum_wta_conf(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras,
-                                   s->d_row_extras, s->d_row_count, s->row_cap, accumulate, s->d_S, uniq, keep, d_out, conf);
+            rc = sgmd_sum_wta_conf(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras.p,
+                                   s->d_row_extras.p, s->d_row_count.p, s->row_cap, accumulate, s->d_S.p, uniq, keep, d_out, conf);
         else
-            rc = sgmd_sum_wta(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras,
-                              s->d_row_extras, s->d_row_count, s->row_cap, accumulate, s->d_S, uniq, keep, d_out);
+            rc = sgmd_sum_wta(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras.p,
+                              s->d_row_extras.p, s->d_row_count.p, s->row_cap, accumulate, s->d_S.p, uniq, keep, d_out);
         if (rc != 0) return rc;
         /* d_S now holds this frame's sum whatever happens next */
         s->s_pending = false;
         s->s_is_zero = false;
-        if (with_marks) mark_on(s, st, 4);
-        if (conf && s->reference_view) rc = sgmd_wta_right_conf(s->device, st, &s->g, s->d_S, uniq, keep, s->d_disp_r, conf);
-        else if (want_right) rc = sgmd_wta_right(s->device, st, &s->g, s->d_S, uniq, keep, s->d_disp_r);
+        if (with_marks) mark_on(s, st, T_WTA);
+        if (conf && s->reference_view) rc = sgmd_wta_right_conf(s->device, st, &s->g, s->d_S.p, uniq, keep, s->d_disp_r.p, conf);
+        else if (want_right) rc = sgmd_wta_right(s->device, st, &s->g, s->d_S.p, uniq, keep, s->d_disp_r.p);
         if (rc != 0) return rc;
     }
     s->s_is_zero = false;
@@ -1038,42 +1018,25 @@ static int sum_and_wta(sgm_instance* s, void* st, void* d_out, bool with_marks)
 static int prepare_costs(sgm_instance* s, const void* d_left, const void* d_right)
 {
     if (!s->census_w) {
-        const bool tiled = s->tile_end != 0 && !s->keep_stages;          /* stage read-back wants the whole census */
+        const bool tiled = row_tiled(s) && !s->keep_stages;          /* stage read-back wants the whole census */
         if (tiled && getenv("SGM_DEBUG_POISON_CENSUS")) {                /* tests: a read of a skipped block must not go unnoticed */
             const size_t bytes = (size_t)s->g.B * s->g.W * s->g.H * 4;
-            if (sgmd_memset_async(s->device, s->stream, s->d_census_l, 0xA5, bytes) != 0 ||
+            if (sgmd_memset_async(s->device, s->stream, s->d_census_l.p, 0xA5, bytes) != 0 ||
                 sgmd_memset_async(s->device, s->stream, s->d_census_r, 0x5A, bytes) != 0) return -1;
         }
         /* the reference's own boundary, one whole frame per match: the unwritten census words stay as they are (Q3) */
-        const int keep_border = s->reference_statics && s->g.B == 1 && s->tile_end == 0;
-        return sgmd_census(s->device, s->stream, &s->g, d_left, d_right, s->d_census_l, s->d_census_r, tiled ? s->d_census_need : NULL,
+        const int keep_border = s->reference_statics && s->g.B == 1 && !row_tiled(s);
+        return sgmd_census(s->device, s->stream, &s->g, d_left, d_right, s->d_census_l.p, s->d_census_r, tiled ? s->d_census_need.p : NULL,
                            keep_border);
     }
     const size_t need = (size_t)s->g.B * s->g.W * s->g.H * 8;
-    if (need > s->cap_census64 || !s->d_census64_l) {
-        sync_streams(s);
-        sgmd_free(s->device, s->d_census64_l);
-        sgmd_free(s->device, s->d_census64_r);
-        s->d_census64_l = s->d_census64_r = NULL;
-        s->cap_census64 = 0;
-        if (sgmd_alloc(s->device, &s->d_census64_l, need) != 0 || sgmd_alloc(s->device, &s->d_census64_r, need) != 0) return -1;
-        s->cap_census64 = need;
-    }
+    const buf_request words[] = {{&s->d_census64_l, need, 0}, {&s->d_census64_r, need, 0}};
+    if (!reserve_all(s, words, 2, 0)) return -1;
     int rc = ensure_cost(s);
-    if (rc == 0) rc = sgmd_census_window(s->device, s->stream, &s->g, s->census_w, s->census_h, d_left, d_right, s->d_census64_l,
-                                         s->d_census64_r);
-    if (rc == 0) rc = sgmd_cost64(s->device, s->stream, &s->g, s->d_census64_l, s->d_census64_r, s->d_cost);
+    if (rc == 0) rc = sgmd_census_window(s->device, s->stream, &s->g, s->census_w, s->census_h, d_left, d_right, s->d_census64_l.p,
+                                         s->d_census64_r.p);
+    if (rc == 0) rc = sgmd_cost64(s->device, s->stream, &s->g, s->d_census64_l.p, s->d_census64_r.p, s->d_cost.p);
     return rc;
-}
-
-/* .c:94: the path aggregation, from the census images or (wide windows) from the cost volume */
-static int launch_aggregation(sgm_instance* s, const sgmd_paths* paths, const void* d_left)
-{
-    if (s->census_w)
-        return sgmd_aggregate_volume(s->device, s->stream, &s->g, paths, d_left, s->d_cost, s->d_lut, s->d_planes, s->plane_bytes,
-                                     s->d_extras);
-    return sgmd_aggregate(s->device, s->stream, &s->g, paths, d_left, s->d_census_l, s->d_census_r, s->d_lut, s->d_planes,
-                          s->plane_bytes, s->d_extras);
 }
 
 /* .c:109 LRCheck on the left map -- or, with the right view as the reference view (extension), the mirrored check on the
@@ -1081,15 +1044,15 @@ static int launch_aggregation(sgm_instance* s, const sgmd_paths* paths, const vo
 static int lr_stage(sgm_instance* s, void* st, void* d_out)
 {
     const SGMOption* o = &s->opt;
-    if (!s->reference_view) return o->is_check_lr ? sgmd_lrcheck(s->device, st, &s->g, d_out, s->d_disp_r, o->lrcheck_thres) : 0;
+    if (!s->reference_view) return o->is_check_lr ? sgmd_lrcheck(s->device, st, &s->g, d_out, s->d_disp_r.p, o->lrcheck_thres) : 0;
     /* the rows this instance computes: all rows of all frames of the batch, or its row tile of each of them */
-    int rc = sgmd_lrcheck_right(s->device, st, &s->g, s->d_disp_r, d_out, o->lrcheck_thres, o->is_check_lr ? 1 : 0, s->d_labels);
+    int rc = sgmd_lrcheck_right(s->device, st, &s->g, s->d_disp_r.p, d_out, o->lrcheck_thres, o->is_check_lr ? 1 : 0, s->d_labels.p);
     const size_t frame = (size_t)s->g.W * s->g.H * sizeof(float), first = (size_t)s->g.row_begin * s->g.W * sizeof(float);
     const size_t rows = (size_t)(s->g.row_end - s->g.row_begin) * s->g.W * sizeof(float);
     if (rows == frame)                                        /* d_labels: scratch until the speckle pass */
-        return rc ? rc : sgmd_d2d_async(s->device, st, d_out, s->d_labels, frame * s->g.B);
+        return rc ? rc : sgmd_d2d_async(s->device, st, d_out, s->d_labels.p, frame * s->g.B);
     for (int f = 0; rc == 0 && f < s->g.B; ++f)
-        rc = sgmd_d2d_async(s->device, st, (char*)d_out + f * frame + first, (char*)s->d_labels + f * frame + first, rows);
+        rc = sgmd_d2d_async(s->device, st, (char*)d_out + f * frame + first, (char*)s->d_labels.p + f * frame + first, rows);
     return rc;
 }
 
@@ -1101,26 +1064,12 @@ static int lr_stage(sgm_instance* s, void* st, void* d_out)
 /* scratch of the fused last sweep (zero when allocated: its progress words start below every generation) and the kept left image */
 static int ensure_upsum(sgm_instance* s)
 {
-    const size_t need = sgmd_upsum_scratch_bytes(&s->g), px = (size_t)s->g.B * s->g.W * s->g.H;
-    if (need > s->cap_up_scratch || !s->d_up_scratch) {
-        sync_streams(s);
-        sgmd_free(s->device, s->d_up_scratch);
-        s->d_up_scratch = NULL; s->cap_up_scratch = 0;
-        if (sgmd_alloc(s->device, &s->d_up_scratch, need) != 0) return -1;
-        if (sgmd_memset_async(s->device, s->stream, s->d_up_scratch, 0, need) != 0) return -1;
-        s->cap_up_scratch = need;
-    }
-    if (px > s->cap_left_keep || !s->d_left_keep) {
-        sync_streams(s);
-        sgmd_free(s->device, s->d_left_keep);
-        s->d_left_keep = NULL; s->cap_left_keep = 0;
-        if (sgmd_alloc(s->device, &s->d_left_keep, px) != 0) return -1;
-        s->cap_left_keep = px;
-    }
-    return 0;
+    const size_t px = (size_t)s->g.B * s->g.W * s->g.H;
+    return reserve(s, &s->d_up_scratch, sgmd_upsum_scratch_bytes(&s->g), BUF_ZERO) && reserve(s, &s->d_left_keep, px, 0) ? 0 : -1;
 }
 
-static bool run_pipeline_body(sgm_instance* s, const void* d_left, const void* d_right, void* d_out)
+/* d_conf: the device map the cost sum stores the reference view's matching confidence to (extension), NULL: none asked for */
+static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_right, void* d_out, void* d_conf)
 {
     const int dev = s->device;
     void* st = s->stream;
@@ -1129,9 +1078,10 @@ static bool run_pipeline_body(sgm_instance* s, const void* d_left, const void* d
     const size_t px_bytes = (size_t)g->B * g->W * g->H * sizeof(float);
 
     /* stage groups on streams of their own (sgm_set_stage_cus / sgm_set_overlap_post; never in row-tile mode) */
-    const bool own_sum = s->sum_stream && s->tile_end == 0;
-    const bool overlap = s->overlap_post && s->post_stream && s->tile_end == 0;
+    const bool own_sum = s->sum_stream && !row_tiled(s);
+    const bool overlap = s->overlap_post && s->post_stream && !row_tiled(s);
     void *sts = st, *st2 = st;
+    if (s->refine_on && !d_conf) d_conf = s->d_rf_conf.p;        /* the refinement needs the confidence: an internal map */
     /* the aggregation rewrites the planes the previous match's cost sum may still be reading on its own stream */
     if (s->sum_pending) LAUNCH(sgmd_stream_wait_event(dev, st, s->ev_sum));
     if (!s->s_is_zero) LAUNCH(materialize_S(s));             /* Match without Reset: S of the previous frame is needed now */
@@ -1140,36 +1090,36 @@ static bool run_pipeline_body(sgm_instance* s, const void* d_left, const void* d
      * what waited for the post pass of match n (the cost sum of match n + 1 waits for it, and this stream waits for that sum) */
     const void* guide = NULL;
     if (s->refine_on) {
-        guide = s->d_rf_guide[s->rf_turn];
+        guide = s->d_rf_guide[s->rf_turn].p;
         s->rf_turn ^= 1;
         LAUNCH(sgmd_d2d_async(dev, st, (void*)guide, s->reference_view ? d_right : d_left, (size_t)g->B * g->W * g->H));
     }
-    mark(s, 0);
+    mark(s, T_CENSUS);
     LAUNCH(prepare_costs(s, d_left, d_right));                                                      /* .c:82-83 */
-    mark(s, 1);
+    mark(s, T_COST);
     /* .c:89: the cost volume is recomputed inside the aggregation kernel; it is only materialised when a
      * test wants to read it back (stage 2) */
     if (s->keep_stages && !s->census_w) {
         LAUNCH(ensure_cost(s));
-        LAUNCH(sgmd_cost(dev, st, g, s->d_census_l, s->d_census_r, s->d_cost));
+        LAUNCH(sgmd_cost(dev, st, g, s->d_census_l.p, s->d_census_r, s->d_cost.p));
     }
-    mark(s, 2);
+    mark(s, T_AGGREGATE);
     if (s->need_plane_memset && s->paths.ndirs > 4)
         for (int f = 0; f < g->B; ++f)
-            LAUNCH(sgmd_memset_async(dev, st, (char*)s->d_planes_alloc + ((size_t)f * 8 + 4) * s->plane_bytes, 0, 4 * s->plane_bytes));
+            LAUNCH(sgmd_memset_async(dev, st, (char*)s->d_planes_alloc.p + ((size_t)f * 8 + 4) * s->plane_bytes, 0, 4 * s->plane_bytes));
     /* the last vertical sweep fused with the cost sum (sgmd_upsum): whenever this match neither adds to an earlier S (Q14) nor has
      * to leave S behind for a test, nor asks for the matching confidence (written by the cost-sum kernels) */
-    const bool use_up = s->up_rows > 0 && !s->keep_stages && s->s_is_zero && s->fused_wta && !s->conf_dst;
+    const bool use_up = s->up_rows > 0 && !s->keep_stages && s->s_is_zero && s->fused_wta && !d_conf;
     s->last_up_rows = use_up ? s->up_rows : 0;
     if (use_up) {
         LAUNCH(ensure_upsum(s));
-        LAUNCH(sgmd_d2d_async(dev, st, s->d_left_keep, d_left, (size_t)g->B * g->W * g->H));
+        LAUNCH(sgmd_d2d_async(dev, st, s->d_left_keep.p, d_left, (size_t)g->B * g->W * g->H));
         sgmd_paths p = s->paths;
         p.up_fused = 1;
         LAUNCH(launch_aggregation(s, &p, d_left));
     } else
         LAUNCH(launch_aggregation(s, &s->paths, d_left));                                           /* .c:94 */
-    mark(s, 3);
+    mark(s, T_SUM);
     if (own_sum) {
         LAUNCH(sgmd_event_record(dev, s->ev_agg, st));
         LAUNCH(sgmd_stream_wait_event(dev, s->sum_stream, s->ev_agg));
@@ -1179,18 +1129,18 @@ static bool run_pipeline_body(sgm_instance* s, const void* d_left, const void* d
     if (s->post_pending) LAUNCH(sgmd_stream_wait_event(dev, sts, s->ev_post));
     mark_on(s, sts, M_SUM_BEGIN);
     if (use_up) {
-        LAUNCH(sgmd_upsum(dev, sts, g, &s->paths, s->d_left_keep, s->d_census_l, s->d_census_r, s->d_lut, s->d_planes, s->plane_bytes, s->d_extras,
-                          s->d_row_extras, s->d_row_count, s->row_cap, (o->is_check_lr || s->reference_view) ? 1 : 0, o->is_check_unique ? 1 : 0,
-                          1 - o->uniqueness_ratio, s->d_up_scratch, ++s->up_gen, s->h_status, s->up_rows, s->env_upsum_wgs > 0 ? s->env_upsum_wgs : 0, d_out, s->d_disp_r));
+        LAUNCH(sgmd_upsum(dev, sts, g, &s->paths, s->d_left_keep.p, s->d_census_l.p, s->d_census_r, s->d_lut.p, s->d_planes, s->plane_bytes, s->d_extras.p,
+                          s->d_row_extras.p, s->d_row_count.p, s->row_cap, (o->is_check_lr || s->reference_view) ? 1 : 0, o->is_check_unique ? 1 : 0,
+                          1 - o->uniqueness_ratio, s->d_up_scratch.p, ++s->up_gen, s->h_status, s->up_rows, s->env_upsum_wgs > 0 ? s->env_upsum_wgs : 0, d_out, s->d_disp_r.p));
         s->planes_partial = true;                                /* S of this frame = five planes + what materialize_S re-creates */
         s->s_pending = true;
         s->s_pending_accumulate = false;
         s->s_is_zero = false;
-        mark_on(s, sts, 4);
+        mark_on(s, sts, T_WTA);
     } else
-        LAUNCH(sum_and_wta(s, sts, d_out, true));                                                   /* .c:94 sum, .c:99, .c:105 */
-    if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, sts, s->d_snap_wta, d_out, px_bytes));
-    mark_on(s, sts, 5);
+        LAUNCH(sum_and_wta(s, sts, d_out, d_conf, true));                                                   /* .c:94 sum, .c:99, .c:105 */
+    if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, sts, s->d_snap_wta.p, d_out, px_bytes));
+    mark_on(s, sts, T_LRCHECK);
     /* the post pass (latency-bound kernels that fill a fraction of the GPU) on its own stream, so that the stream(s) before it
      * can start the next match's census, aggregation and cost sum beside it */
     if (overlap || own_sum) LAUNCH(sgmd_event_record(dev, s->ev_sum, sts));
@@ -1201,19 +1151,19 @@ static bool run_pipeline_body(sgm_instance* s, const void* d_left, const void* d
         s->post_pending = true;                                  /* from here on the post stream has work of this match */
     }
     if (s->fill_on)                  /* hole filling (extension): classes from both WTA maps, before the LR check rewrites them */
-        LAUNCH(sgmd_fill_classify(dev, st2, g, s->reference_view ? s->d_disp_r : d_out, s->reference_view ? d_out : s->d_disp_r,
-                                  o->lrcheck_thres, s->reference_view, o->is_check_lr ? 1 : 0, s->d_fill_class));
+        LAUNCH(sgmd_fill_classify(dev, st2, g, s->reference_view ? s->d_disp_r.p : d_out, s->reference_view ? d_out : s->d_disp_r.p,
+                                  o->lrcheck_thres, s->reference_view, o->is_check_lr ? 1 : 0, s->d_fill_class.p));
     LAUNCH(lr_stage(s, st2, d_out));                                                                /* .c:109 */
-    if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_lr, d_out, px_bytes));
-    mark_on(s, st2, 6);
+    if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_lr.p, d_out, px_bytes));
+    mark_on(s, st2, T_SPECKLE);
     if (o->is_remove_speckles)                                                                      /* .c:115 */
-        LAUNCH(sgmd_speckle(dev, st2, g, d_out, 1.0f, o->min_speckle_area, s->d_labels, s->d_sizes, s->d_totals));
-    if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_speckle, d_out, px_bytes));
-    if (s->fill_on) LAUNCH(fill_passes(s, st2, d_out, s->d_fill_class));                           /* extension; timed as "speckle" */
-    mark_on(s, st2, 7);
-    LAUNCH(sgmd_median(dev, st2, g, d_out, s->d_median_scratch, s->h_status));                                   /* .c:120 */
-    if (s->refine_on) LAUNCH(refine_passes(s, st2, d_out, s->conf_dst, guide, &s->rf_eff));    /* extension; timed as "median" */
-    mark_on(s, st2, 8);
+        LAUNCH(sgmd_speckle(dev, st2, g, d_out, 1.0f, o->min_speckle_area, s->d_labels.p, s->d_sizes.p, s->d_totals.p));
+    if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_speckle.p, d_out, px_bytes));
+    if (s->fill_on) LAUNCH(fill_passes(s, st2, d_out, s->d_fill_class.p));                           /* extension; timed as "speckle" */
+    mark_on(s, st2, T_MEDIAN);
+    LAUNCH(sgmd_median(dev, st2, g, d_out, s->d_median_scratch.p, s->h_status));                                   /* .c:120 */
+    if (s->refine_on) LAUNCH(refine_passes(s, st2, d_out, d_conf, guide, &s->rf_eff));    /* extension; timed as "median" */
+    mark_on(s, st2, M_END);
     if (overlap) LAUNCH(sgmd_event_record(dev, s->ev_post, st2));
     else if (own_sum) LAUNCH(sgmd_event_record(dev, s->ev_sum, st2));   /* the post pass ran on the sum stream: "sum done" = all of it */
     s->tail_stream = st2;
@@ -1231,17 +1181,6 @@ failed:
     FAIL("a kernel launch failed; the match was abandoned");
 }
 
-/* every match: with the refinement on, the cost sum stores the confidence it needs -- to the caller's map (sgm_match_confidence*) or to
- * an internal one */
-static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_right, void* d_out)
-{
-    const bool own_conf = s->refine_on && !s->conf_dst;
-    if (own_conf) s->conf_dst = s->d_rf_conf;
-    const bool ok = run_pipeline_body(s, d_left, d_right, d_out);
-    if (own_conf) s->conf_dst = NULL;
-    return ok;
-}
-
 /* ------------------------------------------------------------------ row tiles (one frame over several GPUs)
  *
  * The instance computes rows [row_begin,row_end) of aggregation, cost sum, both WTAs and the LR check.  The
@@ -1251,14 +1190,6 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
  * Census and the four anomalous diagonal lines are computed on the whole frame by every GPU (the images are
  * replicated: 2 x W*H bytes; that work is ~1 % of a frame).  Speckle removal and the median are whole-frame
  * passes over the gathered W*H disparity map (sgm_tile_post). */
-
-static int sweep_mask(const sgm_instance* s, int forward)
-{
-    int m = 0;
-    for (int d = 0; d < s->paths.ndirs; ++d)
-        if (s->paths.dy[d] == (forward ? 1 : -1)) m |= 1 << d;
-    return m;
-}
 
 bool sgm_set_rows(sgm_instance* s, int row_begin, int row_end)
 {
@@ -1284,7 +1215,7 @@ bool sgm_tile_begin(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_rig
     if (rc == 0) rc = prepare_costs(s, d_left, d_right);
     if (s->need_plane_memset && s->paths.ndirs > 4)
         for (int f = 0; rc == 0 && f < s->g.B; ++f)
-            rc = sgmd_memset_async(s->device, s->stream, (char*)s->d_planes_alloc + ((size_t)f * 8 + 4) * s->plane_bytes, 0, 4 * s->plane_bytes);
+            rc = sgmd_memset_async(s->device, s->stream, (char*)s->d_planes_alloc.p + ((size_t)f * 8 + 4) * s->plane_bytes, 0, 4 * s->plane_bytes);
     if (rc != 0) FAIL("a kernel launch failed");
     s->tile_left = d_left;
     int hmask = 0;
@@ -1332,7 +1263,7 @@ bool sgm_tile_sweep(sgm_instance* s, int forward)
 bool sgm_tile_finish(sgm_instance* s, float* d_disp_left)
 {
     if (!s || !s->initialized || !s->tile_left || !d_disp_left) return false;
-    int rc = sum_and_wta(s, s->stream, d_disp_left, false);
+    int rc = sum_and_wta(s, s->stream, d_disp_left, NULL, false);
     if (rc == 0) rc = lr_stage(s, s->stream, d_disp_left);
     s->tile_left = NULL;
     if (rc != 0) FAIL("a kernel launch failed");
@@ -1344,9 +1275,9 @@ bool sgm_tile_post(sgm_instance* s, float* d_disp_left)
     if (!s || !s->initialized || !d_disp_left) return false;
     int rc = 0;
     if (s->opt.is_remove_speckles)
-        rc = sgmd_speckle(s->device, s->stream, &s->g, d_disp_left, 1.0f, s->opt.min_speckle_area, s->d_labels, s->d_sizes,
-                          s->d_totals);
-    if (rc == 0) rc = sgmd_median(s->device, s->stream, &s->g, d_disp_left, s->d_median_scratch, s->h_status);
+        rc = sgmd_speckle(s->device, s->stream, &s->g, d_disp_left, 1.0f, s->opt.min_speckle_area, s->d_labels.p, s->d_sizes.p,
+                          s->d_totals.p);
+    if (rc == 0) rc = sgmd_median(s->device, s->stream, &s->g, d_disp_left, s->d_median_scratch.p, s->h_status);
     if (rc != 0) FAIL("a kernel launch failed");
     return true;
 }
@@ -1414,8 +1345,8 @@ bool sgm_match_device(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_r
     if (!s || !s->initialized) return false;                     /* .c:70 */
     if (!d_left || !d_right) return false;                       /* .c:73 */
     if (!d_disp_left) return false;
-    if (s->tile_end != 0) FAIL("the instance is in row-tile mode (sgm_set_rows): use the sgm_tile_* sequence");
-    return run_pipeline(s, d_left, d_right, d_disp_left);
+    if (row_tiled(s)) FAIL("the instance is in row-tile mode (sgm_set_rows): use the sgm_tile_* sequence");
+    return run_pipeline(s, d_left, d_right, d_disp_left, NULL);
 }
 
 bool sgm_synchronize(sgm_instance* s)
@@ -1442,13 +1373,13 @@ bool sgm_match_wait(sgm_instance* s)
         const size_t piece = s->async_bytes / (size_t)chunks / 4 * 4;
         for (int i = 0; i + 1 < chunks; ++i) {
             if (sgmd_event_sync(s->device, s->ev_chunk[i]) != 0) break;
-            memcpy((char*)s->async_out + done, (const char*)s->h_disp + done, piece);
+            memcpy((char*)s->async_out + done, (const char*)s->h_disp.p + done, piece);
             done += piece;
         }
     }
     if (!sgm_synchronize(s)) return false;
-    if (s->async_out) memcpy((char*)s->async_out + done, (const char*)s->h_disp + done, s->async_bytes - done);   /* .c:122 */
-    if (s->async_conf_out) memcpy(s->async_conf_out, s->h_conf, s->async_bytes / sizeof(float) * sizeof(uint16_t));
+    if (s->async_out) memcpy((char*)s->async_out + done, (const char*)s->h_disp.p + done, s->async_bytes - done);   /* .c:122 */
+    if (s->async_conf_out) memcpy(s->async_conf_out, s->h_conf.p, s->async_bytes / sizeof(float) * sizeof(uint16_t));
     s->async_out = NULL;
     s->async_conf_out = NULL;
     s->async_chunks = 1;
@@ -1459,36 +1390,15 @@ bool sgm_match_wait(sgm_instance* s)
 static int ensure_conf(sgm_instance* s, bool host_staging)
 {
     const size_t need = (size_t)s->g.B * s->g.W * s->g.H * sizeof(uint16_t);
-    if (!s->d_conf || need > s->cap_conf) {
-        sync_streams(s);
-        sgmd_free(s->device, s->d_conf);
-        s->d_conf = NULL; s->cap_conf = 0;
-        if (sgmd_alloc(s->device, &s->d_conf, need) != 0) return -1;
-        s->cap_conf = need;
-    }
-    if (host_staging && (!s->h_conf || need > s->cap_h_conf)) {
-        sgmd_free_pinned(s->device, s->h_conf);
-        s->h_conf = NULL; s->cap_h_conf = 0;
-        if (sgmd_alloc_pinned(s->device, &s->h_conf, need) != 0) return -1;
-        s->cap_h_conf = need;
-    }
-    return 0;
-}
-
-/* a match whose cost sum also stores the reference view's confidence to the device map d_conf */
-static bool run_pipeline_conf(sgm_instance* s, const void* d_left, const void* d_right, void* d_out, void* d_conf)
-{
-    s->conf_dst = d_conf;
-    const bool ok = run_pipeline(s, d_left, d_right, d_out);
-    s->conf_dst = NULL;
-    return ok;
+    const buf_request maps[] = {{&s->d_conf, need, 0}, {&s->h_conf, need, BUF_PINNED | BUF_LAZY_DRAIN}};
+    return reserve_all(s, maps, host_staging ? 2 : 1, 0) ? 0 : -1;
 }
 
 /* what every confidence entry point checks before it queues anything */
 static bool conf_ready(sgm_instance* s, const void* l, const void* r, const void* disp, const void* conf)
 {
     if (!s || !s->initialized || !l || !r || !disp || !conf) return false;
-    if (s->tile_end != 0) FAIL("the matching confidence works on whole frames: not available in row-tile mode (sgm_set_rows)");
+    if (row_tiled(s)) FAIL("the matching confidence works on whole frames: not available in row-tile mode (sgm_set_rows)");
     if (!conf_available()) FAIL("the matching confidence is not part of this build");
     return true;
 }
@@ -1496,32 +1406,59 @@ static bool conf_ready(sgm_instance* s, const void* l, const void* r, const void
 bool sgm_match_confidence_device(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, float* d_disp, uint16_t* d_conf)
 {
     if (!conf_ready(s, d_left, d_right, d_disp, d_conf)) return false;
-    return run_pipeline_conf(s, d_left, d_right, d_disp, d_conf);
+    return run_pipeline(s, d_left, d_right, d_disp, d_conf);
+}
+
+/* The frame of the host-pointer entries (sgm_match_async and its confidence form, sgm_match_planes_async): what they check before
+ * they queue anything -- afterwards the staging buffers are free again */
+static bool host_entry_ready(sgm_instance* s, const void* in_a, const void* in_b, const void* out)
+{
+    if (!s || !s->initialized) return false;                     /* .c:70 */
+    if (!in_a || !in_b) return false;                            /* .c:73 */
+    if (!out) return false;
+    if (row_tiled(s)) FAIL("the instance is in row-tile mode (sgm_set_rows): use the sgm_tile_* sequence");
+    return sgm_match_wait(s);
+}
+
+/* ... H2D from the caller's buffer, staged unless that buffer is page-locked (sgm_host_alloc) ... */
+static bool upload(sgm_instance* s, void* d_dst, const void* src, void* staging, size_t bytes)
+{
+    if (!sgmd_host_is_pinned(s->device, src, bytes)) { memcpy(staging, src, bytes); src = staging; }
+    return sgmd_h2d_async(s->device, s->stream, d_dst, src, bytes) == 0;
+}
+
+/* ... and their end: a failed entry drains the streams (queued copies may still read the caller's / staging buffers), a queued
+ * one leaves what sgm_match_wait hands over -- out / conf_out: the caller's buffers the staged maps still have to be copied to
+ * (NULL: none, or page-locked and written by the device) */
+static bool async_queued(sgm_instance* s, bool ok, float* out, uint16_t* conf_out, size_t bytes, int chunks)
+{
+    if (!ok) {
+        sync_streams(s);
+        return false;
+    }
+    s->async_pending = true;
+    s->async_out = out;
+    s->async_conf_out = conf_out;
+    s->async_bytes = bytes;
+    s->async_chunks = chunks;
+    return true;
 }
 
 /* The host-pointer match without the final wait: stages the images (not at all when the caller's buffers are pinned,
  * sgm_host_alloc), queues H2D, the pipeline and D2H on the instance's stream and returns.  With a few instances
  * round-robined by the caller, the copies of one overlap the kernels of the others (separate DMA engines). */
-/* conf != NULL (sgm_match_confidence_async): the confidence map comes back behind the disparity map, through s->d_conf */
+/* conf != NULL (sgm_match_confidence_async): the confidence map comes back behind the disparity map, through s->d_conf.p */
 static bool match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left, uint16_t* conf)
 {
-    if (!s || !s->initialized) return false;                     /* .c:70 */
-    if (!img_left || !img_right) return false;                   /* .c:73 */
-    if (!disp_left) return false;
-    if (s->tile_end != 0) FAIL("the instance is in row-tile mode (sgm_set_rows): use the sgm_tile_* sequence");
-    if (!sgm_match_wait(s)) return false;                        /* the staging buffers are free again */
+    if (!host_entry_ready(s, img_left, img_right, disp_left)) return false;
     const size_t px = (size_t)s->g.B * s->g.W * s->g.H;           /* batch > 1: B consecutive frames */
     const bool conf_pinned = conf && sgmd_host_is_pinned(s->device, conf, px * sizeof(uint16_t)) != 0;
     if (conf && ensure_conf(s, !conf_pinned) != 0) FAIL("device allocation failed for the confidence map");
-    const void *src_l = img_left, *src_r = img_right;
-    /* the left image is on the bus while the right one is staged */
-    if (!sgmd_host_is_pinned(s->device, img_left, px)) { memcpy(s->h_left, img_left, px); src_l = s->h_left; }
-    bool ok = sgmd_h2d_async(s->device, s->stream, s->d_left, src_l, px) == 0;
-    if (!sgmd_host_is_pinned(s->device, img_right, px)) { memcpy(s->h_right, img_right, px); src_r = s->h_right; }
-    const bool out_pinned = sgmd_host_is_pinned(s->device, disp_left, px * sizeof(float)) != 0;
     const size_t bytes = px * sizeof(float);
-    ok = ok && sgmd_h2d_async(s->device, s->stream, s->d_right, src_r, px) == 0 &&
-         (conf ? run_pipeline_conf(s, s->d_left, s->d_right, s->d_disp, s->d_conf) : run_pipeline(s, s->d_left, s->d_right, s->d_disp));
+    /* the left image is on the bus while the right one is staged */
+    bool ok = upload(s, s->d_left.p, img_left, s->h_left.p, px) && upload(s, s->d_right.p, img_right, s->h_right.p, px);
+    const bool out_pinned = sgmd_host_is_pinned(s->device, disp_left, bytes) != 0;
+    ok = ok && run_pipeline(s, s->d_left.p, s->d_right.p, s->d_disp.p, conf ? s->d_conf.p : NULL);
     int chunks = 1;
     if (ok && !out_pinned && bytes >= RESULT_CHUNK_MIN) {        /* a single frame: 0.92 -> 0.88 ms per blocking call; batches of 8 through
                                                                    four pipelined instances on pageable buffers: 3500 -> 3640 fps */
@@ -1536,24 +1473,15 @@ static bool match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t*
         size_t off = 0;
         for (int i = 0; ok && i < chunks; ++i) {
             const size_t n = i + 1 < chunks ? piece : bytes - off;
-            ok = queue_result_copy(s, (char*)s->h_disp + off, (const char*)s->d_disp + off, n) &&
+            ok = queue_result_copy(s, (char*)s->h_disp.p + off, (const char*)s->d_disp.p + off, n) &&
                  (i + 1 == chunks || sgmd_event_record(s->device, s->ev_chunk[i], result_stream(s)) == 0);
             off += n;
         }
     } else if (ok)
-        ok = queue_result_copy(s, out_pinned ? (void*)disp_left : s->h_disp, s->d_disp, bytes);
+        ok = queue_result_copy(s, out_pinned ? (void*)disp_left : s->h_disp.p, s->d_disp.p, bytes);
     if (ok && conf)                       /* the confidence behind the map: written by the cost sum, long done by then */
-        ok = queue_result_copy(s, conf_pinned ? (void*)conf : s->h_conf, s->d_conf, px * sizeof(uint16_t));
-    if (!ok) {
-        sync_streams(s);                  /* queued copies may still read the caller's / staging buffers */
-        return false;
-    }
-    s->async_pending = true;
-    s->async_out = out_pinned ? NULL : disp_left;
-    s->async_conf_out = (conf && !conf_pinned) ? conf : NULL;
-    s->async_bytes = bytes;
-    s->async_chunks = chunks;
-    return true;
+        ok = queue_result_copy(s, conf_pinned ? (void*)conf : s->h_conf.p, s->d_conf.p, px * sizeof(uint16_t));
+    return async_queued(s, ok, out_pinned ? NULL : disp_left, conf_pinned ? NULL : conf, bytes, chunks);
 }
 
 bool sgm_match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left)
@@ -1635,52 +1563,30 @@ bool sgm_gray_from_planes(sgm_instance* s, const uint8_t* d_bgr, size_t count, i
 static int ensure_planes_io(sgm_instance* s)
 {
     const size_t px = (size_t)s->g.B * s->g.W * s->g.H;
-    if (px <= s->cap_bgr && s->d_bgr) return 0;
-    sync_streams(s);
-    sgmd_free(s->device, s->d_bgr);
-    sgmd_free(s->device, s->d_depth);
-    sgmd_free_pinned(s->device, s->h_bgr);
-    s->d_bgr = s->d_depth = s->h_bgr = NULL;
-    s->cap_bgr = 0;
-    if (sgmd_alloc(s->device, &s->d_bgr, 6 * px) != 0 || sgmd_alloc(s->device, &s->d_depth, px * sizeof(float)) != 0 ||
-        sgmd_alloc_pinned(s->device, &s->h_bgr, 6 * px) != 0)
-        return -1;
-    s->cap_bgr = px;
-    return 0;
+    const buf_request io[] = {{&s->d_bgr, 6 * px, 0}, {&s->d_depth, px * sizeof(float), 0}, {&s->h_bgr, 6 * px, BUF_PINNED}};
+    return reserve_all(s, io, 3, 0) ? 0 : -1;
 }
 
 bool sgm_match_planes_async(sgm_instance* s, const uint8_t* planes, float fx, float baseline, float doffs, float* depth)
 {
-    if (!s || !s->initialized) return false;
-    if (!planes || !depth) return false;
-    if (s->tile_end != 0) FAIL("the instance is in row-tile mode (sgm_set_rows): use the sgm_tile_* sequence");
-    if (!sgm_match_wait(s)) return false;                        /* the staging buffers are free again */
+    if (!host_entry_ready(s, planes, planes, depth)) return false;
     if (ensure_planes_io(s) != 0) FAIL("device allocation failed for the colour planes of %dx%d", s->g.W, s->g.H);
     const int dev = s->device;
     const size_t fpx = (size_t)s->g.W * s->g.H, px = (size_t)s->g.B * fpx;
-    const void* src = planes;
-    if (!sgmd_host_is_pinned(dev, planes, 6 * px)) { memcpy(s->h_bgr, planes, 6 * px); src = s->h_bgr; }
     const bool out_pinned = sgmd_host_is_pinned(dev, depth, px * sizeof(float)) != 0;
-    bool ok = sgmd_h2d_async(dev, s->stream, s->d_bgr, src, 6 * px) == 0;
+    bool ok = upload(s, s->d_bgr.p, planes, s->h_bgr.p, 6 * px);
     for (int f = 0; ok && f < s->g.B; ++f) {                    /* frame f: left B G R, right B G R (server.py:105-131) */
-        const char* fr = (const char*)s->d_bgr + (size_t)f * 6 * fpx;
-        ok = sgmd_gray_planes(dev, s->stream, fr, fpx, 76, (char*)s->d_left + f * fpx) == 0 &&
-             sgmd_gray_planes(dev, s->stream, fr + 3 * fpx, fpx, 76, (char*)s->d_right + f * fpx) == 0;
+        const char* fr = (const char*)s->d_bgr.p + (size_t)f * 6 * fpx;
+        ok = sgmd_gray_planes(dev, s->stream, fr, fpx, 76, (char*)s->d_left.p + f * fpx) == 0 &&
+             sgmd_gray_planes(dev, s->stream, fr + 3 * fpx, fpx, 76, (char*)s->d_right.p + f * fpx) == 0;
     }
-    ok = ok && run_pipeline(s, s->d_left, s->d_right, s->d_disp);
+    ok = ok && run_pipeline(s, s->d_left.p, s->d_right.p, s->d_disp.p, NULL);
     void* st = result_stream(s);
     /* the depth conversion reads the map the next match's cost sum rewrites: "result done" moves behind it (not behind the copy) */
-    ok = ok && sgmd_depth(dev, st, s->d_disp, px, fx, baseline, doffs, s->d_depth) == 0 && rerecord_result_event(s) == 0 &&
-         queue_result_copy(s, out_pinned ? (void*)depth : s->h_disp, s->d_depth, px * sizeof(float));
-    if (!ok) {
-        sync_streams(s);
-        return false;
-    }
-    s->async_pending = true;
-    s->async_out = out_pinned ? NULL : depth;
-    s->async_bytes = px * sizeof(float);
-    s->async_chunks = 1;                                         /* one copy: no chunk events of an earlier match to wait for */
-    return true;
+    ok = ok && sgmd_depth(dev, st, s->d_disp.p, px, fx, baseline, doffs, s->d_depth.p) == 0 && rerecord_result_event(s) == 0 &&
+         queue_result_copy(s, out_pinned ? (void*)depth : s->h_disp.p, s->d_depth.p, px * sizeof(float));
+    /* one copy: no chunk events of an earlier match to wait for */
+    return async_queued(s, ok, out_pinned ? NULL : depth, NULL, px * sizeof(float), 1);
 }
 
 bool sgm_match_planes(sgm_instance* s, const uint8_t* planes, float fx, float baseline, float doffs, float* depth)
@@ -1726,20 +1632,20 @@ size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacit
     int row_a = 0, row_b = s->g.H;                                /* rows the device holds of a volume stage */
     if ((which == 4 || which == 6 || which == 7 || which == 9 || (which == 2 && !s->census_w)) && !s->keep_stages) return 0;
     if ((which == 9 || which == 18) && !s->fill_on) return 0;
-    if (which == 2 && !s->d_cost) return 0;
+    if (which == 2 && !s->d_cost.p) return 0;
     if (which == 3 && (ensure_S(s) != 0 || materialize_S(s) != 0)) return 0;
     switch (which) {
-    case 0: src = s->census_w ? (const char*)s->d_census64_l + f * px * 8 : (const char*)s->d_census_l + f * px * 4; elem = s->census_w ? 8 : 4; break;
-    case 1: src = s->census_w ? (const char*)s->d_census64_r + f * px * 8 : (const char*)s->d_census_r + f * px * 4; elem = s->census_w ? 8 : 4; break;
-    case 2: src = (const char*)s->d_cost + f * px * s->g.Dp; elem = 1; volume = true; break;
-    case 3: src = (const char*)s->d_S + f * px * s->g.Dp * 2; elem = 2; volume = true; break;
-    case 4: src = (const char*)s->d_snap_wta + f * px * 4; elem = 4; break;
-    case 5: src = (const char*)s->d_disp_r + f * px * 4; elem = 4; break;
-    case 6: src = (const char*)s->d_snap_lr + f * px * 4; elem = 4; break;
-    case 7: src = (const char*)s->d_snap_speckle + f * px * 4; elem = 4; break;
-    case 8: src = (const char*)s->d_disp + f * px * 4; elem = 4; break;
-    case 9: src = (const char*)s->d_fill_map + f * px * 4; elem = 4; break;
-    case 18: src = (const char*)s->d_fill_class + f * px; elem = 1; break;
+    case 0: src = s->census_w ? (const char*)s->d_census64_l.p + f * px * 8 : (const char*)s->d_census_l.p + f * px * 4; elem = s->census_w ? 8 : 4; break;
+    case 1: src = s->census_w ? (const char*)s->d_census64_r.p + f * px * 8 : (const char*)s->d_census_r + f * px * 4; elem = s->census_w ? 8 : 4; break;
+    case 2: src = (const char*)s->d_cost.p + f * px * s->g.Dp; elem = 1; volume = true; break;
+    case 3: src = (const char*)s->d_S.p + f * px * s->g.Dp * 2; elem = 2; volume = true; break;
+    case 4: src = (const char*)s->d_snap_wta.p + f * px * 4; elem = 4; break;
+    case 5: src = (const char*)s->d_disp_r.p + f * px * 4; elem = 4; break;
+    case 6: src = (const char*)s->d_snap_lr.p + f * px * 4; elem = 4; break;
+    case 7: src = (const char*)s->d_snap_speckle.p + f * px * 4; elem = 4; break;
+    case 8: src = (const char*)s->d_disp.p + f * px * 4; elem = 4; break;
+    case 9: src = (const char*)s->d_fill_map.p + f * px * 4; elem = 4; break;
+    case 18: src = (const char*)s->d_fill_class.p + f * px; elem = 1; break;
     default:
         if (which >= 10 && which < 10 + s->paths.ndirs) {
             /* frame-addressed base of the plane; only rows [plane_row_lo, plane_row_lo + plane_rows) have storage */

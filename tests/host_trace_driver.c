@@ -1,0 +1,404 @@
+/* TEST INFRASTRUCTURE (tests/test_host_call_trace.py, tests/record_host_call_trace.py): drives one build of the product's C host
+ * (csrc/sgm_host.c) on the stand-in device (tests/stub_device.c + stub_device_conf.c + stub_device_refine.c) through a fixed list of
+ * scenarios.
+ *
+ *   host_trace_driver trace    every scenario once; prints, as JSON, the unfiltered log of device calls of every step (names and
+ *                              arguments; the confidence / refinement launches of stubc_* / stubr_* merged in at their positions).
+ *                              A step is "init" (create / initialize / reset / destroy) or "frame" (everything a match does).
+ *   host_trace_driver refuse   every scenario once per allocation it performs, with that allocation refused: the step that meets
+ *                              it must return false, a reset at the same shape must then succeed, and the instance is destroyed
+ *                              (the caller runs this mode under the sanitizers).  Reports each refusal on stderr, in line with the
+ *                              library's own messages.
+ */
+#include "../include/sgm_mi355x.h"
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+void stub_clear(void);
+int stub_log_size(void);
+const char* stub_log_name(int i);
+int stub_log_arg(int i);
+void stub_fail_alloc_at(int nth);
+int stub_alloc_count(void);
+void stubc_clear(void);
+int stubc_log_size(void);
+const char* stubc_log_name(int i);
+int stubc_log_arg(int i);
+int stubc_log_pos(int i);
+const void* stubc_log_dst(int i);
+void stubr_clear(void);
+int stubr_log_size(void);
+int stubr_log_flags(int i);
+int stubr_log_pos(int i);
+const void* stubr_log_conf(int i);
+float stubr_log_l0(int i);
+
+enum { WA = 48, HA = 20, WB = 70, HB = 33, WT = 48, HT = 40, MAXPX = 4 * 6 * 70 * 40 };
+static uint8_t g_img[MAXPX];
+static float g_out[4 * 70 * 40];
+static uint16_t g_conf[4 * 70 * 40];
+static uint8_t g_rows[4 * 3 * 70 * 320];
+
+static SGMOption options(int d)
+{
+    SGMOption o;
+    memset(&o, 0, sizeof o);
+    o.num_paths = 8; o.min_disparity = 0; o.max_disparity = (uint16_t)d;
+    o.is_check_lr = true; o.lrcheck_thres = 1.0f; o.is_check_unique = true; o.uniqueness_ratio = 0.99;
+    o.is_remove_speckles = true; o.min_speckle_area = 20; o.p1 = 10; o.p2_init = 150;
+    return o;
+}
+
+/* ---- the run ---- */
+static int g_refuse;                 /* mode */
+static const char* g_scenario;
+static int g_first_step;
+static sgm_instance* g_s;            /* the scenario's instance (NULL: the default instance behind SGM_*) */
+static int g_w, g_h;                 /* the shape and options of its last initialize: what the recovery resets to */
+static SGMOption g_opt;
+static int g_allocs_before;          /* stub_alloc_count() when the scenario began */
+static int g_refused;                /* refuse mode: a step has met the refused allocation (the scenario ends there) */
+
+static void clear_logs(void) { stub_clear(); stubc_clear(); stubr_clear(); }
+
+static const char* whose(const void* p) { return p == NULL ? "none" : (p == (const void*)g_conf ? "caller" : "internal"); }
+
+static void flush_step(const char* path, const char* what)
+{
+    const int n = stub_log_size();
+    if (!g_refuse) {
+        printf("%s\n    {\"path\": \"%s\", \"call\": \"%s\", \"log\": [", g_first_step ? "" : ",", path, what);
+        g_first_step = 0;
+        int c = 0, r = 0, first = 1;
+        for (int i = 0; i <= n; ++i) {
+            for (; c < stubc_log_size() && stubc_log_pos(c) <= i; ++c, first = 0)
+                printf("%s[\"%s\", %d, \"%s\"]", first ? "" : ", ", stubc_log_name(c), stubc_log_arg(c), whose(stubc_log_dst(c)));
+            for (; r < stubr_log_size() && stubr_log_pos(r) <= i; ++r, first = 0)
+                printf("%s[\"refine_pass\", %d, \"%s\", \"%.9g\"]", first ? "" : ", ", stubr_log_flags(r), whose(stubr_log_conf(r)),
+                       (double)stubr_log_l0(r));
+            if (i < n) { printf("%s[\"%s\", %d]", first ? "" : ", ", stub_log_name(i), stub_log_arg(i)); first = 0; }
+        }
+        printf("]}");
+    }
+    clear_logs();
+}
+
+/* a step of a scenario: in refuse mode a false answer is the refused allocation showing */
+#define STEP(path, expr)                                                                                  \
+    do {                                                                                                  \
+        const bool ok_ = (expr);                                                                          \
+        flush_step(path, #expr);                                                                          \
+        if (!ok_) {                                                                                       \
+            if (!g_refuse) { fprintf(stderr, "host_trace_driver: %s: %s failed\n", g_scenario, #expr); return 1; } \
+            fprintf(stderr, "REFUSED %s: %s\n", g_scenario, #expr);                                       \
+            g_refused = 1;                                                                                \
+            return 0;                                                                                     \
+        }                                                                                                 \
+    } while (0)
+
+static bool init(int w, int h, const SGMOption* o, bool reset)
+{
+    g_w = w; g_h = h; g_opt = *o;
+    return reset ? sgm_reset(g_s, (uint16_t)w, (uint16_t)h, o) : sgm_initialize(g_s, (uint16_t)w, (uint16_t)h, o);
+}
+#define INIT(w, h, o) init(w, h, o, false)
+#define RESET(w, h, o) init(w, h, o, true)
+#define MATCH() sgm_match(g_s, g_img, g_img, g_out)
+#define MATCH_DEVICE() (sgm_match_device(g_s, g_img, g_img, g_out) && sgm_synchronize(g_s))
+
+static bool fresh(void)
+{
+    g_s = sgm_create(0);
+    clear_logs();
+    return g_s != NULL;
+}
+
+static int first_initialize(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", MATCH());
+    return 0;
+}
+
+static int reset_same_shape(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", MATCH());
+    STEP("init", RESET(WA, HA, &o));
+    STEP("frame", MATCH());
+    return 0;
+}
+
+static int reset_larger_smaller(void)
+{
+    const SGMOption o = options(16), p = options(40);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", MATCH());
+    STEP("init", RESET(WB, HB, &p));
+    STEP("frame", MATCH());
+    STEP("init", RESET(WA, HA, &o));
+    STEP("frame", MATCH());
+    STEP("init", RESET(WB, HB, &o));
+    STEP("frame", MATCH());
+    STEP("init", RESET(WT, HT, &o));                 /* fewer pixels, more rows: the path tables are replaced */
+    STEP("frame", MATCH());
+    return 0;
+}
+
+static int batch_1_to_4(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", MATCH());
+    STEP("init", sgm_set_batch(g_s, 4) && RESET(WA, HA, &o));
+    STEP("frame", MATCH());
+    STEP("frame", MATCH());
+    return 0;
+}
+
+static int range_300(void)
+{
+    const SGMOption o = options(300);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", MATCH());
+    STEP("frame", MATCH());
+    return 0;
+}
+
+static int match_without_reset(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", MATCH());
+    STEP("frame", MATCH());
+    STEP("frame", MATCH_DEVICE());
+    STEP("init", RESET(WA, HA, &o));
+    STEP("frame", MATCH());
+    return 0;
+}
+
+static int keep_stages(void)
+{
+    const SGMOption o = options(16);
+    sgm_keep_stages(g_s, 1);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", MATCH());
+    STEP("frame", MATCH());
+    return 0;
+}
+
+static int census_7x7(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", sgm_set_census_window(g_s, 7, 7) && INIT(WA, HA, &o));
+    STEP("frame", MATCH());
+    STEP("frame", MATCH());
+    return 0;
+}
+
+static int fill_holes(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", sgm_set_fill_holes(g_s, 1) && INIT(WA, HA, &o));
+    STEP("frame", MATCH());
+    STEP("frame", sgm_fill_holes(g_s, g_out, NULL) && sgm_synchronize(g_s));
+    STEP("init", RESET(WB, HB, &o));
+    STEP("frame", MATCH());
+    return 0;
+}
+
+static int refine(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", sgm_set_refine(g_s, 1, 64.0f, 8.0f, 2, 0) && INIT(WA, HA, &o));
+    STEP("frame", MATCH());
+    STEP("frame", sgm_match_confidence_device(g_s, g_img, g_img, g_out, g_conf) && sgm_synchronize(g_s));
+    STEP("frame", MATCH_DEVICE());
+    STEP("frame", sgm_match_confidence(g_s, g_img, g_img, g_out, g_conf));
+    STEP("init", RESET(WB, HB, &o));
+    STEP("frame", MATCH());
+    return 0;
+}
+
+static int standalone_refinement(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", sgm_set_refine(g_s, 1, 64.0f, 8.0f, 1, 1) && sgm_refine_disparity(g_s, g_out, g_conf, g_img) && sgm_synchronize(g_s));
+    return 0;
+}
+
+static int confidence_host_pointers(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", sgm_match_confidence(g_s, g_img, g_img, g_out, g_conf));
+    STEP("frame", sgm_match_confidence(g_s, g_img, g_img, g_out, g_conf));
+    STEP("frame", MATCH());
+    STEP("init", RESET(WB, HB, &o));
+    STEP("frame", sgm_match_confidence(g_s, g_img, g_img, g_out, g_conf));
+    return 0;
+}
+
+static int match_planes(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", sgm_match_planes(g_s, g_img, 1000.f, 100.f, 0.f, g_out));
+    STEP("frame", sgm_match_planes(g_s, g_img, 1000.f, 100.f, 0.f, g_out));
+    return 0;
+}
+
+static int row_tile(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", sgm_set_rows(g_s, 7, 13) && INIT(WA, HA, &o));
+    for (int frame = 0; frame < 2; ++frame) {
+        STEP("frame", sgm_tile_begin(g_s, g_img, g_img));
+        for (int fwd = 1; fwd >= 0; --fwd) {
+            STEP("frame", sgm_tile_import_boundary(g_s, fwd, g_rows));
+            STEP("frame", sgm_tile_sweep(g_s, fwd));
+            STEP("frame", sgm_tile_export_boundary(g_s, fwd, g_rows));
+        }
+        STEP("frame", sgm_tile_finish(g_s, g_out) && sgm_tile_post(g_s, g_out) && sgm_synchronize(g_s));
+    }
+    return 0;
+}
+
+static int overlap_post(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", sgm_set_overlap_post(g_s, 1) && INIT(WA, HA, &o));
+    STEP("frame", sgm_match_async(g_s, g_img, g_img, g_out));
+    STEP("frame", sgm_match_async(g_s, g_img, g_img, g_out));
+    STEP("frame", sgm_match_wait(g_s));
+    STEP("frame", sgm_match_planes(g_s, g_img, 1000.f, 100.f, 0.f, g_out));
+    return 0;
+}
+
+static int stage_cus(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", sgm_set_stage_cus(g_s, SGM_STAGE_SUM, 0, 8) && sgm_set_stage_cus(g_s, SGM_STAGE_POST, 8, 8) && INIT(WA, HA, &o));
+    STEP("frame", sgm_match_async(g_s, g_img, g_img, g_out));
+    STEP("frame", sgm_match_async(g_s, g_img, g_img, g_out));     /* no reset: S on a cost sum with a stream of its own */
+    STEP("frame", sgm_match_wait(g_s));
+    return 0;
+}
+
+static int fused_last_sweep(void)              /* SGM_UPSUM=1 is in the environment of this scenario's sgm_create */
+{
+    const SGMOption o = options(128);
+    STEP("init", sgm_set_batch(g_s, 2) && INIT(WB, HB, &o));
+    STEP("frame", MATCH());
+    STEP("frame", sgm_fused_sweep_rows(g_s) > 0);
+    STEP("frame", MATCH());                                       /* no reset: the three upward planes are re-created */
+    STEP("init", RESET(WB, HB, &o));
+    STEP("frame", MATCH());
+    return 0;
+}
+
+static bool default_init(int w, int h, const SGMOption* o)
+{
+    g_w = w; g_h = h; g_opt = *o;
+    return SGM_Initialize((uint16_t)w, (uint16_t)h, o);
+}
+
+static int default_instance(void)              /* g_s == NULL; its sgm_create happens inside the first SGM_Initialize */
+{
+    const SGMOption o = options(16);
+    STEP("init", default_init(WA, HA, &o));
+    STEP("frame", SGM_Match(g_img, g_img, g_out));
+    STEP("init", default_init(WB, HB, &o));                       /* Q3: the census words of the first shape are carried over */
+    STEP("frame", SGM_Match(g_img, g_img, g_out));
+    STEP("frame", SGM_Match(g_img, g_img, g_out));
+    return 0;
+}
+
+static const struct {
+    const char* name;
+    int (*run)(void);
+    bool own_instance;
+    const char* env;             /* set to "1" around the scenario */
+    int skip;                    /* refuse mode: leading allocations that are not refused (the default instance's sgm_create) */
+} k_scenarios[] = {
+    {"first_initialize", first_initialize, true, NULL, 0},
+    {"reset_same_shape", reset_same_shape, true, NULL, 0},
+    {"reset_larger_smaller", reset_larger_smaller, true, NULL, 0},
+    {"batch_1_to_4", batch_1_to_4, true, NULL, 0},
+    {"range_300", range_300, true, NULL, 0},
+    {"match_without_reset", match_without_reset, true, NULL, 0},
+    {"keep_stages", keep_stages, true, NULL, 0},
+    {"census_7x7", census_7x7, true, NULL, 0},
+    {"fill_holes", fill_holes, true, NULL, 0},
+    {"refine", refine, true, NULL, 0},
+    {"standalone_refinement", standalone_refinement, true, NULL, 0},
+    {"confidence_host_pointers", confidence_host_pointers, true, NULL, 0},
+    {"match_planes", match_planes, true, NULL, 0},
+    {"row_tile", row_tile, true, NULL, 0},
+    {"overlap_post", overlap_post, true, NULL, 0},
+    {"stage_cus", stage_cus, true, NULL, 0},
+    {"fused_last_sweep", fused_last_sweep, true, "SGM_UPSUM", 0},
+    {"default_instance", default_instance, false, NULL, 1},
+};
+#define N_SCENARIOS ((int)(sizeof k_scenarios / sizeof k_scenarios[0]))
+
+/* one pass over scenario i; refuse_at >= 0: with that allocation (counted from the scenario's start) refused */
+static int run_scenario(int i, int refuse_at)
+{
+    g_scenario = k_scenarios[i].name;
+    g_refused = 0;
+    g_s = NULL;
+    if (k_scenarios[i].env) setenv(k_scenarios[i].env, "1", 1);
+    g_allocs_before = stub_alloc_count();
+    const bool made = !k_scenarios[i].own_instance || fresh();
+    if (k_scenarios[i].env) unsetenv(k_scenarios[i].env);
+    if (!made) return 1;
+    clear_logs();
+    if (k_scenarios[i].own_instance) g_allocs_before = stub_alloc_count();      /* else before the sgm_create inside the scenario */
+    if (refuse_at >= 0) stub_fail_alloc_at(refuse_at);
+    if (k_scenarios[i].run() != 0) return 1;
+    if (refuse_at >= 0) {
+        if (!g_refused) { fprintf(stderr, "host_trace_driver: %s: allocation %d was refused and no call failed\n", g_scenario, refuse_at); return 1; }
+        stub_fail_alloc_at(-1);
+        const bool again = g_s ? sgm_reset(g_s, (uint16_t)g_w, (uint16_t)g_h, &g_opt) : SGM_Reset((uint16_t)g_w, (uint16_t)g_h, &g_opt);
+        fprintf(stderr, "RESET %s: %s\n", g_scenario, again ? "ok" : "failed");
+        if (!again) return 1;
+    }
+    if (g_s) sgm_destroy(g_s);
+    else SGM_Shutdown();
+    flush_step("init", "destroy");
+    return 0;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc != 2 || (strcmp(argv[1], "trace") != 0 && strcmp(argv[1], "refuse") != 0)) {
+        fprintf(stderr, "usage: host_trace_driver trace|refuse\n");
+        return 2;
+    }
+    g_refuse = strcmp(argv[1], "refuse") == 0;
+    setvbuf(stderr, NULL, _IONBF, 0);
+    if (!g_refuse) printf("{");
+    for (int i = 0; i < N_SCENARIOS; ++i) {
+        if (!g_refuse) { printf("%s\n  \"%s\": [", i ? "," : "", k_scenarios[i].name); g_first_step = 1; }
+        if (!g_refuse) {
+            if (run_scenario(i, -1) != 0) return 1;
+            printf("\n  ]");
+            continue;
+        }
+        /* refuse mode: a clean pass counts the allocations, then one pass per allocation */
+        if (run_scenario(i, -1) != 0) return 1;
+        const int total = stub_alloc_count() - g_allocs_before;
+        fprintf(stderr, "SCENARIO %s: %d allocations\n", k_scenarios[i].name, total);
+        for (int k = k_scenarios[i].skip; k < total; ++k)
+            if (run_scenario(i, k) != 0) return 1;
+    }
+    if (!g_refuse) printf("\n}\n");
+    else printf("host_trace_driver ok\n");
+    return 0;
+}

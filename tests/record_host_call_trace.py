@@ -1,0 +1,57 @@
+"""Records the device-call trace of one csrc/sgm_host.c on the stand-in device (tests/host_trace_driver.c has the scenarios).
+
+    python tests/record_host_call_trace.py PATH/TO/sgm_host.c [OUT.json]
+
+The golden file tests/golden/host_call_trace.json is the trace of the host as it was BEFORE a change to sgm_host.c -- record it
+from the parent commit's file (git show HEAD~:soc_project_stereo_matching_amd/csrc/sgm_host.c > /tmp/x/sgm_host.c), never from
+the file under test: tests/test_host_call_trace.py replays the scenarios on the tree's file and compares."""
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "soc_project_stereo_matching_amd", "csrc")
+TESTS = os.path.join(ROOT, "tests")
+GOLDEN = os.path.join(TESTS, "golden", "host_call_trace.json")
+STUBS = ["stub_device.c", "stub_device_conf.c", "stub_device_refine.c"]
+
+
+def build_driver(host_c, exe, extra=()):
+    """host_trace_driver + the given sgm_host.c + the stand-in device -> exe (the headers are the tree's)"""
+    subprocess.check_call(["gcc", "-O1", "-g", "-std=c11", "-D_GNU_SOURCE", *extra, "-I", CSRC, "-o", exe,
+                           os.path.join(TESTS, "host_trace_driver.c"), host_c] + [os.path.join(TESTS, s) for s in STUBS] +
+                          ["-lm", "-lpthread"])
+    return exe
+
+
+def record(host_c, workdir):
+    exe = build_driver(host_c, os.path.join(workdir, "host_trace_driver"))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("SGM_")}
+    out = subprocess.run([exe, "trace"], capture_output=True, text=True, env=env, timeout=120)
+    if out.returncode != 0:
+        raise RuntimeError("host_trace_driver trace failed: " + out.stderr[-2000:])
+    return json.loads(out.stdout)
+
+
+def write(trace, path):
+    """one step per line: a diff of two recordings reads step by step"""
+    with open(path, "w") as fh:
+        fh.write("{\n")
+        for i, (name, steps) in enumerate(trace.items()):
+            fh.write('  %s: [\n' % json.dumps(name))
+            fh.write(",\n".join("    " + json.dumps(s) for s in steps))
+            fh.write("\n  ]%s\n" % ("," if i + 1 < len(trace) else ""))
+        fh.write("}\n")
+
+
+if __name__ == "__main__":
+    if len(sys.argv) not in (2, 3):
+        sys.exit(__doc__)
+    with tempfile.TemporaryDirectory() as tmp:
+        trace = record(os.path.abspath(sys.argv[1]), tmp)
+    dst = sys.argv[2] if len(sys.argv) == 3 else GOLDEN
+    write(trace, dst)
+    print("%s: %d scenarios, %d steps, %d device calls" % (dst, len(trace), sum(len(s) for s in trace.values()),
+                                                          sum(len(st["log"]) for s in trace.values() for st in s)))

@@ -37,9 +37,14 @@ static int note(const char* name, int arg)
     pthread_mutex_unlock(&g_mu);
     return rc;
 }
+static int refused_locked(const char* name);
 static int note_locked(const char* name, int arg)
 {
     if (g_n < LOG_MAX) { snprintf(g_log[g_n], sizeof g_log[g_n], "%s", name); g_log_arg[g_n] = arg; ++g_n; }
+    return refused_locked(name);
+}
+static int refused_locked(const char* name)
+{
     if (g_fail_countdown >= 0 && strcmp(name, g_fail_name) == 0 && g_fail_countdown-- == 0) {
         g_fail_countdown = -1;
         return 719;                                  /* some HIP error code */
@@ -62,10 +67,26 @@ int sgmd_stream_wait_event(int o, void* st, void* e) { (void)o; (void)st; (void)
 int sgmd_event_sync(int o, void* e) { (void)o; (void)e; return note("event_sync", 0); }
 int sgmd_set_device(int o) { (void)o; return 0; }
 int sgmd_mem_info(int o, size_t* f, size_t* t) { (void)o; *f = (size_t)200 << 30; *t = (size_t)288 << 30; return 0; }
-int sgmd_alloc(int o, void** p, size_t n)      /* logged with its size in KiB; nothing the tests do reads the bytes of a volume */
-{ (void)o; *p = calloc(1, n > (1u << 20) ? (1u << 20) : (n ? n : 16)); note("alloc", (int)(n >> 10)); return *p ? 0 : 2; }
+/* device allocations are logged with their size in KiB (nothing the tests do reads the bytes of a volume), page-locked ones are
+ * not; both can be refused like a launch: stub_fail_at("alloc" / "alloc_pinned", n), or stub_fail_alloc_at(n) for the nth
+ * allocation of either kind from now on (< 0: none).  stub_alloc_count(): allocations of either kind so far */
+static int g_alloc_countdown = -1, g_alloc_count;
+void stub_fail_alloc_at(int nth) { g_alloc_countdown = nth; }
+int stub_alloc_count(void) { return g_alloc_count; }
+static int note_alloc(const char* name, size_t n, int logged)
+{
+    pthread_mutex_lock(&g_mu);
+    const int rc = logged ? note_locked(name, (int)(n >> 10)) : refused_locked(name);
+    ++g_alloc_count;
+    const int refused = g_alloc_countdown >= 0 && g_alloc_countdown-- == 0;
+    pthread_mutex_unlock(&g_mu);
+    return refused ? 2 : rc;
+}
+int sgmd_alloc(int o, void** p, size_t n)
+{ (void)o; *p = NULL; if (note_alloc("alloc", n, 1) != 0) return 2; *p = calloc(1, n > (1u << 20) ? (1u << 20) : (n ? n : 16)); return *p ? 0 : 2; }
 int sgmd_free(int o, void* p) { (void)o; free(p); return 0; }
-int sgmd_alloc_pinned(int o, void** p, size_t n) { (void)o; *p = calloc(1, n ? n : 16); return *p ? 0 : 2; }
+int sgmd_alloc_pinned(int o, void** p, size_t n)
+{ (void)o; *p = NULL; if (note_alloc("alloc_pinned", n, 0) != 0) return 2; *p = calloc(1, n ? n : 16); return *p ? 0 : 2; }
 int sgmd_free_pinned(int o, void* p) { (void)o; free(p); return 0; }
 int sgmd_host_is_pinned(int o, const void* p, size_t n) { (void)o; (void)p; (void)n; return 0; }
 int sgmd_h2d_async(int o, void* st, void* d, const void* s, size_t n) { (void)o; (void)st; if (n <= (1u << 20)) memcpy(d, s, n); return note("h2d", (int)n); }
