@@ -183,6 +183,12 @@ int sgmd_lrcheck(int ord, void* stream, const sgmd_geom* g, void* disp_l, const 
 int sgmd_lrcheck_right(int ord, void* stream, const sgmd_geom* g, const void* disp_r, const void* disp_l, float thres,
                        int do_check, void* out);
 
+/* Extension (sgm_match_both): both checks in one pass.  out_l / out_r = the two raw WTA maps after sgmd_lrcheck / its mirror
+ * image (plain copies if !do_check); whole frames only; neither output may alias an input, both raw maps survive.
+ * sgm_host.c references it weakly (a host built without it answers false to the sgm_match_both entry points). */
+int sgmd_lrcheck_both(int ord, void* stream, const sgmd_geom* g, const void* disp_l, const void* disp_r, float thres, int do_check,
+                      void* out_l, void* out_r);
+
 /* connected components (|delta| <= diff, 8-neighbourhood) smaller than min_area -> +INF.
  * labels/sizes/totals: int32 [H][W] scratch each.  SemiGlobalMatching.c:585-642 */
 int sgmd_speckle(int ord, void* stream, const sgmd_geom* g, void* disp, float diff, unsigned min_area,
@@ -219,6 +225,11 @@ int sgmd_median(int ord, void* stream, const sgmd_geom* g, void* disp, void* scr
 int sgmd_depth(int ord, void* stream, const void* disp, size_t n, float fx, float baseline, float doffs, void* depth);
 int sgmd_score(int ord, void* stream, const void* ground_truth, const void* test, size_t n, float abs_thresh, double* sum_sq,
                unsigned long long* n_valid, unsigned long long* n_bad);
+
+/* Extension: depth from both views' maps as the test platform combines them (depth_image.py:167-197): sgmd_depth of disp_l with
+ * fx_l where that is finite, else sgmd_depth of disp_r with fx_r at the same pixel (no warping).  Weakly referenced by sgm_host.c. */
+int sgmd_depth_both(int ord, void* stream, const void* disp_l, const void* disp_r, size_t n, float fx_l, float fx_r, float baseline,
+                    float doffs, void* depth);
 
 /* grey = (weight_r r + 150 g + 29 b) >> 8 of three consecutive n-byte planes B, G, R (the test platform's frame
  * format, server.py:105-131; the firmware's conversion, stereo_matching.c:18-25) */

@@ -127,6 +127,13 @@ struct sgm_instance {
     sgm_buf d_rf_conf;                   /* the confidence of a match whose caller did not ask for it, u16 [B][H][W] */
     sgm_buf d_rf_guide[2];               /* private copies of the reference image, used by turns (u8 [B][H][W] each) */
     int rf_turn;
+    /* both views' maps from one match (sgm_match_both; all allocated at its first use): the raw left WTA map (f32 [B][H][W]; the raw
+     * right one is d_disp_r), the two finished maps as ONE batch of 2 B maps (f32 [2 B][H][W]: the left maps, then the right ones),
+     * the speckle and median scratch of such a batch, the right view's snapshots for sgm_keep_stages (after the LR check, after
+     * speckle removal: f32 [2][B][H][W]) and the page-locked staging of the right map */
+    sgm_buf d_both_raw, d_both_maps, d_both_labels, d_both_sizes, d_both_totals, d_both_median, d_both_snap, h_disp_r;
+    bool last_both;              /* the last match was a sgm_match_both that was queued to its end: stage 8 is the first half of d_both_maps */
+    bool last_both_kept;         /* ... and it ran with sgm_keep_stages: d_both_snap holds ITS right-view snapshots (stages 26, 27) */
     size_t plane_bytes;
     /* pinned staging for the host-pointer entry point */
     sgm_buf h_left, h_right, h_disp;
@@ -136,6 +143,7 @@ struct sgm_instance {
                                     device wrote it directly) */
     size_t async_bytes;
     uint16_t* async_conf_out;    /* caller's confidence buffer the staged map still has to be copied to (NULL: none, or pinned) */
+    float* async_out_r;          /* sgm_match_both_async: caller's buffer the staged right map still has to be copied to (NULL: none, or pinned) */
     /* a staged result (pageable caller buffer) comes back in RESULT_CHUNKS pieces, an event behind each: sgm_match_wait copies piece i
      * to the caller while piece i + 1 is still on the bus (a 1242x375 map: 1.86 MB, ~40 us of DMA + ~90 us of memcpy in sequence otherwise) */
     void* ev_chunk[4];
@@ -152,7 +160,9 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     DEVICE_BUF(d_census64_r), DEVICE_BUF(d_census_need), DEVICE_BUF(d_bgr), DEVICE_BUF(d_depth), PINNED_BUF(h_bgr),
     DEVICE_BUF(d_up_scratch), DEVICE_BUF(d_left_keep), DEVICE_BUF(d_fill_class), DEVICE_BUF(d_fill_map), DEVICE_BUF(d_conf),
     PINNED_BUF(h_conf), DEVICE_BUF(d_rf_u), DEVICE_BUF(d_rf_v), DEVICE_BUF(d_rf_q), DEVICE_BUF(d_rf_conf), DEVICE_BUF(d_rf_guide[0]),
-    DEVICE_BUF(d_rf_guide[1]), PINNED_BUF(h_left), PINNED_BUF(h_right), PINNED_BUF(h_disp),
+    DEVICE_BUF(d_rf_guide[1]), PINNED_BUF(h_left), PINNED_BUF(h_right), PINNED_BUF(h_disp), DEVICE_BUF(d_both_raw),
+    DEVICE_BUF(d_both_maps), DEVICE_BUF(d_both_labels), DEVICE_BUF(d_both_sizes), DEVICE_BUF(d_both_totals), DEVICE_BUF(d_both_median),
+    DEVICE_BUF(d_both_snap), PINNED_BUF(h_disp_r),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -472,6 +482,12 @@ static bool conf_available(void) { return sgmd_sum_wta_conf != NULL && sgmd_sum_
 /* The refinement launcher (sgm_refine.hip), weakly referenced as well; a match with refinement needs the confidence kernels too */
 #pragma weak sgmd_refine_pass
 static bool refine_available(void) { return sgmd_refine_pass != NULL && conf_available(); }
+
+/* The dual LR check (sgm_sum_wta.hip) behind sgm_match_both and the depth from both maps (sgm_post.hip), weakly referenced as
+ * well: a host built without them answers false to those entry points. */
+#pragma weak sgmd_lrcheck_both
+#pragma weak sgmd_depth_both
+static bool both_available(void) { return sgmd_lrcheck_both != NULL; }
 
 bool sgm_refine_table(float lambda, float sigma, int iterations, int t, float* out)
 {
@@ -904,6 +920,7 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
         s->up_rows = sgmd_upsum_rows(&s->g);
     if (s->up_rows > 0 && s->env_upsum_rows >= 1 && s->env_upsum_rows < s->up_rows) s->up_rows = s->env_upsum_rows;
     s->have_ms = false;
+    s->last_both = s->last_both_kept = false;
     s->initialized = true;
     return true;
 }
@@ -971,14 +988,14 @@ static int materialize_S(sgm_instance* s)
 /* .c:94 (sum over the directions), .c:99 and .c:105 (both ComputeDisparity calls); conf: where the reference view's matching
  * confidence goes (extension), NULL: nowhere.  The Q14 bookkeeping (s_is_zero,
  * s_pending) changes only when every launch of the stage was accepted. */
-static int sum_and_wta(sgm_instance* s, void* st, void* d_out, void* conf, bool with_marks)
+static int sum_and_wta(sgm_instance* s, void* st, void* d_out, void* conf, bool with_marks, bool both)
 {
     const SGMOption* o = &s->opt;
     const int accumulate = s->s_is_zero ? 0 : 1;                 /* Q14 */
     const int uniq = o->is_check_unique ? 1 : 0;
     const float keep = 1 - o->uniqueness_ratio;
     int rc;
-    const bool want_right = o->is_check_lr || s->reference_view;
+    const bool want_right = both || o->is_check_lr || s->reference_view;    /* both: sgm_match_both finishes the right map as well */
     if ((!s->fused_wta || accumulate || s->keep_stages) && ensure_S(s) != 0) return -1;
     if (s->fused_wta) {
         const int store = s->keep_stages ? 1 : 0;
@@ -1068,8 +1085,62 @@ static int ensure_upsum(sgm_instance* s)
     return reserve(s, &s->d_up_scratch, sgmd_upsum_scratch_bytes(&s->g), BUF_ZERO) && reserve(s, &s->d_left_keep, px, 0) ? 0 : -1;
 }
 
-/* d_conf: the device map the cost sum stores the reference view's matching confidence to (extension), NULL: none asked for */
-static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_right, void* d_out, void* d_conf)
+/* The buffers of sgm_match_both, sized together on its first use (keep: the right view's snapshots too; staging: the page-locked
+ * right map of the host-pointer forms).  The median scratch starts zeroed like d_median_scratch; that fill is queued on s->stream,
+ * the median may run on another one. */
+static int ensure_both(sgm_instance* s, bool keep, bool staging)
+{
+    const size_t px4 = (size_t)s->g.B * s->g.W * s->g.H * sizeof(float);
+    sgmd_geom g2 = s->g;
+    g2.B *= 2;
+    const size_t med = sgmd_median_scratch_bytes(&g2);
+    const bool med_new = !buf_holds(&s->d_both_median, med);
+    const buf_request maps[] = {{&s->d_both_raw, px4, 0}, {&s->d_both_maps, 2 * px4, 0}, {&s->d_both_labels, 2 * px4, 0},
+                                {&s->d_both_sizes, 2 * px4, 0}, {&s->d_both_totals, 2 * px4, 0}, {&s->d_both_median, med, BUF_ZERO},
+                                {&s->d_both_snap, keep ? 2 * px4 : 0, 0}, {&s->h_disp_r, staging ? px4 : 0, BUF_PINNED | BUF_LAZY_DRAIN}};
+    buf_request want[8];
+    int n = 0;
+    for (int i = 0; i < 8; ++i)
+        if (maps[i].bytes) want[n++] = maps[i];
+    if (reserve_all(s, want, n, 0) && (!med_new || !(s->sum_stream || s->post_stream) || sgmd_stream_sync(s->device, s->stream) == 0))
+        return 0;
+    fprintf(stderr, "sgm_mi355x: device allocation failed for the maps of both views (%zu bytes each)\n", px4);
+    return -1;
+}
+
+/* .c:109-120 for both views at once (sgm_match_both): one dual LR check from the raw maps (wta_l, d_disp_r), then speckle removal and
+ * the median over the 2 B maps of d_both_maps as one batch -- one launch sequence each instead of two, and the second view's median
+ * chain runs beside the first's instead of behind it.  The kernels see a batch of 2 B frames: whatever they choose by batch size
+ * (speckle tile rows, the median's bands) they choose as a plain match with 2 B frames would.  out: where the finished maps are
+ * copied to (device), NULL: they stay in d_both_maps. */
+typedef struct { void *left, *right; } both_out;
+static int post_both(sgm_instance* s, void* st2, const void* wta_l, const both_out* out)
+{
+    const int dev = s->device;
+    const SGMOption* o = &s->opt;
+    const size_t px_bytes = (size_t)s->g.B * s->g.W * s->g.H * sizeof(float);
+    char* const maps = (char*)s->d_both_maps.p;
+    char* const snap = (char*)s->d_both_snap.p;
+    sgmd_geom g2 = s->g;
+    g2.B *= 2;
+    int rc = sgmd_lrcheck_both(dev, st2, &s->g, wta_l, s->d_disp_r.p, o->lrcheck_thres, o->is_check_lr ? 1 : 0, maps, maps + px_bytes);
+    if (rc == 0 && s->keep_stages) rc = sgmd_d2d_async(dev, st2, s->d_snap_lr.p, maps, px_bytes);
+    if (rc == 0 && s->keep_stages) rc = sgmd_d2d_async(dev, st2, snap, maps + px_bytes, px_bytes);
+    mark_on(s, st2, T_SPECKLE);
+    if (rc == 0 && o->is_remove_speckles)
+        rc = sgmd_speckle(dev, st2, &g2, maps, 1.0f, o->min_speckle_area, s->d_both_labels.p, s->d_both_sizes.p, s->d_both_totals.p);
+    if (rc == 0 && s->keep_stages) rc = sgmd_d2d_async(dev, st2, s->d_snap_speckle.p, maps, px_bytes);
+    if (rc == 0 && s->keep_stages) rc = sgmd_d2d_async(dev, st2, snap + px_bytes, maps + px_bytes, px_bytes);
+    mark_on(s, st2, T_MEDIAN);
+    if (rc == 0) rc = sgmd_median(dev, st2, &g2, maps, s->d_both_median.p, s->h_status);
+    if (rc == 0 && out->left) rc = sgmd_d2d_async(dev, st2, out->left, maps, px_bytes);
+    if (rc == 0 && out->right) rc = sgmd_d2d_async(dev, st2, out->right, maps + px_bytes, px_bytes);
+    return rc;
+}
+
+/* d_conf: the device map the cost sum stores the reference view's matching confidence to (extension), NULL: none asked for.
+ * both != NULL (sgm_match_both): d_out receives the raw left WTA map, the post pass finishes both views (post_both) */
+static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_right, void* d_out, void* d_conf, const both_out* both)
 {
     const int dev = s->device;
     void* st = s->stream;
@@ -1081,6 +1152,7 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
     const bool own_sum = s->sum_stream && !row_tiled(s);
     const bool overlap = s->overlap_post && s->post_stream && !row_tiled(s);
     void *sts = st, *st2 = st;
+    s->last_both = s->last_both_kept = false;                    /* until this match is queued to its end */
     if (s->refine_on && !d_conf) d_conf = s->d_rf_conf.p;        /* the refinement needs the confidence: an internal map */
     /* the aggregation rewrites the planes the previous match's cost sum may still be reading on its own stream */
     if (s->sum_pending) LAUNCH(sgmd_stream_wait_event(dev, st, s->ev_sum));
@@ -1109,7 +1181,7 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
             LAUNCH(sgmd_memset_async(dev, st, (char*)s->d_planes_alloc.p + ((size_t)f * 8 + 4) * s->plane_bytes, 0, 4 * s->plane_bytes));
     /* the last vertical sweep fused with the cost sum (sgmd_upsum): whenever this match neither adds to an earlier S (Q14) nor has
      * to leave S behind for a test, nor asks for the matching confidence (written by the cost-sum kernels) */
-    const bool use_up = s->up_rows > 0 && !s->keep_stages && s->s_is_zero && s->fused_wta && !d_conf;
+    const bool use_up = s->up_rows > 0 && !s->keep_stages && s->s_is_zero && s->fused_wta && !d_conf && !both;
     s->last_up_rows = use_up ? s->up_rows : 0;
     if (use_up) {
         LAUNCH(ensure_upsum(s));
@@ -1138,7 +1210,7 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
         s->s_is_zero = false;
         mark_on(s, sts, T_WTA);
     } else
-        LAUNCH(sum_and_wta(s, sts, d_out, d_conf, true));                                                   /* .c:94 sum, .c:99, .c:105 */
+        LAUNCH(sum_and_wta(s, sts, d_out, d_conf, true, both != NULL));                                                   /* .c:94 sum, .c:99, .c:105 */
     if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, sts, s->d_snap_wta.p, d_out, px_bytes));
     mark_on(s, sts, T_LRCHECK);
     /* the post pass (latency-bound kernels that fill a fraction of the GPU) on its own stream, so that the stream(s) before it
@@ -1150,19 +1222,23 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
         st2 = s->post_stream;
         s->post_pending = true;                                  /* from here on the post stream has work of this match */
     }
-    if (s->fill_on)                  /* hole filling (extension): classes from both WTA maps, before the LR check rewrites them */
-        LAUNCH(sgmd_fill_classify(dev, st2, g, s->reference_view ? s->d_disp_r.p : d_out, s->reference_view ? d_out : s->d_disp_r.p,
-                                  o->lrcheck_thres, s->reference_view, o->is_check_lr ? 1 : 0, s->d_fill_class.p));
-    LAUNCH(lr_stage(s, st2, d_out));                                                                /* .c:109 */
-    if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_lr.p, d_out, px_bytes));
-    mark_on(s, st2, T_SPECKLE);
-    if (o->is_remove_speckles)                                                                      /* .c:115 */
-        LAUNCH(sgmd_speckle(dev, st2, g, d_out, 1.0f, o->min_speckle_area, s->d_labels.p, s->d_sizes.p, s->d_totals.p));
-    if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_speckle.p, d_out, px_bytes));
-    if (s->fill_on) LAUNCH(fill_passes(s, st2, d_out, s->d_fill_class.p));                           /* extension; timed as "speckle" */
-    mark_on(s, st2, T_MEDIAN);
-    LAUNCH(sgmd_median(dev, st2, g, d_out, s->d_median_scratch.p, s->h_status));                                   /* .c:120 */
-    if (s->refine_on) LAUNCH(refine_passes(s, st2, d_out, d_conf, guide, &s->rf_eff));    /* extension; timed as "median" */
+    if (both) {
+        LAUNCH(post_both(s, st2, d_out, both));
+    } else {
+        if (s->fill_on)                  /* hole filling (extension): classes from both WTA maps, before the LR check rewrites them */
+            LAUNCH(sgmd_fill_classify(dev, st2, g, s->reference_view ? s->d_disp_r.p : d_out, s->reference_view ? d_out : s->d_disp_r.p,
+                                      o->lrcheck_thres, s->reference_view, o->is_check_lr ? 1 : 0, s->d_fill_class.p));
+        LAUNCH(lr_stage(s, st2, d_out));                                                                /* .c:109 */
+        if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_lr.p, d_out, px_bytes));
+        mark_on(s, st2, T_SPECKLE);
+        if (o->is_remove_speckles)                                                                      /* .c:115 */
+            LAUNCH(sgmd_speckle(dev, st2, g, d_out, 1.0f, o->min_speckle_area, s->d_labels.p, s->d_sizes.p, s->d_totals.p));
+        if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_speckle.p, d_out, px_bytes));
+        if (s->fill_on) LAUNCH(fill_passes(s, st2, d_out, s->d_fill_class.p));                           /* extension; timed as "speckle" */
+        mark_on(s, st2, T_MEDIAN);
+        LAUNCH(sgmd_median(dev, st2, g, d_out, s->d_median_scratch.p, s->h_status));                                   /* .c:120 */
+        if (s->refine_on) LAUNCH(refine_passes(s, st2, d_out, d_conf, guide, &s->rf_eff));    /* extension; timed as "median" */
+    }
     mark_on(s, st2, M_END);
     if (overlap) LAUNCH(sgmd_event_record(dev, s->ev_post, st2));
     else if (own_sum) LAUNCH(sgmd_event_record(dev, s->ev_sum, st2));   /* the post pass ran on the sum stream: "sum done" = all of it */
@@ -1171,6 +1247,8 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
         s->ring_next = (s->ring_next + 1) % TIMING_RING;
         if (s->ring_pending < TIMING_RING) ++s->ring_pending;      /* older sets are overwritten */
     }
+    s->last_both = both != NULL;
+    s->last_both_kept = both != NULL && s->keep_stages;
     return true;
 failed:
     /* this match's timing set is incomplete: it is recorded over by the next match (ring_next did not advance).  Work may sit
@@ -1263,7 +1341,7 @@ bool sgm_tile_sweep(sgm_instance* s, int forward)
 bool sgm_tile_finish(sgm_instance* s, float* d_disp_left)
 {
     if (!s || !s->initialized || !s->tile_left || !d_disp_left) return false;
-    int rc = sum_and_wta(s, s->stream, d_disp_left, NULL, false);
+    int rc = sum_and_wta(s, s->stream, d_disp_left, NULL, false, false);
     if (rc == 0) rc = lr_stage(s, s->stream, d_disp_left);
     s->tile_left = NULL;
     if (rc != 0) FAIL("a kernel launch failed");
@@ -1346,7 +1424,7 @@ bool sgm_match_device(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_r
     if (!d_left || !d_right) return false;                       /* .c:73 */
     if (!d_disp_left) return false;
     if (row_tiled(s)) FAIL("the instance is in row-tile mode (sgm_set_rows): use the sgm_tile_* sequence");
-    return run_pipeline(s, d_left, d_right, d_disp_left, NULL);
+    return run_pipeline(s, d_left, d_right, d_disp_left, NULL, NULL);
 }
 
 bool sgm_synchronize(sgm_instance* s)
@@ -1377,11 +1455,13 @@ bool sgm_match_wait(sgm_instance* s)
             done += piece;
         }
     }
-    if (!sgm_synchronize(s)) return false;
+    if (!sgm_synchronize(s)) { s->async_out_r = NULL; return false; }
     if (s->async_out) memcpy((char*)s->async_out + done, (const char*)s->h_disp.p + done, s->async_bytes - done);   /* .c:122 */
     if (s->async_conf_out) memcpy(s->async_conf_out, s->h_conf.p, s->async_bytes / sizeof(float) * sizeof(uint16_t));
+    if (s->async_out_r) memcpy(s->async_out_r, s->h_disp_r.p, s->async_bytes);
     s->async_out = NULL;
     s->async_conf_out = NULL;
+    s->async_out_r = NULL;
     s->async_chunks = 1;
     return true;
 }
@@ -1406,7 +1486,7 @@ static bool conf_ready(sgm_instance* s, const void* l, const void* r, const void
 bool sgm_match_confidence_device(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, float* d_disp, uint16_t* d_conf)
 {
     if (!conf_ready(s, d_left, d_right, d_disp, d_conf)) return false;
-    return run_pipeline(s, d_left, d_right, d_disp, d_conf);
+    return run_pipeline(s, d_left, d_right, d_disp, d_conf, NULL);
 }
 
 /* The frame of the host-pointer entries (sgm_match_async and its confidence form, sgm_match_planes_async): what they check before
@@ -1458,7 +1538,7 @@ static bool match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t*
     /* the left image is on the bus while the right one is staged */
     bool ok = upload(s, s->d_left.p, img_left, s->h_left.p, px) && upload(s, s->d_right.p, img_right, s->h_right.p, px);
     const bool out_pinned = sgmd_host_is_pinned(s->device, disp_left, bytes) != 0;
-    ok = ok && run_pipeline(s, s->d_left.p, s->d_right.p, s->d_disp.p, conf ? s->d_conf.p : NULL);
+    ok = ok && run_pipeline(s, s->d_left.p, s->d_right.p, s->d_disp.p, conf ? s->d_conf.p : NULL, NULL);
     int chunks = 1;
     if (ok && !out_pinned && bytes >= RESULT_CHUNK_MIN) {        /* a single frame: 0.92 -> 0.88 ms per blocking call; batches of 8 through
                                                                    four pipelined instances on pageable buffers: 3500 -> 3640 fps */
@@ -1505,6 +1585,48 @@ bool sgm_match_confidence(sgm_instance* s, const uint8_t* img_left, const uint8_
     return sgm_match_confidence_async(s, img_left, img_right, disp_left, conf) && sgm_match_wait(s);
 }
 
+/* ------------------------------------------------------------------ both views' maps from one match (extension) */
+
+/* what every sgm_match_both entry point checks before it queues (or allocates) anything */
+static bool both_ready(sgm_instance* s, const void* l, const void* r, const void* disp_l, const void* disp_r)
+{
+    if (!s || !s->initialized || !l || !r || !disp_l || !disp_r) return false;
+    if (row_tiled(s)) FAIL("both views' maps need whole frames: not available in row-tile mode (sgm_set_rows)");
+    if (s->fill_on || s->refine_on)
+        FAIL("sgm_match_both does not combine with hole filling or the refinement: their class map and confidence are defined for one view");
+    if (!both_available()) FAIL("sgm_match_both is not part of this build");
+    return true;
+}
+
+bool sgm_match_both_device(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left, float* d_disp_right)
+{
+    if (!both_ready(s, d_left, d_right, d_disp_left, d_disp_right) || ensure_both(s, s->keep_stages != 0, false) != 0) return false;
+    const both_out out = {d_disp_left, d_disp_right};
+    return run_pipeline(s, d_left, d_right, s->d_both_raw.p, NULL, &out);
+}
+
+/* as match_async; the two maps come back from the halves of d_both_maps, each in one piece */
+bool sgm_match_both_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left, float* disp_right)
+{
+    if (!both_ready(s, img_left, img_right, disp_left, disp_right) || !sgm_match_wait(s)) return false;
+    const size_t px = (size_t)s->g.B * s->g.W * s->g.H, bytes = px * sizeof(float);
+    const bool l_pinned = sgmd_host_is_pinned(s->device, disp_left, bytes) != 0, r_pinned = sgmd_host_is_pinned(s->device, disp_right, bytes) != 0;
+    if (ensure_both(s, s->keep_stages != 0, !r_pinned) != 0) return false;
+    const both_out out = {NULL, NULL};
+    bool ok = upload(s, s->d_left.p, img_left, s->h_left.p, px) && upload(s, s->d_right.p, img_right, s->h_right.p, px);
+    ok = ok && run_pipeline(s, s->d_left.p, s->d_right.p, s->d_both_raw.p, NULL, &out);
+    ok = ok && queue_result_copy(s, l_pinned ? (void*)disp_left : s->h_disp.p, s->d_both_maps.p, bytes) &&
+         queue_result_copy(s, r_pinned ? (void*)disp_right : s->h_disp_r.p, (const char*)s->d_both_maps.p + bytes, bytes);
+    if (!async_queued(s, ok, l_pinned ? NULL : disp_left, NULL, bytes, 1)) return false;
+    s->async_out_r = r_pinned ? NULL : disp_right;
+    return true;
+}
+
+bool sgm_match_both(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left, float* disp_right)
+{
+    return sgm_match_both_async(s, img_left, img_right, disp_left, disp_right) && sgm_match_wait(s);
+}
+
 void* sgm_host_alloc(sgm_instance* s, size_t bytes)
 {
     void* p = NULL;
@@ -1522,6 +1644,15 @@ bool sgm_disparity_to_depth(sgm_instance* s, const float* d_disparity, size_t co
     /* the map may be the result of a match whose last stages run on a stream of their own (sgm_set_overlap_post / _stage_cus) */
     if (wait_for_result(s, s->stream) != 0) return false;
     return sgmd_depth(s->device, s->stream, d_disparity, count, fx, baseline, doffs, d_depth) == 0;
+}
+
+bool sgm_depth_from_both(sgm_instance* s, const float* d_disp_left, const float* d_disp_right, size_t count, float fx_left,
+                         float fx_right, float baseline, float doffs, float* d_depth)
+{
+    if (!s || !d_disp_left || !d_disp_right || !d_depth) return false;
+    if (!sgmd_depth_both) FAIL("the depth from both maps is not part of this build");
+    if (wait_for_result(s, s->stream) != 0) return false;
+    return sgmd_depth_both(s->device, s->stream, d_disp_left, d_disp_right, count, fx_left, fx_right, baseline, doffs, d_depth) == 0;
 }
 
 /* ------------------------------------------------------------------ hole filling of any map (extension) */
@@ -1580,7 +1711,7 @@ bool sgm_match_planes_async(sgm_instance* s, const uint8_t* planes, float fx, fl
         ok = sgmd_gray_planes(dev, s->stream, fr, fpx, 76, (char*)s->d_left.p + f * fpx) == 0 &&
              sgmd_gray_planes(dev, s->stream, fr + 3 * fpx, fpx, 76, (char*)s->d_right.p + f * fpx) == 0;
     }
-    ok = ok && run_pipeline(s, s->d_left.p, s->d_right.p, s->d_disp.p, NULL);
+    ok = ok && run_pipeline(s, s->d_left.p, s->d_right.p, s->d_disp.p, NULL, NULL);
     void* st = result_stream(s);
     /* the depth conversion reads the map the next match's cost sum rewrites: "result done" moves behind it (not behind the copy) */
     ok = ok && sgmd_depth(dev, st, s->d_disp.p, px, fx, baseline, doffs, s->d_depth.p) == 0 && rerecord_result_event(s) == 0 &&
@@ -1632,6 +1763,8 @@ size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacit
     int row_a = 0, row_b = s->g.H;                                /* rows the device holds of a volume stage */
     if ((which == 4 || which == 6 || which == 7 || which == 9 || (which == 2 && !s->census_w)) && !s->keep_stages) return 0;
     if ((which == 9 || which == 18) && !s->fill_on) return 0;
+    if ((which == 26 || which == 27) && !(s->keep_stages && s->last_both_kept)) return 0;
+    if (which == 28 && !s->last_both) return 0;
     if (which == 2 && !s->d_cost.p) return 0;
     if (which == 3 && (ensure_S(s) != 0 || materialize_S(s) != 0)) return 0;
     switch (which) {
@@ -1643,7 +1776,11 @@ size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacit
     case 5: src = (const char*)s->d_disp_r.p + f * px * 4; elem = 4; break;
     case 6: src = (const char*)s->d_snap_lr.p + f * px * 4; elem = 4; break;
     case 7: src = (const char*)s->d_snap_speckle.p + f * px * 4; elem = 4; break;
-    case 8: src = (const char*)s->d_disp.p + f * px * 4; elem = 4; break;
+    case 8: src = (const char*)(s->last_both ? s->d_both_maps.p : s->d_disp.p) + f * px * 4; elem = 4; break;
+    /* sgm_match_both: the right view after the LR check, after speckle removal, and finished */
+    case 26: src = (const char*)s->d_both_snap.p + f * px * 4; elem = 4; break;
+    case 27: src = (const char*)s->d_both_snap.p + ((size_t)s->g.B + f) * px * 4; elem = 4; break;
+    case 28: src = (const char*)s->d_both_maps.p + ((size_t)s->g.B + f) * px * 4; elem = 4; break;
     case 9: src = (const char*)s->d_fill_map.p + f * px * 4; elem = 4; break;
     case 18: src = (const char*)s->d_fill_class.p + f * px; elem = 1; break;
     default:
@@ -1792,6 +1929,12 @@ bool SGM_MatchConfidence(const uint8_t* img_left, const uint8_t* img_right, floa
 {
     if (!g_default) return false;
     return sgm_match_confidence(g_default, img_left, img_right, disp_left, conf);
+}
+
+bool SGM_MatchBoth(const uint8_t* img_left, const uint8_t* img_right, float* disp_left, float* disp_right)
+{
+    if (!g_default) return false;
+    return sgm_match_both(g_default, img_left, img_right, disp_left, disp_right);
 }
 
 bool SGM_MatchDevice(const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left)

@@ -12,6 +12,9 @@
  *            as reference view; the defaults are the reference's behaviour
  *            [--fill-holes]   extension: occlusion-aware hole filling of the invalid disparities (SGM_SetFillHoles)
  *            [--confidence OUT.pgm]   extension: the matching confidence (SGM_MatchConfidence) as a 16-bit PGM
+ *            [--right-out OUT.png] [--right-raw OUT.f32]   extension: the right view's map from the same match (SGM_MatchBoth),
+ *                                     normalised / raw exactly like the left one; not with --confidence, --fill-holes, --refine,
+ *                                     --right-reference (OUT is the left view's map)
  *            [--refine[=LAMBDA,SIGMA,ITERS]]   extension: confidence-guided edge-aware refinement of the map (SGM_SetRefine;
  *                             defaults SGM_REFINE_DEFAULT_*)
  *   sgm_main --convert IN OUT.png        (image I/O only, no GPU: used by the CPU tests)
@@ -37,6 +40,41 @@ static int ends_with(const char* s, const char* suf)
 {
     const size_t n = strlen(s), m = strlen(suf);
     return n >= m && !strcmp(s + n - m, suf);
+}
+
+/* main.c:92-117: the map normalised to 8 bits over its valid range (invalid = 0) as PNG / PGM, and, raw != NULL, its float32
+ * values as they are; either path may be NULL */
+static int write_map(const float* disp, int w, int h, const char* image, const char* raw)
+{
+    const size_t px = (size_t)w * h;
+    float lo = (float)w, hi = -(float)w;
+    size_t valid = 0;
+    for (size_t i = 0; i < px; ++i)
+        if (disp[i] != INFINITY) {
+            if (disp[i] < lo) lo = disp[i];
+            if (disp[i] > hi) hi = disp[i];
+            ++valid;
+        }
+    const float range = (hi - lo) != 0.0f ? (hi - lo) : 1.0f;
+    uint8_t* u8 = (uint8_t*)malloc(px);
+    if (!u8) return -1;
+    for (size_t i = 0; i < px; ++i) {
+        if (disp[i] == INFINITY) { u8[i] = 0; continue; }
+        float v = (disp[i] - lo) / range * 255.0f;
+        if (v < 0) v = 0;
+        if (v > 255) v = 255;
+        u8[i] = (unsigned char)v;
+    }
+    printf("valid %zu of %zu, disparity range [%g, %g]\n", valid, px, lo, hi);
+    int rc = 0;
+    if (image) rc = ends_with(image, ".pgm") ? sgm_write_pgm(image, u8, w, h) : sgm_write_png_gray(image, u8, w, h);
+    if (raw) {
+        FILE* f = fopen(raw, "wb");
+        if (!f || fwrite(disp, sizeof(float), px, f) != px) rc = -1;
+        if (f) fclose(f);
+    }
+    free(u8);
+    return rc;
 }
 
 int main(int argc, char** argv)
@@ -68,6 +106,8 @@ int main(int argc, char** argv)
     opt.p2_init = 150;
     const char* raw_path = NULL;
     const char* conf_path = NULL;
+    const char* right_out = NULL;
+    const char* right_raw = NULL;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
     float refine_lambda = SGM_REFINE_DEFAULT_LAMBDA, refine_sigma = SGM_REFINE_DEFAULT_SIGMA;
     int refine_iters = SGM_REFINE_DEFAULT_ITERS;
@@ -86,6 +126,8 @@ int main(int argc, char** argv)
         else if (v && !strcmp(a, "--speckle-area")) { opt.min_speckle_area = (uint16_t)atoi(v); ++i; }
         else if (v && !strcmp(a, "--raw")) { raw_path = v; ++i; }
         else if (v && !strcmp(a, "--confidence")) { conf_path = v; ++i; }
+        else if (v && !strcmp(a, "--right-out")) { right_out = v; ++i; }
+        else if (v && !strcmp(a, "--right-raw")) { right_raw = v; ++i; }
         else if (v && !strcmp(a, "--repeat")) { repeat = atoi(v); ++i; }
         else if (v && !strcmp(a, "--device")) { device = atoi(v); ++i; }
         else if (v && !strcmp(a, "--paths")) { opt.num_paths = (uint8_t)atoi(v); SGM_SetHonorNumPaths(1); ++i; }
@@ -106,6 +148,11 @@ int main(int argc, char** argv)
         }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
     }
+    if ((right_out || right_raw) && (conf_path || fill_holes || refine || right_ref)) {
+        fprintf(stderr, "--right-out / --right-raw do not combine with --confidence, --fill-holes, --refine or --right-reference "
+                        "(OUT would silently be the left map)\n");
+        return 2;
+    }
 
     int w1, h1, w2, h2;
     uint8_t* left = sgm_load_gray(argv[1], &w1, &h1);
@@ -125,45 +172,24 @@ int main(int argc, char** argv)
     }
     if (!SGM_Initialize((uint16_t)w1, (uint16_t)h1, &opt)) { printf("SGM initialization failed\n"); return -2; }
     float* disp = (float*)malloc(sizeof(float) * (size_t)w1 * h1);
+    float* disp_r = (right_out || right_raw) ? (float*)malloc(sizeof(float) * (size_t)w1 * h1) : NULL;
     uint16_t* conf = conf_path ? (uint16_t*)malloc(sizeof(uint16_t) * (size_t)w1 * h1) : NULL;
     double best = 1e30;
     for (int r = 0; r < repeat; ++r) {
         const double t0 = now_ms();
         if (r > 0 && !SGM_Reset((uint16_t)w1, (uint16_t)h1, &opt)) { printf("SGM reset failed\n"); return -2; }
-        if (!(conf ? SGM_MatchConfidence(left, right, disp, conf) : SGM_Match(left, right, disp))) { printf("SGM matching failed\n"); return -2; }
+        const bool ok = disp_r ? SGM_MatchBoth(left, right, disp, disp_r)
+                               : (conf ? SGM_MatchConfidence(left, right, disp, conf) : SGM_Match(left, right, disp));
+        if (!ok) { printf("SGM matching failed\n"); return -2; }
         const double t = now_ms() - t0;
         if (t < best) best = t;
     }
     printf("SGM_Match (host images in, host disparity out): %.3f ms\n", best);
 
-    /* main.c:92-117 */
-    const size_t px = (size_t)w1 * h1;
-    float lo = (float)w1, hi = -(float)w1;
-    size_t valid = 0;
-    for (size_t i = 0; i < px; ++i)
-        if (disp[i] != INFINITY) {
-            if (disp[i] < lo) lo = disp[i];
-            if (disp[i] > hi) hi = disp[i];
-            ++valid;
-        }
-    const float range = (hi - lo) != 0.0f ? (hi - lo) : 1.0f;
-    uint8_t* u8 = (uint8_t*)malloc(px);
-    for (size_t i = 0; i < px; ++i) {
-        if (disp[i] == INFINITY) { u8[i] = 0; continue; }
-        float v = (disp[i] - lo) / range * 255.0f;
-        if (v < 0) v = 0;
-        if (v > 255) v = 255;
-        u8[i] = (unsigned char)v;
-    }
-    printf("valid %zu of %zu, disparity range [%g, %g]\n", valid, px, lo, hi);
-    int rc = ends_with(argv[3], ".pgm") ? sgm_write_pgm(argv[3], u8, w1, h1) : sgm_write_png_gray(argv[3], u8, w1, h1);
+    int rc = write_map(disp, w1, h1, argv[3], raw_path);
+    if (disp_r && write_map(disp_r, w1, h1, right_out, right_raw) != 0) rc = -1;
     if (conf_path && sgm_write_pgm16(conf_path, conf, w1, h1) != 0) rc = -1;
-    if (raw_path) {
-        FILE* f = fopen(raw_path, "wb");
-        if (!f || fwrite(disp, sizeof(float), px, f) != px) rc = -1;
-        if (f) fclose(f);
-    }
     SGM_Shutdown();
-    free(u8); free(disp); free(conf); free(left); free(right);
+    free(disp); free(disp_r); free(conf); free(left); free(right);
     return rc ? 1 : 0;
 }

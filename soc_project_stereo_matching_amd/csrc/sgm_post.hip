@@ -669,6 +669,21 @@ __global__ __launch_bounds__(256) void sgm_depth_k(const float* __restrict__ dis
     depth[i] = ok ? fb / denom : __uint_as_float(0x7FC00000u);
 }
 
+// depth from both views' maps as the test platform combines them (depth_image.py:167-197): the left depth where it is finite, else
+// the right depth of the SAME pixel -- no warping between the views, which is the reference's behaviour
+__global__ __launch_bounds__(256) void sgm_depth_both_k(const float* __restrict__ disp_l, const float* __restrict__ disp_r,
+                                                        float* __restrict__ depth, size_t n, float fb_l, float fb_r, float doffs)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float den_l = disp_l[i] + doffs, den_r = disp_r[i] + doffs;
+    const bool ok_l = finite_bits(den_l) && (__float_as_uint(den_l) << 1) != 0u;
+    const bool ok_r = finite_bits(den_r) && (__float_as_uint(den_r) << 1) != 0u;
+    const float dl = ok_l ? fb_l / den_l : __uint_as_float(0x7FC00000u);
+    const float dr = ok_r ? fb_r / den_r : __uint_as_float(0x7FC00000u);
+    depth[i] = finite_bits(dl) ? dl : dr;                                // (a quotient that overflows is not finite either)
+}
+
 // per-block partial sums over the pixels finite in both images: sum of squared differences (double), count, count of
 // |difference| > abs_thresh; the host adds the partials in block order (deterministic)
 struct ScorePartial { double sumsq; unsigned long long n, bad; };
@@ -752,6 +767,18 @@ int sgmd_depth(int ord, void* stream, const void* disp, size_t n, float fx, floa
     const float fb = (float)((double)fx * (double)baseline);
     hipLaunchKernelGGL(sgm_depth_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)disp,
                        (float*)depth, n, fb, doffs);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sgmd_depth_both(int ord, void* stream, const void* disp_l, const void* disp_r, size_t n, float fx_l, float fx_r, float baseline,
+                    float doffs, void* depth)
+{
+    HIP_TRY(hipSetDevice(ord));
+    if (n == 0) return 0;
+    const float fb_l = (float)((double)fx_l * (double)baseline), fb_r = (float)((double)fx_r * (double)baseline);
+    hipLaunchKernelGGL(sgm_depth_both_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)disp_l,
+                       (const float*)disp_r, (float*)depth, n, fb_l, fb_r, doffs);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -4,13 +4,15 @@
  * images in, host floats out).
  *
  *   sgm_stream [--width W] [--height H] [--disparities D] [--batch B] [--instances N] [--seconds S] [--frames F] [--seed X]
- *              [--pageable] [--blocking] [--numa-node K]
+ *              [--pageable] [--blocking] [--numa-node K] [--both]
  *
  *   default      N instances, one host thread each, batches of B frames through sgm_reset + sgm_match_async + sgm_match_wait on
  *                page-locked buffers (sgm_host_alloc) for S seconds: the pipelined throughput path (bench.py's headline, in C)
  *   --blocking   one thread, one frame per call through sgm_compute (SGM_Reset + SGM_Match) on malloc'd buffers: the reference
  *                contract as it stands
  *   --pageable   malloc'd caller buffers instead of page-locked ones (staged by the library)
+ *   --both       every match returns both views' maps (sgm_match_both_async; not with --blocking); fps counts frames, each with
+ *                two maps, and "hash_frame0_right" is the right view's hash beside the left one's
  *   --numa-node K  run (and allocate) on the CPUs of NUMA node K -- the node the GPU hangs off (/sys/bus/pci/devices/<bdf>/numa_node):
  *                the host threads spin in stream synchronisation and feed 11 GB/s over PCIe; bench.py pins itself the same way
  *
@@ -64,12 +66,13 @@ static unsigned long long fnv1a(const void* p, size_t n)
 }
 
 typedef struct {
-    int k, n_inst, W, H, B, n_batches, pageable;
+    int k, n_inst, W, H, B, n_batches, pageable, both;
     const SGMOption* opt;
     uint8_t **L, **R;            /* [n_batches] batches of B frames, shared, read-only */
     volatile double stop_at;     /* set by main right after the start barrier */
     long batches_done;
     unsigned long long hash0;    /* hash of frame 0 of batch 0 as this instance computed it (0: never) */
+    unsigned long long hash0_r;  /* --both: the same of the right view's map */
     int failed;
     pthread_barrier_t* start;
 } worker;
@@ -79,27 +82,32 @@ static void* worker_main(void* p)
     worker* w = (worker*)p;
     const size_t px = (size_t)w->W * w->H;
     sgm_instance* s = sgm_create(0);
-    float* out = NULL;
+    float *out = NULL, *out_r = NULL;
     w->failed = 1;
     if (s && sgm_set_batch(s, w->B) && sgm_set_overlap_post(s, 1) && sgm_initialize(s, (uint16_t)w->W, (uint16_t)w->H, w->opt)) {
         out = w->pageable ? (float*)malloc(w->B * px * sizeof(float)) : (float*)sgm_host_alloc(s, w->B * px * sizeof(float));
-        w->failed = out == NULL;
+        if (w->both) out_r = w->pageable ? (float*)malloc(w->B * px * sizeof(float)) : (float*)sgm_host_alloc(s, w->B * px * sizeof(float));
+        w->failed = out == NULL || (w->both && out_r == NULL);
     }
     /* one untimed batch: first-use allocations */
-    if (!w->failed) w->failed = !(sgm_match_async(s, w->L[0], w->R[0], out) && sgm_match_wait(s));
+#define QUEUE(i) (w->both ? sgm_match_both_async(s, w->L[i], w->R[i], out, out_r) : sgm_match_async(s, w->L[i], w->R[i], out))
+    if (!w->failed) w->failed = !(QUEUE(0) && sgm_match_wait(s));
     pthread_barrier_wait(w->start);
     for (long b = w->k; !w->failed && now_s() < w->stop_at; b += w->n_inst) {
         const int i = (int)(b % w->n_batches);
-        if (!(sgm_reset(s, (uint16_t)w->W, (uint16_t)w->H, w->opt) && sgm_match_async(s, w->L[i], w->R[i], out) && sgm_match_wait(s))) {
+        if (!(sgm_reset(s, (uint16_t)w->W, (uint16_t)w->H, w->opt) && QUEUE(i) && sgm_match_wait(s))) {
             w->failed = 1;
             break;
         }
         if (i == 0) w->hash0 = fnv1a(out, px * sizeof(float));
+        if (i == 0 && w->both) w->hash0_r = fnv1a(out_r, px * sizeof(float));
         ++w->batches_done;
     }
     if (s) {
         if (out && !w->pageable) sgm_host_free(s, out);
         else free(out);
+        if (out_r && !w->pageable) sgm_host_free(s, out_r);
+        else free(out_r);
         sgm_destroy(s);
     }
     return NULL;
@@ -107,7 +115,7 @@ static void* worker_main(void* p)
 
 int main(int argc, char** argv)
 {
-    int W = 1242, H = 375, D = 128, B = 8, N = 4, F = 32, pageable = 0, blocking = 0, node = -1;
+    int W = 1242, H = 375, D = 128, B = 8, N = 4, F = 32, pageable = 0, blocking = 0, node = -1, both = 0;
     double seconds = 2.0;
     unsigned seed = 0x5EED0002u;
     for (int i = 1; i < argc; ++i) {
@@ -115,6 +123,7 @@ int main(int argc, char** argv)
         const char* v = i + 1 < argc ? argv[i + 1] : NULL;
         if (!strcmp(a, "--pageable")) pageable = 1;
         else if (!strcmp(a, "--blocking")) blocking = 1;
+        else if (!strcmp(a, "--both")) both = 1;
         else if (v && !strcmp(a, "--width")) W = atoi(argv[++i]);
         else if (v && !strcmp(a, "--height")) H = atoi(argv[++i]);
         else if (v && !strcmp(a, "--disparities")) D = atoi(argv[++i]);
@@ -126,7 +135,7 @@ int main(int argc, char** argv)
         else if (v && !strcmp(a, "--seed")) seed = (unsigned)strtoul(argv[++i], NULL, 0);
         else { fprintf(stderr, "sgm_stream: unknown argument %s (see the header of sgm_stream.c)\n", a); return 2; }
     }
-    if (W < 1 || H < 1 || D < 1 || B < 1 || N < 1 || N > 16 || F < 1) return 2;
+    if (W < 1 || H < 1 || D < 1 || B < 1 || N < 1 || N > 16 || F < 1 || (both && blocking)) return 2;
     if (node >= 0 && !pin_to_node(node)) fprintf(stderr, "sgm_stream: could not pin to NUMA node %d (continuing unpinned)\n", node);
     SGMOption opt;
     memset(&opt, 0, sizeof opt);                       /* main.c:48-65 with max_disparity = D */
@@ -179,7 +188,7 @@ int main(int argc, char** argv)
     pthread_t th[16];
     memset(w, 0, sizeof w);
     for (int k = 0; k < N; ++k) {
-        w[k] = (worker){k, N, W, H, B, n_batches, pageable, &opt, L, R, 1e300, 0, 0, 0, &start};
+        w[k] = (worker){k, N, W, H, B, n_batches, pageable, both, &opt, L, R, 1e300, 0, 0, 0, 0, &start};
         if (pthread_create(&th[k], NULL, worker_main, &w[k]) != 0) return 1;
     }
     /* every worker is set up (its warm-up batch included) when the barrier opens */
@@ -188,7 +197,7 @@ int main(int argc, char** argv)
     for (int k = 0; k < N; ++k) w[k].stop_at = t1 + seconds;
     long batches = 0;
     int failed = 0;
-    unsigned long long hash0 = 0;
+    unsigned long long hash0 = 0, hash0_r = 0;
     for (int k = 0; k < N; ++k) {
         pthread_join(th[k], NULL);
         batches += w[k].batches_done;
@@ -196,6 +205,10 @@ int main(int argc, char** argv)
         if (w[k].hash0) {
             if (hash0 && hash0 != w[k].hash0) failed = 1;      /* every instance must compute the same map for the same frame */
             hash0 = w[k].hash0;
+        }
+        if (w[k].hash0_r) {
+            if (hash0_r && hash0_r != w[k].hash0_r) failed = 1;
+            hash0_r = w[k].hash0_r;
         }
     }
     const double el = now_s() - t1;
@@ -206,10 +219,12 @@ int main(int argc, char** argv)
     sgm_destroy(owner);
     free(L); free(R);
     const long frames = batches * B;
-    printf("{\"mode\": \"%d instances x batches of %d, sgm_reset + sgm_match_async + sgm_match_wait, %s buffers, one thread each\", "
+    char right[64] = "";                                /* --both: the right view's hash beside the left one's */
+    if (both) snprintf(right, sizeof right, "\"hash_frame0_right\": \"%016llx\", ", hash0_r);
+    printf("{\"mode\": \"%d instances x batches of %d, sgm_reset + %s + sgm_match_wait, %s buffers, one thread each\", "
            "\"width\": %d, \"height\": %d, \"disparity_range\": %d, \"frames\": %ld, \"seconds\": %.4f, \"fps\": %.2f, \"ms_per_frame\": %.4f, "
-           "\"mdisp_per_s\": %.1f, \"hash_frame0\": \"%016llx\", \"failed\": %s}\n",
-           N, B, pageable ? "malloc'd" : "page-locked", W, H, D, frames, el, frames / el, frames ? el / frames * 1e3 : 0.0,
-           (double)px * D * 8 * frames / el / 1e6, hash0, failed ? "true" : "false");
+           "\"mdisp_per_s\": %.1f, \"hash_frame0\": \"%016llx\", %s\"failed\": %s}\n",
+           N, B, both ? "sgm_match_both_async" : "sgm_match_async", pageable ? "malloc'd" : "page-locked", W, H, D, frames, el, frames / el,
+           frames ? el / frames * 1e3 : 0.0, (double)px * D * 8 * frames / el / 1e6, hash0, right, failed ? "true" : "false");
     return failed ? 1 : 0;
 }

@@ -532,6 +532,44 @@ __global__ __launch_bounds__(256) void sgm_lrcheck_right_k(const float* __restri
     out[idx] = d;
 }
 
+// Extension: both checks in one pass over the two raw WTA maps (sgm_match_both), each with exactly the arithmetic of its
+// single-view kernel above.  Out of place: either check reads the OTHER view's raw map at another column of the row, so
+// neither input may be rewritten here (two in-place checks in sequence would have the second read an invalidated map).
+// !do_check: plain copies.
+__global__ __launch_bounds__(256) void sgm_lrcheck_both_k(const float* __restrict__ dl, const float* __restrict__ dr,
+                                                          float* __restrict__ out_l, float* __restrict__ out_r, int W, int H,
+                                                          float thres, int do_check)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= W) return;
+    const float inf = __builtin_inff();
+    const size_t row = (size_t)blockIdx.z * W * H + (size_t)y * W;      // batch: z = frame
+    float l = dl[row + x], r = dr[row + x];
+    if (do_check) {
+        if (l != inf) {                                          // sgm_lrcheck_k
+            const int xr = (int)((double)((float)x - l) + 0.5);
+            if (xr >= 0 && xr < W) {
+                const float o = dr[row + xr];
+                if (o != inf && fabs((double)(l - o)) > (double)thres) l = inf;
+            } else {
+                l = inf;
+            }
+        }
+        if (r != inf) {                                          // sgm_lrcheck_right_k
+            const int xl = (int)((double)((float)x + r) + 0.5);
+            if (xl >= 0 && xl < W) {
+                const float o = dl[row + xl];
+                if (o != inf && fabs((double)(r - o)) > (double)thres) r = inf;
+            } else {
+                r = inf;
+            }
+        }
+    }
+    out_l[row + x] = l;
+    out_r[row + x] = r;
+}
+
 template <int DPL, int THREADS, bool TIGHT = false>
 static void launch_sum_wta_lr(dim3 grid, hipStream_t st, const void* planes, size_t plane_bytes, int ndirs, const void* extras,
                               const void* row_extras, const void* row_extra_count, int row_cap, int accumulate, int store_S,
@@ -706,6 +744,17 @@ int sgmd_lrcheck_right(int ord, void* stream, const sgmd_geom* g, const void* di
     dim3 grid((g->W + 255) / 256, g->row_end - g->row_begin, g->B);
     hipLaunchKernelGGL(sgm_lrcheck_right_k, grid, dim3(256), 0, (hipStream_t)stream, (const float*)disp_r, (const float*)disp_l,
                        (float*)out, g->W, g->H, thres, do_check, g->row_begin);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sgmd_lrcheck_both(int ord, void* stream, const sgmd_geom* g, const void* disp_l, const void* disp_r, float thres, int do_check,
+                      void* out_l, void* out_r)
+{
+    HIP_TRY(hipSetDevice(ord));
+    dim3 grid((g->W + 255) / 256, g->H, g->B);                          // whole frames only
+    hipLaunchKernelGGL(sgm_lrcheck_both_k, grid, dim3(256), 0, (hipStream_t)stream, (const float*)disp_l, (const float*)disp_r,
+                       (float*)out_l, (float*)out_r, g->W, g->H, thres, do_check);
     HIP_TRY(hipGetLastError());
     return 0;
 }

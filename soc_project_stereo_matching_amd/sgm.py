@@ -21,6 +21,8 @@ STAGE_NAMES = ["census_l", "census_r", "cost", "aggr", "disp_l", "disp_r", "afte
 _STAGE_DTYPE = [np.uint32, np.uint32, np.uint8, np.uint16] + [np.float32] * 5
 # stages outside STAGE_NAMES (read_stages() leaves them out: they exist only with hole filling on, set_fill_holes)
 STAGE_FILLED, STAGE_FILL_CLASS = 9, 18
+# after a match_both: the right view after the LR check / after speckle removal (both need keep_stages) / finished
+STAGE_RIGHT_AFTER_LR, STAGE_RIGHT_AFTER_SPECKLE, STAGE_RIGHT_FINAL = 26, 27, 28
 # the refinement's default parameters (SGM_REFINE_DEFAULT_* of include/sgm_mi355x.h)
 REFINE_LAMBDA, REFINE_SIGMA, REFINE_ITERS = 16.0, 1.5, 1
 
@@ -143,6 +145,14 @@ def _load() -> C.CDLL:
             f.restype = C.c_bool
         L.SGM_MatchConfidence.argtypes = [C.c_void_p] * 4
         L.SGM_MatchConfidence.restype = C.c_bool
+    if hasattr(L, "sgm_match_both"):          # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        for f in (L.sgm_match_both, L.sgm_match_both_async, L.sgm_match_both_device):
+            f.argtypes = [C.c_void_p] * 5
+            f.restype = C.c_bool
+        L.SGM_MatchBoth.argtypes = [C.c_void_p] * 4
+        L.SGM_MatchBoth.restype = C.c_bool
+        L.sgm_depth_from_both.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_float] * 4 + [C.c_void_p]
+        L.sgm_depth_from_both.restype = C.c_bool
     L.sgm_set_batch.argtypes = [C.c_void_p, C.c_int]
     L.sgm_set_batch.restype = C.c_bool
     L.sgm_select_frame.argtypes = [C.c_void_p, C.c_int]
@@ -276,6 +286,8 @@ class _StageReader:
             dt, shp = np.float32, (h, w)
         elif idx == STAGE_FILL_CLASS:
             dt, shp = np.uint8, (h, w)
+        elif idx in (STAGE_RIGHT_AFTER_LR, STAGE_RIGHT_AFTER_SPECKLE, STAGE_RIGHT_FINAL):
+            dt, shp = np.float32, (h, w)
         elif idx >= 10:
             dt, shp = np.uint8, (h, w, d)
         else:
@@ -361,6 +373,15 @@ class SGM(_StageReader):
         conf = np.empty(left.shape, np.uint16)
         ok = self.lib.SGM_MatchConfidence(left.ctypes.data, right.ctypes.data, out.ctypes.data, conf.ctypes.data)
         return (out, conf) if ok else None
+
+    def match_both(self, left, right):
+        """SGM_MatchBoth: (left-view map, right-view map) of the default instance from one match, float32 each, or None where the C
+        call returns false.  The contract is in include/sgm_mi355x.h."""
+        left, right = _u8(left), _u8(right)
+        out_l = np.empty(left.shape, np.float32)
+        out_r = np.empty(left.shape, np.float32)
+        ok = self.lib.SGM_MatchBoth(left.ctypes.data, right.ctypes.data, out_l.ctypes.data, out_r.ctypes.data)
+        return (out_l, out_r) if ok else None
 
     def compute(self, left, right, option, out=None):
         """sgm_compute: SGM_Reset + SGM_Match in one call (north_star's entry point).  None where it returns false.  `out`: a
@@ -592,6 +613,36 @@ class SGMInstance(_StageReader):
         """sgm_match_confidence_device: device pointers (d_conf: uint16 [batch][H][W]); asynchronous on the instance stream."""
         return bool(self.lib.sgm_match_confidence_device(self.handle, d_left, d_right, d_out, d_conf))
 
+    def match_both(self, left, right):
+        """sgm_match_both: (left-view map, right-view map) from one match, float32 of the instance's shape each, or None where the
+        C call returns false.  The contract is in include/sgm_mi355x.h (SGM_MatchBoth)."""
+        if self.shape is None:
+            return None
+        left, right = _u8(left), _u8(right)
+        want = self._frame_shape()
+        if tuple(left.shape) != want or tuple(right.shape) != want:
+            raise ValueError(f"expected images of shape {want}, got {left.shape}")
+        out_l = np.empty(want, np.float32)
+        out_r = np.empty(want, np.float32)
+        ok = self.lib.sgm_match_both(self.handle, left.ctypes.data, right.ctypes.data, out_l.ctypes.data, out_r.ctypes.data)
+        return (out_l, out_r) if ok else None
+
+    def match_both_async(self, left, right, out_left, out_right) -> bool:
+        """sgm_match_both_async: as match_async with two float32 outputs; all four arrays stay borrowed until match_wait()."""
+        if self.shape is None:
+            return False
+        want = self._frame_shape()
+        for name, a, dt in (("left", left, np.uint8), ("right", right, np.uint8), ("out_left", out_left, np.float32),
+                            ("out_right", out_right, np.float32)):
+            if not a.flags["C_CONTIGUOUS"] or a.dtype != dt or tuple(a.shape) != want:
+                raise ValueError(f"match_both_async: {name} must be a C-contiguous {np.dtype(dt).name} array of shape {want}")
+        return bool(self.lib.sgm_match_both_async(self.handle, left.ctypes.data, right.ctypes.data, out_left.ctypes.data,
+                                                  out_right.ctypes.data))
+
+    def match_both_device(self, d_left: int, d_right: int, d_out_left: int, d_out_right: int) -> bool:
+        """sgm_match_both_device: device pointers (two float32 [batch][H][W] outputs); asynchronous on the instance stream."""
+        return bool(self.lib.sgm_match_both_device(self.handle, d_left, d_right, d_out_left, d_out_right))
+
     def _frame_shape(self):
         h, w = self.shape[:2]
         return (h, w) if self.batch == 1 else (self.batch, h, w)
@@ -646,6 +697,12 @@ class SGMInstance(_StageReader):
     # ---- test-platform arithmetic on device buffers (include/sgm_mi355x.h) ----
     def disparity_to_depth(self, d_disp: int, count: int, fx: float, baseline: float, doffs: float, d_depth: int) -> bool:
         return bool(self.lib.sgm_disparity_to_depth(self.handle, d_disp, count, fx, baseline, doffs, d_depth))
+
+    def depth_from_both(self, d_disp_left: int, d_disp_right: int, count: int, fx_left: float, fx_right: float, baseline: float,
+                        doffs: float, d_depth: int) -> bool:
+        """sgm_depth_from_both: the left map's depth where finite, else the right map's at the same pixel (device pointers)."""
+        return bool(self.lib.sgm_depth_from_both(self.handle, d_disp_left, d_disp_right, count, fx_left, fx_right, baseline, doffs,
+                                                 d_depth))
 
     def compare_depth(self, d_ground_truth: int, d_test: int, count: int, abs_thresh: float = 10.0):
         """(rmse, bad_pixel_rate, n_valid) of two device depth images; None where the C call returns false."""
