@@ -38,6 +38,7 @@ static const int k_dir_dy[8] = {0, 0, 1, -1, 1, -1, -1, 1};
 /* A device or page-locked buffer the instance owns, its capacity in bytes beside it: buffers only grow, so a Reset with the same
  * shape allocates nothing.  reserve() sizes them, free_device_buffers() walks k_buffers, nothing else allocates or frees one. */
 typedef struct { void* p; size_t cap; } sgm_buf;
+typedef struct { void* dst; const void* src; size_t bytes; } handover;     /* a staged output on its way to the caller (sgm_match_wait) */
 
 /* refinement parameters (sgm_set_refine) and the weight tables L_t of their iterations */
 typedef struct {
@@ -137,15 +138,13 @@ struct sgm_instance {
     size_t plane_bytes;
     /* pinned staging for the host-pointer entry point */
     sgm_buf h_left, h_right, h_disp;
-    /* sgm_match_async: a match whose result has been queued on the stream and not yet handed to the caller */
+    /* a host-pointer match whose result has been queued on the stream and not yet handed to the caller: what sgm_match_wait still
+     * has to copy from a staging buffer to the caller's pageable one (nothing for an output that is page-locked: the device writes it) */
     bool async_pending;
-    float* async_out;            /* caller's buffer the staged result still has to be copied to (NULL: it was pinned, the
-                                    device wrote it directly) */
-    size_t async_bytes;
-    uint16_t* async_conf_out;    /* caller's confidence buffer the staged map still has to be copied to (NULL: none, or pinned) */
-    float* async_out_r;          /* sgm_match_both_async: caller's buffer the staged right map still has to be copied to (NULL: none, or pinned) */
-    /* a staged result (pageable caller buffer) comes back in RESULT_CHUNKS pieces, an event behind each: sgm_match_wait copies piece i
-     * to the caller while piece i + 1 is still on the bus (a 1242x375 map: 1.86 MB, ~40 us of DMA + ~90 us of memcpy in sequence otherwise) */
+    handover async_out[3];       /* the map (or depth), the confidence, the right view's map */
+    int async_n;
+    /* the first of them may come back in async_chunks pieces, an event behind each but the last: sgm_match_wait copies piece i to the
+     * caller while piece i + 1 is still on the bus (a 1242x375 map: 1.86 MB, ~40 us of DMA + ~90 us of memcpy in sequence otherwise) */
     void* ev_chunk[4];
     int async_chunks;
 };
@@ -1418,12 +1417,18 @@ static void collect_timing(sgm_instance* s)
     }
 }
 
+#define TILED_MATCH "the instance is in row-tile mode (sgm_set_rows): use the sgm_tile_* sequence"
+/* what every whole-frame entry point checks first: an initialized instance (.c:70), all of its buffers (.c:73), no row tile */
+static bool whole_frames(sgm_instance* s, bool buffers, const char* tiled)
+{
+    if (!s || !s->initialized || !buffers) return false;
+    if (row_tiled(s)) FAIL("%s", tiled);
+    return true;
+}
+
 bool sgm_match_device(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left)
 {
-    if (!s || !s->initialized) return false;                     /* .c:70 */
-    if (!d_left || !d_right) return false;                       /* .c:73 */
-    if (!d_disp_left) return false;
-    if (row_tiled(s)) FAIL("the instance is in row-tile mode (sgm_set_rows): use the sgm_tile_* sequence");
+    if (!whole_frames(s, d_left && d_right && d_disp_left, TILED_MATCH)) return false;
     return run_pipeline(s, d_left, d_right, d_disp_left, NULL, NULL);
 }
 
@@ -1435,34 +1440,30 @@ bool sgm_synchronize(sgm_instance* s)
     return true;
 }
 
-/* Hands the result of a queued sgm_match_async to its caller: waits for the stream, copies the staged disparity map
- * to the caller's buffer (nothing to copy when that buffer was pinned: the device wrote it). */
+/* Hands the result of a queued host-pointer match to its caller: waits for the stream, copies every staged output to the caller's
+ * buffer (.c:122).  The list is empty again on every way out: the next match starts clean. */
 bool sgm_match_wait(sgm_instance* s)
 {
     if (!s) return false;
     if (!s->async_pending) return true;
     s->async_pending = false;
+    const int n = s->async_n, chunks = s->async_chunks;
+    s->async_n = 0;
+    s->async_chunks = 1;
     size_t done = 0;
-    const int chunks = s->async_chunks;
-    s->async_chunks = 1;                                         /* whatever happens below, the next match starts clean */
-    if (s->async_out && chunks > 1) {
+    if (n > 0 && chunks > 1) {
         /* the pieces as they arrive; a map that turns out invalid (sgm_synchronize below) has been handed over in part, as a
          * failed SGM_Match leaves its output undefined */
-        const size_t piece = s->async_bytes / (size_t)chunks / 4 * 4;
+        const size_t piece = s->async_out[0].bytes / (size_t)chunks / 4 * 4;
         for (int i = 0; i + 1 < chunks; ++i) {
             if (sgmd_event_sync(s->device, s->ev_chunk[i]) != 0) break;
-            memcpy((char*)s->async_out + done, (const char*)s->h_disp.p + done, piece);
+            memcpy((char*)s->async_out[0].dst + done, (const char*)s->async_out[0].src + done, piece);
             done += piece;
         }
     }
-    if (!sgm_synchronize(s)) { s->async_out_r = NULL; return false; }
-    if (s->async_out) memcpy((char*)s->async_out + done, (const char*)s->h_disp.p + done, s->async_bytes - done);   /* .c:122 */
-    if (s->async_conf_out) memcpy(s->async_conf_out, s->h_conf.p, s->async_bytes / sizeof(float) * sizeof(uint16_t));
-    if (s->async_out_r) memcpy(s->async_out_r, s->h_disp_r.p, s->async_bytes);
-    s->async_out = NULL;
-    s->async_conf_out = NULL;
-    s->async_out_r = NULL;
-    s->async_chunks = 1;
+    if (!sgm_synchronize(s)) return false;
+    for (int i = 0; i < n; ++i, done = 0)
+        memcpy((char*)s->async_out[i].dst + done, (const char*)s->async_out[i].src + done, s->async_out[i].bytes - done);
     return true;
 }
 
@@ -1474,11 +1475,11 @@ static int ensure_conf(sgm_instance* s, bool host_staging)
     return reserve_all(s, maps, host_staging ? 2 : 1, 0) ? 0 : -1;
 }
 
+#define TILED_CONF "the matching confidence works on whole frames: not available in row-tile mode (sgm_set_rows)"
 /* what every confidence entry point checks before it queues anything */
 static bool conf_ready(sgm_instance* s, const void* l, const void* r, const void* disp, const void* conf)
 {
-    if (!s || !s->initialized || !l || !r || !disp || !conf) return false;
-    if (row_tiled(s)) FAIL("the matching confidence works on whole frames: not available in row-tile mode (sgm_set_rows)");
+    if (!whole_frames(s, l && r && disp && conf, TILED_CONF)) return false;
     if (!conf_available()) FAIL("the matching confidence is not part of this build");
     return true;
 }
@@ -1489,37 +1490,59 @@ bool sgm_match_confidence_device(sgm_instance* s, const uint8_t* d_left, const u
     return run_pipeline(s, d_left, d_right, d_disp, d_conf, NULL);
 }
 
-/* The frame of the host-pointer entries (sgm_match_async and its confidence form, sgm_match_planes_async): what they check before
- * they queue anything -- afterwards the staging buffers are free again */
+/* The frame of the host-pointer entries (sgm_match_async and its confidence form, sgm_match_both_async, sgm_match_planes_async):
+ * validate and wait for the match before (afterwards the staging buffers are free again), see which output buffers of the caller
+ * are page-locked (outputs_pinned), size the staging, upload the images, run the pipeline, queue the outputs (queue_outputs). */
 static bool host_entry_ready(sgm_instance* s, const void* in_a, const void* in_b, const void* out)
 {
-    if (!s || !s->initialized) return false;                     /* .c:70 */
-    if (!in_a || !in_b) return false;                            /* .c:73 */
-    if (!out) return false;
-    if (row_tiled(s)) FAIL("the instance is in row-tile mode (sgm_set_rows): use the sgm_tile_* sequence");
-    return sgm_match_wait(s);
+    return whole_frames(s, in_a && in_b && out, TILED_MATCH) && sgm_match_wait(s);
 }
 
-/* ... H2D from the caller's buffer, staged unless that buffer is page-locked (sgm_host_alloc) ... */
+/* an output of such an entry: the caller's buffer, the page-locked staging buffer for a pageable one, where it is on the device */
+typedef struct { void* caller; const sgm_buf* staging; const sgm_buf* device; size_t offset, bytes; bool pinned; } host_out;
+
+static void outputs_pinned(sgm_instance* s, host_out* out, int n)
+{
+    for (int i = 0; i < n; ++i) out[i].pinned = sgmd_host_is_pinned(s->device, out[i].caller, out[i].bytes) != 0;
+}
+
+/* H2D from the caller's buffer, staged unless that buffer is page-locked (sgm_host_alloc) */
 static bool upload(sgm_instance* s, void* d_dst, const void* src, void* staging, size_t bytes)
 {
     if (!sgmd_host_is_pinned(s->device, src, bytes)) { memcpy(staging, src, bytes); src = staging; }
     return sgmd_h2d_async(s->device, s->stream, d_dst, src, bytes) == 0;
 }
 
-/* ... and their end: a failed entry drains the streams (queued copies may still read the caller's / staging buffers), a queued
- * one leaves what sgm_match_wait hands over -- out / conf_out: the caller's buffers the staged maps still have to be copied to
- * (NULL: none, or page-locked and written by the device) */
-static bool async_queued(sgm_instance* s, bool ok, float* out, uint16_t* conf_out, size_t bytes, int chunks)
+/* The end of such an entry (ok: everything before went well).  A failed entry drains the streams: queued copies may still read the
+ * caller's / staging buffers.  chunk_first: a staged out[0] of RESULT_CHUNK_MIN bytes or more comes back in pieces -- a single frame:
+ * 0.92 -> 0.88 ms per blocking call; batches of 8 through four pipelined instances on pageable buffers: 3500 -> 3640 fps.  Two pieces
+ * for a map of a few MB (an event and a wait per piece: 1.86 MB in 2 / 4 / 8 pieces = 0.708 / 0.733 / 0.79 ms per blocking KITTI
+ * frame), RESULT_CHUNKS for more (a batch of 8 such maps: 3520 / 3575 / 3590 fps pipelined). */
+static bool queue_outputs(sgm_instance* s, bool ok, const host_out* out, int n, bool chunk_first)
 {
-    if (!ok) {
-        sync_streams(s);
-        return false;
+    int chunks = 1;
+    s->async_n = 0;
+    for (int k = 0; ok && k < n; ++k) {
+        const host_out* o = &out[k];
+        const char* src = (const char*)o->device->p + o->offset;
+        if (k == 0 && chunk_first && !o->pinned && o->bytes >= RESULT_CHUNK_MIN) {
+            chunks = o->bytes < RESULT_CHUNK_SPLIT ? 2 : RESULT_CHUNKS;
+            for (int i = 0; ok && i < chunks - 1; ++i)
+                if (!s->ev_chunk[i]) ok = sgmd_event_create(s->device, &s->ev_chunk[i]) == 0;
+            const size_t piece = o->bytes / (size_t)chunks / 4 * 4;
+            size_t off = 0;
+            for (int i = 0; ok && i < chunks; ++i) {
+                const size_t bytes = i + 1 < chunks ? piece : o->bytes - off;
+                ok = queue_result_copy(s, (char*)o->staging->p + off, src + off, bytes) &&
+                     (i + 1 == chunks || sgmd_event_record(s->device, s->ev_chunk[i], result_stream(s)) == 0);
+                off += bytes;
+            }
+        } else
+            ok = queue_result_copy(s, o->pinned ? o->caller : o->staging->p, src, o->bytes);
+        if (!o->pinned) s->async_out[s->async_n++] = (handover){o->caller, o->staging->p, o->bytes};
     }
+    if (!ok) { s->async_n = 0; sync_streams(s); return false; }
     s->async_pending = true;
-    s->async_out = out;
-    s->async_conf_out = conf_out;
-    s->async_bytes = bytes;
     s->async_chunks = chunks;
     return true;
 }
@@ -1527,41 +1550,21 @@ static bool async_queued(sgm_instance* s, bool ok, float* out, uint16_t* conf_ou
 /* The host-pointer match without the final wait: stages the images (not at all when the caller's buffers are pinned,
  * sgm_host_alloc), queues H2D, the pipeline and D2H on the instance's stream and returns.  With a few instances
  * round-robined by the caller, the copies of one overlap the kernels of the others (separate DMA engines). */
-/* conf != NULL (sgm_match_confidence_async): the confidence map comes back behind the disparity map, through s->d_conf.p */
+/* conf != NULL (sgm_match_confidence_async): the confidence map comes back behind the disparity map, through s->d_conf.p (written by
+ * the cost sum, long done by then) */
 static bool match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left, uint16_t* conf)
 {
     if (!host_entry_ready(s, img_left, img_right, disp_left)) return false;
     const size_t px = (size_t)s->g.B * s->g.W * s->g.H;           /* batch > 1: B consecutive frames */
-    const bool conf_pinned = conf && sgmd_host_is_pinned(s->device, conf, px * sizeof(uint16_t)) != 0;
-    if (conf && ensure_conf(s, !conf_pinned) != 0) FAIL("device allocation failed for the confidence map");
-    const size_t bytes = px * sizeof(float);
+    host_out out[2] = {{disp_left, &s->h_disp, &s->d_disp, 0, px * sizeof(float), false},
+                       {conf, &s->h_conf, &s->d_conf, 0, px * sizeof(uint16_t), false}};
+    const int n = conf ? 2 : 1;
+    outputs_pinned(s, out, n);
+    if (conf && ensure_conf(s, !out[1].pinned) != 0) FAIL("device allocation failed for the confidence map");
     /* the left image is on the bus while the right one is staged */
-    bool ok = upload(s, s->d_left.p, img_left, s->h_left.p, px) && upload(s, s->d_right.p, img_right, s->h_right.p, px);
-    const bool out_pinned = sgmd_host_is_pinned(s->device, disp_left, bytes) != 0;
-    ok = ok && run_pipeline(s, s->d_left.p, s->d_right.p, s->d_disp.p, conf ? s->d_conf.p : NULL, NULL);
-    int chunks = 1;
-    if (ok && !out_pinned && bytes >= RESULT_CHUNK_MIN) {        /* a single frame: 0.92 -> 0.88 ms per blocking call; batches of 8 through
-                                                                   four pipelined instances on pageable buffers: 3500 -> 3640 fps */
-        /* two pieces for a map of a few MB (an event and a wait per piece: 1.86 MB in 2 / 4 / 8 pieces = 0.708 / 0.733 / 0.79 ms per
-         * blocking KITTI frame), RESULT_CHUNKS for more (a batch of 8 such maps: 3520 / 3575 / 3590 fps pipelined) */
-        chunks = bytes < RESULT_CHUNK_SPLIT ? 2 : RESULT_CHUNKS;
-        for (int i = 0; ok && i < chunks - 1; ++i)
-            if (!s->ev_chunk[i]) ok = sgmd_event_create(s->device, &s->ev_chunk[i]) == 0;
-    }
-    if (ok && chunks > 1) {
-        const size_t piece = bytes / (size_t)chunks / 4 * 4;
-        size_t off = 0;
-        for (int i = 0; ok && i < chunks; ++i) {
-            const size_t n = i + 1 < chunks ? piece : bytes - off;
-            ok = queue_result_copy(s, (char*)s->h_disp.p + off, (const char*)s->d_disp.p + off, n) &&
-                 (i + 1 == chunks || sgmd_event_record(s->device, s->ev_chunk[i], result_stream(s)) == 0);
-            off += n;
-        }
-    } else if (ok)
-        ok = queue_result_copy(s, out_pinned ? (void*)disp_left : s->h_disp.p, s->d_disp.p, bytes);
-    if (ok && conf)                       /* the confidence behind the map: written by the cost sum, long done by then */
-        ok = queue_result_copy(s, conf_pinned ? (void*)conf : s->h_conf.p, s->d_conf.p, px * sizeof(uint16_t));
-    return async_queued(s, ok, out_pinned ? NULL : disp_left, conf_pinned ? NULL : conf, bytes, chunks);
+    const bool ok = upload(s, s->d_left.p, img_left, s->h_left.p, px) && upload(s, s->d_right.p, img_right, s->h_right.p, px) &&
+                    run_pipeline(s, s->d_left.p, s->d_right.p, s->d_disp.p, conf ? s->d_conf.p : NULL, NULL);
+    return queue_outputs(s, ok, out, n, true);
 }
 
 bool sgm_match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left)
@@ -1587,11 +1590,11 @@ bool sgm_match_confidence(sgm_instance* s, const uint8_t* img_left, const uint8_
 
 /* ------------------------------------------------------------------ both views' maps from one match (extension) */
 
+#define TILED_BOTH "both views' maps need whole frames: not available in row-tile mode (sgm_set_rows)"
 /* what every sgm_match_both entry point checks before it queues (or allocates) anything */
 static bool both_ready(sgm_instance* s, const void* l, const void* r, const void* disp_l, const void* disp_r)
 {
-    if (!s || !s->initialized || !l || !r || !disp_l || !disp_r) return false;
-    if (row_tiled(s)) FAIL("both views' maps need whole frames: not available in row-tile mode (sgm_set_rows)");
+    if (!whole_frames(s, l && r && disp_l && disp_r, TILED_BOTH)) return false;
     if (s->fill_on || s->refine_on)
         FAIL("sgm_match_both does not combine with hole filling or the refinement: their class map and confidence are defined for one view");
     if (!both_available()) FAIL("sgm_match_both is not part of this build");
@@ -1610,16 +1613,14 @@ bool sgm_match_both_async(sgm_instance* s, const uint8_t* img_left, const uint8_
 {
     if (!both_ready(s, img_left, img_right, disp_left, disp_right) || !sgm_match_wait(s)) return false;
     const size_t px = (size_t)s->g.B * s->g.W * s->g.H, bytes = px * sizeof(float);
-    const bool l_pinned = sgmd_host_is_pinned(s->device, disp_left, bytes) != 0, r_pinned = sgmd_host_is_pinned(s->device, disp_right, bytes) != 0;
-    if (ensure_both(s, s->keep_stages != 0, !r_pinned) != 0) return false;
-    const both_out out = {NULL, NULL};
-    bool ok = upload(s, s->d_left.p, img_left, s->h_left.p, px) && upload(s, s->d_right.p, img_right, s->h_right.p, px);
-    ok = ok && run_pipeline(s, s->d_left.p, s->d_right.p, s->d_both_raw.p, NULL, &out);
-    ok = ok && queue_result_copy(s, l_pinned ? (void*)disp_left : s->h_disp.p, s->d_both_maps.p, bytes) &&
-         queue_result_copy(s, r_pinned ? (void*)disp_right : s->h_disp_r.p, (const char*)s->d_both_maps.p + bytes, bytes);
-    if (!async_queued(s, ok, l_pinned ? NULL : disp_left, NULL, bytes, 1)) return false;
-    s->async_out_r = r_pinned ? NULL : disp_right;
-    return true;
+    host_out out[2] = {{disp_left, &s->h_disp, &s->d_both_maps, 0, bytes, false},
+                       {disp_right, &s->h_disp_r, &s->d_both_maps, bytes, bytes, false}};
+    outputs_pinned(s, out, 2);
+    if (ensure_both(s, s->keep_stages != 0, !out[1].pinned) != 0) return false;
+    const both_out maps = {NULL, NULL};
+    const bool ok = upload(s, s->d_left.p, img_left, s->h_left.p, px) && upload(s, s->d_right.p, img_right, s->h_right.p, px) &&
+                    run_pipeline(s, s->d_left.p, s->d_right.p, s->d_both_raw.p, NULL, &maps);
+    return queue_outputs(s, ok, out, 2, false);
 }
 
 bool sgm_match_both(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left, float* disp_right)
@@ -1704,7 +1705,8 @@ bool sgm_match_planes_async(sgm_instance* s, const uint8_t* planes, float fx, fl
     if (ensure_planes_io(s) != 0) FAIL("device allocation failed for the colour planes of %dx%d", s->g.W, s->g.H);
     const int dev = s->device;
     const size_t fpx = (size_t)s->g.W * s->g.H, px = (size_t)s->g.B * fpx;
-    const bool out_pinned = sgmd_host_is_pinned(dev, depth, px * sizeof(float)) != 0;
+    host_out out = {depth, &s->h_disp, &s->d_depth, 0, px * sizeof(float), false};
+    outputs_pinned(s, &out, 1);
     bool ok = upload(s, s->d_bgr.p, planes, s->h_bgr.p, 6 * px);
     for (int f = 0; ok && f < s->g.B; ++f) {                    /* frame f: left B G R, right B G R (server.py:105-131) */
         const char* fr = (const char*)s->d_bgr.p + (size_t)f * 6 * fpx;
@@ -1712,12 +1714,9 @@ bool sgm_match_planes_async(sgm_instance* s, const uint8_t* planes, float fx, fl
              sgmd_gray_planes(dev, s->stream, fr + 3 * fpx, fpx, 76, (char*)s->d_right.p + f * fpx) == 0;
     }
     ok = ok && run_pipeline(s, s->d_left.p, s->d_right.p, s->d_disp.p, NULL, NULL);
-    void* st = result_stream(s);
     /* the depth conversion reads the map the next match's cost sum rewrites: "result done" moves behind it (not behind the copy) */
-    ok = ok && sgmd_depth(dev, st, s->d_disp.p, px, fx, baseline, doffs, s->d_depth.p) == 0 && rerecord_result_event(s) == 0 &&
-         queue_result_copy(s, out_pinned ? (void*)depth : s->h_disp.p, s->d_depth.p, px * sizeof(float));
-    /* one copy: no chunk events of an earlier match to wait for */
-    return async_queued(s, ok, out_pinned ? NULL : depth, NULL, px * sizeof(float), 1);
+    ok = ok && sgmd_depth(dev, result_stream(s), s->d_disp.p, px, fx, baseline, doffs, s->d_depth.p) == 0 && rerecord_result_event(s) == 0;
+    return queue_outputs(s, ok, &out, 1, false);                /* one copy: no chunk events of an earlier match to wait for */
 }
 
 bool sgm_match_planes(sgm_instance* s, const uint8_t* planes, float fx, float baseline, float doffs, float* depth)

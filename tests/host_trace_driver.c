@@ -1,9 +1,8 @@
 /* TEST INFRASTRUCTURE (tests/test_host_call_trace.py, tests/record_host_call_trace.py): drives one build of the product's C host
- * (csrc/sgm_host.c) on the stand-in device (tests/stub_device.c + stub_device_conf.c + stub_device_refine.c) through a fixed list of
- * scenarios.
+ * (csrc/sgm_host.c) on the stand-in device (tests/stub_device.c) through a fixed list of scenarios.
  *
  *   host_trace_driver trace    every scenario once; prints, as JSON, the unfiltered log of device calls of every step (names and
- *                              arguments; the confidence / refinement launches of stubc_* / stubr_* merged in at their positions).
+ *                              arguments; the confidence / refinement launches with the owner of their confidence map).
  *                              A step is "init" (create / initialize / reset / destroy) or "frame" (everything a match does).
  *   host_trace_driver refuse   every scenario once per allocation it performs, with that allocation refused: the step that meets
  *                              it must return false, a reset at the same shape must then succeed, and the instance is destroyed
@@ -22,23 +21,17 @@ const char* stub_log_name(int i);
 int stub_log_arg(int i);
 void stub_fail_alloc_at(int nth);
 int stub_alloc_count(void);
-void stubc_clear(void);
-int stubc_log_size(void);
-const char* stubc_log_name(int i);
-int stubc_log_arg(int i);
-int stubc_log_pos(int i);
-const void* stubc_log_dst(int i);
-void stubr_clear(void);
-int stubr_log_size(void);
-int stubr_log_flags(int i);
-int stubr_log_pos(int i);
-const void* stubr_log_conf(int i);
-float stubr_log_l0(int i);
+const void* stub_log_ptr(int i, int second);
+float stub_log_float(int i);
 
-enum { WA = 48, HA = 20, WB = 70, HB = 33, WT = 48, HT = 40, MAXPX = 4 * 6 * 70 * 40 };
+void stub_set_pinned(int slot, const void* p);
+
+/* W2 x H2: a map of 300 KiB (handed over in two pieces); B4 frames of W4 x H4: one of 4.1 MiB (four pieces, each above what the
+ * stand-in copies for real: its device memory is capped) */
+enum { WA = 48, HA = 20, WB = 70, HB = 33, WT = 48, HT = 40, W2 = 320, H2 = 240, W4 = 640, H4 = 424, B4 = 4, MAXPX = B4 * W4 * H4 };
 static uint8_t g_img[MAXPX];
-static float g_out[4 * 70 * 40];
-static uint16_t g_conf[4 * 70 * 40];
+static float g_out[MAXPX], g_out_r[4 * 70 * 40];
+static uint16_t g_conf[W2 * H2];
 static uint8_t g_rows[4 * 3 * 70 * 320];
 
 static SGMOption options(int d)
@@ -61,8 +54,6 @@ static SGMOption g_opt;
 static int g_allocs_before;          /* stub_alloc_count() when the scenario began */
 static int g_refused;                /* refuse mode: a step has met the refused allocation (the scenario ends there) */
 
-static void clear_logs(void) { stub_clear(); stubc_clear(); stubr_clear(); }
-
 static const char* whose(const void* p) { return p == NULL ? "none" : (p == (const void*)g_conf ? "caller" : "internal"); }
 
 static void flush_step(const char* path, const char* what)
@@ -71,18 +62,17 @@ static void flush_step(const char* path, const char* what)
     if (!g_refuse) {
         printf("%s\n    {\"path\": \"%s\", \"call\": \"%s\", \"log\": [", g_first_step ? "" : ",", path, what);
         g_first_step = 0;
-        int c = 0, r = 0, first = 1;
-        for (int i = 0; i <= n; ++i) {
-            for (; c < stubc_log_size() && stubc_log_pos(c) <= i; ++c, first = 0)
-                printf("%s[\"%s\", %d, \"%s\"]", first ? "" : ", ", stubc_log_name(c), stubc_log_arg(c), whose(stubc_log_dst(c)));
-            for (; r < stubr_log_size() && stubr_log_pos(r) <= i; ++r, first = 0)
-                printf("%s[\"refine_pass\", %d, \"%s\", \"%.9g\"]", first ? "" : ", ", stubr_log_flags(r), whose(stubr_log_conf(r)),
-                       (double)stubr_log_l0(r));
-            if (i < n) { printf("%s[\"%s\", %d]", first ? "" : ", ", stub_log_name(i), stub_log_arg(i)); first = 0; }
+        /* the confidence launchers with whose map they write, the refinement with whose confidence it reads and its L_t[0] */
+        for (int i = 0; i < n; ++i) {
+            const char* name = stub_log_name(i);
+            printf("%s[\"%s\", %d", i ? ", " : "", name, stub_log_arg(i));
+            if (strcmp(name, "refine_pass") == 0) printf(", \"%s\", \"%.9g\"", whose(stub_log_ptr(i, 0)), (double)stub_log_float(i));
+            else if (strstr(name, "_conf")) printf(", \"%s\"", whose(stub_log_ptr(i, 0)));
+            printf("]");
         }
         printf("]}");
     }
-    clear_logs();
+    stub_clear();
 }
 
 /* a step of a scenario: in refuse mode a false answer is the refused allocation showing */
@@ -111,7 +101,7 @@ static bool init(int w, int h, const SGMOption* o, bool reset)
 static bool fresh(void)
 {
     g_s = sgm_create(0);
-    clear_logs();
+    stub_clear();
     return g_s != NULL;
 }
 
@@ -302,6 +292,75 @@ static int fused_last_sweep(void)              /* SGM_UPSUM=1 is in the environm
     return 0;
 }
 
+#define MATCH_BOTH() sgm_match_both(g_s, g_img, g_img, g_out, g_out_r)
+
+static int both_pageable(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", MATCH_BOTH());
+    STEP("frame", MATCH_BOTH());                                  /* no reset: nothing new is allocated, S accumulates once */
+    STEP("frame", MATCH());
+    STEP("init", RESET(WB, HB, &o));
+    STEP("frame", MATCH_BOTH());
+    return 0;
+}
+
+static int both_left_pinned_right_staged(void)
+{
+    const SGMOption o = options(16);
+    stub_set_pinned(0, g_out);                                    /* (run_scenario unpins it) */
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", MATCH_BOTH());
+    STEP("frame", sgm_match_both_async(g_s, g_img, g_img, g_out, g_out_r));
+    STEP("frame", sgm_match_both_async(g_s, g_img, g_img, g_out, g_out_r));
+    STEP("frame", sgm_match_wait(g_s));
+    return 0;
+}
+
+static int both_device(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", sgm_match_both_device(g_s, g_img, g_img, g_out, g_out_r) && sgm_synchronize(g_s));
+    STEP("frame", sgm_match_both_device(g_s, g_img, g_img, g_out, g_out_r) && sgm_synchronize(g_s));
+    STEP("frame", MATCH_BOTH());                                  /* the right map's staging comes with the first host form */
+    return 0;
+}
+
+static int both_keep_stages(void)
+{
+    const SGMOption o = options(16);
+    sgm_keep_stages(g_s, 1);
+    STEP("init", INIT(WA, HA, &o));
+    STEP("frame", MATCH_BOTH());
+    STEP("frame", MATCH_BOTH());
+    return 0;
+}
+
+static int result_in_two_pieces(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", INIT(W2, H2, &o));
+    STEP("frame", sgm_match_async(g_s, g_img, g_img, g_out));
+    STEP("frame", sgm_match_wait(g_s));
+    STEP("frame", sgm_match_async(g_s, g_img, g_img, g_out));
+    STEP("frame", sgm_match_planes_async(g_s, g_img, 1000.f, 100.f, 0.f, g_out));    /* waits for the pieces itself; comes back whole */
+    STEP("frame", sgm_match_wait(g_s));
+    STEP("frame", sgm_match_confidence(g_s, g_img, g_img, g_out, g_conf));  /* the map in pieces, the confidence behind it */
+    return 0;
+}
+
+static int result_in_four_pieces(void)
+{
+    const SGMOption o = options(16);
+    STEP("init", sgm_set_batch(g_s, B4) && INIT(W4, H4, &o));
+    STEP("frame", sgm_match_async(g_s, g_img, g_img, g_out));
+    STEP("frame", sgm_match_wait(g_s));
+    STEP("frame", MATCH());
+    return 0;
+}
+
 static bool default_init(int w, int h, const SGMOption* o)
 {
     g_w = w; g_h = h; g_opt = *o;
@@ -344,6 +403,12 @@ static const struct {
     {"stage_cus", stage_cus, true, NULL, 0},
     {"fused_last_sweep", fused_last_sweep, true, "SGM_UPSUM", 0},
     {"default_instance", default_instance, false, NULL, 1},
+    {"both_pageable", both_pageable, true, NULL, 0},
+    {"both_left_pinned_right_staged", both_left_pinned_right_staged, true, NULL, 0},
+    {"both_device", both_device, true, NULL, 0},
+    {"both_keep_stages", both_keep_stages, true, NULL, 0},
+    {"result_in_two_pieces", result_in_two_pieces, true, NULL, 0},
+    {"result_in_four_pieces", result_in_four_pieces, true, NULL, 0},
 };
 #define N_SCENARIOS ((int)(sizeof k_scenarios / sizeof k_scenarios[0]))
 
@@ -358,10 +423,12 @@ static int run_scenario(int i, int refuse_at)
     const bool made = !k_scenarios[i].own_instance || fresh();
     if (k_scenarios[i].env) unsetenv(k_scenarios[i].env);
     if (!made) return 1;
-    clear_logs();
+    stub_clear();
     if (k_scenarios[i].own_instance) g_allocs_before = stub_alloc_count();      /* else before the sgm_create inside the scenario */
     if (refuse_at >= 0) stub_fail_alloc_at(refuse_at);
-    if (k_scenarios[i].run() != 0) return 1;
+    const int rc = k_scenarios[i].run();
+    stub_set_pinned(0, NULL);
+    if (rc != 0) return 1;
     if (refuse_at >= 0) {
         if (!g_refused) { fprintf(stderr, "host_trace_driver: %s: allocation %d was refused and no call failed\n", g_scenario, refuse_at); return 1; }
         stub_fail_alloc_at(-1);

@@ -11,23 +11,19 @@ import subprocess
 import sys
 import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "soc_project_stereo_matching_amd", "csrc")
-TESTS = os.path.join(ROOT, "tests")
-GOLDEN = os.path.join(TESTS, "golden", "host_call_trace.json")
-STUBS = ["stub_device.c", "stub_device_conf.c", "stub_device_refine.c"]
+import standin
+
+GOLDEN = os.path.join(standin.TESTS, "golden", "host_call_trace.json")
 
 
-def build_driver(host_c, exe, extra=()):
-    """host_trace_driver + the given sgm_host.c + the stand-in device -> exe (the headers are the tree's)"""
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=c11", "-D_GNU_SOURCE", *extra, "-I", CSRC, "-o", exe,
-                           os.path.join(TESTS, "host_trace_driver.c"), host_c] + [os.path.join(TESTS, s) for s in STUBS] +
-                          ["-lm", "-lpthread"])
-    return exe
+def build_driver(host_c, workdir, sanitize=False):
+    """host_trace_driver + the given sgm_host.c + the stand-in device -> the executable (the headers are the tree's)"""
+    return standin.build(workdir, sanitize=sanitize, extra_sources=[os.path.join(standin.TESTS, "host_trace_driver.c")],
+                         exe="host_trace_driver", host_c=host_c, flags=("-g", "-static-libasan") if sanitize else ("-g",))
 
 
 def record(host_c, workdir):
-    exe = build_driver(host_c, os.path.join(workdir, "host_trace_driver"))
+    exe = build_driver(host_c, workdir)
     env = {k: v for k, v in os.environ.items() if not k.startswith("SGM_")}
     out = subprocess.run([exe, "trace"], capture_output=True, text=True, env=env, timeout=120)
     if out.returncode != 0:

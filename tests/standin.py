@@ -1,0 +1,73 @@
+"""The stand-in device of the CPU tests (tests/stub_device.c), built with the product's C host (csrc/sgm_host.c) and read back.
+
+    build(tmpdir, without=(), sanitize=False, extra_sources=(), exe=None)   the loaded test-only library, or the path of an executable
+    log(L)                                                                  the device calls since the last L.stub_clear()
+"""
+import collections
+import ctypes as C
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "soc_project_stereo_matching_amd", "csrc")
+TESTS = os.path.join(ROOT, "tests")
+HOST_C = os.path.join(CSRC, "sgm_host.c")
+GROUPS = ("conf", "refine", "both")              # launcher groups of stub_device.c that -DSTUB_NO_<GROUP> compiles out
+SANITIZE = ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
+# tests/host_sanitize_driver.c and what it drives beside the host: extra_sources of its build
+SANITIZE_DRIVER = [os.path.join(TESTS, "host_sanitize_driver.c"), os.path.join(CSRC, "sgm_tile_sched.c"), os.path.join(CSRC, "sgm_tiles.c")]
+
+# a device call: the launcher's name, its int argument, up to two of its pointers (None: not given), one float
+Entry = collections.namedtuple("Entry", "name arg a b f")
+
+_p, _i, _f, _b, _z, _u16 = C.c_void_p, C.c_int, C.c_float, C.c_bool, C.c_size_t, C.c_uint16
+# restype, argtypes of what the tests call through ctypes (whatever a build lacks is skipped)
+SIGNATURES = {
+    "sgm_create": (_p, [_i]), "sgm_destroy": (None, [_p]),
+    "sgm_initialize": (_b, [_p, _u16, _u16, _p]), "sgm_reset": (_b, [_p, _u16, _u16, _p]),
+    "sgm_match": (_b, [_p] * 4), "sgm_match_async": (_b, [_p] * 4), "sgm_match_device": (_b, [_p] * 4),
+    "sgm_match_wait": (_b, [_p]), "sgm_synchronize": (_b, [_p]),
+    "sgm_match_confidence": (_b, [_p] * 5), "sgm_match_confidence_async": (_b, [_p] * 5), "sgm_match_confidence_device": (_b, [_p] * 5),
+    "sgm_match_both": (_b, [_p] * 5), "sgm_match_both_async": (_b, [_p] * 5), "sgm_match_both_device": (_b, [_p] * 5),
+    "sgm_depth_from_both": (_b, [_p, _p, _p, _z, _f, _f, _f, _f, _p]),
+    "sgm_set_refine": (_b, [_p, _i, _f, _f, _i, _i]), "SGM_SetRefine": (_b, [_i, _f, _f, _i, _i]),
+    "sgm_refine_disparity": (_b, [_p] * 4),
+    "sgm_set_batch": (_b, [_p, _i]), "sgm_set_fill_holes": (_b, [_p, _i]), "sgm_set_overlap_post": (_b, [_p, _i]),
+    "sgm_set_rows": (_b, [_p, _i, _i]), "sgm_set_reference_view": (None, [_p, _i]), "sgm_keep_stages": (None, [_p, _i]),
+    "sgm_fused_sweep_rows": (_i, [_p]), "sgm_read_stage": (_z, [_p, _i, _p, _z]),
+    "stub_log_name": (C.c_char_p, [_i]), "stub_log_arg": (_i, [_i]), "stub_log_ptr": (_p, [_i, _i]), "stub_log_float": (_f, [_i]),
+    "stub_fail_at": (None, [C.c_char_p, _i]), "stub_set_pinned": (None, [_i, _p]), "stub_toy_compute": (None, [_i]),
+}
+
+
+def build(tmpdir, without=(), sanitize=False, extra_sources=(), exe=None, host_c=HOST_C, flags=(), libs=()):
+    """host_c + tests/stub_device.c (without the launcher groups named) + extra_sources -> a shared library under tmpdir, loaded
+    with the SIGNATURES set; or, with exe (a file name), that executable's path."""
+    assert set(without) <= set(GROUPS), without
+    tag = "".join("_no" + g for g in without) + ("_san" if sanitize else "")
+    out = os.path.join(str(tmpdir), exe if exe else "libsgm_standin%s.so" % tag)
+    subprocess.check_call(["gcc", "-O1", "-std=c11", "-D_GNU_SOURCE", "-I", CSRC, *(SANITIZE if sanitize else ()), *flags,
+                           *(() if exe else ("-fPIC", "-shared")), *("-DSTUB_NO_" + g.upper() for g in without), "-o", out,
+                           *extra_sources, host_c, os.path.join(TESTS, "stub_device.c"), *libs, "-lm", "-ldl", "-lpthread"])
+    if exe:
+        return out
+    L = C.CDLL(out)
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if hasattr(L, name):
+            getattr(L, name).restype, getattr(L, name).argtypes = restype, argtypes
+    return L
+
+
+def log(L):
+    return [Entry(L.stub_log_name(i).decode(), L.stub_log_arg(i), L.stub_log_ptr(i, 0), L.stub_log_ptr(i, 1), L.stub_log_float(i))
+            for i in range(L.stub_log_size())]
+
+
+def launches(L, drop=("sync", "h2d", "d2h", "alloc", "memset")):
+    """(name, arg) of the device calls, without the kinds in drop"""
+    return [(e.name, e.arg) for e in log(L) if e.name not in drop]
+
+
+def calls(L, *names):
+    """the entries of the launchers named"""
+    return [e for e in log(L) if e.name in names]

@@ -1,11 +1,14 @@
 /*
- * stub_device.c -- TEST INFRASTRUCTURE ONLY (tests/test_host_error_paths.py).
+ * stub_device.c -- TEST INFRASTRUCTURE ONLY (tests/standin.py builds it; the *_cpu.py, host_* and tiles tests use it).
  *
  * A stand-in for the HIP side of csrc/sgm_device.h so that the product's C host (csrc/sgm_host.c) can be driven on a
  * machine without a GPU: "device" memory is malloc, copies are memcpy, kernel launchers compute nothing -- they append
- * their name (and the arguments the tests look at) to a log and can be told to refuse the n-th call.  This checks
+ * their name (and the arguments the tests look at) to ONE log and can be told to refuse the n-th call.  This checks
  * the ORDER of the stages and the error paths of the host, never results.  It is linked with sgm_host.c into a
  * test-only library under a temporary directory; nothing of it is part of libsgm_mi355x.so.
+ *
+ * The launchers sgm_host.c references weakly are compiled out by -DSTUB_NO_CONF (confidence), -DSTUB_NO_REFINE (refinement and
+ * hole filling) and -DSTUB_NO_BOTH (both views): a host linked with such a stand-in has no such entry points.
  */
 #include "sgm_device.h"
 
@@ -14,35 +17,23 @@
 #include <stdlib.h>
 #include <string.h>
 
+/* a log entry: the launcher's name, an int the tests look at, up to two of its pointers, one float (the refinement's L_t[0]) */
 #define LOG_MAX 4096
-static char g_log[LOG_MAX][40];
-static int g_log_arg[LOG_MAX];
+static struct { char name[40]; int arg; const void *a, *b; float f; } g_log[LOG_MAX];
 static int g_n;
 static char g_fail_name[40];
 static int g_fail_countdown = -1;
 
 void stub_clear(void) { g_n = 0; g_fail_countdown = -1; g_fail_name[0] = 0; }
 int stub_log_size(void) { return g_n; }
-const char* stub_log_name(int i) { return (i >= 0 && i < g_n) ? g_log[i] : ""; }
-int stub_log_arg(int i) { return (i >= 0 && i < g_n) ? g_log_arg[i] : -1; }
+const char* stub_log_name(int i) { return (i >= 0 && i < g_n) ? g_log[i].name : ""; }
+int stub_log_arg(int i) { return (i >= 0 && i < g_n) ? g_log[i].arg : -1; }
+const void* stub_log_ptr(int i, int second) { return (i >= 0 && i < g_n) ? (second ? g_log[i].b : g_log[i].a) : NULL; }
+float stub_log_float(int i) { return (i >= 0 && i < g_n) ? g_log[i].f : -1.0f; }
 /* the nth (0-based) call of launcher `name` from now on returns an error */
 void stub_fail_at(const char* name, int nth) { snprintf(g_fail_name, sizeof g_fail_name, "%s", name); g_fail_countdown = nth; }
 
 static pthread_mutex_t g_mu = PTHREAD_MUTEX_INITIALIZER;     /* the tile-pipeline tests run ranks as threads */
-static int note_locked(const char* name, int arg);
-static int note(const char* name, int arg)
-{
-    pthread_mutex_lock(&g_mu);
-    const int rc = note_locked(name, arg);
-    pthread_mutex_unlock(&g_mu);
-    return rc;
-}
-static int refused_locked(const char* name);
-static int note_locked(const char* name, int arg)
-{
-    if (g_n < LOG_MAX) { snprintf(g_log[g_n], sizeof g_log[g_n], "%s", name); g_log_arg[g_n] = arg; ++g_n; }
-    return refused_locked(name);
-}
 static int refused_locked(const char* name)
 {
     if (g_fail_countdown >= 0 && strcmp(name, g_fail_name) == 0 && g_fail_countdown-- == 0) {
@@ -51,6 +42,23 @@ static int refused_locked(const char* name)
     }
     return 0;
 }
+static int note_locked(const char* name, int arg, const void* a, const void* b, float f)
+{
+    if (g_n < LOG_MAX) {
+        snprintf(g_log[g_n].name, sizeof g_log[g_n].name, "%s", name);
+        g_log[g_n].arg = arg; g_log[g_n].a = a; g_log[g_n].b = b; g_log[g_n].f = f;
+        ++g_n;
+    }
+    return refused_locked(name);
+}
+static int note_ptrs(const char* name, int arg, const void* a, const void* b, float f)
+{
+    pthread_mutex_lock(&g_mu);
+    const int rc = note_locked(name, arg, a, b, f);
+    pthread_mutex_unlock(&g_mu);
+    return rc;
+}
+static int note(const char* name, int arg) { return note_ptrs(name, arg, NULL, NULL, 0.0f); }
 
 int sgmd_device_count(void) { return 1; }
 int sgmd_device_is_gfx950(int o) { (void)o; return 1; }
@@ -76,7 +84,7 @@ int stub_alloc_count(void) { return g_alloc_count; }
 static int note_alloc(const char* name, size_t n, int logged)
 {
     pthread_mutex_lock(&g_mu);
-    const int rc = logged ? note_locked(name, (int)(n >> 10)) : refused_locked(name);
+    const int rc = logged ? note_locked(name, (int)(n >> 10), NULL, NULL, 0.0f) : refused_locked(name);
     ++g_alloc_count;
     const int refused = g_alloc_countdown >= 0 && g_alloc_countdown-- == 0;
     pthread_mutex_unlock(&g_mu);
@@ -88,9 +96,22 @@ int sgmd_free(int o, void* p) { (void)o; free(p); return 0; }
 int sgmd_alloc_pinned(int o, void** p, size_t n)
 { (void)o; *p = NULL; if (note_alloc("alloc_pinned", n, 0) != 0) return 2; *p = calloc(1, n ? n : 16); return *p ? 0 : 2; }
 int sgmd_free_pinned(int o, void* p) { (void)o; free(p); return 0; }
-int sgmd_host_is_pinned(int o, const void* p, size_t n) { (void)o; (void)p; (void)n; return 0; }
+/* nothing is page-locked but what stub_set_pinned names: slot 0 .. PIN_MAX-1 <- a host buffer that counts as page-locked
+ * (sgm_host_alloc) from now on (NULL: nothing) */
+#define PIN_MAX 8
+static const void* g_pinned[PIN_MAX];
+void stub_set_pinned(int slot, const void* p) { if (slot >= 0 && slot < PIN_MAX) g_pinned[slot] = p; }
+int sgmd_host_is_pinned(int o, const void* p, size_t n)
+{
+    (void)o; (void)n;
+    for (int i = 0; i < PIN_MAX; ++i)
+        if (p && g_pinned[i] == p) return 1;
+    return 0;
+}
 int sgmd_h2d_async(int o, void* st, void* d, const void* s, size_t n) { (void)o; (void)st; if (n <= (1u << 20)) memcpy(d, s, n); return note("h2d", (int)n); }
-int sgmd_d2h_async(int o, void* st, void* d, const void* s, size_t n) { (void)o; (void)st; if (n <= (1u << 20)) memcpy(d, s, n); return note("d2h", (int)n); }
+/* (logged with its destination and source: the tests follow a staged result from the staging buffer to the caller) */
+int sgmd_d2h_async(int o, void* st, void* d, const void* s, size_t n)
+{ (void)o; (void)st; if (n <= (1u << 20)) memcpy(d, s, n); return note_ptrs("d2h", (int)n, d, s, 0.0f); }
 int sgmd_plane_rows_copy(int o, void* st, void* planes, size_t pb, size_t ro, size_t rb, const int* dirs, int nd, int frames, void* buf, int to_buf)
 {
     (void)o; (void)st;
@@ -215,3 +236,45 @@ int sgmd_gray_planes(int o, void* st, const void* bgr, size_t n, int wr, void* g
 { (void)o; (void)st; (void)bgr; (void)wr; (void)gray; return note("gray", (int)n); }
 int sgmd_score(int o, void* st, const void* g, const void* t, size_t n, float th, double* s, unsigned long long* nv, unsigned long long* nb)
 { (void)o; (void)st; (void)g; (void)t; (void)th; *s = 0; *nv = 0; *nb = 0; return note("score", (int)n); }
+
+/* ---- the launchers sgm_host.c references weakly: each group is compiled out by its macro ---- */
+#ifndef STUB_NO_CONF                 /* logged with the confidence destination */
+int sgmd_sum_wta_conf(int o, void* st, const sgmd_geom* g, int nd, const void* pl, size_t pb, const void* ex, const void* re,
+                      const void* rc, int cap, int accumulate, void* S, int cu, float omr, void* dl, void* conf)
+{ (void)o; (void)st; (void)g; (void)nd; (void)pl; (void)pb; (void)ex; (void)re; (void)rc; (void)cap; (void)S; (void)cu; (void)omr; (void)dl;
+  return note_ptrs("sum_wta_conf", accumulate, conf, NULL, 0.0f); }
+int sgmd_sum_wta_lr_conf(int o, void* st, const sgmd_geom* g, int nd, const void* pl, size_t pb, const void* ex, const void* re,
+                         const void* rc, int cap, int accumulate, int store_S, int do_right, void* S, int cu, float omr, void* dl,
+                         void* dr, void* conf, int conf_right)
+{ (void)o; (void)st; (void)g; (void)nd; (void)pl; (void)pb; (void)ex; (void)re; (void)rc; (void)cap; (void)S; (void)cu; (void)omr; (void)dl;
+  (void)dr; return note_ptrs("sum_wta_lr_conf", accumulate | (store_S << 1) | (do_right << 2) | (conf_right << 3), conf, NULL, 0.0f); }
+int sgmd_wta_right_conf(int o, void* st, const sgmd_geom* g, const void* S, int cu, float omr, void* dr, void* conf)
+{ (void)o; (void)st; (void)g; (void)S; (void)cu; (void)omr; (void)dr; return note_ptrs("wta_right_conf", 0, conf, NULL, 0.0f); }
+#endif
+
+#ifndef STUB_NO_REFINE               /* logged with vertical | first << 1 | last << 2 | keep_invalid << 3, the confidence and guide
+                                        pointers and the table's first entry; the two hole-filling launchers are unlogged no-ops, so
+                                        that the host offers hole filling (and refuses the combination) */
+int sgmd_refine_pass(int o, void* st, const sgmd_geom* g, int vertical, const float* table, const void* guide, const void* disp,
+                     const void* conf, void* U, void* V, void* Q, int first, int last, int keep_invalid, void* out)
+{ (void)o; (void)st; (void)g; (void)disp; (void)U; (void)V; (void)Q; (void)out;
+  return note_ptrs("refine_pass", vertical | (first << 1) | (last << 2) | (keep_invalid << 3), conf, guide, table[0]); }
+int sgmd_fill_classify(int o, void* st, const sgmd_geom* g, const void* ref, const void* oth, float th, int right, int chk, void* cls)
+{ (void)o; (void)st; (void)g; (void)ref; (void)oth; (void)th; (void)right; (void)chk; (void)cls; return 0; }
+int sgmd_fill_pass(int o, void* st, const sgmd_geom* g, int R, const void* in, void* out, const void* cls, int pass)
+{ (void)o; (void)st; (void)g; (void)R; (void)in; (void)out; (void)cls; (void)pass; return 0; }
+#endif
+
+#ifndef STUB_NO_BOTH                 /* logged with their two map pointers; sgmd_lrcheck_both also fills its outputs (1.0 left, 2.0 right,
+                                        while the maps fit the allocator's cap): the tests follow the two maps to the caller's buffers */
+int sgmd_lrcheck_both(int o, void* st, const sgmd_geom* g, const void* dl, const void* dr, float th, int chk, void* out_l, void* out_r)
+{
+    (void)o; (void)st; (void)dl; (void)dr; (void)th;
+    const size_t px = (size_t)g->B * g->W * g->H;
+    if (2 * px * sizeof(float) <= (1u << 20))
+        for (size_t i = 0; i < px; ++i) { ((float*)out_l)[i] = 1.0f; ((float*)out_r)[i] = 2.0f; }
+    return note_ptrs("lrcheck_both", chk | (g->B << 8), out_l, out_r, 0.0f);
+}
+int sgmd_depth_both(int o, void* st, const void* dl, const void* dr, size_t n, float fx_l, float fx_r, float b, float doffs, void* out)
+{ (void)o; (void)st; (void)fx_l; (void)fx_r; (void)b; (void)doffs; (void)out; return note_ptrs("depth_both", (int)n, dl, dr, 0.0f); }
+#endif

@@ -6,6 +6,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import standin
 from conftest import ROOT
 
 EXE = os.path.join(ROOT, "soc_project_stereo_matching_amd", "sgm_main")
@@ -74,10 +75,8 @@ def test_image_io_is_asan_clean_on_damaged_files(tmp_path):
     if shutil.which("gcc") is None:
         pytest.skip("gcc not available")
     csrc = os.path.join(ROOT, "soc_project_stereo_matching_amd", "csrc")
-    exe = str(tmp_path / "sgm_main_asan")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=c11", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", csrc,
-                           "-o", exe, os.path.join(csrc, "sgm_main.c"), os.path.join(csrc, "sgm_image_io.c"),
-                           os.path.join(csrc, "sgm_host.c"), os.path.join(ROOT, "tests", "stub_device.c"), "-lz", "-lm"])
+    exe = standin.build(tmp_path, sanitize=True, exe="sgm_main_asan", libs=("-lz",),
+                        extra_sources=[os.path.join(csrc, "sgm_main.c"), os.path.join(csrc, "sgm_image_io.c")])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=99")
     env.pop("LD_PRELOAD", None)
     rng = np.random.RandomState(7)

@@ -1,8 +1,11 @@
 """The device calls of the C host (csrc/sgm_host.c) are its behaviour: tests/host_trace_driver.c drives it through a list of scenarios on
-the stand-in device (tests/stub_device*.c), and
+the stand-in device (tests/stub_device.c), and
 
-* the log of every step is compared with tests/golden/host_call_trace.json, recorded by tests/record_host_call_trace.py from the
-  host as it was before the buffers got one owner (reserve / k_buffers in sgm_host.c);
+* the log of every step is compared with tests/golden/host_call_trace.json, recorded by tests/record_host_call_trace.py: the
+  scenarios first_initialize .. default_instance from the host as it was before the buffers got one owner (reserve / k_buffers in
+  sgm_host.c), the scenarios both_pageable .. result_in_four_pieces from the host as it was before the host-pointer entries got one
+  result hand-over (queue_outputs / async_out in sgm_host.c), which printed the older scenarios as the first recording has them
+  but for the one table drain init_path_difference accepts;
 * every allocation the scenarios perform is refused once, under AddressSanitizer + LeakSanitizer + UBSan."""
 import json
 import os
@@ -10,10 +13,7 @@ import re
 import subprocess
 
 import record_host_call_trace as REC
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "soc_project_stereo_matching_amd", "csrc")
-HOST_C = os.path.join(CSRC, "sgm_host.c")
+from standin import HOST_C
 
 SYNC = ["sync", 0]
 
@@ -89,6 +89,7 @@ SITES = {
     "prepare_costs (census64)": (r"the match was abandoned", "census_7x7"),
     "ensure_upsum": (r"the match was abandoned", "fused_last_sweep"),
     "ensure_conf": (r"for the confidence map", None),
+    "ensure_both": (r"maps of both views", None),
     "ensure_planes_io": (r"colour planes", None),
     "upload_census_need": (r"census block map", None),
     "upload_tables": (r"uploading path tables failed", None),
@@ -98,8 +99,7 @@ SITES = {
 def test_every_allocation_refused_once_under_sanitizers(tmp_path):
     """Each allocation of each scenario is refused in a run of its own: the call that meets it returns false with the library's
     message, a reset at the same shape then succeeds, and destroying the instance leaves nothing behind."""
-    exe = REC.build_driver(HOST_C, str(tmp_path / "host_trace_driver_asan"),
-                           extra=("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan"))
+    exe = REC.build_driver(HOST_C, str(tmp_path), sanitize=True)
     env = {k: v for k, v in os.environ.items() if not k.startswith("SGM_")}
     env["ASAN_OPTIONS"] = "detect_leaks=1:abort_on_error=1"
     out = subprocess.run([exe, "refuse"], capture_output=True, text=True, env=env, timeout=600)

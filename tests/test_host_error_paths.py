@@ -7,44 +7,19 @@ stays consistent across a failed match, and that a failed host-pointer match wai
 (queued copies read the caller's buffers)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "soc_project_stereo_matching_amd", "csrc")
+import standin
 
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    out = tmp_path_factory.mktemp("hoststub") / "libsgm_hoststub.so"
-    subprocess.check_call(["gcc", "-O1", "-std=c11", "-fPIC", "-shared", "-I", CSRC, "-o", str(out),
-                           os.path.join(CSRC, "sgm_host.c"), os.path.join(ROOT, "tests", "stub_device.c"), "-lm"])
-    L = C.CDLL(str(out))
-    L.sgm_create.restype = C.c_void_p
-    L.sgm_create.argtypes = [C.c_int]
-    L.sgm_destroy.argtypes = [C.c_void_p]
-    for f in (L.sgm_initialize, L.sgm_reset):
-        f.argtypes = [C.c_void_p, C.c_uint16, C.c_uint16, C.c_void_p]
-        f.restype = C.c_bool
-    for f in (L.sgm_match, L.sgm_match_async, L.sgm_match_device):
-        f.argtypes = [C.c_void_p] * 4
-        f.restype = C.c_bool
-    L.sgm_match_wait.argtypes = [C.c_void_p]
-    L.sgm_match_wait.restype = C.c_bool
-    L.sgm_keep_stages.argtypes = [C.c_void_p, C.c_int]
-    L.stub_log_name.restype = C.c_char_p
-    L.stub_log_name.argtypes = [C.c_int]
-    L.stub_log_arg.argtypes = [C.c_int]
-    L.stub_fail_at.argtypes = [C.c_char_p, C.c_int]
-    return L
+    return standin.build(tmp_path_factory.mktemp("hoststub"))
 
 
-def log(L, drop=("sync", "h2d", "d2h", "alloc", "memset")):
-    return [(L.stub_log_name(i).decode(), L.stub_log_arg(i)) for i in range(L.stub_log_size())
-            if L.stub_log_name(i).decode() not in drop]
+log = standin.launches
 
 
 class Frame:
@@ -215,6 +190,53 @@ def test_staged_result_is_handed_over_in_pieces(host):
     assert names.count("event_sync") == 1 and names[-1] == "sync"
     assert not np.any(out == -1.0)                                   # every piece reached the caller (the stub's device memory is zeroed)
     L.sgm_destroy(s)
+
+
+@pytest.mark.parametrize("pin_map,pin_conf", [(False, False), (False, True), (True, False)],
+                         ids=["staged-staged", "staged-pinned", "pinned-staged"])
+def test_wait_copies_each_staged_output_whole_to_its_own_buffer(host, pin_map, pin_conf):
+    """A confidence match of 300 KiB of disparities: the map comes back in two pieces, the confidence behind it in one.  The staging
+    buffers (the destinations of the queued copies) are filled with a pattern before the wait: the wait must put every byte of each
+    staged output at the same offset of the caller's buffer -- the pieces of the map, then the confidence from ITS start -- and
+    leave a page-locked output alone."""
+    L = host
+    s, opt = fresh(L)
+    w, h = 320, 240
+    assert L.sgm_reset(s, w, h, C.byref(opt))
+    img = np.zeros((h, w), np.uint8)
+    out = np.full((h, w), -1.0, np.float32)
+    conf = np.full((h, w), 0xFFFF, np.uint16)
+    try:
+        L.stub_set_pinned(0, out.ctypes.data if pin_map else None)
+        L.stub_set_pinned(1, conf.ctypes.data if pin_conf else None)
+        L.stub_clear()
+        assert L.sgm_match_confidence_async(s, img.ctypes.data, img.ctypes.data, out.ctypes.data, conf.ctypes.data)
+        d2h = standin.calls(L, "d2h")                                   # a = destination, b = source
+        map_copies, conf_copy = d2h[:-1], d2h[-1]
+        assert [e.arg for e in map_copies] == ([out.nbytes] if pin_map else [out.nbytes // 2] * 2) and conf_copy.arg == conf.nbytes
+        assert (map_copies[0].a == out.ctypes.data) == pin_map and (conf_copy.a == conf.ctypes.data) == pin_conf
+        if not pin_map:
+            assert map_copies[1].a - map_copies[0].a == map_copies[1].b - map_copies[0].b == out.nbytes // 2
+        # what the device "wrote": a pattern into every destination, staging or caller
+        want = np.arange(w * h, dtype=np.float32).reshape(h, w)
+        want_conf = (np.arange(w * h) % 65521).astype(np.uint16).reshape(h, w)
+        out_before, conf_before = out.copy(), conf.copy()
+        if not pin_map:
+            C.memmove(map_copies[0].a, want.ctypes.data, want.nbytes)
+        if not pin_conf:
+            C.memmove(conf_copy.a, want_conf.ctypes.data, want_conf.nbytes)
+        assert np.array_equal(out, out_before) and np.array_equal(conf, conf_before)     # nothing reaches a pageable buffer before the wait
+        assert L.sgm_match_wait(s)
+        assert np.array_equal(out, out_before if pin_map else want)
+        assert np.array_equal(conf, conf_before if pin_conf else want_conf)
+        # handed over once: a second wait copies nothing
+        out.fill(-2.0)
+        conf.fill(7)
+        assert L.sgm_match_wait(s) and (out == -2.0).all() and (conf == 7).all()
+    finally:
+        L.stub_set_pinned(0, None)
+        L.stub_set_pinned(1, None)
+        L.sgm_destroy(s)
 
 
 def test_row_tile_instance_allocates_a_tile_not_a_frame(host):

@@ -6,18 +6,12 @@ import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "soc_project_stereo_matching_amd", "csrc")
+import standin
 
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="gcc not available")
 def test_host_is_asan_ubsan_clean(tmp_path):
-    exe = str(tmp_path / "host_sanitize_driver")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=c11", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D_GNU_SOURCE", "-I", CSRC,
-                           "-o", exe, os.path.join(ROOT, "tests", "host_sanitize_driver.c"), os.path.join(CSRC, "sgm_host.c"),
-                           os.path.join(CSRC, "sgm_tile_sched.c"), os.path.join(CSRC, "sgm_tiles.c"),
-                           os.path.join(ROOT, "tests", "stub_device.c"), "-lm", "-ldl", "-lpthread"])
+    exe = standin.build(tmp_path, sanitize=True, exe="host_sanitize_driver", extra_sources=standin.SANITIZE_DRIVER)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1")
     env.pop("LD_PRELOAD", None)
     out = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)

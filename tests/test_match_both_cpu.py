@@ -1,6 +1,6 @@
 """Both views' maps from one match (include/sgm_mi355x.h, SGM_MatchBoth) on the CPU: the exported interface, the host restatement
-of the both-views post pass by the oracle's stages, the host logic on the stand-in device (tests/stub_device.c +
-tests/stub_device_both.c), and the host under AddressSanitizer / UBSan."""
+of the both-views post pass by the oracle's stages, the host logic on the stand-in device (tests/stub_device.c), and the host
+under AddressSanitizer / UBSan."""
 import ctypes as C
 import os
 import re
@@ -10,9 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import standin
 from conftest import ROOT, case_inputs, option_from_dict
 
-CSRC = os.path.join(ROOT, "soc_project_stereo_matching_amd", "csrc")
 TINY_CASES = ["t24x16_d8", "t70x33_d16", "t20x31_d8_tall", "t40x24_d16_dmin3", "t33x33_d12_square", "t64x20_d40"]
 
 
@@ -84,102 +84,34 @@ def test_library_exports_both():
 
 # ---- host logic on the stand-in device ----------------------------------------------------------------------------------------
 
-def stub_device_object(tmp, flags=()):
-    """tests/stub_device.c as it is, with its "nothing is page-locked" sgmd_host_is_pinned renamed out of the way: stub_device_both.c
-    has the one the tests can steer (stubb_set_pinned)"""
-    obj = str(tmp / "stub_device.o")
-    subprocess.check_call(["gcc", "-O1", "-std=c11", "-fPIC", "-I", CSRC, "-Dsgmd_host_is_pinned=stub_device_never_pinned", *flags,
-                           "-c", os.path.join(ROOT, "tests", "stub_device.c"), "-o", obj])
-    return obj
-
-
-def _build(tmp_path_factory, with_both):
-    tmp = tmp_path_factory.mktemp("bothstub")
-    out = tmp / ("libboth%d.so" % with_both)
-    srcs = [os.path.join(CSRC, "sgm_host.c")]
-    if with_both:
-        srcs += [stub_device_object(tmp), os.path.join(ROOT, "tests", "stub_device_both.c"),
-                 os.path.join(ROOT, "tests", "stub_device_conf.c"), os.path.join(ROOT, "tests", "stub_device_refine.c")]
-    else:
-        srcs.append(os.path.join(ROOT, "tests", "stub_device.c"))
-    subprocess.check_call(["gcc", "-O1", "-std=c11", "-fPIC", "-shared", "-I", CSRC, "-o", str(out)] + srcs + ["-lm"])
-    L = C.CDLL(str(out))
-    L.sgm_create.restype = C.c_void_p
-    L.sgm_create.argtypes = [C.c_int]
-    L.sgm_destroy.argtypes = [C.c_void_p]
-    for f in (L.sgm_initialize, L.sgm_reset):
-        f.argtypes = [C.c_void_p, C.c_uint16, C.c_uint16, C.c_void_p]
-        f.restype = C.c_bool
-    for f in (L.sgm_match, L.sgm_match_async, L.sgm_match_device):
-        f.argtypes = [C.c_void_p] * 4
-        f.restype = C.c_bool
-    for f in (L.sgm_match_both, L.sgm_match_both_async, L.sgm_match_both_device):
-        f.argtypes = [C.c_void_p] * 5
-        f.restype = C.c_bool
-    L.sgm_depth_from_both.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_float] * 4 + [C.c_void_p]
-    L.sgm_depth_from_both.restype = C.c_bool
-    L.sgm_match_wait.argtypes = [C.c_void_p]
-    L.sgm_match_wait.restype = C.c_bool
-    L.sgm_set_reference_view.argtypes = [C.c_void_p, C.c_int]
-    L.sgm_keep_stages.argtypes = [C.c_void_p, C.c_int]
-    for name in ("sgm_set_batch", "sgm_set_fill_holes", "sgm_set_overlap_post"):
-        getattr(L, name).argtypes = [C.c_void_p, C.c_int]
-        getattr(L, name).restype = C.c_bool
-    L.sgm_set_refine.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]
-    L.sgm_set_refine.restype = C.c_bool
-    L.sgm_set_rows.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.sgm_set_rows.restype = C.c_bool
-    L.sgm_fused_sweep_rows.argtypes = [C.c_void_p]
-    L.sgm_read_stage.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-    L.sgm_read_stage.restype = C.c_size_t
-    L.stub_log_name.restype = C.c_char_p
-    L.stub_log_name.argtypes = [C.c_int]
-    L.stub_log_arg.argtypes = [C.c_int]
-    L.stub_fail_at.argtypes = [C.c_char_p, C.c_int]
-    if with_both:
-        L.stubb_log_name.restype = C.c_char_p
-        L.stubb_log_name.argtypes = [C.c_int]
-        for f in (L.stubb_log_arg, L.stubb_log_pos):
-            f.argtypes = [C.c_int]
-        for f in (L.stubb_log_left, L.stubb_log_right):
-            f.restype = C.c_void_p
-            f.argtypes = [C.c_int]
-        L.stubb_set_pinned.argtypes = [C.c_int, C.c_void_p]
-    return L
-
-
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    return _build(tmp_path_factory, True)
+    return standin.build(tmp_path_factory.mktemp("bothstub"))
 
 
 @pytest.fixture(scope="module")
 def host_old(tmp_path_factory):
-    return _build(tmp_path_factory, False)
+    return standin.build(tmp_path_factory.mktemp("bothstub"), without=("conf", "refine", "both"))
 
 
 def full_log(L):
-    return [(L.stub_log_name(i).decode(), L.stub_log_arg(i)) for i in range(L.stub_log_size())]
+    return [(e.name, e.arg) for e in standin.log(L)]
 
 
-def launches(L, drop=("sync", "h2d", "d2h", "alloc", "memset")):
-    """stub_device.c's log with the both-views launchers merged in at the position they were called"""
-    out = full_log(L)
-    if hasattr(L, "stubb_log_size"):
-        for i in reversed(range(L.stubb_log_size())):
-            out.insert(L.stubb_log_pos(i), (L.stubb_log_name(i).decode(), L.stubb_log_arg(i)))
-    return [(n, a) for n, a in out if n not in drop]
+launches = standin.launches
+
+
+def both_calls(L):
+    """the both-views launches: a, b = their left / right map"""
+    return standin.calls(L, "lrcheck_both", "depth_both")
 
 
 def clear(L):
     L.stub_clear()
-    for name in ("stubb_clear", "stubc_clear", "stubr_clear"):
-        if hasattr(L, name):
-            getattr(L, name)()
 
 
 def nothing_queued(L):
-    return [n for n, _ in full_log(L) if n != "sync"] == [] and (not hasattr(L, "stubb_log_size") or L.stubb_log_size() == 0)
+    return [n for n, _ in full_log(L) if n != "sync"] == []
 
 
 class Frame:
@@ -219,9 +151,9 @@ def test_one_cost_sum_feeds_one_post_pass_over_both_views(host, d, view):
     names = [n for n, _ in launches(L)]
     head = ["census", "aggregate", "sum_wta_lr"] if d == 16 else ["census", "aggregate", "sum_wta", "wta_right"]
     assert names == head + ["lrcheck_both", "speckle", "median"]
-    assert L.stubb_log_arg(0) == (1 | (1 << 8))                  # the check is on, on B = 1 frames
+    assert both_calls(L)[0].arg == (1 | (1 << 8))                 # the check is on, on B = 1 frames
     # the two outputs are the halves of one batch of 2 B maps
-    assert L.stubb_log_right(0) - L.stubb_log_left(0) == f.out.nbytes
+    assert both_calls(L)[0].b - both_calls(L)[0].a == f.out.nbytes
     assert (f.out == 1.0).all() and (f.out_r == 2.0).all()
     L.sgm_destroy(s)
 
@@ -232,7 +164,7 @@ def test_lr_check_off_still_finishes_both_maps(host):
     f = Frame()
     assert L.sgm_match_both(s, *f.bargs())
     assert [n for n, _ in launches(L)] == ["census", "aggregate", "sum_wta_lr", "lrcheck_both", "speckle", "median"]
-    assert L.stubb_log_arg(0) == (0 | (1 << 8))                  # plain copies of the raw maps
+    assert both_calls(L)[0].arg == (0 | (1 << 8))                 # plain copies of the raw maps
     L.sgm_destroy(s)
 
 
@@ -258,7 +190,7 @@ def test_buffers_come_with_the_first_both_call_and_only_then(host):
     assert L.sgm_reset(s, 48, 20, C.byref(opt))
     clear(L)
     assert L.sgm_match(s, *f.args())
-    assert full_log(L) == plain_first and L.stubb_log_size() == 0
+    assert full_log(L) == plain_first and both_calls(L) == []
     L.sgm_destroy(s)
 
 
@@ -283,7 +215,7 @@ def test_null_outputs_return_false_and_queue_nothing(host):
                      (None, f.right.ctypes.data, f.out.ctypes.data, f.out_r.ctypes.data)):
             clear(L)
             assert not fn(s, *args)
-            assert full_log(L) == [] and L.stubb_log_size() == 0
+            assert full_log(L) == []
     L.sgm_destroy(s)
 
 
@@ -368,8 +300,8 @@ def test_pinned_and_staged_outputs_each_go_their_own_way(host, pin_left, pin_rig
     s, opt = fresh(L, batch=2)
     f = Frame(b=2)
     try:
-        L.stubb_set_pinned(0, f.out.ctypes.data if pin_left else None)
-        L.stubb_set_pinned(1, f.out_r.ctypes.data if pin_right else None)
+        L.stub_set_pinned(0, f.out.ctypes.data if pin_left else None)
+        L.stub_set_pinned(1, f.out_r.ctypes.data if pin_right else None)
         before = L.stub_alloc_count()
         assert L.sgm_match_both_async(s, *f.bargs())
         # six device buffers at the first call, and the right map's page-locked staging exactly when that map is pageable
@@ -391,8 +323,8 @@ def test_pinned_and_staged_outputs_each_go_their_own_way(host, pin_left, pin_rig
         assert np.array_equal(f.out, want_l) and np.array_equal(f.out_r, want_r)
         # the same instance with the roles swapped: nothing of the first hand-over is left behind
         g = Frame(b=2)
-        L.stubb_set_pinned(0, g.out.ctypes.data if not pin_left else None)
-        L.stubb_set_pinned(1, g.out_r.ctypes.data if not pin_right else None)
+        L.stub_set_pinned(0, g.out.ctypes.data if not pin_left else None)
+        L.stub_set_pinned(1, g.out_r.ctypes.data if not pin_right else None)
         assert L.sgm_reset(s, 48, 20, C.byref(opt)) and L.sgm_match_both_async(s, *g.bargs())
         assert (g.out == (-1.0 if pin_left else 1.0)).all() and (g.out_r == (-1.0 if pin_right else 2.0)).all()
         f.out.fill(-5), f.out_r.fill(-5)
@@ -400,8 +332,8 @@ def test_pinned_and_staged_outputs_each_go_their_own_way(host, pin_left, pin_rig
         assert (g.out == 1.0).all() and (g.out_r == 2.0).all()
         assert (f.out == -5).all() and (f.out_r == -5).all()      # the earlier call's buffers are no longer written
     finally:
-        L.stubb_set_pinned(0, None)
-        L.stubb_set_pinned(1, None)
+        L.stub_set_pinned(0, None)
+        L.stub_set_pinned(1, None)
         L.sgm_destroy(s)
 
 
@@ -411,11 +343,11 @@ def test_pinned_inputs_are_uploaded_in_place(host):
     f = Frame()
     try:
         f.left.fill(9)
-        L.stubb_set_pinned(0, f.left.ctypes.data)
+        L.stub_set_pinned(0, f.left.ctypes.data)
         assert L.sgm_match_both_async(s, *f.bargs()) and L.sgm_match_wait(s)
         assert (f.out == 1.0).all() and (f.out_r == 2.0).all()
     finally:
-        L.stubb_set_pinned(0, None)
+        L.stub_set_pinned(0, None)
         L.sgm_destroy(s)
 
 
@@ -514,7 +446,7 @@ def test_depth_from_both_is_one_launch(host):
     s, _ = fresh(L)
     f = Frame()
     assert L.sgm_depth_from_both(s, f.out.ctypes.data, f.out_r.ctypes.data, f.out.size, 1000.0, 1001.0, 100.0, 0.0, f.out.ctypes.data)
-    assert L.stubb_log_size() == 1 and L.stubb_log_name(0) == b"depth_both" and L.stubb_log_arg(0) == f.out.size
+    assert [(e.name, e.arg) for e in both_calls(L)] == [("depth_both", f.out.size)]
     assert not L.sgm_depth_from_both(s, None, f.out_r.ctypes.data, f.out.size, 1000.0, 1001.0, 100.0, 0.0, f.out.ctypes.data)
     L.sgm_destroy(s)
 
@@ -523,13 +455,8 @@ def test_depth_from_both_is_one_launch(host):
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="gcc not available")
 def test_both_family_is_asan_ubsan_clean(tmp_path):
-    exe = str(tmp_path / "host_sanitize_both_driver")
-    san = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D_GNU_SOURCE"]
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=c11", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D_GNU_SOURCE",
-                           "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "host_sanitize_both_driver.c"),
-                           os.path.join(CSRC, "sgm_host.c"), stub_device_object(tmp_path, san),
-                           os.path.join(ROOT, "tests", "stub_device_both.c"), "-lm", "-lpthread"])
+    exe = standin.build(tmp_path, sanitize=True, exe="host_sanitize_driver", extra_sources=standin.SANITIZE_DRIVER)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0")
-    out = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+    out = subprocess.run([exe, "both"], capture_output=True, text=True, env=env, timeout=120)
     assert out.returncode == 0, (out.stdout[-500:], out.stderr[-3000:])
-    assert out.stdout.strip().endswith("host_sanitize_both_driver ok")
+    assert out.stdout.strip().endswith("host_sanitize_driver both ok")

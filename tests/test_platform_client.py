@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import standin
 from conftest import ROOT, load_npz
 from platform_server import PlatformServer
 
@@ -103,10 +104,7 @@ def test_client_is_asan_clean_with_the_stub_device(tmp_path, oracle):
     if shutil.which("gcc") is None:
         pytest.skip("gcc not available")
     csrc = os.path.join(ROOT, "soc_project_stereo_matching_amd", "csrc")
-    exe_asan = str(tmp_path / "board_client_asan")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=c11", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", csrc,
-                           "-o", exe_asan, os.path.join(csrc, "sgm_board_client.c"), os.path.join(csrc, "sgm_host.c"),
-                           os.path.join(ROOT, "tests", "stub_device.c"), "-lm"])
+    exe_asan = standin.build(tmp_path, sanitize=True, exe="board_client_asan", extra_sources=[os.path.join(csrc, "sgm_board_client.c")])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=99")
     env.pop("LD_PRELOAD", None)
     frames = bgr_frames(2, 96, 40, 16, oracle, 4300) + bgr_frames(2, 64, 24, 16, oracle, 4400)

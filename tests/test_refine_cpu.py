@@ -6,7 +6,6 @@ import ctypes as C
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,9 +13,9 @@ import pytest
 import confidence_ref as CR
 import fill_holes_ref as FH
 import refine_ref as R
+import standin
 from conftest import GOLDEN, ROOT, case_inputs, load_npz, option_from_dict
 
-CSRC = os.path.join(ROOT, "soc_project_stereo_matching_amd", "csrc")
 F = np.float32
 INF = F(np.inf)
 
@@ -210,76 +209,31 @@ def test_library_exports_the_refinement():
 
 # ---- host logic on the stand-in device ---------------------------------------------------------------------------------
 
-def _build(tmp_path_factory, with_refine):
-    out = tmp_path_factory.mktemp("refinestub") / ("librefine%d.so" % with_refine)
-    srcs = [os.path.join(CSRC, "sgm_host.c"), os.path.join(ROOT, "tests", "stub_device.c"),
-            os.path.join(ROOT, "tests", "stub_device_conf.c")]
-    if with_refine:
-        srcs.append(os.path.join(ROOT, "tests", "stub_device_refine.c"))
-    subprocess.check_call(["gcc", "-O1", "-std=c11", "-fPIC", "-shared", "-I", CSRC, "-o", str(out)] + srcs + ["-lm"])
-    L = C.CDLL(str(out))
-    L.sgm_create.restype = C.c_void_p
-    L.sgm_create.argtypes = [C.c_int]
-    L.sgm_destroy.argtypes = [C.c_void_p]
-    for f in (L.sgm_initialize, L.sgm_reset):
-        f.argtypes = [C.c_void_p, C.c_uint16, C.c_uint16, C.c_void_p]
-        f.restype = C.c_bool
-    for f in (L.sgm_match, L.sgm_match_async, L.sgm_match_device):
-        f.argtypes = [C.c_void_p] * 4
-        f.restype = C.c_bool
-    L.sgm_match_confidence_device.argtypes = [C.c_void_p] * 5
-    L.sgm_match_confidence_device.restype = C.c_bool
-    L.sgm_match_wait.argtypes = [C.c_void_p]
-    L.sgm_match_wait.restype = C.c_bool
-    L.sgm_set_refine.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]
-    L.sgm_set_refine.restype = C.c_bool
-    L.SGM_SetRefine.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]
-    L.SGM_SetRefine.restype = C.c_bool
-    L.sgm_refine_disparity.argtypes = [C.c_void_p] * 4
-    L.sgm_refine_disparity.restype = C.c_bool
-    L.sgm_set_fill_holes.argtypes = [C.c_void_p, C.c_int]
-    L.sgm_set_fill_holes.restype = C.c_bool
-    L.sgm_set_overlap_post.argtypes = [C.c_void_p, C.c_int]
-    L.sgm_set_overlap_post.restype = C.c_bool
-    L.sgm_set_reference_view.argtypes = [C.c_void_p, C.c_int]
-    L.sgm_set_rows.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.sgm_set_rows.restype = C.c_bool
-    L.sgm_fused_sweep_rows.argtypes = [C.c_void_p]
-    L.stub_log_name.restype = C.c_char_p
-    L.stub_log_name.argtypes = [C.c_int]
-    L.stub_log_arg.argtypes = [C.c_int]
-    L.stubc_log_dst.restype = C.c_void_p
-    L.stubc_log_dst.argtypes = [C.c_int]
-    if with_refine:
-        for n in ("flags", "pos"):
-            getattr(L, "stubr_log_" + n).argtypes = [C.c_int]
-        for n in ("guide", "conf"):
-            getattr(L, "stubr_log_" + n).argtypes = [C.c_int]
-            getattr(L, "stubr_log_" + n).restype = C.c_void_p
-        L.stubr_log_l0.argtypes = [C.c_int]
-        L.stubr_log_l0.restype = C.c_float
-    return L
-
-
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    return _build(tmp_path_factory, True)
+    return standin.build(tmp_path_factory.mktemp("refinestub"))
 
 
 @pytest.fixture(scope="module")
 def host_old(tmp_path_factory):
-    return _build(tmp_path_factory, False)
+    return standin.build(tmp_path_factory.mktemp("refinestub"), without=("refine", "both"))
 
 
 def clear(L):
     L.stub_clear()
-    L.stubc_clear()
-    if hasattr(L, "stubr_clear"):
-        L.stubr_clear()
 
 
 def names(L):
-    return [L.stub_log_name(i).decode() for i in range(L.stub_log_size())]
+    return [e.name for e in standin.log(L)]
+
+
+def passes(L):
+    """the refinement launches: arg = its flags, a = the confidence it reads, b = the guide, f = L_t[0]"""
+    return standin.calls(L, "refine_pass")
+
+
+def conf_calls(L):
+    return standin.calls(L, "sum_wta_conf", "sum_wta_lr_conf", "wta_right_conf")
 
 
 class Frame:
@@ -330,7 +284,7 @@ def test_refused_params_change_nothing(host):
     clear(L)
     f = Frame()
     assert L.sgm_match(s, *f.args())
-    assert L.stubr_log_size() == 4                               # still T = 2
+    assert len(passes(L)) == 4                                   # still T = 2
     L.sgm_destroy(s)
 
 
@@ -364,19 +318,20 @@ def test_match_runs_2T_passes_after_the_median(host, T, right_view):
     assert L.sgm_match(s, *f.args())
     log = names(L)
     med = log.index("median")
-    assert L.stubr_log_size() == 2 * T
-    flags = [L.stubr_log_flags(i) for i in range(2 * T)]
+    rp = passes(L)
+    assert len(rp) == 2 * T
+    flags = [e.arg for e in rp]
     want = []
     for t in range(T):
         want += [(2 if t == 0 else 0), 1 | ((4 | 8) if t == T - 1 else 0)]
     assert flags == want
-    assert all(L.stubr_log_pos(i) == med + 1 for i in range(2 * T))        # right behind the median, nothing between
+    assert log[med + 1:med + 1 + 2 * T] == ["refine_pass"] * (2 * T)       # right behind the median, nothing between
     # the confidence went to an internal map, the guide is a private copy (a d2d of W*H bytes before the census)
-    conf = L.stubr_log_conf(0)
-    assert conf and conf == L.stubc_log_dst(0) and conf != f.conf.ctypes.data
-    assert all(L.stubr_log_conf(i) is None for i in range(1, 2 * T))    # read by the first pass only
+    conf = rp[0].a
+    assert conf and conf == conf_calls(L)[0].a and conf != f.conf.ctypes.data
+    assert all(e.a is None for e in rp[1:])                              # read by the first pass only
     assert log[:log.index("census")].count("d2d") == 1 and L.stub_log_arg(log.index("d2d")) == 48 * 20
-    assert len({L.stubr_log_guide(i) for i in range(2 * T)}) == 1
+    assert len({e.b for e in rp}) == 1
     assert L.sgm_fused_sweep_rows(s) == 0
     L.sgm_destroy(s)
 
@@ -391,7 +346,7 @@ def test_guide_copies_alternate_between_matches(host):
     for _ in range(3):
         clear(L)
         assert L.sgm_match_async(s, *f.args())
-        guides.append(L.stubr_log_guide(0))
+        guides.append(passes(L)[0].b)
     assert L.sgm_match_wait(s)
     assert guides[0] != guides[1] and guides[0] == guides[2]
     L.sgm_destroy(s)
@@ -404,7 +359,7 @@ def test_confidence_match_refines_from_the_callers_map(host):
     clear(L)
     f = Frame()
     assert L.sgm_match_confidence_device(s, *f.args(), f.conf.ctypes.data)
-    assert L.stubc_log_dst(0) == f.conf.ctypes.data and L.stubr_log_conf(0) == f.conf.ctypes.data
+    assert conf_calls(L)[0].a == f.conf.ctypes.data and passes(L)[0].a == f.conf.ctypes.data
     L.sgm_destroy(s)
 
 
@@ -416,7 +371,7 @@ def test_switching_refinement_off_restores_the_plain_launches(host):
     clear(L)
     assert L.sgm_match(s, *f.args())
     plain = [n for n in names(L) if n not in ("alloc", "sync")]
-    assert L.stubc_log_size() == 0
+    assert conf_calls(L) == []
     L.sgm_destroy(s)
     s, opt = make(L)
     assert L.sgm_reset(s, 48, 20, C.byref(opt))
@@ -426,7 +381,7 @@ def test_switching_refinement_off_restores_the_plain_launches(host):
     clear(L)
     assert L.sgm_match(s, *f.args())
     assert [n for n in names(L) if n not in ("alloc", "sync")] == plain
-    assert L.stubc_log_size() == 0 and L.stubr_log_size() == 0
+    assert conf_calls(L) == [] and passes(L) == []
     L.sgm_destroy(s)
 
 
@@ -439,7 +394,8 @@ def test_standalone_refinement(host):
     assert L.sgm_set_refine(s, 1, 64.0, 8.0, 2, 0)
     clear(L)
     assert L.sgm_refine_disparity(s, f.out.ctypes.data, f.conf.ctypes.data, f.left.ctypes.data)
-    assert L.stubr_log_size() == 4 and L.stubr_log_guide(0) == f.left.ctypes.data and L.stubr_log_conf(0) == f.conf.ctypes.data
+    rp = passes(L)
+    assert len(rp) == 4 and rp[0].b == f.left.ctypes.data and rp[0].a == f.conf.ctypes.data
     for args in ((None, f.conf.ctypes.data, f.left.ctypes.data), (f.out.ctypes.data, None, f.left.ctypes.data),
                  (f.out.ctypes.data, f.conf.ctypes.data, None)):
         assert not L.sgm_refine_disparity(s, *args)

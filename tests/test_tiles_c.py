@@ -15,6 +15,7 @@ import threading
 import numpy as np
 import pytest
 
+import standin
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "soc_project_stereo_matching_amd", "csrc")
@@ -174,16 +175,12 @@ def test_schedule_argument_checks_and_error_propagation():
 @pytest.fixture(scope="module")
 def stub(tmp_path_factory):
     d = tmp_path_factory.mktemp("tilestub")
-    host = str(d / "libsgm_tilestub.so")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=c11", "-D_GNU_SOURCE", "-fPIC", "-shared", "-I", CSRC, "-o", host,
-                           os.path.join(CSRC, "sgm_host.c"), os.path.join(CSRC, "sgm_tile_sched.c"), os.path.join(CSRC, "sgm_tiles.c"),
-                           os.path.join(ROOT, "tests", "stub_device.c"), "-lm", "-ldl", "-lpthread"])
+    L = standin.build(d, extra_sources=[os.path.join(CSRC, "sgm_tile_sched.c"), os.path.join(CSRC, "sgm_tiles.c")], flags=("-g",))
     rccl = str(d / "libstub_rccl.so")
     subprocess.check_call(["gcc", "-O1", "-g", "-std=c11", "-D_GNU_SOURCE", "-fPIC", "-shared", "-o", rccl,
                            os.path.join(ROOT, "tests", "stub_rccl.c"), "-lpthread"])
     os.environ["SGM_RCCL_LIBRARY"] = rccl                            # read by the stub build's rccl_bind at its first use
     from soc_project_stereo_matching_amd import tiles
-    L = C.CDLL(host)
     i, p = C.c_int, C.c_void_p
     L.sgm_tiles_create.argtypes = [i, i, i, C.c_uint16, C.c_uint16, p, i, i, i, i, C.POINTER(tiles.Transport)]
     L.sgm_tiles_create.restype = p
@@ -204,8 +201,6 @@ def stub(tmp_path_factory):
     L.sgm_tiles_rccl_unique_id.restype = C.c_bool
     L.sgm_tiles_rccl_transport.argtypes = [p, i, i, i, C.POINTER(tiles.Transport)]
     L.sgm_tiles_rccl_transport.restype = C.c_bool
-    L.stub_toy_compute.argtypes = [i]
-    L.stub_fail_at.argtypes = [C.c_char_p, i]
     L.rccl_lib = C.CDLL(rccl)
     L.rccl_lib.stub_rccl_stats.argtypes = [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     return L
