@@ -15,6 +15,9 @@ Outputs
   tiny_<name>.npz       full input + all nine stage arrays for the tiny cases
   cone_inputs.npz       the cone pair as 8-bit grey (stb formula) + the committed im2.d.png
   cone_final.npz        final float disparity of the cone pair
+  q14_no_reset_48x20_d16.npz   two matches without a Reset in between (Q14)
+The long runs without Reset (a hundred matches, the uint16 sums past 15 bits and wrapped: q14_deep.json, q14_deep_<shape>.npz)
+come from make_golden_q14_deep.py.
 """
 import json
 import os
