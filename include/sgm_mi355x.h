@@ -89,12 +89,38 @@ void SGM_SetHonorNumPaths(int honor);
  *   census window: any odd width x height of at most 64 pixels (e.g. 7x7, 9x7) instead of SemiGlobalMatching.c:134-159's
  *     5x5 -- same bit order (raster, first comparison in the highest bit, centre included), border of width/2 columns
  *     and height/2 rows zero, off-image cost 127.  Wide windows take the materialised-cost path (u64 census words, cost
- *     volume, volume-fed aggregation kernels): correct, but not the fused fast path of 5x5.
+ *     volume, volume-fed aggregation kernels): correct, but not the fused fast path of 5x5 (SGM_SetCensusKind below has a
+ *     wide-window census that is).
  *   reference view: 1 = the result is the RIGHT image's disparity map (the right-view winner-take-all of
  *     SemiGlobalMatching.c:395-408), validated by the mirror image of LRCheck (.c:445-470: right pixel x with disparity d
  *     must agree with the left map at column x + d), then speckle removal and median as usual.  0 = left (reference). */
 bool SGM_SetCensusWindow(int width, int height);
 void SGM_SetReferenceView(int right);
+
+/* Census kind (extension, "parity unpinned by the reference": the reference has the centre census only; defined here and restated
+ * by tests/census_sym_ref.py).  SGM_CENSUS_CENTRE (default) compares every pixel of the window with the centre pixel, so all of
+ * its bits share one noisy sample.  SGM_CENSUS_SYMMETRIC is the centre-symmetric census (Spangenberg et al. 2013): it compares
+ * the pixel pairs mirrored through the centre.  For the window cw x ch of SGM_SetCensusWindow (odd, cw * ch <= 64; the
+ * reference's 5x5 when none was set), rx = cw / 2, ry = ch / 2, n = (cw * ch - 1) / 2:
+ *   walk the window offsets (r, c) in raster order (r = -ry..ry outer, c = -rx..rx inner) and take the first n of them, those
+ *   strictly before the centre; for each, bits = (bits << 1) | (I[y + r][x + c] < I[y - r][x - c])   (strict, as the centre census).
+ *   u32 words of n <= 31 bits: 5x5 gives 12, 7x7 gives 24, 9x7 gives 31.  Pixels within rx columns or ry rows of the frame edge
+ *   get 0, and every pixel gets 0 when !(W > cw && H > ch).  Every word of the frame is written on every match (the default
+ *   instance's stale-border behaviour, SURVEY.md Q3, belongs to the reference's 5x5 centre census only).
+ *   The cost is popcount(cl ^ cr), 127 off the image; everything downstream is exactly the path of the reference's 5x5.
+ * Because the words are u32 for ANY window, the symmetric kind takes the fast path whatever its window: the cost is recomputed
+ * inside the fused aggregation, no u64 words and no cost volume exist (stage 0 / 1 read back u32, stage 2 needs sgm_keep_stages),
+ * and batches, four-path mode, negative P1, the right reference view, SGM_MatchBoth, the confidence, hole filling, the
+ * refinement, matches without Reset, row tiles and sgm_match_planes compose as they do with 5x5.  Only the opt-in fused last
+ * sweep (SGM_UPSUM) is not used.  Takes effect at the next SGM_Initialize / SGM_Reset; the default instance remembers it across
+ * SGM_Shutdown, as it does the window.  Returns false and changes nothing for any other kind, or for SGM_CENSUS_SYMMETRIC in a
+ * build without the kernel.  Timing: the kernel counts toward "census"; "cost" stays empty.
+ * SGM_CENSUS_SYMMETRIC_DEFAULT_W / _H: the window the drivers use with the symmetric kind when none is given -- under sensor
+ * noise (sigma = 4 grey levels) 7x7 has the lowest bad-pixel rate on the four image pairs the reference ships (NOTES.md). */
+enum { SGM_CENSUS_CENTRE = 0, SGM_CENSUS_SYMMETRIC = 1 };
+#define SGM_CENSUS_SYMMETRIC_DEFAULT_W 7
+#define SGM_CENSUS_SYMMETRIC_DEFAULT_H 7
+bool SGM_SetCensusKind(int kind);
 
 /* Hole filling (extension, "parity unpinned by the reference": SemiGlobalMatching.h:24-40 has no such option; defined here
  * and restated by tests/fill_holes_ref.py).  The discontinuity-preserving interpolation of Hirschmueller's SGM paper: the
@@ -218,6 +244,7 @@ sgm_instance* sgm_create(int device_ordinal);                 /* NULL on failure
 void          sgm_destroy(sgm_instance* s);
 void          sgm_set_honor_num_paths(sgm_instance* s, int honor);
 bool          sgm_set_census_window(sgm_instance* s, int width, int height);   /* see SGM_SetCensusWindow */
+bool          sgm_set_census_kind(sgm_instance* s, int kind);                  /* see SGM_SetCensusKind */
 void          sgm_set_reference_view(sgm_instance* s, int right);              /* see SGM_SetReferenceView */
 bool          sgm_set_fill_holes(sgm_instance* s, int enable);                 /* see SGM_SetFillHoles */
 bool          sgm_set_refine(sgm_instance* s, int enable, float lambda, float sigma, int iterations, int keep_invalid);  /* see SGM_SetRefine */
@@ -374,7 +401,7 @@ bool   sgm_match_planes_async(sgm_instance* s, const uint8_t* planes, float fx, 
 bool   sgm_match_planes(sgm_instance* s, const uint8_t* planes, float fx, float baseline, float doffs, float* depth);
 
 /* ---- stage read-back (parity tests; copies device -> host, blocking) ----
- * which: 0 census left (u32 [H][W])       1 census right (u32 [H][W])    (u64 words with a wide census window)
+ * which: 0 census left (u32 [H][W])       1 census right (u32 [H][W])    (u64 words with a wide CENTRE census window)
  *        2 matching cost (u8 [H][W][D])   3 aggregated cost S (u16 [H][W][D])
  *        4 left disparity after WTA       5 right-view disparity
  *        6 after LR check                 7 after speckle removal        8 final (all f32 [H][W])

@@ -59,6 +59,76 @@ __global__ __launch_bounds__(256) void sgm_census_k(const uint8_t* __restrict__ 
 }
 
 // ============================================================================================
+// Extension (include/sgm_mi355x.h, SGM_SetCensusKind): centre-symmetric census over any odd window cw x ch of at most 64 pixels.
+// The n = (cw * ch - 1) / 2 offsets before the centre in raster order, each compared with its mirror image through the centre:
+// at most 31 bits, so the words are u32 and feed the same fused aggregation as the 5x5 words above.
+// ============================================================================================
+
+// Same blocks as sgm_census_k.  The (64 + cw - 1) x (16 + ch - 1) bytes a block needs are staged in LDS once; a thread owns one
+// column of four consecutive rows.  For one window column c it walks the window rows downwards: its four pixels read four
+// consecutive tile rows of column c (sliding down by one per step) and four of the mirrored column -c (sliding up), so a step
+// costs two LDS bytes for four comparisons instead of eight.
+#define CEN_SYM_LDS 4992                                               // the largest tile: 1 x 63, 64 columns x 78 rows
+__global__ __launch_bounds__(256) void sgm_census_sym_k(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+                                                        uint32_t* __restrict__ cl, uint32_t* __restrict__ cr, int W, int H,
+                                                        int cw, int ch, const uint8_t* __restrict__ need)
+{
+    if (need && !need[blockIdx.y * gridDim.x + blockIdx.x]) return;
+    __shared__ uint8_t tile[CEN_SYM_LDS];
+    const int rx = cw >> 1, ry = ch >> 1, n = (cw * ch - 1) >> 1;
+    const int tw = CEN_BW + cw - 1, th = CEN_BH + ch - 1;              // tw <= 126
+    const int ld = (tw + 3) & ~3;                                      // LDS row stride in bytes
+    const size_t frame_px = (size_t)(blockIdx.z >> 1) * W * H;         // batch: z = 2 * frame + image
+    const uint8_t* img = ((blockIdx.z & 1) ? right : left) + frame_px;
+    uint32_t* out = ((blockIdx.z & 1) ? cr : cl) + frame_px;
+    const int x0 = blockIdx.x * CEN_BW, y0 = blockIdx.y * CEN_BH;
+    // positions outside the image are clamped: only pixels of the zero border ever see them
+    {
+        const int c = threadIdx.x & 127;
+        if (c < tw) {
+            const int xx = min(max(x0 + c - rx, 0), W - 1);
+            for (int r = threadIdx.x >> 7; r < th; r += 2) {
+                const int yy = min(max(y0 + r - ry, 0), H - 1);
+                tile[r * ld + c] = img[(size_t)yy * W + xx];
+            }
+        }
+    }
+    __syncthreads();
+    const int cx = threadIdx.x & 63, li = (threadIdx.x >> 6) * 4;
+    const int x = x0 + cx;
+    if (x >= W) return;
+    uint32_t bits0 = 0, bits1 = 0, bits2 = 0, bits3 = 0;
+    for (int c = -rx; c <= rx; ++c) {
+        // pixel i of the thread (tile row li + i + ry), window row r = j - ry: a = tile row li + i + j of column c,
+        // b = tile row li + i + 2 ry - j of column -c
+        const uint8_t* pa = tile + li * ld + (cx + rx + c);
+        const uint8_t* pb = tile + (li + 2 * ry) * ld + (cx + rx - c);
+        unsigned a0 = pa[0], a1 = pa[ld], a2 = pa[2 * ld];
+        unsigned b1 = pb[ld], b2 = pb[2 * ld], b3 = pb[3 * ld];
+        const int steps = c < 0 ? ry + 1 : ry;                         // the centre row stops in front of the centre
+        int sh = n - 1 - (c + rx);                                     // raster order, first comparison in the highest bit
+        for (int j = 0; j < steps; ++j, sh -= cw) {
+            const unsigned a3 = pa[(j + 3) * ld], b0 = pb[-j * ld];
+            bits0 |= (unsigned)(a0 < b0) << sh;
+            bits1 |= (unsigned)(a1 < b1) << sh;
+            bits2 |= (unsigned)(a2 < b2) << sh;
+            bits3 |= (unsigned)(a3 < b3) << sh;
+            a0 = a1; a1 = a2; a2 = a3;
+            b3 = b2; b2 = b1; b1 = b0;
+        }
+    }
+    // every word of the frame is written: 0 within rx columns / ry rows of the edge, and everywhere when the window does not fit
+    const bool col_ok = W > cw && H > ch && x >= rx && x < W - rx;
+    const uint32_t bits[4] = {bits0, bits1, bits2, bits3};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int y = y0 + li + i;
+        if (y >= H) break;
+        out[(size_t)y * W + x] = (col_ok && y >= ry && y < H - ry) ? bits[i] : 0u;
+    }
+}
+
+// ============================================================================================
 // matching cost  (ref :161-196): one thread = 16 consecutive disparities of one pixel
 // ============================================================================================
 
@@ -197,6 +267,22 @@ int sgmd_census(int ord, void* stream, const sgmd_geom* g, const void* left, con
     dim3 grid((g->W + CEN_BW - 1) / CEN_BW, (g->H + CEN_BH - 1) / CEN_BH, 2 * g->B);
     hipLaunchKernelGGL(sgm_census_k, grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)left,
                        (const uint8_t*)right, (uint32_t*)cl, (uint32_t*)cr, g->W, g->H, (const uint8_t*)need, keep_border);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sgmd_census_sym(int ord, void* stream, const sgmd_geom* g, int cw, int ch, const void* left, const void* right, void* cl, void* cr,
+                    const void* need)
+{
+    if (cw < 1 || ch < 1 || !(cw & 1) || !(ch & 1) || cw * ch > 64 ||
+        (CEN_BH + ch - 1) * ((CEN_BW + cw - 1 + 3) & ~3) > CEN_SYM_LDS) {
+        fprintf(stderr, "sgm_mi355x: symmetric census needs an odd window of at most 64 pixels (got %dx%d)\n", cw, ch);
+        return (int)hipErrorInvalidValue;
+    }
+    HIP_TRY(hipSetDevice(ord));
+    dim3 grid((g->W + CEN_BW - 1) / CEN_BW, (g->H + CEN_BH - 1) / CEN_BH, 2 * g->B);
+    hipLaunchKernelGGL(sgm_census_sym_k, grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)left, (const uint8_t*)right,
+                       (uint32_t*)cl, (uint32_t*)cr, g->W, g->H, cw, ch, (const uint8_t*)need);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -113,6 +113,13 @@ int sgmd_census_window(int ord, void* stream, const sgmd_geom* g, int cw, int ch
                        void* census64_l, void* census64_r);
 int sgmd_cost64(int ord, void* stream, const sgmd_geom* g, const void* census64_l, const void* census64_r, void* cost);
 
+/* Extension (parity unpinned by the reference), the centre-symmetric census of include/sgm_mi355x.h (SGM_SetCensusKind) over an
+ * odd cw x ch window of at most 64 pixels: u32 words of at most 31 bits into the buffers of sgmd_census, for the same
+ * aggregation, with the same block grid and `need` map; every word of a block that is not skipped is written (0 on the border).
+ * sgm_host.c references it weakly (a host built without it refuses that census kind). */
+int sgmd_census_sym(int ord, void* stream, const sgmd_geom* g, int cw, int ch, const void* left, const void* right,
+                    void* census_l, void* census_r, const void* need);
+
 /* All directions of the path aggregation in ONE launch.  SemiGlobalMatching.c:198-372.
  * The matching cost (SemiGlobalMatching.c:161-196) is recomputed from the census images inside the
  * kernel; census_r must be preceded by at least sgmd_census_slack(g) readable bytes (disparities that

@@ -75,6 +75,7 @@ struct sgm_instance {
     int keep_stages;
     int honor_num_paths;
     int census_w, census_h;      /* census window (sgm_set_census_window); 0 = the reference's 5x5 */
+    int census_kind;             /* SGM_CENSUS_CENTRE (reference) or SGM_CENSUS_SYMMETRIC (sgm_set_census_kind) */
     int reference_view;          /* 0 = left (reference), 1 = right (sgm_set_reference_view) */
     int fill_req;                /* hole filling asked for (sgm_set_fill_holes); takes effect at the next initialize */
     bool fill_on;                /* ... and in effect for this shape: the class map and the ping-pong map exist */
@@ -177,6 +178,14 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
 
 /* row-tile mode (sgm_set_rows): the instance computes rows [tile_begin, tile_end) of every frame */
 static bool row_tiled(const sgm_instance* s) { return s->tile_end != 0; }
+
+/* The census decides two things.  reference_census: the reference's own 5x5 centre census (sgmd_census: the stale-border
+ * quirk, the opt-in fused last sweep).  volume_fed: a wide centre window -- u64 words, a materialised cost volume and the
+ * volume-fed aggregation.  Everything else about the fast path only asks for u32 words, i.e. !volume_fed: the symmetric kind
+ * (at most 31 bits for any window) takes it whatever its window. */
+static bool census_symmetric(const sgm_instance* s) { return s->census_kind == SGM_CENSUS_SYMMETRIC; }
+static bool reference_census(const sgm_instance* s) { return !s->census_w && !census_symmetric(s); }
+static bool volume_fed(const sgm_instance* s) { return s->census_w && !census_symmetric(s); }
 
 /* wait for everything the instance has queued (its stream and, with sgm_set_overlap_post, the post-pass stream) */
 static int sync_streams(sgm_instance* s)
@@ -451,6 +460,24 @@ bool sgm_set_census_window(sgm_instance* s, int width, int height)
     if (width == 5 && height == 5) width = height = 0;           /* the reference's window: the fused fast path */
     if (width != s->census_w || height != s->census_h) s->initialized = false;   /* takes effect at the next initialize */
     s->census_w = width; s->census_h = height;
+    return true;
+}
+
+/* The symmetric census launcher (sgm_census.hip), weakly referenced like the extensions below: a host built without it (the
+ * stand-in device of the tests) refuses that kind. */
+#pragma weak sgmd_census_sym
+static bool census_kind_ok(int kind)
+{
+    if (kind != SGM_CENSUS_CENTRE && kind != SGM_CENSUS_SYMMETRIC) return false;
+    if (kind == SGM_CENSUS_SYMMETRIC && sgmd_census_sym == NULL) FAIL("the symmetric census is not part of this build");
+    return true;
+}
+
+bool sgm_set_census_kind(sgm_instance* s, int kind)
+{
+    if (!s || !census_kind_ok(kind)) return false;
+    if (kind != s->census_kind) s->initialized = false;          /* takes effect at the next initialize */
+    s->census_kind = kind;
     return true;
 }
 
@@ -814,7 +841,7 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
         /* negative P1 (defined by the reference's C arithmetic, covered by the parity tests, used by nobody) runs the
          * generic aggregation step, which only exists for 16 lanes per pixel */
         /* the wide census windows feed the aggregation from a cost volume: generic step, 16 lanes per pixel */
-        if (want == 8 && option->p1 >= 0 && !s->census_w && s->g.DPL >= 2 && s->g.DPL <= 8 && s->g.DPL != 6) { s->g.LPP = 8; s->g.DPL *= 2; }
+        if (want == 8 && option->p1 >= 0 && !volume_fed(s) && s->g.DPL >= 2 && s->g.DPL <= 8 && s->g.DPL != 6) { s->g.LPP = 8; s->g.DPL *= 2; }
     }
     /* one frame per launch: the horizontal lines (W-1 serial steps) are the longest chains of the launch -> spread each
      * pixel of those over 32 lanes (2 lines per wave).  64 lanes (SGM_HL=64, one line per wave) measures the same at
@@ -830,7 +857,7 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
         if (want == 64 && !ok64) want = 32;
         if (want == 32 && !ok32) want = 0;
         if (want == 16 && !ok16) want = 0;
-        if (want == s->g.LPP || option->p1 < 0 || s->census_w) want = 0;
+        if (want == s->g.LPP || option->p1 < 0 || volume_fed(s)) want = 0;
         s->g.HL = want;
     }
     s->g.dmin = option->min_disparity;
@@ -898,7 +925,7 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
         s->tab_p1 = option->p1; s->tab_p2 = option->p2_init;
     }
 
-    if (row_tiled(s) && !s->census_w && !upload_census_need(s)) return false;
+    if (row_tiled(s) && !volume_fed(s) && !upload_census_need(s)) return false;
 
     s->s_is_zero = true;                                         /* .c:57: memset of cost_aggr, done lazily */
     s->s_pending = false;
@@ -909,12 +936,12 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
         const int want = s->env_fused >= 0 ? s->env_fused != 0 : 1;        /* SGM_FUSED_WTA */
         s->fused_wta = sgmd_sum_wta_lr_supported(&s->g, s->row_cap) && want;
     }
-    /* the fused last sweep: batches of whole frames with eight paths and non-negative P1 on the census path (sgm_upsum.hip has
-     * the shapes: W > H, Dp = 128).  SGM_UPSUM=0 / 1 forces it off / on (also for one frame per launch, where its row-to-row chain
+    /* the fused last sweep: batches of whole frames with eight paths and non-negative P1 on the reference's census (sgm_upsum.hip
+     * has the shapes: W > H, Dp = 128).  SGM_UPSUM=0 / 1 forces it off / on (also for one frame per launch, where its row-to-row chain
      * costs latency) */
     s->up_rows = 0;
     s->planes_partial = false;
-    if (s->fused_wta && !row_tiled(s) && !s->census_w && s->paths.ndirs == 8 && option->p1 >= 0 && s->row_cap <= 8 &&
+    if (s->fused_wta && !row_tiled(s) && reference_census(s) && s->paths.ndirs == 8 && option->p1 >= 0 && s->row_cap <= 8 &&
         (s->env_upsum >= 0 ? s->env_upsum != 0 : UPSUM_DEFAULT && s->batch >= 2))
         s->up_rows = sgmd_upsum_rows(&s->g);
     if (s->up_rows > 0 && s->env_upsum_rows >= 1 && s->env_upsum_rows < s->up_rows) s->up_rows = s->env_upsum_rows;
@@ -941,7 +968,7 @@ static void mark(sgm_instance* s, int idx) { mark_on(s, s->stream, idx); }
 /* .c:94: the path aggregation, from the census images or (wide windows) from the cost volume */
 static int launch_aggregation(sgm_instance* s, const sgmd_paths* paths, const void* d_left)
 {
-    if (s->census_w)
+    if (volume_fed(s))
         return sgmd_aggregate_volume(s->device, s->stream, &s->g, paths, d_left, s->d_cost.p, s->d_lut.p, s->d_planes, s->plane_bytes,
                                      s->d_extras.p);
     return sgmd_aggregate(s->device, s->stream, &s->g, paths, d_left, s->d_census_l.p, s->d_census_r, s->d_lut.p, s->d_planes,
@@ -1030,20 +1057,23 @@ static int sum_and_wta(sgm_instance* s, void* st, void* d_out, void* conf, bool 
     return 0;
 }
 
-/* .c:82-83 (+ .c:89 for the wide census windows, whose cost is materialised): census of both images */
+/* .c:82-83 (+ .c:89 for the wide centre windows, whose cost is materialised): census of both images */
 static int prepare_costs(sgm_instance* s, const void* d_left, const void* d_right)
 {
-    if (!s->census_w) {
+    if (!volume_fed(s)) {
         const bool tiled = row_tiled(s) && !s->keep_stages;          /* stage read-back wants the whole census */
         if (tiled && getenv("SGM_DEBUG_POISON_CENSUS")) {                /* tests: a read of a skipped block must not go unnoticed */
             const size_t bytes = (size_t)s->g.B * s->g.W * s->g.H * 4;
             if (sgmd_memset_async(s->device, s->stream, s->d_census_l.p, 0xA5, bytes) != 0 ||
                 sgmd_memset_async(s->device, s->stream, s->d_census_r, 0x5A, bytes) != 0) return -1;
         }
+        const void* need = tiled ? s->d_census_need.p : NULL;
+        if (census_symmetric(s))                                     /* extension: every word of the blocks is written */
+            return sgmd_census_sym(s->device, s->stream, &s->g, s->census_w ? s->census_w : 5, s->census_h ? s->census_h : 5, d_left,
+                                   d_right, s->d_census_l.p, s->d_census_r, need);
         /* the reference's own boundary, one whole frame per match: the unwritten census words stay as they are (Q3) */
         const int keep_border = s->reference_statics && s->g.B == 1 && !row_tiled(s);
-        return sgmd_census(s->device, s->stream, &s->g, d_left, d_right, s->d_census_l.p, s->d_census_r, tiled ? s->d_census_need.p : NULL,
-                           keep_border);
+        return sgmd_census(s->device, s->stream, &s->g, d_left, d_right, s->d_census_l.p, s->d_census_r, need, keep_border);
     }
     const size_t need = (size_t)s->g.B * s->g.W * s->g.H * 8;
     const buf_request words[] = {{&s->d_census64_l, need, 0}, {&s->d_census64_r, need, 0}};
@@ -1170,7 +1200,7 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
     mark(s, T_COST);
     /* .c:89: the cost volume is recomputed inside the aggregation kernel; it is only materialised when a
      * test wants to read it back (stage 2) */
-    if (s->keep_stages && !s->census_w) {
+    if (s->keep_stages && !volume_fed(s)) {
         LAUNCH(ensure_cost(s));
         LAUNCH(sgmd_cost(dev, st, g, s->d_census_l.p, s->d_census_r, s->d_cost.p));
     }
@@ -1760,15 +1790,15 @@ size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacit
     size_t elem = 0;
     bool volume = false;
     int row_a = 0, row_b = s->g.H;                                /* rows the device holds of a volume stage */
-    if ((which == 4 || which == 6 || which == 7 || which == 9 || (which == 2 && !s->census_w)) && !s->keep_stages) return 0;
+    if ((which == 4 || which == 6 || which == 7 || which == 9 || (which == 2 && !volume_fed(s))) && !s->keep_stages) return 0;
     if ((which == 9 || which == 18) && !s->fill_on) return 0;
     if ((which == 26 || which == 27) && !(s->keep_stages && s->last_both_kept)) return 0;
     if (which == 28 && !s->last_both) return 0;
     if (which == 2 && !s->d_cost.p) return 0;
     if (which == 3 && (ensure_S(s) != 0 || materialize_S(s) != 0)) return 0;
     switch (which) {
-    case 0: src = s->census_w ? (const char*)s->d_census64_l.p + f * px * 8 : (const char*)s->d_census_l.p + f * px * 4; elem = s->census_w ? 8 : 4; break;
-    case 1: src = s->census_w ? (const char*)s->d_census64_r.p + f * px * 8 : (const char*)s->d_census_r + f * px * 4; elem = s->census_w ? 8 : 4; break;
+    case 0: src = volume_fed(s) ? (const char*)s->d_census64_l.p + f * px * 8 : (const char*)s->d_census_l.p + f * px * 4; elem = volume_fed(s) ? 8 : 4; break;
+    case 1: src = volume_fed(s) ? (const char*)s->d_census64_r.p + f * px * 8 : (const char*)s->d_census_r + f * px * 4; elem = volume_fed(s) ? 8 : 4; break;
     case 2: src = (const char*)s->d_cost.p + f * px * s->g.Dp; elem = 1; volume = true; break;
     case 3: src = (const char*)s->d_S.p + f * px * s->g.Dp * 2; elem = 2; volume = true; break;
     case 4: src = (const char*)s->d_snap_wta.p + f * px * 4; elem = 4; break;
@@ -1835,7 +1865,7 @@ bool SGM_SetDevice(int device_ordinal)
     return true;
 }
 
-static int g_default_census_w, g_default_census_h, g_default_view, g_default_fill;
+static int g_default_census_w, g_default_census_h, g_default_census_kind, g_default_view, g_default_fill;
 
 bool SGM_SetFillHoles(int enable)
 {
@@ -1872,6 +1902,13 @@ bool SGM_SetCensusWindow(int width, int height)
     return g_default ? sgm_set_census_window(g_default, width, height) : true;
 }
 
+bool SGM_SetCensusKind(int kind)
+{
+    if (!census_kind_ok(kind)) return false;
+    g_default_census_kind = kind;
+    return g_default ? sgm_set_census_kind(g_default, kind) : true;
+}
+
 void SGM_SetReferenceView(int right)
 {
     g_default_view = right ? 1 : 0;
@@ -1896,6 +1933,7 @@ bool SGM_Initialize(uint16_t width, uint16_t height, const SGMOption* option)
         g_default->honor_num_paths = g_default_honor;
         g_default->reference_statics = 1;
         if (g_default_census_w) sgm_set_census_window(g_default, g_default_census_w, g_default_census_h);
+        sgm_set_census_kind(g_default, g_default_census_kind);
         sgm_set_reference_view(g_default, g_default_view);
         if (g_default_fill) sgm_set_fill_holes(g_default, 1);
         if (g_default_refine.enable)

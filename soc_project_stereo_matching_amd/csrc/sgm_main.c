@@ -10,6 +10,8 @@
  *            [--paths 4|8] [--census WxH] [--right-reference]      extensions of the boundary: 4-path
  *            aggregation (the reference stores num_paths and ignores it), census windows other than 5x5, the right image
  *            as reference view; the defaults are the reference's behaviour
+ *            [--census-kind centre|symmetric]   extension: the centre-symmetric census (SGM_SetCensusKind), on the fast path for
+ *                             any window; symmetric without --census uses SGM_CENSUS_SYMMETRIC_DEFAULT_W x _H (7x7)
  *            [--fill-holes]   extension: occlusion-aware hole filling of the invalid disparities (SGM_SetFillHoles)
  *            [--confidence OUT.pgm]   extension: the matching confidence (SGM_MatchConfidence) as a 16-bit PGM
  *            [--right-out OUT.png] [--right-raw OUT.f32]   extension: the right view's map from the same match (SGM_MatchBoth),
@@ -109,6 +111,7 @@ int main(int argc, char** argv)
     const char* right_out = NULL;
     const char* right_raw = NULL;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
+    int census_kind = SGM_CENSUS_CENTRE;
     float refine_lambda = SGM_REFINE_DEFAULT_LAMBDA, refine_sigma = SGM_REFINE_DEFAULT_SIGMA;
     int refine_iters = SGM_REFINE_DEFAULT_ITERS;
     for (int i = 4; i < argc; ++i) {
@@ -133,6 +136,11 @@ int main(int argc, char** argv)
         else if (v && !strcmp(a, "--paths")) { opt.num_paths = (uint8_t)atoi(v); SGM_SetHonorNumPaths(1); ++i; }
         else if (v && !strcmp(a, "--census")) {
             if (sscanf(v, "%dx%d", &census_w, &census_h) != 2) { fprintf(stderr, "--census wants WxH, e.g. 7x7\n"); return 2; }
+            ++i;
+        }
+        else if (v && !strcmp(a, "--census-kind")) {
+            if (!strcmp(v, "symmetric")) census_kind = SGM_CENSUS_SYMMETRIC;
+            else if (strcmp(v, "centre")) { fprintf(stderr, "--census-kind wants centre or symmetric\n"); return 2; }
             ++i;
         }
         else if (!strcmp(a, "--right-reference")) right_ref = 1;
@@ -163,6 +171,11 @@ int main(int argc, char** argv)
     printf("w = %d, h = %d, d = [%d,%d]\n", w1, h1, opt.min_disparity, opt.max_disparity);
 
     if (device >= 0) SGM_SetDevice(device);
+    if (census_kind == SGM_CENSUS_SYMMETRIC && !census_w) {
+        census_w = SGM_CENSUS_SYMMETRIC_DEFAULT_W;
+        census_h = SGM_CENSUS_SYMMETRIC_DEFAULT_H;
+    }
+    if (!SGM_SetCensusKind(census_kind)) { printf("unsupported census kind\n"); return -2; }
     if (census_w && !SGM_SetCensusWindow(census_w, census_h)) { printf("unsupported census window %dx%d\n", census_w, census_h); return -2; }
     if (right_ref) SGM_SetReferenceView(1);
     if (fill_holes && !SGM_SetFillHoles(1)) { printf("hole filling unavailable\n"); return -2; }

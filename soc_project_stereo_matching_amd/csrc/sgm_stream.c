@@ -4,7 +4,7 @@
  * images in, host floats out).
  *
  *   sgm_stream [--width W] [--height H] [--disparities D] [--batch B] [--instances N] [--seconds S] [--frames F] [--seed X]
- *              [--pageable] [--blocking] [--numa-node K] [--both]
+ *              [--pageable] [--blocking] [--numa-node K] [--both] [--census WxH] [--census-kind centre|symmetric]
  *
  *   default      N instances, one host thread each, batches of B frames through sgm_reset + sgm_match_async + sgm_match_wait on
  *                page-locked buffers (sgm_host_alloc) for S seconds: the pipelined throughput path (bench.py's headline, in C)
@@ -13,6 +13,8 @@
  *   --pageable   malloc'd caller buffers instead of page-locked ones (staged by the library)
  *   --both       every match returns both views' maps (sgm_match_both_async; not with --blocking); fps counts frames, each with
  *                two maps, and "hash_frame0_right" is the right view's hash beside the left one's
+ *   --census WxH, --census-kind centre|symmetric   extensions: the census window (SGM_SetCensusWindow) and kind (SGM_SetCensusKind);
+ *                symmetric without --census uses SGM_CENSUS_SYMMETRIC_DEFAULT_W x _H
  *   --numa-node K  run (and allocate) on the CPUs of NUMA node K -- the node the GPU hangs off (/sys/bus/pci/devices/<bdf>/numa_node):
  *                the host threads spin in stream synchronisation and feed 11 GB/s over PCIe; bench.py pins itself the same way
  *
@@ -66,7 +68,7 @@ static unsigned long long fnv1a(const void* p, size_t n)
 }
 
 typedef struct {
-    int k, n_inst, W, H, B, n_batches, pageable, both;
+    int k, n_inst, W, H, B, n_batches, pageable, both, census_kind, census_w, census_h;
     const SGMOption* opt;
     uint8_t **L, **R;            /* [n_batches] batches of B frames, shared, read-only */
     volatile double stop_at;     /* set by main right after the start barrier */
@@ -84,7 +86,8 @@ static void* worker_main(void* p)
     sgm_instance* s = sgm_create(0);
     float *out = NULL, *out_r = NULL;
     w->failed = 1;
-    if (s && sgm_set_batch(s, w->B) && sgm_set_overlap_post(s, 1) && sgm_initialize(s, (uint16_t)w->W, (uint16_t)w->H, w->opt)) {
+    if (s && sgm_set_batch(s, w->B) && sgm_set_overlap_post(s, 1) && sgm_set_census_kind(s, w->census_kind) &&
+        (!w->census_w || sgm_set_census_window(s, w->census_w, w->census_h)) && sgm_initialize(s, (uint16_t)w->W, (uint16_t)w->H, w->opt)) {
         out = w->pageable ? (float*)malloc(w->B * px * sizeof(float)) : (float*)sgm_host_alloc(s, w->B * px * sizeof(float));
         if (w->both) out_r = w->pageable ? (float*)malloc(w->B * px * sizeof(float)) : (float*)sgm_host_alloc(s, w->B * px * sizeof(float));
         w->failed = out == NULL || (w->both && out_r == NULL);
@@ -116,6 +119,7 @@ static void* worker_main(void* p)
 int main(int argc, char** argv)
 {
     int W = 1242, H = 375, D = 128, B = 8, N = 4, F = 32, pageable = 0, blocking = 0, node = -1, both = 0;
+    int census_kind = SGM_CENSUS_CENTRE, census_w = 0, census_h = 0;
     double seconds = 2.0;
     unsigned seed = 0x5EED0002u;
     for (int i = 1; i < argc; ++i) {
@@ -133,9 +137,22 @@ int main(int argc, char** argv)
         else if (v && !strcmp(a, "--seconds")) seconds = atof(argv[++i]);
         else if (v && !strcmp(a, "--numa-node")) node = atoi(argv[++i]);
         else if (v && !strcmp(a, "--seed")) seed = (unsigned)strtoul(argv[++i], NULL, 0);
+        else if (v && !strcmp(a, "--census")) {
+            if (sscanf(v, "%dx%d", &census_w, &census_h) != 2) { fprintf(stderr, "sgm_stream: --census wants WxH, e.g. 7x7\n"); return 2; }
+            ++i;
+        }
+        else if (v && !strcmp(a, "--census-kind")) {
+            if (!strcmp(v, "symmetric")) census_kind = SGM_CENSUS_SYMMETRIC;
+            else if (strcmp(v, "centre")) { fprintf(stderr, "sgm_stream: --census-kind wants centre or symmetric\n"); return 2; }
+            ++i;
+        }
         else { fprintf(stderr, "sgm_stream: unknown argument %s (see the header of sgm_stream.c)\n", a); return 2; }
     }
     if (W < 1 || H < 1 || D < 1 || B < 1 || N < 1 || N > 16 || F < 1 || (both && blocking)) return 2;
+    if (census_kind == SGM_CENSUS_SYMMETRIC && !census_w) {
+        census_w = SGM_CENSUS_SYMMETRIC_DEFAULT_W;
+        census_h = SGM_CENSUS_SYMMETRIC_DEFAULT_H;
+    }
     if (node >= 0 && !pin_to_node(node)) fprintf(stderr, "sgm_stream: could not pin to NUMA node %d (continuing unpinned)\n", node);
     SGMOption opt;
     memset(&opt, 0, sizeof opt);                       /* main.c:48-65 with max_disparity = D */
@@ -145,6 +162,10 @@ int main(int argc, char** argv)
     const size_t px = (size_t)W * H;
 
     if (blocking) {
+        if (!SGM_SetCensusKind(census_kind) || (census_w && !SGM_SetCensusWindow(census_w, census_h))) {
+            fprintf(stderr, "sgm_stream: unsupported census %dx%d\n", census_w, census_h);
+            return 2;
+        }
         uint8_t* l = (uint8_t*)malloc(px * F);
         uint8_t* r = (uint8_t*)malloc(px * F);
         float* out = (float*)malloc(px * sizeof(float));
@@ -188,7 +209,7 @@ int main(int argc, char** argv)
     pthread_t th[16];
     memset(w, 0, sizeof w);
     for (int k = 0; k < N; ++k) {
-        w[k] = (worker){k, N, W, H, B, n_batches, pageable, both, &opt, L, R, 1e300, 0, 0, 0, 0, &start};
+        w[k] = (worker){k, N, W, H, B, n_batches, pageable, both, census_kind, census_w, census_h, &opt, L, R, 1e300, 0, 0, 0, 0, &start};
         if (pthread_create(&th[k], NULL, worker_main, &w[k]) != 0) return 1;
     }
     /* every worker is set up (its warm-up batch included) when the barrier opens */

@@ -25,6 +25,9 @@ STAGE_FILLED, STAGE_FILL_CLASS = 9, 18
 STAGE_RIGHT_AFTER_LR, STAGE_RIGHT_AFTER_SPECKLE, STAGE_RIGHT_FINAL = 26, 27, 28
 # the refinement's default parameters (SGM_REFINE_DEFAULT_* of include/sgm_mi355x.h)
 REFINE_LAMBDA, REFINE_SIGMA, REFINE_ITERS = 16.0, 1.5, 1
+# census kinds (SGM_CENSUS_* of include/sgm_mi355x.h) and the drivers' window for the symmetric kind
+CENSUS_CENTRE, CENSUS_SYMMETRIC = 0, 1
+CENSUS_SYMMETRIC_WINDOW = (7, 7)
 
 
 class SGMOption(C.Structure):
@@ -122,6 +125,11 @@ def _load() -> C.CDLL:
     L.SGM_SetCensusWindow.argtypes = [C.c_int, C.c_int]
     L.SGM_SetCensusWindow.restype = C.c_bool
     L.SGM_SetReferenceView.argtypes = [C.c_int]
+    if hasattr(L, "sgm_set_census_kind"):     # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_set_census_kind.argtypes = [C.c_void_p, C.c_int]
+        L.sgm_set_census_kind.restype = C.c_bool
+        L.SGM_SetCensusKind.argtypes = [C.c_int]
+        L.SGM_SetCensusKind.restype = C.c_bool
     L.sgm_keep_stages.argtypes = [C.c_void_p, C.c_int]
     if hasattr(L, "sgm_set_fill_holes"):      # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_set_fill_holes.argtypes = [C.c_void_p, C.c_int]
@@ -273,6 +281,14 @@ def _u8(a):
 
 
 class _StageReader:
+    _wide_window, _census_kind = False, CENSUS_CENTRE
+
+    @property
+    def wide_census(self):
+        """u64 census words and a materialised cost volume: a window other than 5x5 with the centre census.  The symmetric
+        kind has u32 words for any window."""
+        return self._wide_window and self._census_kind == CENSUS_CENTRE
+
     def _read(self, which):
         raise NotImplementedError
 
@@ -280,7 +296,7 @@ class _StageReader:
         """Copy one intermediate buffer of the last match to the host (parity tests)."""
         idx = STAGE_NAMES.index(which) if isinstance(which, str) else which
         h, w, d = self.shape
-        if idx < 2 and getattr(self, "wide_census", False):
+        if idx < 2 and self.wide_census:
             dt, shp = np.uint64, (h, w)
         elif idx == STAGE_FILLED:
             dt, shp = np.float32, (h, w)
@@ -326,7 +342,15 @@ class SGM(_StageReader):
     def set_census_window(self, width: int, height: int) -> bool:
         ok = bool(self.lib.SGM_SetCensusWindow(width, height))
         if ok:
-            self.wide_census = not (width == 5 and height == 5)
+            self._wide_window = not (width == 5 and height == 5)
+        return ok
+
+    def set_census_kind(self, kind: int) -> bool:
+        """Extension: CENSUS_CENTRE (reference) or CENSUS_SYMMETRIC, the centre-symmetric census on the fast path for any window
+        (include/sgm_mi355x.h, SGM_SetCensusKind); next initialize/reset."""
+        ok = bool(self.lib.SGM_SetCensusKind(int(kind)))
+        if ok:
+            self._census_kind = int(kind)
         return ok
 
     def set_reference_view(self, right: bool):
@@ -484,7 +508,15 @@ class SGMInstance(_StageReader):
         """Extension: odd census window of at most 64 pixels (5x5 = reference); next initialize/reset."""
         ok = bool(self.lib.sgm_set_census_window(self.handle, width, height))
         if ok:
-            self.wide_census = not (width == 5 and height == 5)
+            self._wide_window = not (width == 5 and height == 5)
+        return ok
+
+    def set_census_kind(self, kind: int) -> bool:
+        """Extension: CENSUS_CENTRE (reference) or CENSUS_SYMMETRIC, the centre-symmetric census on the fast path for any window
+        (include/sgm_mi355x.h, SGM_SetCensusKind); next initialize/reset."""
+        ok = bool(self.lib.sgm_set_census_kind(self.handle, int(kind)))
+        if ok:
+            self._census_kind = int(kind)
         return ok
 
     def set_reference_view(self, right: bool):
