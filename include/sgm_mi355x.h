@@ -222,6 +222,43 @@ bool SGM_SetRefine(int enable, float lambda, float sigma, int iterations, int ke
  * the ranges of SGM_SetRefine or t outside [0, T). */
 bool sgm_refine_table(float lambda, float sigma, int iterations, int t, float* out);
 
+/* Rectification (extension, "parity unpinned by the reference": its image pairs arrive rectified; defined here and restated by
+ * tests/rectify_ref.py).  Raw camera pairs are undistorted and row-aligned on the device ahead of the match -- OpenCV's
+ * initUndistortRectifyMap -> remap -- so that every entry point can be fed sensor images.  Off by default (every launch, buffer
+ * and result is then exactly what it is without); takes effect at the next SGM_Initialize / sgm_initialize / SGM_Reset /
+ * sgm_reset, which upload the maps and return false when the maps' shape is not the frame's or in row-tile mode (sgm_set_rows).
+ * Maps are as OpenCV's: per camera two float32 arrays map_x, map_y of [height][width]; output pixel (y, x) is sampled from the
+ * source image at (map_y[y][x], map_x[y][x]).  Source and output have the same width x height, the instance's shape; one set of
+ * maps serves all frames of a batch.
+ *   Quantisation (on the host, when the maps are set; the caller's arrays are not borrowed): for a map value m,
+ *     q = (int32_t)floor((double)m * 32.0 + 0.5).  If either coordinate of a pixel is not finite or has |m| > 32768, both xq and
+ *     yq of that pixel become -64: all four taps fall outside.
+ *   Sampling (exact integer arithmetic): x0 = xq >> 5 (arithmetic shift), ax = xq & 31, the same for y0, ay;
+ *     p00 = src(y0, x0), p01 = src(y0, x0 + 1), p10 = src(y0 + 1, x0), p11 = src(y0 + 1, x0 + 1), any tap outside
+ *     [0, H) x [0, W) counting as 0 (a constant border, decided per tap);
+ *     out = ((32-ax)*(32-ay)*p00 + ax*(32-ay)*p01 + (32-ax)*ay*p10 + ax*ay*p11 + 512) >> 10.
+ *   Integer maps copy pixels, identity maps reproduce the image exactly; there is no tolerance anywhere.
+ * SGM_SetRectify / sgm_set_rectify: map_lx == NULL turns rectification off (the other arguments are then not looked at);
+ * false, and nothing changes, for a NULL among the other three maps, width or height < 1, or (maps given) a build without the
+ * kernel.  The default instance remembers its maps across SGM_Shutdown, as it does the census window.
+ * The remap runs first in every match: census, the grey values of the adaptive P2, the refinement's guide and everything else
+ * downstream see the rectified images, so batches, both census kinds and any window, four-path mode, the right reference view,
+ * SGM_MatchBoth, the confidence, hole filling, the refinement, matches without Reset, sgm_set_overlap_post / sgm_set_stage_cus
+ * and sgm_match_planes (grey conversion, then the remap) compose as they do without it.  The caller's images -- also the device
+ * images of sgm_match_device and its twins -- are only read.  The rectified images stay readable as stages 19 / 20.
+ * What it does not do: pixels whose taps fall outside the source are 0, and masking their disparities is left to the caller;
+ * source images of another size than the frame's, row tiles, and per-frame maps within a batch are not supported.
+ * Timing: the remap counts toward "census". */
+bool SGM_SetRectify(int width, int height, const float* map_lx, const float* map_ly, const float* map_rx, const float* map_ry);
+/* The maps of one camera by the formulas of OpenCV's initUndistortRectifyMap, in double, each value rounded once to float32; host
+ * only, no device needed.  K, R, Knew: 3x3 row-major (camera matrix, rectifying rotation, new camera matrix); dist: k1 k2 p1 p2 k3.
+ *   iR = (Knew R)^-1;  [X Y W]' = iR [u v 1]';  x = X / W, y = Y / W, r2 = x^2 + y^2;  rad = 1 + k1 r2 + k2 r2^2 + k3 r2^3;
+ *   xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2);  yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y;
+ *   map_x[v][u] = fx xd + cx,  map_y[v][u] = fy yd + cy   with fx, fy, cx, cy of K.
+ * false for a NULL pointer, a size < 1 or a singular Knew R. */
+bool sgm_rectify_maps(const double K[9], const double dist[5], const double R[9], const double Knew[9], int width, int height,
+                      float* map_x, float* map_y);
+
 /* Same as SGM_Match but all three pointers are DEVICE pointers (HBM-resident frames) on the
  * instance's device.  Asynchronous on the instance's stream; SGM_Synchronize waits. */
 bool SGM_MatchDevice(const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left);
@@ -248,6 +285,8 @@ bool          sgm_set_census_kind(sgm_instance* s, int kind);                  /
 void          sgm_set_reference_view(sgm_instance* s, int right);              /* see SGM_SetReferenceView */
 bool          sgm_set_fill_holes(sgm_instance* s, int enable);                 /* see SGM_SetFillHoles */
 bool          sgm_set_refine(sgm_instance* s, int enable, float lambda, float sigma, int iterations, int keep_invalid);  /* see SGM_SetRefine */
+bool          sgm_set_rectify(sgm_instance* s, int width, int height, const float* map_lx, const float* map_ly, const float* map_rx,
+                              const float* map_ry);                            /* see SGM_SetRectify */
 bool          sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMOption* option);
 bool          sgm_reset(sgm_instance* s, uint16_t width, uint16_t height, const SGMOption* option);
 bool          sgm_match(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left);
@@ -385,6 +424,11 @@ bool   sgm_fill_holes(sgm_instance* s, float* d_disp, const uint8_t* d_class);
  * is on for matches. */
 bool   sgm_refine_disparity(sgm_instance* s, float* d_disp, const uint16_t* d_conf, const uint8_t* d_guide);
 
+/* The remap of SGM_SetRectify on any device images: B frames of the instance's shape each, d_out_* = d_* sampled through the maps
+ * in effect (those of the last initialize / reset).  No output may alias an input.  Asynchronous on sgm_stream(s).  false when no
+ * maps are in effect. */
+bool   sgm_rectify(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, uint8_t* d_out_left, uint8_t* d_out_right);
+
 /* ---- a test-platform frame end to end (the data formats either side of the path) ----
  * The server hands the board six byte planes per frame -- left B, G, R, right B, G, R, each h rows of w bytes
  * (HostScript_Server/server.py:105-131; received into frame_buffer.h:16-51 by tcp_perf_client.c:181-189) -- and expects h rows
@@ -407,6 +451,7 @@ bool   sgm_match_planes(sgm_instance* s, const uint8_t* planes, float fx, float 
  *        6 after LR check                 7 after speckle removal        8 final (all f32 [H][W])
  *        9 after hole filling (f32 [H][W]; needs sgm_keep_stages and filling on, SGM_SetFillHoles)
  *        18 hole-filling classes (u8 [H][W]; after any match with filling on)
+ *        19 rectified left image         20 rectified right image       (u8 [H][W]; 0 bytes with rectification off, SGM_SetRectify)
  *        10..17 per-direction path cost L_r of direction (which-10) (u8 [H][W][D]; cells the
  *               direction never visits read 0, cells visited twice hold the last-but-one visit)
  *        after a sgm_match_both (SGM_MatchBoth), where 4, 6, 7, 8 are the LEFT view's maps and 5 the raw right-view map:

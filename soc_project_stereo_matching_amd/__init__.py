@@ -7,9 +7,10 @@ is only a ctypes mirror of that C interface for tests and benchmarks; it contain
 has no CPU fallback -- importing works anywhere, calling into the library needs a gfx950 GPU.
 """
 from .sgm import (SGM, SGMInstance, SGMOption, default_option, library_path, load_library,  # noqa: F401
-                  STAGE_NAMES, synth_pair, set_refine, refine_table, REFINE_LAMBDA, REFINE_SIGMA, REFINE_ITERS)
+                  STAGE_NAMES, synth_pair, set_refine, refine_table, REFINE_LAMBDA, REFINE_SIGMA, REFINE_ITERS,
+                  rectify_maps, STAGE_RECT_LEFT, STAGE_RECT_RIGHT)
 from .sharding import SGMStream, frames_of_rank, match_sharded  # noqa: F401
 
 __all__ = ["SGM", "SGMInstance", "SGMOption", "default_option", "library_path", "load_library", "STAGE_NAMES",
-           "synth_pair", "set_refine", "refine_table", "REFINE_LAMBDA", "REFINE_SIGMA", "REFINE_ITERS", "SGMStream",
-           "frames_of_rank", "match_sharded"]
+           "synth_pair", "set_refine", "refine_table", "REFINE_LAMBDA", "REFINE_SIGMA", "REFINE_ITERS", "rectify_maps",
+           "STAGE_RECT_LEFT", "STAGE_RECT_RIGHT", "SGMStream", "frames_of_rank", "match_sharded"]

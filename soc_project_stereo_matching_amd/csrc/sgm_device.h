@@ -220,6 +220,14 @@ int sgmd_refine_pass(int ord, void* stream, const sgmd_geom* g, int vertical, co
                      const void* disp, const void* conf, void* U, void* V, void* Q, int first, int last, int keep_invalid,
                      void* out);
 
+/* Extension (parity unpinned by the reference), the rectification of include/sgm_mi355x.h (SGM_SetRectify); sgm_rectify.hip.
+ * One launch for both views of all B frames: out_left / out_right (u8 [B][H][W]) = left / right sampled through the quantised maps.
+ * maps: int32 [view: left, right][plane: xq, yq][SGMD_REMAP_PITCH(W * H)], entry p = y * W + x, the padding holding -64
+ * ("outside").  No output may alias an input.  sgm_host.c references it weakly (a host built without it has no rectification). */
+#define SGMD_REMAP_PITCH(n) (((size_t)(n) + 3) & ~(size_t)3)
+int sgmd_remap(int ord, void* stream, const sgmd_geom* g, const void* maps, const void* left, const void* right, void* out_left,
+               void* out_right);
+
 /* in-place raster-order 3x3 median (the reference calls MedianFilter with in == out, .c:120).
  * scratch: sgmd_median_scratch_bytes(g) bytes for the pre-sorted neighbourhoods. */
 /* status: NULL, or an int in page-locked host memory (sgmd_alloc_pinned) that the chained kernel of tall frames sets to 1 when a

@@ -129,6 +129,13 @@ struct sgm_instance {
     sgm_buf d_rf_conf;                   /* the confidence of a match whose caller did not ask for it, u16 [B][H][W] */
     sgm_buf d_rf_guide[2];               /* private copies of the reference image, used by turns (u8 [B][H][W] each) */
     int rf_turn;
+    /* rectification (sgm_set_rectify): the host's quantised copy of the maps last set (NULL: none; the layout sgmd_remap reads) and
+     * their shape; takes effect at the next initialize, which uploads them when they are new or the device copy is gone */
+    int32_t* rect_q;
+    int rect_w, rect_h;
+    bool rect_dirty;                     /* the device copy is not (or no longer) that of rect_q */
+    bool rect_on;                        /* ... and in effect for this shape: every match rectifies its images first */
+    sgm_buf d_rect_maps, d_rect_l, d_rect_r;   /* the maps; the rectified images, u8 [B][H][W] each: what every stage below the remap reads */
     /* both views' maps from one match (sgm_match_both; all allocated at its first use): the raw left WTA map (f32 [B][H][W]; the raw
      * right one is d_disp_r), the two finished maps as ONE batch of 2 B maps (f32 [2 B][H][W]: the left maps, then the right ones),
      * the speckle and median scratch of such a batch, the right view's snapshots for sgm_keep_stages (after the LR check, after
@@ -162,7 +169,7 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     PINNED_BUF(h_conf), DEVICE_BUF(d_rf_u), DEVICE_BUF(d_rf_v), DEVICE_BUF(d_rf_q), DEVICE_BUF(d_rf_conf), DEVICE_BUF(d_rf_guide[0]),
     DEVICE_BUF(d_rf_guide[1]), PINNED_BUF(h_left), PINNED_BUF(h_right), PINNED_BUF(h_disp), DEVICE_BUF(d_both_raw),
     DEVICE_BUF(d_both_maps), DEVICE_BUF(d_both_labels), DEVICE_BUF(d_both_sizes), DEVICE_BUF(d_both_totals), DEVICE_BUF(d_both_median),
-    DEVICE_BUF(d_both_snap), PINNED_BUF(h_disp_r),
+    DEVICE_BUF(d_both_snap), PINNED_BUF(h_disp_r), DEVICE_BUF(d_rect_maps), DEVICE_BUF(d_rect_l), DEVICE_BUF(d_rect_r),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -366,6 +373,7 @@ static void free_device_buffers(sgm_instance* s)
         buf_release(s, (sgm_buf*)((char*)s + k_buffers[i].offset), k_buffers[i].pinned);
     s->need_key[0] = 0;
     s->tab_W = s->tab_H = 0;
+    s->rect_dirty = true;
 }
 
 void sgm_destroy(sgm_instance* s)
@@ -384,6 +392,7 @@ void sgm_destroy(sgm_instance* s)
     if (s->post_stream) sgmd_stream_destroy(s->device, s->post_stream);
     sgmd_stream_destroy(s->device, s->stream);
     sgmd_free_pinned(s->device, s->h_status);
+    free(s->rect_q);
     free(s);
 }
 
@@ -550,6 +559,108 @@ bool sgm_set_refine(sgm_instance* s, int enable, float lambda, float sigma, int 
     if (!refine_params_set(&p, lambda, sigma, iterations, keep_invalid)) return false;
     s->rf_req = p;
     s->refine_req = 1;
+    return true;
+}
+
+/* ------------------------------------------------------------------ rectification (extension) */
+
+/* The remap launcher (sgm_rectify.hip), weakly referenced like the extensions above: a host built without it has no rectification */
+#pragma weak sgmd_remap
+static bool rectify_available(void) { return sgmd_remap != NULL; }
+
+bool sgm_rectify_maps(const double K[9], const double dist[5], const double R[9], const double Knew[9], int width, int height,
+                      float* map_x, float* map_y)
+{
+    if (!K || !dist || !R || !Knew || !map_x || !map_y || width < 1 || height < 1) return false;
+    double m[9], iR[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) m[3 * i + j] = Knew[3 * i] * R[j] + Knew[3 * i + 1] * R[3 + j] + Knew[3 * i + 2] * R[6 + j];
+    const double c0 = m[4] * m[8] - m[5] * m[7], c1 = m[5] * m[6] - m[3] * m[8], c2 = m[3] * m[7] - m[4] * m[6];
+    const double det = m[0] * c0 + m[1] * c1 + m[2] * c2;
+    if (!isfinite(det) || det == 0.0) return false;
+    iR[0] = c0 / det; iR[1] = (m[2] * m[7] - m[1] * m[8]) / det; iR[2] = (m[1] * m[5] - m[2] * m[4]) / det;
+    iR[3] = c1 / det; iR[4] = (m[0] * m[8] - m[2] * m[6]) / det; iR[5] = (m[2] * m[3] - m[0] * m[5]) / det;
+    iR[6] = c2 / det; iR[7] = (m[1] * m[6] - m[0] * m[7]) / det; iR[8] = (m[0] * m[4] - m[1] * m[3]) / det;
+    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+    const double k1 = dist[0], k2 = dist[1], p1 = dist[2], p2 = dist[3], k3 = dist[4];
+    for (int v = 0; v < height; ++v)
+        for (int u = 0; u < width; ++u) {
+            const double X = iR[0] * u + iR[1] * v + iR[2], Y = iR[3] * u + iR[4] * v + iR[5], Wz = iR[6] * u + iR[7] * v + iR[8];
+            const double x = X / Wz, y = Y / Wz, r2 = x * x + y * y;
+            const double rad = 1 + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2;
+            const double xd = x * rad + 2 * p1 * x * y + p2 * (r2 + 2 * x * x);
+            const double yd = y * rad + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
+            map_x[(size_t)v * width + u] = (float)(fx * xd + cx);
+            map_y[(size_t)v * width + u] = (float)(fy * yd + cy);
+        }
+    return true;
+}
+
+/* The quantised maps of both views in the layout sgmd_remap reads (sgm_device.h), malloc'ed; NULL: bad arguments or out of memory */
+static int32_t* rectify_quantise(int width, int height, const float* map_lx, const float* map_ly, const float* map_rx, const float* map_ry)
+{
+    if (!map_lx || !map_ly || !map_rx || !map_ry || width < 1 || height < 1 || (long long)width * height > 0x7FFFFFFFLL) return NULL;
+    const size_t n = (size_t)width * height, pitch = SGMD_REMAP_PITCH(n);
+    int32_t* q = (int32_t*)malloc(4 * pitch * sizeof *q);
+    if (!q) return NULL;
+    const float* const mx[2] = {map_lx, map_rx};
+    const float* const my[2] = {map_ly, map_ry};
+    for (int view = 0; view < 2; ++view) {
+        int32_t* xq = q + (size_t)view * 2 * pitch;
+        int32_t* yq = xq + pitch;
+        for (size_t p = 0; p < pitch; ++p) {
+            const double x = p < n ? (double)mx[view][p] : NAN, y = p < n ? (double)my[view][p] : NAN;
+            /* !(<=) also catches NaN: such a pixel has all four taps outside */
+            const bool ok = fabs(x) <= 32768.0 && fabs(y) <= 32768.0;
+            xq[p] = ok ? (int32_t)floor(x * 32.0 + 0.5) : -64;
+            yq[p] = ok ? (int32_t)floor(y * 32.0 + 0.5) : -64;
+        }
+    }
+    return q;
+}
+
+/* the instance takes q (NULL: rectification off) */
+static void rectify_install(sgm_instance* s, int32_t* q, int width, int height)
+{
+    free(s->rect_q);
+    s->rect_q = q;
+    s->rect_w = q ? width : 0;
+    s->rect_h = q ? height : 0;
+    s->rect_dirty = true;                                        /* takes effect at the next initialize */
+}
+
+bool sgm_set_rectify(sgm_instance* s, int width, int height, const float* map_lx, const float* map_ly, const float* map_rx,
+                     const float* map_ry)
+{
+    if (!s) return false;
+    if (!map_lx) { rectify_install(s, NULL, 0, 0); return true; }
+    if (!rectify_available()) FAIL("the rectification is not part of this build");
+    int32_t* q = rectify_quantise(width, height, map_lx, map_ly, map_rx, map_ry);
+    if (!q) return false;
+    rectify_install(s, q, width, height);
+    return true;
+}
+
+/* the maps on the device and the two rectified images, beside upload_tables: a Reset with unchanged maps uploads nothing */
+static bool upload_rectify(sgm_instance* s)
+{
+    const size_t px = (size_t)s->g.B * s->g.W * s->g.H;
+    const size_t bytes = 4 * SGMD_REMAP_PITCH((size_t)s->rect_w * s->rect_h) * sizeof(int32_t);
+    const buf_request bufs[] = {{&s->d_rect_maps, bytes, 0}, {&s->d_rect_l, px, 0}, {&s->d_rect_r, px, 0}};
+    if (!reserve_all(s, bufs, 3, 0)) FAIL("device allocation failed for the rectification of %dx%d", s->g.W, s->g.H);
+    if (!s->rect_dirty) return true;
+    /* queued remaps read the maps on s->stream: the upload is behind them; the host copy may be replaced once this returns */
+    if (sgmd_h2d_async(s->device, s->stream, s->d_rect_maps.p, s->rect_q, bytes) != 0 || sync_streams(s) != 0)
+        FAIL("uploading the rectification maps failed");
+    s->rect_dirty = false;
+    return true;
+}
+
+bool sgm_rectify(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, uint8_t* d_out_left, uint8_t* d_out_right)
+{
+    if (!s || !s->initialized || !d_left || !d_right || !d_out_left || !d_out_right) return false;
+    if (!s->rect_on) FAIL("sgm_rectify: no rectification maps are in effect (sgm_set_rectify, then sgm_initialize / sgm_reset)");
+    if (sgmd_remap(s->device, s->stream, &s->g, s->d_rect_maps.p, d_left, d_right, d_out_left, d_out_right) != 0) FAIL("a kernel launch failed");
     return true;
 }
 
@@ -901,7 +1012,16 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
     if (s->refine_req && s->fill_req)
         FAIL("the refinement (sgm_set_refine) and hole filling (sgm_set_fill_holes) do not combine: the refinement fills by itself, "
              "and a filled pixel would carry the confidence of a disparity the LR check rejected");
+    s->rect_on = false;
+    if (s->rect_q && row_tiled(s))
+        FAIL("the rectification (sgm_set_rectify) works on whole frames: not available in row-tile mode (sgm_set_rows)");
+    if (s->rect_q && (s->rect_w != width || s->rect_h != height))
+        FAIL("the rectification maps (sgm_set_rectify) are %dx%d, the frame is %dx%d", s->rect_w, s->rect_h, width, height);
     if (!ensure_buffers(s)) return false;
+    if (s->rect_q) {
+        if (!upload_rectify(s)) return false;
+        s->rect_on = true;
+    }
     if (s->fill_req) {
         if (ensure_fill(s) != 0) return false;
         s->fill_on = true;
@@ -1186,6 +1306,16 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
     /* the aggregation rewrites the planes the previous match's cost sum may still be reading on its own stream */
     if (s->sum_pending) LAUNCH(sgmd_stream_wait_event(dev, st, s->ev_sum));
     if (!s->s_is_zero) LAUNCH(materialize_S(s));             /* Match without Reset: S of the previous frame is needed now */
+    /* rectification (extension): from here on the images are the instance's rectified ones; the caller's are only read.  Everything
+     * that reads them -- the census, the aggregation's grey values, the copies for the guide and for the fused sweep, a later
+     * materialize_S through that copy -- is queued on this stream, so stream order alone keeps the remap of match n + 1 behind the
+     * readers of match n, also with the cost sum and the post pass on streams of their own.  Timed as "census" */
+    if (s->rect_on) {
+        mark(s, T_CENSUS);
+        LAUNCH(sgmd_remap(dev, st, g, s->d_rect_maps.p, d_left, d_right, s->d_rect_l.p, s->d_rect_r.p));
+        d_left = s->d_rect_l.p;
+        d_right = s->d_rect_r.p;
+    }
     /* the refinement's guide: the caller (or the next match's upload) may rewrite the images while the post pass of this match
      * still runs on a stream of its own, so it reads a private copy.  Two copies by turns: the copy of match n + 2 is queued behind
      * what waited for the post pass of match n (the cost sum of match n + 1 waits for it, and this stream waits for that sum) */
@@ -1195,7 +1325,7 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
         s->rf_turn ^= 1;
         LAUNCH(sgmd_d2d_async(dev, st, (void*)guide, s->reference_view ? d_right : d_left, (size_t)g->B * g->W * g->H));
     }
-    mark(s, T_CENSUS);
+    if (!s->rect_on) mark(s, T_CENSUS);
     LAUNCH(prepare_costs(s, d_left, d_right));                                                      /* .c:82-83 */
     mark(s, T_COST);
     /* .c:89: the cost volume is recomputed inside the aggregation kernel; it is only materialised when a
@@ -1794,6 +1924,7 @@ size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacit
     if ((which == 9 || which == 18) && !s->fill_on) return 0;
     if ((which == 26 || which == 27) && !(s->keep_stages && s->last_both_kept)) return 0;
     if (which == 28 && !s->last_both) return 0;
+    if ((which == 19 || which == 20) && !s->rect_on) return 0;
     if (which == 2 && !s->d_cost.p) return 0;
     if (which == 3 && (ensure_S(s) != 0 || materialize_S(s) != 0)) return 0;
     switch (which) {
@@ -1812,6 +1943,8 @@ size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacit
     case 28: src = (const char*)s->d_both_maps.p + ((size_t)s->g.B + f) * px * 4; elem = 4; break;
     case 9: src = (const char*)s->d_fill_map.p + f * px * 4; elem = 4; break;
     case 18: src = (const char*)s->d_fill_class.p + f * px; elem = 1; break;
+    case 19: src = (const char*)s->d_rect_l.p + f * px; elem = 1; break;
+    case 20: src = (const char*)s->d_rect_r.p + f * px; elem = 1; break;
     default:
         if (which >= 10 && which < 10 + s->paths.ndirs) {
             /* frame-addressed base of the plane; only rows [plane_row_lo, plane_row_lo + plane_rows) have storage */
@@ -1895,6 +2028,37 @@ bool SGM_SetRefine(int enable, float lambda, float sigma, int iterations, int ke
     return true;
 }
 
+/* the default instance's maps, quantised: kept across SGM_Shutdown, each default instance gets a copy */
+static struct { int32_t* q; int w, h; } g_default_rect;
+
+static bool default_rectify_install(void)
+{
+    int32_t* copy = NULL;
+    if (g_default_rect.q) {
+        const size_t bytes = 4 * SGMD_REMAP_PITCH((size_t)g_default_rect.w * g_default_rect.h) * sizeof(int32_t);
+        copy = (int32_t*)malloc(bytes);
+        if (!copy) FAIL("out of host memory");
+        memcpy(copy, g_default_rect.q, bytes);
+    }
+    rectify_install(g_default, copy, g_default_rect.w, g_default_rect.h);
+    return true;
+}
+
+bool SGM_SetRectify(int width, int height, const float* map_lx, const float* map_ly, const float* map_rx, const float* map_ry)
+{
+    int32_t* q = NULL;
+    if (map_lx) {
+        if (!rectify_available()) FAIL("the rectification is not part of this build");
+        q = rectify_quantise(width, height, map_lx, map_ly, map_rx, map_ry);
+        if (!q) return false;
+    }
+    free(g_default_rect.q);
+    g_default_rect.q = q;
+    g_default_rect.w = q ? width : 0;
+    g_default_rect.h = q ? height : 0;
+    return g_default ? default_rectify_install() : true;
+}
+
 bool SGM_SetCensusWindow(int width, int height)
 {
     if (width < 1 || height < 1 || !(width & 1) || !(height & 1) || width * height > 64) return false;
@@ -1936,6 +2100,7 @@ bool SGM_Initialize(uint16_t width, uint16_t height, const SGMOption* option)
         sgm_set_census_kind(g_default, g_default_census_kind);
         sgm_set_reference_view(g_default, g_default_view);
         if (g_default_fill) sgm_set_fill_holes(g_default, 1);
+        if (g_default_rect.q && !default_rectify_install()) return false;
         if (g_default_refine.enable)
             sgm_set_refine(g_default, 1, g_default_refine.lambda, g_default_refine.sigma, g_default_refine.iters,
                            g_default_refine.keep_invalid);

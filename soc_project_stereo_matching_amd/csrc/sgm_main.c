@@ -19,10 +19,14 @@
  *                                     --right-reference (OUT is the left view's map)
  *            [--refine[=LAMBDA,SIGMA,ITERS]]   extension: confidence-guided edge-aware refinement of the map (SGM_SetRefine;
  *                             defaults SGM_REFINE_DEFAULT_*)
+ *            [--rectify CALIB.txt]   extension: LEFT and RIGHT are raw camera images, rectified on the device ahead of the match
+ *                             (SGM_SetRectify) through the maps of the 64 numbers in CALIB.txt (sgm_calib.h)
+ *            [--rectified-out LEFT.pgm RIGHT.pgm]   with --rectify: the two rectified images the match ran on
  *   sgm_main --convert IN OUT.png        (image I/O only, no GPU: used by the CPU tests)
  */
 #define _POSIX_C_SOURCE 200809L
 #include "../../include/sgm_mi355x.h"
+#include "sgm_calib.h"
 #include "sgm_image_io.h"
 
 #include <math.h>
@@ -110,6 +114,8 @@ int main(int argc, char** argv)
     const char* conf_path = NULL;
     const char* right_out = NULL;
     const char* right_raw = NULL;
+    const char* calib_path = NULL;
+    const char* rect_out[2] = {NULL, NULL};
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
     int census_kind = SGM_CENSUS_CENTRE;
     float refine_lambda = SGM_REFINE_DEFAULT_LAMBDA, refine_sigma = SGM_REFINE_DEFAULT_SIGMA;
@@ -131,6 +137,8 @@ int main(int argc, char** argv)
         else if (v && !strcmp(a, "--confidence")) { conf_path = v; ++i; }
         else if (v && !strcmp(a, "--right-out")) { right_out = v; ++i; }
         else if (v && !strcmp(a, "--right-raw")) { right_raw = v; ++i; }
+        else if (v && !strcmp(a, "--rectify")) { calib_path = v; ++i; }
+        else if (i + 2 < argc && !strcmp(a, "--rectified-out")) { rect_out[0] = argv[i + 1]; rect_out[1] = argv[i + 2]; i += 2; }
         else if (v && !strcmp(a, "--repeat")) { repeat = atoi(v); ++i; }
         else if (v && !strcmp(a, "--device")) { device = atoi(v); ++i; }
         else if (v && !strcmp(a, "--paths")) { opt.num_paths = (uint8_t)atoi(v); SGM_SetHonorNumPaths(1); ++i; }
@@ -161,6 +169,7 @@ int main(int argc, char** argv)
                         "(OUT would silently be the left map)\n");
         return 2;
     }
+    if (rect_out[0] && !calib_path) { fprintf(stderr, "--rectified-out needs --rectify\n"); return 2; }
 
     int w1, h1, w2, h2;
     uint8_t* left = sgm_load_gray(argv[1], &w1, &h1);
@@ -183,6 +192,13 @@ int main(int argc, char** argv)
         printf("refinement unavailable or parameters out of range (%g, %g, %d)\n", refine_lambda, refine_sigma, refine_iters);
         return -2;
     }
+    if (calib_path) {
+        const size_t px = (size_t)w1 * h1;
+        float* maps = sgm_calib_maps(calib_path, w1, h1);
+        const bool ok = maps && SGM_SetRectify(w1, h1, maps, maps + px, maps + 2 * px, maps + 3 * px);
+        free(maps);
+        if (!ok) { printf("rectification unavailable or a bad calibration file\n"); return -2; }
+    }
     if (!SGM_Initialize((uint16_t)w1, (uint16_t)h1, &opt)) { printf("SGM initialization failed\n"); return -2; }
     float* disp = (float*)malloc(sizeof(float) * (size_t)w1 * h1);
     float* disp_r = (right_out || right_raw) ? (float*)malloc(sizeof(float) * (size_t)w1 * h1) : NULL;
@@ -202,6 +218,12 @@ int main(int argc, char** argv)
     int rc = write_map(disp, w1, h1, argv[3], raw_path);
     if (disp_r && write_map(disp_r, w1, h1, right_out, right_raw) != 0) rc = -1;
     if (conf_path && sgm_write_pgm16(conf_path, conf, w1, h1) != 0) rc = -1;
+    for (int v = 0; v < 2 && rect_out[0]; ++v) {                  /* the images the match ran on: stages 19 / 20 */
+        const size_t px = (size_t)w1 * h1;
+        uint8_t* img = (uint8_t*)malloc(px);
+        if (!img || SGM_ReadStage(19 + v, img, px) != px || sgm_write_pgm(rect_out[v], img, w1, h1) != 0) rc = -1;
+        free(img);
+    }
     SGM_Shutdown();
     free(disp); free(disp_r); free(conf); free(left); free(right);
     return rc ? 1 : 0;

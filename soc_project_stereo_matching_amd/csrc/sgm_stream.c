@@ -15,6 +15,8 @@
  *                two maps, and "hash_frame0_right" is the right view's hash beside the left one's
  *   --census WxH, --census-kind centre|symmetric   extensions: the census window (SGM_SetCensusWindow) and kind (SGM_SetCensusKind);
  *                symmetric without --census uses SGM_CENSUS_SYMMETRIC_DEFAULT_W x _H
+ *   --rectify CALIB.txt   extension: the frames are raw camera images, rectified on the device ahead of every match (SGM_SetRectify)
+ *                through the maps of the 64 numbers in CALIB.txt (sgm_calib.h)
  *   --numa-node K  run (and allocate) on the CPUs of NUMA node K -- the node the GPU hangs off (/sys/bus/pci/devices/<bdf>/numa_node):
  *                the host threads spin in stream synchronisation and feed 11 GB/s over PCIe; bench.py pins itself the same way
  *
@@ -24,6 +26,7 @@
  */
 #define _GNU_SOURCE
 #include "../../include/sgm_mi355x.h"
+#include "sgm_calib.h"
 
 #include <pthread.h>
 #include <sched.h>
@@ -70,6 +73,7 @@ static unsigned long long fnv1a(const void* p, size_t n)
 typedef struct {
     int k, n_inst, W, H, B, n_batches, pageable, both, census_kind, census_w, census_h;
     const SGMOption* opt;
+    const float* maps;           /* --rectify: map_lx, map_ly, map_rx, map_ry of W * H floats each (NULL: none) */
     uint8_t **L, **R;            /* [n_batches] batches of B frames, shared, read-only */
     volatile double stop_at;     /* set by main right after the start barrier */
     long batches_done;
@@ -87,7 +91,8 @@ static void* worker_main(void* p)
     float *out = NULL, *out_r = NULL;
     w->failed = 1;
     if (s && sgm_set_batch(s, w->B) && sgm_set_overlap_post(s, 1) && sgm_set_census_kind(s, w->census_kind) &&
-        (!w->census_w || sgm_set_census_window(s, w->census_w, w->census_h)) && sgm_initialize(s, (uint16_t)w->W, (uint16_t)w->H, w->opt)) {
+        (!w->census_w || sgm_set_census_window(s, w->census_w, w->census_h)) &&
+        (!w->maps || sgm_set_rectify(s, w->W, w->H, w->maps, w->maps + px, w->maps + 2 * px, w->maps + 3 * px)) && sgm_initialize(s, (uint16_t)w->W, (uint16_t)w->H, w->opt)) {
         out = w->pageable ? (float*)malloc(w->B * px * sizeof(float)) : (float*)sgm_host_alloc(s, w->B * px * sizeof(float));
         if (w->both) out_r = w->pageable ? (float*)malloc(w->B * px * sizeof(float)) : (float*)sgm_host_alloc(s, w->B * px * sizeof(float));
         w->failed = out == NULL || (w->both && out_r == NULL);
@@ -122,6 +127,7 @@ int main(int argc, char** argv)
     int census_kind = SGM_CENSUS_CENTRE, census_w = 0, census_h = 0;
     double seconds = 2.0;
     unsigned seed = 0x5EED0002u;
+    const char* calib_path = NULL;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
         const char* v = i + 1 < argc ? argv[i + 1] : NULL;
@@ -137,6 +143,7 @@ int main(int argc, char** argv)
         else if (v && !strcmp(a, "--seconds")) seconds = atof(argv[++i]);
         else if (v && !strcmp(a, "--numa-node")) node = atoi(argv[++i]);
         else if (v && !strcmp(a, "--seed")) seed = (unsigned)strtoul(argv[++i], NULL, 0);
+        else if (v && !strcmp(a, "--rectify")) calib_path = argv[++i];
         else if (v && !strcmp(a, "--census")) {
             if (sscanf(v, "%dx%d", &census_w, &census_h) != 2) { fprintf(stderr, "sgm_stream: --census wants WxH, e.g. 7x7\n"); return 2; }
             ++i;
@@ -160,8 +167,14 @@ int main(int argc, char** argv)
     opt.is_check_lr = true; opt.lrcheck_thres = 1.0f; opt.is_check_unique = true; opt.uniqueness_ratio = 0.99;
     opt.is_remove_speckles = true; opt.min_speckle_area = 50; opt.p1 = 10; opt.p2_init = 150;
     const size_t px = (size_t)W * H;
+    float* maps = calib_path ? sgm_calib_maps(calib_path, W, H) : NULL;
+    if (calib_path && !maps) return 2;
 
     if (blocking) {
+        if (maps && !SGM_SetRectify(W, H, maps, maps + px, maps + 2 * px, maps + 3 * px)) {
+            fprintf(stderr, "sgm_stream: rectification unavailable\n");
+            return 2;
+        }
         if (!SGM_SetCensusKind(census_kind) || (census_w && !SGM_SetCensusWindow(census_w, census_h))) {
             fprintf(stderr, "sgm_stream: unsupported census %dx%d\n", census_w, census_h);
             return 2;
@@ -187,7 +200,7 @@ int main(int argc, char** argv)
                "\"frames\": %ld, \"seconds\": %.4f, \"fps\": %.2f, \"ms_per_frame\": %.4f, \"mdisp_per_s\": %.1f, \"hash_frame0\": \"%016llx\"}\n",
                W, H, D, n, el, n / el, el / n * 1e3, (double)px * D * 8 * n / el / 1e6, hash0);
         SGM_Shutdown();
-        free(l); free(r); free(out);
+        free(l); free(r); free(out); free(maps);
         return 0;
     }
 
@@ -209,7 +222,7 @@ int main(int argc, char** argv)
     pthread_t th[16];
     memset(w, 0, sizeof w);
     for (int k = 0; k < N; ++k) {
-        w[k] = (worker){k, N, W, H, B, n_batches, pageable, both, census_kind, census_w, census_h, &opt, L, R, 1e300, 0, 0, 0, 0, &start};
+        w[k] = (worker){k, N, W, H, B, n_batches, pageable, both, census_kind, census_w, census_h, &opt, maps, L, R, 1e300, 0, 0, 0, 0, &start};
         if (pthread_create(&th[k], NULL, worker_main, &w[k]) != 0) return 1;
     }
     /* every worker is set up (its warm-up batch included) when the barrier opens */
@@ -238,7 +251,7 @@ int main(int argc, char** argv)
         else { sgm_host_free(owner, L[i]); sgm_host_free(owner, R[i]); }
     }
     sgm_destroy(owner);
-    free(L); free(R);
+    free(L); free(R); free(maps);
     const long frames = batches * B;
     char right[64] = "";                                /* --both: the right view's hash beside the left one's */
     if (both) snprintf(right, sizeof right, "\"hash_frame0_right\": \"%016llx\", ", hash0_r);

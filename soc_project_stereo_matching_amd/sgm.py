@@ -23,6 +23,8 @@ _STAGE_DTYPE = [np.uint32, np.uint32, np.uint8, np.uint16] + [np.float32] * 5
 STAGE_FILLED, STAGE_FILL_CLASS = 9, 18
 # after a match_both: the right view after the LR check / after speckle removal (both need keep_stages) / finished
 STAGE_RIGHT_AFTER_LR, STAGE_RIGHT_AFTER_SPECKLE, STAGE_RIGHT_FINAL = 26, 27, 28
+# the rectified left / right image (u8; they exist only with rectification on, set_rectify: read_stages() leaves them out)
+STAGE_RECT_LEFT, STAGE_RECT_RIGHT = 19, 20
 # the refinement's default parameters (SGM_REFINE_DEFAULT_* of include/sgm_mi355x.h)
 REFINE_LAMBDA, REFINE_SIGMA, REFINE_ITERS = 16.0, 1.5, 1
 # census kinds (SGM_CENSUS_* of include/sgm_mi355x.h) and the drivers' window for the symmetric kind
@@ -161,6 +163,15 @@ def _load() -> C.CDLL:
         L.SGM_MatchBoth.restype = C.c_bool
         L.sgm_depth_from_both.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_float] * 4 + [C.c_void_p]
         L.sgm_depth_from_both.restype = C.c_bool
+    if hasattr(L, "sgm_set_rectify"):         # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_set_rectify.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+        L.sgm_set_rectify.restype = C.c_bool
+        L.SGM_SetRectify.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4
+        L.SGM_SetRectify.restype = C.c_bool
+        L.sgm_rectify.argtypes = [C.c_void_p] * 5
+        L.sgm_rectify.restype = C.c_bool
+        L.sgm_rectify_maps.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.sgm_rectify_maps.restype = C.c_bool
     L.sgm_set_batch.argtypes = [C.c_void_p, C.c_int]
     L.sgm_set_batch.restype = C.c_bool
     L.sgm_select_frame.argtypes = [C.c_void_p, C.c_int]
@@ -260,6 +271,31 @@ def refine_table(lam, sigma, iterations, t):
     return out
 
 
+def rectify_maps(K, dist, R, Knew, width, height):
+    """sgm_rectify_maps: (map_x, map_y), float32 [height][width] each, of one camera by the formulas of OpenCV's
+    initUndistortRectifyMap (host only).  K, R, Knew: 3x3; dist: k1 k2 p1 p2 k3."""
+    mats = [np.ascontiguousarray(m, np.float64).reshape(-1) for m in (K, dist, R, Knew)]
+    if [m.size for m in mats] != [9, 5, 9, 9]:
+        raise ValueError("rectify_maps: K, R, Knew are 3x3, dist has 5 coefficients")
+    map_x = np.empty((int(height), int(width)), np.float32)
+    map_y = np.empty((int(height), int(width)), np.float32)
+    if not load_library().sgm_rectify_maps(*(m.ctypes.data for m in mats), int(width), int(height), map_x.ctypes.data,
+                                           map_y.ctypes.data):
+        raise ValueError("sgm_rectify_maps: a size below 1 or a singular Knew R")
+    return map_x, map_y
+
+
+def _rectify_args(maps):
+    """(width, height, four pointers, the arrays kept alive) for sgm_set_rectify / SGM_SetRectify; None first = off"""
+    if maps[0] is None:
+        return 0, 0, [None] * 4, []
+    arrays = [np.ascontiguousarray(m, np.float32) for m in maps]
+    if arrays[0].ndim != 2 or any(a.shape != arrays[0].shape for a in arrays):
+        raise ValueError("set_rectify: four float32 maps of one shape [H][W] are needed")
+    h, w = arrays[0].shape
+    return w, h, [a.ctypes.data for a in arrays], arrays
+
+
 def _device_ptr(x, dtype, count, name):
     """A device pointer from an int or a torch tensor (checked: contiguous, dtype, number of elements)."""
     if isinstance(x, int):
@@ -300,7 +336,7 @@ class _StageReader:
             dt, shp = np.uint64, (h, w)
         elif idx == STAGE_FILLED:
             dt, shp = np.float32, (h, w)
-        elif idx == STAGE_FILL_CLASS:
+        elif idx in (STAGE_FILL_CLASS, STAGE_RECT_LEFT, STAGE_RECT_RIGHT):
             dt, shp = np.uint8, (h, w)
         elif idx in (STAGE_RIGHT_AFTER_LR, STAGE_RIGHT_AFTER_SPECKLE, STAGE_RIGHT_FINAL):
             dt, shp = np.float32, (h, w)
@@ -320,6 +356,10 @@ class _StageReader:
     def read_filled(self):
         """Stage 9: the map after hole filling, before the median (needs keep_stages and fill on)."""
         return self.read_stage(STAGE_FILLED)
+
+    def read_rectified(self):
+        """Stages 19 and 20: the rectified (left, right) images the last match ran on (needs rectification on, set_rectify)."""
+        return self.read_stage(STAGE_RECT_LEFT), self.read_stage(STAGE_RECT_RIGHT)
 
     def read_fill_classes(self):
         """Stage 18: the hole-filling classes, 0 valid / 1 occluded / 2 mismatched (after any match with fill on)."""
@@ -363,6 +403,12 @@ class SGM(_StageReader):
     def set_refine(self, enable=True, lam=REFINE_LAMBDA, sigma=REFINE_SIGMA, iterations=REFINE_ITERS, keep_invalid=False) -> bool:
         """Extension: confidence-guided edge-aware refinement of the map (include/sgm_mi355x.h); next initialize/reset."""
         return set_refine(enable, lam, sigma, iterations, keep_invalid)
+
+    def set_rectify(self, map_lx, map_ly=None, map_rx=None, map_ry=None) -> bool:
+        """Extension: rectify raw camera pairs on the device ahead of every match, through OpenCV-style float32 maps [H][W] of
+        the left and the right camera (include/sgm_mi355x.h, SGM_SetRectify); None turns it off; next initialize/reset."""
+        w, h, ptrs, _keep = _rectify_args((map_lx, map_ly, map_rx, map_ry))
+        return bool(self.lib.SGM_SetRectify(w, h, *ptrs))
 
     def keep_stages(self, enable=True):
         self.lib.SGM_KeepStages(int(enable))
@@ -536,6 +582,20 @@ class SGMInstance(_StageReader):
         """Extension: confidence-guided edge-aware refinement of the map (include/sgm_mi355x.h); next initialize/reset.  False for
         parameters out of range."""
         return bool(self.lib.sgm_set_refine(self.handle, int(enable), lam, sigma, int(iterations), int(keep_invalid)))
+
+    def set_rectify(self, map_lx, map_ly=None, map_rx=None, map_ry=None) -> bool:
+        """Extension: rectify raw camera pairs on the device ahead of every match, through OpenCV-style float32 maps [H][W] of
+        the left and the right camera (include/sgm_mi355x.h, SGM_SetRectify); None turns it off; next initialize/reset."""
+        w, h, ptrs, _keep = _rectify_args((map_lx, map_ly, map_rx, map_ry))
+        return bool(self.lib.sgm_set_rectify(self.handle, w, h, *ptrs))
+
+    def rectify(self, d_left, d_right, d_out_left, d_out_right) -> bool:
+        """sgm_rectify: the remap alone on device images of the instance's batch and shape (uint8; device pointers or torch
+        tensors), through the maps in effect; asynchronous on `stream`.  False when no maps are in effect."""
+        n = self.batch * self.shape[0] * self.shape[1] if self.shape else 0
+        return bool(self.lib.sgm_rectify(self.handle, *(_device_ptr(x, np.uint8, n, name) for x, name in
+                                                        ((d_left, "d_left"), (d_right, "d_right"), (d_out_left, "d_out_left"),
+                                                         (d_out_right, "d_out_right")))))
 
     def refine_disparity(self, d_disp, d_conf, d_guide) -> bool:
         """sgm_refine_disparity: refine a device map of the instance's batch and shape in place with the parameters of the last
