@@ -63,6 +63,8 @@ struct sgm_instance {
     sgm_buf d_up_scratch;        /* its hand-over rows, progress words and tickets */
     sgm_buf d_left_keep;         /* copy of the last fused match's left image(s): what re-creating the three planes needs (Q14, stage read-back) */
     unsigned up_gen;             /* launch counter of the fused kernel (its progress words carry it) */
+    int up_key[5];               /* B, W, H, Dp, rows per workgroup of the fused launches the scratch's progress words belong to
+                                    ([0] == 0: none, the scratch is to be zeroed): ensure_upsum */
     int last_up_rows;            /* rows per workgroup of the fused sweep in the LAST match, 0 if it ran the separate kernels */
     bool planes_partial;         /* the planes of the last frame lack the upward directions: materialize_S re-creates them first */
     int env_upsum, env_upsum_rows, env_upsum_wgs;   /* SGM_UPSUM, SGM_UPSUM_ROWS, SGM_UPSUM_WGS */
@@ -372,6 +374,7 @@ static void free_device_buffers(sgm_instance* s)
     for (size_t i = 0; i < sizeof k_buffers / sizeof k_buffers[0]; ++i)
         buf_release(s, (sgm_buf*)((char*)s + k_buffers[i].offset), k_buffers[i].pinned);
     s->need_key[0] = 0;
+    s->up_key[0] = 0;
     s->tab_W = s->tab_H = 0;
     s->rect_dirty = true;
 }
@@ -1227,11 +1230,32 @@ static int lr_stage(sgm_instance* s, void* st, void* d_out)
  * pending planes) still describe exactly the matches that completed, so a later Match without Reset (Q14) accumulates
  * onto the right thing. */
 #define LAUNCH(expr) do { if ((expr) != 0) goto failed; } while (0)
-/* scratch of the fused last sweep (zero when allocated: its progress words start below every generation) and the kept left image */
+/* Scratch of the fused last sweep and the kept left image.  The kernel's progress words sit BEHIND the hand-over rows, at an
+ * offset that depends on (B, W, Dp); their number on H and the rows per workgroup (sgm_upsum.hip).  A word carries
+ * (generation << 13) + iterations published, the generation being the low 19 bits of up_gen, and a waiting row group compares
+ * (int)(word - want) < 0.
+ *   Unchanged geometry: launch g leaves every word at (g << 13) + n, n < 2^13 (each row group's helper stores its final count before
+ *   it draws the next ticket), and launch g + 1 asks for ((g + 1) << 13) + c with 1 <= c < 2^13.  The difference is n - c - 2^13 in
+ *   [-2^14, 0) modulo 2^32 whatever g is, the wrap of the 19 bits to 0 included: "behind", as it must be.  Nothing to do.
+ *   (A launch that is refused after the counter went up skips a generation: the difference is then within -2^15, behind as well.)
+ *   Changed geometry (or a scratch that is new): the words' places hold hand-over bytes of the earlier shape, or the words of a
+ *   generation far back.  The scratch is zero-filled on s->stream in front of the launch (behind every earlier fused launch: the
+ *   stream has waited for ev_sum, or the launch ran on it) and the counter starts over: a zero word is "behind" want only while
+ *   generation << 13 stays below 2^31, which a restart at 1 guarantees and a zero-fill alone would not from launch 2^18 on.
+ * The one zero-fill of a first launch is the one the allocation always had; an unchanged geometry adds none. */
 static int ensure_upsum(sgm_instance* s)
 {
-    const size_t px = (size_t)s->g.B * s->g.W * s->g.H;
-    return reserve(s, &s->d_up_scratch, sgmd_upsum_scratch_bytes(&s->g), BUF_ZERO) && reserve(s, &s->d_left_keep, px, 0) ? 0 : -1;
+    const size_t px = (size_t)s->g.B * s->g.W * s->g.H, bytes = sgmd_upsum_scratch_bytes(&s->g);
+    const int key[5] = {s->g.B, s->g.W, s->g.H, s->g.Dp, s->up_rows};
+    if (!buf_holds(&s->d_up_scratch, bytes)) s->up_key[0] = 0;
+    if (!reserve(s, &s->d_up_scratch, bytes, 0)) return -1;
+    if (memcmp(key, s->up_key, sizeof key) != 0) {
+        s->up_key[0] = 0;                                        /* (B >= 1: 0 = no key) a fill that fails leaves none behind */
+        if (sgmd_memset_async(s->device, s->stream, s->d_up_scratch.p, 0, bytes) != 0) return -1;
+        memcpy(s->up_key, key, sizeof key);
+        s->up_gen = 0;
+    }
+    return reserve(s, &s->d_left_keep, px, 0) ? 0 : -1;
 }
 
 /* The buffers of sgm_match_both, sized together on its first use (keep: the right view's snapshots too; staging: the page-locked

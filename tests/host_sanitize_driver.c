@@ -138,6 +138,30 @@ static int both_family(void)
     return 0;
 }
 
+/* one instance kept across geometries with the fused last sweep on (SGM_UPSUM=1, read at sgm_create): a large shape, a smaller
+ * one, a smaller batch, a Match without Reset behind a fused match, the large shape again.  The scratch of the fused sweep is
+ * kept and zero-filled for the geometry in effect: the fill must fit what is allocated */
+static int reuse_sequence(void)
+{
+    const int W = 300, H = 40, B = 3;
+    SGMOption o = options(128, 0), shifted = options(128, 3);
+    uint8_t* img = (uint8_t*)calloc((size_t)B * W * H, 1);
+    float* out = (float*)calloc((size_t)B * W * H, sizeof(float));
+    CHECK(img && out && setenv("SGM_UPSUM", "1", 1) == 0);
+    sgm_instance* s = sgm_create(0);
+    CHECK(unsetenv("SGM_UPSUM") == 0);
+    CHECK(s && sgm_set_batch(s, B) && sgm_initialize(s, (uint16_t)W, (uint16_t)H, &o));
+    CHECK(sgm_match(s, img, img, out) && sgm_fused_sweep_rows(s) == 3);
+    CHECK(sgm_reset(s, 161, 20, &shifted) && sgm_match(s, img, img, out) && sgm_fused_sweep_rows(s) == 3);
+    CHECK(sgm_set_batch(s, 2) && sgm_reset(s, 161, 20, &shifted) && sgm_match(s, img, img, out) && sgm_fused_sweep_rows(s) == 3);
+    CHECK(sgm_match(s, img, img, out) && sgm_fused_sweep_rows(s) == 0);        /* no Reset: the upward planes are re-created */
+    CHECK(sgm_reset(s, (uint16_t)W, (uint16_t)H, &o) && sgm_match(s, img, img, out) && sgm_fused_sweep_rows(s) == 3);
+    CHECK(sgm_set_batch(s, B + 1) && sgm_reset(s, (uint16_t)W, (uint16_t)H, &o));     /* grows: every buffer goes and comes back */
+    sgm_destroy(s);
+    free(img); free(out);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     if (argc > 1) return strcmp(argv[1], "both") == 0 ? both_family() : 2;
@@ -218,6 +242,7 @@ int main(int argc, char** argv)
             }
 
     CHECK(tiles_pipeline(img) == 0);
+    CHECK(reuse_sequence() == 0);
 
     free(img); free(out); free(buf); free(stage);
     printf("host_sanitize_driver ok\n");

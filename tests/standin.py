@@ -34,6 +34,7 @@ SIGNATURES = {
     "sgm_refine_disparity": (_b, [_p] * 4),
     "sgm_set_batch": (_b, [_p, _i]), "sgm_set_fill_holes": (_b, [_p, _i]), "sgm_set_overlap_post": (_b, [_p, _i]),
     "sgm_set_rows": (_b, [_p, _i, _i]), "sgm_set_reference_view": (None, [_p, _i]), "sgm_keep_stages": (None, [_p, _i]),
+    "sgm_set_honor_num_paths": (None, [_p, _i]),
     "sgm_fused_sweep_rows": (_i, [_p]), "sgm_read_stage": (_z, [_p, _i, _p, _z]),
     "stub_log_name": (C.c_char_p, [_i]), "stub_log_arg": (_i, [_i]), "stub_log_ptr": (_p, [_i, _i]), "stub_log_float": (_f, [_i]),
     "stub_fail_at": (None, [C.c_char_p, _i]), "stub_set_pinned": (None, [_i, _p]), "stub_toy_compute": (None, [_i]),

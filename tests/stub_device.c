@@ -133,7 +133,9 @@ int sgmd_d2d_2d_async(int o, void* st, void* d, size_t dp, const void* s, size_t
         for (size_t r = 0; r < rows; ++r) memmove((char*)d + r * dp, (const char*)s + r * sp, w);
     return note("d2d_2d", (int)(w * rows));
 }
-int sgmd_memset_async(int o, void* st, void* d, int v, size_t n) { (void)o; (void)st; if (n <= (1u << 20)) memset(d, v, n); return note("memset", (int)n); }
+/* (logged with its destination: the tests look for the fill that covers a given buffer) */
+int sgmd_memset_async(int o, void* st, void* d, int v, size_t n)
+{ (void)o; (void)st; if (n <= (1u << 20)) memset(d, v, n); return note_ptrs("memset", (int)n, d, NULL, 0.0f); }
 
 int sgmd_timer_create(int o, void** t, int n) { (void)o; (void)n; *t = malloc(8); return 0; }
 void sgmd_timer_destroy(int o, void* t) { (void)o; free(t); }
@@ -208,15 +210,18 @@ int sgmd_sum_wta_lr(int o, void* st, const sgmd_geom* g, int nd, const void* pl,
 { (void)o; (void)st; (void)ex; (void)re; (void)rc; (void)cap; (void)do_right; (void)S; (void)cu; (void)omr; (void)dr;
   if (g_toy) toy_sum(g, nd, pl, pb, dl);
   return note("sum_wta_lr", accumulate | (store_S << 1)); }
-/* the fused last sweep: logged with the rows per workgroup; the aggregation launch in front of it is logged by sgmd_aggregate */
+/* the fused last sweep (its shapes and scratch size are deliberately NOT those of csrc/sgm_upsum.hip -- no W >= 64, H >= 4, a flat
+ * 4096 bytes for the progress words and tickets: the tests check what the host does with whatever size the device reports):
+ * logged with the rows per workgroup, its scratch and (in the place of the second pointer) its generation;
+ * the aggregation launch in front of it is logged by sgmd_aggregate */
 int sgmd_upsum_rows(const sgmd_geom* g) { return (g->Dp == 128 && g->W > g->H && g->row_begin == 0 && g->row_end == g->H) ? 3 : 0; }
 size_t sgmd_upsum_scratch_bytes(const sgmd_geom* g) { return sgmd_upsum_rows(g) ? (size_t)g->B * 6 * g->W * g->Dp + 4096 : 0; }
 int sgmd_upsum(int o, void* st, const sgmd_geom* g, const sgmd_paths* p, const void* img, const void* cl, const void* cr, const void* lut,
                const void* pl, size_t pb, const void* ex, const void* re, const void* rc, int cap, int do_right, int cu, float omr,
                void* scratch, unsigned gen, void* status, int rows, int wgs, void* dl, void* dr)
 { (void)o; (void)st; (void)g; (void)p; (void)img; (void)cl; (void)cr; (void)lut; (void)pl; (void)pb; (void)ex; (void)re; (void)rc; (void)cap;
-  (void)do_right; (void)cu; (void)omr; (void)scratch; (void)gen; (void)status; (void)wgs; (void)dl; (void)dr;
-  return note("upsum", rows); }
+  (void)do_right; (void)cu; (void)omr; (void)status; (void)wgs; (void)dl; (void)dr;
+  return note_ptrs("upsum", rows, scratch, (const void*)(uintptr_t)gen, 0.0f); }
 int sgmd_wta_right(int o, void* st, const sgmd_geom* g, const void* S, int cu, float omr, void* dr)
 { (void)o; (void)st; (void)g; (void)S; (void)cu; (void)omr; (void)dr; return note("wta_right", 0); }
 int sgmd_lrcheck(int o, void* st, const sgmd_geom* g, void* dl, const void* dr, float th)

@@ -1,0 +1,247 @@
+"""What ONE instance of the C host (csrc/sgm_host.c) keeps across shapes, batches and options, on the stand-in device
+(tests/standin.py, tests/stub_device.c) -- no GPU.  The host's buffers only grow, some are zero-filled only when they are
+allocated, the path tables and the census block map are cached under a key: every one of these outlives a shape.  The stand-in's
+log records every fill with its destination and byte count and the fused last sweep with its scratch and generation, so what
+re-initialises a piece of retained state is checked deterministically here; tests/test_gpu_instance_reuse.py checks the results
+(NOTES.md section 20 has the table)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import standin
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    return standin.build(tmp_path_factory.mktemp("reusestub"))
+
+
+def option(d, dmin=0, **kw):
+    import soc_project_stereo_matching_amd as S
+    return S.default_option(d + dmin, dmin, **kw)
+
+
+def reset_and_match(L, s, w, h, opt, batch=1, reset=True):
+    """(log of the reset, log of the match) -- Entry lists; reset=False: the match alone"""
+    left = np.zeros((batch, h, w), np.uint8)
+    out = np.zeros((batch, h, w), np.float32)
+    L.stub_clear()
+    if reset:
+        assert L.sgm_reset(s, w, h, C.byref(opt))
+    at_reset = standin.log(L)
+    L.stub_clear()
+    assert L.sgm_match(s, left.ctypes.data, left.ctypes.data, out.ctypes.data)
+    return at_reset, standin.log(L)
+
+
+def names(entries, *keep):
+    return [(e.name, e.arg) for e in entries if not keep or e.name in keep]
+
+
+def stub_scratch_bytes(w, batch, dp=128):
+    return batch * 6 * w * dp + 4096                         # sgmd_upsum_scratch_bytes of tests/stub_device.c
+
+
+def fused(match_log):
+    """(the upsum entry, the fills of its scratch queued in front of it in this match)"""
+    ups = [e for e in match_log if e.name == "upsum"]
+    assert len(ups) == 1, names(match_log)
+    at = match_log.index(ups[0])
+    return ups[0], [e for e in match_log[:at] if e.name == "memset" and e.a == ups[0].a]
+
+
+@pytest.fixture
+def fused_instance(host, monkeypatch):
+    monkeypatch.setenv("SGM_UPSUM", "1")                      # read at sgm_create
+    s = host.sgm_create(0)
+    assert s and host.sgm_set_batch(s, 3)
+    yield s
+    host.sgm_destroy(s)
+
+
+def test_fused_sweep_scratch_is_zeroed_when_the_geometry_changes(host, fused_instance):
+    """The fused last sweep (SGM_UPSUM=1) keeps its progress words behind the hand-over rows of its scratch, at B * 6 * W * Dp: on a
+    smaller shape or batch they lie inside the earlier shape's hand-over rows, and a stale word whose top bit is clear reads as
+    "ahead" of the launch's generation.  Every fused launch whose (B, W, H, Dp, rows per workgroup) differ from the one before has
+    a zero-fill covering the whole scratch of ITS geometry queued in front of it, and runs as generation 1 (a zero word is
+    "behind" only while generation << 13 is below 2^31)."""
+    L, s = host, fused_instance
+    steps = [(300, 40, 0, 3), (161, 20, 0, 3), (161, 20, 0, 2), (300, 40, 0, 2), (300, 39, 0, 2), (300, 39, 3, 2)]
+    scratch = None
+    for k, (w, h, dmin, batch) in enumerate(steps):
+        assert L.sgm_set_batch(s, batch)
+        at_reset, at_match = reset_and_match(L, s, w, h, option(128, dmin), batch)
+        assert L.sgm_fused_sweep_rows(s) == 3, steps[k]
+        up, fills = fused(at_match)
+        changed = k == 0 or steps[k][:2] + steps[k][3:] != steps[k - 1][:2] + steps[k - 1][3:]
+        if changed:
+            assert [e.arg for e in fills] == [stub_scratch_bytes(w, batch)], (steps[k], names(at_match))
+            assert (up.b or 0) == 1, (steps[k], up)
+        else:                                                 # dmin alone: the same words at the same places
+            assert fills == [] and (up.b or 0) == 2, (steps[k], up)
+        if k == 0:
+            scratch = up.a
+        else:                                                 # never larger than the first: the buffer is the first one
+            assert up.a == scratch and "alloc" not in [e.name for e in at_reset + at_match], steps[k]
+
+
+def test_fused_sweep_unchanged_geometry_adds_nothing(host, fused_instance):
+    """Reset + Match at an unchanged geometry: no fill of the scratch (nor any other), the generation counts on, and the device
+    calls of every such match are the same list.  With an unchanged geometry launch g leaves every progress word at
+    (g << 13) + n, n < 2^13, and launch g + 1 compares against ((g + 1) << 13) + c: behind for every g, the 19-bit wrap included
+    (csrc/sgm_host.c, ensure_upsum)."""
+    L, s = host, fused_instance
+    opt = option(128)
+    _, first = reset_and_match(L, s, 300, 40, opt, 3)
+    assert (fused(first)[0].b or 0) == 1 and len(fused(first)[1]) == 1
+    later = []
+    for gen in (2, 3, 4):
+        at_reset, at_match = reset_and_match(L, s, 300, 40, opt, 3)
+        up, fills = fused(at_match)
+        assert fills == [] and (up.b or 0) == gen
+        assert "memset" not in [e.name for e in at_reset + at_match]
+        later.append(names(at_match))
+    assert later[0] == later[1] == later[2]
+    assert [n for n, _ in later[0] if n not in ("sync", "h2d", "d2h")] == ["census", "d2d", "aggregate", "upsum", "lrcheck", "speckle", "median"]
+    # a Match without Reset in between runs the separate kernels and is no fused launch: the count goes on where it was
+    _, q14 = reset_and_match(L, s, 300, 40, opt, 3, reset=False)
+    assert "upsum" not in [e.name for e in q14]
+    _, again = reset_and_match(L, s, 300, 40, opt, 3)
+    assert fused(again)[1] == [] and (fused(again)[0].b or 0) == 5
+
+
+def test_fused_sweep_scratch_after_the_buffers_were_lost(host, fused_instance):
+    """A batch that grows frees every buffer of the instance (ensure_buffers): the scratch comes back through one allocation and
+    ONE fill, and the generation starts over although the shape is the one before."""
+    L, s = host, fused_instance
+    opt = option(128)
+    for _ in range(3):
+        reset_and_match(L, s, 200, 30, opt, 3)
+    assert L.sgm_set_batch(s, 4)
+    _, at_match = reset_and_match(L, s, 200, 30, opt, 4)
+    up, fills = fused(at_match)
+    assert [e.arg for e in fills] == [stub_scratch_bytes(200, 4)] and (up.b or 0) == 1
+    assert len([e for e in at_match if e.name == "memset"]) == 1
+
+
+def test_the_timed_configuration_has_no_fill_per_match(host):
+    """Batches of 8 KITTI frames on the default kernels (what bench.py times): no fill in a Reset + Match once the instance is
+    warm; the launches are the same list every time."""
+    L = host
+    s = L.sgm_create(0)
+    assert s and L.sgm_set_batch(s, 8)
+    opt = option(128)
+    seen = []
+    for _ in range(3):
+        at_reset, at_match = reset_and_match(L, s, 1242, 375, opt, 8)
+        seen.append(names(at_reset + at_match))
+    L.sgm_destroy(s)
+    assert seen[1] == seen[2] and "memset" not in [n for n, _ in seen[1]] and "alloc" not in [n for n, _ in seen[1]]
+    # (the 14.9 MB result goes back in pieces with an event behind each: csrc/sgm_host.c, RESULT_CHUNKS)
+    kernels = [n for n, _ in seen[1] if n not in ("sync", "h2d", "d2h", "event_record", "event_sync")]
+    assert kernels == ["census", "aggregate", "sum_wta_lr", "lrcheck", "speckle", "median"]
+
+
+def test_a_shrink_allocates_nothing(host):
+    L = host
+    s = L.sgm_create(0)
+    assert s and L.sgm_set_batch(s, 3)
+    reset_and_match(L, s, 96, 64, option(64), 3)
+    # (the tall one small enough for the stand-in's allocator, which backs at most 1 MiB and runs the plane fills for real)
+    for (w, h, d, dmin, batch) in ((48, 20, 16, 0, 3), (20, 44, 16, 3, 2), (5, 9, 8, 0, 1), (96, 64, 64, 0, 3)):
+        assert L.sgm_set_batch(s, batch)
+        at_reset, at_match = reset_and_match(L, s, w, h, option(d, dmin), batch)
+        assert "alloc" not in [e.name for e in at_reset + at_match], (w, h, d, batch)
+    L.sgm_destroy(s)
+
+
+@pytest.mark.parametrize("fused_wta", ["1", "0"])
+def test_S_of_the_larger_shape_never_reaches_a_sum_after_a_shrink(host, monkeypatch, fused_wta):
+    """d_S is kept across a shrink, full of the larger shape's sums, and is cleared lazily (s_is_zero).  The first sum after the
+    Reset that writes d_S must REPLACE: with the fused kernel that is the sum a Match without Reset puts together first
+    (sgmd_sum_wta, accumulate 0) ahead of its own accumulating one; with the separate kernels it is the first match's own."""
+    monkeypatch.setenv("SGM_FUSED_WTA", fused_wta)
+    L = host
+    s = L.sgm_create(0)
+    assert s
+    big = option(64)
+    _, first = reset_and_match(L, s, 96, 64, big)
+    _, second = reset_and_match(L, s, 96, 64, big, reset=False)          # d_S exists from here on, holding two frames' sums
+    # (the separate kernels write S in the first match already, the fused one only when a second match asks for it)
+    assert ("alloc" in [e.name for e in first], "alloc" in [e.name for e in second]) == ((False, True) if fused_wta == "1" else (True, False))
+    small = option(16)
+    at_reset, first = reset_and_match(L, s, 48, 20, small)
+    _, second = reset_and_match(L, s, 48, 20, small, reset=False)
+    assert "alloc" not in [e.name for e in at_reset + first + second]
+    sums_first = names(first, "sum_wta", "sum_wta_lr")
+    sums_second = names(second, "sum_wta", "sum_wta_lr")
+    if fused_wta == "1":
+        assert sums_first == [("sum_wta_lr", 0)]                          # accumulate 0, S not stored
+        assert sums_second == [("sum_wta", 0), ("sum_wta_lr", 1)]         # S <- the first frame's sum; then this frame's is added
+    else:
+        assert sums_first == [("sum_wta", 0)] and sums_second == [("sum_wta", 1)]
+    L.sgm_destroy(s)
+
+
+def test_path_tables_are_uploaded_again_exactly_when_their_inputs_change(host):
+    """upload_tables reads W, H, the number of directions, the anomalous lines (a function of W and the direction) and P1 / P2 (the
+    penalty table), and nothing else: neither the disparity range nor min_disparity enters the row tables or the penalty table,
+    and row_cap is derived from the same inputs.  So the cache key (W, H, ndirs, p1, p2) is complete: a Reset that changes only D
+    or dmin rightly uploads nothing, one that changes any of the five uploads all three tables again."""
+    L = host
+    s = L.sgm_create(0)
+    assert s
+    L.sgm_set_honor_num_paths(s, 1)
+
+    def uploads(w, h, d, dmin=0, **kw):
+        opt = option(d, dmin, **kw)
+        L.stub_clear()
+        assert L.sgm_reset(s, w, h, C.byref(opt))
+        return len([e for e in standin.log(L) if e.name == "h2d"])
+
+    assert uploads(96, 64, 64) == 3
+    assert uploads(96, 64, 64) == 0
+    assert uploads(96, 64, 32) == 0                           # D alone
+    assert uploads(96, 64, 32, dmin=3) == 0                   # dmin alone
+    assert uploads(96, 64, 128, dmin=1) == 0                  # both, another Dp
+    assert uploads(95, 64, 64) == 3                           # W
+    assert uploads(95, 63, 64) == 3                           # H
+    assert uploads(63, 95, 64) == 3                           # both swapped: the same pixel count
+    assert uploads(63, 95, 64, p1=11) == 3
+    assert uploads(63, 95, 64, p1=11, p2_init=151) == 3
+    assert uploads(63, 95, 64, p1=11, p2_init=151, num_paths=4) == 3
+    assert uploads(63, 95, 64, p1=11, p2_init=151, num_paths=4) == 0
+    assert uploads(63, 95, 64, p1=11, p2_init=151) == 3
+    # a grown batch loses every buffer, the tables with them
+    assert L.sgm_set_batch(s, 2)
+    assert uploads(63, 95, 64, p1=11, p2_init=151) == 3
+    L.sgm_destroy(s)
+
+
+def test_census_block_map_follows_its_key(host):
+    """Row tiles: the census block map is rebuilt when W, H, the rows, dmin, Dp or the number of directions change, and only then."""
+    L = host
+    s = L.sgm_create(0)
+    assert s
+    L.sgm_set_honor_num_paths(s, 1)
+
+    def uploads(w, h, rows, d, dmin=0, **kw):
+        opt = option(d, dmin, **kw)
+        assert L.sgm_set_rows(s, *rows)
+        L.stub_clear()
+        assert L.sgm_reset(s, w, h, C.byref(opt))
+        return len([e for e in standin.log(L) if e.name == "h2d"])
+
+    tables, the_map = 3, 1
+    assert uploads(96, 64, (0, 32), 64) == tables + the_map
+    assert uploads(96, 64, (0, 32), 64) == 0
+    assert uploads(96, 64, (32, 64), 64) == the_map           # the bottom tile
+    assert uploads(130, 64, (32, 64), 64) == tables + the_map  # W alone
+    assert uploads(130, 64, (32, 64), 64, dmin=3) == the_map
+    assert uploads(130, 64, (32, 64), 128, dmin=3) == the_map  # Dp
+    assert uploads(130, 64, (32, 64), 128, dmin=3, num_paths=4) == tables + the_map
+    assert uploads(130, 64, (32, 64), 128, dmin=3, num_paths=4) == 0
+    assert uploads(130, 64, (0, 0), 128, dmin=3, num_paths=4) == 0          # whole frames again: no map needed
+    assert uploads(130, 64, (32, 64), 128, dmin=3, num_paths=4) == 0        # ... and the one on the device is still that tile's
+    L.sgm_destroy(s)
