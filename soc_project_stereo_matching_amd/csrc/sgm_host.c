@@ -40,6 +40,14 @@ static const int k_dir_dy[8] = {0, 0, 1, -1, 1, -1, -1, 1};
 typedef struct { void* p; size_t cap; } sgm_buf;
 typedef struct { void* dst; const void* src; size_t bytes; } handover;     /* a staged output on its way to the caller (sgm_match_wait) */
 
+/* Where S lives, the aggregated-cost sum of the matches since the last Reset (quirk Q14: a Match without Reset adds to it).  The
+ * fused kernels do not store it: it stays spread over the direction planes of the last frame until somebody needs it (a Match
+ * without Reset, a stage read) and then replaces what d_S holds (the first match behind a Reset) or adds to it; behind a fused last
+ * sweep the three upward planes of that frame are missing as well.  Three writers: sum_reset (Initialize / Reset), sum_accepted (a
+ * cost-sum launch was accepted: exactly then, so a refused launch leaves the matches that completed described) and materialize_S. */
+typedef enum { S_ZERO, S_STORED, S_IN_PLANES, S_IN_PLANES_ADDS } sum_where;
+typedef struct { sum_where where; bool up_missing; } sum_state;
+
 /* refinement parameters (sgm_set_refine) and the weight tables L_t of their iterations */
 typedef struct {
     float lambda, sigma;
@@ -66,7 +74,6 @@ struct sgm_instance {
     int up_key[5];               /* B, W, H, Dp, rows per workgroup of the fused launches the scratch's progress words belong to
                                     ([0] == 0: none, the scratch is to be zeroed): ensure_upsum */
     int last_up_rows;            /* rows per workgroup of the fused sweep in the LAST match, 0 if it ran the separate kernels */
-    bool planes_partial;         /* the planes of the last frame lack the upward directions: materialize_S re-creates them first */
     int env_upsum, env_upsum_rows, env_upsum_wgs;   /* SGM_UPSUM, SGM_UPSUM_ROWS, SGM_UPSUM_WGS */
     int env_lanes, env_hl, env_agg_fast, env_fused;   /* SGM_LANES_PER_PIXEL, SGM_HL, SGM_AGG_FAST, SGM_FUSED_WTA as read at sgm_create
                                     (-1: not set) -- tuning / test knobs, not looked up again on the per-frame sgm_reset path */
@@ -93,11 +100,8 @@ struct sgm_instance {
     const void* tile_left;       /* left image of the frame a tile sequence is working on */
 
     bool initialized;
-    bool s_is_zero;              /* aggregated-cost volume logically zero (set by Initialize/Reset, Q14) */
+    sum_state S;                 /* the aggregated-cost volume: logically zero, in d_S, or still in the planes (Q14) */
     int fused_wta;               /* Dp <= 256: cost sum and both WTA passes in one kernel, S not written */
-    bool s_pending;              /* the planes hold a frame whose sum has not been put into d_S (fused kernel, S not
-                                    stored): done lazily when somebody needs S -- a Match without Reset, a stage read */
-    bool s_pending_accumulate;   /* ... and that sum adds to d_S (true) or replaces it */
     SGMOption opt;
     sgmd_geom g;
     sgmd_paths paths;
@@ -195,6 +199,14 @@ static bool row_tiled(const sgm_instance* s) { return s->tile_end != 0; }
 static bool census_symmetric(const sgm_instance* s) { return s->census_kind == SGM_CENSUS_SYMMETRIC; }
 static bool reference_census(const sgm_instance* s) { return !s->census_w && !census_symmetric(s); }
 static bool volume_fed(const sgm_instance* s) { return s->census_w && !census_symmetric(s); }
+
+static void sum_reset(sgm_instance* s) { s->S = (sum_state){S_ZERO, false}; }
+static void sum_accepted(sgm_instance* s, sum_where where, bool up_missing) { s->S = (sum_state){where, up_missing}; }
+
+/* pixels of one frame and of the batch a match works on (frame-major); maps are f32, images u8 */
+static size_t frame_px(const sgm_instance* s) { return (size_t)s->g.W * s->g.H; }
+static size_t batch_px(const sgm_instance* s) { return (size_t)s->g.B * frame_px(s); }
+static size_t map_bytes(const sgm_instance* s) { return batch_px(s) * sizeof(float); }
 
 /* wait for everything the instance has queued (its stream and, with sgm_set_overlap_post, the post-pass stream) */
 static int sync_streams(sgm_instance* s)
@@ -647,7 +659,7 @@ bool sgm_set_rectify(sgm_instance* s, int width, int height, const float* map_lx
 /* the maps on the device and the two rectified images, beside upload_tables: a Reset with unchanged maps uploads nothing */
 static bool upload_rectify(sgm_instance* s)
 {
-    const size_t px = (size_t)s->g.B * s->g.W * s->g.H;
+    const size_t px = batch_px(s);
     const size_t bytes = 4 * SGMD_REMAP_PITCH((size_t)s->rect_w * s->rect_h) * sizeof(int32_t);
     const buf_request bufs[] = {{&s->d_rect_maps, bytes, 0}, {&s->d_rect_l, px, 0}, {&s->d_rect_r, px, 0}};
     if (!reserve_all(s, bufs, 3, 0)) FAIL("device allocation failed for the rectification of %dx%d", s->g.W, s->g.H);
@@ -812,7 +824,7 @@ static bool upload_tables(sgm_instance* s)
 static bool ensure_buffers(sgm_instance* s)
 {
     const int dev = s->device;
-    const size_t px = (size_t)s->g.B * s->g.W * s->g.H;          /* all frames of the batch, frame-major */
+    const size_t px = batch_px(s);          /* all frames of the batch, frame-major */
     if (!buf_holds(&s->d_disp, px * 4)) {
         /* the per-pixel set grows: everything the instance owns goes (the buffers sized below and in sgm_initialize come back at
          * once, S, the cost volume and the others on their first use).
@@ -863,7 +875,7 @@ static bool ensure_buffers(sgm_instance* s)
  * separate sum / right-view kernels (D > 256, SGM_FUSED_WTA=0), sgm_keep_stages, a stage read-back. */
 static int ensure_S(sgm_instance* s)
 {
-    const size_t need = (size_t)s->g.B * s->g.W * s->g.H * s->g.Dp * 2;
+    const size_t need = batch_px(s) * s->g.Dp * 2;
     if (buf_holds(&s->d_S, need)) return 0;
     if (reserve(s, &s->d_S, need, BUF_ZERO) &&
         (!s->sum_stream || sgmd_stream_sync(s->device, s->stream) == 0))   /* the cost sum may run on another stream */
@@ -874,7 +886,7 @@ static int ensure_S(sgm_instance* s)
 
 static int ensure_cost(sgm_instance* s)
 {
-    const size_t need = (size_t)s->g.B * s->g.W * s->g.H * s->g.Dp;
+    const size_t need = batch_px(s) * s->g.Dp;
     if (reserve(s, &s->d_cost, need, 0)) return 0;
     fprintf(stderr, "sgm_mi355x: device allocation failed for the cost volume (%zu bytes)\n", need);
     return -1;
@@ -883,7 +895,7 @@ static int ensure_cost(sgm_instance* s)
 /* the class map and the ping-pong map of the hole filling, [B][H][W] each */
 static int ensure_fill(sgm_instance* s)
 {
-    const size_t px = (size_t)s->g.B * s->g.W * s->g.H;
+    const size_t px = batch_px(s);
     const buf_request maps[] = {{&s->d_fill_class, px, 0}, {&s->d_fill_map, px * sizeof(float), 0}};
     if (reserve_all(s, maps, 2, 0)) return 0;
     fprintf(stderr, "sgm_mi355x: device allocation failed for the hole-filling maps (%zu pixels)\n", px);
@@ -893,7 +905,7 @@ static int ensure_fill(sgm_instance* s)
 /* the maps of the refinement, [B][H][W] each: U, V, Q (f32), the internal confidence (u16), two guide copies (u8) */
 static int ensure_refine(sgm_instance* s)
 {
-    const size_t px = (size_t)s->g.B * s->g.W * s->g.H;
+    const size_t px = batch_px(s);
     const buf_request maps[] = {{&s->d_rf_u, px * 4, 0}, {&s->d_rf_v, px * 4, 0}, {&s->d_rf_q, px * 4, 0}, {&s->d_rf_conf, px * 2, 0},
                                 {&s->d_rf_guide[0], px, 0}, {&s->d_rf_guide[1], px, 0}};
     if (reserve_all(s, maps, 6, 0)) return 0;
@@ -920,14 +932,13 @@ static int refine_passes(sgm_instance* s, void* st, void* disp, const void* conf
 static int fill_passes(sgm_instance* s, void* st, void* disp, const void* cls)
 {
     const int R = s->opt.max_disparity;
-    const size_t bytes = (size_t)s->g.B * s->g.W * s->g.H * sizeof(float);
     int rc = 0;
     if (cls) {
         rc = sgmd_fill_pass(s->device, st, &s->g, R, disp, s->d_fill_map.p, cls, 1);                  /* occluded */
         if (rc == 0) rc = sgmd_fill_pass(s->device, st, &s->g, R, s->d_fill_map.p, disp, cls, 2);     /* mismatched */
     }
     if (rc == 0) rc = sgmd_fill_pass(s->device, st, &s->g, R, disp, s->d_fill_map.p, NULL, 3);        /* every hole left */
-    if (rc == 0) rc = sgmd_d2d_async(s->device, st, disp, s->d_fill_map.p, bytes);
+    if (rc == 0) rc = sgmd_d2d_async(s->device, st, disp, s->d_fill_map.p, map_bytes(s));
     return rc;
 }
 
@@ -1050,8 +1061,7 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
 
     if (row_tiled(s) && !volume_fed(s) && !upload_census_need(s)) return false;
 
-    s->s_is_zero = true;                                         /* .c:57: memset of cost_aggr, done lazily */
-    s->s_pending = false;
+    sum_reset(s);                                                /* .c:57: memset of cost_aggr, done lazily */
     {
         /* one workgroup per image row segment (the launcher cuts rows into up to 4 segments when a launch has few rows);
          * at KITTI size: a batch of 8 frames 0.093 ms per frame against 0.115 + 0.043 for the two separate kernels, a
@@ -1063,7 +1073,6 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
      * has the shapes: W > H, Dp = 128).  SGM_UPSUM=0 / 1 forces it off / on (also for one frame per launch, where its row-to-row chain
      * costs latency) */
     s->up_rows = 0;
-    s->planes_partial = false;
     if (s->fused_wta && !row_tiled(s) && reference_census(s) && s->paths.ndirs == 8 && option->p1 >= 0 && s->row_cap <= 8 &&
         (s->env_upsum >= 0 ? s->env_upsum != 0 : UPSUM_DEFAULT && s->batch >= 2))
         s->up_rows = sgmd_upsum_rows(&s->g);
@@ -1110,13 +1119,13 @@ static int sweep_mask(const sgm_instance* s, int forward)
 /* d_S <- [d_S +] sum of the planes of the last frame, if the fused kernel skipped that store */
 static int materialize_S(sgm_instance* s)
 {
-    if (!s->s_pending) return 0;
+    if (s->S.where != S_IN_PLANES && s->S.where != S_IN_PLANES_ADDS) return 0;
     if (ensure_S(s) != 0) return -1;
     /* d_S may still be in use by a cost sum on its own stream; the scratch map below is the speckle pass's label map: a post
      * pass still running on its own stream comes first */
     if (s->sum_pending && sgmd_stream_wait_event(s->device, s->stream, s->ev_sum) != 0) return -1;
     if (s->post_pending && sgmd_stream_wait_event(s->device, s->stream, s->ev_post) != 0) return -1;
-    if (s->planes_partial) {
+    if (s->S.up_missing) {
         /* the last match ran the fused sweep: the three upward planes do not exist.  Walk those directions now (the census images
          * and the kept copy of the left image are still that frame's; the anomalous lines and their cells were done then) */
         sgmd_paths p = s->paths;
@@ -1124,30 +1133,65 @@ static int materialize_S(sgm_instance* s)
         p.run_anom = 0;
         p.up_fused = 0;
         if (launch_aggregation(s, &p, s->d_left_keep.p) != 0) return -1;
-        s->planes_partial = false;
+        s->S.up_missing = false;
     }
     /* the left-view WTA this kernel also produces goes to a dead scratch map (speckle labels) */
     const int rc = sgmd_sum_wta(s->device, s->stream, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras.p,
-                                s->d_row_extras.p, s->d_row_count.p, s->row_cap, s->s_pending_accumulate ? 1 : 0, s->d_S.p, 0, 0.0f,
+                                s->d_row_extras.p, s->d_row_count.p, s->row_cap, s->S.where == S_IN_PLANES_ADDS ? 1 : 0, s->d_S.p, 0, 0.0f,
                                 s->d_labels.p);
-    if (rc == 0) s->s_pending = false;                           /* a failed launch leaves the sum pending */
+    if (rc == 0) s->S.where = S_STORED;                          /* a failed launch leaves the sum in the planes */
     return rc;
 }
 
-/* .c:94 (sum over the directions), .c:99 and .c:105 (both ComputeDisparity calls); conf: where the reference view's matching
- * confidence goes (extension), NULL: nowhere.  The Q14 bookkeeping (s_is_zero,
- * s_pending) changes only when every launch of the stage was accepted. */
-static int sum_and_wta(sgm_instance* s, void* st, void* d_out, void* conf, bool with_marks, bool both)
+/* Scratch of the fused last sweep and the kept left image.  The kernel's progress words sit BEHIND the hand-over rows, at an
+ * offset that depends on (B, W, Dp); their number on H and the rows per workgroup (sgm_upsum.hip).  A word carries
+ * (generation << 13) + iterations published, the generation being the low 19 bits of up_gen, and a waiting row group compares
+ * (int)(word - want) < 0.
+ *   Unchanged geometry: launch g leaves every word at (g << 13) + n, n < 2^13 (each row group's helper stores its final count before
+ *   it draws the next ticket), and launch g + 1 asks for ((g + 1) << 13) + c with 1 <= c < 2^13.  The difference is n - c - 2^13 in
+ *   [-2^14, 0) modulo 2^32 whatever g is, the wrap of the 19 bits to 0 included: "behind", as it must be.  Nothing to do.
+ *   (A launch that is refused after the counter went up skips a generation: the difference is then within -2^15, behind as well.)
+ *   Changed geometry (or a scratch that is new): the words' places hold hand-over bytes of the earlier shape, or the words of a
+ *   generation far back.  The scratch is zero-filled on s->stream in front of the launch (behind every earlier fused launch: the
+ *   stream has waited for ev_sum, or the launch ran on it) and the counter starts over: a zero word is "behind" want only while
+ *   generation << 13 stays below 2^31, which a restart at 1 guarantees and a zero-fill alone would not from launch 2^18 on.
+ * The one zero-fill of a first launch is the one the allocation always had; an unchanged geometry adds none. */
+static int ensure_upsum(sgm_instance* s)
+{
+    const size_t px = batch_px(s), bytes = sgmd_upsum_scratch_bytes(&s->g);
+    const int key[5] = {s->g.B, s->g.W, s->g.H, s->g.Dp, s->up_rows};
+    if (!buf_holds(&s->d_up_scratch, bytes)) s->up_key[0] = 0;
+    if (!reserve(s, &s->d_up_scratch, bytes, 0)) return -1;
+    if (memcmp(key, s->up_key, sizeof key) != 0) {
+        s->up_key[0] = 0;                                        /* (B >= 1: 0 = no key) a fill that fails leaves none behind */
+        if (sgmd_memset_async(s->device, s->stream, s->d_up_scratch.p, 0, bytes) != 0) return -1;
+        memcpy(s->up_key, key, sizeof key);
+        s->up_gen = 0;
+    }
+    return reserve(s, &s->d_left_keep, px, 0) ? 0 : -1;
+}
+
+/* .c:94 (sum over the directions), .c:99 and .c:105 (both ComputeDisparity calls) by one of three routes: fused with the last vertical
+ * sweep (sweep: the aggregation in front ran with up_fused, behind ensure_upsum), the fused cost sum, or the separate kernels.
+ * conf: where the reference view's matching confidence goes (extension), NULL: nowhere. */
+static int cost_sum_stage(sgm_instance* s, void* st, void* d_out, void* conf, bool with_marks, bool both, bool sweep)
 {
     const SGMOption* o = &s->opt;
-    const int accumulate = s->s_is_zero ? 0 : 1;                 /* Q14 */
+    const int accumulate = s->S.where == S_ZERO ? 0 : 1;         /* Q14 (materialize_S came first: zero or in d_S) */
+    const int store = s->keep_stages ? 1 : 0;                    /* the fused cost sum writes S only for a test */
     const int uniq = o->is_check_unique ? 1 : 0;
     const float keep = 1 - o->uniqueness_ratio;
-    int rc;
     const bool want_right = both || o->is_check_lr || s->reference_view;    /* both: sgm_match_both finishes the right map as well */
-    if ((!s->fused_wta || accumulate || s->keep_stages) && ensure_S(s) != 0) return -1;
-    if (s->fused_wta) {
-        const int store = s->keep_stages ? 1 : 0;
+    const bool separate = !s->fused_wta;
+    sum_where then = S_STORED;                                   /* where S is once the launch below was accepted */
+    int rc;
+    if ((separate || accumulate || store) && ensure_S(s) != 0) return -1;    /* (never the sweep: S zero, nothing kept) */
+    if (sweep) {
+        rc = sgmd_upsum(s->device, st, &s->g, &s->paths, s->d_left_keep.p, s->d_census_l.p, s->d_census_r, s->d_lut.p, s->d_planes, s->plane_bytes,
+                        s->d_extras.p, s->d_row_extras.p, s->d_row_count.p, s->row_cap, want_right ? 1 : 0, uniq, keep, s->d_up_scratch.p,
+                        ++s->up_gen, s->h_status, s->up_rows, s->env_upsum_wgs > 0 ? s->env_upsum_wgs : 0, d_out, s->d_disp_r.p);
+        then = S_IN_PLANES;                                      /* five planes + the three materialize_S re-creates */
+    } else if (!separate) {
         if (conf)
             rc = sgmd_sum_wta_lr_conf(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras.p, s->d_row_extras.p,
                                       s->d_row_count.p, s->row_cap, accumulate, store, want_right ? 1 : 0, s->d_S.p, uniq, keep, d_out,
@@ -1156,28 +1200,19 @@ static int sum_and_wta(sgm_instance* s, void* st, void* d_out, void* conf, bool 
             rc = sgmd_sum_wta_lr(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras.p,
                                  s->d_row_extras.p, s->d_row_count.p, s->row_cap, accumulate, store, want_right ? 1 : 0, s->d_S.p,
                                  uniq, keep, d_out, s->d_disp_r.p);
-        if (rc != 0) return rc;
-        s->s_pending = !store;
-        s->s_pending_accumulate = accumulate != 0;
-        if (with_marks) mark_on(s, st, T_WTA);
-    } else {
-        if (conf && !s->reference_view)
-            rc = sgmd_sum_wta_conf(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras.p,
-                                   s->d_row_extras.p, s->d_row_count.p, s->row_cap, accumulate, s->d_S.p, uniq, keep, d_out, conf);
-        else
-            rc = sgmd_sum_wta(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras.p,
-                              s->d_row_extras.p, s->d_row_count.p, s->row_cap, accumulate, s->d_S.p, uniq, keep, d_out);
-        if (rc != 0) return rc;
-        /* d_S now holds this frame's sum whatever happens next */
-        s->s_pending = false;
-        s->s_is_zero = false;
-        if (with_marks) mark_on(s, st, T_WTA);
-        if (conf && s->reference_view) rc = sgmd_wta_right_conf(s->device, st, &s->g, s->d_S.p, uniq, keep, s->d_disp_r.p, conf);
-        else if (want_right) rc = sgmd_wta_right(s->device, st, &s->g, s->d_S.p, uniq, keep, s->d_disp_r.p);
-        if (rc != 0) return rc;
-    }
-    s->s_is_zero = false;
-    return 0;
+        if (!store) then = accumulate ? S_IN_PLANES_ADDS : S_IN_PLANES;
+    } else if (conf && !s->reference_view)
+        rc = sgmd_sum_wta_conf(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras.p,
+                               s->d_row_extras.p, s->d_row_count.p, s->row_cap, accumulate, s->d_S.p, uniq, keep, d_out, conf);
+    else
+        rc = sgmd_sum_wta(s->device, st, &s->g, s->paths.ndirs, s->d_planes, s->plane_bytes, s->d_extras.p,
+                          s->d_row_extras.p, s->d_row_count.p, s->row_cap, accumulate, s->d_S.p, uniq, keep, d_out);
+    if (rc != 0) return rc;
+    sum_accepted(s, then, sweep);                                /* the state holds whatever happens next: the right view below */
+    if (with_marks) mark_on(s, st, T_WTA);
+    if (separate && conf && s->reference_view) rc = sgmd_wta_right_conf(s->device, st, &s->g, s->d_S.p, uniq, keep, s->d_disp_r.p, conf);
+    else if (separate && want_right) rc = sgmd_wta_right(s->device, st, &s->g, s->d_S.p, uniq, keep, s->d_disp_r.p);
+    return rc;
 }
 
 /* .c:82-83 (+ .c:89 for the wide centre windows, whose cost is materialised): census of both images */
@@ -1186,7 +1221,7 @@ static int prepare_costs(sgm_instance* s, const void* d_left, const void* d_righ
     if (!volume_fed(s)) {
         const bool tiled = row_tiled(s) && !s->keep_stages;          /* stage read-back wants the whole census */
         if (tiled && getenv("SGM_DEBUG_POISON_CENSUS")) {                /* tests: a read of a skipped block must not go unnoticed */
-            const size_t bytes = (size_t)s->g.B * s->g.W * s->g.H * 4;
+            const size_t bytes = batch_px(s) * 4;
             if (sgmd_memset_async(s->device, s->stream, s->d_census_l.p, 0xA5, bytes) != 0 ||
                 sgmd_memset_async(s->device, s->stream, s->d_census_r, 0x5A, bytes) != 0) return -1;
         }
@@ -1198,7 +1233,7 @@ static int prepare_costs(sgm_instance* s, const void* d_left, const void* d_righ
         const int keep_border = s->reference_statics && s->g.B == 1 && !row_tiled(s);
         return sgmd_census(s->device, s->stream, &s->g, d_left, d_right, s->d_census_l.p, s->d_census_r, need, keep_border);
     }
-    const size_t need = (size_t)s->g.B * s->g.W * s->g.H * 8;
+    const size_t need = batch_px(s) * 8;
     const buf_request words[] = {{&s->d_census64_l, need, 0}, {&s->d_census64_r, need, 0}};
     if (!reserve_all(s, words, 2, 0)) return -1;
     int rc = ensure_cost(s);
@@ -1216,7 +1251,7 @@ static int lr_stage(sgm_instance* s, void* st, void* d_out)
     if (!s->reference_view) return o->is_check_lr ? sgmd_lrcheck(s->device, st, &s->g, d_out, s->d_disp_r.p, o->lrcheck_thres) : 0;
     /* the rows this instance computes: all rows of all frames of the batch, or its row tile of each of them */
     int rc = sgmd_lrcheck_right(s->device, st, &s->g, s->d_disp_r.p, d_out, o->lrcheck_thres, o->is_check_lr ? 1 : 0, s->d_labels.p);
-    const size_t frame = (size_t)s->g.W * s->g.H * sizeof(float), first = (size_t)s->g.row_begin * s->g.W * sizeof(float);
+    const size_t frame = frame_px(s) * sizeof(float), first = (size_t)s->g.row_begin * s->g.W * sizeof(float);
     const size_t rows = (size_t)(s->g.row_end - s->g.row_begin) * s->g.W * sizeof(float);
     if (rows == frame)                                        /* d_labels: scratch until the speckle pass */
         return rc ? rc : sgmd_d2d_async(s->device, st, d_out, s->d_labels.p, frame * s->g.B);
@@ -1225,45 +1260,12 @@ static int lr_stage(sgm_instance* s, void* st, void* d_out)
     return rc;
 }
 
-/* The body of SGM_Match (SemiGlobalMatching.c:80-122) on device buffers.  The first launch that is refused ends the
- * match: nothing further is queued and false is returned with the instance in a consistent state -- d_S (or the
- * pending planes) still describe exactly the matches that completed, so a later Match without Reset (Q14) accumulates
- * onto the right thing. */
-#define LAUNCH(expr) do { if ((expr) != 0) goto failed; } while (0)
-/* Scratch of the fused last sweep and the kept left image.  The kernel's progress words sit BEHIND the hand-over rows, at an
- * offset that depends on (B, W, Dp); their number on H and the rows per workgroup (sgm_upsum.hip).  A word carries
- * (generation << 13) + iterations published, the generation being the low 19 bits of up_gen, and a waiting row group compares
- * (int)(word - want) < 0.
- *   Unchanged geometry: launch g leaves every word at (g << 13) + n, n < 2^13 (each row group's helper stores its final count before
- *   it draws the next ticket), and launch g + 1 asks for ((g + 1) << 13) + c with 1 <= c < 2^13.  The difference is n - c - 2^13 in
- *   [-2^14, 0) modulo 2^32 whatever g is, the wrap of the 19 bits to 0 included: "behind", as it must be.  Nothing to do.
- *   (A launch that is refused after the counter went up skips a generation: the difference is then within -2^15, behind as well.)
- *   Changed geometry (or a scratch that is new): the words' places hold hand-over bytes of the earlier shape, or the words of a
- *   generation far back.  The scratch is zero-filled on s->stream in front of the launch (behind every earlier fused launch: the
- *   stream has waited for ev_sum, or the launch ran on it) and the counter starts over: a zero word is "behind" want only while
- *   generation << 13 stays below 2^31, which a restart at 1 guarantees and a zero-fill alone would not from launch 2^18 on.
- * The one zero-fill of a first launch is the one the allocation always had; an unchanged geometry adds none. */
-static int ensure_upsum(sgm_instance* s)
-{
-    const size_t px = (size_t)s->g.B * s->g.W * s->g.H, bytes = sgmd_upsum_scratch_bytes(&s->g);
-    const int key[5] = {s->g.B, s->g.W, s->g.H, s->g.Dp, s->up_rows};
-    if (!buf_holds(&s->d_up_scratch, bytes)) s->up_key[0] = 0;
-    if (!reserve(s, &s->d_up_scratch, bytes, 0)) return -1;
-    if (memcmp(key, s->up_key, sizeof key) != 0) {
-        s->up_key[0] = 0;                                        /* (B >= 1: 0 = no key) a fill that fails leaves none behind */
-        if (sgmd_memset_async(s->device, s->stream, s->d_up_scratch.p, 0, bytes) != 0) return -1;
-        memcpy(s->up_key, key, sizeof key);
-        s->up_gen = 0;
-    }
-    return reserve(s, &s->d_left_keep, px, 0) ? 0 : -1;
-}
-
 /* The buffers of sgm_match_both, sized together on its first use (keep: the right view's snapshots too; staging: the page-locked
  * right map of the host-pointer forms).  The median scratch starts zeroed like d_median_scratch; that fill is queued on s->stream,
  * the median may run on another one. */
 static int ensure_both(sgm_instance* s, bool keep, bool staging)
 {
-    const size_t px4 = (size_t)s->g.B * s->g.W * s->g.H * sizeof(float);
+    const size_t px4 = map_bytes(s);
     sgmd_geom g2 = s->g;
     g2.B *= 2;
     const size_t med = sgmd_median_scratch_bytes(&g2);
@@ -1281,45 +1283,59 @@ static int ensure_both(sgm_instance* s, bool keep, bool staging)
     return -1;
 }
 
-/* .c:109-120 for both views at once (sgm_match_both): one dual LR check from the raw maps (wta_l, d_disp_r), then speckle removal and
- * the median over the 2 B maps of d_both_maps as one batch -- one launch sequence each instead of two, and the second view's median
- * chain runs beside the first's instead of behind it.  The kernels see a batch of 2 B frames: whatever they choose by batch size
- * (speckle tile rows, the median's bands) they choose as a plain match with 2 B frames would.  out: where the finished maps are
- * copied to (device), NULL: they stay in d_both_maps. */
-typedef struct { void *left, *right; } both_out;
-static int post_both(sgm_instance* s, void* st2, const void* wta_l, const both_out* out)
+/* .c:115-120 behind the LR check: speckle removal and the median, in place on `maps`.  views == 2 (sgm_match_both, on d_both_maps:
+ * the B left maps, then the right ones, with the scratch of that size): one launch sequence for both views instead of two, and the
+ * second view's median chain runs beside the first's instead of behind it; the kernels see a batch of 2 B frames: whatever they
+ * choose by batch size (speckle tile rows, the median's bands) they choose as a plain match with 2 B frames would.  of_match: the tail
+ * of a match -- timed, snapshotted for sgm_keep_stages, hole filling and refinement (conf, guide) hooked in; else the two stages alone. */
+typedef struct { void *labels, *sizes, *totals, *median; } post_scratch;      /* the speckle and median scratch of B maps, or of 2 B */
+static int post_pass(sgm_instance* s, void* st, void* maps, int views, bool of_match, const void* conf, const void* guide)
 {
-    const int dev = s->device;
     const SGMOption* o = &s->opt;
-    const size_t px_bytes = (size_t)s->g.B * s->g.W * s->g.H * sizeof(float);
-    char* const maps = (char*)s->d_both_maps.p;
-    char* const snap = (char*)s->d_both_snap.p;
-    sgmd_geom g2 = s->g;
-    g2.B *= 2;
-    int rc = sgmd_lrcheck_both(dev, st2, &s->g, wta_l, s->d_disp_r.p, o->lrcheck_thres, o->is_check_lr ? 1 : 0, maps, maps + px_bytes);
-    if (rc == 0 && s->keep_stages) rc = sgmd_d2d_async(dev, st2, s->d_snap_lr.p, maps, px_bytes);
-    if (rc == 0 && s->keep_stages) rc = sgmd_d2d_async(dev, st2, snap, maps + px_bytes, px_bytes);
-    mark_on(s, st2, T_SPECKLE);
-    if (rc == 0 && o->is_remove_speckles)
-        rc = sgmd_speckle(dev, st2, &g2, maps, 1.0f, o->min_speckle_area, s->d_both_labels.p, s->d_both_sizes.p, s->d_both_totals.p);
-    if (rc == 0 && s->keep_stages) rc = sgmd_d2d_async(dev, st2, s->d_snap_speckle.p, maps, px_bytes);
-    if (rc == 0 && s->keep_stages) rc = sgmd_d2d_async(dev, st2, snap + px_bytes, maps + px_bytes, px_bytes);
-    mark_on(s, st2, T_MEDIAN);
-    if (rc == 0) rc = sgmd_median(dev, st2, &g2, maps, s->d_both_median.p, s->h_status);
-    if (rc == 0 && out->left) rc = sgmd_d2d_async(dev, st2, out->left, maps, px_bytes);
-    if (rc == 0 && out->right) rc = sgmd_d2d_async(dev, st2, out->right, maps + px_bytes, px_bytes);
+    const size_t bytes = map_bytes(s);
+    const bool keep = of_match && s->keep_stages;
+    const post_scratch x = views == 2 ? (post_scratch){s->d_both_labels.p, s->d_both_sizes.p, s->d_both_totals.p, s->d_both_median.p}
+                                      : (post_scratch){s->d_labels.p, s->d_sizes.p, s->d_totals.p, s->d_median_scratch.p};
+    sgmd_geom g = s->g;
+    g.B *= views;
+    int rc = 0;
+    if (of_match) mark_on(s, st, T_SPECKLE);
+    if (o->is_remove_speckles) rc = sgmd_speckle(s->device, st, &g, maps, 1.0f, o->min_speckle_area, x.labels, x.sizes, x.totals);   /* .c:115 */
+    if (rc == 0 && keep) rc = sgmd_d2d_async(s->device, st, s->d_snap_speckle.p, maps, bytes);
+    if (rc == 0 && keep && views == 2) rc = sgmd_d2d_async(s->device, st, (char*)s->d_both_snap.p + bytes, (char*)maps + bytes, bytes);
+    if (rc == 0 && of_match && s->fill_on) rc = fill_passes(s, st, maps, s->d_fill_class.p);         /* extension; timed as "speckle" */
+    if (rc != 0) return rc;
+    if (of_match) mark_on(s, st, T_MEDIAN);
+    rc = sgmd_median(s->device, st, &g, maps, x.median, s->h_status);                                     /* .c:120 */
+    if (rc == 0 && of_match && s->refine_on) rc = refine_passes(s, st, maps, conf, guide, &s->rf_eff);   /* extension; timed as "median" */
     return rc;
 }
 
+/* W < H: the diagonal planes are cleared before the aggregation */
+static int clear_diagonal_planes(sgm_instance* s)
+{
+    int rc = 0;
+    if (s->need_plane_memset && s->paths.ndirs > 4)
+        for (int f = 0; rc == 0 && f < s->g.B; ++f)
+            rc = sgmd_memset_async(s->device, s->stream, (char*)s->d_planes_alloc.p + ((size_t)f * 8 + 4) * s->plane_bytes, 0, 4 * s->plane_bytes);
+    return rc;
+}
+
+/* The body of SGM_Match (SemiGlobalMatching.c:80-122) on device buffers.  The first launch that is refused ends the
+ * match: nothing further is queued and false is returned with the instance in a consistent state -- the cost-sum state
+ * still describes exactly the matches that completed, so a later Match without Reset (Q14) accumulates onto the right thing. */
+#define LAUNCH(expr) do { if ((expr) != 0) goto failed; } while (0)
+typedef struct { void *left, *right; } both_out;
 /* d_conf: the device map the cost sum stores the reference view's matching confidence to (extension), NULL: none asked for.
- * both != NULL (sgm_match_both): d_out receives the raw left WTA map, the post pass finishes both views (post_both) */
+ * both != NULL (sgm_match_both): d_out receives the raw left WTA map, the post pass finishes both views in d_both_maps, from where
+ * they are copied to both->left / right (device; NULL: they stay there) */
 static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_right, void* d_out, void* d_conf, const both_out* both)
 {
     const int dev = s->device;
     void* st = s->stream;
     const sgmd_geom* g = &s->g;
     const SGMOption* o = &s->opt;
-    const size_t px_bytes = (size_t)g->B * g->W * g->H * sizeof(float);
+    const size_t px_bytes = map_bytes(s);
 
     /* stage groups on streams of their own (sgm_set_stage_cus / sgm_set_overlap_post; never in row-tile mode) */
     const bool own_sum = s->sum_stream && !row_tiled(s);
@@ -1329,7 +1345,7 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
     if (s->refine_on && !d_conf) d_conf = s->d_rf_conf.p;        /* the refinement needs the confidence: an internal map */
     /* the aggregation rewrites the planes the previous match's cost sum may still be reading on its own stream */
     if (s->sum_pending) LAUNCH(sgmd_stream_wait_event(dev, st, s->ev_sum));
-    if (!s->s_is_zero) LAUNCH(materialize_S(s));             /* Match without Reset: S of the previous frame is needed now */
+    LAUNCH(materialize_S(s));                                /* Match without Reset: S of the previous frame is needed now */
     /* rectification (extension): from here on the images are the instance's rectified ones; the caller's are only read.  Everything
      * that reads them -- the census, the aggregation's grey values, the copies for the guide and for the fused sweep, a later
      * materialize_S through that copy -- is queued on this stream, so stream order alone keeps the remap of match n + 1 behind the
@@ -1347,7 +1363,7 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
     if (s->refine_on) {
         guide = s->d_rf_guide[s->rf_turn].p;
         s->rf_turn ^= 1;
-        LAUNCH(sgmd_d2d_async(dev, st, (void*)guide, s->reference_view ? d_right : d_left, (size_t)g->B * g->W * g->H));
+        LAUNCH(sgmd_d2d_async(dev, st, (void*)guide, s->reference_view ? d_right : d_left, batch_px(s)));
     }
     if (!s->rect_on) mark(s, T_CENSUS);
     LAUNCH(prepare_costs(s, d_left, d_right));                                                      /* .c:82-83 */
@@ -1359,16 +1375,14 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
         LAUNCH(sgmd_cost(dev, st, g, s->d_census_l.p, s->d_census_r, s->d_cost.p));
     }
     mark(s, T_AGGREGATE);
-    if (s->need_plane_memset && s->paths.ndirs > 4)
-        for (int f = 0; f < g->B; ++f)
-            LAUNCH(sgmd_memset_async(dev, st, (char*)s->d_planes_alloc.p + ((size_t)f * 8 + 4) * s->plane_bytes, 0, 4 * s->plane_bytes));
+    LAUNCH(clear_diagonal_planes(s));
     /* the last vertical sweep fused with the cost sum (sgmd_upsum): whenever this match neither adds to an earlier S (Q14) nor has
      * to leave S behind for a test, nor asks for the matching confidence (written by the cost-sum kernels) */
-    const bool use_up = s->up_rows > 0 && !s->keep_stages && s->s_is_zero && s->fused_wta && !d_conf && !both;
+    const bool use_up = s->up_rows > 0 && !s->keep_stages && s->S.where == S_ZERO && s->fused_wta && !d_conf && !both;
     s->last_up_rows = use_up ? s->up_rows : 0;
     if (use_up) {
         LAUNCH(ensure_upsum(s));
-        LAUNCH(sgmd_d2d_async(dev, st, s->d_left_keep.p, d_left, (size_t)g->B * g->W * g->H));
+        LAUNCH(sgmd_d2d_async(dev, st, s->d_left_keep.p, d_left, batch_px(s)));
         sgmd_paths p = s->paths;
         p.up_fused = 1;
         LAUNCH(launch_aggregation(s, &p, d_left));
@@ -1383,17 +1397,7 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
     /* the cost sum writes d_out and the right-view map, which the previous match's post pass may still be reading */
     if (s->post_pending) LAUNCH(sgmd_stream_wait_event(dev, sts, s->ev_post));
     mark_on(s, sts, M_SUM_BEGIN);
-    if (use_up) {
-        LAUNCH(sgmd_upsum(dev, sts, g, &s->paths, s->d_left_keep.p, s->d_census_l.p, s->d_census_r, s->d_lut.p, s->d_planes, s->plane_bytes, s->d_extras.p,
-                          s->d_row_extras.p, s->d_row_count.p, s->row_cap, (o->is_check_lr || s->reference_view) ? 1 : 0, o->is_check_unique ? 1 : 0,
-                          1 - o->uniqueness_ratio, s->d_up_scratch.p, ++s->up_gen, s->h_status, s->up_rows, s->env_upsum_wgs > 0 ? s->env_upsum_wgs : 0, d_out, s->d_disp_r.p));
-        s->planes_partial = true;                                /* S of this frame = five planes + what materialize_S re-creates */
-        s->s_pending = true;
-        s->s_pending_accumulate = false;
-        s->s_is_zero = false;
-        mark_on(s, sts, T_WTA);
-    } else
-        LAUNCH(sum_and_wta(s, sts, d_out, d_conf, true, both != NULL));                                                   /* .c:94 sum, .c:99, .c:105 */
+    LAUNCH(cost_sum_stage(s, sts, d_out, d_conf, true, both != NULL, use_up));                      /* .c:94 sum, .c:99, .c:105 */
     if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, sts, s->d_snap_wta.p, d_out, px_bytes));
     mark_on(s, sts, T_LRCHECK);
     /* the post pass (latency-bound kernels that fill a fraction of the GPU) on its own stream, so that the stream(s) before it
@@ -1405,23 +1409,20 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
         st2 = s->post_stream;
         s->post_pending = true;                                  /* from here on the post stream has work of this match */
     }
-    if (both) {
-        LAUNCH(post_both(s, st2, d_out, both));
-    } else {
+    void* maps = both ? s->d_both_maps.p : d_out;                /* what the post pass finishes */
+    if (both)                            /* one dual LR check from the raw maps (d_out, d_disp_r) */
+        LAUNCH(sgmd_lrcheck_both(dev, st2, g, d_out, s->d_disp_r.p, o->lrcheck_thres, o->is_check_lr ? 1 : 0, maps, (char*)maps + px_bytes));
+    else {
         if (s->fill_on)                  /* hole filling (extension): classes from both WTA maps, before the LR check rewrites them */
             LAUNCH(sgmd_fill_classify(dev, st2, g, s->reference_view ? s->d_disp_r.p : d_out, s->reference_view ? d_out : s->d_disp_r.p,
                                       o->lrcheck_thres, s->reference_view, o->is_check_lr ? 1 : 0, s->d_fill_class.p));
         LAUNCH(lr_stage(s, st2, d_out));                                                                /* .c:109 */
-        if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_lr.p, d_out, px_bytes));
-        mark_on(s, st2, T_SPECKLE);
-        if (o->is_remove_speckles)                                                                      /* .c:115 */
-            LAUNCH(sgmd_speckle(dev, st2, g, d_out, 1.0f, o->min_speckle_area, s->d_labels.p, s->d_sizes.p, s->d_totals.p));
-        if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_speckle.p, d_out, px_bytes));
-        if (s->fill_on) LAUNCH(fill_passes(s, st2, d_out, s->d_fill_class.p));                           /* extension; timed as "speckle" */
-        mark_on(s, st2, T_MEDIAN);
-        LAUNCH(sgmd_median(dev, st2, g, d_out, s->d_median_scratch.p, s->h_status));                                   /* .c:120 */
-        if (s->refine_on) LAUNCH(refine_passes(s, st2, d_out, d_conf, guide, &s->rf_eff));    /* extension; timed as "median" */
     }
+    if (s->keep_stages) LAUNCH(sgmd_d2d_async(dev, st2, s->d_snap_lr.p, maps, px_bytes));
+    if (s->keep_stages && both) LAUNCH(sgmd_d2d_async(dev, st2, s->d_both_snap.p, (char*)maps + px_bytes, px_bytes));
+    LAUNCH(post_pass(s, st2, maps, both ? 2 : 1, true, d_conf, guide));                                 /* .c:115-120 */
+    if (both && both->left) LAUNCH(sgmd_d2d_async(dev, st2, both->left, maps, px_bytes));
+    if (both && both->right) LAUNCH(sgmd_d2d_async(dev, st2, both->right, (char*)maps + px_bytes, px_bytes));
     mark_on(s, st2, M_END);
     if (overlap) LAUNCH(sgmd_event_record(dev, s->ev_post, st2));
     else if (own_sum) LAUNCH(sgmd_event_record(dev, s->ev_sum, st2));   /* the post pass ran on the sum stream: "sum done" = all of it */
@@ -1472,11 +1473,9 @@ static bool tile_aggregate(sgm_instance* s, int dir_mask, int run_anom)
 bool sgm_tile_begin(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right)
 {
     if (!s || !s->initialized || !d_left || !d_right) return false;
-    int rc = s->s_is_zero ? 0 : materialize_S(s);
+    int rc = materialize_S(s);
     if (rc == 0) rc = prepare_costs(s, d_left, d_right);
-    if (s->need_plane_memset && s->paths.ndirs > 4)
-        for (int f = 0; rc == 0 && f < s->g.B; ++f)
-            rc = sgmd_memset_async(s->device, s->stream, (char*)s->d_planes_alloc.p + ((size_t)f * 8 + 4) * s->plane_bytes, 0, 4 * s->plane_bytes);
+    if (rc == 0) rc = clear_diagonal_planes(s);
     if (rc != 0) FAIL("a kernel launch failed");
     s->tile_left = d_left;
     int hmask = 0;
@@ -1524,7 +1523,7 @@ bool sgm_tile_sweep(sgm_instance* s, int forward)
 bool sgm_tile_finish(sgm_instance* s, float* d_disp_left)
 {
     if (!s || !s->initialized || !s->tile_left || !d_disp_left) return false;
-    int rc = sum_and_wta(s, s->stream, d_disp_left, NULL, false, false);
+    int rc = cost_sum_stage(s, s->stream, d_disp_left, NULL, false, false, false);
     if (rc == 0) rc = lr_stage(s, s->stream, d_disp_left);
     s->tile_left = NULL;
     if (rc != 0) FAIL("a kernel launch failed");
@@ -1534,12 +1533,7 @@ bool sgm_tile_finish(sgm_instance* s, float* d_disp_left)
 bool sgm_tile_post(sgm_instance* s, float* d_disp_left)
 {
     if (!s || !s->initialized || !d_disp_left) return false;
-    int rc = 0;
-    if (s->opt.is_remove_speckles)
-        rc = sgmd_speckle(s->device, s->stream, &s->g, d_disp_left, 1.0f, s->opt.min_speckle_area, s->d_labels.p, s->d_sizes.p,
-                          s->d_totals.p);
-    if (rc == 0) rc = sgmd_median(s->device, s->stream, &s->g, d_disp_left, s->d_median_scratch.p, s->h_status);
-    if (rc != 0) FAIL("a kernel launch failed");
+    if (post_pass(s, s->stream, d_disp_left, 1, false, NULL, NULL) != 0) FAIL("a kernel launch failed");
     return true;
 }
 
@@ -1654,7 +1648,7 @@ bool sgm_match_wait(sgm_instance* s)
 /* the confidence staging: a device map for the host-pointer forms, and a page-locked one for callers whose buffer is not */
 static int ensure_conf(sgm_instance* s, bool host_staging)
 {
-    const size_t need = (size_t)s->g.B * s->g.W * s->g.H * sizeof(uint16_t);
+    const size_t need = batch_px(s) * sizeof(uint16_t);
     const buf_request maps[] = {{&s->d_conf, need, 0}, {&s->h_conf, need, BUF_PINNED | BUF_LAZY_DRAIN}};
     return reserve_all(s, maps, host_staging ? 2 : 1, 0) ? 0 : -1;
 }
@@ -1739,7 +1733,7 @@ static bool queue_outputs(sgm_instance* s, bool ok, const host_out* out, int n, 
 static bool match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left, uint16_t* conf)
 {
     if (!host_entry_ready(s, img_left, img_right, disp_left)) return false;
-    const size_t px = (size_t)s->g.B * s->g.W * s->g.H;           /* batch > 1: B consecutive frames */
+    const size_t px = batch_px(s);           /* batch > 1: B consecutive frames */
     host_out out[2] = {{disp_left, &s->h_disp, &s->d_disp, 0, px * sizeof(float), false},
                        {conf, &s->h_conf, &s->d_conf, 0, px * sizeof(uint16_t), false}};
     const int n = conf ? 2 : 1;
@@ -1796,7 +1790,7 @@ bool sgm_match_both_device(sgm_instance* s, const uint8_t* d_left, const uint8_t
 bool sgm_match_both_async(sgm_instance* s, const uint8_t* img_left, const uint8_t* img_right, float* disp_left, float* disp_right)
 {
     if (!both_ready(s, img_left, img_right, disp_left, disp_right) || !sgm_match_wait(s)) return false;
-    const size_t px = (size_t)s->g.B * s->g.W * s->g.H, bytes = px * sizeof(float);
+    const size_t px = batch_px(s), bytes = px * sizeof(float);
     host_out out[2] = {{disp_left, &s->h_disp, &s->d_both_maps, 0, bytes, false},
                        {disp_right, &s->h_disp_r, &s->d_both_maps, bytes, bytes, false}};
     outputs_pinned(s, out, 2);
@@ -1878,7 +1872,7 @@ bool sgm_gray_from_planes(sgm_instance* s, const uint8_t* d_bgr, size_t count, i
 
 static int ensure_planes_io(sgm_instance* s)
 {
-    const size_t px = (size_t)s->g.B * s->g.W * s->g.H;
+    const size_t px = batch_px(s);
     const buf_request io[] = {{&s->d_bgr, 6 * px, 0}, {&s->d_depth, px * sizeof(float), 0}, {&s->h_bgr, 6 * px, BUF_PINNED}};
     return reserve_all(s, io, 3, 0) ? 0 : -1;
 }
@@ -1888,7 +1882,7 @@ bool sgm_match_planes_async(sgm_instance* s, const uint8_t* planes, float fx, fl
     if (!host_entry_ready(s, planes, planes, depth)) return false;
     if (ensure_planes_io(s) != 0) FAIL("device allocation failed for the colour planes of %dx%d", s->g.W, s->g.H);
     const int dev = s->device;
-    const size_t fpx = (size_t)s->g.W * s->g.H, px = (size_t)s->g.B * fpx;
+    const size_t fpx = frame_px(s), px = (size_t)s->g.B * fpx;
     host_out out = {depth, &s->h_disp, &s->d_depth, 0, px * sizeof(float), false};
     outputs_pinned(s, &out, 1);
     bool ok = upload(s, s->d_bgr.p, planes, s->h_bgr.p, 6 * px);
@@ -1927,7 +1921,7 @@ bool sgm_compare_depth(sgm_instance* s, const float* d_ground_truth, const float
 
 static size_t compact_volume(const sgm_instance* s, const void* padded, size_t elem, void* out)
 {
-    const size_t px = (size_t)s->g.W * s->g.H;
+    const size_t px = frame_px(s);
     const char* src = (const char*)padded;
     char* dst = (char*)out;
     for (size_t p = 0; p < px; ++p)
@@ -1935,47 +1929,50 @@ static size_t compact_volume(const sgm_instance* s, const void* padded, size_t e
     return px * s->g.D * elem;
 }
 
+/* The stages sgm_read_stage hands out (include/sgm_mi355x.h has the list): the instance's pointer to each, the size of an element,
+ * the half of a buffer of two batches it sits in, whether it is a padded volume ([H][W][Dp], compacted to D on the way out), and what
+ * has to hold for it to exist now.  Two rows with one id: whichever holds.  The direction planes (10 .. 17) are not in here. */
+enum { HAS_KEPT = 1, HAS_FILL = 2, HAS_RECT = 4, HAS_BOTH = 8, HAS_BOTH_KEPT = 16, HAS_WIDE = 32, HAS_COST = 64, NOT_WIDE = 128, NOT_BOTH = 256 };
+#define AT(member) offsetof(struct sgm_instance, member)
+static const struct { int id; size_t at; int elem, half; bool volume; int needs; } k_stages[] = {
+    {0, AT(d_census64_l.p), 8, 0, false, HAS_WIDE},           {0, AT(d_census_l.p), 4, 0, false, NOT_WIDE},
+    {1, AT(d_census64_r.p), 8, 0, false, HAS_WIDE},           {1, AT(d_census_r), 4, 0, false, NOT_WIDE},
+    {2, AT(d_cost.p), 1, 0, true, HAS_WIDE | HAS_COST},       {2, AT(d_cost.p), 1, 0, true, HAS_KEPT | HAS_COST},
+    {3, AT(d_S.p), 2, 0, true, 0},                            /* (materialised first) */
+    {4, AT(d_snap_wta.p), 4, 0, false, HAS_KEPT},             {5, AT(d_disp_r.p), 4, 0, false, 0},
+    {6, AT(d_snap_lr.p), 4, 0, false, HAS_KEPT},              {7, AT(d_snap_speckle.p), 4, 0, false, HAS_KEPT},
+    {8, AT(d_both_maps.p), 4, 0, false, HAS_BOTH},            {8, AT(d_disp.p), 4, 0, false, NOT_BOTH},
+    {9, AT(d_fill_map.p), 4, 0, false, HAS_KEPT | HAS_FILL},  {18, AT(d_fill_class.p), 1, 0, false, HAS_FILL},
+    {19, AT(d_rect_l.p), 1, 0, false, HAS_RECT},              {20, AT(d_rect_r.p), 1, 0, false, HAS_RECT},
+    /* sgm_match_both: the right view after the LR check, after speckle removal, and finished */
+    {26, AT(d_both_snap.p), 4, 0, false, HAS_KEPT | HAS_BOTH_KEPT}, {27, AT(d_both_snap.p), 4, 1, false, HAS_KEPT | HAS_BOTH_KEPT},
+    {28, AT(d_both_maps.p), 4, 1, false, HAS_BOTH},
+};
+
 size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacity)
 {
     if (!s || !s->initialized || !host_out) return 0;
-    const size_t px = (size_t)s->g.W * s->g.H;                    /* one frame */
-    const size_t f = (size_t)s->read_frame;
+    const size_t px = frame_px(s), f = (size_t)s->read_frame;
     const char* src = NULL;
     size_t elem = 0;
     bool volume = false;
     int row_a = 0, row_b = s->g.H;                                /* rows the device holds of a volume stage */
-    if ((which == 4 || which == 6 || which == 7 || which == 9 || (which == 2 && !volume_fed(s))) && !s->keep_stages) return 0;
-    if ((which == 9 || which == 18) && !s->fill_on) return 0;
-    if ((which == 26 || which == 27) && !(s->keep_stages && s->last_both_kept)) return 0;
-    if (which == 28 && !s->last_both) return 0;
-    if ((which == 19 || which == 20) && !s->rect_on) return 0;
-    if (which == 2 && !s->d_cost.p) return 0;
+    const int has = (s->keep_stages ? HAS_KEPT : 0) | (s->fill_on ? HAS_FILL : 0) | (s->rect_on ? HAS_RECT : 0) |
+                    (s->last_both ? HAS_BOTH : NOT_BOTH) | (s->last_both_kept ? HAS_BOTH_KEPT : 0) |
+                    (volume_fed(s) ? HAS_WIDE : NOT_WIDE) | (s->d_cost.p ? HAS_COST : 0);
     if (which == 3 && (ensure_S(s) != 0 || materialize_S(s) != 0)) return 0;
-    switch (which) {
-    case 0: src = volume_fed(s) ? (const char*)s->d_census64_l.p + f * px * 8 : (const char*)s->d_census_l.p + f * px * 4; elem = volume_fed(s) ? 8 : 4; break;
-    case 1: src = volume_fed(s) ? (const char*)s->d_census64_r.p + f * px * 8 : (const char*)s->d_census_r + f * px * 4; elem = volume_fed(s) ? 8 : 4; break;
-    case 2: src = (const char*)s->d_cost.p + f * px * s->g.Dp; elem = 1; volume = true; break;
-    case 3: src = (const char*)s->d_S.p + f * px * s->g.Dp * 2; elem = 2; volume = true; break;
-    case 4: src = (const char*)s->d_snap_wta.p + f * px * 4; elem = 4; break;
-    case 5: src = (const char*)s->d_disp_r.p + f * px * 4; elem = 4; break;
-    case 6: src = (const char*)s->d_snap_lr.p + f * px * 4; elem = 4; break;
-    case 7: src = (const char*)s->d_snap_speckle.p + f * px * 4; elem = 4; break;
-    case 8: src = (const char*)(s->last_both ? s->d_both_maps.p : s->d_disp.p) + f * px * 4; elem = 4; break;
-    /* sgm_match_both: the right view after the LR check, after speckle removal, and finished */
-    case 26: src = (const char*)s->d_both_snap.p + f * px * 4; elem = 4; break;
-    case 27: src = (const char*)s->d_both_snap.p + ((size_t)s->g.B + f) * px * 4; elem = 4; break;
-    case 28: src = (const char*)s->d_both_maps.p + ((size_t)s->g.B + f) * px * 4; elem = 4; break;
-    case 9: src = (const char*)s->d_fill_map.p + f * px * 4; elem = 4; break;
-    case 18: src = (const char*)s->d_fill_class.p + f * px; elem = 1; break;
-    case 19: src = (const char*)s->d_rect_l.p + f * px; elem = 1; break;
-    case 20: src = (const char*)s->d_rect_r.p + f * px; elem = 1; break;
-    default:
-        if (which >= 10 && which < 10 + s->paths.ndirs) {
-            /* frame-addressed base of the plane; only rows [plane_row_lo, plane_row_lo + plane_rows) have storage */
-            src = (const char*)s->d_planes + (f * 8 + (size_t)(which - 10)) * s->plane_bytes;
-            elem = 1; volume = true;
-            row_a = s->plane_row_lo; row_b = s->plane_row_lo + s->plane_rows;
-        }
+    for (size_t i = 0; !src && i < sizeof k_stages / sizeof k_stages[0]; ++i) {
+        const char* base = *(char* const*)((const char*)s + k_stages[i].at);
+        if (k_stages[i].id != which || (k_stages[i].needs & ~has) || !base) continue;
+        elem = (size_t)k_stages[i].elem;
+        volume = k_stages[i].volume;
+        src = base + ((size_t)k_stages[i].half * s->g.B + f) * px * elem * (volume ? (size_t)s->g.Dp : 1);
+    }
+    if (which >= 10 && which < 10 + s->paths.ndirs) {
+        /* frame-addressed base of the plane; only rows [plane_row_lo, plane_row_lo + plane_rows) have storage */
+        src = (const char*)s->d_planes + (f * 8 + (size_t)(which - 10)) * s->plane_bytes;
+        elem = 1; volume = true;
+        row_a = s->plane_row_lo; row_b = s->plane_row_lo + s->plane_rows;
     }
     if (!src) return 0;
     const size_t need = volume ? px * s->g.D * elem : px * elem;

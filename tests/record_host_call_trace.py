@@ -16,10 +16,17 @@ import standin
 GOLDEN = os.path.join(standin.TESTS, "golden", "host_call_trace.json")
 
 
+# launchers the driver wraps (-Wl,--wrap): it notes the roles of their pointers, then calls the stand-in's own
+WRAPPED = ("alloc", "free", "speckle", "median", "lrcheck", "lrcheck_right", "d2d_async", "fill_classify", "fill_pass", "remap")
+
+
 def build_driver(host_c, workdir, sanitize=False):
-    """host_trace_driver + the given sgm_host.c + the stand-in device -> the executable (the headers are the tree's)"""
-    return standin.build(workdir, sanitize=sanitize, extra_sources=[os.path.join(standin.TESTS, "host_trace_driver.c")],
-                         exe="host_trace_driver", host_c=host_c, flags=("-g", "-static-libasan") if sanitize else ("-g",))
+    """host_trace_driver + the given sgm_host.c + the stand-in device (and the stand-in remap) -> the executable (the headers are
+    the tree's)"""
+    wrap = "-Wl," + ",".join("--wrap=sgmd_" + n for n in WRAPPED)
+    return standin.build(workdir, sanitize=sanitize, exe="host_trace_driver", host_c=host_c,
+                         extra_sources=[os.path.join(standin.TESTS, "host_trace_driver.c"), os.path.join(standin.TESTS, "stub_rectify.c")],
+                         flags=("-g", "-static-libasan", wrap) if sanitize else ("-g", wrap))
 
 
 def record(host_c, workdir):

@@ -158,7 +158,7 @@ def test_a_shrink_allocates_nothing(host):
 
 @pytest.mark.parametrize("fused_wta", ["1", "0"])
 def test_S_of_the_larger_shape_never_reaches_a_sum_after_a_shrink(host, monkeypatch, fused_wta):
-    """d_S is kept across a shrink, full of the larger shape's sums, and is cleared lazily (s_is_zero).  The first sum after the
+    """d_S is kept across a shrink, full of the larger shape's sums, and is cleared lazily (sum_reset).  The first sum after the
     Reset that writes d_S must REPLACE: with the fused kernel that is the sum a Match without Reset puts together first
     (sgmd_sum_wta, accumulate 0) ahead of its own accumulating one; with the separate kernels it is the first match's own."""
     monkeypatch.setenv("SGM_FUSED_WTA", fused_wta)
