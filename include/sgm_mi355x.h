@@ -412,6 +412,59 @@ bool   sgm_compare_depth(sgm_instance* s, const float* d_ground_truth, const flo
 bool   sgm_depth_from_both(sgm_instance* s, const float* d_disp_left, const float* d_disp_right, size_t count, float fx_left,
                            float fx_right, float baseline, float doffs, float* d_depth);
 
+/* ---- point clouds: disparity maps to XYZ on the device, organised or compacted ----
+ * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/cloud_ref.py.
+ * Per pixel p = (f, y, x) of a map, in float32, every operation rounded on its own (no contraction, correctly rounded divide):
+ *   fb = (float)((double)fx * (double)baseline)                       (the value sgm_disparity_to_depth uses)
+ *   the pixel is KEPT iff all of:  d = disp[p] is finite (by its bit pattern: a caller's map may hold NaN);
+ *     mask == NULL || mask[p] != 0;   conf == NULL || conf[p] >= min_conf;
+ *     den = d + doffs is finite and den > 0;   Z = fb / den is finite;   z_min <= Z && Z <= z_max
+ *   for a kept pixel  X = (((float)x - cx) * Z) / fx,  Y = (((float)y - cy) * Z) / fy.
+ * So Z of a kept pixel is bit-identical to what sgm_disparity_to_depth writes for it.  Two products of the one predicate:
+ *   organised cloud   float [frames][height][width][3]: X Y Z of a kept pixel, three quiet NaNs (0x7FC00000) for every other
+ *                     (what cv::reprojectImageTo3D and PCL users expect);
+ *   point list        the kept pixels only, as sgm_point records packed in raster order -- frame-major, then row, then column --
+ *                     with offsets[frames + 1] (u32): frame f's points are points[offsets[f] .. offsets[f + 1]), offsets[frames]
+ *                     is the total.  The order is part of the contract: the list is the same on every run (numpy's nonzero
+ *                     order).  Records at index offsets[frames] and beyond are not written.
+ * sgm_cloud_organized / sgm_cloud_points: all pointers are device pointers on the instance's device; d_mask (u8) and d_conf (u16)
+ * may be NULL and, like d_disp, need no alignment beyond their element's (a map that cannot be read 16 bytes at a time takes a
+ * one-pixel-per-lane path with the same results); d_points has room for frames * width * height records (nothing is clipped) and
+ * is 16-byte aligned.  Asynchronous on sgm_stream(s), behind the last match also where its post pass runs on a stream of its own
+ * (sgm_set_overlap_post).
+ * d_disp == NULL: the reference-view final map of the instance's last match, the one stage 8 reads back (after sgm_match_device
+ * and its twins the result is in the caller's buffer: pass that); the spec's width / height / frames must then be the instance's
+ * shape and batch, and row-tile mode (sgm_set_rows) is refused.  With an explicit d_disp the instance need not be initialised.
+ * false, and nothing is queued: NULL s, spec or output; a d_points that is not 16-byte aligned; a spec outside the ranges below;
+ * fx, fy, baseline or fb not finite and > 0; cx, cy or doffs not finite; z_min NaN or < 0; z_max NaN or not > z_min (+INFINITY is allowed); min_conf > 65535; a build
+ * without the kernels.  The point list takes three launches (count per tile, one scan, emit) and a few bytes of scratch per 2048
+ * pixels, allocated at the first such call: an instance that never asks for a cloud allocates and launches what it did before.
+ * sgm_read_cloud (blocking; SGM_ReadCloud: the default instance): the point list of the last match's final map, no mask and no
+ * confidence, made in device buffers of the instance's own.  offsets (frames + 1 entries) is always copied to the host; if
+ * offsets[frames] <= capacity exactly that many records are copied to points and the result is true, else no record is copied
+ * and the result is false: size a buffer from offsets[frames] and call again (points may be NULL with capacity 0). */
+typedef struct {            /* 48 bytes, every field 4 bytes, no padding */
+    int32_t  width, height, frames;     /* maps are f32 [frames][height][width]; 1 <= width, height <= 65535, frames >= 1,
+                                           frames * width * height <= 2^31 */
+    float    fx, fy, cx, cy;            /* pinhole of the rectified reference camera, pixels */
+    float    baseline, doffs;           /* as sgm_disparity_to_depth: depth = fx * baseline / (d + doffs) */
+    float    z_min, z_max;              /* keep z_min <= Z <= z_max; 0 and +INFINITY keep every finite positive Z */
+    uint32_t min_conf;                  /* with a confidence map: keep conf >= min_conf (0..65535) */
+} sgm_cloud_spec;
+typedef struct { float x, y, z; uint32_t pixel; } sgm_point;     /* 16 bytes; pixel = (y << 16) | x */
+bool   sgm_cloud_organized(sgm_instance* s, const sgm_cloud_spec* spec, const float* d_disp, const uint8_t* d_mask,
+                           const uint16_t* d_conf, float* d_xyz);
+bool   sgm_cloud_points(sgm_instance* s, const sgm_cloud_spec* spec, const float* d_disp, const uint8_t* d_mask,
+                        const uint16_t* d_conf, sgm_point* d_points, uint32_t* d_offsets);
+bool   sgm_read_cloud(sgm_instance* s, const sgm_cloud_spec* spec, sgm_point* points, size_t capacity, uint32_t* offsets);
+bool   SGM_ReadCloud(const sgm_cloud_spec* spec, sgm_point* points, size_t capacity, uint32_t* offsets);
+/* The mask SGM_SetRectify leaves to the caller: mask[y][x] = 1 iff all four taps of output pixel (y, x) fall inside
+ * [0, height) x [0, width) under exactly the quantisation and tap rule of SGM_SetRectify (a pixel with a coordinate that is not
+ * finite or has |m| > 32768 gets 0), else 0 -- a tap with weight 0 counts like any other.  Host only, no device needed; one
+ * camera per call: a caller who also wants the right view's footprint combines the two masks itself.  false for a NULL pointer,
+ * a size < 1 or more than 2^31 - 1 pixels. */
+bool   sgm_rectify_valid_mask(int width, int height, const float* map_x, const float* map_y, uint8_t* mask);
+
 /* The filling of SGM_SetFillHoles (step 2) on any device map: d_disp, the instance's B frames of its shape, is filled in
  * place with R = the option's max_disparity; d_class (u8 [B][H][W], classes 0/1/2) drives passes 1 and 2, NULL runs pass 3
  * alone.  Asynchronous on sgm_stream(s), behind the last match.  Works whether or not filling is on for matches; the filled

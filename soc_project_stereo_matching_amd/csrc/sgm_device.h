@@ -246,6 +246,23 @@ int sgmd_score(int ord, void* stream, const void* ground_truth, const void* test
 int sgmd_depth_both(int ord, void* stream, const void* disp_l, const void* disp_r, size_t n, float fx_l, float fx_r, float baseline,
                     float doffs, void* depth);
 
+/* Extension (parity unpinned by the reference), the point clouds of include/sgm_mi355x.h (sgm_cloud_spec); sgm_cloud.hip.
+ * c: the spec as the host validated it, fb = (float)((double)fx * (double)baseline).  disp f32, mask u8 or NULL, conf u16 or NULL,
+ * [B][H][W] each.  sgmd_cloud_organized: xyz f32 [B][H][W][3], X Y Z of a kept pixel, three quiet NaNs (0x7FC00000) elsewhere.
+ * sgmd_cloud_points: the kept pixels as 16-byte records {x, y, z, pixel = y << 16 | x} packed in raster order into points (room
+ * for B * W * H records, 16-byte aligned; records past the total are not written) and offsets u32 [B + 1]; three launches (count,
+ * scan, emit) that use scratch, sgmd_cloud_scratch_bytes(W, H, B) bytes, which must not be shared with a call still in flight.
+ * sgm_host.c references all three weakly (a host built without them answers false to the cloud entry points). */
+typedef struct {
+    int W, H, B;
+    float fx, fy, cx, cy, fb, doffs, z_min, z_max;
+    unsigned min_conf;
+} sgmd_cloud;
+size_t sgmd_cloud_scratch_bytes(int W, int H, int B);
+int sgmd_cloud_organized(int ord, void* stream, const sgmd_cloud* c, const void* disp, const void* mask, const void* conf, void* xyz);
+int sgmd_cloud_points(int ord, void* stream, const sgmd_cloud* c, const void* disp, const void* mask, const void* conf, void* scratch,
+                      void* points, void* offsets);
+
 /* grey = (weight_r r + 150 g + 29 b) >> 8 of three consecutive n-byte planes B, G, R (the test platform's frame
  * format, server.py:105-131; the firmware's conversion, stereo_matching.c:18-25) */
 int sgmd_gray_planes(int ord, void* stream, const void* bgr, size_t n, int weight_r, void* gray);

@@ -147,6 +147,9 @@ struct sgm_instance {
      * the speckle and median scratch of such a batch, the right view's snapshots for sgm_keep_stages (after the LR check, after
      * speckle removal: f32 [2][B][H][W]) and the page-locked staging of the right map */
     sgm_buf d_both_raw, d_both_maps, d_both_labels, d_both_sizes, d_both_totals, d_both_median, d_both_snap, h_disp_r;
+    /* point clouds (sgm_cloud_points / sgm_read_cloud; allocated at the first such call): the tile counts and bases of the point list's
+     * three launches, and the list and offsets sgm_read_cloud makes on the device before it copies them */
+    sgm_buf d_cloud_scratch, d_cloud_points, d_cloud_offsets;
     bool last_both;              /* the last match was a sgm_match_both that was queued to its end: stage 8 is the first half of d_both_maps */
     bool last_both_kept;         /* ... and it ran with sgm_keep_stages: d_both_snap holds ITS right-view snapshots (stages 26, 27) */
     size_t plane_bytes;
@@ -176,6 +179,7 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     DEVICE_BUF(d_rf_guide[1]), PINNED_BUF(h_left), PINNED_BUF(h_right), PINNED_BUF(h_disp), DEVICE_BUF(d_both_raw),
     DEVICE_BUF(d_both_maps), DEVICE_BUF(d_both_labels), DEVICE_BUF(d_both_sizes), DEVICE_BUF(d_both_totals), DEVICE_BUF(d_both_median),
     DEVICE_BUF(d_both_snap), PINNED_BUF(h_disp_r), DEVICE_BUF(d_rect_maps), DEVICE_BUF(d_rect_l), DEVICE_BUF(d_rect_r),
+    DEVICE_BUF(d_cloud_scratch), DEVICE_BUF(d_cloud_points), DEVICE_BUF(d_cloud_offsets),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -611,6 +615,28 @@ bool sgm_rectify_maps(const double K[9], const double dist[5], const double R[9]
     return true;
 }
 
+/* The quantisation of one map entry (include/sgm_mi355x.h): both coordinates become -64, all four taps outside, when either is not
+ * finite or has |m| > 32768 (!(<=) also catches NaN) */
+static void rectify_quantise_entry(double x, double y, int32_t* xq, int32_t* yq)
+{
+    const bool ok = fabs(x) <= 32768.0 && fabs(y) <= 32768.0;
+    *xq = ok ? (int32_t)floor(x * 32.0 + 0.5) : -64;
+    *yq = ok ? (int32_t)floor(y * 32.0 + 0.5) : -64;
+}
+
+bool sgm_rectify_valid_mask(int width, int height, const float* map_x, const float* map_y, uint8_t* mask)
+{
+    if (!map_x || !map_y || !mask || width < 1 || height < 1 || (long long)width * height > 0x7FFFFFFFLL) return false;
+    const size_t n = (size_t)width * height;
+    for (size_t p = 0; p < n; ++p) {
+        int32_t xq, yq;
+        rectify_quantise_entry((double)map_x[p], (double)map_y[p], &xq, &yq);
+        const int32_t x0 = xq >> 5, y0 = yq >> 5;                 /* the taps are (y0, x0) .. (y0 + 1, x0 + 1) */
+        mask[p] = x0 >= 0 && x0 < width - 1 && y0 >= 0 && y0 < height - 1;
+    }
+    return true;
+}
+
 /* The quantised maps of both views in the layout sgmd_remap reads (sgm_device.h), malloc'ed; NULL: bad arguments or out of memory */
 static int32_t* rectify_quantise(int width, int height, const float* map_lx, const float* map_ly, const float* map_rx, const float* map_ry)
 {
@@ -625,10 +651,7 @@ static int32_t* rectify_quantise(int width, int height, const float* map_lx, con
         int32_t* yq = xq + pitch;
         for (size_t p = 0; p < pitch; ++p) {
             const double x = p < n ? (double)mx[view][p] : NAN, y = p < n ? (double)my[view][p] : NAN;
-            /* !(<=) also catches NaN: such a pixel has all four taps outside */
-            const bool ok = fabs(x) <= 32768.0 && fabs(y) <= 32768.0;
-            xq[p] = ok ? (int32_t)floor(x * 32.0 + 0.5) : -64;
-            yq[p] = ok ? (int32_t)floor(y * 32.0 + 0.5) : -64;
+            rectify_quantise_entry(x, y, &xq[p], &yq[p]);
         }
     }
     return q;
@@ -1834,6 +1857,92 @@ bool sgm_depth_from_both(sgm_instance* s, const float* d_disp_left, const float*
     return sgmd_depth_both(s->device, s->stream, d_disp_left, d_disp_right, count, fx_left, fx_right, baseline, doffs, d_depth) == 0;
 }
 
+/* ------------------------------------------------------------------ point clouds (extension) */
+
+/* The cloud launchers (sgm_cloud.hip), weakly referenced like the extensions above: a host built without them has no clouds */
+#pragma weak sgmd_cloud_scratch_bytes
+#pragma weak sgmd_cloud_organized
+#pragma weak sgmd_cloud_points
+static bool cloud_available(void) { return sgmd_cloud_scratch_bytes != NULL && sgmd_cloud_organized != NULL && sgmd_cloud_points != NULL; }
+
+static bool finite_positive(float v) { return isfinite(v) && v > 0.0f; }
+
+/* the spec as the kernels take it; false for anything outside the ranges of include/sgm_mi355x.h */
+static bool cloud_spec_valid(const sgm_cloud_spec* sp, sgmd_cloud* c)
+{
+    if (sp->width < 1 || sp->width > 65535 || sp->height < 1 || sp->height > 65535 || sp->frames < 1 ||
+        (long long)sp->frames * sp->width * sp->height > (1LL << 31))
+        return false;
+    const float fb = (float)((double)sp->fx * (double)sp->baseline);
+    if (!finite_positive(sp->fx) || !finite_positive(sp->fy) || !finite_positive(sp->baseline) || !finite_positive(fb)) return false;
+    if (!isfinite(sp->cx) || !isfinite(sp->cy) || !isfinite(sp->doffs)) return false;
+    if (!(sp->z_min >= 0.0f) || !(sp->z_max > sp->z_min) || sp->min_conf > 65535u) return false;       /* !(..) also catches NaN */
+    *c = (sgmd_cloud){sp->width, sp->height, sp->frames, sp->fx, sp->fy, sp->cx, sp->cy, fb, sp->doffs, sp->z_min, sp->z_max, sp->min_conf};
+    return true;
+}
+
+/* What both device forms check before they queue anything; *disp: the map to read -- the caller's, or (NULL) the reference-view
+ * final map of the last match, where stage 8 finds it */
+static bool cloud_ready(sgm_instance* s, const sgm_cloud_spec* spec, const void* out, sgmd_cloud* c, const float** disp)
+{
+    if (!s || !spec || !out) return false;
+    if (!cloud_available()) FAIL("the point clouds are not part of this build");
+    if (!cloud_spec_valid(spec, c)) return false;
+    if (*disp) return true;
+    if (!s->initialized) return false;
+    if (row_tiled(s)) FAIL("the map of a row tile is the caller's: pass it to the cloud entry points explicitly");
+    if (c->W != s->g.W || c->H != s->g.H || c->B != s->g.B)
+        FAIL("the cloud spec is for %d frames of %dx%d, the instance's last match for %d of %dx%d", c->B, c->W, c->H, s->g.B, s->g.W, s->g.H);
+    *disp = (const float*)(s->last_both ? s->d_both_maps.p : s->d_disp.p);
+    return *disp != NULL;
+}
+
+bool sgm_cloud_organized(sgm_instance* s, const sgm_cloud_spec* spec, const float* d_disp, const uint8_t* d_mask,
+                         const uint16_t* d_conf, float* d_xyz)
+{
+    sgmd_cloud c;
+    if (!cloud_ready(s, spec, d_xyz, &c, &d_disp)) return false;
+    /* the map may be the result of a match whose last stages run on a stream of their own (sgm_set_overlap_post / _stage_cus) */
+    if (wait_for_result(s, s->stream) != 0) return false;
+    return sgmd_cloud_organized(s->device, s->stream, &c, d_disp, d_mask, d_conf, d_xyz) == 0;
+}
+
+/* the point list into any device buffers, behind the last match; the tile scratch is the instance's */
+static bool cloud_points_queue(sgm_instance* s, const sgmd_cloud* c, const float* d_disp, const uint8_t* d_mask, const uint16_t* d_conf,
+                               void* d_points, void* d_offsets)
+{
+    /* (growing the scratch drains the streams first: an earlier list may still be using it) */
+    if (!reserve(s, &s->d_cloud_scratch, sgmd_cloud_scratch_bytes(c->W, c->H, c->B), 0))
+        FAIL("device allocation failed for the point list of %d frames of %dx%d", c->B, c->W, c->H);
+    if (wait_for_result(s, s->stream) != 0) return false;
+    return sgmd_cloud_points(s->device, s->stream, c, d_disp, d_mask, d_conf, s->d_cloud_scratch.p, d_points, d_offsets) == 0;
+}
+
+bool sgm_cloud_points(sgm_instance* s, const sgm_cloud_spec* spec, const float* d_disp, const uint8_t* d_mask,
+                      const uint16_t* d_conf, sgm_point* d_points, uint32_t* d_offsets)
+{
+    sgmd_cloud c;
+    if (!d_offsets || (uintptr_t)d_points % sizeof(sgm_point) != 0 || !cloud_ready(s, spec, d_points, &c, &d_disp)) return false;
+    return cloud_points_queue(s, &c, d_disp, d_mask, d_conf, d_points, d_offsets);
+}
+
+bool sgm_read_cloud(sgm_instance* s, const sgm_cloud_spec* spec, sgm_point* points, size_t capacity, uint32_t* offsets)
+{
+    sgmd_cloud c;
+    const float* d_disp = NULL;
+    if (!offsets || (!points && capacity) || !cloud_ready(s, spec, offsets, &c, &d_disp)) return false;
+    if (!sgm_match_wait(s)) return false;
+    const size_t px = (size_t)c.B * c.W * c.H, off_bytes = ((size_t)c.B + 1) * sizeof(uint32_t);
+    const buf_request bufs[] = {{&s->d_cloud_points, px * sizeof(sgm_point), 0}, {&s->d_cloud_offsets, off_bytes, 0}};
+    if (!reserve_all(s, bufs, 2, 0)) FAIL("device allocation failed for the point list of %d frames of %dx%d", c.B, c.W, c.H);
+    if (!cloud_points_queue(s, &c, d_disp, NULL, NULL, s->d_cloud_points.p, s->d_cloud_offsets.p)) return false;
+    if (sgmd_d2h_async(s->device, s->stream, offsets, s->d_cloud_offsets.p, off_bytes) != 0 || sync_streams(s) != 0) return false;
+    const size_t total = offsets[c.B];
+    if (total > capacity) return false;                          /* the caller sizes a buffer from offsets[frames] and calls again */
+    if (total == 0) return true;
+    return sgmd_d2h_async(s->device, s->stream, points, s->d_cloud_points.p, total * sizeof(sgm_point)) == 0 && sync_streams(s) == 0;
+}
+
 /* ------------------------------------------------------------------ hole filling of any map (extension) */
 
 bool sgm_fill_holes(sgm_instance* s, float* d_disp, const uint8_t* d_class)
@@ -2177,6 +2286,11 @@ void SGM_Shutdown(void)
 size_t SGM_ReadStage(int which, void* host_out, size_t capacity)
 {
     return g_default ? sgm_read_stage(g_default, which, host_out, capacity) : 0;
+}
+
+bool SGM_ReadCloud(const sgm_cloud_spec* spec, sgm_point* points, size_t capacity, uint32_t* offsets)
+{
+    return g_default ? sgm_read_cloud(g_default, spec, points, capacity, offsets) : false;
 }
 
 void SGM_KeepStages(int enable)

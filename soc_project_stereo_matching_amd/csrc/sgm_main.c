@@ -22,6 +22,10 @@
  *            [--rectify CALIB.txt]   extension: LEFT and RIGHT are raw camera images, rectified on the device ahead of the match
  *                             (SGM_SetRectify) through the maps of the 64 numbers in CALIB.txt (sgm_calib.h)
  *            [--rectified-out LEFT.pgm RIGHT.pgm]   with --rectify: the two rectified images the match ran on
+ *            [--cloud OUT.ply --pinhole FX,FY,CX,CY,BASELINE,DOFFS [--cloud-z-max Z]]   extension: the valid pixels of OUT's map as
+ *                             3-D points (SGM_ReadCloud), a binary little-endian PLY with x y z float and red green blue uchar,
+ *                             the colour being the grey at the point's pixel of the image the map belongs to: LEFT (RIGHT with
+ *                             --right-reference), the rectified one with --rectify
  *   sgm_main --convert IN OUT.png        (image I/O only, no GPU: used by the CPU tests)
  */
 #define _POSIX_C_SOURCE 200809L
@@ -83,6 +87,25 @@ static int write_map(const float* disp, int w, int h, const char* image, const c
     return rc;
 }
 
+/* the point list as a binary little-endian PLY: x y z float, red green blue uchar = the grey image's value at the point's pixel */
+static int write_ply(const char* path, const sgm_point* pts, size_t n, const uint8_t* gray, int w)
+{
+    FILE* f = fopen(path, "wb");
+    if (!f) return -1;
+    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+               "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n", n);
+    int rc = 0;
+    for (size_t i = 0; i < n && rc == 0; ++i) {
+        unsigned char rec[15];
+        const uint8_t g = gray[(size_t)(pts[i].pixel >> 16) * w + (pts[i].pixel & 0xFFFFu)];
+        memcpy(rec, &pts[i], 12);                                 /* (the hosts this builds for are little-endian) */
+        rec[12] = rec[13] = rec[14] = g;
+        if (fwrite(rec, 1, sizeof rec, f) != sizeof rec) rc = -1;
+    }
+    if (fclose(f) != 0) rc = -1;
+    return rc;
+}
+
 int main(int argc, char** argv)
 {
     if (argc == 4 && !strcmp(argv[1], "--convert")) {
@@ -116,6 +139,9 @@ int main(int argc, char** argv)
     const char* right_raw = NULL;
     const char* calib_path = NULL;
     const char* rect_out[2] = {NULL, NULL};
+    const char* cloud_path = NULL;
+    float pinhole[6], cloud_z_max = INFINITY;
+    int have_pinhole = 0;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
     int census_kind = SGM_CENSUS_CENTRE;
     float refine_lambda = SGM_REFINE_DEFAULT_LAMBDA, refine_sigma = SGM_REFINE_DEFAULT_SIGMA;
@@ -139,6 +165,16 @@ int main(int argc, char** argv)
         else if (v && !strcmp(a, "--right-raw")) { right_raw = v; ++i; }
         else if (v && !strcmp(a, "--rectify")) { calib_path = v; ++i; }
         else if (i + 2 < argc && !strcmp(a, "--rectified-out")) { rect_out[0] = argv[i + 1]; rect_out[1] = argv[i + 2]; i += 2; }
+        else if (v && !strcmp(a, "--cloud")) { cloud_path = v; ++i; }
+        else if (v && !strcmp(a, "--pinhole")) {
+            if (sscanf(v, "%f,%f,%f,%f,%f,%f", &pinhole[0], &pinhole[1], &pinhole[2], &pinhole[3], &pinhole[4], &pinhole[5]) != 6) {
+                fprintf(stderr, "--pinhole wants FX,FY,CX,CY,BASELINE,DOFFS\n");
+                return 2;
+            }
+            have_pinhole = 1;
+            ++i;
+        }
+        else if (v && !strcmp(a, "--cloud-z-max")) { cloud_z_max = (float)atof(v); ++i; }
         else if (v && !strcmp(a, "--repeat")) { repeat = atoi(v); ++i; }
         else if (v && !strcmp(a, "--device")) { device = atoi(v); ++i; }
         else if (v && !strcmp(a, "--paths")) { opt.num_paths = (uint8_t)atoi(v); SGM_SetHonorNumPaths(1); ++i; }
@@ -170,6 +206,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (rect_out[0] && !calib_path) { fprintf(stderr, "--rectified-out needs --rectify\n"); return 2; }
+    if (cloud_path && !have_pinhole) { fprintf(stderr, "--cloud needs --pinhole FX,FY,CX,CY,BASELINE,DOFFS\n"); return 2; }
 
     int w1, h1, w2, h2;
     uint8_t* left = sgm_load_gray(argv[1], &w1, &h1);
@@ -223,6 +260,31 @@ int main(int argc, char** argv)
         uint8_t* img = (uint8_t*)malloc(px);
         if (!img || SGM_ReadStage(19 + v, img, px) != px || sgm_write_pgm(rect_out[v], img, w1, h1) != 0) rc = -1;
         free(img);
+    }
+    if (cloud_path) {                                             /* sized from a first call, which copies the offsets alone */
+        const sgm_cloud_spec spec = {w1, h1, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], pinhole[4], pinhole[5], 0.0f, cloud_z_max, 0};
+        uint32_t offsets[2] = {0, 0};
+        sgm_point* pts = NULL;
+        bool ok = SGM_ReadCloud(&spec, NULL, 0, offsets);
+        if (!ok && offsets[1] > 0) {
+            pts = (sgm_point*)malloc(sizeof(sgm_point) * offsets[1]);
+            ok = pts && SGM_ReadCloud(&spec, pts, offsets[1], offsets);
+        }
+        if (!ok) { printf("point cloud unavailable or --pinhole / --cloud-z-max out of range\n"); rc = -1; }
+        else {
+            printf("cloud: %u points\n", offsets[1]);
+            /* the image the map's pixels are those of: the reference view's, as the match saw it (stage 19 / 20 with --rectify) */
+            const size_t px = (size_t)w1 * h1;
+            const uint8_t* grey = right_ref ? right : left;
+            uint8_t* rect = NULL;
+            if (calib_path) {
+                rect = (uint8_t*)malloc(px);
+                grey = (rect && SGM_ReadStage(19 + right_ref, rect, px) == px) ? rect : NULL;
+            }
+            if (!grey || write_ply(cloud_path, pts, offsets[1], grey, w1) != 0) rc = -1;
+            free(rect);
+        }
+        free(pts);
     }
     SGM_Shutdown();
     free(disp); free(disp_r); free(conf); free(left); free(right);

@@ -49,6 +49,26 @@ class SGMOption(C.Structure):
     ]
 
 
+class SGMCloudSpec(C.Structure):
+    """Field-for-field sgm_cloud_spec of include/sgm_mi355x.h: 48 bytes, every field 4 bytes."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("frames", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("baseline", C.c_float), ("doffs", C.c_float),
+        ("z_min", C.c_float), ("z_max", C.c_float),
+        ("min_conf", C.c_uint32),
+    ]
+
+
+# sgm_point of include/sgm_mi355x.h: 16 bytes, pixel = (y << 16) | x
+POINT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32), ("pixel", np.uint32)])
+
+
+def cloud_spec(width, height, fx, fy, cx, cy, baseline, doffs=0.0, frames=1, z_min=0.0, z_max=float("inf"), min_conf=0) -> SGMCloudSpec:
+    """A sgm_cloud_spec; the defaults keep every pixel with a finite positive depth."""
+    return SGMCloudSpec(int(width), int(height), int(frames), fx, fy, cx, cy, baseline, doffs, z_min, z_max, int(min_conf))
+
+
 def default_option(max_disparity=64, min_disparity=0, **kw) -> SGMOption:
     """The option values the reference's driver sets (main.c:48-65), with overrides."""
     o = SGMOption()
@@ -172,6 +192,17 @@ def _load() -> C.CDLL:
         L.sgm_rectify.restype = C.c_bool
         L.sgm_rectify_maps.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.sgm_rectify_maps.restype = C.c_bool
+    if hasattr(L, "sgm_cloud_points"):        # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_cloud_organized.argtypes = [C.c_void_p] * 6
+        L.sgm_cloud_organized.restype = C.c_bool
+        L.sgm_cloud_points.argtypes = [C.c_void_p] * 7
+        L.sgm_cloud_points.restype = C.c_bool
+        L.sgm_read_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sgm_read_cloud.restype = C.c_bool
+        L.SGM_ReadCloud.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.SGM_ReadCloud.restype = C.c_bool
+        L.sgm_rectify_valid_mask.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sgm_rectify_valid_mask.restype = C.c_bool
     L.sgm_set_batch.argtypes = [C.c_void_p, C.c_int]
     L.sgm_set_batch.restype = C.c_bool
     L.sgm_select_frame.argtypes = [C.c_void_p, C.c_int]
@@ -283,6 +314,34 @@ def rectify_maps(K, dist, R, Knew, width, height):
                                            map_y.ctypes.data):
         raise ValueError("sgm_rectify_maps: a size below 1 or a singular Knew R")
     return map_x, map_y
+
+
+def rectify_valid_mask(map_x, map_y):
+    """sgm_rectify_valid_mask: uint8 [H][W], 1 where all four taps of SGM_SetRectify's sampling of that output pixel fall inside
+    the source image (host only; one camera's maps)."""
+    mx, my = np.ascontiguousarray(map_x, np.float32), np.ascontiguousarray(map_y, np.float32)
+    if mx.ndim != 2 or mx.shape != my.shape:
+        raise ValueError("rectify_valid_mask: two float32 maps of one shape [H][W] are needed")
+    h, w = mx.shape
+    mask = np.empty((h, w), np.uint8)
+    if not load_library().sgm_rectify_valid_mask(w, h, mx.ctypes.data, my.ctypes.data, mask.ctypes.data):
+        raise ValueError("sgm_rectify_valid_mask: a size below 1")
+    return mask
+
+
+def _read_cloud(call, spec):
+    """(points, offsets) through a sgm_read_cloud-shaped call(spec, points, capacity, offsets): sized from a first call that copies
+    the offsets alone; None where the C call refuses the spec."""
+    offsets = np.zeros(max(int(spec.frames), 0) + 1, np.uint32)
+    if call(C.byref(spec), None, 0, offsets.ctypes.data):
+        return np.empty(0, POINT_DTYPE), offsets                  # an empty cloud
+    total = int(offsets[-1])
+    if total == 0:
+        return None
+    points = np.empty(total, POINT_DTYPE)
+    if not call(C.byref(spec), points.ctypes.data, total, offsets.ctypes.data):
+        return None
+    return points, offsets
 
 
 def _rectify_args(maps):
@@ -472,6 +531,11 @@ class SGM(_StageReader):
 
     def synchronize(self) -> bool:
         return bool(self.lib.SGM_Synchronize())
+
+    def read_cloud(self, spec: SGMCloudSpec):
+        """SGM_ReadCloud: (points as POINT_DTYPE records, offsets uint32 [frames + 1]) of the last match's final map, or None
+        where the C call returns false.  The contract is in include/sgm_mi355x.h (sgm_cloud_spec)."""
+        return _read_cloud(self.lib.SGM_ReadCloud, spec)
 
     def shutdown(self):
         self.lib.SGM_Shutdown()
@@ -795,6 +859,23 @@ class SGMInstance(_StageReader):
         """sgm_depth_from_both: the left map's depth where finite, else the right map's at the same pixel (device pointers)."""
         return bool(self.lib.sgm_depth_from_both(self.handle, d_disp_left, d_disp_right, count, fx_left, fx_right, baseline, doffs,
                                                  d_depth))
+
+    # ---- point clouds (include/sgm_mi355x.h, sgm_cloud_spec); device pointers as ints, None = NULL ----
+    def cloud_organized(self, spec: SGMCloudSpec, d_disp, d_mask, d_conf, d_xyz: int) -> bool:
+        """sgm_cloud_organized: float32 [frames][H][W][3], X Y Z of the kept pixels and NaN elsewhere.  d_disp None: the final map
+        of the last match; d_mask (uint8) / d_conf (uint16) None: no such test.  Asynchronous on `stream`."""
+        return bool(self.lib.sgm_cloud_organized(self.handle, C.byref(spec), d_disp or None, d_mask or None, d_conf or None, d_xyz))
+
+    def cloud_points(self, spec: SGMCloudSpec, d_disp, d_mask, d_conf, d_points: int, d_offsets: int) -> bool:
+        """sgm_cloud_points: the kept pixels as 16-byte records in raster order (room for frames * H * W of them) and
+        uint32 offsets [frames + 1].  Arguments as cloud_organized.  Asynchronous on `stream`."""
+        return bool(self.lib.sgm_cloud_points(self.handle, C.byref(spec), d_disp or None, d_mask or None, d_conf or None, d_points,
+                                              d_offsets))
+
+    def read_cloud(self, spec: SGMCloudSpec):
+        """sgm_read_cloud: (points as POINT_DTYPE records, offsets uint32 [frames + 1]) of the last match's final map, no mask,
+        no confidence; blocking.  None where the C call returns false."""
+        return _read_cloud(lambda *a: self.lib.sgm_read_cloud(self.handle, *a), spec)
 
     def compare_depth(self, d_ground_truth: int, d_test: int, count: int, abs_thresh: float = 10.0):
         """(rmse, bad_pixel_rate, n_valid) of two device depth images; None where the C call returns false."""
