@@ -1,7 +1,9 @@
 // sgm_common.hpp -- shared by the HIP translation units of libsgm_mi355x.so (see sgm_device.h for the C interface).
 // Hand-written gfx950 (CDNA4, wave64) kernels of the SGM hot path, one translation unit per stage:
-//   sgm_census.hip  sgm_aggregate.hip  sgm_sum_wta.hip  sgm_post.hip (speckle, median)  sgm_runtime.hip  No MFMA: the path is integer min-plus and
-// byte streaming, bounded by HBM bandwidth and by the length of the serial path recurrences.
+//   sgm_runtime.hip  sgm_rectify.hip  sgm_census.hip  sgm_aggregate.hip + sgm_aggregate_fast.hip + sgm_aggregate_generic.hip (over
+//   sgm_aggregate_impl.hpp)  sgm_sum_wta.hip + sgm_upsum.hip (the fused last sweep; both over sgm_wta.hpp, the winner-take-all)
+//   sgm_post.hip (speckle, median)  sgm_fill.hip  sgm_refine.hip  sgm_cloud.hip
+// No MFMA: the path is integer min-plus and byte streaming, bounded by HBM bandwidth and by the length of the serial path recurrences.
 //
 // Data layout in HBM (all row-major, disparity fastest, Dp = padded disparity stride):
 //   census  u32 [H][W]            cost   u8  [H][W][Dp]
@@ -183,54 +185,4 @@ static __device__ __forceinline__ void pack_cells(const us2 (&pr)[DPL / 2], Cell
         for (int k = 0; k < DPL / 4; ++k)
             v.w[k] = __builtin_amdgcn_perm(as_u(pr[2 * k + 1]), as_u(pr[2 * k]), 0x06040200u);
     }
-}
-
-
-// ============================================================================================
-// S = [S +] sum over directions of L_r (+ the second visits of the anomalous lines)
-// ============================================================================================
-
-struct WtaState {
-    unsigned m1, m2;   // smallest cost (lowest d wins ties, ref :390) and smallest among the others (ref :413-419)
-    int d1;            // index (d - dmin) of m1, -1 if nothing beat 65535
-    unsigned c1, c2;   // cost_local[best-1], cost_local[best+1] (ref :432-435)
-    unsigned pv;       // cost of the previous index
-    bool want_next;
-};
-
-static __device__ __forceinline__ void wta_feed(WtaState& s, unsigned v, int di)
-{
-    if (s.want_next) { s.c2 = v; s.want_next = false; }
-    if (v < s.m1) {
-        s.m2 = s.m1; s.m1 = v; s.d1 = di; s.c1 = s.pv; s.want_next = true; s.c2 = 0xFFFFu;
-    } else if (v < s.m2) {
-        s.m2 = v;
-    }
-    s.pv = v;
-}
-
-static __device__ __forceinline__ float wta_finish(const WtaState& s, int D, int dmin, int check_unique,
-                                                   float one_minus_ratio)
-{
-    const float inf = __builtin_inff();
-    if (s.d1 < 0) return inf;                             // no candidate at all (see oracle/sgm_oracle.c sgmo_wta)
-    if (check_unique) {                                   // ref :412-426 (Q10)
-        const unsigned margin = (unsigned)(unsigned short)(int)((float)s.m1 * one_minus_ratio);
-        if ((int)s.m2 - (int)s.m1 <= (int)margin) return inf;
-    }
-    if (s.d1 == 0 || s.d1 == D - 1) return inf;          // ref :428
-    const int c1 = (int)(short)s.c1, c2 = (int)(short)s.c2;       // (int16_t) casts, 65535 -> -1 (Q11b)
-    int denom = (int)(short)(c1 + c2 - 2 * (int)s.m1);
-    if (denom < 1) denom = 1;
-    return (float)(s.d1 + dmin) + (float)(c1 - c2) / ((float)denom * 2.0f);     // ref :440
-}
-
-// OR over the 16 lanes of a DPP row, result in every lane
-static __device__ __forceinline__ unsigned row_allor(unsigned v)
-{
-    v |= dpp_perm<DPP_QUAD_XOR1>(v);
-    v |= dpp_perm<DPP_QUAD_XOR2>(v);
-    v |= dpp_perm<DPP_ROW_HALF_MIRROR>(v);
-    v |= dpp_perm<DPP_ROW_MIRROR>(v);
-    return v;
 }

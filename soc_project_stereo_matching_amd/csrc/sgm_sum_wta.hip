@@ -1,19 +1,12 @@
-#include "sgm_common.hpp"
+#include "sgm_wta.hpp"
 
 
 // S = [S +] sum of the L_r planes (+ second visits of the anomalous lines), and -- while the 16 lanes of a
 // pixel still hold its S vector in registers -- the LEFT-view winner-take-all (ref :374-443 with
 // inverse == 0).  16 lanes per pixel, DPL disparities per lane; the kernel is HBM-bound (it streams the 8
 // planes once), so the WTA arithmetic rides along for free.
-//   key = S << 16 | d: the row-wide minimum key is the first minimum the reference's strict '>' finds.
 // CONF (extension, sgm_match_confidence): the lane that finishes a pixel also stores its matching confidence to conf
 // (u16 [B][H][W]); the CONF = false instantiations never touch conf.
-
-// matching confidence from the best and runner-up cost (include/sgm_mi355x.h): 0 for a tie or no candidate; one u32 divide
-static __device__ __forceinline__ uint16_t conf_value(unsigned m1, unsigned m2)
-{
-    return m2 == 0u ? (uint16_t)0 : (uint16_t)(((m2 - m1) * 65535u) / m2);
-}
 
 template <int DPL, bool CONF = false>
 __global__ __launch_bounds__(256) void sgm_sum_wta_k(const uint8_t* __restrict__ planes, size_t plane_bytes, int ndirs,
@@ -74,11 +67,8 @@ __global__ __launch_bounds__(256) void sgm_sum_wta_k(const uint8_t* __restrict__
         key[i] = (idx < D) ? (((acc[i] & 0xFFFFu) << 16) | (unsigned)idx) : 0xFFFFFFFFu;
         kmin = min(kmin, key[i]);
     }
-    const unsigned kbest = row_allmin<16>(kmin);
-    unsigned k2 = 0xFFFFFFFFu;
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) k2 = min(k2, key[i] == kbest ? 0xFFFFFFFFu : key[i]);
-    const unsigned ksecond = row_allmin<16>(k2);
+    unsigned kbest, ksecond;
+    wta_best2<DPL, 16>(key, kmin, kbest, ksecond);
     const int dbest = (int)(kbest & 0xFFFFu);
     unsigned nb = 0;                                     // S[best-1] | S[best+1] << 16 (ref :432-435)
 #pragma unroll
@@ -95,7 +85,6 @@ __global__ __launch_bounds__(256) void sgm_sum_wta_k(const uint8_t* __restrict__
         st.d1 = (kbest == 0xFFFFFFFFu) ? -1 : dbest;
         st.c1 = nb & 0xFFFFu;
         st.c2 = nb >> 16;
-        st.pv = 0; st.want_next = false;
         disp_l[(size_t)row * W + x] = wta_finish(st, D, dmin, check_unique, one_minus_ratio);
         if constexpr (CONF) conf[(size_t)blockIdx.z * W * H + (size_t)row * W + x] = conf_value(st.m1, st.m2);
     }
@@ -112,9 +101,6 @@ __global__ __launch_bounds__(256) void sgm_sum_wta_k(const uint8_t* __restrict__
 //   ring: u16 [R][LD], R = Dp + 32 columns, LD = Dp + 2 (odd dword stride); entries of columns >= W and of
 //   padding disparities hold 65535 = the reference's "off the image" cost (ref :407).
 // ============================================================================================
-// a * b + c for a, b < 2^24: v_mad_u32_u24 (half rate); hipcc turns the plain 32-bit form into v_mad_u64_u32 / v_mul_lo_u32
-static __device__ __forceinline__ unsigned umad24(unsigned a, unsigned b, unsigned c) { return __umul24(a, b) + c; }
-
 template <int DPL, int STAGE>
 static __device__ __forceinline__ void sumlr_prefetch(CellVec<DPL> (&pre)[2][8], const uint8_t* const (&pb)[8], unsigned off)
 {
@@ -210,9 +196,8 @@ __global__ __launch_bounds__(THREADS) void sgm_sum_wta_lr_k(const uint8_t* __res
 
     int slot = px;                                                       // ring slot of this thread's column: x mod R
 
-    // Both views end in ONE wta_finish per iteration (uniqueness test, float divide of the sub-pixel term: ~35
-    // instructions a wave pays in full even for a single active lane): lane 0 of a pixel finishes the left view,
-    // lane 1 the right view.  kl/ks = best and runner-up key of the left view of column x (ignored unless `left`).
+    // the right view of the diagonal that ends in this iteration's column x, then both views' finish (sgm_wta.hpp).
+    // kl/ks = best and runner-up key of the left view of column x (ignored unless `left`).
     auto finish_views = [&](int x, bool left, unsigned kl, unsigned ks) {
         unsigned kbest_r = 0, ksecond_r = 0;
         int base = 0;
@@ -221,60 +206,18 @@ __global__ __launch_bounds__(THREADS) void sgm_sum_wta_lr_k(const uint8_t* __res
         __syncthreads();                                                 // the new columns are in the ring
         base = slot + R - (D - 1);                                       // ring slot of column xr + dmin = x - (D-1)
         if (base >= R) base -= R;
-        unsigned key[DPL], val[DPL];
-        unsigned kmin = 0xFFFFFFFFu;
+        unsigned key[DPL];
         int first = base + sub * DPL;                                    // slot of this lane's first disparity; the others follow (mirror)
         if (first >= R) first -= R;
-        const unsigned short* const diag = &ring[umad24((unsigned)first, (unsigned)LD, (unsigned)(sub * DPL))];
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) val[i] = diag[i * (LD + 1)];      // padding disparities and columns past the image hold 65535
-        if (D == Dp) {                                                   // wave-uniform: no padding disparities, every slot read was written
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) {
-                key[i] = (val[i] << 16) | (unsigned)(sub * DPL + i);
-                kmin = min(kmin, key[i]);
-            }
-        } else {                                                         // padding disparities reach into slots ahead of the newest column
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) {
-                const int k = sub * DPL + i;
-                key[i] = (k < D) ? ((val[i] << 16) | (unsigned)k) : 0xFFFFFFFFu;
-                kmin = min(kmin, key[i]);
-            }
+        const unsigned kmin = wta_diag_keys<DPL>(&ring[umad24((unsigned)first, (unsigned)LD, (unsigned)(sub * DPL))], LD, sub, D, D != Dp, key);
+        wta_best2<DPL, 16>(key, kmin, kbest_r, ksecond_r);
         }
-        const unsigned kbest = row_allmin<16>(kmin);
-        // runner-up: keys are distinct (they carry d), so key - kbest - 1 (mod 2^32) sends the best to the top
-        // and keeps the order of all others
-        const unsigned nbest = ~kbest;
-        unsigned k2 = 0xFFFFFFFFu;
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) k2 = min(k2, key[i] + nbest);
-        kbest_r = kbest;
-        ksecond_r = row_allmin<16>(k2) + kbest + 1;
-        }
-        const bool is_r = (sub == 1);
-        const bool active = is_r ? (do_right && xr >= xa && xr < xb) : (sub == 0 && left);
-        if (active) {
-            const unsigned kb = is_r ? kbest_r : kl, k2nd = is_r ? ksecond_r : ks;
-            const int dbest = (int)(kb & 0xFFFFu);
-            // S[best-1], S[best+1] straight from the ring: the column's own slot for the left view, the diagonal for
-            // the right one (a best at either end of the range is invalid anyway, ref :428: clamp, value unused)
-            const int km = max(dbest - 1, 0), kp = min(dbest + 1, Dp - 1);
-            int sm = base + km, sp = base + kp;
-            if (sm >= R) sm -= R;
-            if (sp >= R) sp -= R;
-            if (!is_r) sm = sp = slot;
-            WtaState st;
-            st.m1 = kb >> 16;
-            st.m2 = k2nd >> 16;
-            st.d1 = (is_r && (kb >> 16) == 0xFFFFu) ? -1 : dbest;        // right view: nothing beat 65535 (ref :381, strict '>')
-            st.c1 = ring[umad24((unsigned)sm, (unsigned)LD, (unsigned)km)];
-            st.c2 = ring[umad24((unsigned)sp, (unsigned)LD, (unsigned)kp)];
-            st.pv = 0; st.want_next = false;
-            float* const out = is_r ? disp_r + xr : disp_l + x;
-            out[(size_t)row * W] = wta_finish(st, D, dmin, check_unique, one_minus_ratio);
+        const WtaViews v = wta_views(ring, R, LD, sub, slot, base, kl, ks, kbest_r, ksecond_r, left, do_right && xr >= xa && xr < xb, Dp);
+        if (v.active) {
+            float* const out = v.is_r ? disp_r + xr : disp_l + x;
+            out[(size_t)row * W] = wta_finish(v.st, D, dmin, check_unique, one_minus_ratio);
             if constexpr (CONF) {
-                if (is_r == (conf_right != 0)) conf[(size_t)row * W + (is_r ? xr : x)] = conf_value(st.m1, st.m2);
+                if (v.is_r == (conf_right != 0)) conf[(size_t)row * W + (v.is_r ? xr : x)] = conf_value(v.st.m1, v.st.m2);
             }
         }
         if (TIGHT && do_right) __syncthreads();                          // every diagonal of this iteration has been read
@@ -369,23 +312,10 @@ __global__ __launch_bounds__(THREADS) void sgm_sum_wta_lr_k(const uint8_t* __res
                 for (int m = 0; m < NPAIR; ++m) dst[(R * LD) / 2 + m] = pr[m];
             }
         }
-        // ---- left-view WTA over the 16 lanes of the pixel (as in sgm_sum_wta_k); padding disparities carry 65535,
-        //      so their keys lose against every real one ----
-        unsigned key[DPL];
-        unsigned kmin = 0xFFFFFFFFu;
-#pragma unroll
-        for (int m = 0; m < NPAIR; ++m) {
-            const unsigned idx = (unsigned)(sub * DPL + 2 * m);
-            key[2 * m] = (pr[m] << 16) | idx;
-            key[2 * m + 1] = (pr[m] & 0xFFFF0000u) | (idx + 1);
-            kmin = min(kmin, min(key[2 * m], key[2 * m + 1]));
-        }
-        const unsigned kbest = row_allmin<16>(kmin);
-        const unsigned nbest = ~kbest;                                   // runner-up as in right_view()
-        unsigned k2 = 0xFFFFFFFFu;
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) k2 = min(k2, key[i] + nbest);
-        const unsigned ksecond = row_allmin<16>(k2) + kbest + 1;
+        // ---- left-view WTA over the 16 lanes of the pixel ----
+        unsigned key[DPL], kbest, ksecond;
+        const unsigned kmin = wta_pair_keys<DPL>(pr, sub, key);
+        wta_best2<DPL, 16>(key, kmin, kbest, ksecond);
         asm volatile("" ::: "memory");                                   // the wave's ring writes above stay above
         finish_views(x, mine, kbest, ksecond);
         next_slot();

@@ -1,4 +1,5 @@
 #include "sgm_aggregate_impl.hpp"
+#include "sgm_wta.hpp"
 
 // ============================================================================================
 // The LAST vertical sweep fused with the cost sum and both winner-take-all passes.
@@ -56,8 +57,6 @@ struct UpArgs {
 #define UPSUM_MAX_EXTRA 8
 #define UPSUM_XC 36            // columns of an exchange ring (34 are live at any time)
 #define UPSUM_POLL_LIMIT (1u << 22)
-
-static __device__ __forceinline__ unsigned up_umad24(unsigned a, unsigned b, unsigned c) { return __umul24(a, b) + c; }
 
 // One step of one direction with the matching cost already packed (shared by the three directions of a pixel): the
 // non-negative-P1 step of agg_step_nn -- L(d) = C(d) + min(min(Lp(d), Lp(d-1)+P1, Lp(d+1)+P1) - min_prev, P2') (ref :329-343) --
@@ -458,7 +457,7 @@ __global__ __launch_bounds__(R * 16 * LPP + 64) void sgm_upsum_k(const UpArgs a)
         }
         // ---- this column's S vector into the ring ----
         {
-            unsigned* dst = reinterpret_cast<unsigned*>(&ring[t][up_umad24((unsigned)slot, (unsigned)LD, (unsigned)(sub * DPL))]);
+            unsigned* dst = reinterpret_cast<unsigned*>(&ring[t][umad24((unsigned)slot, (unsigned)LD, (unsigned)(sub * DPL))]);
 #pragma unroll
             for (int m = 0; m < NP; ++m) dst[m] = pr[m];
             if (slot < MIR) {
@@ -467,23 +466,9 @@ __global__ __launch_bounds__(R * 16 * LPP + 64) void sgm_upsum_k(const UpArgs a)
             }
         }
         // ---- left-view WTA over the 16 lanes of the pixel ----
-        unsigned key[DPL];
-        unsigned kmin = 0xFFFFFFFFu;
-#pragma unroll
-        for (int m = 0; m < NP; ++m) {
-            const unsigned idx = (unsigned)(sub * DPL + 2 * m);
-            key[2 * m] = (pr[m] << 16) | idx;
-            key[2 * m + 1] = (pr[m] & 0xFFFF0000u) | (idx + 1);
-            kmin = min(kmin, min(key[2 * m], key[2 * m + 1]));
-        }
-        const unsigned kbest_l = row_allmin<LPP>(kmin);
-        unsigned k2 = 0xFFFFFFFFu;
-        {
-            const unsigned nbest = ~kbest_l;
-#pragma unroll
-            for (int q = 0; q < DPL; ++q) k2 = min(k2, key[q] + nbest);
-        }
-        const unsigned ksecond_l = row_allmin<LPP>(k2) + kbest_l + 1;
+        unsigned key[DPL], kbest_l, ksecond_l;
+        const unsigned kmin = wta_pair_keys<DPL>(pr, sub, key);
+        wta_best2<DPL, LPP>(key, kmin, kbest_l, ksecond_l);
 
         const unsigned long long c1_ = tr ? __builtin_amdgcn_s_memtime() : 0;
         __syncthreads();                                                 // A: ring columns, exchange cells and the helper's poll are done
@@ -499,48 +484,16 @@ __global__ __launch_bounds__(R * 16 * LPP + 64) void sgm_upsum_k(const UpArgs a)
         if (a.do_right) {
             base = slot + RC - (D - 1);
             if (base >= RC) base -= RC;
-            unsigned val[DPL];
             int first = base + sub * DPL;
             if (first >= RC) first -= RC;
-            const unsigned short* const diag = &ring[t][up_umad24((unsigned)first, (unsigned)LD, (unsigned)(sub * DPL))];
-#pragma unroll
-            for (int q = 0; q < DPL; ++q) val[q] = diag[q * (LD + 1)];
-            unsigned km = 0xFFFFFFFFu;
-#pragma unroll
-            for (int q = 0; q < DPL; ++q) {
-                const int kk = sub * DPL + q;
-                key[q] = (!PAD || kk < D) ? ((val[q] << 16) | (unsigned)kk) : 0xFFFFFFFFu;
-                km = min(km, key[q]);
-            }
-            const unsigned kb = row_allmin<LPP>(km);
-            const unsigned nb = ~kb;
-            unsigned k3 = 0xFFFFFFFFu;
-#pragma unroll
-            for (int q = 0; q < DPL; ++q) k3 = min(k3, key[q] + nb);
-            kbest_r = kb;
-            ksecond_r = row_allmin<LPP>(k3) + kb + 1;
+            const unsigned km = wta_diag_keys<DPL>(&ring[t][umad24((unsigned)first, (unsigned)LD, (unsigned)(sub * DPL))], LD, sub, D, PAD, key);
+            wta_best2<DPL, LPP>(key, km, kbest_r, ksecond_r);
         }
-        {
-            const bool is_r = (sub == 1);
-            const bool active = is_r ? (a.do_right && row_ok && xr >= 0 && xr < W) : (sub == 0 && inside);
-            if (active) {
-                const unsigned kb = is_r ? kbest_r : kbest_l, k2nd = is_r ? ksecond_r : ksecond_l;
-                const int dbest = (int)(kb & 0xFFFFu);
-                const int km = max(dbest - 1, 0), kp = min(dbest + 1, Dp - 1);
-                int sm = base + km, sp = base + kp;
-                if (sm >= RC) sm -= RC;
-                if (sp >= RC) sp -= RC;
-                if (!is_r) sm = sp = slot;
-                WtaState st;
-                st.m1 = kb >> 16;
-                st.m2 = k2nd >> 16;
-                st.d1 = (is_r && (kb >> 16) == 0xFFFFu) ? -1 : dbest;
-                st.c1 = ring[t][up_umad24((unsigned)sm, (unsigned)LD, (unsigned)km)];
-                st.c2 = ring[t][up_umad24((unsigned)sp, (unsigned)LD, (unsigned)kp)];
-                st.pv = 0; st.want_next = false;
-                float* const out = is_r ? disp_r + xr : disp_l + x;
-                *out = wta_finish(st, D, dmin, a.check_unique, a.one_minus_ratio);
-            }
+        const WtaViews v = wta_views(ring[t], RC, LD, sub, slot, base, kbest_l, ksecond_l, kbest_r, ksecond_r, inside,
+                                     a.do_right && row_ok && xr >= 0 && xr < W, Dp);
+        if (v.active) {
+            float* const out = v.is_r ? disp_r + xr : disp_l + x;
+            *out = wta_finish(v.st, D, dmin, a.check_unique, a.one_minus_ratio);
         }
         // The top team's hand-over stores were issued before barrier A; behind them this wave has issued at least 14 loads (fetch_row:
         // >= 7, fetch_planes: 7).  Vector-memory operations complete in issue order, so once at most 12 are outstanding the stores

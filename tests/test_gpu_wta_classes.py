@@ -1,4 +1,4 @@
-"""Every copy of the winner-take-all on the planted inputs of tests/wta_classes.py -- needs an MI355X.  Those inputs make the top
+"""Every caller of the winner-take-all on the planted inputs of tests/wta_classes.py -- needs an MI355X.  Those inputs make the top
 index of every layout the winner, put 65535 beside an interior best and take the denominator's clamp on hundreds of pixels
 (test_wta_classes_cpu.py has the counts and pins the oracle on them against the reference's own C).  Bit-exact, tolerance 0, against
 the CPU oracle: the separate sum / right-view kernels, the fused row kernel plain, storing S (keep_stages), accumulating (a second

@@ -73,9 +73,8 @@ def main():
         with open(os.path.join(d, "log.txt"), "w") as log:
             rc = subprocess.call(cmd, env=e, stdout=log, stderr=subprocess.STDOUT, timeout=600)
         found = [os.path.join(r, f) for r, _, fs in os.walk(d) for f in fs if f.endswith("counter_collection.csv")]
-        if rc != 0 or not found:
-            print(f"  pass {tag} failed (rc {rc}); see {d}/log.txt", flush=True)
-            continue
+        if rc != 0 or not found:                       # no further pass on a GPU that may just have faulted
+            raise SystemExit(f"  pass {tag} failed (rc {rc}); see {d}/log.txt")
         pk = per_kernel(found[0])
         raw[tag] = {"frames_per_launch": batch, "env": env, "kernels": pk}
         for k, cs in pk.items():
