@@ -259,6 +259,34 @@ bool SGM_SetRectify(int width, int height, const float* map_lx, const float* map
 bool sgm_rectify_maps(const double K[9], const double dist[5], const double R[9], const double Knew[9], int width, int height,
                       float* map_x, float* map_y);
 
+/* Bits per image sample (extension, "parity unpinned by the reference", whose images are bytes; defined here and restated by
+ * tests/pixels16_ref.py).  Sensors deliver 10..16 bits; tone-mapping them to 8 before the match throws away what the census lives
+ * on, the order of neighbouring samples.  The census is a rank transform and needs no tone map: with bits in 9..16 it is evaluated
+ * on the samples as they are, and everything below it is the 8-bit pipeline unchanged.
+ * bits == 8 (default): every launch, buffer and result is exactly what it is without this call.  bits in 9..16 takes effect at the
+ * next SGM_Initialize / sgm_initialize / SGM_Reset / sgm_reset.  From then on EVERY image pointer of every match entry point --
+ * SGM_Match, sgm_compute, sgm_match[_async|_device], the _confidence* and _both* families, sgm_rectify (inputs and outputs) --
+ * refers to width * height uint16_t samples per frame: host byte order, row-major, stride = width, the [B] frames of sgm_set_batch
+ * back to back.  The parameter types stay const uint8_t*, so the ABI is unchanged: cast the pointer.  Device images must be 2-byte
+ * aligned and nothing more (the kernels read single samples; an odd address returns false and queues nothing).
+ *   1. Census: the formulas of the 5x5 centre census, of SGM_SetCensusKind(SGM_CENSUS_SYMMETRIC) and of the wide centre windows
+ *      (SGM_SetCensusWindow, u64 words), evaluated on the u16 samples as they are: the same strict <, bit order, zero borders and
+ *      "window does not fit -> all 0" rule.  Every word of the frame is written on every match (the default instance's stale-border
+ *      behaviour, SURVEY.md Q3, belongs to the 8-bit 5x5 centre census only).
+ *   2. Narrowed image, per view: g8 = min(v >> (bits - 8), 255).  A sample >= 2^bits is therefore defined: it saturates.  g8 is
+ *      what the adaptive-P2 lookup, the refinement's guide and every other reader of grey values see; it is written by the census
+ *      kernel and readable as stages 21 (left) and 22 (right), u8 [H][W] (0 bytes with 8-bit input).
+ *   3. Rectification (SGM_SetRectify): the same quantised maps, tap rule and constant-0 border on the u16 samples,
+ *      out = (... + 512) >> 10 in unsigned 32-bit arithmetic (1024 * 65535 + 512 < 2^32).  It runs before the census; stages 19 / 20
+ *      then hold u16 [H][W].
+ *   4. Everything downstream of the census words and g8 is untouched.  So a pair with v = u8 << (bits - 8) gives results
+ *      bit-identical to the 8-bit match of u8 -- every stage, every option, the confidence, both views, filled, refined, clouds.
+ *   5. Refused with more than 8 bits in effect (false, nothing queued, a message): row-tile mode (sgm_set_rows) at initialize /
+ *      reset; sgm_match_planes*, whose planes are bytes by protocol.  The opt-in fused last sweep (SGM_UPSUM) is simply not used.
+ * Returns false and changes nothing for any other bits, and for 9..16 in a build without the kernels.  The default instance
+ * remembers the setting across SGM_Shutdown, as it does the census window.  Timing: everything new counts toward "census". */
+bool SGM_SetPixelBits(int bits);
+
 /* Same as SGM_Match but all three pointers are DEVICE pointers (HBM-resident frames) on the
  * instance's device.  Asynchronous on the instance's stream; SGM_Synchronize waits. */
 bool SGM_MatchDevice(const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left);
@@ -283,6 +311,7 @@ void          sgm_set_honor_num_paths(sgm_instance* s, int honor);
 bool          sgm_set_census_window(sgm_instance* s, int width, int height);   /* see SGM_SetCensusWindow */
 bool          sgm_set_census_kind(sgm_instance* s, int kind);                  /* see SGM_SetCensusKind */
 void          sgm_set_reference_view(sgm_instance* s, int right);              /* see SGM_SetReferenceView */
+bool          sgm_set_pixel_bits(sgm_instance* s, int bits);                   /* see SGM_SetPixelBits */
 bool          sgm_set_fill_holes(sgm_instance* s, int enable);                 /* see SGM_SetFillHoles */
 bool          sgm_set_refine(sgm_instance* s, int enable, float lambda, float sigma, int iterations, int keep_invalid);  /* see SGM_SetRefine */
 bool          sgm_set_rectify(sgm_instance* s, int width, int height, const float* map_lx, const float* map_ly, const float* map_rx,
@@ -479,7 +508,7 @@ bool   sgm_refine_disparity(sgm_instance* s, float* d_disp, const uint16_t* d_co
 
 /* The remap of SGM_SetRectify on any device images: B frames of the instance's shape each, d_out_* = d_* sampled through the maps
  * in effect (those of the last initialize / reset).  No output may alias an input.  Asynchronous on sgm_stream(s).  false when no
- * maps are in effect. */
+ * maps are in effect.  With more than 8 bits per sample in effect (SGM_SetPixelBits) all four images are uint16_t. */
 bool   sgm_rectify(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, uint8_t* d_out_left, uint8_t* d_out_right);
 
 /* ---- a test-platform frame end to end (the data formats either side of the path) ----
@@ -504,7 +533,9 @@ bool   sgm_match_planes(sgm_instance* s, const uint8_t* planes, float fx, float 
  *        6 after LR check                 7 after speckle removal        8 final (all f32 [H][W])
  *        9 after hole filling (f32 [H][W]; needs sgm_keep_stages and filling on, SGM_SetFillHoles)
  *        18 hole-filling classes (u8 [H][W]; after any match with filling on)
- *        19 rectified left image         20 rectified right image       (u8 [H][W]; 0 bytes with rectification off, SGM_SetRectify)
+ *        19 rectified left image         20 rectified right image       (u8 [H][W]; 0 bytes with rectification off, SGM_SetRectify;
+ *                                                                        u16 [H][W] with more than 8 bits per sample, SGM_SetPixelBits)
+ *        21 narrowed left image          22 narrowed right image        (u8 [H][W]; 0 bytes with 8-bit input, SGM_SetPixelBits)
  *        10..17 per-direction path cost L_r of direction (which-10) (u8 [H][W][D]; cells the
  *               direction never visits read 0, cells visited twice hold the last-but-one visit)
  *        after a sgm_match_both (SGM_MatchBoth), where 4, 6, 7, 8 are the LEFT view's maps and 5 the raw right-view map:

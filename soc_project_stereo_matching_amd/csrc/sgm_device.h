@@ -228,6 +228,19 @@ int sgmd_refine_pass(int ord, void* stream, const sgmd_geom* g, int vertical, co
 int sgmd_remap(int ord, void* stream, const sgmd_geom* g, const void* maps, const void* left, const void* right, void* out_left,
                void* out_right);
 
+/* Extension (parity unpinned by the reference), images of 9..16 bits per sample (include/sgm_mi355x.h, SGM_SetPixelBits);
+ * sgm_pixels16.hip.  left / right (and the outputs of sgmd_remap16) are u16 [B][H][W], 2-byte aligned and nothing more.
+ * sgmd_census16: ONE launch for both views of all B frames, with the block grid of sgmd_census: the census of the u16 samples as they
+ * are -- symmetric != 0: the centre-symmetric census over cw x ch into u32 words (as sgmd_census_sym); else cw x ch == 5 x 5: the
+ * reference's centre census into u32 words (as sgmd_census, every word written); else the wide centre census into u64 words (as
+ * sgmd_census_window) -- and, beside it, the narrowed images g8 = min(v >> (bits - 8), 255), u8 [B][H][W], which every reader of
+ * grey values downstream takes.  sgmd_remap16: sgmd_remap on u16 samples (same maps, taps and rounding).  sgm_host.c references
+ * both weakly (a host built without them refuses more than 8 bits). */
+int sgmd_census16(int ord, void* stream, const sgmd_geom* g, int bits, int symmetric, int cw, int ch, const void* left,
+                  const void* right, void* census_l, void* census_r, void* g8_left, void* g8_right);
+int sgmd_remap16(int ord, void* stream, const sgmd_geom* g, const void* maps, const void* left, const void* right, void* out_left,
+                 void* out_right);
+
 /* in-place raster-order 3x3 median (the reference calls MedianFilter with in == out, .c:120).
  * scratch: sgmd_median_scratch_bytes(g) bytes for the pre-sorted neighbourhoods. */
 /* status: NULL, or an int in page-locked host memory (sgmd_alloc_pinned) that the chained kernel of tall frames sets to 1 when a

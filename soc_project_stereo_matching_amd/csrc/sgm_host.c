@@ -86,6 +86,8 @@ struct sgm_instance {
     int census_w, census_h;      /* census window (sgm_set_census_window); 0 = the reference's 5x5 */
     int census_kind;             /* SGM_CENSUS_CENTRE (reference) or SGM_CENSUS_SYMMETRIC (sgm_set_census_kind) */
     int reference_view;          /* 0 = left (reference), 1 = right (sgm_set_reference_view) */
+    int pixel_bits_req;          /* bits per image sample asked for (sgm_set_pixel_bits; 0 = never set = 8); takes effect at the next initialize */
+    int pixel_bits;              /* ... and in effect for this shape: 8 = u8 images (reference), 9..16 = u16 images */
     int fill_req;                /* hole filling asked for (sgm_set_fill_holes); takes effect at the next initialize */
     bool fill_on;                /* ... and in effect for this shape: the class map and the ping-pong map exist */
     int refine_req;              /* refinement asked for (sgm_set_refine); takes effect at the next initialize */
@@ -141,7 +143,10 @@ struct sgm_instance {
     int rect_w, rect_h;
     bool rect_dirty;                     /* the device copy is not (or no longer) that of rect_q */
     bool rect_on;                        /* ... and in effect for this shape: every match rectifies its images first */
-    sgm_buf d_rect_maps, d_rect_l, d_rect_r;   /* the maps; the rectified images, u8 [B][H][W] each: what every stage below the remap reads */
+    sgm_buf d_rect_maps, d_rect_l, d_rect_r;   /* the maps; the rectified images, u8 (u16 with more than 8 bits) [B][H][W] each: what every
+                                            stage below the remap reads */
+    sgm_buf d_g8_l, d_g8_r;              /* more than 8 bits per sample: the narrowed images the census writes on the side, u8 [B][H][W]
+                                            each: what every reader of grey values below the census takes */
     /* both views' maps from one match (sgm_match_both; all allocated at its first use): the raw left WTA map (f32 [B][H][W]; the raw
      * right one is d_disp_r), the two finished maps as ONE batch of 2 B maps (f32 [2 B][H][W]: the left maps, then the right ones),
      * the speckle and median scratch of such a batch, the right view's snapshots for sgm_keep_stages (after the LR check, after
@@ -179,7 +184,7 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     DEVICE_BUF(d_rf_guide[1]), PINNED_BUF(h_left), PINNED_BUF(h_right), PINNED_BUF(h_disp), DEVICE_BUF(d_both_raw),
     DEVICE_BUF(d_both_maps), DEVICE_BUF(d_both_labels), DEVICE_BUF(d_both_sizes), DEVICE_BUF(d_both_totals), DEVICE_BUF(d_both_median),
     DEVICE_BUF(d_both_snap), PINNED_BUF(h_disp_r), DEVICE_BUF(d_rect_maps), DEVICE_BUF(d_rect_l), DEVICE_BUF(d_rect_r),
-    DEVICE_BUF(d_cloud_scratch), DEVICE_BUF(d_cloud_points), DEVICE_BUF(d_cloud_offsets),
+    DEVICE_BUF(d_cloud_scratch), DEVICE_BUF(d_cloud_points), DEVICE_BUF(d_cloud_offsets), DEVICE_BUF(d_g8_l), DEVICE_BUF(d_g8_r),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -211,6 +216,9 @@ static void sum_accepted(sgm_instance* s, sum_where where, bool up_missing) { s-
 static size_t frame_px(const sgm_instance* s) { return (size_t)s->g.W * s->g.H; }
 static size_t batch_px(const sgm_instance* s) { return (size_t)s->g.B * frame_px(s); }
 static size_t map_bytes(const sgm_instance* s) { return batch_px(s) * sizeof(float); }
+/* images of more than 8 bits per sample (sgm_set_pixel_bits) are u16: the bytes of the caller's images of a batch */
+static bool wide_pixels(const sgm_instance* s) { return s->pixel_bits > 8; }
+static size_t image_bytes(const sgm_instance* s) { return batch_px(s) * (wide_pixels(s) ? 2 : 1); }
 
 /* wait for everything the instance has queued (its stream and, with sgm_set_overlap_post, the post-pass stream) */
 static int sync_streams(sgm_instance* s)
@@ -511,6 +519,32 @@ bool sgm_set_census_kind(sgm_instance* s, int kind)
 
 void sgm_set_reference_view(sgm_instance* s, int right) { if (s) s->reference_view = right ? 1 : 0; }
 
+/* The launchers for images of more than 8 bits per sample (sgm_pixels16.hip), weakly referenced like the other extensions: a host
+ * built without them (the stand-in device of the tests) keeps to 8 bits. */
+#pragma weak sgmd_census16
+#pragma weak sgmd_remap16
+static bool pixel_bits_ok(int bits)
+{
+    if (bits < 8 || bits > 16) return false;
+    if (bits > 8 && (sgmd_census16 == NULL || sgmd_remap16 == NULL)) FAIL("images of more than 8 bits are not part of this build");
+    return true;
+}
+
+bool sgm_set_pixel_bits(sgm_instance* s, int bits)
+{
+    if (!s || !pixel_bits_ok(bits)) return false;
+    if (bits != (s->pixel_bits_req ? s->pixel_bits_req : 8)) s->initialized = false;   /* takes effect at the next initialize */
+    s->pixel_bits_req = bits;
+    return true;
+}
+
+/* device images of more than 8 bits are read two bytes at a time */
+static bool images_aligned(const sgm_instance* s, const void* a, const void* b)
+{
+    if (wide_pixels(s) && (((uintptr_t)a | (uintptr_t)b) & 1u)) FAIL("device images of %d bits per sample must be 2-byte aligned", s->pixel_bits);
+    return true;
+}
+
 /* The hole-filling launchers live in sgm_fill.hip; the host is also built without any HIP (tests link it against a stand-in
  * device), where they are absent: weak references, and no filling there. */
 #pragma weak sgmd_fill_classify
@@ -682,7 +716,7 @@ bool sgm_set_rectify(sgm_instance* s, int width, int height, const float* map_lx
 /* the maps on the device and the two rectified images, beside upload_tables: a Reset with unchanged maps uploads nothing */
 static bool upload_rectify(sgm_instance* s)
 {
-    const size_t px = batch_px(s);
+    const size_t px = image_bytes(s);
     const size_t bytes = 4 * SGMD_REMAP_PITCH((size_t)s->rect_w * s->rect_h) * sizeof(int32_t);
     const buf_request bufs[] = {{&s->d_rect_maps, bytes, 0}, {&s->d_rect_l, px, 0}, {&s->d_rect_r, px, 0}};
     if (!reserve_all(s, bufs, 3, 0)) FAIL("device allocation failed for the rectification of %dx%d", s->g.W, s->g.H);
@@ -698,7 +732,9 @@ bool sgm_rectify(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right,
 {
     if (!s || !s->initialized || !d_left || !d_right || !d_out_left || !d_out_right) return false;
     if (!s->rect_on) FAIL("sgm_rectify: no rectification maps are in effect (sgm_set_rectify, then sgm_initialize / sgm_reset)");
-    if (sgmd_remap(s->device, s->stream, &s->g, s->d_rect_maps.p, d_left, d_right, d_out_left, d_out_right) != 0) FAIL("a kernel launch failed");
+    if (!images_aligned(s, d_left, d_right) || !images_aligned(s, d_out_left, d_out_right)) return false;
+    if ((wide_pixels(s) ? sgmd_remap16 : sgmd_remap)(s->device, s->stream, &s->g, s->d_rect_maps.p, d_left, d_right, d_out_left, d_out_right) != 0)
+        FAIL("a kernel launch failed");
     return true;
 }
 
@@ -853,11 +889,12 @@ static bool ensure_buffers(sgm_instance* s)
          * once, S, the cost volume and the others on their first use).
          * The aggregation kernel reads census-right up to dmin + Dp - 1 words left of a row start (masked to 127
          * afterwards); give the buffer that much readable slack in front, sized for the largest options */
-        const buf_request images[] = {{&s->d_left, px, 0}, {&s->d_right, px, 0}, {&s->d_census_l, px * 4, 0},
+        const size_t img = image_bytes(s);
+        const buf_request images[] = {{&s->d_left, img, 0}, {&s->d_right, img, 0}, {&s->d_census_l, px * 4, 0},
                                       {&s->d_census_r_alloc, CENSUS_FRONT_SLACK + px * 4, 0}};
         const buf_request maps[] = {{&s->d_disp, px * 4, 0}, {&s->d_disp_r, px * 4, 0}, {&s->d_labels, px * 4, 0}, {&s->d_sizes, px * 4, 0},
                                     {&s->d_totals, px * 4, 0}, {&s->d_lut, 512, 0}, {&s->d_snap_wta, px * 4, 0}, {&s->d_snap_lr, px * 4, 0},
-                                    {&s->d_snap_speckle, px * 4, 0}, {&s->h_left, px, BUF_PINNED}, {&s->h_right, px, BUF_PINNED},
+                                    {&s->d_snap_speckle, px * 4, 0}, {&s->h_left, img, BUF_PINNED}, {&s->h_right, img, BUF_PINNED},
                                     {&s->h_disp, px * 4, BUF_PINNED}};
         sync_streams(s);
         /* the census words of earlier frames outlive a re-allocation (reference_statics): set the old buffers aside */
@@ -880,6 +917,13 @@ static bool ensure_buffers(sgm_instance* s)
             free_device_buffers(s);
             FAIL("device allocation failed for %dx%dx%d", s->g.W, s->g.H, s->g.D);
         }
+    }
+    if (wide_pixels(s)) {
+        /* the same frames with more bits per sample: the images (and their staging) grow to u16, the narrowed images appear */
+        const size_t img = image_bytes(s);
+        const buf_request wide[] = {{&s->d_left, img, 0}, {&s->d_right, img, 0}, {&s->h_left, img, BUF_PINNED}, {&s->h_right, img, BUF_PINNED},
+                                    {&s->d_g8_l, px, 0}, {&s->d_g8_r, px, 0}};
+        if (!reserve_all(s, wide, 6, 0)) FAIL("device allocation failed for the %d-bit images of %dx%d", s->pixel_bits, s->g.W, s->g.H);
     }
     const bool tiled = row_tiled(s);
     s->plane_row_lo = tiled && s->g.row_begin > 0 ? s->g.row_begin - 1 : 0;
@@ -1040,6 +1084,10 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
     s->paths.run_anom = 1;
     s->need_plane_memset = !s->paths.ghost_zero;
 
+    s->pixel_bits = 8;
+    if (s->pixel_bits_req > 8 && row_tiled(s))
+        FAIL("images of more than 8 bits (sgm_set_pixel_bits) work on whole frames: not available in row-tile mode (sgm_set_rows)");
+    if (s->pixel_bits_req > 8) s->pixel_bits = s->pixel_bits_req;
     s->fill_on = false;
     if (s->fill_req && row_tiled(s))
         FAIL("hole filling (sgm_set_fill_holes) works on whole frames: not available in row-tile mode (sgm_set_rows)");
@@ -1096,7 +1144,7 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
      * has the shapes: W > H, Dp = 128).  SGM_UPSUM=0 / 1 forces it off / on (also for one frame per launch, where its row-to-row chain
      * costs latency) */
     s->up_rows = 0;
-    if (s->fused_wta && !row_tiled(s) && reference_census(s) && s->paths.ndirs == 8 && option->p1 >= 0 && s->row_cap <= 8 &&
+    if (s->fused_wta && !row_tiled(s) && reference_census(s) && !wide_pixels(s) && s->paths.ndirs == 8 && option->p1 >= 0 && s->row_cap <= 8 &&
         (s->env_upsum >= 0 ? s->env_upsum != 0 : UPSUM_DEFAULT && s->batch >= 2))
         s->up_rows = sgmd_upsum_rows(&s->g);
     if (s->up_rows > 0 && s->env_upsum_rows >= 1 && s->env_upsum_rows < s->up_rows) s->up_rows = s->env_upsum_rows;
@@ -1241,6 +1289,22 @@ static int cost_sum_stage(sgm_instance* s, void* st, void* d_out, void* conf, bo
 /* .c:82-83 (+ .c:89 for the wide centre windows, whose cost is materialised): census of both images */
 static int prepare_costs(sgm_instance* s, const void* d_left, const void* d_right)
 {
+    if (wide_pixels(s)) {
+        /* extension: one launch for any census kind and window on the u16 samples, which also writes the narrowed images; every
+         * word of the frame is written */
+        const int cw = s->census_w ? s->census_w : 5, ch = s->census_h ? s->census_h : 5;
+        if (!volume_fed(s))
+            return sgmd_census16(s->device, s->stream, &s->g, s->pixel_bits, census_symmetric(s), cw, ch, d_left, d_right, s->d_census_l.p,
+                                 s->d_census_r, s->d_g8_l.p, s->d_g8_r.p);
+        const size_t need = batch_px(s) * 8;
+        const buf_request words[] = {{&s->d_census64_l, need, 0}, {&s->d_census64_r, need, 0}};
+        if (!reserve_all(s, words, 2, 0)) return -1;
+        int rc = ensure_cost(s);
+        if (rc == 0) rc = sgmd_census16(s->device, s->stream, &s->g, s->pixel_bits, 0, cw, ch, d_left, d_right, s->d_census64_l.p,
+                                        s->d_census64_r.p, s->d_g8_l.p, s->d_g8_r.p);
+        if (rc == 0) rc = sgmd_cost64(s->device, s->stream, &s->g, s->d_census64_l.p, s->d_census64_r.p, s->d_cost.p);
+        return rc;
+    }
     if (!volume_fed(s)) {
         const bool tiled = row_tiled(s) && !s->keep_stages;          /* stage read-back wants the whole census */
         if (tiled && getenv("SGM_DEBUG_POISON_CENSUS")) {                /* tests: a read of a skipped block must not go unnoticed */
@@ -1375,7 +1439,7 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
      * readers of match n, also with the cost sum and the post pass on streams of their own.  Timed as "census" */
     if (s->rect_on) {
         mark(s, T_CENSUS);
-        LAUNCH(sgmd_remap(dev, st, g, s->d_rect_maps.p, d_left, d_right, s->d_rect_l.p, s->d_rect_r.p));
+        LAUNCH((wide_pixels(s) ? sgmd_remap16 : sgmd_remap)(dev, st, g, s->d_rect_maps.p, d_left, d_right, s->d_rect_l.p, s->d_rect_r.p));
         d_left = s->d_rect_l.p;
         d_right = s->d_rect_r.p;
     }
@@ -1386,10 +1450,17 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
     if (s->refine_on) {
         guide = s->d_rf_guide[s->rf_turn].p;
         s->rf_turn ^= 1;
-        LAUNCH(sgmd_d2d_async(dev, st, (void*)guide, s->reference_view ? d_right : d_left, batch_px(s)));
+        if (!wide_pixels(s)) LAUNCH(sgmd_d2d_async(dev, st, (void*)guide, s->reference_view ? d_right : d_left, batch_px(s)));
     }
     if (!s->rect_on) mark(s, T_CENSUS);
     LAUNCH(prepare_costs(s, d_left, d_right));                                                      /* .c:82-83 */
+    /* more than 8 bits per sample (extension): the census has written the narrowed images; the guide copy (queued behind it),
+     * the aggregation's grey values and everything else below read those */
+    if (wide_pixels(s)) {
+        d_left = s->d_g8_l.p;
+        d_right = s->d_g8_r.p;
+        if (s->refine_on) LAUNCH(sgmd_d2d_async(dev, st, (void*)guide, s->reference_view ? d_right : d_left, batch_px(s)));
+    }
     mark(s, T_COST);
     /* .c:89: the cost volume is recomputed inside the aggregation kernel; it is only materialised when a
      * test wants to read it back (stage 2) */
@@ -1629,7 +1700,7 @@ static bool whole_frames(sgm_instance* s, bool buffers, const char* tiled)
 
 bool sgm_match_device(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left)
 {
-    if (!whole_frames(s, d_left && d_right && d_disp_left, TILED_MATCH)) return false;
+    if (!whole_frames(s, d_left && d_right && d_disp_left, TILED_MATCH) || !images_aligned(s, d_left, d_right)) return false;
     return run_pipeline(s, d_left, d_right, d_disp_left, NULL, NULL);
 }
 
@@ -1687,7 +1758,7 @@ static bool conf_ready(sgm_instance* s, const void* l, const void* r, const void
 
 bool sgm_match_confidence_device(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, float* d_disp, uint16_t* d_conf)
 {
-    if (!conf_ready(s, d_left, d_right, d_disp, d_conf)) return false;
+    if (!conf_ready(s, d_left, d_right, d_disp, d_conf) || !images_aligned(s, d_left, d_right)) return false;
     return run_pipeline(s, d_left, d_right, d_disp, d_conf, NULL);
 }
 
@@ -1763,7 +1834,8 @@ static bool match_async(sgm_instance* s, const uint8_t* img_left, const uint8_t*
     outputs_pinned(s, out, n);
     if (conf && ensure_conf(s, !out[1].pinned) != 0) FAIL("device allocation failed for the confidence map");
     /* the left image is on the bus while the right one is staged */
-    const bool ok = upload(s, s->d_left.p, img_left, s->h_left.p, px) && upload(s, s->d_right.p, img_right, s->h_right.p, px) &&
+    const size_t img = image_bytes(s);
+    const bool ok = upload(s, s->d_left.p, img_left, s->h_left.p, img) && upload(s, s->d_right.p, img_right, s->h_right.p, img) &&
                     run_pipeline(s, s->d_left.p, s->d_right.p, s->d_disp.p, conf ? s->d_conf.p : NULL, NULL);
     return queue_outputs(s, ok, out, n, true);
 }
@@ -1804,7 +1876,9 @@ static bool both_ready(sgm_instance* s, const void* l, const void* r, const void
 
 bool sgm_match_both_device(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left, float* d_disp_right)
 {
-    if (!both_ready(s, d_left, d_right, d_disp_left, d_disp_right) || ensure_both(s, s->keep_stages != 0, false) != 0) return false;
+    if (!both_ready(s, d_left, d_right, d_disp_left, d_disp_right) || !images_aligned(s, d_left, d_right) ||
+        ensure_both(s, s->keep_stages != 0, false) != 0)
+        return false;
     const both_out out = {d_disp_left, d_disp_right};
     return run_pipeline(s, d_left, d_right, s->d_both_raw.p, NULL, &out);
 }
@@ -1819,7 +1893,8 @@ bool sgm_match_both_async(sgm_instance* s, const uint8_t* img_left, const uint8_
     outputs_pinned(s, out, 2);
     if (ensure_both(s, s->keep_stages != 0, !out[1].pinned) != 0) return false;
     const both_out maps = {NULL, NULL};
-    const bool ok = upload(s, s->d_left.p, img_left, s->h_left.p, px) && upload(s, s->d_right.p, img_right, s->h_right.p, px) &&
+    const size_t img = image_bytes(s);
+    const bool ok = upload(s, s->d_left.p, img_left, s->h_left.p, img) && upload(s, s->d_right.p, img_right, s->h_right.p, img) &&
                     run_pipeline(s, s->d_left.p, s->d_right.p, s->d_both_raw.p, NULL, &maps);
     return queue_outputs(s, ok, out, 2, false);
 }
@@ -1989,6 +2064,7 @@ static int ensure_planes_io(sgm_instance* s)
 bool sgm_match_planes_async(sgm_instance* s, const uint8_t* planes, float fx, float baseline, float doffs, float* depth)
 {
     if (!host_entry_ready(s, planes, planes, depth)) return false;
+    if (wide_pixels(s)) FAIL("sgm_match_planes takes byte planes: not available with %d bits per sample (sgm_set_pixel_bits)", s->pixel_bits);
     if (ensure_planes_io(s) != 0) FAIL("device allocation failed for the colour planes of %dx%d", s->g.W, s->g.H);
     const int dev = s->device;
     const size_t fpx = frame_px(s), px = (size_t)s->g.B * fpx;
@@ -2041,7 +2117,8 @@ static size_t compact_volume(const sgm_instance* s, const void* padded, size_t e
 /* The stages sgm_read_stage hands out (include/sgm_mi355x.h has the list): the instance's pointer to each, the size of an element,
  * the half of a buffer of two batches it sits in, whether it is a padded volume ([H][W][Dp], compacted to D on the way out), and what
  * has to hold for it to exist now.  Two rows with one id: whichever holds.  The direction planes (10 .. 17) are not in here. */
-enum { HAS_KEPT = 1, HAS_FILL = 2, HAS_RECT = 4, HAS_BOTH = 8, HAS_BOTH_KEPT = 16, HAS_WIDE = 32, HAS_COST = 64, NOT_WIDE = 128, NOT_BOTH = 256 };
+enum { HAS_KEPT = 1, HAS_FILL = 2, HAS_RECT = 4, HAS_BOTH = 8, HAS_BOTH_KEPT = 16, HAS_WIDE = 32, HAS_COST = 64, NOT_WIDE = 128, NOT_BOTH = 256,
+       HAS_PIX16 = 512, NOT_PIX16 = 1024 };
 #define AT(member) offsetof(struct sgm_instance, member)
 static const struct { int id; size_t at; int elem, half; bool volume; int needs; } k_stages[] = {
     {0, AT(d_census64_l.p), 8, 0, false, HAS_WIDE},           {0, AT(d_census_l.p), 4, 0, false, NOT_WIDE},
@@ -2052,7 +2129,10 @@ static const struct { int id; size_t at; int elem, half; bool volume; int needs;
     {6, AT(d_snap_lr.p), 4, 0, false, HAS_KEPT},              {7, AT(d_snap_speckle.p), 4, 0, false, HAS_KEPT},
     {8, AT(d_both_maps.p), 4, 0, false, HAS_BOTH},            {8, AT(d_disp.p), 4, 0, false, NOT_BOTH},
     {9, AT(d_fill_map.p), 4, 0, false, HAS_KEPT | HAS_FILL},  {18, AT(d_fill_class.p), 1, 0, false, HAS_FILL},
-    {19, AT(d_rect_l.p), 1, 0, false, HAS_RECT},              {20, AT(d_rect_r.p), 1, 0, false, HAS_RECT},
+    {19, AT(d_rect_l.p), 1, 0, false, HAS_RECT | NOT_PIX16},  {20, AT(d_rect_r.p), 1, 0, false, HAS_RECT | NOT_PIX16},
+    /* more than 8 bits per sample: the rectified images are u16; the narrowed images the census wrote */
+    {19, AT(d_rect_l.p), 2, 0, false, HAS_RECT | HAS_PIX16},  {20, AT(d_rect_r.p), 2, 0, false, HAS_RECT | HAS_PIX16},
+    {21, AT(d_g8_l.p), 1, 0, false, HAS_PIX16},               {22, AT(d_g8_r.p), 1, 0, false, HAS_PIX16},
     /* sgm_match_both: the right view after the LR check, after speckle removal, and finished */
     {26, AT(d_both_snap.p), 4, 0, false, HAS_KEPT | HAS_BOTH_KEPT}, {27, AT(d_both_snap.p), 4, 1, false, HAS_KEPT | HAS_BOTH_KEPT},
     {28, AT(d_both_maps.p), 4, 1, false, HAS_BOTH},
@@ -2068,7 +2148,7 @@ size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacit
     int row_a = 0, row_b = s->g.H;                                /* rows the device holds of a volume stage */
     const int has = (s->keep_stages ? HAS_KEPT : 0) | (s->fill_on ? HAS_FILL : 0) | (s->rect_on ? HAS_RECT : 0) |
                     (s->last_both ? HAS_BOTH : NOT_BOTH) | (s->last_both_kept ? HAS_BOTH_KEPT : 0) |
-                    (volume_fed(s) ? HAS_WIDE : NOT_WIDE) | (s->d_cost.p ? HAS_COST : 0);
+                    (volume_fed(s) ? HAS_WIDE : NOT_WIDE) | (s->d_cost.p ? HAS_COST : 0) | (wide_pixels(s) ? HAS_PIX16 : NOT_PIX16);
     if (which == 3 && (ensure_S(s) != 0 || materialize_S(s) != 0)) return 0;
     for (size_t i = 0; !src && i < sizeof k_stages / sizeof k_stages[0]; ++i) {
         const char* base = *(char* const*)((const char*)s + k_stages[i].at);
@@ -2128,7 +2208,14 @@ bool SGM_SetDevice(int device_ordinal)
     return true;
 }
 
-static int g_default_census_w, g_default_census_h, g_default_census_kind, g_default_view, g_default_fill;
+static int g_default_census_w, g_default_census_h, g_default_census_kind, g_default_view, g_default_fill, g_default_pixel_bits;
+
+bool SGM_SetPixelBits(int bits)
+{
+    if (!pixel_bits_ok(bits)) return false;
+    g_default_pixel_bits = bits;
+    return g_default ? sgm_set_pixel_bits(g_default, bits) : true;
+}
 
 bool SGM_SetFillHoles(int enable)
 {
@@ -2229,6 +2316,7 @@ bool SGM_Initialize(uint16_t width, uint16_t height, const SGMOption* option)
         if (g_default_census_w) sgm_set_census_window(g_default, g_default_census_w, g_default_census_h);
         sgm_set_census_kind(g_default, g_default_census_kind);
         sgm_set_reference_view(g_default, g_default_view);
+        if (g_default_pixel_bits) sgm_set_pixel_bits(g_default, g_default_pixel_bits);
         if (g_default_fill) sgm_set_fill_holes(g_default, 1);
         if (g_default_rect.q && !default_rectify_install()) return false;
         if (g_default_refine.enable)

@@ -40,6 +40,32 @@ static int pnm_token(const uint8_t* b, size_t n, size_t* pos, int* value)
     return 0;
 }
 
+/* binary PGM with maxval 256..65535: two bytes per sample, most significant first (the Netpbm format) */
+static uint16_t* load_pgm16(const uint8_t* b, size_t n, int* w, int* h, int* maxval)
+{
+    size_t pos = 2;
+    if (b[1] != '5' || pnm_token(b, n, &pos, w) || pnm_token(b, n, &pos, h) || pnm_token(b, n, &pos, maxval) || *maxval < 256 ||
+        *maxval > 65535 || *w <= 0 || *h <= 0) {
+        fprintf(stderr, "unsupported PNM header (need binary P5 with maxval 256..65535)\n");
+        return NULL;
+    }
+    ++pos;                                              /* the single whitespace after maxval */
+    const size_t px = (size_t)*w * *h;
+    if (pos + 2 * px > n) { fprintf(stderr, "truncated PNM\n"); return NULL; }
+    uint16_t* out = (uint16_t*)malloc(px * sizeof *out);
+    if (!out) return NULL;
+    for (size_t i = 0; i < px; ++i) out[i] = (uint16_t)((b[pos + 2 * i] << 8) | b[pos + 2 * i + 1]);
+    return out;
+}
+
+/* the maxval of a PNM header, 0 if there is none */
+static int pnm_maxval(const uint8_t* b, size_t n)
+{
+    size_t pos = 2;
+    int w, h, maxv;
+    return (pnm_token(b, n, &pos, &w) || pnm_token(b, n, &pos, &h) || pnm_token(b, n, &pos, &maxv)) ? 0 : maxv;
+}
+
 static uint8_t* load_pnm(const uint8_t* b, size_t n, int* w, int* h)
 {
     const int colour = (b[1] == '6');
@@ -69,7 +95,9 @@ static int paeth(int a, int b, int c)
     return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
 }
 
-static uint8_t* load_png(const uint8_t* b, size_t n, int* w, int* h)
+/* deep == NULL: 8-bit files only, as 8-bit grey.  Else a 16-bit grey file is accepted too: *deep = 1 and the result is w*h
+ * uint16_t samples (the file's are most significant byte first); *deep = 0 and 8-bit grey for any other file */
+static void* load_png(const uint8_t* b, size_t n, int* w, int* h, int* deep)
 {
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     if (n < 33 || memcmp(b, sig, 8)) { fprintf(stderr, "not a PNG\n"); return NULL; }
@@ -97,13 +125,16 @@ static uint8_t* load_png(const uint8_t* b, size_t n, int* w, int* h)
         }
         pos += 12 + (size_t)len;
     }
-    if (!idat || !have_ihdr || depth != 8 || interlace != 0 || *w <= 0 || *h <= 0 ||
+    const int grey16 = deep && depth == 16 && ctype == 0;
+    if (deep) *deep = grey16;
+    if (!idat || !have_ihdr || (depth != 8 && !grey16) || interlace != 0 || *w <= 0 || *h <= 0 ||
         !(ctype == 0 || ctype == 2 || ctype == 3 || ctype == 4 || ctype == 6)) {
-        fprintf(stderr, "unsupported PNG (need 8-bit, non-interlaced)\n");
+        fprintf(stderr, deep ? "unsupported PNG (need 8-bit, or 16-bit grey; non-interlaced)\n"
+                             : "unsupported PNG (need 8-bit, non-interlaced; 16-bit grey files need --bits)\n");
         free(idat);
         return NULL;
     }
-    const int ch = (ctype == 0 || ctype == 3) ? 1 : (ctype == 4 ? 2 : (ctype == 2 ? 3 : 4));
+    const int ch = grey16 ? 2 : (ctype == 0 || ctype == 3) ? 1 : (ctype == 4 ? 2 : (ctype == 2 ? 3 : 4));   /* bytes per pixel */
     const size_t stride = (size_t)*w * ch;
     uLongf raw_len = (uLongf)((stride + 1) * (size_t)*h);
     uint8_t* raw = (uint8_t*)malloc(raw_len);
@@ -133,6 +164,16 @@ static uint8_t* load_png(const uint8_t* b, size_t n, int* w, int* h)
         }
     }
     const size_t px = (size_t)*w * *h;
+    if (grey16) {
+        uint16_t* out16 = (uint16_t*)malloc(px * sizeof *out16);
+        if (out16)
+            for (int y = 0; y < *h; ++y) {
+                const uint8_t* row = raw + (size_t)y * (stride + 1) + 1;
+                for (int x = 0; x < *w; ++x) out16[(size_t)y * *w + x] = (uint16_t)((row[2 * x] << 8) | row[2 * x + 1]);
+            }
+        free(raw);
+        return out16;
+    }
     uint8_t* out = (uint8_t*)malloc(px);
     if (out)
         for (int y = 0; y < *h; ++y) {
@@ -157,8 +198,34 @@ uint8_t* sgm_load_gray(const char* path, int* w, int* h)
     if (!b) return NULL;
     uint8_t* out = NULL;
     if (n > 2 && b[0] == 'P' && (b[1] == '5' || b[1] == '6')) out = load_pnm(b, n, w, h);
-    else out = load_png(b, n, w, h);
+    else out = (uint8_t*)load_png(b, n, w, h, NULL);
     free(b);
+    return out;
+}
+
+uint16_t* sgm_load_gray16(const char* path, int* w, int* h, int* maxval)
+{
+    size_t n = 0;
+    uint8_t* b = read_file(path, &n);
+    if (!b) return NULL;
+    uint16_t* out = NULL;
+    uint8_t* narrow = NULL;
+    if (n > 2 && b[0] == 'P' && b[1] == '5' && pnm_maxval(b, n) > 255) out = load_pgm16(b, n, w, h, maxval);
+    else if (n > 2 && b[0] == 'P' && (b[1] == '5' || b[1] == '6')) narrow = load_pnm(b, n, w, h);
+    else {
+        int deep = 0;
+        void* img = load_png(b, n, w, h, &deep);
+        if (deep) { out = (uint16_t*)img; *maxval = 65535; }
+        else narrow = (uint8_t*)img;
+    }
+    free(b);
+    if (narrow) {                                       /* an 8-bit file: the same values, unshifted */
+        const size_t px = (size_t)*w * *h;
+        out = (uint16_t*)malloc(px * sizeof *out);
+        for (size_t i = 0; out && i < px; ++i) out[i] = narrow[i];
+        free(narrow);
+        *maxval = 255;
+    }
     return out;
 }
 

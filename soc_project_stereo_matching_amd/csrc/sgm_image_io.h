@@ -9,6 +9,11 @@
  * Returns a malloc'ed buffer of w*h bytes or NULL (message on stderr). */
 uint8_t* sgm_load_gray(const char* path, int* w, int* h);
 
+/* Loads a grey image of up to 16 bits per sample as w*h uint16_t samples (malloc'ed; NULL and a message on stderr otherwise):
+ * binary PGM (P5) with maxval 256..65535, two bytes per sample, most significant first; PNG grey of depth 16 (*maxval = 65535);
+ * and everything sgm_load_gray reads, as the same values unshifted (*maxval = 255). */
+uint16_t* sgm_load_gray16(const char* path, int* w, int* h, int* maxval);
+
 /* 8-bit grey writers; return 0 on success. */
 int sgm_write_png_gray(const char* path, const uint8_t* data, int w, int h);
 int sgm_write_pgm(const char* path, const uint8_t* data, int w, int h);

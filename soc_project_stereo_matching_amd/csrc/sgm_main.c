@@ -26,7 +26,13 @@
  *                             3-D points (SGM_ReadCloud), a binary little-endian PLY with x y z float and red green blue uchar,
  *                             the colour being the grey at the point's pixel of the image the map belongs to: LEFT (RIGHT with
  *                             --right-reference), the rectified one with --rectify
+ *            [--bits N]       extension: images of N = 9..16 bits per sample (SGM_SetPixelBits): LEFT and RIGHT are loaded with
+ *                             sgm_load_gray16 (binary PGM with maxval up to 65535, PNG grey of depth 16; 8-bit files are widened
+ *                             unshifted) and matched on all their bits.  --bits 0: the smallest N >= 8 that holds the files' maxval.
+ *                             Default 8, which refuses a 16-bit file.  With --bits above 8, --rectified-out writes 16-bit PGMs and
+ *                             the cloud's colour is the narrowed image's
  *   sgm_main --convert IN OUT.png        (image I/O only, no GPU: used by the CPU tests)
+ *   sgm_main --convert16 IN OUT.pgm      (the same through sgm_load_gray16 and the 16-bit PGM writer; prints the file's maxval)
  */
 #define _POSIX_C_SOURCE 200809L
 #include "../../include/sgm_mi355x.h"
@@ -116,6 +122,15 @@ int main(int argc, char** argv)
         free(g);
         return rc ? 1 : 0;
     }
+    if (argc == 4 && !strcmp(argv[1], "--convert16")) {
+        int w, h, maxval;
+        uint16_t* g = sgm_load_gray16(argv[2], &w, &h, &maxval);
+        if (!g) return 1;
+        printf("w = %d, h = %d, maxval = %d\n", w, h, maxval);
+        const int rc = sgm_write_pgm16(argv[3], g, w, h);
+        free(g);
+        return rc ? 1 : 0;
+    }
     if (argc < 4) {
         fprintf(stderr, "usage: %s LEFT RIGHT OUT.png [options]   (see the header of sgm_main.c)\n", argv[0]);
         return 2;
@@ -143,7 +158,7 @@ int main(int argc, char** argv)
     float pinhole[6], cloud_z_max = INFINITY;
     int have_pinhole = 0;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
-    int census_kind = SGM_CENSUS_CENTRE;
+    int census_kind = SGM_CENSUS_CENTRE, bits = 8;
     float refine_lambda = SGM_REFINE_DEFAULT_LAMBDA, refine_sigma = SGM_REFINE_DEFAULT_SIGMA;
     int refine_iters = SGM_REFINE_DEFAULT_ITERS;
     for (int i = 4; i < argc; ++i) {
@@ -177,6 +192,11 @@ int main(int argc, char** argv)
         else if (v && !strcmp(a, "--cloud-z-max")) { cloud_z_max = (float)atof(v); ++i; }
         else if (v && !strcmp(a, "--repeat")) { repeat = atoi(v); ++i; }
         else if (v && !strcmp(a, "--device")) { device = atoi(v); ++i; }
+        else if (v && !strcmp(a, "--bits")) {
+            bits = atoi(v);
+            if (bits != 0 && (bits < 8 || bits > 16)) { fprintf(stderr, "--bits wants 8..16, or 0 for what the files hold\n"); return 2; }
+            ++i;
+        }
         else if (v && !strcmp(a, "--paths")) { opt.num_paths = (uint8_t)atoi(v); SGM_SetHonorNumPaths(1); ++i; }
         else if (v && !strcmp(a, "--census")) {
             if (sscanf(v, "%dx%d", &census_w, &census_h) != 2) { fprintf(stderr, "--census wants WxH, e.g. 7x7\n"); return 2; }
@@ -209,8 +229,27 @@ int main(int argc, char** argv)
     if (cloud_path && !have_pinhole) { fprintf(stderr, "--cloud needs --pinhole FX,FY,CX,CY,BASELINE,DOFFS\n"); return 2; }
 
     int w1, h1, w2, h2;
-    uint8_t* left = sgm_load_gray(argv[1], &w1, &h1);
-    uint8_t* right = sgm_load_gray(argv[2], &w2, &h2);
+    uint8_t *left = NULL, *right = NULL;                          /* the images as the library takes them: bytes, or uint16_t samples */
+    if (bits == 8) {
+        left = sgm_load_gray(argv[1], &w1, &h1);
+        right = sgm_load_gray(argv[2], &w2, &h2);
+    } else {
+        int max1 = 0, max2 = 0;
+        uint16_t* l16 = sgm_load_gray16(argv[1], &w1, &h1, &max1);
+        uint16_t* r16 = sgm_load_gray16(argv[2], &w2, &h2, &max2);
+        const int maxval = max1 > max2 ? max1 : max2;
+        if (bits == 0)
+            for (bits = 8; (1 << bits) <= maxval; ++bits) {}
+        if (l16 && r16) printf("maxval %d, %d bits per sample\n", maxval, bits);
+        if (l16 && r16 && bits > 8 && maxval >= (1 << bits)) printf("warning: samples of %d bits and more saturate the narrowed image\n", bits);
+        if (l16 && r16 && bits == 8 && w1 == w2 && h1 == h2) {     /* --bits 0 on 8-bit files: the plain path */
+            const size_t px = (size_t)w1 * h1;
+            left = (uint8_t*)malloc(px);
+            right = (uint8_t*)malloc(px);
+            for (size_t i = 0; left && right && i < px; ++i) { left[i] = (uint8_t)l16[i]; right[i] = (uint8_t)r16[i]; }
+            free(l16); free(r16);
+        } else { left = (uint8_t*)l16; right = (uint8_t*)r16; }
+    }
     if (!left || !right) { printf("Failed to load images\n"); return -1; }
     if (w1 != w2 || h1 != h2) { printf("Images must have same dimensions\n"); return -1; }
     if (w1 > 65535 || h1 > 65535) { printf("Image too large\n"); return -1; }
@@ -224,6 +263,7 @@ int main(int argc, char** argv)
     if (!SGM_SetCensusKind(census_kind)) { printf("unsupported census kind\n"); return -2; }
     if (census_w && !SGM_SetCensusWindow(census_w, census_h)) { printf("unsupported census window %dx%d\n", census_w, census_h); return -2; }
     if (right_ref) SGM_SetReferenceView(1);
+    if (!SGM_SetPixelBits(bits)) { printf("%d bits per sample are not available\n", bits); return -2; }
     if (fill_holes && !SGM_SetFillHoles(1)) { printf("hole filling unavailable\n"); return -2; }
     if (refine && !SGM_SetRefine(1, refine_lambda, refine_sigma, refine_iters, 0)) {
         printf("refinement unavailable or parameters out of range (%g, %g, %d)\n", refine_lambda, refine_sigma, refine_iters);
@@ -256,9 +296,11 @@ int main(int argc, char** argv)
     if (disp_r && write_map(disp_r, w1, h1, right_out, right_raw) != 0) rc = -1;
     if (conf_path && sgm_write_pgm16(conf_path, conf, w1, h1) != 0) rc = -1;
     for (int v = 0; v < 2 && rect_out[0]; ++v) {                  /* the images the match ran on: stages 19 / 20 */
-        const size_t px = (size_t)w1 * h1;
-        uint8_t* img = (uint8_t*)malloc(px);
-        if (!img || SGM_ReadStage(19 + v, img, px) != px || sgm_write_pgm(rect_out[v], img, w1, h1) != 0) rc = -1;
+        const size_t px = (size_t)w1 * h1, bytes = px * (bits > 8 ? 2 : 1);
+        uint8_t* img = (uint8_t*)malloc(bytes);
+        if (!img || SGM_ReadStage(19 + v, img, bytes) != bytes ||
+            (bits > 8 ? sgm_write_pgm16(rect_out[v], (const uint16_t*)img, w1, h1) : sgm_write_pgm(rect_out[v], img, w1, h1)) != 0)
+            rc = -1;
         free(img);
     }
     if (cloud_path) {                                             /* sized from a first call, which copies the offsets alone */
@@ -277,9 +319,9 @@ int main(int argc, char** argv)
             const size_t px = (size_t)w1 * h1;
             const uint8_t* grey = right_ref ? right : left;
             uint8_t* rect = NULL;
-            if (calib_path) {
+            if (calib_path || bits > 8) {                         /* more than 8 bits: the narrowed image, stage 21 / 22 */
                 rect = (uint8_t*)malloc(px);
-                grey = (rect && SGM_ReadStage(19 + right_ref, rect, px) == px) ? rect : NULL;
+                grey = (rect && SGM_ReadStage((bits > 8 ? 21 : 19) + right_ref, rect, px) == px) ? rect : NULL;
             }
             if (!grey || write_ply(cloud_path, pts, offsets[1], grey, w1) != 0) rc = -1;
             free(rect);

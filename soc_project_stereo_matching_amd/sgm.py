@@ -25,6 +25,8 @@ STAGE_FILLED, STAGE_FILL_CLASS = 9, 18
 STAGE_RIGHT_AFTER_LR, STAGE_RIGHT_AFTER_SPECKLE, STAGE_RIGHT_FINAL = 26, 27, 28
 # the rectified left / right image (u8; they exist only with rectification on, set_rectify: read_stages() leaves them out)
 STAGE_RECT_LEFT, STAGE_RECT_RIGHT = 19, 20
+# the narrowed left / right image of a match on more than 8 bits per sample (u8; set_pixel_bits: read_stages() leaves them out)
+STAGE_NARROW_LEFT, STAGE_NARROW_RIGHT = 21, 22
 # the refinement's default parameters (SGM_REFINE_DEFAULT_* of include/sgm_mi355x.h)
 REFINE_LAMBDA, REFINE_SIGMA, REFINE_ITERS = 16.0, 1.5, 1
 # census kinds (SGM_CENSUS_* of include/sgm_mi355x.h) and the drivers' window for the symmetric kind
@@ -203,6 +205,11 @@ def _load() -> C.CDLL:
         L.SGM_ReadCloud.restype = C.c_bool
         L.sgm_rectify_valid_mask.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sgm_rectify_valid_mask.restype = C.c_bool
+    if hasattr(L, "sgm_set_pixel_bits"):      # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_set_pixel_bits.argtypes = [C.c_void_p, C.c_int]
+        L.sgm_set_pixel_bits.restype = C.c_bool
+        L.SGM_SetPixelBits.argtypes = [C.c_int]
+        L.SGM_SetPixelBits.restype = C.c_bool
     L.sgm_set_batch.argtypes = [C.c_void_p, C.c_int]
     L.sgm_set_batch.restype = C.c_bool
     L.sgm_select_frame.argtypes = [C.c_void_p, C.c_int]
@@ -368,15 +375,24 @@ def _device_ptr(x, dtype, count, name):
     return x.data_ptr()
 
 
-def _u8(a):
-    a = np.ascontiguousarray(a)
-    if a.dtype != np.uint8:
-        raise TypeError("images must be uint8")
-    return a
+def _pixel_dtype(bits):
+    return np.uint16 if bits > 8 else np.uint8
 
 
 class _StageReader:
     _wide_window, _census_kind = False, CENSUS_CENTRE
+    _bits_req = _bits = 8            # bits per sample asked for (set_pixel_bits) / in effect since the last initialize or reset
+
+    def _img(self, a, bits=None):
+        """A C-contiguous image of the dtype the instance reads: uint8, or uint16 with more than 8 bits per sample in effect
+        (bits: another width than the one in effect).  The C side moves width * height samples of that size whatever the array
+        holds, so any other dtype is a TypeError."""
+        a = np.ascontiguousarray(a)
+        bits = self._bits if bits is None else bits
+        want = _pixel_dtype(bits)
+        if a.dtype != want:
+            raise TypeError(f"images must be {np.dtype(want).name} with {bits} bits per sample (set_pixel_bits), got {a.dtype}")
+        return a
 
     @property
     def wide_census(self):
@@ -395,7 +411,9 @@ class _StageReader:
             dt, shp = np.uint64, (h, w)
         elif idx == STAGE_FILLED:
             dt, shp = np.float32, (h, w)
-        elif idx in (STAGE_FILL_CLASS, STAGE_RECT_LEFT, STAGE_RECT_RIGHT):
+        elif idx in (STAGE_RECT_LEFT, STAGE_RECT_RIGHT):
+            dt, shp = _pixel_dtype(self._bits), (h, w)
+        elif idx in (STAGE_FILL_CLASS, STAGE_NARROW_LEFT, STAGE_NARROW_RIGHT):
             dt, shp = np.uint8, (h, w)
         elif idx in (STAGE_RIGHT_AFTER_LR, STAGE_RIGHT_AFTER_SPECKLE, STAGE_RIGHT_FINAL):
             dt, shp = np.float32, (h, w)
@@ -420,13 +438,20 @@ class _StageReader:
         """Stages 19 and 20: the rectified (left, right) images the last match ran on (needs rectification on, set_rectify)."""
         return self.read_stage(STAGE_RECT_LEFT), self.read_stage(STAGE_RECT_RIGHT)
 
+    def read_narrowed(self):
+        """Stages 21 and 22: the narrowed (left, right) images g8 = min(v >> (bits - 8), 255) of the last match (needs more than 8
+        bits per sample in effect, set_pixel_bits)."""
+        return self.read_stage(STAGE_NARROW_LEFT), self.read_stage(STAGE_NARROW_RIGHT)
+
     def read_fill_classes(self):
         """Stage 18: the hole-filling classes, 0 valid / 1 occluded / 2 mismatched (after any match with fill on)."""
         return self.read_stage(STAGE_FILL_CLASS)
 
 
 class SGM(_StageReader):
-    """The reference's global-instance API: SGM_Initialize / SGM_Reset / SGM_Match."""
+    """The reference's global-instance API: SGM_Initialize / SGM_Reset / SGM_Match.  The default instance is one per process in C,
+    and so are its bits per sample: every SGM object reads and writes them on the class (SGM._bits_req / SGM._bits), so that a
+    second object, or one made after set_pixel_bits, checks image dtypes against the width the library really reads."""
 
     def __init__(self):
         self.lib = load_library()
@@ -455,6 +480,14 @@ class SGM(_StageReader):
     def set_reference_view(self, right: bool):
         self.lib.SGM_SetReferenceView(int(right))
 
+    def set_pixel_bits(self, bits: int) -> bool:
+        """Extension: bits per image sample, 8 (reference) or 9..16: from the next initialize/reset on the images of every match
+        are uint16 arrays (include/sgm_mi355x.h, SGM_SetPixelBits).  False, and nothing changes, for any other value."""
+        ok = bool(self.lib.SGM_SetPixelBits(int(bits)))
+        if ok:
+            SGM._bits_req = int(bits)
+        return ok
+
     def set_fill_holes(self, enable: bool = True) -> bool:
         """Extension: occlusion-aware hole filling of the +INF pixels (include/sgm_mi355x.h); next initialize/reset."""
         return bool(self.lib.SGM_SetFillHoles(int(enable)))
@@ -475,12 +508,14 @@ class SGM(_StageReader):
     def initialize(self, width, height, option) -> bool:
         ok = bool(self.lib.SGM_Initialize(width, height, C.byref(option)))
         if ok:
+            SGM._bits = SGM._bits_req
             self.shape = (height, width, option.max_disparity - option.min_disparity)
         return ok
 
     def reset(self, width, height, option) -> bool:
         ok = bool(self.lib.SGM_Reset(width, height, C.byref(option)))
         if ok:
+            SGM._bits = SGM._bits_req
             self.shape = (height, width, option.max_disparity - option.min_disparity)
         return ok
 
@@ -489,7 +524,7 @@ class SGM(_StageReader):
         if left is None or right is None:
             assert not self.lib.SGM_Match(None, None, None)
             return None
-        left, right = _u8(left), _u8(right)
+        left, right = self._img(left), self._img(right)
         out = np.empty(left.shape, np.float32)
         ok = self.lib.SGM_Match(left.ctypes.data, right.ctypes.data, out.ctypes.data)
         return out if ok else None
@@ -497,7 +532,7 @@ class SGM(_StageReader):
     def match_confidence(self, left, right):
         """SGM_MatchConfidence: (disparity float32, confidence uint16) of the default instance, or None where the C call returns
         false.  The confidence contract is in include/sgm_mi355x.h."""
-        left, right = _u8(left), _u8(right)
+        left, right = self._img(left), self._img(right)
         out = np.empty(left.shape, np.float32)
         conf = np.empty(left.shape, np.uint16)
         ok = self.lib.SGM_MatchConfidence(left.ctypes.data, right.ctypes.data, out.ctypes.data, conf.ctypes.data)
@@ -506,7 +541,7 @@ class SGM(_StageReader):
     def match_both(self, left, right):
         """SGM_MatchBoth: (left-view map, right-view map) of the default instance from one match, float32 each, or None where the C
         call returns false.  The contract is in include/sgm_mi355x.h."""
-        left, right = _u8(left), _u8(right)
+        left, right = self._img(left), self._img(right)
         out_l = np.empty(left.shape, np.float32)
         out_r = np.empty(left.shape, np.float32)
         ok = self.lib.SGM_MatchBoth(left.ctypes.data, right.ctypes.data, out_l.ctypes.data, out_r.ctypes.data)
@@ -515,7 +550,7 @@ class SGM(_StageReader):
     def compute(self, left, right, option, out=None):
         """sgm_compute: SGM_Reset + SGM_Match in one call (north_star's entry point).  None where it returns false.  `out`: a
         C-contiguous float32 [H][W] array to write into (a caller with a stream of frames allocates it once)."""
-        left, right = _u8(left), _u8(right)
+        left, right = self._img(left, SGM._bits_req), self._img(right, SGM._bits_req)    # the call resets first: the bits asked for hold
         h, w = left.shape
         if out is None:
             out = np.empty((h, w), np.float32)
@@ -523,6 +558,7 @@ class SGM(_StageReader):
             raise ValueError(f"compute: out must be a C-contiguous float32 array of shape {(h, w)}")
         ok = self.lib.sgm_compute(left.ctypes.data, right.ctypes.data, w, h, C.byref(option), out.ctypes.data)
         if ok:
+            SGM._bits = SGM._bits_req
             self.shape = (h, w, option.max_disparity - option.min_disparity)
         return out if ok else None
 
@@ -633,6 +669,15 @@ class SGMInstance(_StageReader):
         """Extension: True = the result is the right image's disparity map (mirrored LR check)."""
         self.lib.sgm_set_reference_view(self.handle, int(right))
 
+    def set_pixel_bits(self, bits: int) -> bool:
+        """Extension: bits per image sample, 8 (reference) or 9..16: from the next initialize/reset on the images of every match
+        are uint16 arrays (device images: uint16, 2-byte aligned) (include/sgm_mi355x.h, SGM_SetPixelBits).  False, and nothing
+        changes, for any other value."""
+        ok = bool(self.lib.sgm_set_pixel_bits(self.handle, int(bits)))
+        if ok:
+            self._bits_req = int(bits)
+        return ok
+
     def set_fill_holes(self, enable: bool = True) -> bool:
         """Extension: occlusion-aware hole filling of the +INF pixels (include/sgm_mi355x.h); next initialize/reset."""
         return bool(self.lib.sgm_set_fill_holes(self.handle, int(enable)))
@@ -654,10 +699,10 @@ class SGMInstance(_StageReader):
         return bool(self.lib.sgm_set_rectify(self.handle, w, h, *ptrs))
 
     def rectify(self, d_left, d_right, d_out_left, d_out_right) -> bool:
-        """sgm_rectify: the remap alone on device images of the instance's batch and shape (uint8; device pointers or torch
-        tensors), through the maps in effect; asynchronous on `stream`.  False when no maps are in effect."""
+        """sgm_rectify: the remap alone on device images of the instance's batch and shape (uint8, or uint16 with more than 8 bits
+        per sample in effect; device pointers or torch tensors), through the maps in effect; asynchronous on `stream`.  False when no maps are in effect."""
         n = self.batch * self.shape[0] * self.shape[1] if self.shape else 0
-        return bool(self.lib.sgm_rectify(self.handle, *(_device_ptr(x, np.uint8, n, name) for x, name in
+        return bool(self.lib.sgm_rectify(self.handle, *(_device_ptr(x, _pixel_dtype(self._bits), n, name) for x, name in
                                                         ((d_left, "d_left"), (d_right, "d_right"), (d_out_left, "d_out_left"),
                                                          (d_out_right, "d_out_right")))))
 
@@ -701,20 +746,23 @@ class SGMInstance(_StageReader):
     def initialize(self, width, height, option) -> bool:
         ok = bool(self.lib.sgm_initialize(self.handle, width, height, C.byref(option)))
         if ok:
+            self._bits = self._bits_req
             self.shape = (height, width, option.max_disparity - option.min_disparity)
         return ok
 
     def reset(self, width, height, option) -> bool:
         ok = bool(self.lib.sgm_reset(self.handle, width, height, C.byref(option)))
         if ok:
+            self._bits = self._bits_req
             self.shape = (height, width, option.max_disparity - option.min_disparity)
         return ok
 
     def match(self, left, right):
-        """left/right: uint8 [H][W], or [batch][H][W] when the instance has a batch > 1."""
+        """left/right: uint8 (uint16 with more than 8 bits per sample in effect, set_pixel_bits) [H][W], or [batch][H][W] when the
+        instance has a batch > 1."""
         if self.shape is None:
             return None                                   # Match before Initialize: false in the reference (.c:70)
-        left, right = _u8(left), _u8(right)
+        left, right = self._img(left), self._img(right)
         want = self.shape[:2] if self.batch == 1 else (self.batch,) + tuple(self.shape[:2])
         if tuple(left.shape) != tuple(want):
             raise ValueError(f"expected images of shape {want}, got {left.shape}")
@@ -730,8 +778,9 @@ class SGMInstance(_StageReader):
         for a in (left, right, out):
             if not a.flags["C_CONTIGUOUS"]:
                 raise ValueError("match_async needs C-contiguous arrays")
-        if left.dtype != np.uint8 or right.dtype != np.uint8 or out.dtype != np.float32:
-            raise TypeError("match_async: uint8 images, float32 output")
+        px = _pixel_dtype(self._bits)
+        if left.dtype != px or right.dtype != px or out.dtype != np.float32:
+            raise TypeError(f"match_async: {np.dtype(px).name} images ({self._bits} bits per sample), float32 output")
         # the C side moves batch * W * H bytes (4x that for the output) whatever the arrays hold: check before handing pointers over
         want = self._frame_shape()
         for name, a in (("left", left), ("right", right), ("out", out)):
@@ -744,7 +793,7 @@ class SGMInstance(_StageReader):
         returns false.  The confidence contract is in include/sgm_mi355x.h."""
         if self.shape is None:
             return None
-        left, right = _u8(left), _u8(right)
+        left, right = self._img(left), self._img(right)
         want = self._frame_shape()
         if tuple(left.shape) != want or tuple(right.shape) != want:
             raise ValueError(f"expected images of shape {want}, got {left.shape}")
@@ -759,7 +808,10 @@ class SGMInstance(_StageReader):
         if self.shape is None:
             return False
         want = self._frame_shape()
-        for name, a, dt in (("left", left, np.uint8), ("right", right, np.uint8), ("out", out, np.float32), ("conf", conf, np.uint16)):
+        px = _pixel_dtype(self._bits)
+        for name, a, dt in (("left", left, px), ("right", right, px), ("out", out, np.float32), ("conf", conf, np.uint16)):
+            if a.dtype != dt and name in ("left", "right"):
+                raise TypeError(f"match_confidence_async: {name} must be {np.dtype(dt).name} with {self._bits} bits per sample")
             if not a.flags["C_CONTIGUOUS"] or a.dtype != dt or tuple(a.shape) != want:
                 raise ValueError(f"match_confidence_async: {name} must be a C-contiguous {np.dtype(dt).name} array of shape {want}")
         return bool(self.lib.sgm_match_confidence_async(self.handle, left.ctypes.data, right.ctypes.data, out.ctypes.data,
@@ -774,7 +826,7 @@ class SGMInstance(_StageReader):
         C call returns false.  The contract is in include/sgm_mi355x.h (SGM_MatchBoth)."""
         if self.shape is None:
             return None
-        left, right = _u8(left), _u8(right)
+        left, right = self._img(left), self._img(right)
         want = self._frame_shape()
         if tuple(left.shape) != want or tuple(right.shape) != want:
             raise ValueError(f"expected images of shape {want}, got {left.shape}")
@@ -788,8 +840,11 @@ class SGMInstance(_StageReader):
         if self.shape is None:
             return False
         want = self._frame_shape()
-        for name, a, dt in (("left", left, np.uint8), ("right", right, np.uint8), ("out_left", out_left, np.float32),
+        px = _pixel_dtype(self._bits)
+        for name, a, dt in (("left", left, px), ("right", right, px), ("out_left", out_left, np.float32),
                             ("out_right", out_right, np.float32)):
+            if a.dtype != dt and name in ("left", "right"):
+                raise TypeError(f"match_both_async: {name} must be {np.dtype(dt).name} with {self._bits} bits per sample")
             if not a.flags["C_CONTIGUOUS"] or a.dtype != dt or tuple(a.shape) != want:
                 raise ValueError(f"match_both_async: {name} must be a C-contiguous {np.dtype(dt).name} array of shape {want}")
         return bool(self.lib.sgm_match_both_async(self.handle, left.ctypes.data, right.ctypes.data, out_left.ctypes.data,
