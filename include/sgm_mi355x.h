@@ -54,7 +54,19 @@ typedef struct {
  * false for width==0, height==0, max_disparity<=min_disparity (as the reference) and, in addition,
  * when no gfx950 device is usable, a HIP call fails, or the disparity range exceeds
  * SGM_MAX_DISPARITY_RANGE (the reason is printed to stderr).  Sizes device buffers for this
- * shape and marks the aggregated-cost volume as zero. */
+ * shape and marks the aggregated-cost volume as zero.
+ * Admitted: width and height up to 65535 each with width * height < 2^31, min_disparity up to
+ * 65535 - D, and a padded volume width * height * Dp < 2^32 - 1 cells (Dp = D rounded up to 32, 64,
+ * 128, 192, 256 or 512); anything beyond is refused.  Also refused: a frame whose per-row table of
+ * anomalous-line visits, [height][cap] with cap = the most visits of one row, would pass 2^24
+ * entries.  With eight paths that is width == 1 with height > 4096 only (two diagonal lines stay on
+ * one row there, cap = height or height + 1; no other width has cap > 6): 1 x 4096 is accepted,
+ * 1 x 4097 is not.  tests/test_gpu_limits.py runs every kernel at these ends (DESIGN.md section 2
+ * has the table).
+ * One deviation past 32768 columns or rows: the reference's RemoveSpeckles keeps neighbour
+ * coordinates in int16_t (SemiGlobalMatching.c:618-620), so a neighbour in a column or row >= 32768
+ * wraps negative and is rejected, and components are cut there.  This library (and the CPU oracle)
+ * grows whole components at every size; up to 32768 x 32768 the two are the same. */
 bool SGM_Initialize(uint16_t width, uint16_t height, const SGMOption* option);
 
 /* replaces SemiGlobalMatching.h:79 / SemiGlobalMatching.c:128-132 (clear + Initialize). */

@@ -827,6 +827,9 @@ static bool upload_census_need(sgm_instance* s)
     return true;
 }
 
+/* most entries of the per-row table [H][cap] (8 bytes each: 128 MB) */
+#define ROW_EXTRAS_MAX ((size_t)1 << 24)
+
 /* Build the per-row table of anomalous-line visits and upload it together with the P2 table. */
 static bool upload_tables(sgm_instance* s)
 {
@@ -851,6 +854,17 @@ static bool upload_tables(sgm_instance* s)
     }
     int cap = 1;
     for (int r = 0; r < H; ++r) if (count[r] > cap) cap = count[r];
+    /* W = 1: for the two directions with dx != dy a diagonal step is W - 1 = 0 pixels and the tracker never finds column 0 again:
+     * after its first step the (-1,+1) line stays on row 1 and the (+1,-1) line on row H - 2, H - 1 visits each.  The other two
+     * lines move two rows per step, (1,1) over rows 0, 1, 3, 5, ..., (-1,-1) over H - 1, H - 2, H - 4, ...; both meet row 1 where H
+     * is odd.  So cap = H for even H and H + 1 for odd H: a table of about H^2 entries (34 GB at H = 65535) that the kernels index
+     * with row * cap in int.  The limit admits H * cap <= 2^24: 1 x 4096 (4096 * 4096, exactly the limit) is the tallest such
+     * frame, 1 x 4097 (4097 * 4098) is refused.  No other width has more than 6 visits in a row. */
+    if ((size_t)H * cap > ROW_EXTRAS_MAX) {
+        free(pix); free(count); free(visits);
+        FAIL("a frame %d wide and %d rows tall is not supported: its anomalous lines visit one row %d times (a frame one pixel wide "
+             "is accepted up to 4096 rows)", W, H, cap);
+    }
     sgmd_row_extra* table = (sgmd_row_extra*)calloc((size_t)H * cap, sizeof *table);
     if (!table) { free(pix); free(count); free(visits); FAIL("out of host memory"); }
     memset(count, 0, sizeof(int) * (size_t)H);

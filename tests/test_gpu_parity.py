@@ -377,9 +377,9 @@ def _big_cases():
 
 @pytest.mark.parametrize("case", _big_cases(), ids=lambda c: c["name"])
 def test_full_size_digests(case):
-    """BASELINE.json's two large shapes (2880x1988 D=256 = the maximum volume the library accepts short of 2^32
-    cells; 1762x800 D=192) against digests the REFERENCE produced for every stage (tests/golden/cases_big.json,
-    minutes of CPU time, generated in the build container)."""
+    """BASELINE.json's two large shapes (2880x1988 D=256: 1.47e9 cells, a third of the 2^32 the library accepts and below
+    2^31 -- tests/test_gpu_limits.py has the volumes beyond; 1762x800 D=192) against digests the REFERENCE produced for every
+    stage (tests/golden/cases_big.json, minutes of CPU time, generated in the build container)."""
     import gc
     import soc_project_stereo_matching_amd as S
     w, h, d = case["w"], case["h"], case["d"]
