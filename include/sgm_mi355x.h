@@ -506,6 +506,76 @@ bool   SGM_ReadCloud(const sgm_cloud_spec* spec, sgm_point* points, size_t capac
  * a size < 1 or more than 2^31 - 1 pixels. */
 bool   sgm_rectify_valid_mask(int width, int height, const float* map_x, const float* map_y, uint8_t* mask);
 
+/* ---- matching at half or quarter scale, re-search at full resolution ----
+ * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/scaled_ref.py.  A match at
+ * 1/f scale pays for f^3 fewer cells of W x H x D for the same metric range; the result is brought back to the full grid by a guided
+ * selection and a small search on the FULL-resolution census words.  Off unless called: an instance that never calls one of these
+ * entry points allocates and launches exactly what it did before.
+ *
+ * The low-resolution shape is w = width / f, h = height / f (floor); sgm_scaled_shape (host only) computes it and is false for a
+ * spec outside its ranges or with w < 1 or h < 1.  All images and maps are [frames][rows][columns], frames back to back.
+ *
+ * sgm_downscale: out[j][i] = (sum of the f x f block of `in` at (f j, f i) + f^2 / 2) >> log2(f^2), exact, on u8 (bits == 8) or u16
+ *   samples; trailing rows and columns that do not fill a block are not read.  One image stack per call; no alignment beyond the
+ *   element's.
+ *
+ * sgm_upscale_disparity: for every full-resolution pixel (y, x) of every frame --
+ *   Prior by guided selection (compares and selects only).  ny = 2 y + 1 - f, j0 = floor(ny / 2f), j1 = j0 + 1, ay = ny - 2f j0; the
+ *   same for x gives i0, i1, ax; j0, j1 are then clamped to [0, h) and i0, i1 to [0, w).  The four candidates, in the order (j0,i0),
+ *   (j0,i1), (j1,i0), (j1,i1), carry the weights (2f-ay)(2f-ax), (2f-ay) ax, ay (2f-ax), ay ax.  Among the candidates whose
+ *   low-resolution disparity is finite (by its bit pattern: exponent bits not all ones) the one with the smallest
+ *   |guide_small[j][i] - guide_full[y][x]| is selected; ties go to the larger weight, then to the earlier candidate.  No finite
+ *   candidate: the output is +INF.  prior = f * d_sel (exact).  With radius < 0 the output is prior.
+ *   Re-search (integers).  p = (int)rintf(min(max(prior, -2^20), 2^20)) (round to nearest even; the clamp changes no result, no
+ *   candidate is admitted out there).  Candidates d = p + o, o = -f .. f; one is admitted iff d_lo <= d <= d_hi.  With no admitted
+ *   candidate the output is prior.  A(d) = sum over the (2r+1)^2 window offsets (dy, dx) of t, where q = (y + dy, x + dx),
+ *   xo = q.x - d (left view) or q.x + d (right_view != 0), t = popcount(census_ref[q] ^ census_oth[q.y][xo]), and t = 24 where q is
+ *   outside the frame or xo is outside [0, width).  C(o) = 2 A + penalty |o| (2r+1)^2.  The winner is the admitted o with the
+ *   smallest C; ties go to the smaller |o|, then to the smaller d.
+ *   Sub-pixel.  If o-1 and o+1 are both admitted and den = C(o-1) + C(o+1) - 2 C(o) > 0:
+ *   out = (float)d + (float)(C(o-1) - C(o+1)) / (float)(2 den), float32 operations each rounded on its own, the divide correctly
+ *   rounded; otherwise out = (float)d.
+ *   The guides are grey images of `bits` (u8, or u16 with more than 8 bits, 2-byte aligned); the census planes are u32
+ *   [frames][height][width] of the reference view (the view the map belongs to) and of the other view, and may be NULL with
+ *   radius < 0.  Every column is bounds-checked: nothing outside the planes is read.
+ *
+ * sgm_downscale, sgm_upscale_disparity and sgm_match_scaled_device take device pointers and are asynchronous on sgm_stream(s);
+ * the first two need no initialised instance.  false, nothing queued and a message on stderr: a NULL pointer (but the census planes
+ * with radius < 0), a spec outside the ranges below, a misaligned pointer, a build without the kernels.
+ *
+ * sgm_match_scaled (host pointers, blocking; pinned buffers of sgm_host_alloc are used in place) / sgm_match_scaled_device: the
+ * instance must be initialised at (w, h) with the batch spec->frames and the pixel bits spec->bits.  In order: (1) both views are
+ * downscaled; (2) the instance's ordinary match runs on the small pair, with every option of the instance (census kind, reference
+ * view, four paths, hole filling, refinement, a match without Reset); its final map is the one stage 8 reads back; (3) the census of
+ * both FULL-resolution views is computed by the instance's census kind (5x5 centre, or symmetric with its window; on the u16 samples
+ * with more than 8 bits), every word written, the border 0, into buffers of the call's own: the instance's census planes are
+ * untouched; (4) sgm_upscale_disparity with the reference view's image and its downscaled twin as guides, right_view of the
+ * instance, d_lo = f * min_disparity and d_hi = f * max_disparity - 1 of the instance's option (the spec's d_lo / d_hi are ignored).
+ * Additionally refused: a shape, batch or bits mismatch; row-tile mode; rectification in effect (its maps are for the small shape
+ * and the guide would be unrectified); a wide CENTRE census window (u64 words) with radius >= 0.  Device buffers are reserved at the
+ * first call.  A plain sgm_match on the same instance afterwards returns what it would have returned.
+ * Not part of it: confidence at full resolution, both views, rectification, row tiles, factors other than 2 and 4,
+ * sgm_match_planes. */
+typedef struct {            /* 36 bytes, every field 4 bytes, no padding */
+    int32_t width, height, frames;   /* FULL resolution; 1 <= width, height <= 65535, 1 <= frames <= 65535, frames * width * height <= 2^31 */
+    int32_t factor;                  /* f: 2 or 4 */
+    int32_t bits;                    /* 8: samples are u8;  9..16: samples are u16 (as SGM_SetPixelBits) */
+    int32_t radius;                  /* r: window radius of the re-search, 0..4; < 0: no re-search (guided upscale only) */
+    int32_t penalty;                 /* pull toward the prior, 0..16, in half Hamming bits per window pixel per step */
+    int32_t d_lo, d_hi;              /* admitted full-resolution disparities, inclusive, 0 <= d_lo <= d_hi <= 65535 */
+} sgm_scale_spec;
+#define SGM_SCALE_DEFAULT_RADIUS 3
+#define SGM_SCALE_DEFAULT_PENALTY 1
+bool   sgm_scaled_shape(const sgm_scale_spec* spec, int* w, int* h);
+bool   sgm_downscale(sgm_instance* s, const sgm_scale_spec* spec, const void* d_in, void* d_out);
+bool   sgm_upscale_disparity(sgm_instance* s, const sgm_scale_spec* spec, const float* d_disp_small, const void* d_guide_small,
+                             const void* d_guide_full, const uint32_t* d_census_ref, const uint32_t* d_census_oth, int right_view,
+                             float* d_disp_full);
+bool   sgm_match_scaled(sgm_instance* s, const sgm_scale_spec* spec, const uint8_t* img_left, const uint8_t* img_right, float* disp_full);
+bool   sgm_match_scaled_device(sgm_instance* s, const sgm_scale_spec* spec, const uint8_t* d_left, const uint8_t* d_right,
+                               float* d_disp_full);
+bool   SGM_MatchScaled(const sgm_scale_spec* spec, const uint8_t* img_left, const uint8_t* img_right, float* disp_full);   /* the default instance */
+
 /* The filling of SGM_SetFillHoles (step 2) on any device map: d_disp, the instance's B frames of its shape, is filled in
  * place with R = the option's max_disparity; d_class (u8 [B][H][W], classes 0/1/2) drives passes 1 and 2, NULL runs pass 3
  * alone.  Asynchronous on sgm_stream(s), behind the last match.  Works whether or not filling is on for matches; the filled

@@ -276,6 +276,21 @@ int sgmd_cloud_organized(int ord, void* stream, const sgmd_cloud* c, const void*
 int sgmd_cloud_points(int ord, void* stream, const sgmd_cloud* c, const void* disp, const void* mask, const void* conf, void* scratch,
                       void* points, void* offsets);
 
+/* Extension (parity unpinned by the reference), matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); sgm_scale.hip.
+ * c: the spec as the host validated it (W, H: FULL resolution; the low resolution is W / f x H / f).  sgmd_downscale: the f x f box
+ * mean with rounding of one image stack, u8 (bits == 8) or u16 [B][H][W] -> [B][H / f][W / f]; trailing rows and columns are not
+ * read; no alignment beyond the element's.  sgmd_upscale: disp_full f32 [B][H][W] from disp_small f32 and guide_small [B][H / f][W / f],
+ * guide_full and the u32 census planes of the reference and the other view [B][H][W] (unused, may be NULL, with radius < 0); every
+ * census column is bounds-checked, nothing in front of a plane is read.  sgm_host.c references both weakly (a host built without
+ * them answers false to the scaled entry points). */
+typedef struct {
+    int W, H, B;
+    int f, bits, radius, penalty, d_lo, d_hi, right;
+} sgmd_scale;
+int sgmd_downscale(int ord, void* stream, const sgmd_scale* c, const void* in, void* out);
+int sgmd_upscale(int ord, void* stream, const sgmd_scale* c, const void* disp_small, const void* guide_small, const void* guide_full,
+                 const void* census_ref, const void* census_oth, void* disp_full);
+
 /* grey = (weight_r r + 150 g + 29 b) >> 8 of three consecutive n-byte planes B, G, R (the test platform's frame
  * format, server.py:105-131; the firmware's conversion, stereo_matching.c:18-25) */
 int sgmd_gray_planes(int ord, void* stream, const void* bgr, size_t n, int weight_r, void* gray);

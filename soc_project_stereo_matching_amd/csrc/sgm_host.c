@@ -155,6 +155,11 @@ struct sgm_instance {
     /* point clouds (sgm_cloud_points / sgm_read_cloud; allocated at the first such call): the tile counts and bases of the point list's
      * three launches, and the list and offsets sgm_read_cloud makes on the device before it copies them */
     sgm_buf d_cloud_scratch, d_cloud_points, d_cloud_offsets;
+    /* matching at 1/f scale (sgm_match_scaled; allocated at its first use): the downscaled views, the census planes of the
+     * FULL-resolution views with the narrowed images sgmd_census16 writes beside them, and for the host-pointer form the full
+     * images, the full map and their page-locked staging */
+    sgm_buf d_sc_small_l, d_sc_small_r, d_sc_census_l, d_sc_census_r, d_sc_g8_l, d_sc_g8_r, d_sc_full_l, d_sc_full_r, d_sc_disp;
+    sgm_buf h_sc_l, h_sc_r, h_sc_disp;
     bool last_both;              /* the last match was a sgm_match_both that was queued to its end: stage 8 is the first half of d_both_maps */
     bool last_both_kept;         /* ... and it ran with sgm_keep_stages: d_both_snap holds ITS right-view snapshots (stages 26, 27) */
     size_t plane_bytes;
@@ -185,6 +190,9 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     DEVICE_BUF(d_both_maps), DEVICE_BUF(d_both_labels), DEVICE_BUF(d_both_sizes), DEVICE_BUF(d_both_totals), DEVICE_BUF(d_both_median),
     DEVICE_BUF(d_both_snap), PINNED_BUF(h_disp_r), DEVICE_BUF(d_rect_maps), DEVICE_BUF(d_rect_l), DEVICE_BUF(d_rect_r),
     DEVICE_BUF(d_cloud_scratch), DEVICE_BUF(d_cloud_points), DEVICE_BUF(d_cloud_offsets), DEVICE_BUF(d_g8_l), DEVICE_BUF(d_g8_r),
+    DEVICE_BUF(d_sc_small_l), DEVICE_BUF(d_sc_small_r), DEVICE_BUF(d_sc_census_l), DEVICE_BUF(d_sc_census_r), DEVICE_BUF(d_sc_g8_l),
+    DEVICE_BUF(d_sc_g8_r), DEVICE_BUF(d_sc_full_l), DEVICE_BUF(d_sc_full_r), DEVICE_BUF(d_sc_disp), PINNED_BUF(h_sc_l), PINNED_BUF(h_sc_r),
+    PINNED_BUF(h_sc_disp),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -2032,6 +2040,172 @@ bool sgm_read_cloud(sgm_instance* s, const sgm_cloud_spec* spec, sgm_point* poin
     return sgmd_d2h_async(s->device, s->stream, points, s->d_cloud_points.p, total * sizeof(sgm_point)) == 0 && sync_streams(s) == 0;
 }
 
+/* ------------------------------------------------------------------ matching at 1/f scale (extension) */
+
+/* The launchers of sgm_scale.hip, weakly referenced like the extensions above: a host built without them has no scaled match */
+#pragma weak sgmd_downscale
+#pragma weak sgmd_upscale
+static bool scale_available(void) { return sgmd_downscale != NULL && sgmd_upscale != NULL; }
+
+/* the spec as the kernels take it; false for anything outside the ranges of include/sgm_mi355x.h */
+static bool scale_spec_valid(const sgm_scale_spec* sp, sgmd_scale* c)
+{
+    if (!sp || sp->width < 1 || sp->width > 65535 || sp->height < 1 || sp->height > 65535 || sp->frames < 1 || sp->frames > 65535 ||
+        (long long)sp->frames * sp->width * sp->height > (1LL << 31))
+        return false;
+    if ((sp->factor != 2 && sp->factor != 4) || sp->width / sp->factor < 1 || sp->height / sp->factor < 1) return false;
+    if (sp->bits < 8 || sp->bits > 16 || sp->radius > 4 || sp->penalty < 0 || sp->penalty > 16) return false;
+    if (sp->d_lo < 0 || sp->d_lo > sp->d_hi || sp->d_hi > 65535) return false;
+    if (c) *c = (sgmd_scale){sp->width, sp->height, sp->frames, sp->factor, sp->bits, sp->radius < 0 ? -1 : sp->radius, sp->penalty,
+                             sp->d_lo, sp->d_hi, 0};
+    return true;
+}
+
+bool sgm_scaled_shape(const sgm_scale_spec* spec, int* w, int* h)
+{
+    if (!w || !h || !scale_spec_valid(spec, NULL)) return false;
+    *w = spec->width / spec->factor;
+    *h = spec->height / spec->factor;
+    return true;
+}
+
+/* what every scaled entry point checks first */
+static bool scale_ready(sgm_instance* s, const sgm_scale_spec* spec, bool pointers, sgmd_scale* c)
+{
+    if (!s || !spec || !pointers) FAIL("a scaled entry point was given a NULL pointer");
+    if (!scale_available()) FAIL("matching at 1/f scale is not part of this build");
+    if (!scale_spec_valid(spec, c)) FAIL("the scale spec is outside its ranges (include/sgm_mi355x.h, sgm_scale_spec)");
+    return true;
+}
+
+static bool samples_aligned(const sgmd_scale* c, const void* a, const void* b)
+{
+    if (c->bits > 8 && (((uintptr_t)a | (uintptr_t)b) & 1u)) FAIL("device images of %d bits per sample must be 2-byte aligned", c->bits);
+    return true;
+}
+
+bool sgm_downscale(sgm_instance* s, const sgm_scale_spec* spec, const void* d_in, void* d_out)
+{
+    sgmd_scale c;
+    if (!scale_ready(s, spec, d_in && d_out, &c) || !samples_aligned(&c, d_in, d_out)) return false;
+    return sgmd_downscale(s->device, s->stream, &c, d_in, d_out) == 0;
+}
+
+bool sgm_upscale_disparity(sgm_instance* s, const sgm_scale_spec* spec, const float* d_disp_small, const void* d_guide_small,
+                           const void* d_guide_full, const uint32_t* d_census_ref, const uint32_t* d_census_oth, int right_view,
+                           float* d_disp_full)
+{
+    sgmd_scale c;
+    const bool planes = (spec && spec->radius < 0) || (d_census_ref && d_census_oth);
+    if (!scale_ready(s, spec, d_disp_small && d_guide_small && d_guide_full && d_disp_full && planes, &c) ||
+        !samples_aligned(&c, d_guide_small, d_guide_full))
+        return false;
+    if (((uintptr_t)d_disp_small | (uintptr_t)d_disp_full | (uintptr_t)d_census_ref | (uintptr_t)d_census_oth) & 3u)
+        FAIL("the maps and census planes of sgm_upscale_disparity must be 4-byte aligned");
+    c.right = right_view ? 1 : 0;
+    /* the small map may be the result of a match whose last stages run on a stream of their own */
+    if (wait_for_result(s, s->stream) != 0) return false;
+    return sgmd_upscale(s->device, s->stream, &c, d_disp_small, d_guide_small, d_guide_full, d_census_ref, d_census_oth, d_disp_full) == 0;
+}
+
+/* The composed match on device images (include/sgm_mi355x.h): downscale, the instance's match, the full-resolution census, the
+ * upscale with re-search.  Everything is queued on the instance's stream but what the match itself puts elsewhere; later matches
+ * write d_disp only behind an event of this stream (run_pipeline), so stream order keeps them behind the upscale's reads. */
+static bool scaled_ready(sgm_instance* s, const sgm_scale_spec* spec, const void* l, const void* r, const void* out, sgmd_scale* c)
+{
+    if (!scale_ready(s, spec, l && r && out, c)) return false;
+    if (!s->initialized) FAIL("sgm_match_scaled needs an instance initialised at the low-resolution shape");
+    if (row_tiled(s)) FAIL("sgm_match_scaled works on whole frames: not available in row-tile mode (sgm_set_rows)");
+    const int w = c->W / c->f, h = c->H / c->f;
+    if (s->g.W != w || s->g.H != h || s->g.B != c->B || s->pixel_bits != c->bits)
+        FAIL("the scale spec asks for %d frames of %dx%d at %d bits, the instance is initialised for %d of %dx%d at %d", c->B, w, h, c->bits,
+             s->g.B, s->g.W, s->g.H, s->pixel_bits);
+    if (s->rect_on) FAIL("sgm_match_scaled does not combine with rectification: its maps are for the small shape");
+    if (c->radius >= 0 && volume_fed(s)) FAIL("the re-search reads u32 census words: not available with a wide CENTRE census window");
+    if (c->radius >= 0 && ((c->bits > 8 && !sgmd_census16) || (c->bits == 8 && census_symmetric(s) && !sgmd_census_sym)))
+        FAIL("the census of this instance is not part of this build");
+    c->right = s->reference_view;
+    c->d_lo = c->f * s->opt.min_disparity;
+    c->d_hi = c->f * s->opt.max_disparity - 1;
+    return true;
+}
+
+static bool scaled_queue(sgm_instance* s, const sgmd_scale* c, const void* d_left, const void* d_right, void* d_out)
+{
+    const size_t es = c->bits > 8 ? 2 : 1, px = (size_t)c->B * c->W * c->H;
+    const bool search = c->radius >= 0;
+    const buf_request bufs[] = {{&s->d_sc_small_l, image_bytes(s), 0}, {&s->d_sc_small_r, image_bytes(s), 0},
+                                {&s->d_sc_census_l, search ? px * 4 : 0, 0}, {&s->d_sc_census_r, search ? px * 4 : 0, 0},
+                                {&s->d_sc_g8_l, search && es == 2 ? px : 0, 0}, {&s->d_sc_g8_r, search && es == 2 ? px : 0, 0}};
+    int n = 0;
+    buf_request need[6];
+    for (int i = 0; i < 6; ++i)
+        if (bufs[i].bytes) need[n++] = bufs[i];
+    if (!reserve_all(s, need, n, 0)) FAIL("device allocation failed for the scaled match of %d frames of %dx%d", c->B, c->W, c->H);
+    const int dev = s->device;
+    void* st = s->stream;
+    if (sgmd_downscale(dev, st, c, d_left, s->d_sc_small_l.p) != 0 || sgmd_downscale(dev, st, c, d_right, s->d_sc_small_r.p) != 0)
+        FAIL("the downscale launch failed; the scaled match was abandoned");
+    if (!run_pipeline(s, s->d_sc_small_l.p, s->d_sc_small_r.p, s->d_disp.p, NULL, NULL)) return false;
+    if (search) {
+        /* the census of the full-resolution views, by the instance's kind: every word written, the border 0 */
+        sgmd_geom gf = s->g;
+        gf.W = c->W; gf.H = c->H;
+        gf.row_begin = 0; gf.row_end = c->H;
+        const int cw = s->census_w ? s->census_w : 5, ch = s->census_h ? s->census_h : 5;
+        int rc;
+        if (es == 2)
+            rc = sgmd_census16(dev, st, &gf, c->bits, census_symmetric(s), cw, ch, d_left, d_right, s->d_sc_census_l.p, s->d_sc_census_r.p,
+                               s->d_sc_g8_l.p, s->d_sc_g8_r.p);
+        else if (census_symmetric(s))
+            rc = sgmd_census_sym(dev, st, &gf, cw, ch, d_left, d_right, s->d_sc_census_l.p, s->d_sc_census_r.p, NULL);
+        else
+            rc = sgmd_census(dev, st, &gf, d_left, d_right, s->d_sc_census_l.p, s->d_sc_census_r.p, NULL, 0);
+        if (rc != 0) FAIL("the full-resolution census launch failed; the scaled match was abandoned");
+    }
+    if (wait_for_result(s, st) != 0) return false;
+    const bool right = c->right != 0;
+    if (sgmd_upscale(dev, st, c, s->d_disp.p, right ? s->d_sc_small_r.p : s->d_sc_small_l.p, right ? d_right : d_left,
+                     search ? (right ? s->d_sc_census_r.p : s->d_sc_census_l.p) : NULL,
+                     search ? (right ? s->d_sc_census_l.p : s->d_sc_census_r.p) : NULL, d_out) != 0)
+        FAIL("the upscale launch failed; the scaled match was abandoned");
+    return true;
+}
+
+bool sgm_match_scaled_device(sgm_instance* s, const sgm_scale_spec* spec, const uint8_t* d_left, const uint8_t* d_right, float* d_disp_full)
+{
+    sgmd_scale c;
+    if (!scaled_ready(s, spec, d_left, d_right, d_disp_full, &c) || !samples_aligned(&c, d_left, d_right)) return false;
+    if ((uintptr_t)d_disp_full & 3u) FAIL("the map of sgm_match_scaled_device must be 4-byte aligned");
+    if (!sgm_match_wait(s)) return false;                        /* an earlier host-pointer match still copies out of d_disp */
+    return scaled_queue(s, &c, d_left, d_right, d_disp_full);
+}
+
+bool sgm_match_scaled(sgm_instance* s, const sgm_scale_spec* spec, const uint8_t* img_left, const uint8_t* img_right, float* disp_full)
+{
+    sgmd_scale c;
+    if (!scaled_ready(s, spec, img_left, img_right, disp_full, &c) || !sgm_match_wait(s)) return false;
+    const size_t px = (size_t)c.B * c.W * c.H, img = px * (c.bits > 8 ? 2 : 1), map = px * sizeof(float);
+    const bool pin_l = sgmd_host_is_pinned(s->device, img_left, img) != 0, pin_r = sgmd_host_is_pinned(s->device, img_right, img) != 0;
+    const bool pin_out = sgmd_host_is_pinned(s->device, disp_full, map) != 0;
+    const buf_request bufs[] = {{&s->d_sc_full_l, img, 0}, {&s->d_sc_full_r, img, 0}, {&s->d_sc_disp, map, 0},
+                                {&s->h_sc_l, pin_l ? 0 : img, BUF_PINNED}, {&s->h_sc_r, pin_r ? 0 : img, BUF_PINNED},
+                                {&s->h_sc_disp, pin_out ? 0 : map, BUF_PINNED}};
+    int n = 0;
+    buf_request need[6];
+    for (int i = 0; i < 6; ++i)
+        if (bufs[i].bytes) need[n++] = bufs[i];
+    if (!reserve_all(s, need, n, 0)) FAIL("allocation failed for the scaled match of %d frames of %dx%d", c.B, c.W, c.H);
+    void* back = pin_out ? (void*)disp_full : s->h_sc_disp.p;
+    const bool ok = upload(s, s->d_sc_full_l.p, img_left, s->h_sc_l.p, img) && upload(s, s->d_sc_full_r.p, img_right, s->h_sc_r.p, img) &&
+                    scaled_queue(s, &c, s->d_sc_full_l.p, s->d_sc_full_r.p, s->d_sc_disp.p) &&
+                    sgmd_d2h_async(s->device, s->stream, back, s->d_sc_disp.p, map) == 0;
+    /* also after a failure: queued copies may still read the caller's / the staging buffers */
+    if (!sgm_synchronize(s) || !ok) return false;
+    if (!pin_out) memcpy(disp_full, back, map);
+    return true;
+}
+
 /* ------------------------------------------------------------------ hole filling of any map (extension) */
 
 bool sgm_fill_holes(sgm_instance* s, float* d_disp, const uint8_t* d_class)
@@ -2393,6 +2567,11 @@ size_t SGM_ReadStage(int which, void* host_out, size_t capacity)
 bool SGM_ReadCloud(const sgm_cloud_spec* spec, sgm_point* points, size_t capacity, uint32_t* offsets)
 {
     return g_default ? sgm_read_cloud(g_default, spec, points, capacity, offsets) : false;
+}
+
+bool SGM_MatchScaled(const sgm_scale_spec* spec, const uint8_t* img_left, const uint8_t* img_right, float* disp_full)
+{
+    return g_default ? sgm_match_scaled(g_default, spec, img_left, img_right, disp_full) : false;
 }
 
 void SGM_KeepStages(int enable)

@@ -31,6 +31,12 @@
  *                             unshifted) and matched on all their bits.  --bits 0: the smallest N >= 8 that holds the files' maxval.
  *                             Default 8, which refuses a 16-bit file.  With --bits above 8, --rectified-out writes 16-bit PGMs and
  *                             the cloud's colour is the narrowed image's
+ *            [--scale F [--scale-radius R] [--scale-penalty P]]   extension: match at 1/F scale (F = 2 or 4) and bring the map back
+ *                             to the full grid with the re-search on the full-resolution census (SGM_MatchScaled; R and P default to
+ *                             SGM_SCALE_DEFAULT_RADIUS / _PENALTY, R < 0: the guided upscale alone).  --min-disparity and
+ *                             --max-disparity stay in full-resolution pixels: the match runs at W / F x H / F with min / F (floor)
+ *                             and max / F (ceil).  OUT and --raw are the full-resolution map.  Not with --cloud, --confidence,
+ *                             --right-out / --right-raw or --rectify
  *   sgm_main --convert IN OUT.png        (image I/O only, no GPU: used by the CPU tests)
  *   sgm_main --convert16 IN OUT.pgm      (the same through sgm_load_gray16 and the 16-bit PGM writer; prints the file's maxval)
  */
@@ -159,6 +165,7 @@ int main(int argc, char** argv)
     int have_pinhole = 0;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
     int census_kind = SGM_CENSUS_CENTRE, bits = 8;
+    int scale = 0, scale_radius = SGM_SCALE_DEFAULT_RADIUS, scale_penalty = SGM_SCALE_DEFAULT_PENALTY, scale_tuned = 0;
     float refine_lambda = SGM_REFINE_DEFAULT_LAMBDA, refine_sigma = SGM_REFINE_DEFAULT_SIGMA;
     int refine_iters = SGM_REFINE_DEFAULT_ITERS;
     for (int i = 4; i < argc; ++i) {
@@ -197,6 +204,13 @@ int main(int argc, char** argv)
             if (bits != 0 && (bits < 8 || bits > 16)) { fprintf(stderr, "--bits wants 8..16, or 0 for what the files hold\n"); return 2; }
             ++i;
         }
+        else if (v && !strcmp(a, "--scale")) {
+            scale = atoi(v);
+            if (scale != 2 && scale != 4) { fprintf(stderr, "--scale wants 2 or 4\n"); return 2; }
+            ++i;
+        }
+        else if (v && !strcmp(a, "--scale-radius")) { scale_radius = atoi(v); scale_tuned = 1; ++i; }
+        else if (v && !strcmp(a, "--scale-penalty")) { scale_penalty = atoi(v); scale_tuned = 1; ++i; }
         else if (v && !strcmp(a, "--paths")) { opt.num_paths = (uint8_t)atoi(v); SGM_SetHonorNumPaths(1); ++i; }
         else if (v && !strcmp(a, "--census")) {
             if (sscanf(v, "%dx%d", &census_w, &census_h) != 2) { fprintf(stderr, "--census wants WxH, e.g. 7x7\n"); return 2; }
@@ -223,6 +237,16 @@ int main(int argc, char** argv)
     if ((right_out || right_raw) && (conf_path || fill_holes || refine || right_ref)) {
         fprintf(stderr, "--right-out / --right-raw do not combine with --confidence, --fill-holes, --refine or --right-reference "
                         "(OUT would silently be the left map)\n");
+        return 2;
+    }
+    if (scale && (cloud_path || conf_path || right_out || right_raw || calib_path)) {
+        fprintf(stderr, "--scale does not combine with --cloud, --confidence, --right-out / --right-raw or --rectify "
+                        "(they work on the low-resolution match)\n");
+        return 2;
+    }
+    if (scale_tuned && !scale) { fprintf(stderr, "--scale-radius / --scale-penalty need --scale\n"); return 2; }
+    if (scale && (scale_radius > 4 || scale_penalty < 0 || scale_penalty > 16)) {
+        fprintf(stderr, "--scale-radius wants at most 4 (negative: no re-search), --scale-penalty 0..16\n");
         return 2;
     }
     if (rect_out[0] && !calib_path) { fprintf(stderr, "--rectified-out needs --rectify\n"); return 2; }
@@ -276,16 +300,27 @@ int main(int argc, char** argv)
         free(maps);
         if (!ok) { printf("rectification unavailable or a bad calibration file\n"); return -2; }
     }
-    if (!SGM_Initialize((uint16_t)w1, (uint16_t)h1, &opt)) { printf("SGM initialization failed\n"); return -2; }
+    /* --scale: the instance works at the low resolution, on the disparities of that resolution */
+    int wm = w1, hm = h1;
+    sgm_scale_spec scale_spec = {w1, h1, 1, scale, bits, scale_radius, scale_penalty, 0, 65535};
+    if (scale) {
+        if (!sgm_scaled_shape(&scale_spec, &wm, &hm)) { printf("the images are too small for --scale %d\n", scale); return -2; }
+        opt.min_disparity = (uint16_t)(opt.min_disparity / scale);
+        opt.max_disparity = (uint16_t)((opt.max_disparity + scale - 1) / scale);
+        printf("scale %d: matching %d x %d, d = [%d,%d], radius %d, penalty %d\n", scale, wm, hm, opt.min_disparity, opt.max_disparity,
+               scale_radius, scale_penalty);
+    }
+    if (!SGM_Initialize((uint16_t)wm, (uint16_t)hm, &opt)) { printf("SGM initialization failed\n"); return -2; }
     float* disp = (float*)malloc(sizeof(float) * (size_t)w1 * h1);
     float* disp_r = (right_out || right_raw) ? (float*)malloc(sizeof(float) * (size_t)w1 * h1) : NULL;
     uint16_t* conf = conf_path ? (uint16_t*)malloc(sizeof(uint16_t) * (size_t)w1 * h1) : NULL;
     double best = 1e30;
     for (int r = 0; r < repeat; ++r) {
         const double t0 = now_ms();
-        if (r > 0 && !SGM_Reset((uint16_t)w1, (uint16_t)h1, &opt)) { printf("SGM reset failed\n"); return -2; }
-        const bool ok = disp_r ? SGM_MatchBoth(left, right, disp, disp_r)
-                               : (conf ? SGM_MatchConfidence(left, right, disp, conf) : SGM_Match(left, right, disp));
+        if (r > 0 && !SGM_Reset((uint16_t)wm, (uint16_t)hm, &opt)) { printf("SGM reset failed\n"); return -2; }
+        const bool ok = scale ? SGM_MatchScaled(&scale_spec, left, right, disp)
+                              : disp_r ? SGM_MatchBoth(left, right, disp, disp_r)
+                                       : (conf ? SGM_MatchConfidence(left, right, disp, conf) : SGM_Match(left, right, disp));
         if (!ok) { printf("SGM matching failed\n"); return -2; }
         const double t = now_ms() - t0;
         if (t < best) best = t;

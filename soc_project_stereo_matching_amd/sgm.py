@@ -71,6 +71,31 @@ def cloud_spec(width, height, fx, fy, cx, cy, baseline, doffs=0.0, frames=1, z_m
     return SGMCloudSpec(int(width), int(height), int(frames), fx, fy, cx, cy, baseline, doffs, z_min, z_max, int(min_conf))
 
 
+class SGMScaleSpec(C.Structure):
+    """Field-for-field sgm_scale_spec of include/sgm_mi355x.h: 36 bytes, every field 4 bytes."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("frames", C.c_int32),
+        ("factor", C.c_int32), ("bits", C.c_int32), ("radius", C.c_int32), ("penalty", C.c_int32),
+        ("d_lo", C.c_int32), ("d_hi", C.c_int32),
+    ]
+
+
+SCALE_DEFAULT_RADIUS, SCALE_DEFAULT_PENALTY = 3, 1
+
+
+def scale_spec(width, height, factor, frames=1, bits=8, radius=SCALE_DEFAULT_RADIUS, penalty=SCALE_DEFAULT_PENALTY, d_lo=0,
+               d_hi=65535) -> SGMScaleSpec:
+    """A sgm_scale_spec for FULL-resolution frames of width x height, matched at 1 / factor."""
+    return SGMScaleSpec(int(width), int(height), int(frames), int(factor), int(bits), int(radius), int(penalty), int(d_lo), int(d_hi))
+
+
+def scaled_shape(spec: SGMScaleSpec):
+    """sgm_scaled_shape: (w, h) of the low-resolution frames, or None for a spec the library refuses.  Host only."""
+    w, h = C.c_int(0), C.c_int(0)
+    ok = load_library().sgm_scaled_shape(C.byref(spec), C.byref(w), C.byref(h))
+    return (w.value, h.value) if ok else None
+
+
 def default_option(max_disparity=64, min_disparity=0, **kw) -> SGMOption:
     """The option values the reference's driver sets (main.c:48-65), with overrides."""
     o = SGMOption()
@@ -194,6 +219,19 @@ def _load() -> C.CDLL:
         L.sgm_rectify.restype = C.c_bool
         L.sgm_rectify_maps.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.sgm_rectify_maps.restype = C.c_bool
+    if hasattr(L, "sgm_match_scaled"):
+        L.sgm_scaled_shape.argtypes = [C.c_void_p] * 3
+        L.sgm_scaled_shape.restype = C.c_bool
+        L.sgm_downscale.argtypes = [C.c_void_p] * 4
+        L.sgm_downscale.restype = C.c_bool
+        L.sgm_upscale_disparity.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
+        L.sgm_upscale_disparity.restype = C.c_bool
+        L.sgm_match_scaled.argtypes = [C.c_void_p] * 5
+        L.sgm_match_scaled.restype = C.c_bool
+        L.sgm_match_scaled_device.argtypes = [C.c_void_p] * 5
+        L.sgm_match_scaled_device.restype = C.c_bool
+        L.SGM_MatchScaled.argtypes = [C.c_void_p] * 4
+        L.SGM_MatchScaled.restype = C.c_bool
     if hasattr(L, "sgm_cloud_points"):        # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_cloud_organized.argtypes = [C.c_void_p] * 6
         L.sgm_cloud_organized.restype = C.c_bool
@@ -573,6 +611,17 @@ class SGM(_StageReader):
         where the C call returns false.  The contract is in include/sgm_mi355x.h (sgm_cloud_spec)."""
         return _read_cloud(self.lib.SGM_ReadCloud, spec)
 
+    def match_scaled(self, spec: SGMScaleSpec, left, right):
+        """SGM_MatchScaled: one FULL-resolution pair through the default instance, initialised at the low-resolution shape; the
+        full-resolution float32 map, or None where the C call returns false (include/sgm_mi355x.h, sgm_scale_spec)."""
+        left, right = self._img(left, spec.bits), self._img(right, spec.bits)
+        want = (spec.height, spec.width)
+        if tuple(left.shape) != want or tuple(right.shape) != want:
+            raise ValueError(f"expected images of shape {want}, got {left.shape} and {right.shape}")
+        out = np.empty(want, np.float32)
+        ok = self.lib.SGM_MatchScaled(C.byref(spec), left.ctypes.data, right.ctypes.data, out.ctypes.data)
+        return out if ok else None
+
     def shutdown(self):
         self.lib.SGM_Shutdown()
 
@@ -931,6 +980,33 @@ class SGMInstance(_StageReader):
         """sgm_read_cloud: (points as POINT_DTYPE records, offsets uint32 [frames + 1]) of the last match's final map, no mask,
         no confidence; blocking.  None where the C call returns false."""
         return _read_cloud(lambda *a: self.lib.sgm_read_cloud(self.handle, *a), spec)
+
+    # ---- matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); device pointers as ints, None = NULL ----
+    def downscale(self, spec: SGMScaleSpec, d_in: int, d_out: int) -> bool:
+        """sgm_downscale: the f x f box mean of one image stack [frames][H][W] -> [frames][H / f][W / f].  Asynchronous on `stream`."""
+        return bool(self.lib.sgm_downscale(self.handle, C.byref(spec), d_in, d_out))
+
+    def upscale_disparity(self, spec: SGMScaleSpec, d_disp_small: int, d_guide_small: int, d_guide_full: int, d_census_ref,
+                          d_census_oth, right_view: bool, d_disp_full: int) -> bool:
+        """sgm_upscale_disparity: the guided selection and the re-search on the full-resolution census planes (None with a negative
+        radius).  Asynchronous on `stream`."""
+        return bool(self.lib.sgm_upscale_disparity(self.handle, C.byref(spec), d_disp_small, d_guide_small, d_guide_full,
+                                                   d_census_ref or None, d_census_oth or None, 1 if right_view else 0, d_disp_full))
+
+    def match_scaled(self, spec: SGMScaleSpec, left, right):
+        """sgm_match_scaled: FULL-resolution images ([H][W], or [frames][H][W] with a batch) through an instance initialised at the
+        low-resolution shape; the full-resolution float32 map, or None where the C call returns false."""
+        left, right = self._img(left, spec.bits), self._img(right, spec.bits)
+        want = (spec.height, spec.width) if spec.frames == 1 and left.ndim == 2 else (spec.frames, spec.height, spec.width)
+        if tuple(left.shape) != want or tuple(right.shape) != want:
+            raise ValueError(f"expected images of shape {want}, got {left.shape} and {right.shape}")
+        out = np.empty(want, np.float32)
+        ok = self.lib.sgm_match_scaled(self.handle, C.byref(spec), left.ctypes.data, right.ctypes.data, out.ctypes.data)
+        return out if ok else None
+
+    def match_scaled_device(self, spec: SGMScaleSpec, d_left: int, d_right: int, d_out: int) -> bool:
+        """sgm_match_scaled_device: the same on device buffers, asynchronous on `stream`."""
+        return bool(self.lib.sgm_match_scaled_device(self.handle, C.byref(spec), d_left, d_right, d_out))
 
     def compare_depth(self, d_ground_truth: int, d_test: int, count: int, abs_thresh: float = 10.0):
         """(rmse, bad_pixel_rate, n_valid) of two device depth images; None where the C call returns false."""

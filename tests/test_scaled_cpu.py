@@ -1,0 +1,690 @@
+"""Matching at 1/f scale (extension; include/sgm_mi355x.h, sgm_scale_spec) without a GPU: the numpy restatement tests/scaled_ref.py
+against a plain double loop of the header's text, the struct layout in header, library and Python, the C host on the stand-in
+device (tests/stub_device.c + tests/stub_scale.c: refusals, the launch order of the composed call, an untouched instance, refused
+launches), a stand-alone ASan / UBSan driver, the command-line driver's option arithmetic, and the quality of the definition on
+the three golden scenes.  Parity unpinned by the reference; tolerance 0 wherever two implementations are compared."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import scaled_ref as SR
+import standin
+from conftest import GOLDEN, ROOT, load_npz, option_from_dict
+
+INF = np.float32(np.inf)
+TESTS = os.path.join(ROOT, "tests")
+STUB_SCALE = os.path.join(TESTS, "stub_scale.c")
+STUB_P16 = os.path.join(TESTS, "stub_pixels16.c")
+STUB_RECT = os.path.join(TESTS, "stub_rectify.c")
+_p, _i, _b, _z = C.c_void_p, C.c_int, C.c_bool, C.c_size_t
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+# ---- the restatement against a plain double loop ------------------------------------------------------------------------------
+
+def popcount(v):
+    return bin(int(v)).count("1")
+
+
+def finite(v):
+    return (int(np.float32(v).view(np.uint32)) & 0x7F800000) != 0x7F800000
+
+
+def loop_downscale(img, f):
+    H, W = img.shape
+    h, w = H // f, W // f
+    out = np.zeros((h, w), img.dtype)
+    for j in range(h):
+        for i in range(w):
+            total = sum(int(img[f * j + r, f * i + c]) for r in range(f) for c in range(f))
+            out[j, i] = (total + f * f // 2) >> {2: 2, 4: 4}[f]
+    return out
+
+
+def loop_upscale(small, g_small, g_full, c_ref, c_oth, f, radius, penalty, d_lo, d_hi, right):
+    """sgm_upscale_disparity as the header words it, one pixel at a time"""
+    H, W = g_full.shape
+    h, w = small.shape
+    out = np.zeros((H, W), np.float32)
+    for y in range(H):
+        for x in range(W):
+            ny, nx = 2 * y + 1 - f, 2 * x + 1 - f
+            j0, i0 = ny // (2 * f), nx // (2 * f)                    # Python's // is the floor
+            ay, ax = ny - 2 * f * j0, nx - 2 * f * i0
+            j1, i1 = j0 + 1, i0 + 1
+            j0, j1 = (min(max(j, 0), h - 1) for j in (j0, j1))
+            i0, i1 = (min(max(i, 0), w - 1) for i in (i0, i1))
+            cands = [(j0, i0, (2 * f - ay) * (2 * f - ax)), (j0, i1, (2 * f - ay) * ax), (j1, i0, ay * (2 * f - ax)), (j1, i1, ay * ax)]
+            best = None
+            for order, (j, i, wgt) in enumerate(cands):
+                if not finite(small[j, i]):
+                    continue
+                key = (abs(int(g_small[j, i]) - int(g_full[y, x])), -wgt, order)
+                if best is None or key < best[0]:
+                    best = (key, small[j, i])
+            if best is None:
+                out[y, x] = INF
+                continue
+            prior = np.float32(f) * np.float32(best[1])
+            out[y, x] = prior
+            if radius < 0:
+                continue
+            p = int(np.rint(min(max(prior, -SR.PRIOR_MAX), SR.PRIOR_MAX)))
+            cost = {}
+            for o in range(-f, f + 1):
+                d = p + o
+                if not d_lo <= d <= d_hi:
+                    continue
+                A = 0
+                for dy in range(-radius, radius + 1):
+                    for dx in range(-radius, radius + 1):
+                        qy, qx = y + dy, x + dx
+                        xo = qx + d if right else qx - d
+                        if 0 <= qy < H and 0 <= qx < W and 0 <= xo < W:
+                            A += popcount(c_ref[qy, qx] ^ c_oth[qy, xo])
+                        else:
+                            A += SR.OUTSIDE
+                cost[o] = 2 * A + penalty * abs(o) * (2 * radius + 1) ** 2
+            if not cost:
+                continue
+            o = min(cost, key=lambda k: (cost[k], abs(k), k))
+            v = np.float32(p + o)
+            if o - 1 in cost and o + 1 in cost:
+                den = cost[o - 1] + cost[o + 1] - 2 * cost[o]
+                if den > 0:
+                    v = np.float32(v + np.float32(np.float32(cost[o - 1] - cost[o + 1]) / np.float32(2 * den)))
+            out[y, x] = v
+    return out
+
+
+def planted(rng, W, H, f, bits, flat_census):
+    """holes (+INF, NaN, -INF), quarter-pixel values that reach past both ends of the admitted range and past the pixel's own
+    column, guides of four grey values (candidates tie), random census words or one constant (every cost ties)"""
+    w, h = W // f, H // f
+    dt = np.uint16 if bits > 8 else np.uint8
+    small = (rng.integers(-4, 4 * 14 // f + 1, (h, w)) / 4.0).astype(np.float32)
+    small[rng.random((h, w)) < 0.25] = INF
+    small[0, 0], small[-1, -1] = np.nan, -np.inf
+    g_small = (rng.integers(0, 4, (h, w)) * ((1 << bits) // 4 - 1)).astype(dt)
+    g_full = (rng.integers(0, 4, (H, W)) * ((1 << bits) // 4 - 1)).astype(dt)
+    if flat_census:
+        c_ref = c_oth = np.full((H, W), 0x0F0F1234, np.uint32)
+    else:
+        c_ref, c_oth = (rng.integers(0, 1 << 32, (H, W), dtype=np.uint64).astype(np.uint32) for _ in range(2))
+    return small, g_small, g_full, c_ref, c_oth
+
+
+@pytest.mark.parametrize("W,H", [(13, 9), (22, 11)])
+@pytest.mark.parametrize("f", [2, 4])
+def test_restatement_equals_the_double_loop(W, H, f):
+    rng = np.random.default_rng(W * 10 + f)
+    for bits in (8, 12):
+        img = rng.integers(0, 1 << bits, (H, W)).astype(np.uint16 if bits > 8 else np.uint8)
+        assert np.array_equal(SR.downscale(img, f), loop_downscale(img, f))
+        img[:] = (1 << bits) - 1
+        assert (SR.downscale(img, f) == (1 << bits) - 1).all()
+    n_sub = n_prior = n_tie = 0
+    for right in (False, True):
+        for radius, penalty, flat in ((-1, 0, False), (0, 0, False), (1, 1, True), (3, 1, False), (4, 16, False), (3, 0, True)):
+            arrays = planted(rng, W, H, f, 12 if radius == 3 else 8, flat)
+            got = SR.upscale(*arrays, f, radius, penalty, 3, 11, right)
+            want = loop_upscale(*arrays, f, radius, penalty, 3, 11, right)
+            assert same_bits(got, want), (right, radius, penalty, flat, np.argwhere(got.view(np.uint32) != want.view(np.uint32))[:4])
+            fin = np.isfinite(got)
+            if radius >= 0:
+                n_sub += int((got[fin] != np.rint(got[fin])).sum())
+                n_prior += int(((got[fin] > 11) | (got[fin] < 3)).sum())
+                n_tie += int(flat)
+            assert np.isposinf(got).any() and not np.isnan(got).any()
+    assert n_sub and n_prior and n_tie
+
+
+def test_ties_go_to_the_smaller_offset_then_the_smaller_disparity():
+    """constant census words: every cost inside the frame ties, so without a penalty the winner is o = 0 wherever the whole
+    footprint is inside, and the sub-pixel term (den == 0) does not apply"""
+    W, H, f = 40, 12, 2
+    small = np.full((H // f, W // f), 3.0, np.float32)
+    g = np.zeros((H, W), np.uint8)
+    words = np.full((H, W), 0xABCD, np.uint32)
+    out = SR.upscale(small, g[:H // f, :W // f], g, words, words, f, 1, 0, 0, 63, False)
+    assert (out[:, 10:-2] == 6.0).all()
+    # near the left edge a candidate whose partner column xo = q.x - d is < 0 pays 24 for that window pixel: at x = 6 that is d = 6
+    # (q.x = 5) and more, so d = 5 wins -- the smaller |o| of the two free candidates 4 and 5 -- and the sub-pixel term applies;
+    # at x = 0 every candidate pays for every window pixel: a tie again, o = 0
+    assert (out[:, 6] == 4.5).all() and (out[:, 0] == 6.0).all()
+    # only d = 7 admitted where the prior is 6: no neighbour, no sub-pixel term
+    one = SR.upscale(small, g[:H // f, :W // f], g, words, words, f, 1, 0, 7, 7, False)
+    assert (one == 7.0).all()
+
+
+# ---- header, library, Python -------------------------------------------------------------------------------------------------
+
+NEW = ("sgm_scaled_shape", "sgm_downscale", "sgm_upscale_disparity", "sgm_match_scaled", "sgm_match_scaled_device", "SGM_MatchScaled")
+ORDER = ["width", "height", "frames", "factor", "bits", "radius", "penalty", "d_lo", "d_hi"]
+
+
+def test_header_library_and_python_agree():
+    import soc_project_stereo_matching_amd as S
+    from test_cabi import _declared_functions
+    lib = S.load_library()
+    declared = _declared_functions()
+    for name in NEW:
+        assert name in declared and hasattr(lib, name), name
+    for name in ("sgmd_downscale", "sgmd_upscale"):
+        assert hasattr(lib, name), name
+    with open(os.path.join(ROOT, "include", "sgm_mi355x.h")) as fh:
+        text = fh.read()
+    assert C.sizeof(S.SGMScaleSpec) == 36
+    assert [f[0] for f in S.SGMScaleSpec._fields_] == ORDER
+    for k, name in enumerate(ORDER):
+        assert getattr(S.SGMScaleSpec, name).offset == 4 * k and getattr(S.SGMScaleSpec, name).size == 4, name
+    body = re.search(r"typedef struct \{([^}]*)\} sgm_scale_spec;", text).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = [n.strip() for decl in body.split(";") if decl.strip() for n in decl.strip().split(None, 1)[1].split(",")]
+    assert fields == ORDER and "int32_t" in body and "36 bytes" in text
+    assert re.search(r"#define SGM_SCALE_DEFAULT_RADIUS 3\b", text) and re.search(r"#define SGM_SCALE_DEFAULT_PENALTY 1\b", text)
+    assert (S.sgm.SCALE_DEFAULT_RADIUS, S.sgm.SCALE_DEFAULT_PENALTY) == (3, 1)
+    for m in ("downscale", "upscale_disparity", "match_scaled", "match_scaled_device"):
+        assert callable(getattr(S.SGMInstance, m, None)), m
+    assert callable(S.SGM.match_scaled)
+    # sgm_scaled_shape is host only: it answers without a device
+    assert S.scaled_shape(S.scale_spec(67, 19, 2)) == (33, 9) and S.scaled_shape(S.scale_spec(67, 19, 4)) == (16, 4)
+    assert S.scaled_shape(S.scale_spec(3, 19, 4)) is None and S.scaled_shape(S.scale_spec(67, 1, 2)) is None
+    assert S.scaled_shape(S.scale_spec(67, 19, 3)) is None and S.scaled_shape(S.scale_spec(67, 19, 2, bits=17)) is None
+    sp = S.scale_spec(8, 6, 2)
+    assert (sp.frames, sp.bits, sp.radius, sp.penalty, sp.d_lo, sp.d_hi) == (1, 8, 3, 1, 0, 65535)
+
+
+# ---- the C host on the stand-in device ------------------------------------------------------------------------------------------
+
+class DeviceSpec(C.Structure):                                   # sgmd_scale of csrc/sgm_device.h, as the stand-in logs it
+    _fields_ = [(n, _i) for n in ("W", "H", "B", "f", "bits", "radius", "penalty", "d_lo", "d_hi", "right")]
+
+
+def _sign(L):
+    for name, (res, args) in {"sgm_scaled_shape": (_b, [_p] * 3), "sgm_downscale": (_b, [_p] * 4),
+                              "sgm_upscale_disparity": (_b, [_p] * 7 + [_i, _p]), "sgm_match_scaled": (_b, [_p] * 5),
+                              "sgm_match_scaled_device": (_b, [_p] * 5), "SGM_MatchScaled": (_b, [_p] * 4),
+                              "sgm_set_census_window": (_b, [_p, _i, _i]), "sgm_set_census_kind": (_b, [_p, _i]),
+                              "sgm_set_pixel_bits": (_b, [_p, _i]), "sgm_set_rectify": (_b, [_p, _i, _i, _p, _p, _p, _p]),
+                              "stub_scale_clear": (None, []), "stub_scale_count": (_i, []), "stub_scale_kind": (_i, [_i]),
+                              "stub_scale_at": (_i, [_i]), "stub_scale_ptr": (_p, [_i, _i]),
+                              "stub_scale_spec": (C.POINTER(DeviceSpec), [_i]), "stub_scale_fail_at": (None, [_i]),
+                              "stub_fail_alloc_at": (None, [_i]), "stub_log_size": (_i, [])}.items():
+        if hasattr(L, name):
+            getattr(L, name).restype, getattr(L, name).argtypes = res, args
+    return L
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    return _sign(standin.build(tmp_path_factory.mktemp("scalestub"), extra_sources=[STUB_SCALE, STUB_P16, STUB_RECT],
+                               flags=("-ffp-contract=off",)))
+
+
+@pytest.fixture(scope="module")
+def host_without(tmp_path_factory):
+    return _sign(standin.build(tmp_path_factory.mktemp("scalestub_without"), extra_sources=[STUB_P16, STUB_RECT],
+                               flags=("-ffp-contract=off",)))
+
+
+W, H, F = 96, 40, 2
+
+
+def c_spec(**kw):
+    import soc_project_stereo_matching_amd as S
+    base = dict(width=W, height=H, factor=F)
+    base.update(kw)
+    return S.scale_spec(base.pop("width"), base.pop("height"), base.pop("factor"), **base)
+
+
+def make(L, w=W // F, h=H // F, batch=1, dmin=0, dmax=16, setup=None):
+    import soc_project_stereo_matching_amd as S
+    s = L.sgm_create(0)
+    assert s
+    if setup:
+        setup(s)
+    opt = S.default_option(dmax, dmin)
+    assert L.sgm_set_batch(s, batch) and L.sgm_reset(s, w, h, C.byref(opt))
+    return s, opt
+
+
+def merged(L, drop=("sync", "h2d", "d2h", "alloc", "memset", "event_record", "wait_event")):
+    """the device calls in order, the scale launchers (a log of their own) placed where they fell"""
+    log = standin.log(L)
+    scale = [(L.stub_scale_at(k), ("downscale", "upscale")[L.stub_scale_kind(k)]) for k in range(L.stub_scale_count())]
+    out = []
+    for pos in range(len(log) + 1):
+        out += [name for at, name in scale if at == pos]
+        if pos < len(log) and log[pos].name not in drop:
+            out.append(log[pos].name)
+    return out
+
+
+def test_composed_call_launches_in_the_order_of_the_header(host):
+    L = host
+    rng = np.random.default_rng(5)
+    for batch, dmin, dmax, right in ((1, 0, 16, 0), (2, 3, 19, 1)):
+        s, opt = make(L, batch=batch, dmin=dmin, dmax=dmax)
+        L.sgm_set_reference_view(s, right)
+        left = rng.integers(0, 256, (batch, H, W)).astype(np.uint8)
+        right_img = rng.integers(0, 256, (batch, H, W)).astype(np.uint8)
+        out = np.full((batch, H, W), -7, np.float32)
+        small_l, small_r = SR.downscale(left, F), SR.downscale(right_img, F)
+        small_out = np.zeros((batch, H // F, W // F), np.float32)
+        L.stub_clear(); L.stub_scale_clear()
+        assert L.sgm_match_device(s, small_l.ctypes.data, small_r.ctypes.data, small_out.ctypes.data)
+        plain = merged(L)
+        assert L.sgm_reset(s, W // F, H // F, C.byref(opt))
+        sp = c_spec(frames=batch, radius=2, penalty=5, d_lo=1, d_hi=2)
+        L.stub_clear(); L.stub_scale_clear()
+        assert L.sgm_match_scaled_device(s, C.byref(sp), left.ctypes.data, right_img.ctypes.data, out.ctypes.data)
+        assert merged(L) == ["downscale", "downscale"] + plain + ["census", "upscale"]
+        # the specs the launchers got: the caller's, with the instance's view and range in the place of the spec's own
+        want = (W, H, batch, F, 8, 2, 5, F * dmin, F * dmax - 1, right)
+        for k in range(3):
+            got = L.stub_scale_spec(k).contents
+            assert tuple(getattr(got, n) for n, _ in DeviceSpec._fields_) == want, k
+        # the pointers: the caller's images in, the two small images on to the match and (the reference view's) the upscale
+        assert (L.stub_scale_ptr(0, 0), L.stub_scale_ptr(1, 0)) == (left.ctypes.data, right_img.ctypes.data)
+        small = (L.stub_scale_ptr(0, 1), L.stub_scale_ptr(1, 1))
+        assert small[0] and small[1] and small[0] != small[1]
+        census = standin.calls(L, "census")
+        assert len(census) == 2 and [e.arg & 0xFFFF for e in census] == [batch, batch]
+        assert L.stub_scale_ptr(2, 1) == small[right] and L.stub_scale_ptr(2, 2) == (right_img if right else left).ctypes.data
+        assert L.stub_scale_ptr(2, 3) and L.stub_scale_ptr(2, 4) and L.stub_scale_ptr(2, 3) != L.stub_scale_ptr(2, 4)
+        assert L.stub_scale_ptr(2, 5) == out.ctypes.data
+        # the stand-in computes: the small images are the restatement's, and the full map is its upscale of the all-zero small map
+        # over all-zero census words
+        assert L.sgm_synchronize(s)
+        n = small_l.size
+        for view, ref in enumerate((small_l, small_r)):
+            got = np.ctypeslib.as_array(C.cast(small[view], C.POINTER(C.c_uint8)), (n,))
+            assert np.array_equal(got.reshape(ref.shape), ref), view
+        guide, guide_small = (right_img, small_r) if right else (left, small_l)
+        zeros = np.zeros((batch, H, W), np.uint32)
+        want_map = SR.upscale_batch(np.zeros_like(small_out), guide_small, guide, zeros, zeros, F, 2, 5, F * dmin, F * dmax - 1, bool(right))
+        assert same_bits(out, want_map)
+        # radius < 0: no census, no planes
+        assert L.sgm_reset(s, W // F, H // F, C.byref(opt))
+        sp = c_spec(frames=batch, radius=-3)
+        L.stub_clear(); L.stub_scale_clear()
+        assert L.sgm_match_scaled_device(s, C.byref(sp), left.ctypes.data, right_img.ctypes.data, out.ctypes.data)
+        assert merged(L) == ["downscale", "downscale"] + plain + ["upscale"]
+        assert L.stub_scale_spec(2).contents.radius == -1 and not L.stub_scale_ptr(2, 3) and not L.stub_scale_ptr(2, 4)
+        L.sgm_destroy(s)
+
+
+def test_host_form_uploads_matches_and_hands_the_full_map_over(host):
+    L = host
+    rng = np.random.default_rng(6)
+    s, opt = make(L)
+    left = rng.integers(0, 256, (H, W)).astype(np.uint8)
+    right = rng.integers(0, 256, (H, W)).astype(np.uint8)
+    out = np.full((H, W), -7, np.float32)
+    sp = c_spec()
+    L.stub_clear(); L.stub_scale_clear()
+    assert L.sgm_match_scaled(s, C.byref(sp), left.ctypes.data, right.ctypes.data, out.ctypes.data)
+    log = standin.log(L)
+    assert [e.arg for e in log if e.name == "h2d"][:2] == [W * H, W * H]
+    assert [e.arg for e in log if e.name == "d2h"] == [4 * W * H]
+    zeros = np.zeros((H, W), np.uint32)
+    want = SR.upscale(np.zeros((H // F, W // F), np.float32), SR.downscale(left, F), left, zeros, zeros, F, 3, 1, 0, 31, False)
+    assert same_bits(out, want)
+    # a second call allocates nothing (behind a Reset: without one the small match adds to the sums, Q14, and allocates S as any
+    # second match does); pinned buffers are used in place (no staging copy in between)
+    assert L.sgm_reset(s, W // F, H // F, C.byref(opt))
+    L.stub_clear(); L.stub_scale_clear()
+    for k, a in enumerate((left, right, out)):
+        L.stub_set_pinned(k, a.ctypes.data)
+    try:
+        assert L.sgm_match_scaled(s, C.byref(sp), left.ctypes.data, right.ctypes.data, out.ctypes.data)
+        log = standin.log(L)
+        assert not [e for e in log if e.name == "alloc"]
+        assert [e.a for e in log if e.name == "d2h"] == [out.ctypes.data] and same_bits(out, want)
+    finally:
+        for k in range(3):
+            L.stub_set_pinned(k, None)
+    # stage 8 holds the small map
+    small = np.full((H // F, W // F), -1, np.float32)
+    assert L.sgm_read_stage(s, 8, small.ctypes.data, small.nbytes) == small.nbytes and (small == 0).all()
+    L.sgm_destroy(s)
+
+
+def _rectify_on(L, s):
+    w, h = W // F, H // F
+    xs, ys = np.meshgrid(np.arange(w, dtype=np.float32), np.arange(h, dtype=np.float32))
+    xs, ys = np.ascontiguousarray(xs), np.ascontiguousarray(ys)
+    return L.sgm_set_rectify(s, w, h, xs.ctypes.data, ys.ctypes.data, xs.ctypes.data, ys.ctypes.data)
+
+
+REFUSALS = {
+    # name -> (instance setup or None, spec changes, says)
+    "factor 3": (None, dict(factor=3), "outside its ranges"),
+    "factor 1": (None, dict(factor=1), "outside its ranges"),
+    "bits 7": (None, dict(bits=7), "outside its ranges"),
+    "bits 17": (None, dict(bits=17), "outside its ranges"),
+    "radius 5": (None, dict(radius=5), "outside its ranges"),
+    "penalty -1": (None, dict(penalty=-1), "outside its ranges"),
+    "penalty 17": (None, dict(penalty=17), "outside its ranges"),
+    "d_lo > d_hi": (None, dict(d_lo=9, d_hi=8), "outside its ranges"),
+    "d_hi 65536": (None, dict(d_hi=65536), "outside its ranges"),
+    "d_lo -1": (None, dict(d_lo=-1), "outside its ranges"),
+    "width 0": (None, dict(width=0), "outside its ranges"),
+    "frames 0": (None, dict(frames=0), "outside its ranges"),
+    "small width 0": (None, dict(width=3, factor=4), "outside its ranges"),
+    "shape": (None, dict(width=W + 2 * F), "the instance is initialised for"),
+    "batch": (None, dict(frames=2), "the instance is initialised for"),
+    "bits": (None, dict(bits=12), "the instance is initialised for"),
+    "row tiles": ("rows", {}, "row-tile mode"),
+    "rectification": ("rectify", {}, "rectification"),
+    "wide centre census": ("wide", {}, "wide CENTRE census"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(REFUSALS))
+def test_every_refusal_returns_false_queues_nothing_and_says_why(host, capfd, name):
+    L = host
+    setup, changes, says = REFUSALS[name]
+    how = {None: None, "rows": lambda s: L.sgm_set_rows(s, 4, 12), "rectify": lambda s: _rectify_on(L, s),
+           "wide": lambda s: L.sgm_set_census_window(s, 9, 7)}[setup]
+    s, opt = make(L, setup=how)
+    left = np.zeros((2, H + 8, W + 8), np.uint16)
+    out = np.zeros((2, H + 8, W + 8), np.float32)
+    sp = c_spec(**changes)
+    L.stub_clear(); L.stub_scale_clear()
+    capfd.readouterr()
+    for call in (L.sgm_match_scaled, L.sgm_match_scaled_device):
+        assert not call(s, C.byref(sp), left.ctypes.data, left.ctypes.data, out.ctypes.data), name
+        assert says in capfd.readouterr().err, name
+    assert L.stub_scale_count() == 0 and standin.launches(L) == [], name
+    if setup is None and "ranges" in says:                        # the stand-alone forms refuse the same specs
+        assert not L.sgm_downscale(s, C.byref(sp), left.ctypes.data, out.ctypes.data)
+        assert not L.sgm_upscale_disparity(s, C.byref(sp), out.ctypes.data, left.ctypes.data, left.ctypes.data, out.ctypes.data,
+                                           out.ctypes.data, 0, out.ctypes.data)
+        w, h = C.c_int(-1), C.c_int(-1)
+        assert not L.sgm_scaled_shape(C.byref(sp), C.byref(w), C.byref(h)) and (w.value, h.value) == (-1, -1)
+        assert L.stub_scale_count() == 0
+    if setup == "wide":                                           # ... but without the re-search no census word is read
+        assert L.sgm_match_scaled_device(s, C.byref(c_spec(radius=-1)), left.ctypes.data, left.ctypes.data, out.ctypes.data)
+    L.sgm_destroy(s)
+
+
+def test_null_pointers_misalignment_and_the_uninitialised_instance(host, capfd):
+    L = host
+    s = L.sgm_create(0)
+    img = np.zeros((H, W), np.uint16)
+    out = np.zeros((H, W), np.float32)
+    sp = c_spec()
+    a, o = img.ctypes.data, out.ctypes.data
+    assert not L.sgm_match_scaled(s, C.byref(sp), a, a, o) and "initialised at the low-resolution shape" in capfd.readouterr().err
+    L.sgm_destroy(s)
+    s, opt = make(L)
+    L.stub_clear(); L.stub_scale_clear()
+    for call in (L.sgm_match_scaled, L.sgm_match_scaled_device):
+        for args in ((None, C.byref(sp), a, a, o), (s, None, a, a, o), (s, C.byref(sp), None, a, o), (s, C.byref(sp), a, None, o),
+                     (s, C.byref(sp), a, a, None)):
+            assert not call(*args)
+    assert not L.sgm_downscale(s, C.byref(sp), None, o) and not L.sgm_downscale(s, C.byref(sp), a, None)
+    for k in range(2, 7):                                         # each pointer of sgm_upscale_disparity in turn
+        args = [s, C.byref(sp), o, a, a, o, o, 0, o]
+        args[k] = None
+        assert not L.sgm_upscale_disparity(*args), k
+    args = [s, C.byref(c_spec(radius=-1)), o, a, a, None, None, 0, o]
+    assert L.sgm_upscale_disparity(*args) and L.stub_scale_count() == 1             # the planes may be NULL without a re-search
+    sp12 = c_spec(bits=12)
+    assert not L.sgm_downscale(s, C.byref(sp12), a + 1, o) and not L.sgm_upscale_disparity(s, C.byref(sp12), o, a + 1, a, o, o, 0, o)
+    assert not L.sgm_upscale_disparity(s, C.byref(sp), o + 2, a, a, o, o, 0, o) and not L.sgm_match_scaled_device(s, C.byref(sp), a, a, o + 2)
+    assert L.sgm_downscale(s, C.byref(sp), a + 1, o + 1)                             # u8 samples need no alignment
+    assert L.stub_scale_count() == 2
+    L.sgm_destroy(s)
+
+
+def test_host_without_the_launchers_links_and_refuses(host_without, capfd):
+    L = host_without
+    assert not hasattr(L, "sgmd_downscale") and not hasattr(L, "stub_scale_count")
+    s, opt = make(L)
+    img, out = np.zeros((H, W), np.uint8), np.zeros((H, W), np.float32)
+    sp = c_spec()
+    L.stub_clear()
+    capfd.readouterr()
+    assert not L.sgm_match_scaled(s, C.byref(sp), img.ctypes.data, img.ctypes.data, out.ctypes.data)
+    assert "not part of this build" in capfd.readouterr().err
+    assert not L.sgm_match_scaled_device(s, C.byref(sp), img.ctypes.data, img.ctypes.data, out.ctypes.data)
+    assert not L.sgm_downscale(s, C.byref(sp), img.ctypes.data, out.ctypes.data)
+    assert not L.sgm_upscale_disparity(s, C.byref(sp), out.ctypes.data, img.ctypes.data, img.ctypes.data, out.ctypes.data, out.ctypes.data, 0,
+                                       out.ctypes.data)
+    assert standin.launches(L) == []
+    w, h = C.c_int(0), C.c_int(0)
+    assert L.sgm_scaled_shape(C.byref(sp), C.byref(w), C.byref(h)) and (w.value, h.value) == (W // F, H // F)     # host only
+    L.sgm_destroy(s)
+
+
+def test_plain_match_logs_what_it_logs_without_the_scaled_match(host, host_without):
+    """allocations and their sizes included: an instance that never calls a scaled entry point is the instance it was"""
+    import soc_project_stereo_matching_amd as S
+    left, right = np.zeros((H, W), np.uint8), np.ones((H, W), np.uint8)
+    out, conf = np.zeros((H, W), np.float32), np.zeros((H, W), np.uint16)
+    logs = []
+    for L in (host, host_without):
+        s = L.sgm_create(0)
+        opt = S.default_option(16)
+        L.stub_clear()
+        if hasattr(L, "stub_scale_clear"):
+            L.stub_scale_clear()
+        assert L.sgm_reset(s, W, H, C.byref(opt)) and L.sgm_match(s, left.ctypes.data, right.ctypes.data, out.ctypes.data)
+        assert L.sgm_match(s, left.ctypes.data, right.ctypes.data, out.ctypes.data)                     # without Reset
+        assert L.sgm_reset(s, W, H, C.byref(opt)) and L.sgm_match_confidence(s, left.ctypes.data, right.ctypes.data, out.ctypes.data,
+                                                                           conf.ctypes.data)
+        assert L.sgm_set_overlap_post(s, 1)
+        assert L.sgm_reset(s, W, H, C.byref(opt)) and L.sgm_match(s, left.ctypes.data, right.ctypes.data, out.ctypes.data)
+        logs.append([(e.name, e.arg) for e in standin.log(L)])
+        L.sgm_destroy(s)
+    assert logs[0] == logs[1] and host.stub_scale_count() == 0
+
+
+def test_a_refused_launch_or_allocation_fails_the_call_and_leaves_the_instance_usable(host):
+    L = host
+    s, opt = make(L)
+    rng = np.random.default_rng(8)
+    left = rng.integers(0, 256, (H, W)).astype(np.uint8)
+    right = rng.integers(0, 256, (H, W)).astype(np.uint8)
+    out = np.zeros((H, W), np.float32)
+    sp = c_spec()
+    args = (s, C.byref(sp), left.ctypes.data, right.ctypes.data, out.ctypes.data)
+    assert L.sgm_match_scaled(*args)
+    good = out.copy()
+    L.stub_clear(); L.stub_scale_clear()
+    assert L.sgm_match_scaled_device(*args)
+    n_launches = len(merged(L))
+    # each launch of the sequence in turn: the scale launchers by their own counter, the others by name
+    for nth in range(3):
+        L.stub_scale_fail_at(nth)
+        assert not L.sgm_match_scaled(*args), nth
+        L.stub_scale_fail_at(-1)
+    for name, nth in (("census", 0), ("census", 1), ("aggregate", 0), ("sum_wta_lr", 0), ("lrcheck", 0), ("speckle", 0), ("median", 0)):
+        L.stub_clear(); L.stub_scale_clear()
+        L.stub_fail_at(name.encode(), nth)
+        assert not L.sgm_match_scaled_device(*args), (name, nth)
+        assert len(merged(L)) < n_launches, (name, nth)           # nothing further was queued
+        L.stub_clear()
+    for call in (L.sgm_match_scaled, L.sgm_match_scaled_device):
+        assert L.sgm_reset(s, W // F, H // F, C.byref(opt))
+        out[:] = -1
+        assert call(*args) and L.sgm_synchronize(s) and same_bits(out, good)
+    # a plain match still runs and logs what a fresh instance logs
+    small = SR.downscale(left, F)
+    small_out = np.zeros((H // F, W // F), np.float32)
+    assert L.sgm_reset(s, W // F, H // F, C.byref(opt))
+    L.stub_clear()
+    assert L.sgm_match(s, small.ctypes.data, small.ctypes.data, small_out.ctypes.data)
+    after = standin.launches(L)
+    t, _ = make(L)
+    L.stub_clear()
+    assert L.sgm_match(t, small.ctypes.data, small.ctypes.data, small_out.ctypes.data)
+    assert standin.launches(L) == after
+    L.sgm_destroy(t)
+    # a refused allocation of the call's own buffers, on a fresh instance
+    t, _ = make(L)
+    L.stub_fail_alloc_at(0)
+    assert not L.sgm_match_scaled_device(t, *args[1:])
+    L.stub_fail_alloc_at(-1)
+    assert L.sgm_match_scaled_device(t, *args[1:]) and L.sgm_synchronize(t)
+    L.sgm_destroy(t)
+    L.sgm_destroy(s)
+
+
+def test_more_bits_and_the_symmetric_census_go_through_their_launchers(host):
+    """12 bits: one sgmd_census16 launch for both full-resolution views, with narrowed images of the call's own; 8 bits with the
+    symmetric kind: sgmd_census_sym with the instance's window"""
+    L = host
+    _arg = L.stub_p16_arg
+    _arg.restype, _arg.argtypes = _i, [_i, _i]
+    L.stub_p16_ptr.restype, L.stub_p16_ptr.argtypes = _p, [_i, _i]
+    rng = np.random.default_rng(9)
+    left = rng.integers(0, 4096, (H, W)).astype(np.uint16)
+    right = rng.integers(0, 4096, (H, W)).astype(np.uint16)
+    out = np.zeros((H, W), np.float32)
+    s, opt = make(L, setup=lambda s: L.sgm_set_pixel_bits(s, 12) and L.sgm_set_census_kind(s, 1) and L.sgm_set_census_window(s, 7, 7))
+    L.stub_clear(); L.stub_scale_clear(); L.stub_p16_clear()
+    assert L.sgm_match_scaled_device(s, C.byref(c_spec(bits=12)), left.ctypes.data, right.ctypes.data, out.ctypes.data)
+    assert L.stub_p16_count() == 2
+    # kind, bits, symmetric, cw, ch, frames
+    assert [[_arg(k, f) for f in range(6)] for k in range(2)] == [[0, 12, 1, 7, 7, 1]] * 2
+    assert (L.stub_p16_ptr(1, 0), L.stub_p16_ptr(1, 1)) == (left.ctypes.data, right.ctypes.data)
+    own = [L.stub_p16_ptr(1, k) for k in range(2, 6)]
+    assert all(own) and len(set(own)) == 4 and not set(own) & {L.stub_p16_ptr(0, k) for k in range(2, 6)}
+    assert (L.stub_scale_ptr(2, 3), L.stub_scale_ptr(2, 4)) == (own[0], own[1])
+    # the stand-in census computed the symmetric words of the u16 samples: the full map is the restatement's
+    import pixels16_ref as P
+    small_l = SR.downscale(left, F)
+    want = SR.upscale(np.zeros((H // F, W // F), np.float32), small_l, left, P.census_sym(left, 7, 7), P.census_sym(right, 7, 7), F, 3, 1,
+                      0, 31, False)
+    assert L.sgm_synchronize(s) and same_bits(out, want)
+    L.sgm_destroy(s)
+    left8, right8 = (left >> 4).astype(np.uint8), (right >> 4).astype(np.uint8)
+    s, opt = make(L, setup=lambda s: L.sgm_set_census_kind(s, 1) and L.sgm_set_census_window(s, 9, 5))
+    L.stub_clear(); L.stub_scale_clear(); L.stub_p16_clear()
+    assert L.sgm_match_scaled_device(s, C.byref(c_spec()), left8.ctypes.data, right8.ctypes.data, out.ctypes.data)
+    assert [[_arg(k, f) for f in range(6)] for k in range(2)] == [[2, 8, 1, 9, 5, 1]] * 2
+    assert (L.stub_p16_ptr(1, 0), L.stub_p16_ptr(1, 1)) == (left8.ctypes.data, right8.ctypes.data)
+    L.sgm_destroy(s)
+
+
+def test_stand_in_kernels_equal_the_restatement(host):
+    """the plain C loops of tests/stub_scale.c are a third statement of the definition; through the stand-alone entry points"""
+    L = host
+    s = L.sgm_create(0)
+    rng = np.random.default_rng(10)
+    for (w, h, f, bits, radius, right) in ((67, 19, 2, 8, 3, 0), (70, 23, 4, 12, 4, 1), (5, 5, 2, 8, 3, 0), (22, 11, 4, 8, 0, 1)):
+        arrays = [np.stack(a) for a in zip(*(planted(rng, w, h, f, bits, k == 1) for k in range(2)))]
+        img = rng.integers(0, 1 << bits, (2, h, w)).astype(np.uint16 if bits > 8 else np.uint8)
+        sp = c_spec(width=w, height=h, factor=f, frames=2, bits=bits, radius=radius, penalty=2, d_lo=2, d_hi=12)
+        small = np.zeros((2, h // f, w // f), img.dtype)
+        assert L.sgm_downscale(s, C.byref(sp), img.ctypes.data, small.ctypes.data)
+        assert np.array_equal(small, SR.downscale(img, f))
+        out = np.zeros((2, h, w), np.float32)
+        assert L.sgm_upscale_disparity(s, C.byref(sp), *(a.ctypes.data for a in arrays), right, out.ctypes.data)
+        assert same_bits(out, SR.upscale_batch(*arrays, f, radius, 2, 2, 12, bool(right))), (w, h, f)
+    L.sgm_destroy(s)
+
+
+# ---- sanitizers on a stand-alone program ---------------------------------------------------------------------------------------
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="gcc not available")
+def test_scaled_host_is_asan_ubsan_clean(tmp_path):
+    """tests/scaled_sanitize_driver.c: a program of its own, linked with the host, the stub device and the stand-in launchers."""
+    exe = standin.build(tmp_path, sanitize=True, exe="scaled_sanitize_driver",
+                        flags=("-ffp-contract=off", "-static-libasan", "-static-libubsan"),
+                        extra_sources=[os.path.join(TESTS, "scaled_sanitize_driver.c"), STUB_SCALE, STUB_P16])
+    # the sanitizer runtimes are linked statically, so the program runs in the environment as it is: nothing is unset for it
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1")
+    out = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
+    assert out.returncode == 0, (out.stdout[-500:], out.stderr[-3000:])
+    assert out.stdout.strip().endswith("scaled_sanitize_driver ok")
+
+
+# ---- the command-line driver on the stand-in -------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    """csrc/sgm_main.c linked with the host and the stand-in device instead of the library"""
+    if shutil.which("gcc") is None:
+        pytest.skip("gcc not available")
+    csrc = standin.CSRC
+    return standin.build(tmp_path_factory.mktemp("scaledriver"), exe="sgm_main_standin", host_c=os.path.join(csrc, "sgm_main.c"),
+                         extra_sources=[os.path.join(csrc, "sgm_image_io.c"), standin.HOST_C, STUB_SCALE], flags=("-ffp-contract=off",),
+                         libs=("-lz",))
+
+
+def test_driver_scale_option_arithmetic_and_refused_combinations(driver, tmp_path):
+    l, r = os.path.join(GOLDEN, "cone_im2.png"), os.path.join(GOLDEN, "cone_im6.png")          # 450 x 375
+    raw = str(tmp_path / "d.f32")
+
+    def run(*extra):
+        return subprocess.run([driver, l, r, str(tmp_path / "d.png"), *extra], capture_output=True, text=True, timeout=120)
+
+    out = run("--scale", "2", "--min-disparity", "5", "--max-disparity", "63", "--raw", raw)
+    assert out.returncode == 0, (out.stdout, out.stderr)
+    assert "w = 450, h = 375, d = [5,63]" in out.stdout
+    assert "scale 2: matching 225 x 187, d = [2,32], radius 3, penalty 1" in out.stdout
+    full = np.fromfile(raw, np.float32)
+    assert full.size == 450 * 375                                  # the full-resolution map: the outputs work on it
+    # the stand-in's small map is all 0: priors 0, re-searched within [2 * 2, 2 * 32 - 1] -> nothing admitted but d = 4 .. at o = 2
+    assert f"valid {full.size} of {full.size}" in out.stdout
+    out = run("--scale", "4", "--max-disparity", "64", "--scale-radius", "-1", "--scale-penalty", "7")
+    assert out.returncode == 0 and "scale 4: matching 112 x 93, d = [0,16], radius -1, penalty 7" in out.stdout
+    # usage errors, told apart by what they say
+    for extra, says in ((["--scale", "3"], "--scale wants 2 or 4"), (["--scale-radius", "2"], "need --scale"),
+                        (["--scale-penalty", "3"], "need --scale"), (["--scale", "2", "--scale-radius", "5"], "--scale-radius wants"),
+                        (["--scale", "2", "--scale-penalty", "17"], "--scale-penalty 0..16"),
+                        (["--scale", "2", "--cloud", "c.ply", "--pinhole", "1,2,3,4,5,6"], "--scale does not combine"),
+                        (["--scale", "2", "--confidence", "c.pgm"], "--scale does not combine"),
+                        (["--scale", "2", "--right-out", "r.png"], "--scale does not combine"),
+                        (["--scale", "2", "--right-raw", "r.f32"], "--scale does not combine"),
+                        (["--scale", "2", "--rectify", "calib.txt"], "--scale does not combine")):
+        out = run(*extra)
+        assert out.returncode == 2 and says in out.stderr and "unknown option" not in out.stderr, (extra, out.stdout, out.stderr)
+
+
+# ---- the quality of the definition ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("scene", ["cloth3", "reindeer", "wood2"])
+def test_research_beats_the_nearest_neighbour_upscale_on_the_golden_scenes(oracle, golden_cases, scene):
+    """The table of NOTES.md: the bad-pixel share at 1 px over the pixels with known ground truth (invalid counted as bad) of the
+    full-resolution match, and at f = 2 and f = 4 of the nearest-neighbour upscale, the guided selection alone and the selection
+    with the re-search at the defaults, all of the CPU oracle's small map.  Asserted: the re-search has a lower share than the
+    nearest-neighbour upscale of the same small map at both factors (the prototype's margins: 1.5 to 2.5 points at f = 2, 14 to 19
+    at f = 4)."""
+    import soc_project_stereo_matching_amd as S
+    c = golden_cases["scene_" + scene]
+    z = load_npz("scene_%s.npz" % scene)
+    left, right = z["left"], z["right"]
+    Hs, Ws = left.shape
+    g = load_npz("gt_disparity.npz")
+    gt = np.where(g[scene] > 0, g[scene].astype(np.float32) / g[scene + "_scale"], np.float32(0))
+    opt = option_from_dict(c["option"])
+    share = {"full": SR.bad_share(oracle.run(left, right, opt)["final"], gt)}
+    words_l, words_r = oracle.census(left), oracle.census(right)
+    for f in (2, 4):
+        small_opt = option_from_dict(c["option"])
+        small_opt.min_disparity, small_opt.max_disparity = opt.min_disparity // f, -(-opt.max_disparity // f)
+        ls, rs = SR.downscale(left, f), SR.downscale(right, f)
+        small = oracle.run(ls, rs, small_opt)["final"]
+        share[f, "nearest"] = SR.bad_share(SR.nearest_upscale(small, f, Hs, Ws), gt)
+        share[f, "select"] = SR.bad_share(SR.upscale(small, ls, left, None, None, f, -1, 0, 0, 0, False), gt)
+        share[f, "research"] = SR.bad_share(SR.upscale(small, ls, left, words_l, words_r, f, S.sgm.SCALE_DEFAULT_RADIUS,
+                                                       S.sgm.SCALE_DEFAULT_PENALTY, f * small_opt.min_disparity,
+                                                       f * small_opt.max_disparity - 1, False), gt)
+    print(f"{scene}: " + "  ".join(f"{k}: {v:.4f}" for k, v in share.items()))
+    for f in (2, 4):
+        assert share[f, "research"] < share[f, "nearest"], (f, share)
