@@ -30,7 +30,7 @@
 struct AggArgs {
     const uint8_t* img;
     const uint32_t* census_l;
-    const uint32_t* census_r;   // the allocation has >= dmin + Dp dwords of slack in front (reads left of column 0)
+    const uint32_t* census_r;   // the allocation has >= dmin + Dp + 8 dwords of slack in front (reads left of column 0) and 16 behind (agg_feed's whole 16-byte groups)
     const uint8_t* cost;        // VOL kernels only: the materialised cost volume u8 [B][H][W][Dp] (census pointers unused)
     int dmin;
     const uint16_t* lut;        // (uint16) max(P1, P2 / (|dg| + 1)), 256 entries (ref :335)
@@ -306,6 +306,24 @@ static __device__ __forceinline__ unsigned agg_step_nn(unsigned cl, const Census
 
 enum { AGG_H = 0, AGG_V = 1, AGG_D = 2 };
 
+// ---- census feed of the vertical and the wide diagonal lines (non-negative P1, census-fed) ----
+// The 64 / LPP lines of a wave sit on adjacent columns of one row, so their census-right windows are ONE contiguous run of
+// Dp + lines - 1 words (plus a word of margin on each side: the line that steps aside for the anomalous one moves by one column).
+// Loaded lane by lane every word of it came through the L1 Dp times per direction (1.9 GB per KITTI frame for a 1.9 MB image).
+// The wave loads the run once per step instead -- one 16-byte load in RUNW / 4 lanes, kept in the prefetch ring as 4 registers per
+// slot --, puts it into its LDS slot when the step comes up and every lane reads its DPL words from there.  A wave whose columns
+// straddle the wrap of a wide diagonal has a second run W words further down (loaded always: away from the wrap it is the first
+// one again -- a conditional load in the hot loop would drain the ring, NOTES.md 4.1).
+// Used where it replaces at least four loads per lane and a run fits one load of the wave: 16 disparities per lane on 8 lanes per
+// pixel, the batch layout of D <= 128.  Measured slower or no faster elsewhere (NOTES.md 26): 8 disparities per lane trade two
+// loads for one or two plus the LDS round trip, and the 261-word run of 16 lanes x 16 disparities needs two loads per run.
+template <int DPL, int LPP> struct agg_feed {
+    static constexpr int LPW = 64 / LPP;
+    static constexpr int RUNW = (DPL * LPP + LPW + 2 + 3) & ~3;            // words of a run, whole 16-byte groups
+    static constexpr bool on = DPL >= 16 && LPP <= 16 && RUNW / 4 <= 64;
+    static constexpr int BASE_DOWN = 16;                                   // words the load base lies below the lanes' own (run B starts up to LPW words in front of a row)
+};
+
 // Regular lines of one direction kind.  All addressing is 32-bit offsets from the volume bases
 // (the host guarantees W*H*Dp < 2^32); the walk is the reference's (ref :281-323, 359-367) with the
 // row test dropped (a regular line is never in the last row before its final step) and the two
@@ -319,9 +337,13 @@ enum { AGG_H = 0, AGG_V = 1, AGG_D = 2 };
 // (sgm_upsum.hip) cannot compute itself; a separate instantiation, so the ordinary lines pay nothing for it.
 template <int DPL, bool PAD, int LPP, int KIND, int NN, bool WIDE = false, bool VOL = false, bool PWO = false>
 static __device__ __forceinline__ void agg_regular(const AggArgs& a, const AggFrame& fr, const unsigned short* lut_s,
-                                                   const unsigned* lut32_s, int dir, int grp)
+                                                   const unsigned* lut32_s, unsigned* feed_s, int dir, int grp)
 {
     constexpr int NP = DPL / 2;
+    // the wave's shared census run (agg_feed) instead of every lane's own window
+    using FD = agg_feed<DPL, LPP>;
+    constexpr bool FEED = FD::on && NN != 0 && !VOL && !PWO && (KIND == AGG_V || (KIND == AGG_D && WIDE));
+    constexpr int NRUN = (KIND == AGG_D) ? 2 : 1;
     constexpr int PF = (LPP >= 32) ? SGM_AGG_PF_HL : SGM_AGG_PF;                              // prefetch depth (steps): 2 keeps the 8-lines-per-wave kernel at 8 waves/SIMD; the latency-critical 32-lane lines look further ahead
     const int lane = threadIdx.x;
     const int dx = a.dx[dir], dy = a.dy[dir];
@@ -344,13 +366,15 @@ static __device__ __forceinline__ void agg_regular(const AggArgs& a, const AggFr
     constexpr int LPW = 64 / LPP;                                          // path lines per wave
     const int sub = lane & (LPP - 1);
     const bool first_lane = (sub == 0), last_lane = (sub == LPP - 1);
-    int line = ((KIND == AGG_H) ? 0 : a.line_lo[dir]) + grp * LPW + lane / LPP;
+    const int line0 = ((KIND == AGG_H) ? 0 : a.line_lo[dir]) + grp * LPW;  // the wave's first line
+    int line = line0 + lane / LPP;
     bool store_ok = line < nlines;
     if (!store_ok) line = nlines - 1;                                      // keep the wave convergent; stores are masked
     if (KIND == AGG_D && line == a.anom_line[dir]) {                       // handled by agg_anomalous()
         store_ok = false;
         line = (line == 0) ? 1 : line - 1;
     }
+    const int feed_col = line - line0 + 1;                                 // FEED: the lane's column in the wave's run, 0 .. LPW + 1 (0 and LPW + 1: the margins)
     const unsigned lane_off = (unsigned)(sub * DPL);
     uint8_t* const plane = fr.planes + (size_t)dir * a.plane_bytes;
 
@@ -367,6 +391,7 @@ static __device__ __forceinline__ void agg_regular(const AggArgs& a, const AggFr
     int x;
     unsigned rowpix = 0, rowoff = 0, pcol = 0, col = 0;                    // AGG_D only
     int dstep_p = 0, dstep_off = 0;
+    unsigned frow = 0, fcol = 0;                                           // FEED: row start and column (wave-uniform) of the run's margin word feed_col = 0
     if (KIND == AGG_H) {
         x = fwd ? 0 : W - 1;
         p = (unsigned)((a.row_begin + line) * W + x);
@@ -377,6 +402,8 @@ static __device__ __forceinline__ void agg_regular(const AggArgs& a, const AggFr
         const int r = fwd ? a.row_begin - (import_state ? 1 : 0) : a.row_end - 1 + (import_state ? 1 : 0);
         p = (unsigned)(r * W + line);
         dstep_p = s * W; dstep_off = s * W * Dp;
+        frow = (unsigned)(r * W);
+        fcol = (unsigned)(line0 - 1);                                      // -1 for the first wave: the run starts one word in front of the row
     } else {
         rowpix = (unsigned)(fwd ? 0 : (H - 1) * W);
         rowoff = rowpix * (unsigned)Dp;
@@ -384,6 +411,8 @@ static __device__ __forceinline__ void agg_regular(const AggArgs& a, const AggFr
         x = line;
         p = rowpix + pcol;
         dstep_p = s * W; dstep_off = s * W * Dp;
+        frow = rowpix;
+        fcol = (unsigned)(line0 > 0 ? line0 - 1 : W - 1);
     }
     off = p * (unsigned)Dp + lane_off;
     const int col_step = (dx == dy) ? s : -s;                              // ref :360-367
@@ -403,7 +432,12 @@ static __device__ __forceinline__ void agg_regular(const AggArgs& a, const AggFr
         } else if (KIND == AGG_V) {
             p += (unsigned)dstep_p;
             off += (unsigned)dstep_off;
+            if constexpr (FEED) frow += (unsigned)dstep_p;
         } else if (WIDE) {
+            if constexpr (FEED) {                                          // the run's margin column walks like a line's
+                fcol = (fcol == wrap_at) ? wrap_to : fcol + (unsigned)col_step;
+                frow += (unsigned)dstep_p;
+            }
             const bool wrap = (pcol == wrap_at);
             if constexpr (PWO) wrapped = wrapped || wrap;
             pcol = wrap ? wrap_to : pcol + (unsigned)col_step;
@@ -438,6 +472,27 @@ static __device__ __forceinline__ void agg_regular(const AggArgs& a, const AggFr
         }
         g = fr.img[p];
     };
+    // FEED: the wave's run(s) of the cursor's row instead of the lane's own window.  Word i of run A is census-right word
+    // frow + fcol - dmin - Dp + 1 + i, i.e. lane (feed_col, sub) finds its window at i = feed_col + Dp - (sub + 1) * DPL; run B is the
+    // same W words further down -- where the lanes whose column has wrapped (column < feed_col) find theirs.  A lane loads its
+    // 16-byte group of a run; the lanes past the run's end load its last group again and store nothing.
+    struct FeedRegs { unsigned w[NRUN][4]; };
+    const char* const frb = reinterpret_cast<const char*>(fr.census_r - (a.dmin + Dp + FD::BASE_DOWN));
+    auto fetch_feed = [&](FeedRegs& f, unsigned& cl, uint8_t& g) {
+        struct __attribute__((packed, aligned(4))) u4 { unsigned a, b, c, d; };
+        const unsigned wa = frow + fcol + (unsigned)(FD::BASE_DOWN + 1);
+#pragma unroll
+        for (int r = 0; r < NRUN; ++r) {
+            const unsigned wr = (r == 1 && (int)fcol + FD::LPW + 1 >= W) ? wa - (unsigned)W : wa;
+            const unsigned grp4 = min((unsigned)lane, (unsigned)(FD::RUNW / 4 - 1));
+            const u4 t = *reinterpret_cast<const u4*>(frb + (size_t)((wr + 4 * grp4) << 2));
+            f.w[r][0] = t.a; f.w[r][1] = t.b; f.w[r][2] = t.c; f.w[r][3] = t.d;
+        }
+        cl = *reinterpret_cast<const uint32_t*>(clb_base + (size_t)(p << 2));
+        g = fr.img[p];
+    };
+    const unsigned feed_rd = (unsigned)(feed_col + Dp - (int)lane_off - DPL);        // the lane's first word in a run
+    const int feed_wrap_lim = feed_col - lim_bias;                                     // lim < this: the lane's column has wrapped (run B)
 
     // a diagonal line of a row tile: replay the walk from the frame edge up to the pixel before the tile (cheap
     // register arithmetic; it reproduces the tracker state exactly, early wraps included)
@@ -491,6 +546,7 @@ static __device__ __forceinline__ void agg_regular(const AggArgs& a, const AggFr
     // of every pass of the hot loop (one v_and per slot on the just-loaded registers, sunk to the loop latch), so the wave drained
     // ALL its outstanding loads and plane stores (s_waitcnt vmcnt(0)) every PF steps whatever the prefetch depth.
     CensusVec<DPL> cb[PF];
+    FeedRegs fb[PF];                                                       // FEED: the wave's runs instead of cb (4 registers per run)
     unsigned clb[PF];
     uint8_t gb[PF];
     int limb[PF];
@@ -501,14 +557,35 @@ static __device__ __forceinline__ void agg_regular(const AggArgs& a, const AggFr
         gb[u] = 0; ob[u] = off; clb[u] = 0; limb[u] = 0; wb[u] = false;
 #pragma unroll
         for (int i = 0; i < DPL; ++i) cb[u].r[i] = 0;
+        if constexpr (FEED) {
+#pragma unroll
+            for (int i = 0; i < NRUN * 4; ++i) (&fb[u].w[0][0])[i] = 0;
+        }
         if (1 + u <= nsteps) {
             advance();
             ob[u] = off;
             if constexpr (PWO) wb[u] = wrapped;
             limb[u] = x - lim_bias;
-            fetch(cb[u], clb[u], gb[u]);
+            if constexpr (FEED) fetch_feed(fb[u], clb[u], gb[u]);
+            else fetch(cb[u], clb[u], gb[u]);
         }
     }
+    // FEED: ring slot u's run(s) into the wave's LDS slot, then the lane's window out of it.  One wave, and the LDS serves a wave's
+    // accesses in order: the reads see this step's run, and the next step's writes come behind them.
+    auto feed_window = [&](const FeedRegs& f, int lim, CensusVec<DPL>& cv) {
+#pragma unroll
+        for (int r = 0; r < NRUN; ++r)
+            if (lane < FD::RUNW / 4) {
+                uint4 t;
+                t.x = f.w[r][0]; t.y = f.w[r][1]; t.z = f.w[r][2]; t.w = f.w[r][3];
+                *reinterpret_cast<uint4*>(feed_s + r * FD::RUNW + 4 * lane) = t;
+            }
+        __builtin_amdgcn_wave_barrier();
+        const unsigned* const src = feed_s + feed_rd + ((NRUN == 2 && lim < feed_wrap_lim) ? (unsigned)FD::RUNW : 0u);
+#pragma unroll
+        for (int i = 0; i < DPL; ++i) cv.r[i] = src[i];
+        __builtin_amdgcn_wave_barrier();
+    };
     const us2 p1v = splat((unsigned)a.p1);
     unsigned sent[2] = {0x00FF00FFu, 0x00FF00FFu};                         // agg_step_nn's carried sentinel registers
     if constexpr (NN) min_prev |= min_prev << 16;                          // ... and its packed minimum
@@ -523,6 +600,7 @@ static __device__ __forceinline__ void agg_regular(const AggArgs& a, const AggFr
         const unsigned dg = __builtin_amdgcn_sad_u8((unsigned)g, (unsigned)g_prev, 0u);   // |g - g_prev| (grey values: one byte)
         CellVec<DPL> packed;
         if constexpr (NN) {
+            if constexpr (FEED) feed_window(fb[u], lim, cb[u]);
             min_prev = agg_step_nn<DPL, PAD, LPP, NN == 2>(clb[u], cb[u], lim, __any(lim < DPL - 1) != 0, Lp, min_prev, lut32_s[dg], p1v,
                                                   padmask, first_lane, last_lane, sent, packed);
             if (refill) {                                                      // the slot's census words are consumed now
@@ -530,7 +608,8 @@ static __device__ __forceinline__ void agg_regular(const AggArgs& a, const AggFr
                 ob[u] = off;
                 if constexpr (PWO) wb[u] = wrapped;
                 limb[u] = x - lim_bias;
-                fetch(cb[u], clb[u], gb[u]);
+                if constexpr (FEED) fetch_feed(fb[u], clb[u], gb[u]);
+                else fetch(cb[u], clb[u], gb[u]);
             }
         } else {
             us2 C[NP];
@@ -840,13 +919,17 @@ __global__ __launch_bounds__(64) void sgm_aggregate_k(const AggArgs a)
         }
     } probe{clk0, rt0};
 #endif
-    __shared__ unsigned short lut_s[256];
+    // the generic step reads lut_s, the non-negative-P1 steps lut32_s only; the census-fed ones of those also have the wave's
+    // census runs here (agg_feed: two runs, the second for a wave on the wrap of a wide diagonal)
+    constexpr bool FEEDS = NN != 0 && !VOL && agg_feed<DPL, LPP>::on;
+    __shared__ unsigned short lut_s[NN != 0 ? 2 : 256];
     __shared__ unsigned lut32_s[256];                        // the same penalties in both halves of a dword (packed u16 operand)
+    __shared__ __attribute__((aligned(16))) unsigned feed_s[FEEDS ? 2 * agg_feed<DPL, LPP>::RUNW : 4];
     const int lane = threadIdx.x;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const unsigned pen = a.lut[lane * 4 + i];
-        lut_s[lane * 4 + i] = (unsigned short)pen;
+        if constexpr (NN == 0) lut_s[lane * 4 + i] = (unsigned short)pen;
         lut32_s[lane * 4 + i] = pen * 0x00010001u;
     }
     __syncthreads();
@@ -905,20 +988,20 @@ __global__ __launch_bounds__(64) void sgm_aggregate_k(const AggArgs a)
     // they get 32 lanes per pixel -- fewer disparities per lane, the shortest step -- while the vertical and
     // diagonal lines keep the lane count that costs the fewest instructions per cell
     if (a.dy[dir] == 0) {
-        if constexpr (HL != 0) agg_regular<DPL * LPP / HL, PAD, HL, AGG_H, NN, false, VOL>(a, fr, lut_s, lut32_s, dir, grp);
-        else               agg_regular<DPL, PAD, LPP, AGG_H, NN, false, VOL>(a, fr, lut_s, lut32_s, dir, grp);
+        if constexpr (HL != 0) agg_regular<DPL * LPP / HL, PAD, HL, AGG_H, NN, false, VOL>(a, fr, lut_s, lut32_s, feed_s, dir, grp);
+        else               agg_regular<DPL, PAD, LPP, AGG_H, NN, false, VOL>(a, fr, lut_s, lut32_s, feed_s, dir, grp);
     }
-    else if (a.dx[dir] == 0) agg_regular<DPL, PAD, LPP, AGG_V, NN, false, VOL>(a, fr, lut_s, lut32_s, dir, grp);
+    else if (a.dx[dir] == 0) agg_regular<DPL, PAD, LPP, AGG_V, NN, false, VOL>(a, fr, lut_s, lut32_s, feed_s, dir, grp);
     else if (a.W > a.H) {
         if constexpr (NN != 0 && !VOL) {                                      // the fused last sweep exists for the non-negative-P1 census path only
             if ((a.post_wrap_mask >> dir) & 1) {
-                agg_regular<DPL, PAD, LPP, AGG_D, NN, true, VOL, true>(a, fr, lut_s, lut32_s, dir, grp);
+                agg_regular<DPL, PAD, LPP, AGG_D, NN, true, VOL, true>(a, fr, lut_s, lut32_s, feed_s, dir, grp);
                 return;
             }
         }
-        agg_regular<DPL, PAD, LPP, AGG_D, NN, true, VOL>(a, fr, lut_s, lut32_s, dir, grp);
+        agg_regular<DPL, PAD, LPP, AGG_D, NN, true, VOL>(a, fr, lut_s, lut32_s, feed_s, dir, grp);
     }
-    else                     agg_regular<DPL, PAD, LPP, AGG_D, NN, false, VOL>(a, fr, lut_s, lut32_s, dir, grp);
+    else                     agg_regular<DPL, PAD, LPP, AGG_D, NN, false, VOL>(a, fr, lut_s, lut32_s, feed_s, dir, grp);
 }
 
 template <int DPL, int LPP, int HL, int NN>

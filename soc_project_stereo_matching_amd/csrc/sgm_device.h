@@ -123,7 +123,8 @@ int sgmd_census_sym(int ord, void* stream, const sgmd_geom* g, int cw, int ch, c
 /* All directions of the path aggregation in ONE launch.  SemiGlobalMatching.c:198-372.
  * The matching cost (SemiGlobalMatching.c:161-196) is recomputed from the census images inside the
  * kernel; census_r must be preceded by at least sgmd_census_slack(g) readable bytes (disparities that
- * reach left of column 0 read there and are masked to 127).
+ * reach left of column 0 read there and are masked to 127) and followed by 64 readable bytes (a wave's
+ * census run is loaded in whole 16-byte groups).
  * planes: u8 [ndirs][H][W][Dp] per-direction path costs L_r; extras: u8 [4][H][Dp] path costs of
  * the four anomalous diagonal lines (step-major); lut: u16[256] = (uint16)max(P1, P2/(a+1)). */
 size_t sgmd_census_slack(const sgmd_geom* g);

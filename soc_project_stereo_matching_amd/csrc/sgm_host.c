@@ -21,6 +21,9 @@
 
 #define SGM_VERSION_STRING "sgm_mi355x 0.3 (gfx950, hand-written HIP)"
 #define CENSUS_FRONT_SLACK ((size_t)(65535 + SGM_MAX_DISPARITY_RANGE + 8 + 63) / 64 * 64 * 4)   /* >= sgmd_census_slack() for any options */
+/* the aggregation loads a wave's census run in whole 16-byte groups, up to 12 words past the last pixel: readable bytes behind
+ * the census-right words (allocated, never written: nothing uses what is read there) */
+#define CENSUS_BACK_SLACK ((size_t)64)
 
 #define TIMING_RING 64
 enum { T_CENSUS, T_COST, T_AGGREGATE, T_SUM, T_WTA, T_LRCHECK, T_SPECKLE, T_MEDIAN, T_COUNT };
@@ -913,7 +916,7 @@ static bool ensure_buffers(sgm_instance* s)
          * afterwards); give the buffer that much readable slack in front, sized for the largest options */
         const size_t img = image_bytes(s);
         const buf_request images[] = {{&s->d_left, img, 0}, {&s->d_right, img, 0}, {&s->d_census_l, px * 4, 0},
-                                      {&s->d_census_r_alloc, CENSUS_FRONT_SLACK + px * 4, 0}};
+                                      {&s->d_census_r_alloc, CENSUS_FRONT_SLACK + px * 4 + CENSUS_BACK_SLACK, 0}};
         const buf_request maps[] = {{&s->d_disp, px * 4, 0}, {&s->d_disp_r, px * 4, 0}, {&s->d_labels, px * 4, 0}, {&s->d_sizes, px * 4, 0},
                                     {&s->d_totals, px * 4, 0}, {&s->d_lut, 512, 0}, {&s->d_snap_wta, px * 4, 0}, {&s->d_snap_lr, px * 4, 0},
                                     {&s->d_snap_speckle, px * 4, 0}, {&s->h_left, img, BUF_PINNED}, {&s->h_right, img, BUF_PINNED},
