@@ -576,6 +576,80 @@ bool   sgm_match_scaled_device(sgm_instance* s, const sgm_scale_spec* spec, cons
                                float* d_disp_full);
 bool   SGM_MatchScaled(const sgm_scale_spec* spec, const uint8_t* img_left, const uint8_t* img_right, float* disp_full);   /* the default instance */
 
+/* ---- temporal filter for streams of maps: history, motion gate, hold ----
+ * Extension, "parity unpinned by the reference" (it treats every frame as the only one); defined here and restated by
+ * tests/temporal_ref.py.  The device matches it bit for bit.  All arithmetic is float32, every operation rounded on its own,
+ * subnormals kept.  "Finite" always means by bit pattern, exponent bits not all ones: a caller's map may hold NaN.
+ *
+ * State per stream and pixel: hv (f32), the last output value, starts at +INF; hb (u8), the validity of the last eight INPUTS,
+ * newest in bit 0, starts at 0.  Constants: a = alpha, b = 1.0f - a, rounded once on the host.
+ * One step, with input x, optional confidence K, n = hold_window, k = hold_count and cnt = popcount(hb & ((1 << n) - 1)):
+ *   1. valid = finite(x) && (no confidence given || min_conf == 0 || K >= min_conf).
+ *   2. The decision; the classes are numbered for the statistics.
+ *        0 first     valid and hv not finite:                                   out = x
+ *        1 smoothed  valid, hv finite and fabsf(x - hv) <= delta:               out = a * x + b * hv   (two products and one sum,
+ *                                                                               each rounded; hence alpha == 1 returns x)
+ *        2 replaced  valid, hv finite, gate exceeded (motion, an edge):         out = x
+ *        3 held      not valid, n > 0, hv finite and cnt >= k:                  out = hv
+ *        4 invalid   otherwise:                                                 out = +INF
+ *   3. hb' = (hb << 1 | valid) & 0xFF.
+ *   4. hv' = out if out is finite; else +INF if hb' == 0 (the history forgets after eight invalid inputs); else hv.
+ * The validity bits record inputs, not outputs: a held value cannot keep itself alive.  The steps of a stream run in order,
+ * pixels are independent, and the result is a pure function of (state, inputs, spec), also for arbitrary caller-made state.
+ * Statistics: uint32_t [maps][5], one exact count per class and map; maps = streams x steps in the order the maps lie in memory.
+ *
+ * sgm_temporal_filter: the filter on any device maps, in place.  d_maps f32 [streams][steps][pixels]; d_conf u16 of the same
+ *   shape, or NULL; the history d_hist_value f32 / d_hist_bits u8 [streams][pixels]; d_stats [streams * steps][5] or NULL, zeroed
+ *   by the call on the stream.  spec->sequence and spec->stats are not looked at: the geometry and d_stats say it.  Asynchronous on
+ *   sgm_stream(s), behind the last match; needs no initialised instance and no alignment beyond the element's (a map that cannot
+ *   be read 16 bytes at a time takes a one-pixel-per-lane path with the same results).  false, nothing queued and a message on
+ *   stderr: a NULL required pointer, a pointer that is not aligned to its element, a spec outside its ranges, streams, steps or
+ *   pixels < 1 or a product above 2^31, a build without the kernel.
+ * sgm_temporal_clear: +INF / 0 into streams x pixels history entries, on the stream.
+ * sgm_set_temporal (SGM_SetTemporal: the default instance, remembered across SGM_Shutdown): turns the filter on for matches, NULL
+ *   turns it off; takes effect at the next SGM_Initialize / sgm_initialize / SGM_Reset / sgm_reset, which return false in row-tile
+ *   mode (sgm_set_rows) with it on.  false, and nothing changes, for a spec outside its ranges, a build without the kernel, or
+ *   min_conf > 0 in a build without the confidence kernels.  Every entry point then returns the filtered map: sgm_match, _async,
+ *   _device, sgm_compute, sgm_match_confidence*, sgm_match_both* (both maps, each view with a history of its own),
+ *   sgm_match_planes* (the depth is computed from the filtered map) and sgm_match_scaled* (its small map, because it runs the
+ *   ordinary match).  The filter is the last step of the post pass -- after the median, after hole filling, after the refinement
+ *   -- on the post-pass stream; timing: it counts toward "median".  With min_conf > 0 every match computes the confidence the way a
+ *   refining instance does (into the caller's map where one is given, else into an internal one; the fused last sweep is not
+ *   used) and sgm_match_both* is refused, the confidence being defined for one reference view; with min_conf == 0 no confidence is
+ *   computed for the filter's sake.  sequence = 0: the B frames of a batch are B streams; sequence = 1: they are B consecutive
+ *   frames of ONE stream.
+ * History lifetime.  The history belongs to the instance.  It SURVIVES sgm_reset / sgm_initialize with an unchanged stream
+ *   signature -- the per-frame Reset of a stream.  It restarts (a clear queued on the stream the filter runs on, ahead of its next
+ *   launch) when the signature of the match about to be filtered differs from that of the last filtered one -- width, height,
+ *   batch, reference view, single or both views, sequence --, after every sgm_set_temporal(s, non-NULL), and after
+ *   sgm_temporal_restart(s), the caller's scene cut.  A match that fails before or at the filter's launch leaves the history
+ *   exactly as it was.
+ * sgm_temporal_stats (blocking): the counters of the last match, [B * views][5], into out (room for `capacity` maps); returns the
+ *   number of maps written, 0 when stats was off, nothing was filtered yet or capacity is too small.
+ * Stage read-back: 8 stays "what the match returned"; 29 the map as it entered the filter (needs sgm_keep_stages); 30 hv and 31 hb
+ *   of the selected frame's stream after the last match; 32 / 33 / 34 the same three for the right view after sgm_match_both.  With
+ *   sequence = 1 every frame index reads the one stream for 30 / 31 (33 / 34).
+ * An instance that never calls sgm_set_temporal with a spec allocates and launches exactly what it did before.
+ * Not part of it: motion compensation, filtering the confidence map, row tiles, a history shared between instances. */
+typedef struct {            /* 28 bytes, every field 4 bytes, no padding */
+    float    alpha;         /* weight of the new measurement, finite, 0 < alpha <= 1 */
+    float    delta;         /* gate in disparities, finite, >= 0 */
+    int32_t  hold_window;   /* n: 0..8; 0 = holes are never bridged */
+    int32_t  hold_count;    /* k: 1..n (not looked at with n == 0) */
+    int32_t  sequence;      /* 0: every frame of a batch is a stream of its own; 1: the B frames of a call are consecutive frames of ONE stream */
+    uint32_t min_conf;      /* 0..65535; > 0: a measurement whose matching confidence is below it counts as a hole */
+    int32_t  stats;         /* 0 / 1: count the decisions */
+} sgm_temporal_spec;
+bool   sgm_temporal_filter(sgm_instance* s, const sgm_temporal_spec* spec, size_t streams, size_t steps, size_t pixels, float* d_maps,
+                           const uint16_t* d_conf, float* d_hist_value, uint8_t* d_hist_bits, uint32_t* d_stats);
+bool   sgm_temporal_clear(sgm_instance* s, size_t streams, size_t pixels, float* d_hist_value, uint8_t* d_hist_bits);
+bool   sgm_set_temporal(sgm_instance* s, const sgm_temporal_spec* spec);
+bool   sgm_temporal_restart(sgm_instance* s);
+int    sgm_temporal_stats(sgm_instance* s, uint32_t* out, int capacity);
+bool   SGM_SetTemporal(const sgm_temporal_spec* spec);
+bool   SGM_TemporalRestart(void);
+int    SGM_TemporalStats(uint32_t* out, int capacity);
+
 /* The filling of SGM_SetFillHoles (step 2) on any device map: d_disp, the instance's B frames of its shape, is filled in
  * place with R = the option's max_disparity; d_class (u8 [B][H][W], classes 0/1/2) drives passes 1 and 2, NULL runs pass 3
  * alone.  Asynchronous on sgm_stream(s), behind the last match.  Works whether or not filling is on for matches; the filled
@@ -623,6 +697,9 @@ bool   sgm_match_planes(sgm_instance* s, const uint8_t* planes, float fx, float 
  *        after a sgm_match_both (SGM_MatchBoth), where 4, 6, 7, 8 are the LEFT view's maps and 5 the raw right-view map:
  *        26 right view after the LR check   27 right view after speckle removal   (both need sgm_keep_stages during that match)
  *        28 right view, final               (all f32 [H][W]; 0 bytes after any other kind of match or a sgm_match_both that failed)
+ *        with the temporal filter on (sgm_set_temporal), after a match it filtered:
+ *        29 the map as it entered the filter (f32 [H][W]; needs sgm_keep_stages)   30 hv (f32 [H][W])   31 hb (u8 [H][W])
+ *        32 / 33 / 34 the same three for the right view after a sgm_match_both
  * Returns the number of bytes written, 0 on error or if `capacity` is too small. */
 size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacity);
 size_t SGM_ReadStage(int which, void* host_out, size_t capacity);

@@ -292,6 +292,26 @@ int sgmd_downscale(int ord, void* stream, const sgmd_scale* c, const void* in, v
 int sgmd_upscale(int ord, void* stream, const sgmd_scale* c, const void* disp_small, const void* guide_small, const void* guide_full,
                  const void* census_ref, const void* census_oth, void* disp_full);
 
+/* Extension (parity unpinned by the reference), the temporal filter of include/sgm_mi355x.h (sgm_temporal_spec); sgm_temporal.hip.
+ * p: the spec as the host validated it -- a = alpha, b = 1.0f - a rounded once by the host, n = 0..8, k = 1..n (n == 0: not looked
+ * at).  maps f32 [streams][steps][pixels], filtered in place; conf u16 of that shape or NULL (also with min_conf == 0: the test
+ * is then always true); hist_value f32 and hist_bits u8 [streams][pixels], read once and written once per call however many
+ * steps; stats u32 [streams * steps][5] or NULL, zeroed by the call on the stream, then counted; scratch: NULL, or
+ * sgmd_temporal_scratch_bytes() bytes the call spreads the waves' counter adds over before it sums them into stats (few maps are
+ * few cache lines for thousands of adds), which must not be shared with a call still in flight.  No alignment beyond the
+ * element's: pointers or a pixel count that do not allow 16-byte accesses take a one-pixel-per-lane path with the same results.
+ * streams, steps, pixels >= 1 and streams * steps * pixels <= 2^31.  sgmd_temporal_clear: hist_value <- +INF, hist_bits <- 0,
+ * count entries each.  sgm_host.c references both weakly (a host built without them answers false to the temporal entry points). */
+typedef struct {
+    float a, b, delta;
+    int n, k;
+    unsigned min_conf;
+} sgmd_temporal_params;
+int sgmd_temporal(int ord, void* stream, const sgmd_temporal_params* p, size_t streams, size_t steps, size_t pixels, void* maps,
+                  const void* conf, void* hist_value, void* hist_bits, void* stats, void* scratch);
+size_t sgmd_temporal_scratch_bytes(void);
+int sgmd_temporal_clear(int ord, void* stream, size_t count, void* hist_value, void* hist_bits);
+
 /* grey = (weight_r r + 150 g + 29 b) >> 8 of three consecutive n-byte planes B, G, R (the test platform's frame
  * format, server.py:105-131; the firmware's conversion, stereo_matching.c:18-25) */
 int sgmd_gray_planes(int ord, void* stream, const void* bgr, size_t n, int weight_r, void* gray);

@@ -163,6 +163,19 @@ struct sgm_instance {
      * images, the full map and their page-locked staging */
     sgm_buf d_sc_small_l, d_sc_small_r, d_sc_census_l, d_sc_census_r, d_sc_g8_l, d_sc_g8_r, d_sc_full_l, d_sc_full_r, d_sc_disp;
     sgm_buf h_sc_l, h_sc_r, h_sc_disp;
+    /* temporal filter (sgm_set_temporal): the spec last set and whether one is; the spec in effect for this shape and whether one is.
+     * The history -- hv f32 and hb u8 [views][streams][H][W], streams = B or (sequence) 1 --, the counters u32 [views][B][5], and for
+     * sgm_keep_stages the maps as they entered the filter (f32 [views][B][H][W]); the second view's share only once a
+     * sgm_match_both ran.  tp_sig: W, H, B, reference view, views, sequence of the last filtered match ([0] == 0: none, the
+     * history is to be cleared); tp_restart: a clear is owed for another reason (sgm_set_temporal, sgm_temporal_restart);
+     * tp_stat_maps: counter rows the last match filled (0: none) */
+    sgm_temporal_spec tp_req, tp_eff;
+    bool temporal_req, temporal_on;
+    sgm_buf d_tp_value, d_tp_bits, d_tp_stats, d_tp_pre;
+    sgm_buf d_tp_scratch;        /* where a filter launch that counts spreads its counter adds (sgmd_temporal_scratch_bytes; first use) */
+    int tp_sig[6];
+    bool tp_restart;
+    int tp_stat_maps;
     bool last_both;              /* the last match was a sgm_match_both that was queued to its end: stage 8 is the first half of d_both_maps */
     bool last_both_kept;         /* ... and it ran with sgm_keep_stages: d_both_snap holds ITS right-view snapshots (stages 26, 27) */
     size_t plane_bytes;
@@ -195,7 +208,8 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     DEVICE_BUF(d_cloud_scratch), DEVICE_BUF(d_cloud_points), DEVICE_BUF(d_cloud_offsets), DEVICE_BUF(d_g8_l), DEVICE_BUF(d_g8_r),
     DEVICE_BUF(d_sc_small_l), DEVICE_BUF(d_sc_small_r), DEVICE_BUF(d_sc_census_l), DEVICE_BUF(d_sc_census_r), DEVICE_BUF(d_sc_g8_l),
     DEVICE_BUF(d_sc_g8_r), DEVICE_BUF(d_sc_full_l), DEVICE_BUF(d_sc_full_r), DEVICE_BUF(d_sc_disp), PINNED_BUF(h_sc_l), PINNED_BUF(h_sc_r),
-    PINNED_BUF(h_sc_disp),
+    PINNED_BUF(h_sc_disp), DEVICE_BUF(d_tp_value), DEVICE_BUF(d_tp_bits), DEVICE_BUF(d_tp_stats), DEVICE_BUF(d_tp_pre),
+    DEVICE_BUF(d_tp_scratch),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -412,6 +426,8 @@ static void free_device_buffers(sgm_instance* s)
     s->up_key[0] = 0;
     s->tab_W = s->tab_H = 0;
     s->rect_dirty = true;
+    s->tp_sig[0] = 0;                                            /* the history went with its buffers */
+    s->tp_stat_maps = 0;
 }
 
 void sgm_destroy(sgm_instance* s)
@@ -624,6 +640,65 @@ bool sgm_set_refine(sgm_instance* s, int enable, float lambda, float sigma, int 
     s->rf_req = p;
     s->refine_req = 1;
     return true;
+}
+
+/* ------------------------------------------------------------------ temporal filter (extension) */
+
+/* The launchers of sgm_temporal.hip, weakly referenced like the extensions above: a host built without them has no temporal filter */
+#pragma weak sgmd_temporal
+#pragma weak sgmd_temporal_clear
+#pragma weak sgmd_temporal_scratch_bytes
+static bool temporal_available(void) { return sgmd_temporal != NULL && sgmd_temporal_clear != NULL && sgmd_temporal_scratch_bytes != NULL; }
+
+/* the spec as the kernel takes it; false for anything outside the ranges of include/sgm_mi355x.h.  flags: sequence and stats are
+ * checked too (sgm_set_temporal; sgm_temporal_filter does not look at them) */
+static bool temporal_spec_valid(const sgm_temporal_spec* sp, bool flags, sgmd_temporal_params* c)
+{
+    if (!isfinite(sp->alpha) || !(sp->alpha > 0.0f) || !(sp->alpha <= 1.0f) || !isfinite(sp->delta) || !(sp->delta >= 0.0f)) return false;
+    if (sp->hold_window < 0 || sp->hold_window > 8 || sp->min_conf > 65535u) return false;
+    if (sp->hold_window > 0 && (sp->hold_count < 1 || sp->hold_count > sp->hold_window)) return false;
+    if (flags && ((sp->sequence != 0 && sp->sequence != 1) || (sp->stats != 0 && sp->stats != 1))) return false;
+    const float b = 1.0f - sp->alpha;
+    if (c) *c = (sgmd_temporal_params){sp->alpha, b, sp->delta, sp->hold_window, sp->hold_window > 0 ? sp->hold_count : 0, sp->min_conf};
+    return true;
+}
+
+/* what sgm_set_temporal / SGM_SetTemporal check */
+static bool temporal_spec_ok(const sgm_temporal_spec* spec)
+{
+    if (!temporal_available()) FAIL("the temporal filter is not part of this build");
+    if (!temporal_spec_valid(spec, true, NULL)) FAIL("the temporal spec is outside its ranges (include/sgm_mi355x.h, sgm_temporal_spec)");
+    if (spec->min_conf > 0 && !conf_available()) FAIL("a temporal filter with min_conf > 0 needs the confidence kernels, which are not part of this build");
+    return true;
+}
+
+bool sgm_set_temporal(sgm_instance* s, const sgm_temporal_spec* spec)
+{
+    if (!s) return false;
+    if (!spec) {
+        s->temporal_req = false;                                 /* takes effect at the next initialize */
+        return true;
+    }
+    if (!temporal_spec_ok(spec)) return false;
+    s->tp_req = *spec;
+    s->temporal_req = true;
+    s->tp_restart = true;                                        /* every spec set starts a new history */
+    return true;
+}
+
+bool sgm_temporal_restart(sgm_instance* s)
+{
+    if (!s) return false;
+    s->tp_restart = true;
+    return true;
+}
+
+/* what the standalone entry points check of their geometry */
+static bool temporal_geometry_ok(size_t streams, size_t steps, size_t pixels)
+{
+    const size_t lim = (size_t)1 << 31;
+    return streams >= 1 && steps >= 1 && pixels >= 1 && streams <= lim && steps <= lim && pixels <= lim && streams * steps <= lim &&
+           streams * steps * pixels <= lim;
 }
 
 /* ------------------------------------------------------------------ rectification (extension) */
@@ -1005,6 +1080,29 @@ static int ensure_refine(sgm_instance* s)
     return -1;
 }
 
+/* streams per view of the filter in effect: the B frames of a batch, or (sequence) one */
+static size_t temporal_streams(const sgm_instance* s) { return s->tp_eff.sequence ? 1 : (size_t)s->g.B; }
+
+/* The history, the counters, the internal confidence (min_conf > 0) and, for sgm_keep_stages, the pre-filter maps, for `views` views.
+ * A history that has to grow is a new one: its signature goes, the next filtered match clears it. */
+static int ensure_temporal(sgm_instance* s, int views, bool keep)
+{
+    const size_t px = frame_px(s), hist = (size_t)views * temporal_streams(s) * px;
+    if (!buf_holds(&s->d_tp_value, hist * sizeof(float)) || !buf_holds(&s->d_tp_bits, hist)) s->tp_sig[0] = 0;
+    const buf_request bufs[] = {{&s->d_tp_value, hist * sizeof(float), 0}, {&s->d_tp_bits, hist, 0},
+                                {&s->d_tp_stats, (size_t)views * s->g.B * 5 * sizeof(uint32_t), 0},
+                                {&s->d_rf_conf, s->tp_eff.min_conf > 0 ? batch_px(s) * sizeof(uint16_t) : 0, 0},
+                                {&s->d_tp_pre, keep ? (size_t)views * map_bytes(s) : 0, 0},
+                                {&s->d_tp_scratch, s->tp_eff.stats ? sgmd_temporal_scratch_bytes() : 0, 0}};
+    buf_request want[6];
+    int n = 0;
+    for (int i = 0; i < 6; ++i)
+        if (bufs[i].bytes) want[n++] = bufs[i];
+    if (reserve_all(s, want, n, 0)) return 0;
+    fprintf(stderr, "sgm_mi355x: device allocation failed for the temporal filter of %d views of %dx%d\n", views, s->g.W, s->g.H);
+    return -1;
+}
+
 /* the 2 T passes of the refinement on `disp`, in place (include/sgm_mi355x.h, sgm_set_refine) */
 static int refine_passes(sgm_instance* s, void* st, void* disp, const void* conf, const void* guide, const refine_params* p)
 {
@@ -1122,6 +1220,9 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
     if (s->refine_req && s->fill_req)
         FAIL("the refinement (sgm_set_refine) and hole filling (sgm_set_fill_holes) do not combine: the refinement fills by itself, "
              "and a filled pixel would carry the confidence of a disparity the LR check rejected");
+    s->temporal_on = false;
+    if (s->temporal_req && row_tiled(s))
+        FAIL("the temporal filter (sgm_set_temporal) works on whole frames: not available in row-tile mode (sgm_set_rows)");
     s->rect_on = false;
     if (s->rect_q && row_tiled(s))
         FAIL("the rectification (sgm_set_rectify) works on whole frames: not available in row-tile mode (sgm_set_rows)");
@@ -1140,6 +1241,12 @@ bool sgm_initialize(sgm_instance* s, uint16_t width, uint16_t height, const SGMO
         if (ensure_refine(s) != 0) return false;
         s->rf_eff = s->rf_req;
         s->refine_on = true;
+    }
+    if (s->temporal_req) {
+        /* (the history survives this: its buffers only grow, and what restarts it is decided where the filter is launched) */
+        s->tp_eff = s->tp_req;
+        if (ensure_temporal(s, 1, false) != 0) return false;
+        s->temporal_on = true;
     }
     /* extras: 4 anomalous lines x H steps x Dp bytes */
     const size_t extras_bytes = (size_t)s->g.B * 4 * height * s->g.Dp;
@@ -1401,6 +1508,30 @@ static int ensure_both(sgm_instance* s, bool keep, bool staging)
  * choose by batch size (speckle tile rows, the median's bands) they choose as a plain match with 2 B frames would.  of_match: the tail
  * of a match -- timed, snapshotted for sgm_keep_stages, hole filling and refinement (conf, guide) hooked in; else the two stages alone. */
 typedef struct { void *labels, *sizes, *totals, *median; } post_scratch;      /* the speckle and median scratch of B maps, or of 2 B */
+
+/* The filter behind a match's post pass, on the maps it finished (views == 2: the B left maps, then the right ones): the clear a
+ * restart owes, the snapshot for sgm_keep_stages, the launch.  The host's record of the history changes exactly where a launch was
+ * accepted: a clear that was queued has restarted the history under the new signature whatever happens next, and a refused
+ * filter launch leaves history and record as they were. */
+static int temporal_stage(sgm_instance* s, void* st, void* maps, int views, const void* conf)
+{
+    const size_t streams = temporal_streams(s), px = frame_px(s);
+    const int sig[6] = {s->g.W, s->g.H, s->g.B, views == 2 ? 0 : s->reference_view, views, s->tp_eff.sequence};
+    sgmd_temporal_params c;
+    if (!temporal_spec_valid(&s->tp_eff, true, &c)) return -1;
+    if (ensure_temporal(s, views, s->keep_stages != 0) != 0) return -1;
+    if (s->tp_restart || memcmp(sig, s->tp_sig, sizeof sig) != 0) {
+        if (sgmd_temporal_clear(s->device, st, (size_t)views * streams * px, s->d_tp_value.p, s->d_tp_bits.p) != 0) return -1;
+        memcpy(s->tp_sig, sig, sizeof sig);
+        s->tp_restart = false;
+    }
+    if (s->keep_stages && sgmd_d2d_async(s->device, st, s->d_tp_pre.p, maps, (size_t)views * map_bytes(s)) != 0) return -1;
+    const int rc = sgmd_temporal(s->device, st, &c, (size_t)views * streams, s->tp_eff.sequence ? (size_t)s->g.B : 1, px, maps,
+                                 s->tp_eff.min_conf > 0 ? conf : NULL, s->d_tp_value.p, s->d_tp_bits.p,
+                                 s->tp_eff.stats ? s->d_tp_stats.p : NULL, s->tp_eff.stats ? s->d_tp_scratch.p : NULL);
+    if (rc == 0) s->tp_stat_maps = s->tp_eff.stats ? views * s->g.B : 0;
+    return rc;
+}
 static int post_pass(sgm_instance* s, void* st, void* maps, int views, bool of_match, const void* conf, const void* guide)
 {
     const SGMOption* o = &s->opt;
@@ -1420,6 +1551,7 @@ static int post_pass(sgm_instance* s, void* st, void* maps, int views, bool of_m
     if (of_match) mark_on(s, st, T_MEDIAN);
     rc = sgmd_median(s->device, st, &g, maps, x.median, s->h_status);                                     /* .c:120 */
     if (rc == 0 && of_match && s->refine_on) rc = refine_passes(s, st, maps, conf, guide, &s->rf_eff);   /* extension; timed as "median" */
+    if (rc == 0 && of_match && s->temporal_on) rc = temporal_stage(s, st, maps, views, conf);            /* extension; timed as "median" */
     return rc;
 }
 
@@ -1454,7 +1586,9 @@ static bool run_pipeline(sgm_instance* s, const void* d_left, const void* d_righ
     const bool overlap = s->overlap_post && s->post_stream && !row_tiled(s);
     void *sts = st, *st2 = st;
     s->last_both = s->last_both_kept = false;                    /* until this match is queued to its end */
+    s->tp_stat_maps = 0;                                         /* until this match's filter launch is accepted */
     if (s->refine_on && !d_conf) d_conf = s->d_rf_conf.p;        /* the refinement needs the confidence: an internal map */
+    if (s->temporal_on && s->tp_eff.min_conf > 0 && !d_conf) d_conf = s->d_rf_conf.p;   /* ... and so does a temporal filter with min_conf */
     /* the aggregation rewrites the planes the previous match's cost sum may still be reading on its own stream */
     if (s->sum_pending) LAUNCH(sgmd_stream_wait_event(dev, st, s->ev_sum));
     LAUNCH(materialize_S(s));                                /* Match without Reset: S of the previous frame is needed now */
@@ -1895,6 +2029,8 @@ static bool both_ready(sgm_instance* s, const void* l, const void* r, const void
     if (!whole_frames(s, l && r && disp_l && disp_r, TILED_BOTH)) return false;
     if (s->fill_on || s->refine_on)
         FAIL("sgm_match_both does not combine with hole filling or the refinement: their class map and confidence are defined for one view");
+    if (s->temporal_on && s->tp_eff.min_conf > 0)
+        FAIL("sgm_match_both does not combine with a temporal filter with min_conf > 0: the confidence is defined for one view");
     if (!both_available()) FAIL("sgm_match_both is not part of this build");
     return true;
 }
@@ -1902,7 +2038,7 @@ static bool both_ready(sgm_instance* s, const void* l, const void* r, const void
 bool sgm_match_both_device(sgm_instance* s, const uint8_t* d_left, const uint8_t* d_right, float* d_disp_left, float* d_disp_right)
 {
     if (!both_ready(s, d_left, d_right, d_disp_left, d_disp_right) || !images_aligned(s, d_left, d_right) ||
-        ensure_both(s, s->keep_stages != 0, false) != 0)
+        ensure_both(s, s->keep_stages != 0, false) != 0 || (s->temporal_on && ensure_temporal(s, 2, s->keep_stages != 0) != 0))
         return false;
     const both_out out = {d_disp_left, d_disp_right};
     return run_pipeline(s, d_left, d_right, s->d_both_raw.p, NULL, &out);
@@ -1916,7 +2052,8 @@ bool sgm_match_both_async(sgm_instance* s, const uint8_t* img_left, const uint8_
     host_out out[2] = {{disp_left, &s->h_disp, &s->d_both_maps, 0, bytes, false},
                        {disp_right, &s->h_disp_r, &s->d_both_maps, bytes, bytes, false}};
     outputs_pinned(s, out, 2);
-    if (ensure_both(s, s->keep_stages != 0, !out[1].pinned) != 0) return false;
+    if (ensure_both(s, s->keep_stages != 0, !out[1].pinned) != 0 || (s->temporal_on && ensure_temporal(s, 2, s->keep_stages != 0) != 0))
+        return false;
     const both_out maps = {NULL, NULL};
     const size_t img = image_bytes(s);
     const bool ok = upload(s, s->d_left.p, img_left, s->h_left.p, img) && upload(s, s->d_right.p, img_right, s->h_right.p, img) &&
@@ -2209,6 +2346,49 @@ bool sgm_match_scaled(sgm_instance* s, const sgm_scale_spec* spec, const uint8_t
     return true;
 }
 
+/* ------------------------------------------------------------------ temporal filter of any maps (extension) */
+
+bool sgm_temporal_filter(sgm_instance* s, const sgm_temporal_spec* spec, size_t streams, size_t steps, size_t pixels, float* d_maps,
+                         const uint16_t* d_conf, float* d_hist_value, uint8_t* d_hist_bits, uint32_t* d_stats)
+{
+    sgmd_temporal_params c;
+    if (!s || !spec || !d_maps || !d_hist_value || !d_hist_bits) FAIL("sgm_temporal_filter was given a NULL pointer");
+    if (!temporal_available()) FAIL("the temporal filter is not part of this build");
+    if (!temporal_spec_valid(spec, false, &c)) FAIL("the temporal spec is outside its ranges (include/sgm_mi355x.h, sgm_temporal_spec)");
+    if (!temporal_geometry_ok(streams, steps, pixels))
+        FAIL("sgm_temporal_filter: streams, steps and pixels must be at least 1 and their product at most 2^31");
+    if ((((uintptr_t)d_maps | (uintptr_t)d_hist_value | (uintptr_t)d_stats) & 3u) || ((uintptr_t)d_conf & 1u))
+        FAIL("the maps, history values and counters of sgm_temporal_filter must be 4-byte aligned, the confidence 2-byte aligned");
+    /* (growing the scratch drains the streams first: an earlier call may still be using it) */
+    if (d_stats && !reserve(s, &s->d_tp_scratch, sgmd_temporal_scratch_bytes(), 0)) FAIL("device allocation failed for the counters' scratch");
+    /* the maps may be the result of a match whose last stages run on a stream of their own (sgm_set_overlap_post / _stage_cus); the
+     * scratch is shared with the matches' filter, which a later match queues behind everything queued here */
+    if (wait_for_result(s, s->stream) != 0) return false;
+    if (sgmd_temporal(s->device, s->stream, &c, streams, steps, pixels, d_maps, d_conf, d_hist_value, d_hist_bits, d_stats,
+                      d_stats ? s->d_tp_scratch.p : NULL) != 0)
+        FAIL("a kernel launch failed");
+    return true;
+}
+
+bool sgm_temporal_clear(sgm_instance* s, size_t streams, size_t pixels, float* d_hist_value, uint8_t* d_hist_bits)
+{
+    if (!s || !d_hist_value || !d_hist_bits) FAIL("sgm_temporal_clear was given a NULL pointer");
+    if (!temporal_available()) FAIL("the temporal filter is not part of this build");
+    if (!temporal_geometry_ok(streams, 1, pixels)) FAIL("sgm_temporal_clear: streams and pixels must be at least 1 and their product at most 2^31");
+    if ((uintptr_t)d_hist_value & 3u) FAIL("the history values of sgm_temporal_clear must be 4-byte aligned");
+    if (sgmd_temporal_clear(s->device, s->stream, streams * pixels, d_hist_value, d_hist_bits) != 0) FAIL("a kernel launch failed");
+    return true;
+}
+
+int sgm_temporal_stats(sgm_instance* s, uint32_t* out, int capacity)
+{
+    if (!s || !out || s->tp_stat_maps < 1 || capacity < s->tp_stat_maps || !s->d_tp_stats.p) return 0;
+    const size_t bytes = (size_t)s->tp_stat_maps * 5 * sizeof(uint32_t);
+    if (!sgm_match_wait(s) || sync_streams(s) != 0) return 0;
+    if (sgmd_d2h_async(s->device, s->stream, out, s->d_tp_stats.p, bytes) != 0 || sync_streams(s) != 0) return 0;
+    return s->tp_stat_maps;
+}
+
 /* ------------------------------------------------------------------ hole filling of any map (extension) */
 
 bool sgm_fill_holes(sgm_instance* s, float* d_disp, const uint8_t* d_class)
@@ -2309,7 +2489,7 @@ static size_t compact_volume(const sgm_instance* s, const void* padded, size_t e
  * the half of a buffer of two batches it sits in, whether it is a padded volume ([H][W][Dp], compacted to D on the way out), and what
  * has to hold for it to exist now.  Two rows with one id: whichever holds.  The direction planes (10 .. 17) are not in here. */
 enum { HAS_KEPT = 1, HAS_FILL = 2, HAS_RECT = 4, HAS_BOTH = 8, HAS_BOTH_KEPT = 16, HAS_WIDE = 32, HAS_COST = 64, NOT_WIDE = 128, NOT_BOTH = 256,
-       HAS_PIX16 = 512, NOT_PIX16 = 1024 };
+       HAS_PIX16 = 512, NOT_PIX16 = 1024, HAS_TEMPORAL = 2048 };
 #define AT(member) offsetof(struct sgm_instance, member)
 static const struct { int id; size_t at; int elem, half; bool volume; int needs; } k_stages[] = {
     {0, AT(d_census64_l.p), 8, 0, false, HAS_WIDE},           {0, AT(d_census_l.p), 4, 0, false, NOT_WIDE},
@@ -2327,6 +2507,8 @@ static const struct { int id; size_t at; int elem, half; bool volume; int needs;
     /* sgm_match_both: the right view after the LR check, after speckle removal, and finished */
     {26, AT(d_both_snap.p), 4, 0, false, HAS_KEPT | HAS_BOTH_KEPT}, {27, AT(d_both_snap.p), 4, 1, false, HAS_KEPT | HAS_BOTH_KEPT},
     {28, AT(d_both_maps.p), 4, 1, false, HAS_BOTH},
+    /* the temporal filter: the maps as they entered it (the right view's after a sgm_match_both); 30 / 31 / 33 / 34 are not in here */
+    {29, AT(d_tp_pre.p), 4, 0, false, HAS_KEPT | HAS_TEMPORAL}, {32, AT(d_tp_pre.p), 4, 1, false, HAS_KEPT | HAS_TEMPORAL | HAS_BOTH},
 };
 
 size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacity)
@@ -2339,7 +2521,8 @@ size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacit
     int row_a = 0, row_b = s->g.H;                                /* rows the device holds of a volume stage */
     const int has = (s->keep_stages ? HAS_KEPT : 0) | (s->fill_on ? HAS_FILL : 0) | (s->rect_on ? HAS_RECT : 0) |
                     (s->last_both ? HAS_BOTH : NOT_BOTH) | (s->last_both_kept ? HAS_BOTH_KEPT : 0) |
-                    (volume_fed(s) ? HAS_WIDE : NOT_WIDE) | (s->d_cost.p ? HAS_COST : 0) | (wide_pixels(s) ? HAS_PIX16 : NOT_PIX16);
+                    (volume_fed(s) ? HAS_WIDE : NOT_WIDE) | (s->d_cost.p ? HAS_COST : 0) | (wide_pixels(s) ? HAS_PIX16 : NOT_PIX16) |
+                    (s->temporal_on && s->tp_sig[0] ? HAS_TEMPORAL : 0);
     if (which == 3 && (ensure_S(s) != 0 || materialize_S(s) != 0)) return 0;
     for (size_t i = 0; !src && i < sizeof k_stages / sizeof k_stages[0]; ++i) {
         const char* base = *(char* const*)((const char*)s + k_stages[i].at);
@@ -2353,6 +2536,14 @@ size_t sgm_read_stage(sgm_instance* s, int which, void* host_out, size_t capacit
         src = (const char*)s->d_planes + (f * 8 + (size_t)(which - 10)) * s->plane_bytes;
         elem = 1; volume = true;
         row_a = s->plane_row_lo; row_b = s->plane_row_lo + s->plane_rows;
+    }
+    if ((which == 30 || which == 31 || which == 33 || which == 34) && s->temporal_on && s->tp_sig[0] == s->g.W && s->tp_sig[1] == s->g.H &&
+        s->tp_sig[2] == s->g.B && s->d_tp_value.p && s->d_tp_bits.p && (which < 33 || s->tp_sig[4] == 2)) {
+        /* the history of the selected frame's stream (sequence: the one stream), the right view's behind the left view's */
+        const size_t streams = s->tp_sig[5] ? 1 : (size_t)s->g.B, at = ((which >= 33 ? streams : 0) + (s->tp_sig[5] ? 0 : f)) * px;
+        const bool bits = which == 31 || which == 34;
+        elem = bits ? 1 : 4;
+        src = (bits ? (const char*)s->d_tp_bits.p : (const char*)s->d_tp_value.p) + at * elem;
     }
     if (!src) return 0;
     const size_t need = volume ? px * s->g.D * elem : px * elem;
@@ -2436,6 +2627,20 @@ bool SGM_SetRefine(int enable, float lambda, float sigma, int iterations, int ke
     return true;
 }
 
+static struct { bool on; sgm_temporal_spec spec; } g_default_temporal;
+
+bool SGM_SetTemporal(const sgm_temporal_spec* spec)
+{
+    if (spec && !temporal_spec_ok(spec)) return false;
+    if (g_default && !sgm_set_temporal(g_default, spec)) return false;
+    g_default_temporal.on = spec != NULL;
+    if (spec) g_default_temporal.spec = *spec;
+    return true;
+}
+
+bool SGM_TemporalRestart(void) { return g_default ? sgm_temporal_restart(g_default) : false; }
+int SGM_TemporalStats(uint32_t* out, int capacity) { return g_default ? sgm_temporal_stats(g_default, out, capacity) : 0; }
+
 /* the default instance's maps, quantised: kept across SGM_Shutdown, each default instance gets a copy */
 static struct { int32_t* q; int w, h; } g_default_rect;
 
@@ -2510,6 +2715,7 @@ bool SGM_Initialize(uint16_t width, uint16_t height, const SGMOption* option)
         if (g_default_pixel_bits) sgm_set_pixel_bits(g_default, g_default_pixel_bits);
         if (g_default_fill) sgm_set_fill_holes(g_default, 1);
         if (g_default_rect.q && !default_rectify_install()) return false;
+        if (g_default_temporal.on) sgm_set_temporal(g_default, &g_default_temporal.spec);
         if (g_default_refine.enable)
             sgm_set_refine(g_default, 1, g_default_refine.lambda, g_default_refine.sigma, g_default_refine.iters,
                            g_default_refine.keep_invalid);

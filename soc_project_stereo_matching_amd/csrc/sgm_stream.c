@@ -5,6 +5,7 @@
  *
  *   sgm_stream [--width W] [--height H] [--disparities D] [--batch B] [--instances N] [--seconds S] [--frames F] [--seed X]
  *              [--pageable] [--blocking] [--numa-node K] [--both] [--census WxH] [--census-kind centre|symmetric]
+ *              [--temporal A,D,N,K]
  *
  *   default      N instances, one host thread each, batches of B frames through sgm_reset + sgm_match_async + sgm_match_wait on
  *                page-locked buffers (sgm_host_alloc) for S seconds: the pipelined throughput path (bench.py's headline, in C)
@@ -17,6 +18,11 @@
  *                symmetric without --census uses SGM_CENSUS_SYMMETRIC_DEFAULT_W x _H
  *   --rectify CALIB.txt   extension: the frames are raw camera images, rectified on the device ahead of every match (SGM_SetRectify)
  *                through the maps of the 64 numbers in CALIB.txt (sgm_calib.h)
+ *   --temporal A,D,N,K   extension: the temporal filter (sgm_set_temporal) with alpha A, gate D and hold K of N; every instance is ONE
+ *                stream whose consecutive frames are the frames of its batches (sequence = 1; not with --blocking).  After the
+ *                untimed warm-up batch the worker calls sgm_temporal_restart, and the line gains "hash_temporal": the hash of the
+ *                LAST frame of batch 0 the first time the timed loop computes it (with --instances 1: frame B - 1 filtered through
+ *                frames 0 .. B - 2); "hash_frame0" is then taken at that moment too (frame 0 meets an empty history)
  *   --numa-node K  run (and allocate) on the CPUs of NUMA node K -- the node the GPU hangs off (/sys/bus/pci/devices/<bdf>/numa_node):
  *                the host threads spin in stream synchronisation and feed 11 GB/s over PCIe; bench.py pins itself the same way
  *
@@ -73,6 +79,8 @@ static unsigned long long fnv1a(const void* p, size_t n)
 typedef struct {
     int k, n_inst, W, H, B, n_batches, pageable, both, census_kind, census_w, census_h;
     const SGMOption* opt;
+    const sgm_temporal_spec* temporal;   /* --temporal (NULL: none) */
+    unsigned long long hash_t;   /* --temporal: hash of the last frame of batch 0, the first time this instance computed it (0: never) */
     const float* maps;           /* --rectify: map_lx, map_ly, map_rx, map_ry of W * H floats each (NULL: none) */
     uint8_t **L, **R;            /* [n_batches] batches of B frames, shared, read-only */
     volatile double stop_at;     /* set by main right after the start barrier */
@@ -91,7 +99,7 @@ static void* worker_main(void* p)
     float *out = NULL, *out_r = NULL;
     w->failed = 1;
     if (s && sgm_set_batch(s, w->B) && sgm_set_overlap_post(s, 1) && sgm_set_census_kind(s, w->census_kind) &&
-        (!w->census_w || sgm_set_census_window(s, w->census_w, w->census_h)) &&
+        (!w->census_w || sgm_set_census_window(s, w->census_w, w->census_h)) && (!w->temporal || sgm_set_temporal(s, w->temporal)) &&
         (!w->maps || sgm_set_rectify(s, w->W, w->H, w->maps, w->maps + px, w->maps + 2 * px, w->maps + 3 * px)) && sgm_initialize(s, (uint16_t)w->W, (uint16_t)w->H, w->opt)) {
         out = w->pageable ? (float*)malloc(w->B * px * sizeof(float)) : (float*)sgm_host_alloc(s, w->B * px * sizeof(float));
         if (w->both) out_r = w->pageable ? (float*)malloc(w->B * px * sizeof(float)) : (float*)sgm_host_alloc(s, w->B * px * sizeof(float));
@@ -100,12 +108,22 @@ static void* worker_main(void* p)
     /* one untimed batch: first-use allocations */
 #define QUEUE(i) (w->both ? sgm_match_both_async(s, w->L[i], w->R[i], out, out_r) : sgm_match_async(s, w->L[i], w->R[i], out))
     if (!w->failed) w->failed = !(QUEUE(0) && sgm_match_wait(s));
+    if (!w->failed && w->temporal) w->failed = !sgm_temporal_restart(s);      /* the timed stream starts from an empty history */
     pthread_barrier_wait(w->start);
     for (long b = w->k; !w->failed && now_s() < w->stop_at; b += w->n_inst) {
         const int i = (int)(b % w->n_batches);
         if (!(sgm_reset(s, (uint16_t)w->W, (uint16_t)w->H, w->opt) && QUEUE(i) && sgm_match_wait(s))) {
             w->failed = 1;
             break;
+        }
+        if (w->temporal) {
+            /* the maps depend on what the instance saw before: the first pass over batch 0 is the one that is defined */
+            if (i == 0 && !w->hash_t) {
+                w->hash0 = fnv1a(out, px * sizeof(float));
+                w->hash_t = fnv1a(out + (size_t)(w->B - 1) * px, px * sizeof(float));
+            }
+            ++w->batches_done;
+            continue;
         }
         if (i == 0) w->hash0 = fnv1a(out, px * sizeof(float));
         if (i == 0 && w->both) w->hash0_r = fnv1a(out_r, px * sizeof(float));
@@ -128,6 +146,8 @@ int main(int argc, char** argv)
     double seconds = 2.0;
     unsigned seed = 0x5EED0002u;
     const char* calib_path = NULL;
+    sgm_temporal_spec temporal;
+    int use_temporal = 0;
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
         const char* v = i + 1 < argc ? argv[i + 1] : NULL;
@@ -144,6 +164,16 @@ int main(int argc, char** argv)
         else if (v && !strcmp(a, "--numa-node")) node = atoi(argv[++i]);
         else if (v && !strcmp(a, "--seed")) seed = (unsigned)strtoul(argv[++i], NULL, 0);
         else if (v && !strcmp(a, "--rectify")) calib_path = argv[++i];
+        else if (v && !strcmp(a, "--temporal")) {
+            memset(&temporal, 0, sizeof temporal);
+            if (sscanf(v, "%f,%f,%d,%d", &temporal.alpha, &temporal.delta, &temporal.hold_window, &temporal.hold_count) != 4) {
+                fprintf(stderr, "sgm_stream: --temporal wants ALPHA,DELTA,WINDOW,COUNT, e.g. 0.4,1.0,3,2\n");
+                return 2;
+            }
+            temporal.sequence = 1;
+            use_temporal = 1;
+            ++i;
+        }
         else if (v && !strcmp(a, "--census")) {
             if (sscanf(v, "%dx%d", &census_w, &census_h) != 2) { fprintf(stderr, "sgm_stream: --census wants WxH, e.g. 7x7\n"); return 2; }
             ++i;
@@ -155,7 +185,7 @@ int main(int argc, char** argv)
         }
         else { fprintf(stderr, "sgm_stream: unknown argument %s (see the header of sgm_stream.c)\n", a); return 2; }
     }
-    if (W < 1 || H < 1 || D < 1 || B < 1 || N < 1 || N > 16 || F < 1 || (both && blocking)) return 2;
+    if (W < 1 || H < 1 || D < 1 || B < 1 || N < 1 || N > 16 || F < 1 || (both && blocking) || (use_temporal && blocking)) return 2;
     if (census_kind == SGM_CENSUS_SYMMETRIC && !census_w) {
         census_w = SGM_CENSUS_SYMMETRIC_DEFAULT_W;
         census_h = SGM_CENSUS_SYMMETRIC_DEFAULT_H;
@@ -222,7 +252,8 @@ int main(int argc, char** argv)
     pthread_t th[16];
     memset(w, 0, sizeof w);
     for (int k = 0; k < N; ++k) {
-        w[k] = (worker){k, N, W, H, B, n_batches, pageable, both, census_kind, census_w, census_h, &opt, maps, L, R, 1e300, 0, 0, 0, 0, &start};
+        w[k] = (worker){k, N, W, H, B, n_batches, pageable, both, census_kind, census_w, census_h, &opt, use_temporal ? &temporal : NULL, 0,
+                        maps, L, R, 1e300, 0, 0, 0, 0, &start};
         if (pthread_create(&th[k], NULL, worker_main, &w[k]) != 0) return 1;
     }
     /* every worker is set up (its warm-up batch included) when the barrier opens */
@@ -231,11 +262,16 @@ int main(int argc, char** argv)
     for (int k = 0; k < N; ++k) w[k].stop_at = t1 + seconds;
     long batches = 0;
     int failed = 0;
-    unsigned long long hash0 = 0, hash0_r = 0;
+    unsigned long long hash0 = 0, hash0_r = 0, hash_t = 0;
     for (int k = 0; k < N; ++k) {
         pthread_join(th[k], NULL);
         batches += w[k].batches_done;
         failed |= w[k].failed;
+        if (use_temporal) {
+            /* every instance is a stream of its own with a history of its own: the one that ran batch 0 first speaks */
+            if (k == 0) { hash0 = w[k].hash0; hash_t = w[k].hash_t; }
+            continue;
+        }
         if (w[k].hash0) {
             if (hash0 && hash0 != w[k].hash0) failed = 1;      /* every instance must compute the same map for the same frame */
             hash0 = w[k].hash0;
@@ -253,8 +289,9 @@ int main(int argc, char** argv)
     sgm_destroy(owner);
     free(L); free(R); free(maps);
     const long frames = batches * B;
-    char right[64] = "";                                /* --both: the right view's hash beside the left one's */
+    char right[128] = "";                                /* --both: the right view's hash beside the left one's */
     if (both) snprintf(right, sizeof right, "\"hash_frame0_right\": \"%016llx\", ", hash0_r);
+    if (use_temporal) snprintf(right + strlen(right), sizeof right - strlen(right), "\"hash_temporal\": \"%016llx\", ", hash_t);
     printf("{\"mode\": \"%d instances x batches of %d, sgm_reset + %s + sgm_match_wait, %s buffers, one thread each\", "
            "\"width\": %d, \"height\": %d, \"disparity_range\": %d, \"frames\": %ld, \"seconds\": %.4f, \"fps\": %.2f, \"ms_per_frame\": %.4f, "
            "\"mdisp_per_s\": %.1f, \"hash_frame0\": \"%016llx\", %s\"failed\": %s}\n",

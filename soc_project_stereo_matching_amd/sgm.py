@@ -27,6 +27,12 @@ STAGE_RIGHT_AFTER_LR, STAGE_RIGHT_AFTER_SPECKLE, STAGE_RIGHT_FINAL = 26, 27, 28
 STAGE_RECT_LEFT, STAGE_RECT_RIGHT = 19, 20
 # the narrowed left / right image of a match on more than 8 bits per sample (u8; set_pixel_bits: read_stages() leaves them out)
 STAGE_NARROW_LEFT, STAGE_NARROW_RIGHT = 21, 22
+# the temporal filter (set_temporal): the map as it entered the filter (needs keep_stages), the history value hv (float32) and the
+# validity bits hb (uint8) of the selected frame's stream; the same three for the right view after a match_both
+STAGE_TEMPORAL_IN, STAGE_TEMPORAL_VALUE, STAGE_TEMPORAL_BITS = 29, 30, 31
+STAGE_RIGHT_TEMPORAL_IN, STAGE_RIGHT_TEMPORAL_VALUE, STAGE_RIGHT_TEMPORAL_BITS = 32, 33, 34
+# the decisions the temporal filter counts, in the order of its statistics
+TEMPORAL_CLASSES = ("first", "smoothed", "replaced", "held", "invalid")
 # the refinement's default parameters (SGM_REFINE_DEFAULT_* of include/sgm_mi355x.h)
 REFINE_LAMBDA, REFINE_SIGMA, REFINE_ITERS = 16.0, 1.5, 1
 # census kinds (SGM_CENSUS_* of include/sgm_mi355x.h) and the drivers' window for the symmetric kind
@@ -81,6 +87,20 @@ class SGMScaleSpec(C.Structure):
 
 
 SCALE_DEFAULT_RADIUS, SCALE_DEFAULT_PENALTY = 3, 1
+
+
+class SGMTemporalSpec(C.Structure):
+    """Field-for-field sgm_temporal_spec of include/sgm_mi355x.h: 28 bytes, every field 4 bytes."""
+    _fields_ = [
+        ("alpha", C.c_float), ("delta", C.c_float),
+        ("hold_window", C.c_int32), ("hold_count", C.c_int32), ("sequence", C.c_int32),
+        ("min_conf", C.c_uint32), ("stats", C.c_int32),
+    ]
+
+
+def temporal_spec(alpha=0.4, delta=1.0, hold_window=0, hold_count=1, sequence=False, min_conf=0, stats=False) -> SGMTemporalSpec:
+    """A sgm_temporal_spec; the defaults smooth within one disparity and never bridge a hole."""
+    return SGMTemporalSpec(alpha, delta, int(hold_window), int(hold_count), int(sequence), int(min_conf), int(stats))
 
 
 def scale_spec(width, height, factor, frames=1, bits=8, radius=SCALE_DEFAULT_RADIUS, penalty=SCALE_DEFAULT_PENALTY, d_lo=0,
@@ -243,6 +263,22 @@ def _load() -> C.CDLL:
         L.SGM_ReadCloud.restype = C.c_bool
         L.sgm_rectify_valid_mask.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sgm_rectify_valid_mask.restype = C.c_bool
+    if hasattr(L, "sgm_set_temporal"):        # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_temporal_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t] + [C.c_void_p] * 5
+        L.sgm_temporal_filter.restype = C.c_bool
+        L.sgm_temporal_clear.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.sgm_temporal_clear.restype = C.c_bool
+        L.sgm_set_temporal.argtypes = [C.c_void_p, C.c_void_p]
+        L.sgm_set_temporal.restype = C.c_bool
+        L.sgm_temporal_restart.argtypes = [C.c_void_p]
+        L.sgm_temporal_restart.restype = C.c_bool
+        L.sgm_temporal_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.sgm_temporal_stats.restype = C.c_int
+        L.SGM_SetTemporal.argtypes = [C.c_void_p]
+        L.SGM_SetTemporal.restype = C.c_bool
+        L.SGM_TemporalRestart.restype = C.c_bool
+        L.SGM_TemporalStats.argtypes = [C.c_void_p, C.c_int]
+        L.SGM_TemporalStats.restype = C.c_int
     if hasattr(L, "sgm_set_pixel_bits"):      # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_set_pixel_bits.argtypes = [C.c_void_p, C.c_int]
         L.sgm_set_pixel_bits.restype = C.c_bool
@@ -389,6 +425,13 @@ def _read_cloud(call, spec):
     return points, offsets
 
 
+def _temporal_stats(call, maps):
+    """uint32 [maps][5] through a sgm_temporal_stats-shaped call(out, capacity); None where it returns no entries"""
+    out = np.zeros((max(int(maps), 1), 5), np.uint32)
+    n = call(out.ctypes.data, out.shape[0])
+    return out[:n] if n > 0 else None
+
+
 def _rectify_args(maps):
     """(width, height, four pointers, the arrays kept alive) for sgm_set_rectify / SGM_SetRectify; None first = off"""
     if maps[0] is None:
@@ -453,8 +496,11 @@ class _StageReader:
             dt, shp = _pixel_dtype(self._bits), (h, w)
         elif idx in (STAGE_FILL_CLASS, STAGE_NARROW_LEFT, STAGE_NARROW_RIGHT):
             dt, shp = np.uint8, (h, w)
-        elif idx in (STAGE_RIGHT_AFTER_LR, STAGE_RIGHT_AFTER_SPECKLE, STAGE_RIGHT_FINAL):
+        elif idx in (STAGE_RIGHT_AFTER_LR, STAGE_RIGHT_AFTER_SPECKLE, STAGE_RIGHT_FINAL, STAGE_TEMPORAL_IN, STAGE_TEMPORAL_VALUE,
+                     STAGE_RIGHT_TEMPORAL_IN, STAGE_RIGHT_TEMPORAL_VALUE):
             dt, shp = np.float32, (h, w)
+        elif idx in (STAGE_TEMPORAL_BITS, STAGE_RIGHT_TEMPORAL_BITS):
+            dt, shp = np.uint8, (h, w)
         elif idx >= 10:
             dt, shp = np.uint8, (h, w, d)
         else:
@@ -480,6 +526,13 @@ class _StageReader:
         """Stages 21 and 22: the narrowed (left, right) images g8 = min(v >> (bits - 8), 255) of the last match (needs more than 8
         bits per sample in effect, set_pixel_bits)."""
         return self.read_stage(STAGE_NARROW_LEFT), self.read_stage(STAGE_NARROW_RIGHT)
+
+    def read_temporal(self, right=False):
+        """Stages 30 and 31 (33 and 34 with right, after a match_both): the temporal filter's history (hv float32, hb uint8) of the
+        selected frame's stream after the last match (needs set_temporal in effect)."""
+        if right:
+            return self.read_stage(STAGE_RIGHT_TEMPORAL_VALUE), self.read_stage(STAGE_RIGHT_TEMPORAL_BITS)
+        return self.read_stage(STAGE_TEMPORAL_VALUE), self.read_stage(STAGE_TEMPORAL_BITS)
 
     def read_fill_classes(self):
         """Stage 18: the hole-filling classes, 0 valid / 1 occluded / 2 mismatched (after any match with fill on)."""
@@ -539,6 +592,20 @@ class SGM(_StageReader):
         the left and the right camera (include/sgm_mi355x.h, SGM_SetRectify); None turns it off; next initialize/reset."""
         w, h, ptrs, _keep = _rectify_args((map_lx, map_ly, map_rx, map_ry))
         return bool(self.lib.SGM_SetRectify(w, h, *ptrs))
+
+    def set_temporal(self, spec) -> bool:
+        """Extension: the temporal filter of a stream of matches (include/sgm_mi355x.h, sgm_temporal_spec); None turns it off; next
+        initialize/reset.  The history survives the per-frame reset.  False for a spec out of range."""
+        return bool(self.lib.SGM_SetTemporal(C.byref(spec) if spec is not None else None))
+
+    def temporal_restart(self) -> bool:
+        """SGM_TemporalRestart: the next filtered match starts from an empty history (a scene cut)."""
+        return bool(self.lib.SGM_TemporalRestart())
+
+    def temporal_stats(self):
+        """SGM_TemporalStats: uint32 [1][5], the decisions of the last match per class (TEMPORAL_CLASSES), or None when the spec's
+        stats is off."""
+        return _temporal_stats(self.lib.SGM_TemporalStats, 1)
 
     def keep_stages(self, enable=True):
         self.lib.SGM_KeepStages(int(enable))
@@ -746,6 +813,33 @@ class SGMInstance(_StageReader):
         the left and the right camera (include/sgm_mi355x.h, SGM_SetRectify); None turns it off; next initialize/reset."""
         w, h, ptrs, _keep = _rectify_args((map_lx, map_ly, map_rx, map_ry))
         return bool(self.lib.sgm_set_rectify(self.handle, w, h, *ptrs))
+
+    def set_temporal(self, spec) -> bool:
+        """Extension: the temporal filter of a stream of matches (include/sgm_mi355x.h, sgm_temporal_spec); None turns it off; next
+        initialize/reset.  One instance is one stream per frame of its batch (spec.sequence = 0) or one stream whose consecutive
+        frames are the frames of a batch (1); the history survives the per-frame reset.  False for a spec out of range."""
+        return bool(self.lib.sgm_set_temporal(self.handle, C.byref(spec) if spec is not None else None))
+
+    def temporal_restart(self) -> bool:
+        """sgm_temporal_restart: the next filtered match starts from an empty history (a scene cut)."""
+        return bool(self.lib.sgm_temporal_restart(self.handle))
+
+    def temporal_stats(self):
+        """sgm_temporal_stats: uint32 [batch * views][5], the decisions of the last match per map and class (TEMPORAL_CLASSES);
+        None when the spec's stats is off or nothing was filtered.  Blocking."""
+        return _temporal_stats(lambda *a: self.lib.sgm_temporal_stats(self.handle, *a), 2 * self.batch)
+
+    def temporal_filter(self, spec, streams: int, steps: int, pixels: int, d_maps: int, d_conf, d_hist_value: int, d_hist_bits: int,
+                        d_stats=None) -> bool:
+        """sgm_temporal_filter: the filter on any device maps float32 [streams][steps][pixels], in place, with the caller's history
+        (float32 / uint8 [streams][pixels]); d_conf (uint16) / d_stats (uint32 [streams * steps][5]) None: none.  Device pointers;
+        asynchronous on `stream`."""
+        return bool(self.lib.sgm_temporal_filter(self.handle, C.byref(spec), streams, steps, pixels, d_maps, d_conf or None,
+                                                 d_hist_value, d_hist_bits, d_stats or None))
+
+    def temporal_clear(self, streams: int, pixels: int, d_hist_value: int, d_hist_bits: int) -> bool:
+        """sgm_temporal_clear: +INF / 0 into a history of streams x pixels entries; asynchronous on `stream`."""
+        return bool(self.lib.sgm_temporal_clear(self.handle, streams, pixels, d_hist_value, d_hist_bits))
 
     def rectify(self, d_left, d_right, d_out_left, d_out_right) -> bool:
         """sgm_rectify: the remap alone on device images of the instance's batch and shape (uint8, or uint16 with more than 8 bits
