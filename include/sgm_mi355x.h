@@ -720,6 +720,22 @@ int    sgm_last_timing(sgm_instance* s, const char** names, float* ms, int max_e
  * sgm_synchronize (up to 64 matches between two synchronizes are kept); *matches = how many. */
 int    sgm_mean_timing(sgm_instance* s, const char** names, float* mean_ms, float* min_ms, int max_entries, long* matches);
 
+/* ---- debugging: guard bands and poison around every device buffer of the library ----
+ * Off unless asked for through the environment, read at every allocation (buffers only grow, so that is off the hot path):
+ *   SGM_DEBUG_GUARD=<bytes>    every device buffer the library allocates from then on gets a band of that many bytes (rounded up
+ *                              to 4096) in front of it and one behind it, the second starting at the buffer's last byte + 1
+ *   SGM_DEBUG_POISON=<0..255>  the byte that fills the bands AND the buffer itself before anybody uses it (0xA5 unless given;
+ *                              given alone: poisoned buffers without bands)
+ * With neither set the library allocates exactly what it always did and keeps no record.
+ * sgm_debug_guard_check waits for the device, copies every live band back and compares it with the poison.  Returns the number of
+ * violated bands, those of buffers freed (or re-allocated larger) since the last call included -- these are reported once.
+ * Every violation is one line on stderr: the buffer's size, the band, the first and last byte that changed, as an offset from the
+ * buffer's start (front band: -1 is the byte just in front of it) or its end (back band: +0 is the first byte behind it).
+ * live_allocations / live_bytes (either may be NULL): how many buffers are under guard and the sum of their sizes; 0 with the
+ * mode off, and the return value is 0 then.  A write of the very poison byte cannot show: run under two different bytes.
+ * Caller-owned buffers are not covered.  Thread-safe. */
+int    sgm_debug_guard_check(int* live_allocations, size_t* live_bytes);
+
 /* Seeded synthetic stereo pair of SURVEY.md 8(d) (host buffers of width*height bytes each). */
 void   SGM_SynthPair(int width, int height, int disparity_range, uint32_t seed, uint8_t* left, uint8_t* right);
 

@@ -35,6 +35,10 @@ int   sgmd_set_device(int ordinal);                                  /* the call
 int   sgmd_mem_info(int ordinal, size_t* free_bytes, size_t* total_bytes);
 int   sgmd_alloc(int ordinal, void** dptr, size_t bytes);
 int   sgmd_free(int ordinal, void* dptr);
+/* the debug allocation mode of sgmd_alloc / sgmd_free (sgm_guard.h): the number of violated guard bands, those found at free time
+ * since the last call included; 0 with 0 live allocations while the mode is off.  Not an error code.  The C host does not call
+ * it (csrc/sgm_runtime.hip exports it as sgm_debug_guard_check itself), so a stand-in device layer need not have it. */
+int   sgmd_guard_check(int* live_allocations, size_t* live_bytes);
 int   sgmd_alloc_pinned(int ordinal, void** hptr, size_t bytes);
 int   sgmd_free_pinned(int ordinal, void* hptr);
 int   sgmd_host_is_pinned(int ordinal, const void* hptr, size_t bytes);   /* 1: [hptr, hptr+bytes) is page-locked HIP host memory, else 0 */

@@ -793,7 +793,7 @@ int sgmd_score(int ord, void* stream, const void* gt, const void* test, size_t n
     const size_t per_block = 256 * SCORE_PER_THREAD;
     const unsigned blocks = (unsigned)((n + per_block - 1) / per_block);
     ScorePartial* d_part = nullptr;
-    HIP_TRY(hipMalloc(&d_part, sizeof(ScorePartial) * blocks));
+    if (sgmd_alloc(ord, (void**)&d_part, sizeof(ScorePartial) * blocks) != 0) return -1;
     hipLaunchKernelGGL(sgm_score_k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)gt, (const float*)test, n,
                        abs_thresh, d_part);
     ScorePartial* h = new ScorePartial[blocks];
@@ -803,7 +803,7 @@ int sgmd_score(int ord, void* stream, const void* gt, const void* test, size_t n
     if (e == hipSuccess)
         for (unsigned b = 0; b < blocks; ++b) { *sumsq += h[b].sumsq; *n_valid += h[b].n; *n_bad += h[b].bad; }
     delete[] h;
-    (void)hipFree(d_part);
+    (void)sgmd_free(ord, d_part);
     HIP_TRY(e);
     return 0;
 }

@@ -341,6 +341,9 @@ def _load() -> C.CDLL:
     L.sgm_host_anomalous_line.argtypes = [C.c_int, C.c_int]
     L.sgm_host_anomalous_line.restype = C.c_int
     L.sgm_host_p2_table.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    if hasattr(L, "sgm_debug_guard_check"):   # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_debug_guard_check.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+        L.sgm_debug_guard_check.restype = C.c_int
     return L
 
 
@@ -367,6 +370,14 @@ def synth_pair(width, height, disparity_range, seed):
     right = np.empty((height, width), np.uint8)
     L.SGM_SynthPair(width, height, disparity_range, seed & 0xFFFFFFFF, left.ctypes.data, right.ctypes.data)
     return left, right
+
+
+def debug_guard_check():
+    """sgm_debug_guard_check: (violated bands, live allocations, live bytes) of the debug allocation mode (SGM_DEBUG_GUARD /
+    SGM_DEBUG_POISON in the environment when the buffers were allocated; include/sgm_mi355x.h).  (0, 0, 0) with the mode off."""
+    live, size = C.c_int(0), C.c_size_t(0)
+    bad = load_library().sgm_debug_guard_check(C.byref(live), C.byref(size))
+    return int(bad), int(live.value), int(size.value)
 
 
 def set_refine(enable=True, lam=REFINE_LAMBDA, sigma=REFINE_SIGMA, iterations=REFINE_ITERS, keep_invalid=False) -> bool:
