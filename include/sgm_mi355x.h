@@ -506,6 +506,69 @@ bool   SGM_ReadCloud(const sgm_cloud_spec* spec, sgm_point* points, size_t capac
  * a size < 1 or more than 2^31 - 1 pixels. */
 bool   sgm_rectify_valid_mask(int width, int height, const float* map_x, const float* map_y, uint8_t* mask);
 
+/* ---- depth registered to another camera: a z-buffered forward warp on the device ----
+ * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/register_ref.py.  Every
+ * result of a match lives in the rectified reference camera; a caller's pixels live in the raw image that was fed in
+ * (SGM_SetRectify) or in a colour camera beside the pair.  This is the "align / register depth to colour" step of a stereo SDK.
+ *
+ * Points.  The contributing pixels are exactly the KEPT pixels of the cloud contract above -- the same predicate over src, d_mask,
+ * d_conf, min_conf and the source's z_min / z_max -- and X, Y, Z are the float32 values sgm_cloud_organized writes for them.
+ * Projection.  float32, every operation rounded on its own (no contraction, correctly rounded divide, subnormals kept); the
+ * parentheses are the contract:
+ *   X' = ((R0*X + R1*Y) + R2*Z) + t0          (Y' with R3..5, t1;  Z' with R6..8, t2)
+ *   drop unless Z' is finite (by its bit pattern), Z' > 0, z_min <= Z' && Z' <= z_max
+ *   a = X'/Z', b = Y'/Z';  aa = a*a, bb = b*b, ab = a*b;  r2 = aa + bb
+ *   rad = ((k3*r2 + k2)*r2 + k1)*r2 + 1
+ *   xd  = (a*rad + (2*p1)*ab) + p2*(r2 + 2*aa)
+ *   yd  = (b*rad + p1*(r2 + 2*bb)) + (2*p2)*ab
+ *   u = fx*xd + cx,  v = fy*yd + cy;  drop unless both are finite
+ * Candidates.  splat == 1: the one target pixel (floorf(u + 0.5f), floorf(v + 0.5f)).  splat == 2: with u0 = floorf(u),
+ * v0 = floorf(v) the four (u0, v0), (u0 + 1, v0), (u0, v0 + 1), (u0 + 1, v0 + 1).  A candidate (uf, vf) is admitted iff
+ * 0 <= uf && uf < (float)width && 0 <= vf && vf < (float)height, tested in float before any conversion to int.
+ * Z-buffer.  Per target pixel the winner among all admitted candidates of its frame is the one with the smallest 64-bit key
+ * ((uint64)bits(Z') << 32) | pixel, pixel = (y << 16) | x of the source: Z' > 0 makes the bit pattern monotonic, so the nearest
+ * surface wins, equal Z' bits go to the smaller source pixel, and the result does not depend on the order of arrival: it is the
+ * same on every run.  Frame f of the source writes frame f of the target.
+ * Outputs.  d_depth f32 [frames][height][width]: Z' of the winner, the quiet NaN 0x7FC00000 where nothing landed.  d_source u32 of
+ * the same shape (may be NULL): the winner's pixel, 0xFFFFFFFF where nothing landed.  Nothing outside these arrays is written.
+ *
+ * sgm_register_gather: out[f][v][u] = source[f][v][u] == 0xFFFFFFFF ? *fill : map[f][y][x], for a map of 1-, 2- or 4-byte elements
+ * of the source's shape: how a confidence, the disparity itself, a grey or colour plane or a mask follows the depth into the
+ * target image.  fill is a HOST pointer to one element, read before the call returns; a source word that names no pixel of the
+ * source shape reads nothing and gives *fill as well.
+ * sgm_register_spec_raw (host only): the target "back into the raw camera that sgm_rectify_maps(K, dist, R, Knew, ..) rectified":
+ * pinhole and dist from K / dist, R the transpose of the rectifying rotation, t = 0, z_min = 0, z_max = +INFINITY, every value
+ * computed in double and rounded once to float32; the source pinhole a caller pairs with it is Knew's.  false for a NULL pointer,
+ * a size outside 1..65535, a splat other than 1 or 2, a non-finite input.
+ *
+ * All other pointers are device pointers on the instance's device and need no alignment beyond their element's (a map that cannot
+ * be read 16 bytes at a time takes the one-pixel-per-lane path with the same results).  Asynchronous on sgm_stream(s), behind the
+ * last match also with sgm_set_overlap_post, as for clouds.  d_disp == NULL: the instance's last final map, under the cloud entry
+ * points' rules.  false, nothing queued and a message on stderr: a NULL s, spec, d_depth (d_source, d_map, fill, d_out for the
+ * gather); an output that aliases d_disp (an input, for the gather) or the other output; a pointer not aligned to its element; a
+ * src outside the cloud spec's ranges; a dst with width or height outside 1..65535 or frames * width * height > 2^31; fx or fy
+ * not finite and > 0; a non-finite cx, cy, dist, R or t; z_min NaN or < 0; z_max NaN or not > z_min; a splat that is not 1 or 2;
+ * an elem_bytes other than 1, 2 or 4; a build without the kernels.  Three launches (clear, scatter, resolve) and 8 bytes of key
+ * scratch per target pixel, reserved at the first call: an instance that never calls these entry points allocates and launches
+ * exactly what it did before.  Not part of it: closing the holes of the registered map, fisheye or rational distortion models,
+ * per-frame extrinsics within a batch, row tiles, sgm_match_planes. */
+typedef struct {            /* 104 bytes, every field 4 bytes, no padding */
+    int32_t width, height;  /* target image, 1..65535 each; frames * width * height <= 2^31 */
+    float   fx, fy, cx, cy; /* target pinhole, pixels */
+    float   dist[5];        /* k1 k2 p1 p2 k3 of the target camera (all 0: none) */
+    float   R[9], t[3];     /* P' = R P + t: source (rectified reference camera) coordinates -> target camera coordinates; row-major; t in the units of baseline */
+    float   z_min, z_max;   /* keep z_min <= Z' <= z_max; 0 and +INFINITY keep every finite positive Z' */
+    int32_t splat;          /* 1: the nearest target pixel;  2: the four target pixels around the projection */
+} sgm_register_spec;
+bool   sgm_register_depth(sgm_instance* s, const sgm_cloud_spec* src, const sgm_register_spec* dst,
+                          const float* d_disp, const uint8_t* d_mask, const uint16_t* d_conf,
+                          float* d_depth, uint32_t* d_source /* may be NULL */);
+bool   sgm_register_gather(sgm_instance* s, const sgm_cloud_spec* src, const sgm_register_spec* dst,
+                           const uint32_t* d_source, int elem_bytes /* 1, 2, 4 */,
+                           const void* d_map, const void* fill, void* d_out);
+bool   sgm_register_spec_raw(const double K[9], const double dist[5], const double R[9],
+                             int width, int height, int splat, sgm_register_spec* out);   /* host only */
+
 /* ---- matching at half or quarter scale, re-search at full resolution ----
  * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/scaled_ref.py.  A match at
  * 1/f scale pays for f^3 fewer cells of W x H x D for the same metric range; the result is brought back to the full grid by a guided

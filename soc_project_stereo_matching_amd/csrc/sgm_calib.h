@@ -11,17 +11,24 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+/* the 64 numbers of CALIB.txt; 0 with the reason on stderr */
+static int sgm_calib_read(const char* path, double c[64])
+{
+    FILE* f = fopen(path, "r");
+    if (!f) { fprintf(stderr, "%s: cannot open\n", path); return 0; }
+    int n = 0;
+    while (n < 64 && fscanf(f, "%lf", &c[n]) == 1) ++n;
+    fclose(f);
+    if (n != 64) { fprintf(stderr, "%s: 64 numbers wanted (K dist R Knew of the left camera, then of the right one), %d found\n", path, n); return 0; }
+    return 1;
+}
+
 /* the four maps of a width x height frame as one malloc'ed block -- map_lx, map_ly, map_rx, map_ry, width * height floats each --
  * or NULL with the reason on stderr */
 static float* sgm_calib_maps(const char* path, int width, int height)
 {
     double c[64];
-    FILE* f = fopen(path, "r");
-    if (!f) { fprintf(stderr, "%s: cannot open\n", path); return NULL; }
-    int n = 0;
-    while (n < 64 && fscanf(f, "%lf", &c[n]) == 1) ++n;
-    fclose(f);
-    if (n != 64) { fprintf(stderr, "%s: 64 numbers wanted (K dist R Knew of the left camera, then of the right one), %d found\n", path, n); return NULL; }
+    if (!sgm_calib_read(path, c)) return NULL;
     const size_t px = (size_t)width * height;
     float* maps = (float*)malloc(4 * px * sizeof(float));
     if (!maps) return NULL;

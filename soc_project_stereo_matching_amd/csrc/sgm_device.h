@@ -281,6 +281,24 @@ int sgmd_cloud_organized(int ord, void* stream, const sgmd_cloud* c, const void*
 int sgmd_cloud_points(int ord, void* stream, const sgmd_cloud* c, const void* disp, const void* mask, const void* conf, void* scratch,
                       void* points, void* offsets);
 
+/* Extension (parity unpinned by the reference), depth registered to another camera (include/sgm_mi355x.h, sgm_register_spec);
+ * sgm_register.hip.  c: the source as the cloud entry points take it; r: the target as the host validated it.  disp, mask, conf:
+ * the source maps, [B][c->H][c->W].  sgmd_register_depth: depth f32 and source u32 (or NULL), [B][r->H][r->W]; three launches
+ * (clear, scatter, resolve) that use keys, sgmd_register_scratch_bytes(r->W, r->H, B) bytes (one 8-byte key per target pixel, an
+ * even number of them), 16-byte aligned, which must not be shared with a call still in flight.  sgmd_register_gather:
+ * out[f][v][u] = source[f][v][u] names a pixel (y, x) of the source ? map[f][y][x] : fill, elements of elem_bytes (1, 2, 4); fill:
+ * the element in the low bytes.  sgm_host.c references all three weakly (a host built without them answers false). */
+typedef struct {
+    int W, H;
+    float fx, fy, cx, cy, dist[5], R[9], t[3], z_min, z_max;
+    int splat;
+} sgmd_register;
+size_t sgmd_register_scratch_bytes(int W, int H, int B);
+int sgmd_register_depth(int ord, void* stream, const sgmd_cloud* c, const sgmd_register* r, const void* disp, const void* mask,
+                        const void* conf, void* keys, void* depth, void* source);
+int sgmd_register_gather(int ord, void* stream, const sgmd_cloud* c, const sgmd_register* r, const void* source, int elem_bytes,
+                         const void* map, unsigned fill, void* out);
+
 /* Extension (parity unpinned by the reference), matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); sgm_scale.hip.
  * c: the spec as the host validated it (W, H: FULL resolution; the low resolution is W / f x H / f).  sgmd_downscale: the f x f box
  * mean with rounding of one image stack, u8 (bits == 8) or u16 [B][H][W] -> [B][H / f][W / f]; trailing rows and columns are not

@@ -158,6 +158,8 @@ struct sgm_instance {
     /* point clouds (sgm_cloud_points / sgm_read_cloud; allocated at the first such call): the tile counts and bases of the point list's
      * three launches, and the list and offsets sgm_read_cloud makes on the device before it copies them */
     sgm_buf d_cloud_scratch, d_cloud_points, d_cloud_offsets;
+    /* registration (sgm_register_depth; allocated at the first such call): one 8-byte z-buffer key per target pixel */
+    sgm_buf d_register_keys;
     /* matching at 1/f scale (sgm_match_scaled; allocated at its first use): the downscaled views, the census planes of the
      * FULL-resolution views with the narrowed images sgmd_census16 writes beside them, and for the host-pointer form the full
      * images, the full map and their page-locked staging */
@@ -209,7 +211,7 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     DEVICE_BUF(d_sc_small_l), DEVICE_BUF(d_sc_small_r), DEVICE_BUF(d_sc_census_l), DEVICE_BUF(d_sc_census_r), DEVICE_BUF(d_sc_g8_l),
     DEVICE_BUF(d_sc_g8_r), DEVICE_BUF(d_sc_full_l), DEVICE_BUF(d_sc_full_r), DEVICE_BUF(d_sc_disp), PINNED_BUF(h_sc_l), PINNED_BUF(h_sc_r),
     PINNED_BUF(h_sc_disp), DEVICE_BUF(d_tp_value), DEVICE_BUF(d_tp_bits), DEVICE_BUF(d_tp_stats), DEVICE_BUF(d_tp_pre),
-    DEVICE_BUF(d_tp_scratch),
+    DEVICE_BUF(d_tp_scratch), DEVICE_BUF(d_register_keys),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -2178,6 +2180,116 @@ bool sgm_read_cloud(sgm_instance* s, const sgm_cloud_spec* spec, sgm_point* poin
     if (total > capacity) return false;                          /* the caller sizes a buffer from offsets[frames] and calls again */
     if (total == 0) return true;
     return sgmd_d2h_async(s->device, s->stream, points, s->d_cloud_points.p, total * sizeof(sgm_point)) == 0 && sync_streams(s) == 0;
+}
+
+/* ------------------------------------------------------------------ depth registered to another camera (extension) */
+
+/* The launchers of sgm_register.hip, weakly referenced like the extensions above: a host built without them has no registration */
+#pragma weak sgmd_register_scratch_bytes
+#pragma weak sgmd_register_depth
+#pragma weak sgmd_register_gather
+static bool register_available(void) { return sgmd_register_scratch_bytes != NULL && sgmd_register_depth != NULL && sgmd_register_gather != NULL; }
+
+/* the target as the kernels take it; false for anything outside the ranges of include/sgm_mi355x.h */
+static bool register_spec_valid(const sgm_register_spec* sp, int frames, sgmd_register* r)
+{
+    if (sp->width < 1 || sp->width > 65535 || sp->height < 1 || sp->height > 65535 ||
+        (long long)frames * sp->width * sp->height > (1LL << 31))
+        return false;
+    if (!finite_positive(sp->fx) || !finite_positive(sp->fy) || !isfinite(sp->cx) || !isfinite(sp->cy)) return false;
+    for (int i = 0; i < 5; ++i) if (!isfinite(sp->dist[i])) return false;
+    for (int i = 0; i < 9; ++i) if (!isfinite(sp->R[i])) return false;
+    for (int i = 0; i < 3; ++i) if (!isfinite(sp->t[i])) return false;
+    if (!(sp->z_min >= 0.0f) || !(sp->z_max > sp->z_min) || (sp->splat != 1 && sp->splat != 2)) return false;     /* !(..) also catches NaN */
+    r->W = sp->width; r->H = sp->height;
+    r->fx = sp->fx; r->fy = sp->fy; r->cx = sp->cx; r->cy = sp->cy;
+    memcpy(r->dist, sp->dist, sizeof r->dist);
+    memcpy(r->R, sp->R, sizeof r->R);
+    memcpy(r->t, sp->t, sizeof r->t);
+    r->z_min = sp->z_min; r->z_max = sp->z_max;
+    r->splat = sp->splat;
+    return true;
+}
+
+/* What both entry points check of their specs before they queue anything */
+static bool register_specs(sgm_instance* s, const sgm_cloud_spec* src, const sgm_register_spec* dst, sgmd_cloud* c, sgmd_register* r)
+{
+    if (!s || !src || !dst) FAIL("sgm_register: NULL instance or spec");
+    if (!register_available()) FAIL("the registration is not part of this build");
+    if (!cloud_spec_valid(src, c)) FAIL("sgm_register: the source spec is outside its ranges");
+    if (!register_spec_valid(dst, c->B, r)) FAIL("sgm_register: the target spec is outside its ranges");
+    return true;
+}
+
+static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    return a && b && (uintptr_t)a < (uintptr_t)b + b_bytes && (uintptr_t)b < (uintptr_t)a + a_bytes;
+}
+
+bool sgm_register_depth(sgm_instance* s, const sgm_cloud_spec* src, const sgm_register_spec* dst, const float* d_disp,
+                        const uint8_t* d_mask, const uint16_t* d_conf, float* d_depth, uint32_t* d_source)
+{
+    sgmd_cloud c;
+    sgmd_register r;
+    if (!register_specs(s, src, dst, &c, &r)) return false;
+    if (!d_depth) FAIL("sgm_register_depth: NULL output");
+    if ((uintptr_t)d_disp % sizeof(float) != 0 || (uintptr_t)d_conf % sizeof(uint16_t) != 0 || (uintptr_t)d_depth % sizeof(float) != 0 ||
+        (uintptr_t)d_source % sizeof(uint32_t) != 0)
+        FAIL("sgm_register_depth: a pointer is not aligned to its element");
+    if (!d_disp) {                                               /* the cloud entry points' rules */
+        if (!s->initialized) FAIL("sgm_register_depth: no map given and no match to take one from");
+        if (row_tiled(s)) FAIL("the map of a row tile is the caller's: pass it to sgm_register_depth explicitly");
+        if (c.W != s->g.W || c.H != s->g.H || c.B != s->g.B)
+            FAIL("the source spec is for %d frames of %dx%d, the instance's last match for %d of %dx%d", c.B, c.W, c.H, s->g.B, s->g.W, s->g.H);
+        d_disp = (const float*)(s->last_both ? s->d_both_maps.p : s->d_disp.p);
+        if (!d_disp) FAIL("sgm_register_depth: no map given and no match to take one from");
+    }
+    const size_t in_bytes = (size_t)c.B * c.W * c.H * sizeof(float), out_bytes = (size_t)c.B * r.W * r.H * sizeof(float);
+    if (ranges_overlap(d_depth, out_bytes, d_disp, in_bytes) || ranges_overlap(d_source, out_bytes, d_disp, in_bytes) ||
+        ranges_overlap(d_depth, out_bytes, d_source, out_bytes))
+        FAIL("sgm_register_depth: an output aliases the map or the other output");
+    /* (growing the scratch drains the streams first: an earlier registration may still be using it) */
+    if (!reserve(s, &s->d_register_keys, sgmd_register_scratch_bytes(r.W, r.H, c.B), 0))
+        FAIL("device allocation failed for the z-buffer of %d frames of %dx%d", c.B, r.W, r.H);
+    /* the map may be the result of a match whose last stages run on a stream of their own (sgm_set_overlap_post / _stage_cus) */
+    if (wait_for_result(s, s->stream) != 0) return false;
+    return sgmd_register_depth(s->device, s->stream, &c, &r, d_disp, d_mask, d_conf, s->d_register_keys.p, d_depth, d_source) == 0;
+}
+
+bool sgm_register_gather(sgm_instance* s, const sgm_cloud_spec* src, const sgm_register_spec* dst, const uint32_t* d_source,
+                         int elem_bytes, const void* d_map, const void* fill, void* d_out)
+{
+    sgmd_cloud c;
+    sgmd_register r;
+    if (!register_specs(s, src, dst, &c, &r)) return false;
+    if (!d_source || !d_map || !fill || !d_out) FAIL("sgm_register_gather: NULL argument");
+    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4) FAIL("sgm_register_gather: elements of %d bytes (1, 2 or 4)", elem_bytes);
+    if ((uintptr_t)d_source % sizeof(uint32_t) != 0 || (uintptr_t)d_map % (size_t)elem_bytes != 0 || (uintptr_t)d_out % (size_t)elem_bytes != 0)
+        FAIL("sgm_register_gather: a pointer is not aligned to its element");
+    const size_t in_bytes = (size_t)c.B * c.W * c.H * (size_t)elem_bytes, px = (size_t)c.B * r.W * r.H;
+    if (ranges_overlap(d_out, px * (size_t)elem_bytes, d_map, in_bytes) || ranges_overlap(d_out, px * (size_t)elem_bytes, d_source, px * 4))
+        FAIL("sgm_register_gather: the output aliases an input");
+    uint32_t fill_word = 0;
+    memcpy(&fill_word, fill, (size_t)elem_bytes);                /* (little endian: the element in the low bytes) */
+    if (wait_for_result(s, s->stream) != 0) return false;
+    return sgmd_register_gather(s->device, s->stream, &c, &r, d_source, elem_bytes, d_map, fill_word, d_out) == 0;
+}
+
+bool sgm_register_spec_raw(const double K[9], const double dist[5], const double R[9], int width, int height, int splat,
+                           sgm_register_spec* out)
+{
+    if (!K || !dist || !R || !out || width < 1 || width > 65535 || height < 1 || height > 65535 || (splat != 1 && splat != 2)) return false;
+    for (int i = 0; i < 9; ++i) if (!isfinite(K[i]) || !isfinite(R[i])) return false;
+    for (int i = 0; i < 5; ++i) if (!isfinite(dist[i])) return false;
+    memset(out, 0, sizeof *out);
+    out->width = width; out->height = height;
+    out->fx = (float)K[0]; out->fy = (float)K[4]; out->cx = (float)K[2]; out->cy = (float)K[5];
+    for (int i = 0; i < 5; ++i) out->dist[i] = (float)dist[i];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) out->R[3 * i + j] = (float)R[3 * j + i];      /* back out of the rectified camera: the transpose */
+    out->z_min = 0.0f; out->z_max = INFINITY;
+    out->splat = splat;
+    return true;
 }
 
 /* ------------------------------------------------------------------ matching at 1/f scale (extension) */

@@ -26,6 +26,11 @@
  *                             3-D points (SGM_ReadCloud), a binary little-endian PLY with x y z float and red green blue uchar,
  *                             the colour being the grey at the point's pixel of the image the map belongs to: LEFT (RIGHT with
  *                             --right-reference), the rectified one with --rectify
+ *            [--register-raw OUT.f32 [--register-splat 1|2]]   extension: with --rectify and --pinhole (the rectified camera's:
+ *                             Knew's focal lengths and principal point), the depth of OUT's map registered back into the raw
+ *                             camera LEFT came from (RIGHT with --right-reference) -- sgm_register_depth into the target of
+ *                             sgm_register_spec_raw -- as raw float32 [H][W] like --raw, NaN where nothing landed; splat 2 (default)
+ *                             votes for the four raw pixels around a projection, 1 for the nearest.  --cloud-z-max cuts it too
  *            [--bits N]       extension: images of N = 9..16 bits per sample (SGM_SetPixelBits): LEFT and RIGHT are loaded with
  *                             sgm_load_gray16 (binary PGM with maxval up to 65535, PNG grey of depth 16; 8-bit files are widened
  *                             unshifted) and matched on all their bits.  --bits 0: the smallest N >= 8 that holds the files' maxval.
@@ -118,6 +123,45 @@ static int write_ply(const char* path, const sgm_point* pts, size_t n, const uin
     return rc;
 }
 
+/* --register-raw: the depth of the map registered into the raw camera of the reference view, as raw float32.  The entry points
+ * take device pointers on an explicit instance: the map and the result go through page-locked buffers of an instance of their own,
+ * which the device reads and writes in place. */
+static int register_raw(const char* path, const char* calib_path, int right_ref, int device, int w, int h, const float* pinhole,
+                        float z_max, int splat, const float* disp)
+{
+    double c[64];
+    if (!sgm_calib_read(calib_path, c)) return -1;
+    const double* cam = c + (right_ref ? 32 : 0);                 /* K (9), dist (5), R (9), Knew (9) */
+    sgm_register_spec dst;
+    if (!sgm_register_spec_raw(cam, cam + 9, cam + 14, w, h, splat, &dst)) return -1;
+    const sgm_cloud_spec src = {w, h, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], pinhole[4], pinhole[5], 0.0f, z_max, 0};
+    if (device < 0) {
+        const char* e = getenv("SGM_DEVICE");
+        device = (e && *e) ? atoi(e) : 0;
+    }
+    sgm_instance* s = sgm_create(device);
+    if (!s) return -1;
+    const size_t px = (size_t)w * h;
+    float* d_disp = (float*)sgm_host_alloc(s, px * sizeof(float));
+    float* d_depth = (float*)sgm_host_alloc(s, px * sizeof(float));
+    int rc = -1;
+    if (d_disp && d_depth) {
+        memcpy(d_disp, disp, px * sizeof(float));
+        if (sgm_register_depth(s, &src, &dst, d_disp, NULL, NULL, d_depth, NULL) && sgm_synchronize(s)) {
+            size_t landed = 0;
+            for (size_t i = 0; i < px; ++i) landed += d_depth[i] == d_depth[i];
+            printf("registered: %zu of %zu raw pixels, splat %d\n", landed, px, splat);
+            FILE* f = fopen(path, "wb");
+            rc = (f && fwrite(d_depth, sizeof(float), px, f) == px) ? 0 : -1;
+            if (f && fclose(f) != 0) rc = -1;
+        }
+    }
+    sgm_host_free(s, d_disp);
+    sgm_host_free(s, d_depth);
+    sgm_destroy(s);
+    return rc;
+}
+
 int main(int argc, char** argv)
 {
     if (argc == 4 && !strcmp(argv[1], "--convert")) {
@@ -163,6 +207,8 @@ int main(int argc, char** argv)
     const char* cloud_path = NULL;
     float pinhole[6], cloud_z_max = INFINITY;
     int have_pinhole = 0;
+    const char* register_path = NULL;
+    int register_splat = 2, register_splat_set = 0;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
     int census_kind = SGM_CENSUS_CENTRE, bits = 8;
     int scale = 0, scale_radius = SGM_SCALE_DEFAULT_RADIUS, scale_penalty = SGM_SCALE_DEFAULT_PENALTY, scale_tuned = 0;
@@ -197,6 +243,13 @@ int main(int argc, char** argv)
             ++i;
         }
         else if (v && !strcmp(a, "--cloud-z-max")) { cloud_z_max = (float)atof(v); ++i; }
+        else if (v && !strcmp(a, "--register-raw")) { register_path = v; ++i; }
+        else if (v && !strcmp(a, "--register-splat")) {
+            if (strcmp(v, "1") && strcmp(v, "2")) { fprintf(stderr, "--register-splat wants 1 or 2\n"); return 2; }
+            register_splat = atoi(v);
+            register_splat_set = 1;
+            ++i;
+        }
         else if (v && !strcmp(a, "--repeat")) { repeat = atoi(v); ++i; }
         else if (v && !strcmp(a, "--device")) { device = atoi(v); ++i; }
         else if (v && !strcmp(a, "--bits")) {
@@ -239,6 +292,7 @@ int main(int argc, char** argv)
                         "(OUT would silently be the left map)\n");
         return 2;
     }
+    if (scale && register_path) { fprintf(stderr, "--scale does not combine with --register-raw (it needs --rectify)\n"); return 2; }
     if (scale && (cloud_path || conf_path || right_out || right_raw || calib_path)) {
         fprintf(stderr, "--scale does not combine with --cloud, --confidence, --right-out / --right-raw or --rectify "
                         "(they work on the low-resolution match)\n");
@@ -251,6 +305,9 @@ int main(int argc, char** argv)
     }
     if (rect_out[0] && !calib_path) { fprintf(stderr, "--rectified-out needs --rectify\n"); return 2; }
     if (cloud_path && !have_pinhole) { fprintf(stderr, "--cloud needs --pinhole FX,FY,CX,CY,BASELINE,DOFFS\n"); return 2; }
+    if (register_path && !have_pinhole) { fprintf(stderr, "--register-raw needs --pinhole FX,FY,CX,CY,BASELINE,DOFFS\n"); return 2; }
+    if (register_path && !calib_path) { fprintf(stderr, "--register-raw needs --rectify CALIB.txt\n"); return 2; }
+    if (register_splat_set && !register_path) { fprintf(stderr, "--register-splat needs --register-raw\n"); return 2; }
 
     int w1, h1, w2, h2;
     uint8_t *left = NULL, *right = NULL;                          /* the images as the library takes them: bytes, or uint16_t samples */
@@ -362,6 +419,10 @@ int main(int argc, char** argv)
             free(rect);
         }
         free(pts);
+    }
+    if (register_path && register_raw(register_path, calib_path, right_ref, device, w1, h1, pinhole, cloud_z_max, register_splat, disp) != 0) {
+        printf("registration unavailable, a bad calibration file or --pinhole / --cloud-z-max out of range\n");
+        rc = -1;
     }
     SGM_Shutdown();
     free(disp); free(disp_r); free(conf); free(left); free(right);

@@ -77,6 +77,43 @@ def cloud_spec(width, height, fx, fy, cx, cy, baseline, doffs=0.0, frames=1, z_m
     return SGMCloudSpec(int(width), int(height), int(frames), fx, fy, cx, cy, baseline, doffs, z_min, z_max, int(min_conf))
 
 
+class SGMRegisterSpec(C.Structure):
+    """Field-for-field sgm_register_spec of include/sgm_mi355x.h: 104 bytes, every field 4 bytes."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("dist", C.c_float * 5), ("R", C.c_float * 9), ("t", C.c_float * 3),
+        ("z_min", C.c_float), ("z_max", C.c_float),
+        ("splat", C.c_int32),
+    ]
+
+
+REGISTER_NONE = 0xFFFFFFFF                      # what sgm_register_depth's source holds where nothing landed
+
+
+def register_spec(width, height, fx, fy, cx, cy, dist=(0.0,) * 5, R=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), t=(0.0,) * 3,
+                  z_min=0.0, z_max=float("inf"), splat=2) -> SGMRegisterSpec:
+    """A sgm_register_spec: the target camera of sgm_register_depth.  R (3x3, row-major) and t take a point of the rectified
+    reference camera into the target camera; the defaults are the same place and every finite positive depth."""
+    dist, R, t = (np.asarray(v, np.float64).reshape(-1) for v in (dist, R, t))
+    if (dist.size, R.size, t.size) != (5, 9, 3):
+        raise ValueError("register_spec: dist has 5 coefficients, R is 3x3, t has 3 entries")
+    return SGMRegisterSpec(int(width), int(height), fx, fy, cx, cy, (C.c_float * 5)(*dist), (C.c_float * 9)(*R), (C.c_float * 3)(*t),
+                           z_min, z_max, int(splat))
+
+
+def register_spec_raw(K, dist, R, width, height, splat=2) -> SGMRegisterSpec:
+    """sgm_register_spec_raw: the target "back into the raw camera that rectify_maps(K, dist, R, Knew, ..) rectified" (host only);
+    the source pinhole to pair with it is Knew's."""
+    mats = [np.ascontiguousarray(m, np.float64).reshape(-1) for m in (K, dist, R)]
+    if [m.size for m in mats] != [9, 5, 9]:
+        raise ValueError("register_spec_raw: K and R are 3x3, dist has 5 coefficients")
+    out = SGMRegisterSpec()
+    if not load_library().sgm_register_spec_raw(*(m.ctypes.data for m in mats), int(width), int(height), int(splat), C.byref(out)):
+        raise ValueError("sgm_register_spec_raw: a size outside 1..65535, a splat other than 1 or 2 or a non-finite input")
+    return out
+
+
 class SGMScaleSpec(C.Structure):
     """Field-for-field sgm_scale_spec of include/sgm_mi355x.h: 36 bytes, every field 4 bytes."""
     _fields_ = [
@@ -263,6 +300,13 @@ def _load() -> C.CDLL:
         L.SGM_ReadCloud.restype = C.c_bool
         L.sgm_rectify_valid_mask.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sgm_rectify_valid_mask.restype = C.c_bool
+    if hasattr(L, "sgm_register_depth"):      # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_register_depth.argtypes = [C.c_void_p] * 8
+        L.sgm_register_depth.restype = C.c_bool
+        L.sgm_register_gather.argtypes = [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3
+        L.sgm_register_gather.restype = C.c_bool
+        L.sgm_register_spec_raw.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]
+        L.sgm_register_spec_raw.restype = C.c_bool
     if hasattr(L, "sgm_set_temporal"):        # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_temporal_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t] + [C.c_void_p] * 5
         L.sgm_temporal_filter.restype = C.c_bool
@@ -1085,6 +1129,21 @@ class SGMInstance(_StageReader):
         """sgm_read_cloud: (points as POINT_DTYPE records, offsets uint32 [frames + 1]) of the last match's final map, no mask,
         no confidence; blocking.  None where the C call returns false."""
         return _read_cloud(lambda *a: self.lib.sgm_read_cloud(self.handle, *a), spec)
+
+    # ---- depth registered to another camera (include/sgm_mi355x.h, sgm_register_spec); device pointers as ints, None = NULL ----
+    def register_depth(self, src: SGMCloudSpec, dst: SGMRegisterSpec, d_disp, d_mask, d_conf, d_depth: int, d_source=None) -> bool:
+        """sgm_register_depth: the kept pixels of the source map, z-buffered into the target camera: float32 depth
+        [frames][dst.height][dst.width] (NaN where nothing landed) and, when asked, the uint32 source pixel (y << 16) | x of every
+        winner (REGISTER_NONE elsewhere).  d_disp None: the final map of the last match.  Asynchronous on `stream`."""
+        return bool(self.lib.sgm_register_depth(self.handle, C.byref(src), C.byref(dst), d_disp or None, d_mask or None, d_conf or None,
+                                                d_depth, d_source or None))
+
+    def register_gather(self, src: SGMCloudSpec, dst: SGMRegisterSpec, d_source: int, d_map: int, d_out: int, dtype, fill=0) -> bool:
+        """sgm_register_gather: a map of the source's shape (elements of dtype: 1, 2 or 4 bytes) carried into the target image through
+        register_depth's source; `fill` where nothing landed.  Asynchronous on `stream`."""
+        value = np.array([fill]).astype(np.dtype(dtype))
+        return bool(self.lib.sgm_register_gather(self.handle, C.byref(src), C.byref(dst), d_source, value.itemsize, d_map,
+                                                 value.ctypes.data, d_out))
 
     # ---- matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); device pointers as ints, None = NULL ----
     def downscale(self, spec: SGMScaleSpec, d_in: int, d_out: int) -> bool:
