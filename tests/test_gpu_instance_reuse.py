@@ -6,23 +6,17 @@ when they are allocated (d_S, the median scratch, the scratch of the fused last 
 are cached under a key, S is cleared lazily.  Every one of these outlives a shape.  Here one instance is driven through a list of
 steps and, after EVERY step, compared with what a fresh computation of that step alone gives: the CPU oracle (explicit instances
 have no census history, tests/test_census_history.py), and for what the reference does not have the checkers the feature's own
-GPU test uses (census_sym_ref, fill_holes_ref, refine_ref on confidence_ref, rectify_ref).  Compared: the final map (both maps of
+GPU test uses (census_sym_ref, fill_holes_ref, refine_ref on confidence_ref, rectify_ref; composed in tests/instance_steps.py).  Compared: the final map (both maps of
 sgm_match_both, the confidence of sgm_match_confidence), the raw right-view map and the aggregated costs read back (re-created
 where the fused kernels never stored them).  Tolerance 0, bit patterns.  tests/test_instance_reuse_cpu.py checks on the stand-in
 device what re-initialises each piece of retained state; NOTES.md section 20 has the table."""
 import numpy as np
 import pytest
 
-import census_sym_ref as CS
-import confidence_ref as CR
-import fill_holes_ref as FH
-import rectify_ref as RR
-import refine_ref as RF
-from oracle.pyoracle import Oracle, default_option
+from instance_steps import CENTRE, SYMMETRIC, apply, expected, option_of, step   # (tests/instance_steps.py; importers take them from here too)
+from oracle.pyoracle import default_option
 
 pytestmark = pytest.mark.gpu
-
-CENTRE, SYMMETRIC = 0, 1
 
 
 def assert_same(got, want, what):
@@ -34,83 +28,6 @@ def assert_same(got, want, what):
         bad = np.argwhere(g != w)
         first = tuple(bad[0])
         raise AssertionError(f"{what}: {len(bad)} of {g.size} elements differ; first at {first}: gpu={got[first]} want={want[first]}")
-
-
-# ---- a step: the shape and range, and everything that can be switched on a live instance ----------------------------------
-
-DEFAULTS = dict(dmin=0, batch=1, paths4=False, kind=CENTRE, window=(5, 5), view=False, fill=False, refine=False, rect=None,
-                keep=False, pen=None, entry="match", q14=False)
-
-
-def step(w, h, d, **kw):
-    assert set(kw) <= set(DEFAULTS), kw
-    return dict(DEFAULTS, w=w, h=h, d=d, **kw)
-
-
-def option_of(st):
-    kw = {"min_speckle_area": 10}
-    if st["paths4"]:
-        kw["num_paths"] = 4
-    if st["pen"]:
-        kw["p1"], kw["p2_init"] = st["pen"]
-    return default_option(st["d"] + st["dmin"], st["dmin"], **kw)
-
-
-def apply(inst, st):
-    """every switch of the step on the instance (all of them take effect at the next reset)"""
-    assert inst.set_batch(st["batch"])
-    inst.set_honor_num_paths(st["paths4"])
-    assert inst.set_census_kind(st["kind"]) and inst.set_census_window(*st["window"])
-    inst.set_reference_view(st["view"])
-    assert inst.set_fill_holes(st["fill"])
-    assert inst.set_refine(st["refine"])
-    assert inst.set_rectify(*st["rect"]) if st["rect"] else inst.set_rectify(None)
-    inst.keep_stages(st["keep"])
-
-
-def stages_of(oracle, st, opt, left, right, view, prev=None):
-    """the nine stages of one frame of the step, computed from nothing; prev: the frame matched before it without a Reset (Q14)"""
-    if st["kind"] == SYMMETRIC:
-        S_prev = None if prev is None else CS.pipeline(oracle, prev[0], prev[1], opt, *st["window"], right_view=view,
-                                                       honor_num_paths=st["paths4"])["aggr"]
-        return CS.pipeline(oracle, left, right, opt, *st["window"], right_view=view, honor_num_paths=st["paths4"], S_prev=S_prev)
-    orc = Oracle()                                            # a context of its own: zeroed census words, its own S
-    orc.set_honor_num_paths(st["paths4"])
-    assert orc.set_census_window(*st["window"])
-    orc.set_reference_view(view)
-    assert orc.reset(st["w"], st["h"], opt)
-    if prev is not None:
-        assert orc.match(np.ascontiguousarray(prev[0]), np.ascontiguousarray(prev[1])) is not None
-    assert orc.match(np.ascontiguousarray(left), np.ascontiguousarray(right)) is not None
-    return orc.stages()
-
-
-def expected(oracle, st, opt, left, right, prev=None):
-    """what one frame of the step has to give: dict of final / disp_r / aggr (+ final_r, conf, and the kept stages)"""
-    if st["rect"]:
-        lx, ly, rx, ry = st["rect"]
-        left, right = RR.remap(left, lx, ly), RR.remap(right, rx, ry)
-        if prev is not None:
-            prev = (RR.remap(prev[0], lx, ly), RR.remap(prev[1], rx, ry))
-    view = st["view"]
-    s = stages_of(oracle, st, opt, left, right, view, prev)
-    want = {"final": s["final"], "disp_r": s["disp_r"], "aggr": s["aggr"]}
-    if st["keep"]:
-        want.update({k: s[k] for k in ("disp_l", "after_lr", "after_speckle")})
-    if st["fill"]:
-        want["final"] = FH.expected(s, opt, oracle, right=view)[2]
-    if st["refine"] or st["entry"] == "confidence":
-        conf = CR.confidence(s["aggr"], opt.min_disparity, view)[3]
-        if st["entry"] == "confidence":
-            want["conf"] = conf
-        if st["refine"]:
-            import soc_project_stereo_matching_amd as S
-            tabs = RF.tables(S.REFINE_LAMBDA, S.REFINE_SIGMA, S.REFINE_ITERS, S.load_library())
-            want["final"] = RF.refine(s["final"], conf, right if view else left, tabs, False)
-    if st["entry"] == "both":
-        want["final"] = s["final"] if not view else stages_of(oracle, st, opt, left, right, False, prev)["final"]
-        want["final_r"] = s["final"] if view else stages_of(oracle, st, opt, left, right, True, prev)["final"]
-    return want
 
 
 def frames_of(oracle, st, seed):
