@@ -569,6 +569,64 @@ bool   sgm_register_gather(sgm_instance* s, const sgm_cloud_spec* src, const sgm
 bool   sgm_register_spec_raw(const double K[9], const double dist[5], const double R[9],
                              int width, int height, int splat, sgm_register_spec* out);   /* host only */
 
+/* ---- depth from a moving rig fused into a TSDF volume on the device ----
+ * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/volume_ref.py.  Clouds,
+ * registration and the temporal filter stop at one camera position; depth maps with known poses are integrated into a truncated
+ * signed distance volume and the surface is read back out: the "spatial mapping" of a stereo SDK.
+ *
+ * The volume.  A caller-owned device array of nx * ny * nz uint32 words, voxel n = (k*ny + j)*nx + i (x fastest), each
+ * (w << 16) | (uint16_t)tq: tq an int16, 32767 meaning +trunc, and w the weight.  All-zero bytes are the empty volume (there is no
+ * clear entry point: hipMemset it).  sgm_volume_bytes: its size, host only, 0 for a refused spec.
+ * Integration.  The contributing pixels are the KEPT pixels of the cloud contract above (src, d_mask, d_conf) and Z is their cloud
+ * Z.  For voxel (i, j, k) and frame f, in float32, every operation rounded on its own (no contraction, correctly rounded divide);
+ * the parentheses are the contract:
+ *   px = ox + ((float)i + 0.5f) * voxel          (py, pz alike)
+ *   X' = ((R0*px + R1*py) + R2*pz) + t0          (Y' with R3..5, t1;  Z' with R6..8, t2;  R, t of frame f: world -> camera f)
+ *   skip unless Z' is finite (by its bits) and Z' > 0
+ *   u = fx*(X'/Z') + cx,  v = fy*(Y'/Z') + cy;   skip unless both finite
+ *   uf = floorf(u + 0.5f), vf = floorf(v + 0.5f); skip unless 0 <= uf < (float)width && 0 <= vf < (float)height, tested in float
+ *   skip unless source pixel (f, vf, uf) is KEPT;  Z = its cloud Z
+ *   sdf = Z - Z';  skip if sdf < -trunc
+ *   q   = (int)rintf((fminf(sdf, trunc) / trunc) * 32767.0f)                    (round half to even)
+ *   num = tq*w + q;  den = w + 1;  tq = floor_div(2*num + den, 2*den)            (signed, floor: num / den rounded, halves up)
+ *   w   = min(w + 1, max_weight)
+ * (2*num + den is meant exactly: past w = 32767 it leaves int32, so the kernel takes the floor quotient and remainder of num / den
+ * and adds 1 when twice the remainder reaches den, which is the same number.)  Frames take effect in order f = 0 .. frames-1; one
+ * call over B frames equals B calls of one frame each, bit for bit; a launch reads and writes each voxel word at most once,
+ * whatever B is (a lane owns its voxels and loops over the frames: no atomics, no order between workgroups).
+ * Surface points.  For voxel n and axis a = 0, 1, 2 with the neighbour m one step up in x, y or z and inside the grid, a crossing
+ * exists iff w[n] >= min_weight && w[m] >= min_weight && (tq[n] < 0) != (tq[m] < 0).  Its point is the centre of voxel n (px, py,
+ * pz above) with s * voxel added along the axis, s = (float)tq[n] / ((float)tq[n] - (float)tq[m]), and id = n*4 + a.  The list is
+ * sorted by id and the same on every run (count per tile, one scan, emit: no atomics).  d_count[0] always receives the full number
+ * of crossings; records with index >= capacity are not written; nothing else is written.
+ *
+ * poses is a HOST pointer, [src->frames][12]: R row-major, then t, P' = R P + t as in sgm_register_spec, t and the volume in the
+ * units of baseline; it is read before the call returns.  All other pointers are device pointers on the instance's device and
+ * need no alignment beyond their element's, except d_points (16 bytes): a volume with nx % 4 != 0 or a d_voxels that cannot be
+ * accessed 16 bytes at a time takes a one-voxel-per-lane path with the same results.  Asynchronous on sgm_stream(s), behind the
+ * last match also with sgm_set_overlap_post, as for clouds.  d_disp == NULL: the instance's last final map, under the cloud entry
+ * points' rules.  false, nothing queued and a message on stderr: a NULL s, spec, src, poses, d_voxels (d_count; d_points unless
+ * capacity is 0); a spec outside the ranges below; a src outside the cloud spec's ranges or with more than 64 frames (the poses
+ * travel as kernel arguments); a non-finite pose entry; a min_weight outside 1..65535; a pointer not aligned as said; a d_voxels
+ * that aliases a map (d_points or d_count that alias the volume or each other); a build without the kernels.  The extraction
+ * keeps 8 bytes of scratch per tile of 2048 voxels, reserved at its first call: an instance that never calls these entry points
+ * allocates and launches exactly what it did before.  Not part of it: ray-casting the volume into a view, meshing,
+ * confidence-weighted updates, colour, voxel hashing or a moving volume, estimating the poses, row tiles, sgm_match_planes. */
+typedef struct {            /* 36 bytes, every field 4 bytes, no padding */
+    int32_t  nx, ny, nz;    /* 1..1024 each, nx*ny*nz <= 2^30; voxel n = (k*ny + j)*nx + i, x fastest */
+    float    voxel;         /* edge length, units of baseline; finite, > 0 */
+    float    origin[3];     /* world position of the corner of voxel (0,0,0); finite */
+    float    trunc;         /* truncation distance; finite, > 0 */
+    uint32_t max_weight;    /* 1..65535 */
+} sgm_volume_spec;
+typedef struct { float x, y, z; uint32_t id; } sgm_surface_point;   /* 16 bytes; id = n*4 + axis */
+size_t sgm_volume_bytes(const sgm_volume_spec* spec);                /* host only; 0 for a refused spec */
+bool   sgm_volume_integrate(sgm_instance* s, const sgm_volume_spec* spec, const sgm_cloud_spec* src,
+                            const float* poses /* HOST, [src->frames][12]: R row-major then t; read before return */,
+                            const float* d_disp, const uint8_t* d_mask, const uint16_t* d_conf, uint32_t* d_voxels);
+bool   sgm_volume_points(sgm_instance* s, const sgm_volume_spec* spec, const uint32_t* d_voxels, uint32_t min_weight /* 1..65535 */,
+                         sgm_surface_point* d_points /* 16-byte aligned */, size_t capacity, uint32_t* d_count);
+
 /* ---- matching at half or quarter scale, re-search at full resolution ----
  * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/scaled_ref.py.  A match at
  * 1/f scale pays for f^3 fewer cells of W x H x D for the same metric range; the result is brought back to the full grid by a guided

@@ -126,53 +126,16 @@ __global__ __launch_bounds__(CLOUD_THREADS) void sgm_cloud_count_k(CloudParams c
 }
 
 // ONE workgroup: base[i] = kept[0] + .. + kept[i - 1]; offsets[f] = base of frame f's first tile, offsets[frames] = the total.
-// Chunks of 4 * 1024 tiles with a running carry, so any number of tiles works.
-#define SCAN_THREADS 1024
-#define SCAN_PER_THREAD 4
+// (tile_scan of sgm_cloud_common.hpp: any number of tiles works)
 __global__ __launch_bounds__(SCAN_THREADS) void sgm_cloud_scan_k(const unsigned* __restrict__ kept, unsigned ntiles,
                                                                  unsigned tiles_per_frame, unsigned frames,
                                                                  unsigned* __restrict__ base, unsigned* __restrict__ offsets)
 {
-    __shared__ unsigned s_wave[2][SCAN_THREADS / 64];
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned carry = 0, turn = 0;
-    for (unsigned chunk = 0; chunk < ntiles; chunk += SCAN_THREADS * SCAN_PER_THREAD, turn ^= 1u) {
-        const unsigned i0 = chunk + threadIdx.x * SCAN_PER_THREAD;
-        unsigned v[SCAN_PER_THREAD], mine = 0;
-#pragma unroll
-        for (int j = 0; j < SCAN_PER_THREAD; ++j) {
-            v[j] = i0 + j < ntiles ? kept[i0 + j] : 0u;
-            mine += v[j];
-        }
-        unsigned incl = mine;                                 // inclusive prefix over the wave's lanes
-#pragma unroll
-        for (int step = 1; step < 64; step <<= 1) {
-            const unsigned up = __shfl_up(incl, step);
-            if (lane >= (unsigned)step) incl += up;
-        }
-        if (lane == 63) s_wave[turn][wave] = incl;
-        __syncthreads();                                      // (the other half of s_wave is what the previous chunk still reads)
-        unsigned before = 0, all = 0;
-#pragma unroll
-        for (unsigned w = 0; w < SCAN_THREADS / 64; ++w) {
-            const unsigned s = s_wave[turn][w];
-            before += w < wave ? s : 0u;
-            all += s;
-        }
-        unsigned run = carry + before + incl - mine;
-#pragma unroll
-        for (int j = 0; j < SCAN_PER_THREAD; ++j) {
-            const unsigned i = i0 + j;
-            if (i < ntiles) {
-                base[i] = run;
-                const unsigned f = i / tiles_per_frame;
-                if (i == f * tiles_per_frame) offsets[f] = run;
-            }
-            run += v[j];
-        }
-        carry += all;
-    }
-    if (threadIdx.x == 0) offsets[frames] = carry;
+    const unsigned total = tile_scan(kept, ntiles, base, [&](unsigned i, unsigned run) {
+        const unsigned f = i / tiles_per_frame;
+        if (i == f * tiles_per_frame) offsets[f] = run;
+    });
+    if (threadIdx.x == 0) offsets[frames] = total;
 }
 
 struct __attribute__((aligned(16))) CloudPoint { float x, y, z; unsigned pixel; };

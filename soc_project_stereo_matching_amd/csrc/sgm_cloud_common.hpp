@@ -1,6 +1,7 @@
 #pragma once
 // The predicate, the formulas and the load paths of the point clouds (include/sgm_mi355x.h, sgm_cloud_spec), shared by the
-// translation units that turn a disparity map into 3-D points: sgm_cloud.hip and sgm_register.hip.  Include after sgm_common.hpp.
+// translation units that turn a disparity map into 3-D points: sgm_cloud.hip, sgm_register.hip and sgm_volume.hip; and the scan of
+// the ordered compactions of sgm_cloud.hip and sgm_volume.hip.  Include after sgm_common.hpp.
 
 struct CloudParams {
     float fx, fy, cx, cy, fb, doffs, z_min, z_max;
@@ -24,6 +25,56 @@ static __device__ __forceinline__ void cloud_xy(const CloudParams& c, unsigned x
 {
     X = (((float)x - c.cx) * Z) / c.fx;
     Y = (((float)y - c.cy) * Z) / c.fy;
+}
+
+// The scan of an ordered compaction's three launches (count per tile, scan, emit), for ONE workgroup of SCAN_THREADS:
+// base[i] = kept[0] + .. + kept[i - 1], at_tile(i, base[i]) for every tile, the total as the result (in every thread).
+// Chunks of 4 * 1024 tiles with a running carry, so any number of tiles works.
+#define SCAN_THREADS 1024
+#define SCAN_PER_THREAD 4
+template <class AtTile>
+static __device__ __forceinline__ unsigned tile_scan(const unsigned* __restrict__ kept, unsigned ntiles, unsigned* __restrict__ base,
+                                                     AtTile at_tile)
+{
+    __shared__ unsigned s_wave[2][SCAN_THREADS / 64];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned carry = 0, turn = 0;
+    for (unsigned chunk = 0; chunk < ntiles; chunk += SCAN_THREADS * SCAN_PER_THREAD, turn ^= 1u) {
+        const unsigned i0 = chunk + threadIdx.x * SCAN_PER_THREAD;
+        unsigned v[SCAN_PER_THREAD], mine = 0;
+#pragma unroll
+        for (int j = 0; j < SCAN_PER_THREAD; ++j) {
+            v[j] = i0 + j < ntiles ? kept[i0 + j] : 0u;
+            mine += v[j];
+        }
+        unsigned incl = mine;                                 // inclusive prefix over the wave's lanes
+#pragma unroll
+        for (int step = 1; step < 64; step <<= 1) {
+            const unsigned up = __shfl_up(incl, step);
+            if (lane >= (unsigned)step) incl += up;
+        }
+        if (lane == 63) s_wave[turn][wave] = incl;
+        __syncthreads();                                      // (the other half of s_wave is what the previous chunk still reads)
+        unsigned before = 0, all = 0;
+#pragma unroll
+        for (unsigned w = 0; w < SCAN_THREADS / 64; ++w) {
+            const unsigned s = s_wave[turn][w];
+            before += w < wave ? s : 0u;
+            all += s;
+        }
+        unsigned run = carry + before + incl - mine;
+#pragma unroll
+        for (int j = 0; j < SCAN_PER_THREAD; ++j) {
+            const unsigned i = i0 + j;
+            if (i < ntiles) {
+                base[i] = run;
+                at_tile(i, run);
+            }
+            run += v[j];
+        }
+        carry += all;
+    }
+    return carry;
 }
 
 // V consecutive pixels of one frame starting at frame-relative index p (p % V == 0 with V == 4), those at or past `end` read

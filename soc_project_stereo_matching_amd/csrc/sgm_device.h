@@ -299,6 +299,24 @@ int sgmd_register_depth(int ord, void* stream, const sgmd_cloud* c, const sgmd_r
 int sgmd_register_gather(int ord, void* stream, const sgmd_cloud* c, const sgmd_register* r, const void* source, int elem_bytes,
                          const void* map, unsigned fill, void* out);
 
+/* Extension (parity unpinned by the reference), depth fused into a TSDF volume (include/sgm_mi355x.h, sgm_volume_spec);
+ * sgm_volume.hip.  v: the volume as the host validated it; c: the source as the cloud entry points take it (c->B <= 64).
+ * sgmd_volume_integrate: poses (HOST, [c->B][12], read before it returns: they travel as kernel arguments), disp, mask, conf
+ * [B][c->H][c->W], voxels u32 [nz][ny][nx] updated in place by one launch.  sgmd_volume_points: three launches (count per tile,
+ * one scan, emit) that use scratch, sgmd_volume_scratch_bytes(nx, ny, nz) bytes, which must not be shared with a call still in
+ * flight; points: 16-byte records sorted by id, those at index >= capacity not written; count[0]: the number of crossings.
+ * sgm_host.c references all three weakly (a host built without them answers false). */
+typedef struct {
+    int nx, ny, nz;
+    float voxel, origin[3], trunc;
+    unsigned max_weight;
+} sgmd_volume;
+size_t sgmd_volume_scratch_bytes(int nx, int ny, int nz);
+int sgmd_volume_integrate(int ord, void* stream, const sgmd_volume* v, const sgmd_cloud* c, const float* poses, const void* disp,
+                          const void* mask, const void* conf, void* voxels);
+int sgmd_volume_points(int ord, void* stream, const sgmd_volume* v, const void* voxels, unsigned min_weight, void* scratch,
+                       void* points, size_t capacity, void* count);
+
 /* Extension (parity unpinned by the reference), matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); sgm_scale.hip.
  * c: the spec as the host validated it (W, H: FULL resolution; the low resolution is W / f x H / f).  sgmd_downscale: the f x f box
  * mean with rounding of one image stack, u8 (bits == 8) or u16 [B][H][W] -> [B][H / f][W / f]; trailing rows and columns are not

@@ -160,6 +160,8 @@ struct sgm_instance {
     sgm_buf d_cloud_scratch, d_cloud_points, d_cloud_offsets;
     /* registration (sgm_register_depth; allocated at the first such call): one 8-byte z-buffer key per target pixel */
     sgm_buf d_register_keys;
+    /* TSDF volume (sgm_volume_points; allocated at the first such call): the tile counts and bases of the surface list's three launches */
+    sgm_buf d_volume_scratch;
     /* matching at 1/f scale (sgm_match_scaled; allocated at its first use): the downscaled views, the census planes of the
      * FULL-resolution views with the narrowed images sgmd_census16 writes beside them, and for the host-pointer form the full
      * images, the full map and their page-locked staging */
@@ -211,7 +213,7 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     DEVICE_BUF(d_sc_small_l), DEVICE_BUF(d_sc_small_r), DEVICE_BUF(d_sc_census_l), DEVICE_BUF(d_sc_census_r), DEVICE_BUF(d_sc_g8_l),
     DEVICE_BUF(d_sc_g8_r), DEVICE_BUF(d_sc_full_l), DEVICE_BUF(d_sc_full_r), DEVICE_BUF(d_sc_disp), PINNED_BUF(h_sc_l), PINNED_BUF(h_sc_r),
     PINNED_BUF(h_sc_disp), DEVICE_BUF(d_tp_value), DEVICE_BUF(d_tp_bits), DEVICE_BUF(d_tp_stats), DEVICE_BUF(d_tp_pre),
-    DEVICE_BUF(d_tp_scratch), DEVICE_BUF(d_register_keys),
+    DEVICE_BUF(d_tp_scratch), DEVICE_BUF(d_register_keys), DEVICE_BUF(d_volume_scratch),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -2290,6 +2292,90 @@ bool sgm_register_spec_raw(const double K[9], const double dist[5], const double
     out->z_min = 0.0f; out->z_max = INFINITY;
     out->splat = splat;
     return true;
+}
+
+/* ------------------------------------------------------------------ depth fused into a TSDF volume (extension) */
+
+/* The launchers of sgm_volume.hip, weakly referenced like the extensions above: a host built without them has no volume */
+#pragma weak sgmd_volume_scratch_bytes
+#pragma weak sgmd_volume_integrate
+#pragma weak sgmd_volume_points
+static bool volume_available(void) { return sgmd_volume_scratch_bytes != NULL && sgmd_volume_integrate != NULL && sgmd_volume_points != NULL; }
+
+#define VOLUME_MAX_FRAMES 64    /* the poses travel as kernel arguments */
+
+/* the volume as the kernels take it; false for anything outside the ranges of include/sgm_mi355x.h */
+static bool volume_spec_valid(const sgm_volume_spec* sp, sgmd_volume* v)
+{
+    if (sp->nx < 1 || sp->nx > 1024 || sp->ny < 1 || sp->ny > 1024 || sp->nz < 1 || sp->nz > 1024 ||
+        (long long)sp->nx * sp->ny * sp->nz > (1LL << 30))
+        return false;
+    if (!finite_positive(sp->voxel) || !finite_positive(sp->trunc) || sp->max_weight < 1u || sp->max_weight > 65535u) return false;
+    for (int i = 0; i < 3; ++i) if (!isfinite(sp->origin[i])) return false;
+    *v = (sgmd_volume){sp->nx, sp->ny, sp->nz, sp->voxel, {sp->origin[0], sp->origin[1], sp->origin[2]}, sp->trunc, sp->max_weight};
+    return true;
+}
+
+size_t sgm_volume_bytes(const sgm_volume_spec* spec)
+{
+    sgmd_volume v;
+    if (!spec || !volume_spec_valid(spec, &v)) return 0;
+    return (size_t)v.nx * v.ny * v.nz * sizeof(uint32_t);
+}
+
+bool sgm_volume_integrate(sgm_instance* s, const sgm_volume_spec* spec, const sgm_cloud_spec* src, const float* poses, const float* d_disp,
+                          const uint8_t* d_mask, const uint16_t* d_conf, uint32_t* d_voxels)
+{
+    sgmd_volume v;
+    sgmd_cloud c;
+    if (!s || !spec || !src || !poses || !d_voxels) FAIL("sgm_volume_integrate: NULL argument");
+    if (!volume_available()) FAIL("the volume is not part of this build");
+    if (!volume_spec_valid(spec, &v)) FAIL("sgm_volume_integrate: the volume spec is outside its ranges");
+    if (!cloud_spec_valid(src, &c)) FAIL("sgm_volume_integrate: the source spec is outside its ranges");
+    if (c.B > VOLUME_MAX_FRAMES) FAIL("sgm_volume_integrate: %d frames in one call (at most %d)", c.B, VOLUME_MAX_FRAMES);
+    for (int i = 0; i < 12 * c.B; ++i)
+        if (!isfinite(poses[i])) FAIL("sgm_volume_integrate: entry %d of the pose of frame %d is not finite", i % 12, i / 12);
+    if ((uintptr_t)d_disp % sizeof(float) != 0 || (uintptr_t)d_conf % sizeof(uint16_t) != 0 || (uintptr_t)d_voxels % sizeof(uint32_t) != 0)
+        FAIL("sgm_volume_integrate: a pointer is not aligned to its element");
+    if (!d_disp) {                                               /* the cloud entry points' rules */
+        if (!s->initialized) FAIL("sgm_volume_integrate: no map given and no match to take one from");
+        if (row_tiled(s)) FAIL("the map of a row tile is the caller's: pass it to sgm_volume_integrate explicitly");
+        if (c.W != s->g.W || c.H != s->g.H || c.B != s->g.B)
+            FAIL("the source spec is for %d frames of %dx%d, the instance's last match for %d of %dx%d", c.B, c.W, c.H, s->g.B, s->g.W, s->g.H);
+        d_disp = (const float*)(s->last_both ? s->d_both_maps.p : s->d_disp.p);
+        if (!d_disp) FAIL("sgm_volume_integrate: no map given and no match to take one from");
+    }
+    const size_t px = (size_t)c.B * c.W * c.H, vol_bytes = (size_t)v.nx * v.ny * v.nz * sizeof(uint32_t);
+    if (ranges_overlap(d_voxels, vol_bytes, d_disp, px * sizeof(float)) || ranges_overlap(d_voxels, vol_bytes, d_mask, px) ||
+        ranges_overlap(d_voxels, vol_bytes, d_conf, px * sizeof(uint16_t)))
+        FAIL("sgm_volume_integrate: the volume aliases a map");
+    /* the map may be the result of a match whose last stages run on a stream of their own (sgm_set_overlap_post / _stage_cus) */
+    if (wait_for_result(s, s->stream) != 0) return false;
+    return sgmd_volume_integrate(s->device, s->stream, &v, &c, poses, d_disp, d_mask, d_conf, d_voxels) == 0;
+}
+
+bool sgm_volume_points(sgm_instance* s, const sgm_volume_spec* spec, const uint32_t* d_voxels, uint32_t min_weight,
+                       sgm_surface_point* d_points, size_t capacity, uint32_t* d_count)
+{
+    sgmd_volume v;
+    if (!s || !spec || !d_voxels || !d_count || (!d_points && capacity)) FAIL("sgm_volume_points: NULL argument");
+    if (!volume_available()) FAIL("the volume is not part of this build");
+    if (!volume_spec_valid(spec, &v)) FAIL("sgm_volume_points: the volume spec is outside its ranges");
+    if (min_weight < 1u || min_weight > 65535u) FAIL("sgm_volume_points: a min_weight of %u (1..65535)", min_weight);
+    if ((uintptr_t)d_voxels % sizeof(uint32_t) != 0 || (uintptr_t)d_points % sizeof(sgm_surface_point) != 0 ||
+        (uintptr_t)d_count % sizeof(uint32_t) != 0)
+        FAIL("sgm_volume_points: a pointer is not aligned (the points to 16 bytes, the others to their element)");
+    const size_t n = (size_t)v.nx * v.ny * v.nz, vol_bytes = n * sizeof(uint32_t);
+    /* (no more than three crossings per voxel can be written, whatever the capacity says) */
+    const size_t pts_bytes = (capacity < 3 * n ? capacity : 3 * n) * sizeof(sgm_surface_point);
+    if (ranges_overlap(d_points, pts_bytes, d_voxels, vol_bytes) || ranges_overlap(d_count, sizeof(uint32_t), d_voxels, vol_bytes) ||
+        ranges_overlap(d_count, sizeof(uint32_t), d_points, pts_bytes))
+        FAIL("sgm_volume_points: an output aliases the volume or the other output");
+    /* (growing the scratch drains the streams first: an earlier list may still be using it) */
+    if (!reserve(s, &s->d_volume_scratch, sgmd_volume_scratch_bytes(v.nx, v.ny, v.nz), 0))
+        FAIL("device allocation failed for the surface list of %dx%dx%d voxels", v.nx, v.ny, v.nz);
+    if (wait_for_result(s, s->stream) != 0) return false;
+    return sgmd_volume_points(s->device, s->stream, &v, d_voxels, min_weight, s->d_volume_scratch.p, d_points, capacity, d_count) == 0;
 }
 
 /* ------------------------------------------------------------------ matching at 1/f scale (extension) */

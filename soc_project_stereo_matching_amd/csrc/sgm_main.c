@@ -31,6 +31,11 @@
  *                             camera LEFT came from (RIGHT with --right-reference) -- sgm_register_depth into the target of
  *                             sgm_register_spec_raw -- as raw float32 [H][W] like --raw, NaN where nothing landed; splat 2 (default)
  *                             votes for the four raw pixels around a projection, 1 for the nearest.  --cloud-z-max cuts it too
+ *            [--volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC --volume-ply OUT.ply]   extension: with --pinhole, OUT's map fused into a TSDF
+ *                             volume of NX x NY x NZ voxels of edge VOXEL with its corner at (OX, OY, OZ) in the camera's frame
+ *                             (units of BASELINE) and truncation distance TRUNC -- sgm_volume_integrate of the one frame with the
+ *                             identity pose -- and the volume's surface points (sgm_volume_points, min_weight 1) as a PLY like
+ *                             --cloud's, coloured with the grey at the pixel a point projects to.  --cloud-z-max cuts it too
  *            [--bits N]       extension: images of N = 9..16 bits per sample (SGM_SetPixelBits): LEFT and RIGHT are loaded with
  *                             sgm_load_gray16 (binary PGM with maxval up to 65535, PNG grey of depth 16; 8-bit files are widened
  *                             unshifted) and matched on all their bits.  --bits 0: the smallest N >= 8 that holds the files' maxval.
@@ -162,6 +167,73 @@ static int register_raw(const char* path, const char* calib_path, int right_ref,
     return rc;
 }
 
+/* --volume: the map fused into a TSDF volume with the identity pose, and the surface points read back, as sgm_point records whose
+ * pixel is the one the point projects to (clamped to the image), for write_ply.  Page-locked buffers of an instance of its own, as
+ * above.  *out: malloc'ed, *n records. */
+static int volume_surface(const sgm_volume_spec* vol, int device, int w, int h, const float* pinhole, float z_max, const float* disp,
+                          sgm_point** out, size_t* n)
+{
+    const sgm_cloud_spec src = {w, h, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], pinhole[4], pinhole[5], 0.0f, z_max, 0};
+    static const float identity[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    const size_t bytes = sgm_volume_bytes(vol);
+    if (!bytes) return -1;
+    if (device < 0) {
+        const char* e = getenv("SGM_DEVICE");
+        device = (e && *e) ? atoi(e) : 0;
+    }
+    sgm_instance* s = sgm_create(device);
+    if (!s) return -1;
+    const size_t px = (size_t)w * h;
+    float* d_disp = (float*)sgm_host_alloc(s, px * sizeof(float));
+    uint32_t* d_voxels = (uint32_t*)sgm_host_alloc(s, bytes);
+    uint32_t* d_count = (uint32_t*)sgm_host_alloc(s, sizeof(uint32_t));
+    sgm_surface_point* d_points = NULL;
+    int rc = -1;
+    *out = NULL;
+    *n = 0;
+    if (d_disp && d_voxels && d_count) {
+        memcpy(d_disp, disp, px * sizeof(float));
+        memset(d_voxels, 0, bytes);                               /* the empty volume */
+        if (sgm_volume_integrate(s, vol, &src, identity, d_disp, NULL, NULL, d_voxels) &&
+            sgm_volume_points(s, vol, d_voxels, 1, NULL, 0, d_count) && sgm_synchronize(s)) {
+            const size_t count = *d_count;
+            size_t seen = 0;
+            for (size_t i = 0; i < bytes / sizeof(uint32_t); ++i) seen += (d_voxels[i] >> 16) != 0;
+            printf("volume: %zu of %zu voxels seen, %zu surface points\n", seen, bytes / sizeof(uint32_t), count);
+            d_points = count ? (sgm_surface_point*)sgm_host_alloc(s, count * sizeof(sgm_surface_point)) : NULL;
+            *out = (sgm_point*)malloc((count ? count : 1) * sizeof(sgm_point));
+            if (*out && (!count || (d_points && sgm_volume_points(s, vol, d_voxels, 1, d_points, count, d_count) && sgm_synchronize(s)))) {
+                for (size_t i = 0; i < count; ++i) {
+                    const sgm_surface_point q = d_points[i];
+                    float u = floorf(pinhole[0] * (q.x / q.z) + pinhole[2] + 0.5f), v = floorf(pinhole[1] * (q.y / q.z) + pinhole[3] + 0.5f);
+                    u = u >= 0.0f ? (u < (float)w ? u : (float)(w - 1)) : 0.0f;          /* (a NaN lands on pixel 0) */
+                    v = v >= 0.0f ? (v < (float)h ? v : (float)(h - 1)) : 0.0f;
+                    (*out)[i] = (sgm_point){q.x, q.y, q.z, ((uint32_t)v << 16) | (uint32_t)u};
+                }
+                *n = count;
+                rc = 0;
+            }
+        }
+    }
+    sgm_host_free(s, d_disp);
+    sgm_host_free(s, d_voxels);
+    sgm_host_free(s, d_count);
+    sgm_host_free(s, d_points);
+    sgm_destroy(s);
+    return rc;
+}
+
+/* the 8-bit image the map's pixels are those of: the reference view's, as the match saw it (stage 19 / 20 with --rectify, the
+ * narrowed image, stage 21 / 22, with more than 8 bits); *owned: what to free afterwards.  NULL: not available */
+static const uint8_t* reference_grey(const uint8_t* left, const uint8_t* right, int right_ref, int rectified, int bits, size_t px,
+                                     uint8_t** owned)
+{
+    *owned = NULL;
+    if (!rectified && bits <= 8) return right_ref ? right : left;
+    *owned = (uint8_t*)malloc(px);
+    return (*owned && SGM_ReadStage((bits > 8 ? 21 : 19) + right_ref, *owned, px) == px) ? *owned : NULL;
+}
+
 int main(int argc, char** argv)
 {
     if (argc == 4 && !strcmp(argv[1], "--convert")) {
@@ -208,6 +280,9 @@ int main(int argc, char** argv)
     float pinhole[6], cloud_z_max = INFINITY;
     int have_pinhole = 0;
     const char* register_path = NULL;
+    const char* volume_path = NULL;
+    sgm_volume_spec volume = {0, 0, 0, 0.0f, {0.0f, 0.0f, 0.0f}, 0.0f, 65535};
+    int have_volume = 0;
     int register_splat = 2, register_splat_set = 0;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
     int census_kind = SGM_CENSUS_CENTRE, bits = 8;
@@ -244,6 +319,16 @@ int main(int argc, char** argv)
         }
         else if (v && !strcmp(a, "--cloud-z-max")) { cloud_z_max = (float)atof(v); ++i; }
         else if (v && !strcmp(a, "--register-raw")) { register_path = v; ++i; }
+        else if (v && !strcmp(a, "--volume")) {
+            if (sscanf(v, "%d,%d,%d,%f,%f,%f,%f,%f", &volume.nx, &volume.ny, &volume.nz, &volume.voxel, &volume.origin[0], &volume.origin[1],
+                       &volume.origin[2], &volume.trunc) != 8) {
+                fprintf(stderr, "--volume wants NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n");
+                return 2;
+            }
+            have_volume = 1;
+            ++i;
+        }
+        else if (v && !strcmp(a, "--volume-ply")) { volume_path = v; ++i; }
         else if (v && !strcmp(a, "--register-splat")) {
             if (strcmp(v, "1") && strcmp(v, "2")) { fprintf(stderr, "--register-splat wants 1 or 2\n"); return 2; }
             register_splat = atoi(v);
@@ -292,6 +377,9 @@ int main(int argc, char** argv)
                         "(OUT would silently be the left map)\n");
         return 2;
     }
+    if (have_volume != (volume_path != NULL)) { fprintf(stderr, "--volume and --volume-ply OUT.ply come together\n"); return 2; }
+    if (volume_path && !have_pinhole) { fprintf(stderr, "--volume needs --pinhole FX,FY,CX,CY,BASELINE,DOFFS\n"); return 2; }
+    if (scale && volume_path) { fprintf(stderr, "--scale does not combine with --volume\n"); return 2; }
     if (scale && register_path) { fprintf(stderr, "--scale does not combine with --register-raw (it needs --rectify)\n"); return 2; }
     if (scale && (cloud_path || conf_path || right_out || right_raw || calib_path)) {
         fprintf(stderr, "--scale does not combine with --cloud, --confidence, --right-out / --right-raw or --rectify "
@@ -407,14 +495,8 @@ int main(int argc, char** argv)
         if (!ok) { printf("point cloud unavailable or --pinhole / --cloud-z-max out of range\n"); rc = -1; }
         else {
             printf("cloud: %u points\n", offsets[1]);
-            /* the image the map's pixels are those of: the reference view's, as the match saw it (stage 19 / 20 with --rectify) */
-            const size_t px = (size_t)w1 * h1;
-            const uint8_t* grey = right_ref ? right : left;
             uint8_t* rect = NULL;
-            if (calib_path || bits > 8) {                         /* more than 8 bits: the narrowed image, stage 21 / 22 */
-                rect = (uint8_t*)malloc(px);
-                grey = (rect && SGM_ReadStage((bits > 8 ? 21 : 19) + right_ref, rect, px) == px) ? rect : NULL;
-            }
+            const uint8_t* grey = reference_grey(left, right, right_ref, calib_path != NULL, bits, (size_t)w1 * h1, &rect);
             if (!grey || write_ply(cloud_path, pts, offsets[1], grey, w1) != 0) rc = -1;
             free(rect);
         }
@@ -423,6 +505,20 @@ int main(int argc, char** argv)
     if (register_path && register_raw(register_path, calib_path, right_ref, device, w1, h1, pinhole, cloud_z_max, register_splat, disp) != 0) {
         printf("registration unavailable, a bad calibration file or --pinhole / --cloud-z-max out of range\n");
         rc = -1;
+    }
+    if (volume_path) {
+        sgm_point* pts = NULL;
+        size_t n = 0;
+        if (volume_surface(&volume, device, w1, h1, pinhole, cloud_z_max, disp, &pts, &n) != 0) {
+            printf("volume unavailable or --volume / --pinhole / --cloud-z-max out of range\n");
+            rc = -1;
+        } else {
+            uint8_t* rect = NULL;
+            const uint8_t* grey = reference_grey(left, right, right_ref, calib_path != NULL, bits, (size_t)w1 * h1, &rect);
+            if (!grey || write_ply(volume_path, pts, n, grey, w1) != 0) rc = -1;
+            free(rect);
+        }
+        free(pts);
     }
     SGM_Shutdown();
     free(disp); free(disp_r); free(conf); free(left); free(right);

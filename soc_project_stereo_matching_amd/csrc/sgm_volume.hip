@@ -1,0 +1,338 @@
+#include "sgm_common.hpp"
+#include "sgm_cloud_common.hpp"
+
+// ============================================================================================
+// Extension (parity unpinned by the reference): depth maps with known poses fused into a truncated signed distance volume
+// (TSDF), and the surface read back out as points.  The contract is written out in include/sgm_mi355x.h (sgm_volume_spec);
+// tests/volume_ref.py restates it in numpy.
+//
+// Integration   ONE launch, owner-computes: a lane owns its voxels, loads their words once, walks the frames of the batch in
+//               order with the words in registers and stores them once -- no atomics and no order between workgroups, so a call
+//               over B frames is B calls of one frame, bit for bit.  Per voxel and frame: the voxel centre into the camera
+//               (the poses are kernel arguments, read with scalar loads), the pinhole, one gather of the source pixel (the
+//               cloud's predicate, cloud_kept, decides whether it contributes and gives Z), the running average in integers.
+//               Four consecutive-x voxels per lane with 16-byte loads and stores where nx % 4 == 0 and the pointer allows it,
+//               else one voxel per lane.  A lane none of whose voxels was updated does not store.
+// Extraction    the ordered compaction of sgm_cloud.hip with a lane contributing 0..3 records (one per axis) instead of 0..1:
+//               count per tile, one scan (tile_scan), emit; three ballots give a record's rank inside its wave.  No atomic
+//               decides a place: the list is sorted by id and the same on every run.
+//
+// (this translation unit is compiled with -fno-honor-nans like the others: "finite" is tested on the bit pattern, before any
+// comparison)
+// ============================================================================================
+
+#define VOL_THREADS 256
+#define VOL_WAVES (VOL_THREADS / 64)
+#define VOL_TILE_MAX 2048
+#define VOL_MAX_FRAMES 64
+// SGM_VOLUME_VEC (make VOL_VEC=0): 0 sends every volume down the one-voxel-per-lane path -- the measurement of NOTES.md section 31
+#ifndef SGM_VOLUME_VEC
+#define SGM_VOLUME_VEC 1
+#endif
+
+struct VolumeParams {
+    unsigned nx, ny, nz;
+    unsigned n;                // voxels
+    float voxel, ox, oy, oz, trunc;
+    unsigned max_weight;
+};
+struct VolumePoses { float p[VOL_MAX_FRAMES][12]; };          // 3 KiB of the 4 KiB a kernel's arguments may take
+
+// the source image as the integration needs it beside CloudParams
+struct VolumeSource { float wf, hf; unsigned frames; };
+
+static __device__ __forceinline__ float volume_centre(float o, unsigned i, float voxel) { return o + ((float)i + 0.5f) * voxel; }
+
+// n -> (i, j, k)
+static __device__ __forceinline__ void volume_ijk(const VolumeParams& v, unsigned n, unsigned& i, unsigned& j, unsigned& k)
+{
+    const unsigned row = n / v.nx;
+    i = n - row * v.nx;
+    k = row / v.ny;
+    j = row - k * v.ny;
+}
+
+// ---- integration ---------------------------------------------------------------------------------------------------------------
+
+// One frame's say on one voxel whose centre is (px, py, pz); true when the voxel was updated.  The parentheses are the contract's.
+static __device__ __forceinline__ bool volume_update(const VolumeParams& v, const CloudParams& c, const VolumeSource& s,
+                                                     const float* P, size_t frame_base, const float* __restrict__ disp,
+                                                     const uint8_t* __restrict__ mask, const uint16_t* __restrict__ conf, float px,
+                                                     float py, float pz, int& tq, unsigned& w)
+{
+    const float Xp = ((P[0] * px + P[1] * py) + P[2] * pz) + P[9];
+    const float Yp = ((P[3] * px + P[4] * py) + P[5] * pz) + P[10];
+    const float Zp = ((P[6] * px + P[7] * py) + P[8] * pz) + P[11];
+    if (!cloud_finite(Zp)) return false;
+    if (!(Zp > 0.0f)) return false;
+    const float u = c.fx * (Xp / Zp) + c.cx, vv = c.fy * (Yp / Zp) + c.cy;
+    if (!cloud_finite(u) || !cloud_finite(vv)) return false;
+    const float uf = floorf(u + 0.5f), vf = floorf(vv + 0.5f);
+    // admitted in float, before any conversion to int
+    if (!(0.0f <= uf && uf < s.wf && 0.0f <= vf && vf < s.hf)) return false;
+    const size_t at = frame_base + (size_t)(unsigned)vf * c.W + (unsigned)uf;
+    float Z;
+    if (!cloud_kept(c, disp[at], mask ? mask[at] : 1u, conf ? conf[at] : 65535u, Z)) return false;
+    const float sdf = Z - Zp;
+    if (sdf < -v.trunc) return false;
+    const int q = (int)rintf((fminf(sdf, v.trunc) / v.trunc) * 32767.0f);
+    // num / den rounded to the nearest integer, halves up: |num| < 2^31, but 2 * num + den leaves int32 past w = 32767
+    const int num = tq * (int)w + q, den = (int)w + 1;
+    int quot = num / den, rem = num - quot * den;
+    if (rem < 0) { rem += den; --quot; }
+    tq = quot + (2 * rem >= den ? 1 : 0);
+    w = min(w + 1u, v.max_weight);
+    return true;
+}
+
+template <int V>
+__global__ __launch_bounds__(VOL_THREADS) void sgm_volume_integrate_k(VolumeParams v, CloudParams c, VolumeSource s, VolumePoses poses,
+                                                                      const float* __restrict__ disp, const uint8_t* __restrict__ mask,
+                                                                      const uint16_t* __restrict__ conf, unsigned* __restrict__ voxels)
+{
+    const unsigned g = (blockIdx.x * VOL_THREADS + threadIdx.x) * V;             // V == 4: nx % 4 == 0, the four share a row
+    if (g >= v.n) return;
+    unsigned i, j, k;
+    volume_ijk(v, g, i, j, k);
+    unsigned word[V];
+    if constexpr (V == 4) {
+        const uint4 t = *reinterpret_cast<const uint4*>(voxels + g);
+        word[0] = t.x; word[1] = t.y; word[2] = t.z; word[3] = t.w;
+    } else {
+        word[0] = voxels[g];
+    }
+    int tq[V];
+    unsigned w[V];
+    float px[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+        tq[e] = (int)(short)(word[e] & 0xFFFFu);
+        w[e] = word[e] >> 16;
+        px[e] = volume_centre(v.ox, i + e, v.voxel);
+    }
+    const float py = volume_centre(v.oy, j, v.voxel), pz = volume_centre(v.oz, k, v.voxel);
+    bool touched = false;
+    for (unsigned f = 0; f < s.frames; ++f) {                                   // frames take effect in order
+        const float* P = poses.p[f];
+        const size_t frame_base = (size_t)f * c.npx;
+#pragma unroll
+        for (int e = 0; e < V; ++e) touched |= volume_update(v, c, s, P, frame_base, disp, mask, conf, px[e], py, pz, tq[e], w[e]);
+    }
+    if (!touched) return;
+#pragma unroll
+    for (int e = 0; e < V; ++e) word[e] = (w[e] << 16) | ((unsigned)tq[e] & 0xFFFFu);
+    if constexpr (V == 4)
+        *reinterpret_cast<uint4*>(voxels + g) = make_uint4(word[0], word[1], word[2], word[3]);
+    else
+        voxels[g] = word[0];
+}
+
+// ---- surface points ------------------------------------------------------------------------------------------------------------
+
+// One pass of a workgroup over its tile: this lane's voxel n (not live: none).  Returns the lane's crossings (bit a: axis a) and,
+// through the references, the voxel's place, its tq and its three neighbours', how many records the wave's lower lanes hold and
+// the wave's total.
+static __device__ __forceinline__ unsigned volume_pass(const VolumeParams& v, const unsigned* __restrict__ voxels, unsigned min_weight,
+                                                       unsigned n, bool live, unsigned (&at)[3], int& tn, int (&tm)[3], unsigned& lower,
+                                                       unsigned& wave_total)
+{
+    unsigned flags = 0;
+    tn = 0;
+    at[0] = at[1] = at[2] = 0;
+    tm[0] = tm[1] = tm[2] = 0;
+    if (live) {
+        const unsigned word = voxels[n];
+        volume_ijk(v, n, at[0], at[1], at[2]);
+        if ((word >> 16) >= min_weight) {
+            tn = (int)(short)(word & 0xFFFFu);
+            const unsigned step[3] = {1u, v.nx, v.nx * v.ny};
+            const bool inside[3] = {at[0] + 1 < v.nx, at[1] + 1 < v.ny, at[2] + 1 < v.nz};
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                if (inside[a]) {
+                    const unsigned other = voxels[n + step[a]];
+                    tm[a] = (int)(short)(other & 0xFFFFu);
+                    if ((other >> 16) >= min_weight && (tn < 0) != (tm[a] < 0)) flags |= 1u << a;
+                }
+            }
+        }
+    }
+    lower = wave_total = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const unsigned long long b = __ballot((flags >> a) & 1u);
+        lower += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+        wave_total += (unsigned)__popcll(b);
+    }
+    return flags;
+}
+
+__global__ __launch_bounds__(VOL_THREADS) void sgm_volume_count_k(VolumeParams v, unsigned tile, unsigned min_weight,
+                                                                  const unsigned* __restrict__ voxels, unsigned* __restrict__ kept)
+{
+    __shared__ unsigned s_wave[VOL_WAVES];
+    const unsigned first = blockIdx.x * tile, end = min(first + tile, v.n);
+    unsigned total = 0;                                       // of this wave, the same in all of its lanes
+    for (unsigned p = first + threadIdx.x; p - threadIdx.x < end; p += VOL_THREADS) {
+        unsigned at[3], lower, wave_total;
+        int tn, tm[3];
+        volume_pass(v, voxels, min_weight, p, p < end, at, tn, tm, lower, wave_total);
+        total += wave_total;
+    }
+    if ((threadIdx.x & 63u) == 0) s_wave[threadIdx.x >> 6] = total;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned sum = 0;
+#pragma unroll
+        for (int w = 0; w < VOL_WAVES; ++w) sum += s_wave[w];
+        kept[blockIdx.x] = sum;
+    }
+}
+
+// ONE workgroup: base[i] = kept[0] + .. + kept[i - 1]; count[0] = the total
+__global__ __launch_bounds__(SCAN_THREADS) void sgm_volume_scan_k(const unsigned* __restrict__ kept, unsigned ntiles,
+                                                                  unsigned* __restrict__ base, unsigned* __restrict__ count)
+{
+    const unsigned total = tile_scan(kept, ntiles, base, [](unsigned, unsigned) {});
+    if (threadIdx.x == 0) count[0] = total;
+}
+
+struct __attribute__((aligned(16))) SurfacePoint { float x, y, z; unsigned id; };
+
+__global__ __launch_bounds__(VOL_THREADS) void sgm_volume_emit_k(VolumeParams v, unsigned tile, unsigned min_weight,
+                                                                 const unsigned* __restrict__ voxels, const unsigned* __restrict__ base,
+                                                                 SurfacePoint* __restrict__ points, size_t capacity)
+{
+    __shared__ unsigned s_wave[2][VOL_WAVES];
+    const unsigned first = blockIdx.x * tile, end = min(first + tile, v.n);
+    const unsigned wave = threadIdx.x >> 6;
+    size_t run = base[blockIdx.x];                            // where this pass's first record goes
+    unsigned turn = 0;
+    for (unsigned p = first + threadIdx.x; p - threadIdx.x < end; p += VOL_THREADS, turn ^= 1u) {
+        unsigned at[3], lower, wave_total;
+        int tn, tm[3];
+        const unsigned flags = volume_pass(v, voxels, min_weight, p, p < end, at, tn, tm, lower, wave_total);
+        if ((threadIdx.x & 63u) == 0) s_wave[turn][wave] = wave_total;
+        __syncthreads();                                      // (the other half of s_wave is what the previous pass still reads)
+        unsigned before = 0, all = 0;
+#pragma unroll
+        for (unsigned w = 0; w < VOL_WAVES; ++w) {
+            const unsigned s = s_wave[turn][w];
+            before += w < wave ? s : 0u;
+            all += s;
+        }
+        if (flags) {
+            size_t to = run + before + lower;
+            const float centre[3] = {volume_centre(v.ox, at[0], v.voxel), volume_centre(v.oy, at[1], v.voxel),
+                                     volume_centre(v.oz, at[2], v.voxel)};
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                if (flags & (1u << a)) {
+                    const float s = (float)tn / ((float)tn - (float)tm[a]);
+                    const float moved = centre[a] + s * v.voxel;
+                    SurfacePoint q;
+                    q.x = a == 0 ? moved : centre[0];
+                    q.y = a == 1 ? moved : centre[1];
+                    q.z = a == 2 ? moved : centre[2];
+                    q.id = p * 4u + (unsigned)a;
+                    if (to < capacity) points[to] = q;
+                    ++to;
+                }
+            }
+        }
+        run += all;
+    }
+}
+
+static bool volume_ok(const sgmd_volume* v)
+{
+    return v && v->nx >= 1 && v->ny >= 1 && v->nz >= 1 && v->nx <= 1024 && v->ny <= 1024 && v->nz <= 1024 &&
+           (unsigned long long)v->nx * v->ny * v->nz <= (1ull << 30) && v->max_weight >= 1 && v->max_weight <= 65535;
+}
+
+static VolumeParams volume_params(const sgmd_volume* v)
+{
+    VolumeParams p;
+    p.nx = (unsigned)v->nx; p.ny = (unsigned)v->ny; p.nz = (unsigned)v->nz;
+    p.n = p.nx * p.ny * p.nz;
+    p.voxel = v->voxel; p.ox = v->origin[0]; p.oy = v->origin[1]; p.oz = v->origin[2]; p.trunc = v->trunc;
+    p.max_weight = v->max_weight;
+    return p;
+}
+
+// a tile: a power-of-two run of at most 2048 voxels
+static unsigned volume_tile(size_t n)
+{
+    unsigned tile = 1;
+    while (tile < VOL_TILE_MAX && tile < n) tile <<= 1;
+    return tile;
+}
+
+extern "C" {
+
+size_t sgmd_volume_scratch_bytes(int nx, int ny, int nz)
+{
+    if (nx < 1 || ny < 1 || nz < 1) return 0;
+    const size_t n = (size_t)nx * ny * nz;
+    return 2 * sizeof(unsigned) * ((n + VOL_TILE_MAX - 1) / VOL_TILE_MAX);      // kept[], base[]
+}
+
+int sgmd_volume_integrate(int ord, void* stream, const sgmd_volume* v, const sgmd_cloud* c, const float* poses, const void* disp,
+                          const void* mask, const void* conf, void* voxels)
+{
+    if (!volume_ok(v) || !c || !poses || !disp || !voxels || c->W < 1 || c->H < 1 || c->W > 65535 || c->H > 65535 || c->B < 1 ||
+        c->B > VOL_MAX_FRAMES || (unsigned long long)c->W * c->H * c->B > (1ull << 31) || (uintptr_t)voxels % 4 != 0 ||
+        (uintptr_t)disp % 4 != 0 || (uintptr_t)conf % 2 != 0) {
+        fprintf(stderr, "sgm_mi355x: sgmd_volume_integrate: bad arguments\n");
+        return -1;
+    }
+    HIP_TRY(hipSetDevice(ord));
+    const VolumeParams p = volume_params(v);
+    CloudParams q;
+    q.fx = c->fx; q.fy = c->fy; q.cx = c->cx; q.cy = c->cy; q.fb = c->fb; q.doffs = c->doffs; q.z_min = c->z_min; q.z_max = c->z_max;
+    q.min_conf = c->min_conf;
+    q.W = (unsigned)c->W;
+    q.npx = (unsigned)((size_t)c->W * c->H);
+    VolumeSource s;
+    s.wf = (float)c->W; s.hf = (float)c->H;
+    s.frames = (unsigned)c->B;
+    VolumePoses pose;
+    memset(&pose, 0, sizeof pose);
+    memcpy(pose.p, poses, (size_t)c->B * 12 * sizeof(float));
+    const hipStream_t st = (hipStream_t)stream;
+    if (SGM_VOLUME_VEC && p.nx % 4 == 0 && (uintptr_t)voxels % 16 == 0)
+        hipLaunchKernelGGL(sgm_volume_integrate_k<4>, dim3((p.n / 4 + VOL_THREADS - 1) / VOL_THREADS), dim3(VOL_THREADS), 0, st, p, q, s,
+                           pose, (const float*)disp, (const uint8_t*)mask, (const uint16_t*)conf, (unsigned*)voxels);
+    else
+        hipLaunchKernelGGL(sgm_volume_integrate_k<1>, dim3((p.n + VOL_THREADS - 1) / VOL_THREADS), dim3(VOL_THREADS), 0, st, p, q, s, pose,
+                           (const float*)disp, (const uint8_t*)mask, (const uint16_t*)conf, (unsigned*)voxels);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sgmd_volume_points(int ord, void* stream, const sgmd_volume* v, const void* voxels, unsigned min_weight, void* scratch, void* points,
+                       size_t capacity, void* count)
+{
+    if (!volume_ok(v) || !voxels || !scratch || !count || (!points && capacity) || min_weight < 1 || min_weight > 65535 ||
+        (uintptr_t)voxels % 4 != 0 || (uintptr_t)points % 16 != 0 || (uintptr_t)count % 4 != 0) {
+        fprintf(stderr, "sgm_mi355x: sgmd_volume_points: bad arguments\n");
+        return -1;
+    }
+    HIP_TRY(hipSetDevice(ord));
+    const VolumeParams p = volume_params(v);
+    const unsigned tile = volume_tile(p.n), ntiles = (p.n + tile - 1) / tile;
+    unsigned* kept = (unsigned*)scratch;
+    unsigned* base = kept + ntiles;
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sgm_volume_count_k, dim3(ntiles), dim3(VOL_THREADS), 0, st, p, tile, min_weight, (const unsigned*)voxels, kept);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sgm_volume_scan_k, dim3(1), dim3(SCAN_THREADS), 0, st, (const unsigned*)kept, ntiles, base, (unsigned*)count);
+    HIP_TRY(hipGetLastError());
+    if (capacity == 0) return 0;                              // the count is all that was asked for
+    hipLaunchKernelGGL(sgm_volume_emit_k, dim3(ntiles), dim3(VOL_THREADS), 0, st, p, tile, min_weight, (const unsigned*)voxels,
+                       (const unsigned*)base, (SurfacePoint*)points, capacity);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

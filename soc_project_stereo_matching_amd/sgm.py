@@ -114,6 +114,32 @@ def register_spec_raw(K, dist, R, width, height, splat=2) -> SGMRegisterSpec:
     return out
 
 
+class SGMVolumeSpec(C.Structure):
+    """Field-for-field sgm_volume_spec of include/sgm_mi355x.h: 36 bytes, every field 4 bytes."""
+    _fields_ = [
+        ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+        ("voxel", C.c_float), ("origin", C.c_float * 3), ("trunc", C.c_float),
+        ("max_weight", C.c_uint32),
+    ]
+
+
+SURFACE_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32), ("id", np.uint32)])   # sgm_surface_point
+
+
+def volume_spec(nx, ny, nz, voxel, origin, trunc, max_weight=64) -> SGMVolumeSpec:
+    """A sgm_volume_spec: nx x ny x nz voxels of edge `voxel` (units of baseline), the corner of voxel (0, 0, 0) at `origin` in the
+    world, truncation distance `trunc`, weights capped at max_weight (1..65535)."""
+    origin = np.asarray(origin, np.float64).reshape(-1)
+    if origin.size != 3:
+        raise ValueError("volume_spec: origin has 3 entries")
+    return SGMVolumeSpec(int(nx), int(ny), int(nz), voxel, (C.c_float * 3)(*origin), trunc, int(max_weight))
+
+
+def volume_bytes(spec: SGMVolumeSpec) -> int:
+    """sgm_volume_bytes: the size of the volume's device array (uint32 per voxel), 0 for a spec outside its ranges (host only)."""
+    return int(load_library().sgm_volume_bytes(C.byref(spec)))
+
+
 class SGMScaleSpec(C.Structure):
     """Field-for-field sgm_scale_spec of include/sgm_mi355x.h: 36 bytes, every field 4 bytes."""
     _fields_ = [
@@ -307,6 +333,13 @@ def _load() -> C.CDLL:
         L.sgm_register_gather.restype = C.c_bool
         L.sgm_register_spec_raw.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]
         L.sgm_register_spec_raw.restype = C.c_bool
+    if hasattr(L, "sgm_volume_integrate"):    # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_volume_bytes.argtypes = [C.c_void_p]
+        L.sgm_volume_bytes.restype = C.c_size_t
+        L.sgm_volume_integrate.argtypes = [C.c_void_p] * 8
+        L.sgm_volume_integrate.restype = C.c_bool
+        L.sgm_volume_points.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sgm_volume_points.restype = C.c_bool
     if hasattr(L, "sgm_set_temporal"):        # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_temporal_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t] + [C.c_void_p] * 5
         L.sgm_temporal_filter.restype = C.c_bool
@@ -1144,6 +1177,23 @@ class SGMInstance(_StageReader):
         value = np.array([fill]).astype(np.dtype(dtype))
         return bool(self.lib.sgm_register_gather(self.handle, C.byref(src), C.byref(dst), d_source, value.itemsize, d_map,
                                                  value.ctypes.data, d_out))
+
+    # ---- depth fused into a TSDF volume (include/sgm_mi355x.h, sgm_volume_spec); device pointers as ints, None = NULL ----
+    def volume_integrate(self, spec: SGMVolumeSpec, src: SGMCloudSpec, poses, d_disp, d_mask, d_conf, d_voxels: int) -> bool:
+        """sgm_volume_integrate: the kept pixels of src.frames maps fused into the volume at d_voxels (volume_bytes(spec) bytes, all
+        zero when empty).  poses: [frames][12] (or [frames][3][4]) host floats, R row-major then t (world -> camera), read before the
+        call returns.  d_disp None: the final map of the last match.  Asynchronous on `stream`."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1)
+        if poses.size != 12 * src.frames:
+            raise ValueError("volume_integrate: one pose of 12 floats (R row-major, then t) per frame")
+        return bool(self.lib.sgm_volume_integrate(self.handle, C.byref(spec), C.byref(src), poses.ctypes.data, d_disp or None,
+                                                  d_mask or None, d_conf or None, d_voxels))
+
+    def volume_points(self, spec: SGMVolumeSpec, d_voxels: int, min_weight: int, d_points, capacity: int, d_count: int) -> bool:
+        """sgm_volume_points: the zero crossings of the volume as SURFACE_DTYPE records sorted by id into d_points (16-byte aligned,
+        room for `capacity` records; None with capacity 0) and their full number into d_count[0].  Asynchronous on `stream`."""
+        return bool(self.lib.sgm_volume_points(self.handle, C.byref(spec), d_voxels, int(min_weight), d_points or None, int(capacity),
+                                               d_count))
 
     # ---- matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); device pointers as ints, None = NULL ----
     def downscale(self, spec: SGMScaleSpec, d_in: int, d_out: int) -> bool:
