@@ -19,18 +19,14 @@
 // No kernel reads what another workgroup of the same launch writes, nothing waits for another
 // workgroup, and no atomic decides a place: the list is the same on every run.
 //
-// Loads: four pixels per lane (one 16-byte load of the map) where a frame's pixel count and the
-// pointers allow it, else one pixel per lane.  A lane's pixels are consecutive, so raster order is
-// lane-major, then the lane's own pixels: the rank of pixel k of a lane is the number of kept pixels
-// in lower lanes (the sum over k of mbcnt(ballot_k)) plus the kept ones among the lane's first k.
+// Loads: four consecutive pixels per lane (one 16-byte load of the map) where cloud_vector allows
+// it, else one pixel per lane; wave_rank (sgm_cloud_common.hpp) has the rank that follows from it.
 //
 // (this translation unit is compiled with -fno-honor-nans like the others: a caller's map may hold
 // NaN, so "finite" is tested on the bit pattern and NaN is made from bits)
 // ============================================================================================
 
-#define CLOUD_THREADS 256
-#define CLOUD_WAVES (CLOUD_THREADS / 64)
-#define CLOUD_TILE_MAX 2048
+#define CLOUD_THREADS 256                                     // the organised cloud's; the point list's kernels run TILE_THREADS
 #define CLOUD_QNAN 0x7FC00000u
 
 // ---- organised cloud: float [frames][H][W][3] ------------------------------------------------------------------------------
@@ -91,38 +87,28 @@ static __device__ __forceinline__ unsigned cloud_pass(const CloudParams& c, cons
 #pragma unroll
     for (int i = 0; i < V; ++i) {
         const bool keep = cloud_kept(c, d[i], m[i], k[i], Z[i]);
-        const unsigned long long b = __ballot(keep);
-        lower += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        wave_total += (unsigned)__popcll(b);
+        wave_rank(keep, lower, wave_total);
         flags |= keep ? 1u << i : 0u;
     }
     return flags;
 }
 
 template <int V>
-__global__ __launch_bounds__(CLOUD_THREADS) void sgm_cloud_count_k(CloudParams c, CloudTiling t, const float* __restrict__ disp,
-                                                                   const uint8_t* __restrict__ mask,
-                                                                   const uint16_t* __restrict__ conf, unsigned* __restrict__ kept)
+__global__ __launch_bounds__(TILE_THREADS) void sgm_cloud_count_k(CloudParams c, CloudTiling t, const float* __restrict__ disp,
+                                                                  const uint8_t* __restrict__ mask,
+                                                                  const uint16_t* __restrict__ conf, unsigned* __restrict__ kept)
 {
-    __shared__ unsigned s_wave[CLOUD_WAVES];
     const unsigned frame = blockIdx.x / t.tiles_per_frame, first = (blockIdx.x - frame * t.tiles_per_frame) * t.tile;
     const unsigned end = min(first + t.tile, c.npx);
     const size_t frame_base = (size_t)frame * c.npx;
     unsigned total = 0;                                       // of this wave, the same in all of its lanes
-    for (unsigned p = first + threadIdx.x * V; p - threadIdx.x * V < end; p += CLOUD_THREADS * V) {
+    for (unsigned p = first + threadIdx.x * V; p - threadIdx.x * V < end; p += TILE_THREADS * V) {
         float Z[V];
         unsigned lower, wave_total;
         cloud_pass<V>(c, disp, mask, conf, frame_base, p, end, Z, lower, wave_total);
         total += wave_total;
     }
-    if ((threadIdx.x & 63u) == 0) s_wave[threadIdx.x >> 6] = total;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned sum = 0;
-#pragma unroll
-        for (int w = 0; w < CLOUD_WAVES; ++w) sum += s_wave[w];
-        kept[blockIdx.x] = sum;
-    }
+    tile_total(total, kept + blockIdx.x);
 }
 
 // ONE workgroup: base[i] = kept[0] + .. + kept[i - 1]; offsets[f] = base of frame f's first tile, offsets[frames] = the total.
@@ -141,31 +127,21 @@ __global__ __launch_bounds__(SCAN_THREADS) void sgm_cloud_scan_k(const unsigned*
 struct __attribute__((aligned(16))) CloudPoint { float x, y, z; unsigned pixel; };
 
 template <int V>
-__global__ __launch_bounds__(CLOUD_THREADS) void sgm_cloud_emit_k(CloudParams c, CloudTiling t, const float* __restrict__ disp,
-                                                                  const uint8_t* __restrict__ mask,
-                                                                  const uint16_t* __restrict__ conf,
-                                                                  const unsigned* __restrict__ base, CloudPoint* __restrict__ points)
+__global__ __launch_bounds__(TILE_THREADS) void sgm_cloud_emit_k(CloudParams c, CloudTiling t, const float* __restrict__ disp,
+                                                                 const uint8_t* __restrict__ mask,
+                                                                 const uint16_t* __restrict__ conf,
+                                                                 const unsigned* __restrict__ base, CloudPoint* __restrict__ points)
 {
-    __shared__ unsigned s_wave[2][CLOUD_WAVES];
     const unsigned frame = blockIdx.x / t.tiles_per_frame, first = (blockIdx.x - frame * t.tiles_per_frame) * t.tile;
     const unsigned end = min(first + t.tile, c.npx);
     const size_t frame_base = (size_t)frame * c.npx;
-    const unsigned wave = threadIdx.x >> 6;
     size_t run = base[blockIdx.x];                            // where this pass's first kept pixel goes
     unsigned turn = 0;
-    for (unsigned p = first + threadIdx.x * V; p - threadIdx.x * V < end; p += CLOUD_THREADS * V, turn ^= 1u) {
+    for (unsigned p = first + threadIdx.x * V; p - threadIdx.x * V < end; p += TILE_THREADS * V, turn ^= 1u) {
         float Z[V];
-        unsigned lower, wave_total;
+        unsigned lower, wave_total, all;
         const unsigned flags = cloud_pass<V>(c, disp, mask, conf, frame_base, p, end, Z, lower, wave_total);
-        if ((threadIdx.x & 63u) == 0) s_wave[turn][wave] = wave_total;
-        __syncthreads();                                      // (the other half of s_wave is what the previous pass still reads)
-        unsigned before = 0, all = 0;
-#pragma unroll
-        for (unsigned w = 0; w < CLOUD_WAVES; ++w) {
-            const unsigned s = s_wave[turn][w];
-            before += w < wave ? s : 0u;
-            all += s;
-        }
+        const unsigned before = pass_before(wave_total, turn, all);
         if (flags) {
             size_t at = run + before + lower;
             unsigned y = p / c.W, x = p - y * c.W;
@@ -185,34 +161,12 @@ __global__ __launch_bounds__(CLOUD_THREADS) void sgm_cloud_emit_k(CloudParams c,
     }
 }
 
-static CloudParams cloud_params(const sgmd_cloud* c)
+// tiles never span frames: every frame has its own, so that offsets[f] is the base of a tile
+static CloudTiling cloud_tiling(int W, int H)
 {
-    CloudParams p;
-    p.fx = c->fx; p.fy = c->fy; p.cx = c->cx; p.cy = c->cy; p.fb = c->fb; p.doffs = c->doffs; p.z_min = c->z_min; p.z_max = c->z_max;
-    p.min_conf = c->min_conf;
-    p.W = (unsigned)c->W;
-    p.npx = (unsigned)((size_t)c->W * c->H);
-    return p;
-}
-
-static bool cloud_args_ok(const sgmd_cloud* c, const void* disp, const void* out)
-{
-    return c && disp && out && c->W >= 1 && c->H >= 1 && c->W <= 65535 && c->H <= 65535 && c->B >= 1 &&
-           (unsigned long long)c->W * c->H * c->B <= (1ull << 31);
-}
-
-// four pixels per lane: every frame starts at a multiple of four pixels and the three maps can be read 16 / 4 / 8 bytes at a time
-static bool cloud_vector(const sgmd_cloud* c, const void* disp, const void* mask, const void* conf)
-{
-    return ((size_t)c->W * c->H) % 4 == 0 && (uintptr_t)disp % 16 == 0 && (uintptr_t)mask % 4 == 0 && (uintptr_t)conf % 8 == 0;
-}
-
-static CloudTiling cloud_tiling(const sgmd_cloud* c)
-{
-    const size_t npx = (size_t)c->W * c->H;
+    const size_t npx = (size_t)W * H;
     CloudTiling t;
-    t.tile = 1;
-    while (t.tile < CLOUD_TILE_MAX && t.tile < npx) t.tile <<= 1;
+    t.tile = tile_size(npx);
     t.tiles_per_frame = (unsigned)((npx + t.tile - 1) / t.tile);
     return t;
 }
@@ -222,13 +176,12 @@ extern "C" {
 size_t sgmd_cloud_scratch_bytes(int W, int H, int B)
 {
     if (W < 1 || H < 1 || B < 1) return 0;
-    const sgmd_cloud c = {W, H, B, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    return 2 * sizeof(unsigned) * (size_t)cloud_tiling(&c).tiles_per_frame * (size_t)B;      // kept[], base[]
+    return tile_scratch_bytes((size_t)cloud_tiling(W, H).tiles_per_frame * (size_t)B);
 }
 
 int sgmd_cloud_organized(int ord, void* stream, const sgmd_cloud* c, const void* disp, const void* mask, const void* conf, void* xyz)
 {
-    if (!cloud_args_ok(c, disp, xyz)) {
+    if (!cloud_shape_ok(c) || !disp || !xyz) {
         fprintf(stderr, "sgm_mi355x: sgmd_cloud_organized: bad arguments\n");
         return -1;
     }
@@ -248,11 +201,11 @@ int sgmd_cloud_organized(int ord, void* stream, const sgmd_cloud* c, const void*
 int sgmd_cloud_points(int ord, void* stream, const sgmd_cloud* c, const void* disp, const void* mask, const void* conf, void* scratch,
                       void* points, void* offsets)
 {
-    if (!cloud_args_ok(c, disp, points) || !scratch || !offsets || (uintptr_t)points % 16 != 0) {
+    if (!cloud_shape_ok(c) || !disp || !points || !scratch || !offsets || (uintptr_t)points % 16 != 0) {
         fprintf(stderr, "sgm_mi355x: sgmd_cloud_points: bad arguments\n");
         return -1;
     }
-    const CloudTiling t = cloud_tiling(c);
+    const CloudTiling t = cloud_tiling(c->W, c->H);
     const size_t ntiles = (size_t)t.tiles_per_frame * c->B;
     if (ntiles > 0x7FFFFFFFu) {
         fprintf(stderr, "sgm_mi355x: sgmd_cloud_points: %zu tiles are more than one launch takes\n", ntiles);
@@ -260,26 +213,25 @@ int sgmd_cloud_points(int ord, void* stream, const sgmd_cloud* c, const void* di
     }
     HIP_TRY(hipSetDevice(ord));
     const CloudParams p = cloud_params(c);
-    unsigned* kept = (unsigned*)scratch;
-    unsigned* base = kept + ntiles;
+    const TileScratch s = tile_scratch(scratch, ntiles);
     const hipStream_t st = (hipStream_t)stream;
     const bool vec = cloud_vector(c, disp, mask, conf);
     if (vec)
-        hipLaunchKernelGGL(sgm_cloud_count_k<4>, dim3((unsigned)ntiles), dim3(CLOUD_THREADS), 0, st, p, t, (const float*)disp,
-                           (const uint8_t*)mask, (const uint16_t*)conf, kept);
+        hipLaunchKernelGGL(sgm_cloud_count_k<4>, dim3((unsigned)ntiles), dim3(TILE_THREADS), 0, st, p, t, (const float*)disp,
+                           (const uint8_t*)mask, (const uint16_t*)conf, s.kept);
     else
-        hipLaunchKernelGGL(sgm_cloud_count_k<1>, dim3((unsigned)ntiles), dim3(CLOUD_THREADS), 0, st, p, t, (const float*)disp,
-                           (const uint8_t*)mask, (const uint16_t*)conf, kept);
+        hipLaunchKernelGGL(sgm_cloud_count_k<1>, dim3((unsigned)ntiles), dim3(TILE_THREADS), 0, st, p, t, (const float*)disp,
+                           (const uint8_t*)mask, (const uint16_t*)conf, s.kept);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sgm_cloud_scan_k, dim3(1), dim3(SCAN_THREADS), 0, st, (const unsigned*)kept, (unsigned)ntiles, t.tiles_per_frame,
-                       (unsigned)c->B, base, (unsigned*)offsets);
+    hipLaunchKernelGGL(sgm_cloud_scan_k, dim3(1), dim3(SCAN_THREADS), 0, st, (const unsigned*)s.kept, (unsigned)ntiles, t.tiles_per_frame,
+                       (unsigned)c->B, s.base, (unsigned*)offsets);
     HIP_TRY(hipGetLastError());
     if (vec)
-        hipLaunchKernelGGL(sgm_cloud_emit_k<4>, dim3((unsigned)ntiles), dim3(CLOUD_THREADS), 0, st, p, t, (const float*)disp,
-                           (const uint8_t*)mask, (const uint16_t*)conf, (const unsigned*)base, (CloudPoint*)points);
+        hipLaunchKernelGGL(sgm_cloud_emit_k<4>, dim3((unsigned)ntiles), dim3(TILE_THREADS), 0, st, p, t, (const float*)disp,
+                           (const uint8_t*)mask, (const uint16_t*)conf, (const unsigned*)s.base, (CloudPoint*)points);
     else
-        hipLaunchKernelGGL(sgm_cloud_emit_k<1>, dim3((unsigned)ntiles), dim3(CLOUD_THREADS), 0, st, p, t, (const float*)disp,
-                           (const uint8_t*)mask, (const uint16_t*)conf, (const unsigned*)base, (CloudPoint*)points);
+        hipLaunchKernelGGL(sgm_cloud_emit_k<1>, dim3((unsigned)ntiles), dim3(TILE_THREADS), 0, st, p, t, (const float*)disp,
+                           (const uint8_t*)mask, (const uint16_t*)conf, (const unsigned*)s.base, (CloudPoint*)points);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1,7 +1,7 @@
 #pragma once
-// The predicate, the formulas and the load paths of the point clouds (include/sgm_mi355x.h, sgm_cloud_spec), shared by the
-// translation units that turn a disparity map into 3-D points: sgm_cloud.hip, sgm_register.hip and sgm_volume.hip; and the scan of
-// the ordered compactions of sgm_cloud.hip and sgm_volume.hip.  Include after sgm_common.hpp.
+// What sgm_cloud.hip, sgm_register.hip and sgm_volume.hip share.  The source map: the predicate, the formulas and the load paths of
+// the point clouds (include/sgm_mi355x.h, sgm_cloud_spec) and, for the launchers, the one reading of a sgmd_cloud.  The ordered
+// compaction of the point list and the surface list: its device pieces, its tile size and its scratch.  Include after sgm_common.hpp.
 
 struct CloudParams {
     float fx, fy, cx, cy, fb, doffs, z_min, z_max;
@@ -27,7 +27,57 @@ static __device__ __forceinline__ void cloud_xy(const CloudParams& c, unsigned x
     Y = (((float)y - c.cy) * Z) / c.fy;
 }
 
-// The scan of an ordered compaction's three launches (count per tile, scan, emit), for ONE workgroup of SCAN_THREADS:
+// ---- the ordered compaction: count per tile, scan, emit ---------------------------------------------------------------------------
+// A tile is a power-of-two run of at most TILE_MAX items, one workgroup of TILE_THREADS per tile in `count` and `emit`, which pass
+// over it TILE_THREADS lanes at a time.  A lane contributes a few flags per pass (the cloud: its V pixels, the volume: three axes).
+
+#define TILE_THREADS 256
+#define TILE_WAVES (TILE_THREADS / 64)
+#define TILE_MAX 2048
+
+// The wave rank, one flag at a time: adds the kept flags of the lower lanes to `lower` and those of the whole wave to `wave_total`.
+// The rank of a lane's flag k is `lower` after all of its flags plus the kept ones among its first k (raster order is lane-major).
+static __device__ __forceinline__ void wave_rank(bool keep, unsigned& lower, unsigned& wave_total)
+{
+    const unsigned long long b = __ballot(keep);
+    lower += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+    wave_total += (unsigned)__popcll(b);
+}
+
+// The end of `count`: the sum of the waves' totals (each the same in all lanes of its wave) -> *kept, by thread 0.
+static __device__ __forceinline__ void tile_total(unsigned wave_total, unsigned* __restrict__ kept)
+{
+    __shared__ unsigned s_wave[TILE_WAVES];
+    if ((threadIdx.x & 63u) == 0) s_wave[threadIdx.x >> 6] = wave_total;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned sum = 0;
+#pragma unroll
+        for (int w = 0; w < TILE_WAVES; ++w) sum += s_wave[w];
+        *kept = sum;
+    }
+}
+
+// The hand-over of one pass of `emit` (turn: 0, 1, 0, .. over the passes): returns what the lower waves kept in this pass, `all`
+// what the workgroup kept.  One barrier per pass.
+static __device__ __forceinline__ unsigned pass_before(unsigned wave_total, unsigned turn, unsigned& all)
+{
+    __shared__ unsigned s_wave[2][TILE_WAVES];
+    const unsigned wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0) s_wave[turn][wave] = wave_total;
+    __syncthreads();                                          // (the other half of s_wave is what the previous pass still reads)
+    unsigned before = 0;
+    all = 0;
+#pragma unroll
+    for (unsigned w = 0; w < TILE_WAVES; ++w) {
+        const unsigned s = s_wave[turn][w];
+        before += w < wave ? s : 0u;
+        all += s;
+    }
+    return before;
+}
+
+// The scan of the three launches (count per tile, scan, emit), for ONE workgroup of SCAN_THREADS:
 // base[i] = kept[0] + .. + kept[i - 1], at_tile(i, base[i]) for every tile, the total as the result (in every thread).
 // Chunks of 4 * 1024 tiles with a running carry, so any number of tiles works.
 #define SCAN_THREADS 1024
@@ -104,3 +154,40 @@ static __device__ __forceinline__ void cloud_load(const float* __restrict__ disp
         if (conf) k[0] = conf[g];
     }
 }
+
+// ---- the launchers' side ---------------------------------------------------------------------------------------------------------
+// the shapes the kernels take: frame-relative pixel indices and (y << 16) | x fit 32 bits, a launch covers the batch
+static bool cloud_shape_ok(const sgmd_cloud* c)
+{
+    return c && c->W >= 1 && c->H >= 1 && c->W <= 65535 && c->H <= 65535 && c->B >= 1 &&
+           (unsigned long long)c->W * c->H * c->B <= (1ull << 31);
+}
+
+static CloudParams cloud_params(const sgmd_cloud* c)
+{
+    CloudParams p;
+    p.fx = c->fx; p.fy = c->fy; p.cx = c->cx; p.cy = c->cy; p.fb = c->fb; p.doffs = c->doffs; p.z_min = c->z_min; p.z_max = c->z_max;
+    p.min_conf = c->min_conf;
+    p.W = (unsigned)c->W;
+    p.npx = (unsigned)((size_t)c->W * c->H);
+    return p;
+}
+
+// four pixels per lane: every frame starts at a multiple of four pixels and the three maps can be read 16 / 4 / 8 bytes at a time
+static bool cloud_vector(const sgmd_cloud* c, const void* disp, const void* mask, const void* conf)
+{
+    return ((size_t)c->W * c->H) % 4 == 0 && (uintptr_t)disp % 16 == 0 && (uintptr_t)mask % 4 == 0 && (uintptr_t)conf % 8 == 0;
+}
+
+// the tile of a compaction over runs of n items: a power of two, at most TILE_MAX, at least 1
+static unsigned tile_size(size_t n)
+{
+    unsigned tile = 1;
+    while (tile < TILE_MAX && tile < n) tile <<= 1;
+    return tile;
+}
+
+// the scratch of a compaction over ntiles tiles: kept[ntiles], then base[ntiles]
+struct TileScratch { unsigned* kept; unsigned* base; };
+static size_t tile_scratch_bytes(size_t ntiles) { return 2 * sizeof(unsigned) * ntiles; }
+static TileScratch tile_scratch(void* scratch, size_t ntiles) { return {(unsigned*)scratch, (unsigned*)scratch + ntiles}; }

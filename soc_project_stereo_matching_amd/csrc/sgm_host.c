@@ -2108,12 +2108,52 @@ static bool cloud_available(void) { return sgmd_cloud_scratch_bytes != NULL && s
 
 static bool finite_positive(float v) { return isfinite(v) && v > 0.0f; }
 
+/* ---- what the entry points that read a map share (clouds, registration, volume; the scale spec and the temporal filter in part) */
+
+/* a frame the kernels take, (y << 16) | x naming its pixels, and at most 2^31 pixels in `frames` of them */
+static bool frame_size_valid(int width, int height, long long frames)
+{
+    return width >= 1 && width <= 65535 && height >= 1 && height <= 65535 && frames * width * height <= (1LL << 31);
+}
+
+static bool aligned_to(const void* p, size_t bytes) { return (uintptr_t)p % bytes == 0; }
+
+static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    return a && b && (uintptr_t)a < (uintptr_t)b + b_bytes && (uintptr_t)b < (uintptr_t)a + a_bytes;
+}
+
+/* The map `entry` reads: the caller's, or (d_disp == NULL) the reference-view final map of the last match, where stage 8 finds it --
+ * of an initialised instance that is not row-tiled and whose frames are the spec's.  NULL, with a line on stderr, where there is none. */
+static const float* source_map(sgm_instance* s, const sgmd_cloud* c, const float* d_disp, const char* entry)
+{
+    if (d_disp) return d_disp;
+    const float* last = s->initialized ? (const float*)(s->last_both ? s->d_both_maps.p : s->d_disp.p) : NULL;
+    if (!last)
+        fprintf(stderr, "sgm_mi355x: %s: no map given and no match to take one from\n", entry);
+    else if (row_tiled(s))
+        fprintf(stderr, "sgm_mi355x: %s: the map of a row tile is the caller's: pass it explicitly\n", entry);
+    else if (c->W != s->g.W || c->H != s->g.H || c->B != s->g.B)
+        fprintf(stderr, "sgm_mi355x: %s: the source spec is for %d frames of %dx%d, the instance's last match for %d of %dx%d\n", entry,
+                c->B, c->W, c->H, s->g.B, s->g.W, s->g.H);
+    else
+        return last;
+    return NULL;
+}
+
+/* The scratch `what` of an entry point that works on the last match's result (b == NULL: none), then its place in the queue: behind
+ * that result, which may come from a stream of its own (sgm_set_overlap_post / _stage_cus).  The scratch first: growing it drains
+ * the streams, since an earlier call may still be using it. */
+static bool scratch_then_wait(sgm_instance* s, sgm_buf* b, size_t bytes, const char* what)
+{
+    if (b && !reserve(s, b, bytes, 0)) FAIL("device allocation failed for %s (%zu bytes)", what, bytes);
+    return wait_for_result(s, s->stream) == 0;
+}
+
 /* the spec as the kernels take it; false for anything outside the ranges of include/sgm_mi355x.h */
 static bool cloud_spec_valid(const sgm_cloud_spec* sp, sgmd_cloud* c)
 {
-    if (sp->width < 1 || sp->width > 65535 || sp->height < 1 || sp->height > 65535 || sp->frames < 1 ||
-        (long long)sp->frames * sp->width * sp->height > (1LL << 31))
-        return false;
+    if (sp->frames < 1 || !frame_size_valid(sp->width, sp->height, sp->frames)) return false;
     const float fb = (float)((double)sp->fx * (double)sp->baseline);
     if (!finite_positive(sp->fx) || !finite_positive(sp->fy) || !finite_positive(sp->baseline) || !finite_positive(fb)) return false;
     if (!isfinite(sp->cx) || !isfinite(sp->cy) || !isfinite(sp->doffs)) return false;
@@ -2122,19 +2162,13 @@ static bool cloud_spec_valid(const sgm_cloud_spec* sp, sgmd_cloud* c)
     return true;
 }
 
-/* What both device forms check before they queue anything; *disp: the map to read -- the caller's, or (NULL) the reference-view
- * final map of the last match, where stage 8 finds it */
-static bool cloud_ready(sgm_instance* s, const sgm_cloud_spec* spec, const void* out, sgmd_cloud* c, const float** disp)
+/* What the cloud entry points check before they queue anything; *disp: the map to read (source_map) */
+static bool cloud_ready(sgm_instance* s, const sgm_cloud_spec* spec, const void* out, sgmd_cloud* c, const float** disp, const char* entry)
 {
     if (!s || !spec || !out) return false;
     if (!cloud_available()) FAIL("the point clouds are not part of this build");
     if (!cloud_spec_valid(spec, c)) return false;
-    if (*disp) return true;
-    if (!s->initialized) return false;
-    if (row_tiled(s)) FAIL("the map of a row tile is the caller's: pass it to the cloud entry points explicitly");
-    if (c->W != s->g.W || c->H != s->g.H || c->B != s->g.B)
-        FAIL("the cloud spec is for %d frames of %dx%d, the instance's last match for %d of %dx%d", c->B, c->W, c->H, s->g.B, s->g.W, s->g.H);
-    *disp = (const float*)(s->last_both ? s->d_both_maps.p : s->d_disp.p);
+    *disp = source_map(s, c, *disp, entry);
     return *disp != NULL;
 }
 
@@ -2142,7 +2176,7 @@ bool sgm_cloud_organized(sgm_instance* s, const sgm_cloud_spec* spec, const floa
                          const uint16_t* d_conf, float* d_xyz)
 {
     sgmd_cloud c;
-    if (!cloud_ready(s, spec, d_xyz, &c, &d_disp)) return false;
+    if (!cloud_ready(s, spec, d_xyz, &c, &d_disp, "sgm_cloud_organized")) return false;
     /* the map may be the result of a match whose last stages run on a stream of their own (sgm_set_overlap_post / _stage_cus) */
     if (wait_for_result(s, s->stream) != 0) return false;
     return sgmd_cloud_organized(s->device, s->stream, &c, d_disp, d_mask, d_conf, d_xyz) == 0;
@@ -2152,10 +2186,7 @@ bool sgm_cloud_organized(sgm_instance* s, const sgm_cloud_spec* spec, const floa
 static bool cloud_points_queue(sgm_instance* s, const sgmd_cloud* c, const float* d_disp, const uint8_t* d_mask, const uint16_t* d_conf,
                                void* d_points, void* d_offsets)
 {
-    /* (growing the scratch drains the streams first: an earlier list may still be using it) */
-    if (!reserve(s, &s->d_cloud_scratch, sgmd_cloud_scratch_bytes(c->W, c->H, c->B), 0))
-        FAIL("device allocation failed for the point list of %d frames of %dx%d", c->B, c->W, c->H);
-    if (wait_for_result(s, s->stream) != 0) return false;
+    if (!scratch_then_wait(s, &s->d_cloud_scratch, sgmd_cloud_scratch_bytes(c->W, c->H, c->B), "the point list's tiles")) return false;
     return sgmd_cloud_points(s->device, s->stream, c, d_disp, d_mask, d_conf, s->d_cloud_scratch.p, d_points, d_offsets) == 0;
 }
 
@@ -2163,7 +2194,7 @@ bool sgm_cloud_points(sgm_instance* s, const sgm_cloud_spec* spec, const float* 
                       const uint16_t* d_conf, sgm_point* d_points, uint32_t* d_offsets)
 {
     sgmd_cloud c;
-    if (!d_offsets || (uintptr_t)d_points % sizeof(sgm_point) != 0 || !cloud_ready(s, spec, d_points, &c, &d_disp)) return false;
+    if (!d_offsets || !aligned_to(d_points, sizeof(sgm_point)) || !cloud_ready(s, spec, d_points, &c, &d_disp, "sgm_cloud_points")) return false;
     return cloud_points_queue(s, &c, d_disp, d_mask, d_conf, d_points, d_offsets);
 }
 
@@ -2171,7 +2202,7 @@ bool sgm_read_cloud(sgm_instance* s, const sgm_cloud_spec* spec, sgm_point* poin
 {
     sgmd_cloud c;
     const float* d_disp = NULL;
-    if (!offsets || (!points && capacity) || !cloud_ready(s, spec, offsets, &c, &d_disp)) return false;
+    if (!offsets || (!points && capacity) || !cloud_ready(s, spec, offsets, &c, &d_disp, "sgm_read_cloud")) return false;
     if (!sgm_match_wait(s)) return false;
     const size_t px = (size_t)c.B * c.W * c.H, off_bytes = ((size_t)c.B + 1) * sizeof(uint32_t);
     const buf_request bufs[] = {{&s->d_cloud_points, px * sizeof(sgm_point), 0}, {&s->d_cloud_offsets, off_bytes, 0}};
@@ -2195,9 +2226,7 @@ static bool register_available(void) { return sgmd_register_scratch_bytes != NUL
 /* the target as the kernels take it; false for anything outside the ranges of include/sgm_mi355x.h */
 static bool register_spec_valid(const sgm_register_spec* sp, int frames, sgmd_register* r)
 {
-    if (sp->width < 1 || sp->width > 65535 || sp->height < 1 || sp->height > 65535 ||
-        (long long)frames * sp->width * sp->height > (1LL << 31))
-        return false;
+    if (!frame_size_valid(sp->width, sp->height, frames)) return false;
     if (!finite_positive(sp->fx) || !finite_positive(sp->fy) || !isfinite(sp->cx) || !isfinite(sp->cy)) return false;
     for (int i = 0; i < 5; ++i) if (!isfinite(sp->dist[i])) return false;
     for (int i = 0; i < 9; ++i) if (!isfinite(sp->R[i])) return false;
@@ -2223,11 +2252,6 @@ static bool register_specs(sgm_instance* s, const sgm_cloud_spec* src, const sgm
     return true;
 }
 
-static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    return a && b && (uintptr_t)a < (uintptr_t)b + b_bytes && (uintptr_t)b < (uintptr_t)a + a_bytes;
-}
-
 bool sgm_register_depth(sgm_instance* s, const sgm_cloud_spec* src, const sgm_register_spec* dst, const float* d_disp,
                         const uint8_t* d_mask, const uint16_t* d_conf, float* d_depth, uint32_t* d_source)
 {
@@ -2235,26 +2259,16 @@ bool sgm_register_depth(sgm_instance* s, const sgm_cloud_spec* src, const sgm_re
     sgmd_register r;
     if (!register_specs(s, src, dst, &c, &r)) return false;
     if (!d_depth) FAIL("sgm_register_depth: NULL output");
-    if ((uintptr_t)d_disp % sizeof(float) != 0 || (uintptr_t)d_conf % sizeof(uint16_t) != 0 || (uintptr_t)d_depth % sizeof(float) != 0 ||
-        (uintptr_t)d_source % sizeof(uint32_t) != 0)
+    if (!aligned_to(d_disp, sizeof(float)) || !aligned_to(d_conf, sizeof(uint16_t)) || !aligned_to(d_depth, sizeof(float)) ||
+        !aligned_to(d_source, sizeof(uint32_t)))
         FAIL("sgm_register_depth: a pointer is not aligned to its element");
-    if (!d_disp) {                                               /* the cloud entry points' rules */
-        if (!s->initialized) FAIL("sgm_register_depth: no map given and no match to take one from");
-        if (row_tiled(s)) FAIL("the map of a row tile is the caller's: pass it to sgm_register_depth explicitly");
-        if (c.W != s->g.W || c.H != s->g.H || c.B != s->g.B)
-            FAIL("the source spec is for %d frames of %dx%d, the instance's last match for %d of %dx%d", c.B, c.W, c.H, s->g.B, s->g.W, s->g.H);
-        d_disp = (const float*)(s->last_both ? s->d_both_maps.p : s->d_disp.p);
-        if (!d_disp) FAIL("sgm_register_depth: no map given and no match to take one from");
-    }
+    d_disp = source_map(s, &c, d_disp, "sgm_register_depth");
+    if (!d_disp) return false;
     const size_t in_bytes = (size_t)c.B * c.W * c.H * sizeof(float), out_bytes = (size_t)c.B * r.W * r.H * sizeof(float);
     if (ranges_overlap(d_depth, out_bytes, d_disp, in_bytes) || ranges_overlap(d_source, out_bytes, d_disp, in_bytes) ||
         ranges_overlap(d_depth, out_bytes, d_source, out_bytes))
         FAIL("sgm_register_depth: an output aliases the map or the other output");
-    /* (growing the scratch drains the streams first: an earlier registration may still be using it) */
-    if (!reserve(s, &s->d_register_keys, sgmd_register_scratch_bytes(r.W, r.H, c.B), 0))
-        FAIL("device allocation failed for the z-buffer of %d frames of %dx%d", c.B, r.W, r.H);
-    /* the map may be the result of a match whose last stages run on a stream of their own (sgm_set_overlap_post / _stage_cus) */
-    if (wait_for_result(s, s->stream) != 0) return false;
+    if (!scratch_then_wait(s, &s->d_register_keys, sgmd_register_scratch_bytes(r.W, r.H, c.B), "the z-buffer")) return false;
     return sgmd_register_depth(s->device, s->stream, &c, &r, d_disp, d_mask, d_conf, s->d_register_keys.p, d_depth, d_source) == 0;
 }
 
@@ -2266,7 +2280,7 @@ bool sgm_register_gather(sgm_instance* s, const sgm_cloud_spec* src, const sgm_r
     if (!register_specs(s, src, dst, &c, &r)) return false;
     if (!d_source || !d_map || !fill || !d_out) FAIL("sgm_register_gather: NULL argument");
     if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4) FAIL("sgm_register_gather: elements of %d bytes (1, 2 or 4)", elem_bytes);
-    if ((uintptr_t)d_source % sizeof(uint32_t) != 0 || (uintptr_t)d_map % (size_t)elem_bytes != 0 || (uintptr_t)d_out % (size_t)elem_bytes != 0)
+    if (!aligned_to(d_source, sizeof(uint32_t)) || !aligned_to(d_map, (size_t)elem_bytes) || !aligned_to(d_out, (size_t)elem_bytes))
         FAIL("sgm_register_gather: a pointer is not aligned to its element");
     const size_t in_bytes = (size_t)c.B * c.W * c.H * (size_t)elem_bytes, px = (size_t)c.B * r.W * r.H;
     if (ranges_overlap(d_out, px * (size_t)elem_bytes, d_map, in_bytes) || ranges_overlap(d_out, px * (size_t)elem_bytes, d_source, px * 4))
@@ -2280,7 +2294,8 @@ bool sgm_register_gather(sgm_instance* s, const sgm_cloud_spec* src, const sgm_r
 bool sgm_register_spec_raw(const double K[9], const double dist[5], const double R[9], int width, int height, int splat,
                            sgm_register_spec* out)
 {
-    if (!K || !dist || !R || !out || width < 1 || width > 65535 || height < 1 || height > 65535 || (splat != 1 && splat != 2)) return false;
+    /* (frames 0: a target has no pixel count until a call brings the frames) */
+    if (!K || !dist || !R || !out || !frame_size_valid(width, height, 0) || (splat != 1 && splat != 2)) return false;
     for (int i = 0; i < 9; ++i) if (!isfinite(K[i]) || !isfinite(R[i])) return false;
     for (int i = 0; i < 5; ++i) if (!isfinite(dist[i])) return false;
     memset(out, 0, sizeof *out);
@@ -2335,16 +2350,10 @@ bool sgm_volume_integrate(sgm_instance* s, const sgm_volume_spec* spec, const sg
     if (c.B > VOLUME_MAX_FRAMES) FAIL("sgm_volume_integrate: %d frames in one call (at most %d)", c.B, VOLUME_MAX_FRAMES);
     for (int i = 0; i < 12 * c.B; ++i)
         if (!isfinite(poses[i])) FAIL("sgm_volume_integrate: entry %d of the pose of frame %d is not finite", i % 12, i / 12);
-    if ((uintptr_t)d_disp % sizeof(float) != 0 || (uintptr_t)d_conf % sizeof(uint16_t) != 0 || (uintptr_t)d_voxels % sizeof(uint32_t) != 0)
+    if (!aligned_to(d_disp, sizeof(float)) || !aligned_to(d_conf, sizeof(uint16_t)) || !aligned_to(d_voxels, sizeof(uint32_t)))
         FAIL("sgm_volume_integrate: a pointer is not aligned to its element");
-    if (!d_disp) {                                               /* the cloud entry points' rules */
-        if (!s->initialized) FAIL("sgm_volume_integrate: no map given and no match to take one from");
-        if (row_tiled(s)) FAIL("the map of a row tile is the caller's: pass it to sgm_volume_integrate explicitly");
-        if (c.W != s->g.W || c.H != s->g.H || c.B != s->g.B)
-            FAIL("the source spec is for %d frames of %dx%d, the instance's last match for %d of %dx%d", c.B, c.W, c.H, s->g.B, s->g.W, s->g.H);
-        d_disp = (const float*)(s->last_both ? s->d_both_maps.p : s->d_disp.p);
-        if (!d_disp) FAIL("sgm_volume_integrate: no map given and no match to take one from");
-    }
+    d_disp = source_map(s, &c, d_disp, "sgm_volume_integrate");
+    if (!d_disp) return false;
     const size_t px = (size_t)c.B * c.W * c.H, vol_bytes = (size_t)v.nx * v.ny * v.nz * sizeof(uint32_t);
     if (ranges_overlap(d_voxels, vol_bytes, d_disp, px * sizeof(float)) || ranges_overlap(d_voxels, vol_bytes, d_mask, px) ||
         ranges_overlap(d_voxels, vol_bytes, d_conf, px * sizeof(uint16_t)))
@@ -2362,8 +2371,7 @@ bool sgm_volume_points(sgm_instance* s, const sgm_volume_spec* spec, const uint3
     if (!volume_available()) FAIL("the volume is not part of this build");
     if (!volume_spec_valid(spec, &v)) FAIL("sgm_volume_points: the volume spec is outside its ranges");
     if (min_weight < 1u || min_weight > 65535u) FAIL("sgm_volume_points: a min_weight of %u (1..65535)", min_weight);
-    if ((uintptr_t)d_voxels % sizeof(uint32_t) != 0 || (uintptr_t)d_points % sizeof(sgm_surface_point) != 0 ||
-        (uintptr_t)d_count % sizeof(uint32_t) != 0)
+    if (!aligned_to(d_voxels, sizeof(uint32_t)) || !aligned_to(d_points, sizeof(sgm_surface_point)) || !aligned_to(d_count, sizeof(uint32_t)))
         FAIL("sgm_volume_points: a pointer is not aligned (the points to 16 bytes, the others to their element)");
     const size_t n = (size_t)v.nx * v.ny * v.nz, vol_bytes = n * sizeof(uint32_t);
     /* (no more than three crossings per voxel can be written, whatever the capacity says) */
@@ -2371,10 +2379,7 @@ bool sgm_volume_points(sgm_instance* s, const sgm_volume_spec* spec, const uint3
     if (ranges_overlap(d_points, pts_bytes, d_voxels, vol_bytes) || ranges_overlap(d_count, sizeof(uint32_t), d_voxels, vol_bytes) ||
         ranges_overlap(d_count, sizeof(uint32_t), d_points, pts_bytes))
         FAIL("sgm_volume_points: an output aliases the volume or the other output");
-    /* (growing the scratch drains the streams first: an earlier list may still be using it) */
-    if (!reserve(s, &s->d_volume_scratch, sgmd_volume_scratch_bytes(v.nx, v.ny, v.nz), 0))
-        FAIL("device allocation failed for the surface list of %dx%dx%d voxels", v.nx, v.ny, v.nz);
-    if (wait_for_result(s, s->stream) != 0) return false;
+    if (!scratch_then_wait(s, &s->d_volume_scratch, sgmd_volume_scratch_bytes(v.nx, v.ny, v.nz), "the surface list's tiles")) return false;
     return sgmd_volume_points(s->device, s->stream, &v, d_voxels, min_weight, s->d_volume_scratch.p, d_points, capacity, d_count) == 0;
 }
 
@@ -2388,9 +2393,7 @@ static bool scale_available(void) { return sgmd_downscale != NULL && sgmd_upscal
 /* the spec as the kernels take it; false for anything outside the ranges of include/sgm_mi355x.h */
 static bool scale_spec_valid(const sgm_scale_spec* sp, sgmd_scale* c)
 {
-    if (!sp || sp->width < 1 || sp->width > 65535 || sp->height < 1 || sp->height > 65535 || sp->frames < 1 || sp->frames > 65535 ||
-        (long long)sp->frames * sp->width * sp->height > (1LL << 31))
-        return false;
+    if (!sp || sp->frames < 1 || sp->frames > 65535 || !frame_size_valid(sp->width, sp->height, sp->frames)) return false;
     if ((sp->factor != 2 && sp->factor != 4) || sp->width / sp->factor < 1 || sp->height / sp->factor < 1) return false;
     if (sp->bits < 8 || sp->bits > 16 || sp->radius > 4 || sp->penalty < 0 || sp->penalty > 16) return false;
     if (sp->d_lo < 0 || sp->d_lo > sp->d_hi || sp->d_hi > 65535) return false;
@@ -2555,13 +2558,11 @@ bool sgm_temporal_filter(sgm_instance* s, const sgm_temporal_spec* spec, size_t 
     if (!temporal_spec_valid(spec, false, &c)) FAIL("the temporal spec is outside its ranges (include/sgm_mi355x.h, sgm_temporal_spec)");
     if (!temporal_geometry_ok(streams, steps, pixels))
         FAIL("sgm_temporal_filter: streams, steps and pixels must be at least 1 and their product at most 2^31");
-    if ((((uintptr_t)d_maps | (uintptr_t)d_hist_value | (uintptr_t)d_stats) & 3u) || ((uintptr_t)d_conf & 1u))
+    if (!aligned_to(d_maps, 4) || !aligned_to(d_hist_value, 4) || !aligned_to(d_stats, 4) || !aligned_to(d_conf, 2))
         FAIL("the maps, history values and counters of sgm_temporal_filter must be 4-byte aligned, the confidence 2-byte aligned");
-    /* (growing the scratch drains the streams first: an earlier call may still be using it) */
-    if (d_stats && !reserve(s, &s->d_tp_scratch, sgmd_temporal_scratch_bytes(), 0)) FAIL("device allocation failed for the counters' scratch");
-    /* the maps may be the result of a match whose last stages run on a stream of their own (sgm_set_overlap_post / _stage_cus); the
-     * scratch is shared with the matches' filter, which a later match queues behind everything queued here */
-    if (wait_for_result(s, s->stream) != 0) return false;
+    /* (the scratch is shared with the matches' filter, which a later match queues behind everything queued here) */
+    if (!scratch_then_wait(s, d_stats ? &s->d_tp_scratch : NULL, d_stats ? sgmd_temporal_scratch_bytes() : 0, "the counters' scratch"))
+        return false;
     if (sgmd_temporal(s->device, s->stream, &c, streams, steps, pixels, d_maps, d_conf, d_hist_value, d_hist_bits, d_stats,
                       d_stats ? s->d_tp_scratch.p : NULL) != 0)
         FAIL("a kernel launch failed");

@@ -157,20 +157,10 @@ __global__ __launch_bounds__(REG_THREADS) void sgm_register_gather_k(size_t n, u
     out[g] = (s != REG_NONE && y < H && x < W) ? map[frame * npx + (size_t)y * W + x] : fill;
 }
 
-static CloudParams register_cloud_params(const sgmd_cloud* c)
-{
-    CloudParams p;
-    p.fx = c->fx; p.fy = c->fy; p.cx = c->cx; p.cy = c->cy; p.fb = c->fb; p.doffs = c->doffs; p.z_min = c->z_min; p.z_max = c->z_max;
-    p.min_conf = c->min_conf;
-    p.W = (unsigned)c->W;
-    p.npx = (unsigned)((size_t)c->W * c->H);
-    return p;
-}
-
+// the source's shape (cloud_shape_ok) and the target's own: its size, the batch's pixels in it, its splat
 static bool register_shapes_ok(const sgmd_cloud* c, const sgmd_register* r)
 {
-    return c && r && c->W >= 1 && c->H >= 1 && c->W <= 65535 && c->H <= 65535 && c->B >= 1 &&
-           (unsigned long long)c->W * c->H * c->B <= (1ull << 31) && r->W >= 1 && r->H >= 1 && r->W <= 65535 && r->H <= 65535 &&
+    return cloud_shape_ok(c) && r && r->W >= 1 && r->H >= 1 && r->W <= 65535 && r->H <= 65535 &&
            (unsigned long long)r->W * r->H * c->B <= (1ull << 31) && (r->splat == 1 || r->splat == 2);
 }
 
@@ -196,7 +186,7 @@ int sgmd_register_depth(int ord, void* stream, const sgmd_cloud* c, const sgmd_r
     HIP_TRY(hipSetDevice(ord));
     const hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)c->W * c->H * c->B, nk = (size_t)r->W * r->H * c->B, n2 = (nk + 1) / 2;
-    const CloudParams p = register_cloud_params(c);
+    const CloudParams p = cloud_params(c);
     RegisterParams q;
     q.fx = r->fx; q.fy = r->fy; q.cx = r->cx; q.cy = r->cy;
     q.k1 = r->dist[0]; q.k2 = r->dist[1]; q.p1 = r->dist[2]; q.p2 = r->dist[3]; q.k3 = r->dist[4];
@@ -209,8 +199,7 @@ int sgmd_register_depth(int ord, void* stream, const sgmd_cloud* c, const sgmd_r
     q.splat = r->splat;
     hipLaunchKernelGGL(sgm_register_clear_k, dim3(register_blocks(n2)), dim3(REG_THREADS), 0, st, (uint4*)keys, n2);
     HIP_TRY(hipGetLastError());
-    // the cloud's rule: every frame starts at a multiple of four pixels and the three maps can be read 16 / 4 / 8 bytes at a time
-    if (((size_t)c->W * c->H) % 4 == 0 && (uintptr_t)disp % 16 == 0 && (uintptr_t)mask % 4 == 0 && (uintptr_t)conf % 8 == 0)
+    if (cloud_vector(c, disp, mask, conf))
         hipLaunchKernelGGL(sgm_register_scatter_k<4>, dim3(register_blocks(n / 4)), dim3(REG_THREADS), 0, st, p, q, n, (const float*)disp,
                            (const uint8_t*)mask, (const uint16_t*)conf, (reg_key*)keys);
     else

@@ -21,9 +21,7 @@
 // comparison)
 // ============================================================================================
 
-#define VOL_THREADS 256
-#define VOL_WAVES (VOL_THREADS / 64)
-#define VOL_TILE_MAX 2048
+#define VOL_THREADS 256                                       // the integration's; the surface list's kernels run TILE_THREADS
 #define VOL_MAX_FRAMES 64
 // SGM_VOLUME_VEC (make VOL_VEC=0): 0 sends every volume down the one-voxel-per-lane path -- the measurement of NOTES.md section 31
 #ifndef SGM_VOLUME_VEC
@@ -159,34 +157,22 @@ static __device__ __forceinline__ unsigned volume_pass(const VolumeParams& v, co
     }
     lower = wave_total = 0;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const unsigned long long b = __ballot((flags >> a) & 1u);
-        lower += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        wave_total += (unsigned)__popcll(b);
-    }
+    for (int a = 0; a < 3; ++a) wave_rank((flags >> a) & 1u, lower, wave_total);
     return flags;
 }
 
-__global__ __launch_bounds__(VOL_THREADS) void sgm_volume_count_k(VolumeParams v, unsigned tile, unsigned min_weight,
-                                                                  const unsigned* __restrict__ voxels, unsigned* __restrict__ kept)
+__global__ __launch_bounds__(TILE_THREADS) void sgm_volume_count_k(VolumeParams v, unsigned tile, unsigned min_weight,
+                                                                   const unsigned* __restrict__ voxels, unsigned* __restrict__ kept)
 {
-    __shared__ unsigned s_wave[VOL_WAVES];
     const unsigned first = blockIdx.x * tile, end = min(first + tile, v.n);
     unsigned total = 0;                                       // of this wave, the same in all of its lanes
-    for (unsigned p = first + threadIdx.x; p - threadIdx.x < end; p += VOL_THREADS) {
+    for (unsigned p = first + threadIdx.x; p - threadIdx.x < end; p += TILE_THREADS) {
         unsigned at[3], lower, wave_total;
         int tn, tm[3];
         volume_pass(v, voxels, min_weight, p, p < end, at, tn, tm, lower, wave_total);
         total += wave_total;
     }
-    if ((threadIdx.x & 63u) == 0) s_wave[threadIdx.x >> 6] = total;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned sum = 0;
-#pragma unroll
-        for (int w = 0; w < VOL_WAVES; ++w) sum += s_wave[w];
-        kept[blockIdx.x] = sum;
-    }
+    tile_total(total, kept + blockIdx.x);
 }
 
 // ONE workgroup: base[i] = kept[0] + .. + kept[i - 1]; count[0] = the total
@@ -199,28 +185,18 @@ __global__ __launch_bounds__(SCAN_THREADS) void sgm_volume_scan_k(const unsigned
 
 struct __attribute__((aligned(16))) SurfacePoint { float x, y, z; unsigned id; };
 
-__global__ __launch_bounds__(VOL_THREADS) void sgm_volume_emit_k(VolumeParams v, unsigned tile, unsigned min_weight,
-                                                                 const unsigned* __restrict__ voxels, const unsigned* __restrict__ base,
-                                                                 SurfacePoint* __restrict__ points, size_t capacity)
+__global__ __launch_bounds__(TILE_THREADS) void sgm_volume_emit_k(VolumeParams v, unsigned tile, unsigned min_weight,
+                                                                  const unsigned* __restrict__ voxels, const unsigned* __restrict__ base,
+                                                                  SurfacePoint* __restrict__ points, size_t capacity)
 {
-    __shared__ unsigned s_wave[2][VOL_WAVES];
     const unsigned first = blockIdx.x * tile, end = min(first + tile, v.n);
-    const unsigned wave = threadIdx.x >> 6;
     size_t run = base[blockIdx.x];                            // where this pass's first record goes
     unsigned turn = 0;
-    for (unsigned p = first + threadIdx.x; p - threadIdx.x < end; p += VOL_THREADS, turn ^= 1u) {
-        unsigned at[3], lower, wave_total;
+    for (unsigned p = first + threadIdx.x; p - threadIdx.x < end; p += TILE_THREADS, turn ^= 1u) {
+        unsigned at[3], lower, wave_total, all;
         int tn, tm[3];
         const unsigned flags = volume_pass(v, voxels, min_weight, p, p < end, at, tn, tm, lower, wave_total);
-        if ((threadIdx.x & 63u) == 0) s_wave[turn][wave] = wave_total;
-        __syncthreads();                                      // (the other half of s_wave is what the previous pass still reads)
-        unsigned before = 0, all = 0;
-#pragma unroll
-        for (unsigned w = 0; w < VOL_WAVES; ++w) {
-            const unsigned s = s_wave[turn][w];
-            before += w < wave ? s : 0u;
-            all += s;
-        }
+        const unsigned before = pass_before(wave_total, turn, all);
         if (flags) {
             size_t to = run + before + lower;
             const float centre[3] = {volume_centre(v.ox, at[0], v.voxel), volume_centre(v.oy, at[1], v.voxel),
@@ -260,39 +236,27 @@ static VolumeParams volume_params(const sgmd_volume* v)
     return p;
 }
 
-// a tile: a power-of-two run of at most 2048 voxels
-static unsigned volume_tile(size_t n)
-{
-    unsigned tile = 1;
-    while (tile < VOL_TILE_MAX && tile < n) tile <<= 1;
-    return tile;
-}
-
 extern "C" {
 
+// (whole tiles of TILE_MAX voxels: sgmd_volume_points takes a smaller tile only where there is one tile)
 size_t sgmd_volume_scratch_bytes(int nx, int ny, int nz)
 {
     if (nx < 1 || ny < 1 || nz < 1) return 0;
     const size_t n = (size_t)nx * ny * nz;
-    return 2 * sizeof(unsigned) * ((n + VOL_TILE_MAX - 1) / VOL_TILE_MAX);      // kept[], base[]
+    return tile_scratch_bytes((n + TILE_MAX - 1) / TILE_MAX);
 }
 
 int sgmd_volume_integrate(int ord, void* stream, const sgmd_volume* v, const sgmd_cloud* c, const float* poses, const void* disp,
                           const void* mask, const void* conf, void* voxels)
 {
-    if (!volume_ok(v) || !c || !poses || !disp || !voxels || c->W < 1 || c->H < 1 || c->W > 65535 || c->H > 65535 || c->B < 1 ||
-        c->B > VOL_MAX_FRAMES || (unsigned long long)c->W * c->H * c->B > (1ull << 31) || (uintptr_t)voxels % 4 != 0 ||
+    if (!volume_ok(v) || !cloud_shape_ok(c) || !poses || !disp || !voxels || c->B > VOL_MAX_FRAMES || (uintptr_t)voxels % 4 != 0 ||
         (uintptr_t)disp % 4 != 0 || (uintptr_t)conf % 2 != 0) {
         fprintf(stderr, "sgm_mi355x: sgmd_volume_integrate: bad arguments\n");
         return -1;
     }
     HIP_TRY(hipSetDevice(ord));
     const VolumeParams p = volume_params(v);
-    CloudParams q;
-    q.fx = c->fx; q.fy = c->fy; q.cx = c->cx; q.cy = c->cy; q.fb = c->fb; q.doffs = c->doffs; q.z_min = c->z_min; q.z_max = c->z_max;
-    q.min_conf = c->min_conf;
-    q.W = (unsigned)c->W;
-    q.npx = (unsigned)((size_t)c->W * c->H);
+    const CloudParams q = cloud_params(c);
     VolumeSource s;
     s.wf = (float)c->W; s.hf = (float)c->H;
     s.frames = (unsigned)c->B;
@@ -320,17 +284,16 @@ int sgmd_volume_points(int ord, void* stream, const sgmd_volume* v, const void* 
     }
     HIP_TRY(hipSetDevice(ord));
     const VolumeParams p = volume_params(v);
-    const unsigned tile = volume_tile(p.n), ntiles = (p.n + tile - 1) / tile;
-    unsigned* kept = (unsigned*)scratch;
-    unsigned* base = kept + ntiles;
+    const unsigned tile = tile_size(p.n), ntiles = (p.n + tile - 1) / tile;
+    const TileScratch s = tile_scratch(scratch, ntiles);
     const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sgm_volume_count_k, dim3(ntiles), dim3(VOL_THREADS), 0, st, p, tile, min_weight, (const unsigned*)voxels, kept);
+    hipLaunchKernelGGL(sgm_volume_count_k, dim3(ntiles), dim3(TILE_THREADS), 0, st, p, tile, min_weight, (const unsigned*)voxels, s.kept);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sgm_volume_scan_k, dim3(1), dim3(SCAN_THREADS), 0, st, (const unsigned*)kept, ntiles, base, (unsigned*)count);
+    hipLaunchKernelGGL(sgm_volume_scan_k, dim3(1), dim3(SCAN_THREADS), 0, st, (const unsigned*)s.kept, ntiles, s.base, (unsigned*)count);
     HIP_TRY(hipGetLastError());
     if (capacity == 0) return 0;                              // the count is all that was asked for
-    hipLaunchKernelGGL(sgm_volume_emit_k, dim3(ntiles), dim3(VOL_THREADS), 0, st, p, tile, min_weight, (const unsigned*)voxels,
-                       (const unsigned*)base, (SurfacePoint*)points, capacity);
+    hipLaunchKernelGGL(sgm_volume_emit_k, dim3(ntiles), dim3(TILE_THREADS), 0, st, p, tile, min_weight, (const unsigned*)voxels,
+                       (const unsigned*)s.base, (SurfacePoint*)points, capacity);
     HIP_TRY(hipGetLastError());
     return 0;
 }
