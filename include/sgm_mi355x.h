@@ -610,8 +610,9 @@ bool   sgm_register_spec_raw(const double K[9], const double dist[5], const doub
  * travel as kernel arguments); a non-finite pose entry; a min_weight outside 1..65535; a pointer not aligned as said; a d_voxels
  * that aliases a map (d_points or d_count that alias the volume or each other); a build without the kernels.  The extraction
  * keeps 8 bytes of scratch per tile of 2048 voxels, reserved at its first call: an instance that never calls these entry points
- * allocates and launches exactly what it did before.  Not part of it: ray-casting the volume into a view, meshing,
- * confidence-weighted updates, colour, voxel hashing or a moving volume, estimating the poses, row tiles, sgm_match_planes. */
+ * allocates and launches exactly what it did before.  Not part of it: meshing (ray-casting the volume into a view is
+ * sgm_volume_raycast below), confidence-weighted updates, colour, voxel hashing or a moving volume, estimating the poses, row tiles,
+ * sgm_match_planes. */
 typedef struct {            /* 36 bytes, every field 4 bytes, no padding */
     int32_t  nx, ny, nz;    /* 1..1024 each, nx*ny*nz <= 2^30; voxel n = (k*ny + j)*nx + i, x fastest */
     float    voxel;         /* edge length, units of baseline; finite, > 0 */
@@ -626,6 +627,63 @@ bool   sgm_volume_integrate(sgm_instance* s, const sgm_volume_spec* spec, const 
                             const float* d_disp, const uint8_t* d_mask, const uint16_t* d_conf, uint32_t* d_voxels);
 bool   sgm_volume_points(sgm_instance* s, const sgm_volume_spec* spec, const uint32_t* d_voxels, uint32_t min_weight /* 1..65535 */,
                          sgm_surface_point* d_points /* 16-byte aligned */, size_t capacity, uint32_t* d_count);
+
+/* ---- the TSDF volume ray-cast into depth and normal maps of any view ----
+ * Extension, "parity unpinned by the reference"; defined here and restated by tests/raycast_ref.py.  The third step of spatial
+ * mapping (integrate, extract, render): the fused surface as an image -- the denoised depth of the current frame, a preview from a
+ * virtual viewpoint, the model prediction of frame-to-model tracking.  Takes a volume as sgm_volume_integrate leaves it, a pinhole
+ * view and one world -> camera pose per frame; per pixel it writes the depth Z of the first front-facing surface along the pixel's
+ * ray and, optionally, the unit surface normal in camera coordinates.
+ *
+ * All arithmetic is float32, every operation rounded on its own (no contraction; divide and sqrt correctly rounded); the
+ * parentheses are the contract; "finite" is tested on the bit pattern, before any comparison.  Per frame, R, t its pose (R[r][i] =
+ * poses[3*r + i], t_r = poses[9 + r]); the camera centre and the ray directions in world coordinates:
+ *   c_i = -((R[0][i]*t0 + R[1][i]*t1) + R[2][i]*t2)            i = 0,1,2        (R^T is a transposition, no arithmetic)
+ * Per pixel (x, y):
+ *   a = ((float)x - cx) / fx,   b = ((float)y - cy) / fy
+ *   d_i  = (R[0][i]*a + R[1][i]*b) + R[2][i]                   world direction per unit of camera Z
+ *   go_i = (c_i - origin_i) / voxel,   gd_i = d_i / voxel      grid units: voxel (i,j,k) covers [i,i+1) x [j,j+1) x [k,k+1)
+ *   g(Z)_i = go_i + Z * gd_i
+ * The march is in Z, not in ray length (the result is the depth itself; the stored distance is projective along Z as well):
+ *   Z_k = z_min + (float)k * step,  k = 0, 1, ...  while Z_k <= z_max
+ * The nearest sample at g = g(Z_k) is valid iff all three g_i are finite, 0 <= g_i < (float)n_i (tested in float before any
+ * conversion) and the word of voxel (floorf g_x, floorf g_y, floorf g_z) has w >= min_weight; its sign is tq < 0, the crossing
+ * rule of sgm_volume_points (zero counts as non-negative).  An invalid sample forgets the previous one.  Previous valid and
+ * non-negative, current valid and negative: a front hit at k, the march ends.  Previous valid and negative, current valid and
+ * non-negative: a back face, the march ends and the pixel is empty.  Reaching z_max without a hit leaves the pixel empty.
+ * Refinement at a hit.  F(g) is the trilinear value of tq at h = g - 0.5f, i0 = floorf(h), f = h - i0 per axis; valid iff h is
+ * finite, 0 <= i0 and i0 + 1 < n on every axis (in float) and all eight words have w >= min_weight;
+ * lerp(p, q, s) = p + s*(q - p) on (float)tq, along x first, then y, then z.
+ *   Fp = F(g(Z_{k-1})),  Fc = F(g(Z_k)),  den = Fp - Fc
+ *   hit iff both are valid and den > 0;   s = fminf(fmaxf(Fp / den, 0), 1);   Z* = Z_{k-1} + s * step
+ * Otherwise the pixel is empty and the march does not resume.  d_depth receives Z*; an empty pixel the quiet NaN 0x7FC00000, as in
+ * the other 3-D units.  The normal (written only if d_normal != NULL), at g* = go + Z* * gd:
+ *   nw_a = F(g* + e_a) - F(g* - e_a)  for the three unit steps   (g*_a + 1.0f and g*_a - 1.0f, then F's own - 0.5f)
+ *   n_r  = (R[r][0]*nw_0 + R[r][1]*nw_1) + R[r][2]*nw_2
+ *   len  = sqrtf((n_0*n_0 + n_1*n_1) + n_2*n_2)
+ * If all six samples are valid and len is finite and > 0 the normal is n_r / len, else three quiet NaNs (the depth stays).  It
+ * points out of the surface towards free space: n_z < 0 for a wall facing the camera.  An empty pixel gets three quiet NaNs.
+ *
+ * false, nothing queued and one "sgm_mi355x: sgm_volume_raycast: ..." line on stderr: a NULL s, vol, view, poses, d_voxels or
+ * d_depth; a volume spec sgm_volume_integrate refuses; a view outside the ranges below; fx, fy not finite and > 0; cx, cy not
+ * finite; z_min NaN or < 0; z_max not finite or not > z_min; step not finite or not > 0; (z_max - z_min) / step >= 65536 (in
+ * double: k fits and a launch is bounded); a min_weight outside 1..65535; a non-finite pose entry; a pointer not aligned to its
+ * element; an output that overlaps the volume or the other output; a build without the kernel.  poses is a HOST pointer, read
+ * before the call returns; the others are device pointers.  Asynchronous on sgm_stream(s), ordered as sgm_volume_points is (behind
+ * the last match also with sgm_set_overlap_post).  No scratch; nothing outside the two output arrays is written; an instance that
+ * never calls it allocates and launches exactly what it did before; one lane per pixel with no dependence between lanes, so the
+ * result is the same on every run and one call over B frames equals B calls of one frame.  Not part of it: adaptive step lengths,
+ * shading and colour, pose estimation, row tiles. */
+typedef struct {            /* 44 bytes, every field 4 bytes, no padding */
+    int32_t  width, height, frames;   /* 1..65535 each for width/height; 1 <= frames <= 64; frames*width*height <= 2^31 */
+    float    fx, fy, cx, cy;          /* pinhole of the view */
+    float    z_min, z_max, step;      /* march Z = z_min + k*step while Z <= z_max; units of the volume */
+    uint32_t min_weight;              /* 1..65535: a voxel counts iff w >= min_weight */
+} sgm_raycast_spec;
+bool sgm_volume_raycast(sgm_instance* s, const sgm_volume_spec* vol, const sgm_raycast_spec* view,
+                        const float* poses /* HOST [frames][12], R row-major then t, world -> camera, as sgm_volume_integrate */,
+                        const uint32_t* d_voxels, float* d_depth /* [frames][height][width] */,
+                        float* d_normal /* [frames][height][width][3], may be NULL */);
 
 /* ---- matching at half or quarter scale, re-search at full resolution ----
  * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/scaled_ref.py.  A match at

@@ -317,6 +317,18 @@ int sgmd_volume_integrate(int ord, void* stream, const sgmd_volume* v, const sgm
 int sgmd_volume_points(int ord, void* stream, const sgmd_volume* v, const void* voxels, unsigned min_weight, void* scratch,
                        void* points, size_t capacity, void* count);
 
+/* The volume ray-cast into depth and normal maps of a view (include/sgm_mi355x.h, sgm_raycast_spec); sgm_volume.hip.  r: the view as
+ * the host validated it (r->B <= 64 frames, one pose each).  poses: HOST, [r->B][12], read before it returns.  One launch, no
+ * scratch: depth f32 [B][H][W], normal f32 [B][H][W][3] or NULL (then not written).  sgm_host.c references it weakly, on its own:
+ * a host built without it answers false to sgm_volume_raycast and keeps the rest of the volume. */
+typedef struct {
+    int W, H, B;
+    float fx, fy, cx, cy, z_min, z_max, step;
+    unsigned min_weight;
+} sgmd_raycast;
+int sgmd_volume_raycast(int ord, void* stream, const sgmd_volume* v, const sgmd_raycast* r, const float* poses, const void* voxels,
+                        void* depth, void* normal);
+
 /* Extension (parity unpinned by the reference), matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); sgm_scale.hip.
  * c: the spec as the host validated it (W, H: FULL resolution; the low resolution is W / f x H / f).  sgmd_downscale: the f x f box
  * mean with rounding of one image stack, u8 (bits == 8) or u16 [B][H][W] -> [B][H / f][W / f]; trailing rows and columns are not

@@ -2383,6 +2383,49 @@ bool sgm_volume_points(sgm_instance* s, const sgm_volume_spec* spec, const uint3
     return sgmd_volume_points(s->device, s->stream, &v, d_voxels, min_weight, s->d_volume_scratch.p, d_points, capacity, d_count) == 0;
 }
 
+/* The ray-cast's launcher, a weak symbol of its own: a host built with the volume but without it keeps the volume */
+#pragma weak sgmd_volume_raycast
+static bool raycast_available(void) { return sgmd_volume_raycast != NULL; }
+
+/* the view as the kernel takes it; NULL, or what is outside the ranges of include/sgm_mi355x.h */
+static const char* raycast_spec_invalid(const sgm_raycast_spec* sp, sgmd_raycast* r)
+{
+    if (sp->frames < 1 || sp->frames > VOLUME_MAX_FRAMES) return "1..64 frames in one call (the poses travel as kernel arguments)";
+    if (!frame_size_valid(sp->width, sp->height, sp->frames)) return "width and height 1..65535, frames*width*height <= 2^31";
+    if (!finite_positive(sp->fx) || !finite_positive(sp->fy)) return "fx, fy finite and > 0";
+    if (!isfinite(sp->cx) || !isfinite(sp->cy)) return "cx, cy finite";
+    if (!(sp->z_min >= 0.0f)) return "z_min >= 0";                                                  /* !(..) also catches NaN */
+    if (!isfinite(sp->z_max) || !(sp->z_max > sp->z_min)) return "z_max finite and > z_min";
+    if (!finite_positive(sp->step)) return "step finite and > 0";
+    if (!(((double)sp->z_max - (double)sp->z_min) / (double)sp->step < 65536.0)) return "(z_max - z_min) / step < 65536";
+    if (sp->min_weight < 1u || sp->min_weight > 65535u) return "min_weight 1..65535";
+    *r = (sgmd_raycast){sp->width, sp->height, sp->frames, sp->fx, sp->fy, sp->cx, sp->cy, sp->z_min, sp->z_max, sp->step, sp->min_weight};
+    return NULL;
+}
+
+bool sgm_volume_raycast(sgm_instance* s, const sgm_volume_spec* vol, const sgm_raycast_spec* view, const float* poses,
+                        const uint32_t* d_voxels, float* d_depth, float* d_normal)
+{
+    sgmd_volume v;
+    sgmd_raycast r;
+    if (!s || !vol || !view || !poses || !d_voxels || !d_depth) FAIL("sgm_volume_raycast: NULL argument");
+    if (!raycast_available()) FAIL("sgm_volume_raycast: the ray-cast is not part of this build");
+    if (!volume_spec_valid(vol, &v)) FAIL("sgm_volume_raycast: the volume spec is outside its ranges");
+    const char* why = raycast_spec_invalid(view, &r);
+    if (why) FAIL("sgm_volume_raycast: the view is outside its ranges (%s)", why);
+    for (int i = 0; i < 12 * r.B; ++i)
+        if (!isfinite(poses[i])) FAIL("sgm_volume_raycast: entry %d of the pose of frame %d is not finite", i % 12, i / 12);
+    if (!aligned_to(d_voxels, sizeof(uint32_t)) || !aligned_to(d_depth, sizeof(float)) || !aligned_to(d_normal, sizeof(float)))
+        FAIL("sgm_volume_raycast: a pointer is not aligned to its element");
+    const size_t vol_bytes = (size_t)v.nx * v.ny * v.nz * sizeof(uint32_t), depth_bytes = (size_t)r.B * r.W * r.H * sizeof(float);
+    if (ranges_overlap(d_depth, depth_bytes, d_voxels, vol_bytes) || ranges_overlap(d_normal, 3 * depth_bytes, d_voxels, vol_bytes) ||
+        ranges_overlap(d_normal, 3 * depth_bytes, d_depth, depth_bytes))
+        FAIL("sgm_volume_raycast: an output overlaps the volume or the other output");
+    /* the volume may be the work of an integration that read a match's result: the same place in the queue as sgm_volume_points */
+    if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
+    return sgmd_volume_raycast(s->device, s->stream, &v, &r, poses, d_voxels, d_depth, d_normal) == 0;
+}
+
 /* ------------------------------------------------------------------ matching at 1/f scale (extension) */
 
 /* The launchers of sgm_scale.hip, weakly referenced like the extensions above: a host built without them has no scaled match */

@@ -36,6 +36,11 @@
  *                             (units of BASELINE) and truncation distance TRUNC -- sgm_volume_integrate of the one frame with the
  *                             identity pose -- and the volume's surface points (sgm_volume_points, min_weight 1) as a PLY like
  *                             --cloud's, coloured with the grey at the pixel a point projects to.  --cloud-z-max cuts it too
+ *            [--volume-view ZMIN,ZMAX,STEP[,MINWEIGHT] [--volume-depth OUT.f32] [--volume-normals OUT.f32]]   extension: with
+ *                             --volume, the volume rendered back into the frame's own camera after the frame is integrated
+ *                             (sgm_volume_raycast: the --pinhole intrinsics, the identity pose, the image's size), marched at
+ *                             Z = ZMIN + k * STEP up to ZMAX over voxels of weight MINWEIGHT (default 1) or more: the depth as raw
+ *                             float32 [H][W] like --raw, the unit normals as raw float32 [H][W][3], NaN where no surface is met
  *            [--bits N]       extension: images of N = 9..16 bits per sample (SGM_SetPixelBits): LEFT and RIGHT are loaded with
  *                             sgm_load_gray16 (binary PGM with maxval up to 65535, PNG grey of depth 16; 8-bit files are widened
  *                             unshifted) and matched on all their bits.  --bits 0: the smallest N >= 8 that holds the files' maxval.
@@ -167,11 +172,51 @@ static int register_raw(const char* path, const char* calib_path, int right_ref,
     return rc;
 }
 
+/* --volume-view: the march and where the maps go (a path that is NULL is not written) */
+typedef struct {
+    float z_min, z_max, step;
+    uint32_t min_weight;
+    const char* depth_path;
+    const char* normals_path;
+} volume_view;
+
+static int write_floats(const char* path, const float* v, size_t n)
+{
+    FILE* f = fopen(path, "wb");
+    if (!f) return -1;
+    const size_t put = fwrite(v, sizeof(float), n, f);
+    return (fclose(f) == 0 && put == n) ? 0 : -1;
+}
+
+/* the volume rendered into the frame's own camera with the identity pose, and the maps written */
+static int volume_render(sgm_instance* s, const sgm_volume_spec* vol, const volume_view* view, int w, int h, const float* pinhole,
+                         const uint32_t* d_voxels)
+{
+    static const float identity[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    const sgm_raycast_spec spec = {w, h, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], view->z_min, view->z_max, view->step, view->min_weight};
+    const size_t px = (size_t)w * h;
+    float* d_depth = (float*)sgm_host_alloc(s, px * sizeof(float));
+    float* d_normal = view->normals_path ? (float*)sgm_host_alloc(s, 3 * px * sizeof(float)) : NULL;
+    int rc = -1;
+    if (d_depth && (d_normal || !view->normals_path) && sgm_volume_raycast(s, vol, &spec, identity, d_voxels, d_depth, d_normal) &&
+        sgm_synchronize(s)) {
+        size_t hits = 0;
+        for (size_t i = 0; i < px; ++i) hits += d_depth[i] == d_depth[i];
+        printf("volume view: %zu of %zu pixels meet the surface\n", hits, px);
+        rc = 0;
+        if (view->depth_path && write_floats(view->depth_path, d_depth, px) != 0) rc = -1;
+        if (view->normals_path && write_floats(view->normals_path, d_normal, 3 * px) != 0) rc = -1;
+    }
+    sgm_host_free(s, d_depth);
+    sgm_host_free(s, d_normal);
+    return rc;
+}
+
 /* --volume: the map fused into a TSDF volume with the identity pose, and the surface points read back, as sgm_point records whose
- * pixel is the one the point projects to (clamped to the image), for write_ply.  Page-locked buffers of an instance of its own, as
- * above.  *out: malloc'ed, *n records. */
-static int volume_surface(const sgm_volume_spec* vol, int device, int w, int h, const float* pinhole, float z_max, const float* disp,
-                          sgm_point** out, size_t* n)
+ * pixel is the one the point projects to (clamped to the image), for write_ply; with view != NULL the volume rendered as well.
+ * Page-locked buffers of an instance of its own, as above.  *out: malloc'ed, *n records. */
+static int volume_surface(const sgm_volume_spec* vol, const volume_view* view, int device, int w, int h, const float* pinhole, float z_max,
+                          const float* disp, sgm_point** out, size_t* n)
 {
     const sgm_cloud_spec src = {w, h, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], pinhole[4], pinhole[5], 0.0f, z_max, 0};
     static const float identity[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
@@ -211,7 +256,7 @@ static int volume_surface(const sgm_volume_spec* vol, int device, int w, int h, 
                     (*out)[i] = (sgm_point){q.x, q.y, q.z, ((uint32_t)v << 16) | (uint32_t)u};
                 }
                 *n = count;
-                rc = 0;
+                rc = view ? volume_render(s, vol, view, w, h, pinhole, d_voxels) : 0;
             }
         }
     }
@@ -283,6 +328,8 @@ int main(int argc, char** argv)
     const char* volume_path = NULL;
     sgm_volume_spec volume = {0, 0, 0, 0.0f, {0.0f, 0.0f, 0.0f}, 0.0f, 65535};
     int have_volume = 0;
+    volume_view view = {0.0f, 0.0f, 0.0f, 1, NULL, NULL};
+    int have_view = 0;
     int register_splat = 2, register_splat_set = 0;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
     int census_kind = SGM_CENSUS_CENTRE, bits = 8;
@@ -329,6 +376,14 @@ int main(int argc, char** argv)
             ++i;
         }
         else if (v && !strcmp(a, "--volume-ply")) { volume_path = v; ++i; }
+        else if (v && !strcmp(a, "--volume-view")) {
+            const int got = sscanf(v, "%f,%f,%f,%u", &view.z_min, &view.z_max, &view.step, &view.min_weight);
+            if (got != 3 && got != 4) { fprintf(stderr, "--volume-view wants ZMIN,ZMAX,STEP[,MINWEIGHT]\n"); return 2; }
+            have_view = 1;
+            ++i;
+        }
+        else if (v && !strcmp(a, "--volume-depth")) { view.depth_path = v; ++i; }
+        else if (v && !strcmp(a, "--volume-normals")) { view.normals_path = v; ++i; }
         else if (v && !strcmp(a, "--register-splat")) {
             if (strcmp(v, "1") && strcmp(v, "2")) { fprintf(stderr, "--register-splat wants 1 or 2\n"); return 2; }
             register_splat = atoi(v);
@@ -378,6 +433,14 @@ int main(int argc, char** argv)
         return 2;
     }
     if (have_volume != (volume_path != NULL)) { fprintf(stderr, "--volume and --volume-ply OUT.ply come together\n"); return 2; }
+    if ((have_view || view.depth_path || view.normals_path) && !have_volume) {
+        fprintf(stderr, "--volume-view, --volume-depth and --volume-normals need --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n");
+        return 2;
+    }
+    if (have_view != (view.depth_path || view.normals_path)) {
+        fprintf(stderr, "--volume-view ZMIN,ZMAX,STEP[,MINWEIGHT] and --volume-depth / --volume-normals OUT.f32 come together\n");
+        return 2;
+    }
     if (volume_path && !have_pinhole) { fprintf(stderr, "--volume needs --pinhole FX,FY,CX,CY,BASELINE,DOFFS\n"); return 2; }
     if (scale && volume_path) { fprintf(stderr, "--scale does not combine with --volume\n"); return 2; }
     if (scale && register_path) { fprintf(stderr, "--scale does not combine with --register-raw (it needs --rectify)\n"); return 2; }
@@ -509,8 +572,8 @@ int main(int argc, char** argv)
     if (volume_path) {
         sgm_point* pts = NULL;
         size_t n = 0;
-        if (volume_surface(&volume, device, w1, h1, pinhole, cloud_z_max, disp, &pts, &n) != 0) {
-            printf("volume unavailable or --volume / --pinhole / --cloud-z-max out of range\n");
+        if (volume_surface(&volume, have_view ? &view : NULL, device, w1, h1, pinhole, cloud_z_max, disp, &pts, &n) != 0) {
+            printf("volume unavailable or --volume / --volume-view / --pinhole / --cloud-z-max out of range\n");
             rc = -1;
         } else {
             uint8_t* rect = NULL;

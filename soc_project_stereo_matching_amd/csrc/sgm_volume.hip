@@ -16,6 +16,8 @@
 // Extraction    the ordered compaction of sgm_cloud.hip with a lane contributing 0..3 records (one per axis) instead of 0..1:
 //               count per tile, one scan (tile_scan), emit; three ballots give a record's rank inside its wave.  No atomic
 //               decides a place: the list is sorted by id and the same on every run.
+// Ray-cast      the volume rendered into depth and normal maps of a view (sgm_raycast_spec; tests/raycast_ref.py): one lane per
+//               pixel, one launch for all frames; see the block further down.
 //
 // (this translation unit is compiled with -fno-honor-nans like the others: "finite" is tested on the bit pattern, before any
 // comparison)
@@ -220,6 +222,195 @@ __global__ __launch_bounds__(TILE_THREADS) void sgm_volume_emit_k(VolumeParams v
     }
 }
 
+// ---- ray-cast ------------------------------------------------------------------------------------------------------------------
+// The volume rendered into depth and normal maps of a pinhole view (include/sgm_mi355x.h, sgm_raycast_spec; tests/raycast_ref.py
+// restates it).  One lane per pixel, one launch for all frames (blockIdx.z: the frame, whose pose is read from the kernel
+// arguments with scalar loads), no LDS, no atomics and no dependence between lanes: a lane marches its ray in Z, reads one word
+// per sample, and at a front hit 16 words for the two trilinear values and 48 for the normal.
+//
+// SGM_RAYCAST_TILE (make RAY_TILE=0 | 1): how a wave covers the image -- 1: an 8 x 8 pixel tile, whose rays stay together in the
+//                  volume; 0: a 64 x 1 row segment, whose stores coalesce.
+// SGM_RAYCAST_SKIP (make RAY_SKIP=0 | 1): 1 starts and ends the march at the volume's box (ray_box below); 0 marches z_min..z_max.
+// Both were measured (NOTES.md section 34); the defaults are the winners.
+#define RAY_THREADS 256
+#ifndef SGM_RAYCAST_TILE
+#define SGM_RAYCAST_TILE 1
+#endif
+#ifndef SGM_RAYCAST_SKIP
+#define SGM_RAYCAST_SKIP 1
+#endif
+#if SGM_RAYCAST_TILE
+#define RAY_BLOCK_W 32                                        // four 8 x 8 tiles side by side
+#define RAY_BLOCK_H 8
+#else
+#define RAY_BLOCK_W RAY_THREADS                               // four row segments of 64 in a row
+#define RAY_BLOCK_H 1
+#endif
+
+struct RaycastView {
+    unsigned W, H;
+    float fx, fy, cx, cy, z_min, z_max, step;
+    unsigned min_weight;
+};
+
+// The nearest sample at g: 0 invalid, 1 valid and non-negative, 2 valid and negative
+static __device__ __forceinline__ unsigned ray_nearest(const VolumeParams& v, const unsigned* __restrict__ voxels, unsigned min_weight,
+                                                       float gx, float gy, float gz)
+{
+    if (!cloud_finite(gx) || !cloud_finite(gy) || !cloud_finite(gz)) return 0u;
+    // admitted in float, before any conversion to int; floorf of a value in [0, n) is its truncation
+    if (!(0.0f <= gx && gx < (float)v.nx && 0.0f <= gy && gy < (float)v.ny && 0.0f <= gz && gz < (float)v.nz)) return 0u;
+    const unsigned word = voxels[((unsigned)gz * v.ny + (unsigned)gy) * v.nx + (unsigned)gx];
+    if ((word >> 16) < min_weight) return 0u;
+    return (word & 0x8000u) ? 2u : 1u;
+}
+
+static __device__ __forceinline__ float ray_lerp(float p, float q, float s) { return p + s * (q - p); }
+
+// F(g): the trilinear value of tq at h = g - 0.5, along x first, then y, then z; false where a word is missing or outside the grid
+static __device__ __forceinline__ bool ray_trilinear(const VolumeParams& v, const unsigned* __restrict__ voxels, unsigned min_weight,
+                                                     float gx, float gy, float gz, float& F)
+{
+    const float hx = gx - 0.5f, hy = gy - 0.5f, hz = gz - 0.5f;
+    if (!cloud_finite(hx) || !cloud_finite(hy) || !cloud_finite(hz)) return false;
+    const float ix = floorf(hx), iy = floorf(hy), iz = floorf(hz);
+    if (!(0.0f <= ix && ix + 1.0f < (float)v.nx && 0.0f <= iy && iy + 1.0f < (float)v.ny && 0.0f <= iz && iz + 1.0f < (float)v.nz))
+        return false;
+    const float fx = hx - ix, fy = hy - iy, fz = hz - iz;
+    const unsigned* at = voxels + (((unsigned)iz * v.ny + (unsigned)iy) * v.nx + (unsigned)ix);
+    const unsigned sy = v.nx, sz = v.nx * v.ny;
+    unsigned word[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) word[e] = at[(e & 1) + ((e >> 1) & 1) * sy + (e >> 2) * sz];
+    bool ok = true;
+    float t[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        ok = ok && (word[e] >> 16) >= min_weight;
+        t[e] = (float)(int)(short)(word[e] & 0xFFFFu);
+    }
+    const float c00 = ray_lerp(t[0], t[1], fx), c10 = ray_lerp(t[2], t[3], fx), c01 = ray_lerp(t[4], t[5], fx), c11 = ray_lerp(t[6], t[7], fx);
+    F = ray_lerp(ray_lerp(c00, c10, fy), ray_lerp(c01, c11, fy), fz);
+    return ok;
+}
+
+// The part of the march that can meet the volume: on return every k < k0 and every Z_k > z_end has a sample outside the box, which
+// the contract calls invalid -- skipping them changes no bit, and a skipped prefix leaves "no previous sample" as invalid samples
+// do.  Per axis the slab [-m, n + m] in grid units, m = 1 voxel + 2^-20 of the magnitudes involved (the float slab test is some
+// 2^-23 of them off), then one step on either side; k0 is taken only if Z_k0 itself, as the march computes it, lies below the
+// entry (Z_k does not decrease with k).  Anything non-finite on the way: no skip.
+static __device__ __forceinline__ void ray_box(const VolumeParams& v, const RaycastView& r, const float (&go)[3], const float (&gd)[3],
+                                               unsigned& k0, float& z_end)
+{
+    const float n[3] = {(float)v.nx, (float)v.ny, (float)v.nz};
+    float z_in = r.z_min, z_out = r.z_max;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (!cloud_finite(go[i]) || !cloud_finite(gd[i])) return;
+        if (gd[i] == 0.0f) continue;                          // (g_i == go_i all the way: the per-sample test decides)
+        const float m = 1.0f + (fabsf(go[i]) + n[i]) * 9.5367431640625e-07f;
+        const float za = (-m - go[i]) / gd[i], zb = ((n[i] + m) - go[i]) / gd[i];
+        if (!cloud_finite(za) || !cloud_finite(zb)) return;
+        z_in = fmaxf(z_in, fminf(za, zb) - r.step);
+        z_out = fminf(z_out, fmaxf(za, zb) + r.step);
+    }
+    if (!cloud_finite(z_in) || !cloud_finite(z_out)) return;
+    z_end = z_out;
+    const float kf = floorf((z_in - r.z_min) / r.step) - 2.0f;
+    if (cloud_finite(kf) && kf >= 1.0f && kf < 16777216.0f) {
+        const unsigned k = (unsigned)kf;
+        if (r.z_min + (float)k * r.step < z_in) k0 = k;
+    }
+}
+
+template <bool NORMALS>
+__global__ __launch_bounds__(RAY_THREADS) void sgm_volume_raycast_k(VolumeParams v, RaycastView r, VolumePoses poses,
+                                                                    const unsigned* __restrict__ voxels, float* __restrict__ depth,
+                                                                    float* __restrict__ normal)
+{
+#if SGM_RAYCAST_TILE
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned x = blockIdx.x * RAY_BLOCK_W + (threadIdx.x >> 6) * 8u + (lane & 7u), y = blockIdx.y * RAY_BLOCK_H + (lane >> 3);
+#else
+    const unsigned x = blockIdx.x * RAY_BLOCK_W + threadIdx.x, y = blockIdx.y;
+#endif
+    if (x >= r.W || y >= r.H) return;
+    const float* P = poses.p[blockIdx.z];                     // R row-major, then t: world -> camera
+    const float a = ((float)x - r.cx) / r.fx, b = ((float)y - r.cy) / r.fy;
+    const float origin[3] = {v.ox, v.oy, v.oz};
+    float go[3], gd[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float c = -((P[i] * P[9] + P[3 + i] * P[10]) + P[6 + i] * P[11]);
+        const float d = (P[i] * a + P[3 + i] * b) + P[6 + i];
+        go[i] = (c - origin[i]) / v.voxel;
+        gd[i] = d / v.voxel;
+    }
+    unsigned k = 0;
+    float z_end = r.z_max;
+#if SGM_RAYCAST_SKIP
+    ray_box(v, r, go, gd, k, z_end);
+#endif
+    const float nan = __uint_as_float(0x7FC00000u);
+    float Z = nan, nrm[3] = {nan, nan, nan};
+    unsigned prev = 0;
+    float Zp = 0.0f;
+    bool front = false;
+    for (;; ++k) {
+        const float Zk = r.z_min + (float)k * r.step;
+        if (!(Zk <= z_end)) break;
+        const unsigned cur = ray_nearest(v, voxels, r.min_weight, go[0] + Zk * gd[0], go[1] + Zk * gd[1], go[2] + Zk * gd[2]);
+        if (prev == 1u && cur == 2u) { front = true; break; }
+        if (prev == 2u && cur == 1u) break;                   // a back face: the pixel is empty
+        prev = cur;
+        Zp = Zk;
+    }
+    if (front) {
+        const float Zc = r.z_min + (float)k * r.step;
+        float Fp, Fc;
+        const bool okp = ray_trilinear(v, voxels, r.min_weight, go[0] + Zp * gd[0], go[1] + Zp * gd[1], go[2] + Zp * gd[2], Fp);
+        const bool okc = ray_trilinear(v, voxels, r.min_weight, go[0] + Zc * gd[0], go[1] + Zc * gd[1], go[2] + Zc * gd[2], Fc);
+        if (okp && okc) {
+            const float den = Fp - Fc;
+            if (den > 0.0f) {
+                const float s = fminf(fmaxf(Fp / den, 0.0f), 1.0f);
+                Z = Zp + s * r.step;
+                if constexpr (NORMALS) {
+                    const float g[3] = {go[0] + Z * gd[0], go[1] + Z * gd[1], go[2] + Z * gd[2]};
+                    float nw[3];
+                    bool ok = true;
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax) {
+                        float up, dn;
+                        ok = ray_trilinear(v, voxels, r.min_weight, ax == 0 ? g[0] + 1.0f : g[0], ax == 1 ? g[1] + 1.0f : g[1],
+                                           ax == 2 ? g[2] + 1.0f : g[2], up) && ok;
+                        ok = ray_trilinear(v, voxels, r.min_weight, ax == 0 ? g[0] - 1.0f : g[0], ax == 1 ? g[1] - 1.0f : g[1],
+                                           ax == 2 ? g[2] - 1.0f : g[2], dn) && ok;
+                        nw[ax] = up - dn;
+                    }
+                    if (ok) {
+                        float n[3];
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) n[q] = (P[3 * q] * nw[0] + P[3 * q + 1] * nw[1]) + P[3 * q + 2] * nw[2];
+                        const float len = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+                        if (cloud_finite(len) && len > 0.0f) {
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) nrm[q] = n[q] / len;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    const size_t at = ((size_t)blockIdx.z * r.H + y) * r.W + x;
+    depth[at] = Z;
+    if constexpr (NORMALS) {
+        normal[3 * at] = nrm[0];
+        normal[3 * at + 1] = nrm[1];
+        normal[3 * at + 2] = nrm[2];
+    }
+}
+
 static bool volume_ok(const sgmd_volume* v)
 {
     return v && v->nx >= 1 && v->ny >= 1 && v->nz >= 1 && v->nx <= 1024 && v->ny <= 1024 && v->nz <= 1024 &&
@@ -294,6 +485,36 @@ int sgmd_volume_points(int ord, void* stream, const sgmd_volume* v, const void* 
     if (capacity == 0) return 0;                              // the count is all that was asked for
     hipLaunchKernelGGL(sgm_volume_emit_k, dim3(ntiles), dim3(TILE_THREADS), 0, st, p, tile, min_weight, (const unsigned*)voxels,
                        (const unsigned*)s.base, (SurfacePoint*)points, capacity);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sgmd_volume_raycast(int ord, void* stream, const sgmd_volume* v, const sgmd_raycast* r, const float* poses, const void* voxels,
+                        void* depth, void* normal)
+{
+    if (!volume_ok(v) || !r || !poses || !voxels || !depth || r->W < 1 || r->H < 1 || r->W > 65535 || r->H > 65535 || r->B < 1 ||
+        r->B > VOL_MAX_FRAMES || (unsigned long long)r->W * r->H * r->B > (1ull << 31) || r->min_weight < 1 || r->min_weight > 65535 ||
+        (uintptr_t)voxels % 4 != 0 || (uintptr_t)depth % 4 != 0 || (uintptr_t)normal % 4 != 0) {
+        fprintf(stderr, "sgm_mi355x: sgmd_volume_raycast: bad arguments\n");
+        return -1;
+    }
+    HIP_TRY(hipSetDevice(ord));
+    const VolumeParams p = volume_params(v);
+    RaycastView q;
+    q.W = (unsigned)r->W; q.H = (unsigned)r->H;
+    q.fx = r->fx; q.fy = r->fy; q.cx = r->cx; q.cy = r->cy; q.z_min = r->z_min; q.z_max = r->z_max; q.step = r->step;
+    q.min_weight = r->min_weight;
+    VolumePoses pose;
+    memset(&pose, 0, sizeof pose);
+    memcpy(pose.p, poses, (size_t)r->B * 12 * sizeof(float));
+    const dim3 grid((q.W + RAY_BLOCK_W - 1) / RAY_BLOCK_W, (q.H + RAY_BLOCK_H - 1) / RAY_BLOCK_H, (unsigned)r->B);
+    const hipStream_t st = (hipStream_t)stream;
+    if (normal)
+        hipLaunchKernelGGL(sgm_volume_raycast_k<true>, grid, dim3(RAY_THREADS), 0, st, p, q, pose, (const unsigned*)voxels, (float*)depth,
+                           (float*)normal);
+    else
+        hipLaunchKernelGGL(sgm_volume_raycast_k<false>, grid, dim3(RAY_THREADS), 0, st, p, q, pose, (const unsigned*)voxels, (float*)depth,
+                           (float*)nullptr);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -140,6 +140,22 @@ def volume_bytes(spec: SGMVolumeSpec) -> int:
     return int(load_library().sgm_volume_bytes(C.byref(spec)))
 
 
+class SGMRaycastSpec(C.Structure):
+    """Field-for-field sgm_raycast_spec of include/sgm_mi355x.h: 44 bytes, every field 4 bytes."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("frames", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("z_min", C.c_float), ("z_max", C.c_float), ("step", C.c_float),
+        ("min_weight", C.c_uint32),
+    ]
+
+
+def raycast_spec(width, height, fx, fy, cx, cy, z_min, z_max, step, min_weight=1, frames=1) -> SGMRaycastSpec:
+    """A sgm_raycast_spec: `frames` pinhole views of width x height, marched at Z = z_min + k * step while Z <= z_max (units of the
+    volume); a voxel counts with a weight of at least min_weight (1..65535)."""
+    return SGMRaycastSpec(int(width), int(height), int(frames), fx, fy, cx, cy, z_min, z_max, step, int(min_weight))
+
+
 class SGMScaleSpec(C.Structure):
     """Field-for-field sgm_scale_spec of include/sgm_mi355x.h: 36 bytes, every field 4 bytes."""
     _fields_ = [
@@ -340,6 +356,9 @@ def _load() -> C.CDLL:
         L.sgm_volume_integrate.restype = C.c_bool
         L.sgm_volume_points.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
         L.sgm_volume_points.restype = C.c_bool
+    if hasattr(L, "sgm_volume_raycast"):      # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_volume_raycast.argtypes = [C.c_void_p] * 7
+        L.sgm_volume_raycast.restype = C.c_bool
     if hasattr(L, "sgm_set_temporal"):        # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_temporal_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t] + [C.c_void_p] * 5
         L.sgm_temporal_filter.restype = C.c_bool
@@ -1194,6 +1213,16 @@ class SGMInstance(_StageReader):
         room for `capacity` records; None with capacity 0) and their full number into d_count[0].  Asynchronous on `stream`."""
         return bool(self.lib.sgm_volume_points(self.handle, C.byref(spec), d_voxels, int(min_weight), d_points or None, int(capacity),
                                                d_count))
+
+    def volume_raycast(self, vol: SGMVolumeSpec, view: SGMRaycastSpec, poses, d_voxels: int, d_depth: int, d_normal=None) -> bool:
+        """sgm_volume_raycast: the volume at d_voxels rendered into view.frames depth maps [frames][height][width] float32 at d_depth
+        and, with d_normal, unit normals [frames][height][width][3] in camera coordinates; empty pixels hold the quiet NaN.  poses:
+        [frames][12] host floats, R row-major then t (world -> camera), read before the call returns.  Asynchronous on `stream`."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1)
+        if poses.size != 12 * view.frames:
+            raise ValueError("volume_raycast: one pose of 12 floats (R row-major, then t) per frame")
+        return bool(self.lib.sgm_volume_raycast(self.handle, C.byref(vol), C.byref(view), poses.ctypes.data, d_voxels, d_depth,
+                                                d_normal or None))
 
     # ---- matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); device pointers as ints, None = NULL ----
     def downscale(self, spec: SGMScaleSpec, d_in: int, d_out: int) -> bool:
