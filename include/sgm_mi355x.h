@@ -611,8 +611,8 @@ bool   sgm_register_spec_raw(const double K[9], const double dist[5], const doub
  * that aliases a map (d_points or d_count that alias the volume or each other); a build without the kernels.  The extraction
  * keeps 8 bytes of scratch per tile of 2048 voxels, reserved at its first call: an instance that never calls these entry points
  * allocates and launches exactly what it did before.  Not part of it: meshing (ray-casting the volume into a view is
- * sgm_volume_raycast below), confidence-weighted updates, colour, voxel hashing or a moving volume, estimating the poses, row tiles,
- * sgm_match_planes. */
+ * sgm_volume_raycast below), confidence-weighted updates, colour, voxel hashing or a moving volume, estimating the poses (sgm_track
+ * below does that against a ray-cast), row tiles, sgm_match_planes. */
 typedef struct {            /* 36 bytes, every field 4 bytes, no padding */
     int32_t  nx, ny, nz;    /* 1..1024 each, nx*ny*nz <= 2^30; voxel n = (k*ny + j)*nx + i, x fastest */
     float    voxel;         /* edge length, units of baseline; finite, > 0 */
@@ -673,7 +673,7 @@ bool   sgm_volume_points(sgm_instance* s, const sgm_volume_spec* spec, const uin
  * the last match also with sgm_set_overlap_post).  No scratch; nothing outside the two output arrays is written; an instance that
  * never calls it allocates and launches exactly what it did before; one lane per pixel with no dependence between lanes, so the
  * result is the same on every run and one call over B frames equals B calls of one frame.  Not part of it: adaptive step lengths,
- * shading and colour, pose estimation, row tiles. */
+ * shading and colour, pose estimation (sgm_track below tracks a frame against these maps), row tiles. */
 typedef struct {            /* 44 bytes, every field 4 bytes, no padding */
     int32_t  width, height, frames;   /* 1..65535 each for width/height; 1 <= frames <= 64; frames*width*height <= 2^31 */
     float    fx, fy, cx, cy;          /* pinhole of the view */
@@ -684,6 +684,115 @@ bool sgm_volume_raycast(sgm_instance* s, const sgm_volume_spec* vol, const sgm_r
                         const float* poses /* HOST [frames][12], R row-major then t, world -> camera, as sgm_volume_integrate */,
                         const uint32_t* d_voxels, float* d_depth /* [frames][height][width] */,
                         float* d_normal /* [frames][height][width][3], may be NULL */);
+
+/* ---- frame-to-model tracking: projective point-to-plane ICP against the ray-cast ----
+ * Extension, "parity unpinned by the reference"; defined here and restated by tests/track_ref.py.  The step that makes spatial
+ * mapping work without an outside tracker: given the depth of the current frame and the depth and normal maps sgm_volume_raycast
+ * rendered from the last known pose, it estimates the rigid motion between the two, so that a caller can run match -> track ->
+ * integrate -> ray-cast on the device.  Conventions are registration's: a pose is [12], R row-major, then t, P' = R P + t.  The
+ * tracked pose maps the SOURCE camera (the rectified reference camera of the current frame) into the MODEL camera (the view the
+ * maps were ray-cast from).
+ *
+ * Inputs.  The contributing pixels are the KEPT pixels of the cloud contract above (src, d_disp, d_mask, d_conf) with their cloud
+ * X, Y, Z.  The model maps are d_model_depth f32 [frames][mh][mw] and d_model_normal f32 [frames][mh][mw][3] as sgm_volume_raycast
+ * writes them (width = mw, height = mh and the pinhole of sgm_track_spec); the model view may differ in size and pinhole from the
+ * source.  Frame f of the source meets frame f of the model under pose f.
+ * Per source pixel of frame f.  All arithmetic is float32, every operation rounded on its own (no contraction, correctly rounded
+ * divide); the parentheses are the contract; "finite" is tested on the bit pattern, before any comparison:
+ *   Px = ((R0*X + R1*Y) + R2*Z) + t0          (Py with R3..5, t1;  Pz with R6..8, t2;  R, t of frame f)
+ *   skip unless Pz is finite and Pz > 0
+ *   u = fx*(Px/Pz) + cx,  v = fy*(Py/Pz) + cy;   skip unless both finite
+ *   uf = floorf(u + 0.5f), vf = floorf(v + 0.5f); skip unless 0 <= uf < (float)width && 0 <= vf < (float)height, tested in float
+ *   Zm = model_depth[f][vf][uf];  skip unless Zm is finite and Zm > 0
+ *   n  = model_normal[f][vf][uf][0..2];  skip unless all three are finite
+ *   Q  = (((uf - cx)*Zm)/fx, ((vf - cy)*Zm)/fy, Zm)
+ *   e  = Q - P;   skip unless (e0*e0 + e1*e1) + e2*e2 is finite and <= dist_max*dist_max   (the right side rounded once to float)
+ *   r  = (n0*e0 + n1*e1) + n2*e2
+ *   c  = P x n:   c0 = Py*n2 - Pz*n1,  c1 = Pz*n0 - Px*n2,  c2 = Px*n1 - Py*n0
+ *   v[0..6] = c0/span, c1/span, c2/span, n0, n1, n2, r/dist_max
+ *   skip unless every v_i is finite and |v_i| <= 8.0f
+ *   q_i = (int32)rintf(v_i * 65536.0f)              (the product is exact; round half to even; |q_i| <= 2^19)
+ * A pixel that was not skipped is ASSOCIATED.  Why these seven: moving P by w x P + v changes r by -(P x n).w - n.v, so the row of
+ * the Jacobian of the six unknowns (w, v) is J = [P x n, n] and J xi = r is the linearised point-to-plane equation; span and
+ * dist_max bring the three kinds of entries to order one before they are quantised.
+ * Sums.  The result of frame f is int64 sums[f][29]: sums[k], k = 0..27, is the sum over the associated pixels of q_i*q_j for
+ * (i, j), i <= j, in row-major order of the upper triangle of the 7 x 7 matrix ((0,0) (0,1) .. (0,6) (1,1) .. (6,6)); sums[28] is
+ * the number of associated pixels.  Bound: |q_i| <= 2^19, so a term is at most 2^38; the entry points refuse a source of more
+ * than 2^24 pixels per frame (width * height > 2^24), so a sum stays at or below 2^62 and no addition overflows int64.
+ * Determinism: the sums are exact integers, so any order of addition gives the same bytes; the result is the same on every run and
+ * one call over B frames equals B calls of one frame.
+ *
+ * The step (sgm_track_solve; host only, double, every operation rounded on its own, no contraction).  sums(i, j), i <= j, is the
+ * entry of the pair.  status 1 (too few pixels) if sums[28] < min_pixels.  Else A_ij = A_ji = (double)sums(i, j) for i <= j < 6,
+ * b_i = (double)sums(i, 6), and A xi = b is solved by LDL^T without square roots, columns j = 0..5 left to right; every inner sum
+ * starts at 0.0 and adds its terms in index order k = 0, 1, ..:
+ *   D_j  = A_jj - sum_{k<j} (L_jk*L_jk)*D_k
+ *   status 2 (degenerate) unless D_j is finite and D_j > min_pivot * A_jj
+ *   L_ij = (A_ij - sum_{k<j} (L_ik*L_jk)*D_k) / D_j                for i = j+1..5
+ * then  y_i = b_i - sum_{k<i} L_ik*y_k   (i = 0..5),   z_i = y_i / D_i,   xi_i = z_i - sum_{k=i+1..5} L_ki*xi_k   (i = 5..0).
+ * status 2 as well if an xi_i or an entry of the stepped pose is not finite.  The motion, with dist_max and span as doubles:
+ *   w_i = xi_i * (dist_max / span),   v_i = xi_{3+i} * dist_max                     i = 0, 1, 2
+ * and the rotation is the Cayley map of s = w * 0.5 -- only + - * /, no libm, so numpy and C give the same bits:
+ *   ss = (s0*s0 + s1*s1) + s2*s2,   a = 1 - ss,   den = 1 + ss
+ *   X  = [s]x:  X01 = -s2, X02 = s1, X10 = s2, X12 = -s0, X20 = -s1, X21 = s0, X_rr = 0
+ *   Ri_rc = ((a*I_rc + 2*(s_r*s_c)) + 2*X_rc) / den                                 (I the identity, as 1.0 and 0.0)
+ *   R'_rc = (Ri_r0*R_0c + Ri_r1*R_1c) + Ri_r2*R_2c,    t'_r = ((Ri_r0*t0 + Ri_r1*t1) + Ri_r2*t2) + v_r
+ * Ri is a rotation exactly in real arithmetic and to rounding here.  stats: pixels = sums[28]; rms = dist_max * sqrt((double)
+ * sums[27] / (double)sums[28]) / 65536 (0 without pixels), the root mean square of the point-to-plane residuals that went into the
+ * sums, in the units of dist_max; status 0 (pose_out is the stepped pose), 1 or 2 (pose_out is pose_in).
+ *
+ * sgm_track_sums: asynchronous on sgm_stream(s), ordered as sgm_volume_raycast is (behind the last match also with
+ * sgm_set_overlap_post; a ray-cast queued before it on the same instance is finished when it reads the maps).  poses is a HOST
+ * pointer, [src->frames][12] float, read before the call returns (the poses travel as kernel arguments: 1..64 frames); d_sums is a
+ * device pointer, int64 [frames][29], 8-byte aligned, zeroed on the stream inside the call; the other pointers are device pointers
+ * that need no alignment beyond their element's (a map that cannot be read 16 bytes at a time takes a one-pixel-per-lane path with
+ * the same result).  d_disp == NULL: the instance's last final map, under the cloud entry points' rules.  Nothing outside d_sums
+ * is written and there is no scratch.
+ * sgm_track (blocking): model->iterations rounds of { one sgm_track_sums launch for all frames into a buffer of the instance's own
+ * (232 bytes per frame, reserved at the first call), that buffer copied to the host, sgm_track_solve per frame }.  poses is a HOST
+ * pointer, [frames][12] double: in, the guess; out, the estimate.  The kernel receives each pose rounded once to float32; the
+ * solve steps the double pose.  A frame whose solve does not return status 0 keeps its pose, records that status and sits out the
+ * remaining rounds (the launches still cover it, at the pose it kept).  stats[f]: the stats of the last solve made for frame f.
+ * trace_sums (HOST, int64 [iterations][frames][29], or NULL) receives the sums of every round, trace_poses (HOST, double
+ * [iterations + 1][frames][12], or NULL) the poses before the first round and after every round.
+ * sgm_track_world_pose (host only): out = rel^-1 o model_pose, the world -> camera pose of the tracked frame, ready for
+ * sgm_volume_integrate, for model_pose the world -> camera pose the maps were ray-cast from and rel the tracked pose.  In double,
+ * rel^-1 taken as (R^T, -R^T t), every result rounded once to float:
+ *   out_R[r][c] = (Rr[0][r]*Rm[0][c] + Rr[1][r]*Rm[1][c]) + Rr[2][r]*Rm[2][c]
+ *   out_t[r]    = (Rr[0][r]*(tm0 - tr0) + Rr[1][r]*(tm1 - tr1)) + Rr[2][r]*(tm2 - tr2)
+ *
+ * false, nothing queued and one "sgm_mi355x: <entry point>: ..." line on stderr: a NULL pointer other than d_disp, d_mask, d_conf
+ * and the traces; a src outside the cloud spec's ranges, with more than 64 frames or with width * height > 2^24; a model outside
+ * the ranges below; a pose entry that is not finite (for sgm_track: also after rounding to float); a pointer not aligned as
+ * said; a d_sums that overlaps a map; a sums[28] outside 0..2^24, which no launch gives (sgm_track_solve); a build without the
+ * kernel (sgm_track_sums, sgm_track).  An instance that never calls these entry points allocates and launches exactly what it did
+ * before.  Not part of it: image pyramids (a caller can ray-cast and match at a lower scale), robust weights beyond the distance
+ * gate, normals of the source frame and a normal-angle gate, photometric terms, loop closure, row tiles, sgm_match_planes. */
+typedef struct {            /* 44 bytes, every field 4 bytes, no padding */
+    int32_t  width, height;           /* the model maps, 1..65535 each */
+    float    fx, fy, cx, cy;          /* pinhole of the model view; fx, fy finite and > 0, cx, cy finite */
+    float    dist_max;                /* finite, > 0: the association gate and the unit of the residual */
+    float    span;                    /* finite, > 0: the length that normalises the rotational Jacobian; about the scene depth */
+    int32_t  iterations;              /* 1..64: rounds of sgm_track */
+    uint32_t min_pixels;              /* at least 6: fewer associated pixels are status 1 */
+    float    min_pivot;               /* finite, >= 0: a pivot D_j <= min_pivot * A_jj is status 2 */
+} sgm_track_spec;
+typedef struct { double rms; uint32_t pixels; int32_t status; } sgm_track_stats;   /* 16 bytes; status 0 ok, 1 too few pixels, 2 degenerate */
+bool sgm_track_sums(sgm_instance* s, const sgm_cloud_spec* src, const sgm_track_spec* model,
+                    const float* poses /* HOST [frames][12], source camera -> model camera; read before return */,
+                    const float* d_disp, const uint8_t* d_mask, const uint16_t* d_conf,
+                    const float* d_model_depth, const float* d_model_normal,
+                    int64_t* d_sums /* device, [frames][29], 8-byte aligned */);
+bool sgm_track_solve(const sgm_track_spec* model, const int64_t sums[29], const double pose_in[12], double pose_out[12],
+                     sgm_track_stats* stats);                                        /* host only */
+bool sgm_track(sgm_instance* s, const sgm_cloud_spec* src, const sgm_track_spec* model,
+               double* poses /* HOST [frames][12]; in: the guess, out: the estimate */,
+               const float* d_disp, const uint8_t* d_mask, const uint16_t* d_conf,
+               const float* d_model_depth, const float* d_model_normal,
+               sgm_track_stats* stats /* HOST [frames] */,
+               int64_t* trace_sums /* HOST [iterations][frames][29], or NULL */,
+               double* trace_poses /* HOST [iterations + 1][frames][12], or NULL */);
+bool sgm_track_world_pose(const float model_pose[12], const double rel[12], float out[12]);   /* host only */
 
 /* ---- matching at half or quarter scale, re-search at full resolution ----
  * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/scaled_ref.py.  A match at

@@ -1,6 +1,7 @@
 #pragma once
-// What sgm_cloud.hip, sgm_register.hip and sgm_volume.hip share.  The source map: the predicate, the formulas and the load paths of
-// the point clouds (include/sgm_mi355x.h, sgm_cloud_spec) and, for the launchers, the one reading of a sgmd_cloud.  The ordered
+// What sgm_cloud.hip, sgm_register.hip, sgm_volume.hip and sgm_track.hip share.  The source map: the predicate, the formulas and
+// the load paths of the point clouds (include/sgm_mi355x.h, sgm_cloud_spec) and, for the launchers, the one reading of a
+// sgmd_cloud.  The ordered
 // compaction of the point list and the surface list: its device pieces, its tile size and its scratch.  Include after sgm_common.hpp.
 
 struct CloudParams {

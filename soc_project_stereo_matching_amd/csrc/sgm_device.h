@@ -329,6 +329,21 @@ typedef struct {
 int sgmd_volume_raycast(int ord, void* stream, const sgmd_volume* v, const sgmd_raycast* r, const float* poses, const void* voxels,
                         void* depth, void* normal);
 
+/* Extension (parity unpinned by the reference), the sums of frame-to-model tracking (include/sgm_mi355x.h, sgm_track_spec);
+ * sgm_track.hip.  c: the source as the host validated it (c->B <= 64 frames, one pose each, c->W * c->H <= 2^24); t: the model view.
+ * poses: HOST, [c->B][12], source camera -> model camera, read before it returns.  model_depth f32 [B][t->H][t->W], model_normal
+ * f32 [B][t->H][t->W][3]; sums int64 [B][29], 8-byte aligned, zeroed on the stream and then added to with integer atomics.
+ * scratch: sgmd_track_scratch_bytes(W, H, B) bytes, 8-byte aligned -- 0 bytes (scratch may be NULL) in the default build; a build
+ * with make TRACK_FOLD=1 keeps the workgroups' partial sums there and folds them with a second launch.  sgm_host.c references both
+ * weakly, on their own: a host built without them answers false to sgm_track_sums and sgm_track. */
+typedef struct {
+    int W, H;
+    float fx, fy, cx, cy, dist_max, span;
+} sgmd_track;
+size_t sgmd_track_scratch_bytes(int W, int H, int B);
+int sgmd_track_sums(int ord, void* stream, const sgmd_cloud* c, const sgmd_track* t, const float* poses, const void* disp,
+                    const void* mask, const void* conf, const void* model_depth, const void* model_normal, void* scratch, void* sums);
+
 /* Extension (parity unpinned by the reference), matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); sgm_scale.hip.
  * c: the spec as the host validated it (W, H: FULL resolution; the low resolution is W / f x H / f).  sgmd_downscale: the f x f box
  * mean with rounding of one image stack, u8 (bits == 8) or u16 [B][H][W] -> [B][H / f][W / f]; trailing rows and columns are not

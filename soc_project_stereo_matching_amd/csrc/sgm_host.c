@@ -162,6 +162,9 @@ struct sgm_instance {
     sgm_buf d_register_keys;
     /* TSDF volume (sgm_volume_points; allocated at the first such call): the tile counts and bases of the surface list's three launches */
     sgm_buf d_volume_scratch;
+    /* tracking (allocated at the first such call): the sums of a round of sgm_track, 29 int64 per frame, and whatever scratch the
+     * launcher asks for (none in the default build) */
+    sgm_buf d_track_sums, d_track_scratch;
     /* matching at 1/f scale (sgm_match_scaled; allocated at its first use): the downscaled views, the census planes of the
      * FULL-resolution views with the narrowed images sgmd_census16 writes beside them, and for the host-pointer form the full
      * images, the full map and their page-locked staging */
@@ -213,7 +216,7 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     DEVICE_BUF(d_sc_small_l), DEVICE_BUF(d_sc_small_r), DEVICE_BUF(d_sc_census_l), DEVICE_BUF(d_sc_census_r), DEVICE_BUF(d_sc_g8_l),
     DEVICE_BUF(d_sc_g8_r), DEVICE_BUF(d_sc_full_l), DEVICE_BUF(d_sc_full_r), DEVICE_BUF(d_sc_disp), PINNED_BUF(h_sc_l), PINNED_BUF(h_sc_r),
     PINNED_BUF(h_sc_disp), DEVICE_BUF(d_tp_value), DEVICE_BUF(d_tp_bits), DEVICE_BUF(d_tp_stats), DEVICE_BUF(d_tp_pre),
-    DEVICE_BUF(d_tp_scratch), DEVICE_BUF(d_register_keys), DEVICE_BUF(d_volume_scratch),
+    DEVICE_BUF(d_tp_scratch), DEVICE_BUF(d_register_keys), DEVICE_BUF(d_volume_scratch), DEVICE_BUF(d_track_sums), DEVICE_BUF(d_track_scratch),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -2424,6 +2427,207 @@ bool sgm_volume_raycast(sgm_instance* s, const sgm_volume_spec* vol, const sgm_r
     /* the volume may be the work of an integration that read a match's result: the same place in the queue as sgm_volume_points */
     if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
     return sgmd_volume_raycast(s->device, s->stream, &v, &r, poses, d_voxels, d_depth, d_normal) == 0;
+}
+
+/* ------------------------------------------------------------------ frame-to-model tracking (extension) */
+
+/* The launcher of sgm_track.hip and its scratch size, weak symbols of their own: a host built without them keeps the volume and
+ * the ray-cast */
+#pragma weak sgmd_track_scratch_bytes
+#pragma weak sgmd_track_sums
+static bool track_available(void) { return sgmd_track_scratch_bytes != NULL && sgmd_track_sums != NULL; }
+
+/* the launcher's scratch (b == NULL for a launcher that wants none), reserved at the first call that needs it */
+static sgm_buf* track_scratch(sgm_instance* s, const sgmd_cloud* c, size_t* bytes)
+{
+    *bytes = sgmd_track_scratch_bytes(c->W, c->H, c->B);
+    return *bytes ? &s->d_track_scratch : NULL;
+}
+
+#define TRACK_SUMS 29
+#define TRACK_MAX_PIXELS (1LL << 24)    /* per frame: a term is at most 2^38, a sum stays at or below 2^62 */
+
+/* the model view as the kernel takes it; NULL, or what is outside the ranges of include/sgm_mi355x.h */
+static const char* track_spec_invalid(const sgm_track_spec* sp, sgmd_track* t)
+{
+    if (sp->width < 1 || sp->width > 65535 || sp->height < 1 || sp->height > 65535) return "width and height 1..65535";
+    if (!finite_positive(sp->fx) || !finite_positive(sp->fy)) return "fx, fy finite and > 0";
+    if (!isfinite(sp->cx) || !isfinite(sp->cy)) return "cx, cy finite";
+    if (!finite_positive(sp->dist_max)) return "dist_max finite and > 0";
+    if (!finite_positive(sp->span)) return "span finite and > 0";
+    if (sp->iterations < 1 || sp->iterations > 64) return "iterations 1..64";
+    if (sp->min_pixels < 6u) return "min_pixels at least 6";
+    if (!isfinite(sp->min_pivot) || !(sp->min_pivot >= 0.0f)) return "min_pivot finite and >= 0";
+    if (t) *t = (sgmd_track){sp->width, sp->height, sp->fx, sp->fy, sp->cx, sp->cy, sp->dist_max, sp->span};
+    return NULL;
+}
+
+/* the entry of the pair (i, j), i <= j, of the upper triangle of the 7 x 7 matrix in row-major order */
+static double track_sum(const int64_t* sums, int i, int j) { return (double)sums[i * 7 - i * (i - 1) / 2 + (j - i)]; }
+
+bool sgm_track_solve(const sgm_track_spec* model, const int64_t sums[29], const double pose_in[12], double pose_out[12], sgm_track_stats* stats)
+{
+    if (!model || !sums || !pose_in || !pose_out || !stats) FAIL("sgm_track_solve: NULL argument");
+    const char* why = track_spec_invalid(model, NULL);
+    if (why) FAIL("sgm_track_solve: the model is outside its ranges (%s)", why);
+    for (int i = 0; i < 12; ++i)
+        if (!isfinite(pose_in[i])) FAIL("sgm_track_solve: entry %d of the pose is not finite", i);
+    if (sums[28] < 0 || sums[28] > TRACK_MAX_PIXELS) FAIL("sgm_track_solve: %lld associated pixels (0..2^24)", (long long)sums[28]);
+    const double dist_max = (double)model->dist_max, span = (double)model->span;
+    double out[12];
+    memcpy(out, pose_in, sizeof out);
+    stats->pixels = (uint32_t)sums[28];
+    stats->rms = sums[28] > 0 ? dist_max * sqrt((double)sums[27] / (double)sums[28]) / 65536.0 : 0.0;
+    stats->status = 0;
+    if ((uint64_t)sums[28] < model->min_pixels) stats->status = 1;
+    double L[6][6], D[6], y[6], xi[6];
+    memset(L, 0, sizeof L);
+    for (int j = 0; j < 6 && stats->status == 0; ++j) {
+        const double Ajj = track_sum(sums, j, j);
+        double acc = 0.0;
+        for (int k = 0; k < j; ++k) acc += (L[j][k] * L[j][k]) * D[k];
+        D[j] = Ajj - acc;
+        if (!isfinite(D[j]) || !(D[j] > (double)model->min_pivot * Ajj)) { stats->status = 2; break; }
+        for (int i = j + 1; i < 6; ++i) {
+            acc = 0.0;
+            for (int k = 0; k < j; ++k) acc += (L[i][k] * L[j][k]) * D[k];
+            L[i][j] = (track_sum(sums, j, i) - acc) / D[j];
+        }
+    }
+    if (stats->status == 0) {
+        for (int i = 0; i < 6; ++i) {
+            double acc = 0.0;
+            for (int k = 0; k < i; ++k) acc += L[i][k] * y[k];
+            y[i] = track_sum(sums, i, 6) - acc;
+        }
+        for (int i = 5; i >= 0; --i) {
+            double acc = 0.0;
+            for (int k = i + 1; k < 6; ++k) acc += L[k][i] * xi[k];
+            xi[i] = y[i] / D[i] - acc;
+        }
+        for (int i = 0; i < 6; ++i)
+            if (!isfinite(xi[i])) stats->status = 2;
+    }
+    if (stats->status == 0) {
+        const double k = dist_max / span;
+        const double s[3] = {(xi[0] * k) * 0.5, (xi[1] * k) * 0.5, (xi[2] * k) * 0.5};
+        const double v[3] = {xi[3] * dist_max, xi[4] * dist_max, xi[5] * dist_max};
+        const double ss = (s[0] * s[0] + s[1] * s[1]) + s[2] * s[2], a = 1.0 - ss, den = 1.0 + ss;
+        const double X[3][3] = {{0.0, -s[2], s[1]}, {s[2], 0.0, -s[0]}, {-s[1], s[0], 0.0}};
+        double Ri[3][3];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) Ri[r][c] = ((a * (r == c ? 1.0 : 0.0) + 2.0 * (s[r] * s[c])) + 2.0 * X[r][c]) / den;
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) out[3 * r + c] = (Ri[r][0] * pose_in[c] + Ri[r][1] * pose_in[3 + c]) + Ri[r][2] * pose_in[6 + c];
+            out[9 + r] = ((Ri[r][0] * pose_in[9] + Ri[r][1] * pose_in[10]) + Ri[r][2] * pose_in[11]) + v[r];
+        }
+        for (int i = 0; i < 12; ++i)
+            if (!isfinite(out[i])) stats->status = 2;
+        if (stats->status != 0) memcpy(out, pose_in, sizeof out);
+    }
+    memcpy(pose_out, out, sizeof out);
+    return true;
+}
+
+bool sgm_track_world_pose(const float model_pose[12], const double rel[12], float out[12])
+{
+    if (!model_pose || !rel || !out) FAIL("sgm_track_world_pose: NULL argument");
+    for (int i = 0; i < 12; ++i)
+        if (!isfinite(model_pose[i]) || !isfinite(rel[i])) FAIL("sgm_track_world_pose: entry %d of a pose is not finite", i);
+    double m[12];
+    float res[12];
+    for (int i = 0; i < 12; ++i) m[i] = (double)model_pose[i];
+    const double dt[3] = {m[9] - rel[9], m[10] - rel[10], m[11] - rel[11]};
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) res[3 * r + c] = (float)((rel[r] * m[c] + rel[3 + r] * m[3 + c]) + rel[6 + r] * m[6 + c]);
+        res[9 + r] = (float)((rel[r] * dt[0] + rel[3 + r] * dt[1]) + rel[6 + r] * dt[2]);
+    }
+    memcpy(out, res, sizeof res);
+    return true;
+}
+
+/* What sgm_track_sums and sgm_track check before they queue anything; *disp: the map to read (source_map).  sums: the caller's
+ * device array, or NULL for the instance's own. */
+static bool track_ready(sgm_instance* s, const sgm_cloud_spec* src, const sgm_track_spec* model, const float** disp, const uint8_t* d_mask,
+                        const uint16_t* d_conf, const float* d_depth, const float* d_normal, const int64_t* sums, sgmd_cloud* c,
+                        sgmd_track* t, const char* entry)
+{
+    if (!track_available()) FAIL("%s: tracking is not part of this build", entry);
+    if (!cloud_spec_valid(src, c)) FAIL("%s: the source spec is outside its ranges", entry);
+    if (c->B > VOLUME_MAX_FRAMES) FAIL("%s: %d frames in one call (at most %d)", entry, c->B, VOLUME_MAX_FRAMES);
+    if ((long long)c->W * c->H > TRACK_MAX_PIXELS) FAIL("%s: a source of %dx%d pixels (at most 2^24: the sums are 64-bit)", entry, c->W, c->H);
+    const char* why = track_spec_invalid(model, t);
+    if (why) FAIL("%s: the model is outside its ranges (%s)", entry, why);
+    if (!aligned_to(*disp, sizeof(float)) || !aligned_to(d_conf, sizeof(uint16_t)) || !aligned_to(d_depth, sizeof(float)) ||
+        !aligned_to(d_normal, sizeof(float)) || !aligned_to(sums, sizeof(int64_t)))
+        FAIL("%s: a pointer is not aligned (the sums to 8 bytes, the others to their element)", entry);
+    *disp = source_map(s, c, *disp, entry);
+    if (!*disp) return false;
+    const size_t px = (size_t)c->B * c->W * c->H, mpx = (size_t)c->B * t->W * t->H, sum_bytes = (size_t)c->B * TRACK_SUMS * sizeof(int64_t);
+    if (ranges_overlap(sums, sum_bytes, *disp, px * sizeof(float)) || ranges_overlap(sums, sum_bytes, d_mask, px) ||
+        ranges_overlap(sums, sum_bytes, d_conf, px * sizeof(uint16_t)) || ranges_overlap(sums, sum_bytes, d_depth, mpx * sizeof(float)) ||
+        ranges_overlap(sums, sum_bytes, d_normal, 3 * mpx * sizeof(float)))
+        FAIL("%s: the sums overlap a map", entry);
+    return true;
+}
+
+bool sgm_track_sums(sgm_instance* s, const sgm_cloud_spec* src, const sgm_track_spec* model, const float* poses, const float* d_disp,
+                    const uint8_t* d_mask, const uint16_t* d_conf, const float* d_model_depth, const float* d_model_normal, int64_t* d_sums)
+{
+    sgmd_cloud c;
+    sgmd_track t;
+    if (!s || !src || !model || !poses || !d_model_depth || !d_model_normal || !d_sums) FAIL("sgm_track_sums: NULL argument");
+    if (!track_ready(s, src, model, &d_disp, d_mask, d_conf, d_model_depth, d_model_normal, d_sums, &c, &t, "sgm_track_sums")) return false;
+    for (int i = 0; i < 12 * c.B; ++i)
+        if (!isfinite(poses[i])) FAIL("sgm_track_sums: entry %d of the pose of frame %d is not finite", i % 12, i / 12);
+    /* the maps may be the work of a ray-cast on this stream and of a match: the same place in the queue as sgm_volume_raycast */
+    size_t scratch_bytes;
+    sgm_buf* scratch = track_scratch(s, &c, &scratch_bytes);
+    if (!scratch_then_wait(s, scratch, scratch_bytes, "the partial sums of tracking")) return false;
+    return sgmd_track_sums(s->device, s->stream, &c, &t, poses, d_disp, d_mask, d_conf, d_model_depth, d_model_normal,
+                           s->d_track_scratch.p, d_sums) == 0;
+}
+
+bool sgm_track(sgm_instance* s, const sgm_cloud_spec* src, const sgm_track_spec* model, double* poses, const float* d_disp,
+               const uint8_t* d_mask, const uint16_t* d_conf, const float* d_model_depth, const float* d_model_normal,
+               sgm_track_stats* stats, int64_t* trace_sums, double* trace_poses)
+{
+    sgmd_cloud c;
+    sgmd_track t;
+    if (!s || !src || !model || !poses || !d_model_depth || !d_model_normal || !stats) FAIL("sgm_track: NULL argument");
+    if (!track_ready(s, src, model, &d_disp, d_mask, d_conf, d_model_depth, d_model_normal, NULL, &c, &t, "sgm_track")) return false;
+    for (int i = 0; i < 12 * c.B; ++i)
+        if (!isfinite(poses[i]) || !isfinite((float)poses[i]))
+            FAIL("sgm_track: entry %d of the pose of frame %d is not finite as a float", i % 12, i / 12);
+    const size_t sum_bytes = (size_t)c.B * TRACK_SUMS * sizeof(int64_t);
+    size_t scratch_bytes;
+    sgm_buf* scratch = track_scratch(s, &c, &scratch_bytes);
+    if (scratch && !reserve(s, scratch, scratch_bytes, 0)) FAIL("device allocation failed for the partial sums of tracking (%zu bytes)", scratch_bytes);
+    if (!scratch_then_wait(s, &s->d_track_sums, sum_bytes, "the sums of tracking")) return false;
+    int64_t sums[VOLUME_MAX_FRAMES * TRACK_SUMS];
+    float pose32[VOLUME_MAX_FRAMES * 12];
+    bool out[VOLUME_MAX_FRAMES] = {false};                       /* a frame whose solve failed sits out the remaining rounds */
+    for (int f = 0; f < c.B; ++f) stats[f] = (sgm_track_stats){0.0, 0u, 0};
+    if (trace_poses) memcpy(trace_poses, poses, (size_t)c.B * 12 * sizeof(double));
+    for (int it = 0; it < model->iterations; ++it) {
+        for (int i = 0; i < 12 * c.B; ++i) pose32[i] = (float)poses[i];
+        if (sgmd_track_sums(s->device, s->stream, &c, &t, pose32, d_disp, d_mask, d_conf, d_model_depth, d_model_normal, s->d_track_scratch.p,
+                            s->d_track_sums.p) != 0 ||
+            sgmd_d2h_async(s->device, s->stream, sums, s->d_track_sums.p, sum_bytes) != 0 || sync_streams(s) != 0)
+            return false;
+        if (trace_sums) memcpy(trace_sums + (size_t)it * c.B * TRACK_SUMS, sums, sum_bytes);
+        for (int f = 0; f < c.B; ++f) {
+            if (out[f]) continue;
+            double next[12];
+            if (!sgm_track_solve(model, sums + f * TRACK_SUMS, poses + 12 * f, next, &stats[f])) return false;
+            for (int i = 0; i < 12; ++i)
+                if (!isfinite((float)next[i])) stats[f].status = 2;
+            if (stats[f].status != 0) out[f] = true;
+            else memcpy(poses + 12 * f, next, sizeof next);
+        }
+        if (trace_poses) memcpy(trace_poses + (size_t)(it + 1) * c.B * 12, poses, (size_t)c.B * 12 * sizeof(double));
+    }
+    return true;
 }
 
 /* ------------------------------------------------------------------ matching at 1/f scale (extension) */

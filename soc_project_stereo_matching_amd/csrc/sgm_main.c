@@ -41,6 +41,11 @@
  *                             (sgm_volume_raycast: the --pinhole intrinsics, the identity pose, the image's size), marched at
  *                             Z = ZMIN + k * STEP up to ZMAX over voxels of weight MINWEIGHT (default 1) or more: the depth as raw
  *                             float32 [H][W] like --raw, the unit normals as raw float32 [H][W][3], NaN where no surface is met
+ *            [--volume-track ITER,DISTMAX[,TX,TY,TZ]]   extension: with --volume and --volume-view, the frame tracked against that
+ *                             render (sgm_track: ITER rounds, gate DISTMAX, span the middle of the march (ZMIN + ZMAX) / 2, at least
+ *                             6 pixels, pivots above 1e-6) from the identity displaced by the translation TX,TY,TZ (default 0,0,0);
+ *                             prints the status, the associated pixels, the rms and the estimated pose source -> model camera, and
+ *                             the world -> camera pose sgm_track_world_pose makes of it
  *            [--bits N]       extension: images of N = 9..16 bits per sample (SGM_SetPixelBits): LEFT and RIGHT are loaded with
  *                             sgm_load_gray16 (binary PGM with maxval up to 65535, PNG grey of depth 16; 8-bit files are widened
  *                             unshifted) and matched on all their bits.  --bits 0: the smallest N >= 8 that holds the files' maxval.
@@ -178,6 +183,8 @@ typedef struct {
     uint32_t min_weight;
     const char* depth_path;
     const char* normals_path;
+    int track_iterations;          /* --volume-track: 0 without it */
+    float track_dist_max, track_t[3];
 } volume_view;
 
 static int write_floats(const char* path, const float* v, size_t n)
@@ -188,17 +195,41 @@ static int write_floats(const char* path, const float* v, size_t n)
     return (fclose(f) == 0 && put == n) ? 0 : -1;
 }
 
-/* the volume rendered into the frame's own camera with the identity pose, and the maps written */
+/* --volume-track: the frame tracked against its own render, from the identity displaced by the given translation */
+static int volume_track(sgm_instance* s, const volume_view* view, const sgm_cloud_spec* src, const float* d_disp, const float* d_depth,
+                        const float* d_normal)
+{
+    static const float identity[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    const sgm_track_spec model = {src->width, src->height, src->fx, src->fy, src->cx, src->cy, view->track_dist_max,
+                                  0.5f * (view->z_min + view->z_max), view->track_iterations, 6, 1e-6f};
+    double pose[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, view->track_t[0], view->track_t[1], view->track_t[2]};
+    sgm_track_stats stats;
+    float world[12];
+    if (!sgm_track(s, src, &model, pose, d_disp, NULL, NULL, d_depth, d_normal, &stats, NULL, NULL) ||
+        !sgm_track_world_pose(identity, pose, world))
+        return -1;
+    printf("volume track: frame 0 status %d, %u pixels, rms %.17g\n", stats.status, stats.pixels, stats.rms);
+    printf("volume track: pose");
+    for (int i = 0; i < 12; ++i) printf(" %.17g", pose[i]);
+    printf("\nvolume track: world pose");
+    for (int i = 0; i < 12; ++i) printf(" %.9g", (double)world[i]);
+    printf("\n");
+    return 0;
+}
+
+/* the volume rendered into the frame's own camera with the identity pose, and the maps written; with --volume-track the frame
+ * (src, d_disp) tracked against that render, which then has normals whether they are written or not */
 static int volume_render(sgm_instance* s, const sgm_volume_spec* vol, const volume_view* view, int w, int h, const float* pinhole,
-                         const uint32_t* d_voxels)
+                         const uint32_t* d_voxels, const sgm_cloud_spec* src, const float* d_disp)
 {
     static const float identity[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
     const sgm_raycast_spec spec = {w, h, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], view->z_min, view->z_max, view->step, view->min_weight};
     const size_t px = (size_t)w * h;
     float* d_depth = (float*)sgm_host_alloc(s, px * sizeof(float));
-    float* d_normal = view->normals_path ? (float*)sgm_host_alloc(s, 3 * px * sizeof(float)) : NULL;
+    const int normals = view->normals_path || view->track_iterations;
+    float* d_normal = normals ? (float*)sgm_host_alloc(s, 3 * px * sizeof(float)) : NULL;
     int rc = -1;
-    if (d_depth && (d_normal || !view->normals_path) && sgm_volume_raycast(s, vol, &spec, identity, d_voxels, d_depth, d_normal) &&
+    if (d_depth && (d_normal || !normals) && sgm_volume_raycast(s, vol, &spec, identity, d_voxels, d_depth, d_normal) &&
         sgm_synchronize(s)) {
         size_t hits = 0;
         for (size_t i = 0; i < px; ++i) hits += d_depth[i] == d_depth[i];
@@ -206,6 +237,7 @@ static int volume_render(sgm_instance* s, const sgm_volume_spec* vol, const volu
         rc = 0;
         if (view->depth_path && write_floats(view->depth_path, d_depth, px) != 0) rc = -1;
         if (view->normals_path && write_floats(view->normals_path, d_normal, 3 * px) != 0) rc = -1;
+        if (rc == 0 && view->track_iterations) rc = volume_track(s, view, src, d_disp, d_depth, d_normal);
     }
     sgm_host_free(s, d_depth);
     sgm_host_free(s, d_normal);
@@ -256,7 +288,7 @@ static int volume_surface(const sgm_volume_spec* vol, const volume_view* view, i
                     (*out)[i] = (sgm_point){q.x, q.y, q.z, ((uint32_t)v << 16) | (uint32_t)u};
                 }
                 *n = count;
-                rc = view ? volume_render(s, vol, view, w, h, pinhole, d_voxels) : 0;
+                rc = view ? volume_render(s, vol, view, w, h, pinhole, d_voxels, &src, d_disp) : 0;
             }
         }
     }
@@ -328,7 +360,8 @@ int main(int argc, char** argv)
     const char* volume_path = NULL;
     sgm_volume_spec volume = {0, 0, 0, 0.0f, {0.0f, 0.0f, 0.0f}, 0.0f, 65535};
     int have_volume = 0;
-    volume_view view = {0.0f, 0.0f, 0.0f, 1, NULL, NULL};
+    volume_view view = {0.0f, 0.0f, 0.0f, 1, NULL, NULL, 0, 0.0f, {0.0f, 0.0f, 0.0f}};
+    int have_track = 0;
     int have_view = 0;
     int register_splat = 2, register_splat_set = 0;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
@@ -384,6 +417,16 @@ int main(int argc, char** argv)
         }
         else if (v && !strcmp(a, "--volume-depth")) { view.depth_path = v; ++i; }
         else if (v && !strcmp(a, "--volume-normals")) { view.normals_path = v; ++i; }
+        else if (v && !strcmp(a, "--volume-track")) {
+            const int got = sscanf(v, "%d,%f,%f,%f,%f", &view.track_iterations, &view.track_dist_max, &view.track_t[0], &view.track_t[1],
+                                   &view.track_t[2]);
+            if ((got != 2 && got != 5) || view.track_iterations < 1) {
+                fprintf(stderr, "--volume-track wants ITER,DISTMAX[,TX,TY,TZ] with ITER >= 1\n");
+                return 2;
+            }
+            have_track = 1;
+            ++i;
+        }
         else if (v && !strcmp(a, "--register-splat")) {
             if (strcmp(v, "1") && strcmp(v, "2")) { fprintf(stderr, "--register-splat wants 1 or 2\n"); return 2; }
             register_splat = atoi(v);
@@ -437,7 +480,11 @@ int main(int argc, char** argv)
         fprintf(stderr, "--volume-view, --volume-depth and --volume-normals need --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n");
         return 2;
     }
-    if (have_view != (view.depth_path || view.normals_path)) {
+    if (have_track && (!have_volume || !have_view)) {
+        fprintf(stderr, "--volume-track needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC and --volume-view ZMIN,ZMAX,STEP[,MINWEIGHT]\n");
+        return 2;
+    }
+    if (have_view != (view.depth_path || view.normals_path || have_track)) {
         fprintf(stderr, "--volume-view ZMIN,ZMAX,STEP[,MINWEIGHT] and --volume-depth / --volume-normals OUT.f32 come together\n");
         return 2;
     }

@@ -156,6 +156,54 @@ def raycast_spec(width, height, fx, fy, cx, cy, z_min, z_max, step, min_weight=1
     return SGMRaycastSpec(int(width), int(height), int(frames), fx, fy, cx, cy, z_min, z_max, step, int(min_weight))
 
 
+class SGMTrackSpec(C.Structure):
+    """Field-for-field sgm_track_spec of include/sgm_mi355x.h: 44 bytes, every field 4 bytes."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("dist_max", C.c_float), ("span", C.c_float),
+        ("iterations", C.c_int32), ("min_pixels", C.c_uint32), ("min_pivot", C.c_float),
+    ]
+
+
+class SGMTrackStats(C.Structure):
+    """sgm_track_stats of include/sgm_mi355x.h: 16 bytes; status 0 ok, 1 too few pixels, 2 degenerate."""
+    _fields_ = [("rms", C.c_double), ("pixels", C.c_uint32), ("status", C.c_int32)]
+
+
+def track_spec(width, height, fx, fy, cx, cy, dist_max, span, iterations=1, min_pixels=6, min_pivot=0.0) -> SGMTrackSpec:
+    """A sgm_track_spec: the model maps' size and pinhole, the association gate dist_max (also the unit of the residual), the length
+    `span` that normalises the rotational Jacobian (about the scene depth), the rounds of SGMInstance.track and the two thresholds
+    of the solve."""
+    return SGMTrackSpec(int(width), int(height), fx, fy, cx, cy, dist_max, span, int(iterations), int(min_pixels), min_pivot)
+
+
+def track_solve(model: SGMTrackSpec, sums, pose):
+    """sgm_track_solve (host only): one step from the 29 sums of a frame -> (the stepped pose, float64 [12], or `pose` where the
+    status is not 0; a dict of pixels, rms and status).  None for a refused call."""
+    sums = np.ascontiguousarray(sums, np.int64).reshape(-1)
+    pose = np.ascontiguousarray(pose, np.float64).reshape(-1)
+    if sums.size != 29 or pose.size != 12:
+        raise ValueError("track_solve: 29 sums and a pose of 12 doubles")
+    out, st = np.empty(12, np.float64), SGMTrackStats()
+    if not load_library().sgm_track_solve(C.byref(model), sums.ctypes.data, pose.ctypes.data, out.ctypes.data, C.byref(st)):
+        return None
+    return out, dict(pixels=int(st.pixels), rms=float(st.rms), status=int(st.status))
+
+
+def track_world_pose(model_pose, rel):
+    """sgm_track_world_pose (host only): rel^-1 o model_pose as float32 [12], the world -> camera pose of the tracked frame; None
+    for a refused call."""
+    model_pose = np.ascontiguousarray(model_pose, np.float32).reshape(-1)
+    rel = np.ascontiguousarray(rel, np.float64).reshape(-1)
+    if model_pose.size != 12 or rel.size != 12:
+        raise ValueError("track_world_pose: two poses of 12 entries")
+    out = np.empty(12, np.float32)
+    if not load_library().sgm_track_world_pose(model_pose.ctypes.data, rel.ctypes.data, out.ctypes.data):
+        return None
+    return out
+
+
 class SGMScaleSpec(C.Structure):
     """Field-for-field sgm_scale_spec of include/sgm_mi355x.h: 36 bytes, every field 4 bytes."""
     _fields_ = [
@@ -359,6 +407,15 @@ def _load() -> C.CDLL:
     if hasattr(L, "sgm_volume_raycast"):      # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_volume_raycast.argtypes = [C.c_void_p] * 7
         L.sgm_volume_raycast.restype = C.c_bool
+    if hasattr(L, "sgm_track_sums"):          # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_track_sums.argtypes = [C.c_void_p] * 10
+        L.sgm_track_sums.restype = C.c_bool
+        L.sgm_track_solve.argtypes = [C.c_void_p] * 5
+        L.sgm_track_solve.restype = C.c_bool
+        L.sgm_track.argtypes = [C.c_void_p] * 12
+        L.sgm_track.restype = C.c_bool
+        L.sgm_track_world_pose.argtypes = [C.c_void_p] * 3
+        L.sgm_track_world_pose.restype = C.c_bool
     if hasattr(L, "sgm_set_temporal"):        # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_temporal_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t] + [C.c_void_p] * 5
         L.sgm_temporal_filter.restype = C.c_bool
@@ -1223,6 +1280,38 @@ class SGMInstance(_StageReader):
             raise ValueError("volume_raycast: one pose of 12 floats (R row-major, then t) per frame")
         return bool(self.lib.sgm_volume_raycast(self.handle, C.byref(vol), C.byref(view), poses.ctypes.data, d_voxels, d_depth,
                                                 d_normal or None))
+
+    # ---- frame-to-model tracking (include/sgm_mi355x.h, sgm_track_spec); device pointers as ints, None = NULL ----
+    def track_sums(self, src: SGMCloudSpec, model: SGMTrackSpec, poses, d_disp, d_mask, d_conf, d_model_depth: int, d_model_normal: int,
+                   d_sums: int) -> bool:
+        """sgm_track_sums: the 29 int64 sums of every frame into d_sums ([frames][29], 8-byte aligned) for the kept pixels of src
+        moved by poses ([frames][12] host floats, source camera -> model camera, read before the call returns) against the model
+        maps as volume_raycast writes them.  d_disp None: the final map of the last match.  Asynchronous on `stream`."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1)
+        if poses.size != 12 * src.frames:
+            raise ValueError("track_sums: one pose of 12 floats (R row-major, then t) per frame")
+        return bool(self.lib.sgm_track_sums(self.handle, C.byref(src), C.byref(model), poses.ctypes.data, d_disp or None, d_mask or None,
+                                            d_conf or None, d_model_depth, d_model_normal, d_sums))
+
+    def track(self, src: SGMCloudSpec, model: SGMTrackSpec, poses, d_disp, d_mask, d_conf, d_model_depth: int, d_model_normal: int,
+              trace: bool = False):
+        """sgm_track (blocking): model.iterations rounds from the guess `poses` ([frames][12] doubles) -> (the estimate, float64
+        [frames][12]; a list of dicts of pixels, rms and status per frame), with trace=True also the sums of every round (int64
+        [iterations][frames][29]) and the poses before and after every round (float64 [iterations + 1][frames][12]).  None for a
+        refused or failed call."""
+        poses = np.array(poses, np.float64).reshape(-1)
+        if poses.size != 12 * src.frames:
+            raise ValueError("track: one pose of 12 doubles (R row-major, then t) per frame")
+        stats = (SGMTrackStats * src.frames)()
+        n = max(int(model.iterations), 0)
+        t_sums = np.zeros((n, src.frames, 29), np.int64) if trace else None
+        t_poses = np.zeros((n + 1, src.frames, 12), np.float64) if trace else None
+        if not self.lib.sgm_track(self.handle, C.byref(src), C.byref(model), poses.ctypes.data, d_disp or None, d_mask or None,
+                                  d_conf or None, d_model_depth, d_model_normal, C.addressof(stats),
+                                  t_sums.ctypes.data if trace else None, t_poses.ctypes.data if trace else None):
+            return None
+        out = [dict(pixels=int(st.pixels), rms=float(st.rms), status=int(st.status)) for st in stats]
+        return (poses.reshape(src.frames, 12), out, t_sums, t_poses) if trace else (poses.reshape(src.frames, 12), out)
 
     # ---- matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); device pointers as ints, None = NULL ----
     def downscale(self, spec: SGMScaleSpec, d_in: int, d_out: int) -> bool:
