@@ -1,7 +1,8 @@
 #pragma once
 // What sgm_cloud.hip, sgm_register.hip, sgm_volume.hip and sgm_track.hip share.  The source map: the predicate, the formulas and
 // the load paths of the point clouds (include/sgm_mi355x.h, sgm_cloud_spec) and, for the launchers, the one reading of a
-// sgmd_cloud.  The ordered
+// sgmd_cloud.  A point into another camera: the rigid move, the pinhole to the nearest admitted pixel and the block of poses a
+// launch takes.  The ordered
 // compaction of the point list and the surface list: its device pieces, its tile size and its scratch.  Include after sgm_common.hpp.
 
 struct CloudParams {
@@ -26,6 +27,33 @@ static __device__ __forceinline__ void cloud_xy(const CloudParams& c, unsigned x
 {
     X = (((float)x - c.cx) * Z) / c.fx;
     Y = (((float)y - c.cy) * Z) / c.fy;
+}
+
+// ---- a point into another camera: the rigid move, the pinhole, the nearest pixel.  The parentheses are the contracts'. --------------
+
+// the poses of a launch's frames, R row-major then t each: 3 KiB of the 4 KiB a kernel's arguments may take, read with scalar loads
+struct PoseBlock { float p[SGMD_MAX_POSES][12]; };
+static_assert(sizeof(PoseBlock) == 3072, "the poses travel as kernel arguments");
+
+static __device__ __forceinline__ void pose_move(const float* R, const float* t, float x, float y, float z, float& X, float& Y, float& Z)
+{
+    X = ((R[0] * x + R[1] * y) + R[2] * z) + t[0];
+    Y = ((R[3] * x + R[4] * y) + R[5] * z) + t[1];
+    Z = ((R[6] * x + R[7] * y) + R[8] * z) + t[2];
+}
+
+// (X, Y, Z) in front of a pinhole -> the nearest pixel (uf, vf) of a wf x hf image; false where it has none
+static __device__ __forceinline__ bool pinhole_pixel(float fx, float fy, float cx, float cy, float wf, float hf, float X, float Y, float Z,
+                                                     float& uf, float& vf)
+{
+    if (!cloud_finite(Z)) return false;
+    if (!(Z > 0.0f)) return false;
+    const float u = fx * (X / Z) + cx, v = fy * (Y / Z) + cy;
+    if (!cloud_finite(u) || !cloud_finite(v)) return false;
+    uf = floorf(u + 0.5f);
+    vf = floorf(v + 0.5f);
+    // admitted in float, before any conversion to int
+    return 0.0f <= uf && uf < wf && 0.0f <= vf && vf < hf;
 }
 
 // ---- the ordered compaction: count per tile, scan, emit ---------------------------------------------------------------------------
@@ -178,6 +206,15 @@ static CloudParams cloud_params(const sgmd_cloud* c)
 static bool cloud_vector(const sgmd_cloud* c, const void* disp, const void* mask, const void* conf)
 {
     return ((size_t)c->W * c->H) % 4 == 0 && (uintptr_t)disp % 16 == 0 && (uintptr_t)mask % 4 == 0 && (uintptr_t)conf % 8 == 0;
+}
+
+// the poses of `frames` frames ([frames][12], frames <= SGMD_MAX_POSES) as the kernel argument, the rest zero
+static PoseBlock pose_block(const float* poses, int frames)
+{
+    PoseBlock b;
+    memset(&b, 0, sizeof b);
+    memcpy(b.p, poses, (size_t)frames * 12 * sizeof(float));
+    return b;
 }
 
 // the tile of a compaction over runs of n items: a power of two, at most TILE_MAX, at least 1

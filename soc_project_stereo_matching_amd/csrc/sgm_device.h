@@ -299,6 +299,10 @@ int sgmd_register_depth(int ord, void* stream, const sgmd_cloud* c, const sgmd_r
 int sgmd_register_gather(int ord, void* stream, const sgmd_cloud* c, const sgmd_register* r, const void* source, int elem_bytes,
                          const void* map, unsigned fill, void* out);
 
+/* The frames of one call of the volume's integration, its ray-cast and tracking, one pose each: the poses travel as kernel
+ * arguments, 3 KiB of the 4 KiB a launch may take */
+#define SGMD_MAX_POSES 64
+
 /* Extension (parity unpinned by the reference), depth fused into a TSDF volume (include/sgm_mi355x.h, sgm_volume_spec);
  * sgm_volume.hip.  v: the volume as the host validated it; c: the source as the cloud entry points take it (c->B <= 64).
  * sgmd_volume_integrate: poses (HOST, [c->B][12], read before it returns: they travel as kernel arguments), disp, mask, conf
@@ -333,16 +337,14 @@ int sgmd_volume_raycast(int ord, void* stream, const sgmd_volume* v, const sgmd_
  * sgm_track.hip.  c: the source as the host validated it (c->B <= 64 frames, one pose each, c->W * c->H <= 2^24); t: the model view.
  * poses: HOST, [c->B][12], source camera -> model camera, read before it returns.  model_depth f32 [B][t->H][t->W], model_normal
  * f32 [B][t->H][t->W][3]; sums int64 [B][29], 8-byte aligned, zeroed on the stream and then added to with integer atomics.
- * scratch: sgmd_track_scratch_bytes(W, H, B) bytes, 8-byte aligned -- 0 bytes (scratch may be NULL) in the default build; a build
- * with make TRACK_FOLD=1 keeps the workgroups' partial sums there and folds them with a second launch.  sgm_host.c references both
- * weakly, on their own: a host built without them answers false to sgm_track_sums and sgm_track. */
+ * One launch, no scratch.  sgm_host.c references it weakly, on its own: a host built without it answers false to sgm_track_sums and
+ * sgm_track. */
 typedef struct {
     int W, H;
     float fx, fy, cx, cy, dist_max, span;
 } sgmd_track;
-size_t sgmd_track_scratch_bytes(int W, int H, int B);
 int sgmd_track_sums(int ord, void* stream, const sgmd_cloud* c, const sgmd_track* t, const float* poses, const void* disp,
-                    const void* mask, const void* conf, const void* model_depth, const void* model_normal, void* scratch, void* sums);
+                    const void* mask, const void* conf, const void* model_depth, const void* model_normal, void* sums);
 
 /* Extension (parity unpinned by the reference), matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); sgm_scale.hip.
  * c: the spec as the host validated it (W, H: FULL resolution; the low resolution is W / f x H / f).  sgmd_downscale: the f x f box

@@ -164,7 +164,7 @@ struct sgm_instance {
     sgm_buf d_volume_scratch;
     /* tracking (allocated at the first such call): the sums of a round of sgm_track, 29 int64 per frame, and whatever scratch the
      * launcher asks for (none in the default build) */
-    sgm_buf d_track_sums, d_track_scratch;
+    sgm_buf d_track_sums;
     /* matching at 1/f scale (sgm_match_scaled; allocated at its first use): the downscaled views, the census planes of the
      * FULL-resolution views with the narrowed images sgmd_census16 writes beside them, and for the host-pointer form the full
      * images, the full map and their page-locked staging */
@@ -216,7 +216,7 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     DEVICE_BUF(d_sc_small_l), DEVICE_BUF(d_sc_small_r), DEVICE_BUF(d_sc_census_l), DEVICE_BUF(d_sc_census_r), DEVICE_BUF(d_sc_g8_l),
     DEVICE_BUF(d_sc_g8_r), DEVICE_BUF(d_sc_full_l), DEVICE_BUF(d_sc_full_r), DEVICE_BUF(d_sc_disp), PINNED_BUF(h_sc_l), PINNED_BUF(h_sc_r),
     PINNED_BUF(h_sc_disp), DEVICE_BUF(d_tp_value), DEVICE_BUF(d_tp_bits), DEVICE_BUF(d_tp_stats), DEVICE_BUF(d_tp_pre),
-    DEVICE_BUF(d_tp_scratch), DEVICE_BUF(d_register_keys), DEVICE_BUF(d_volume_scratch), DEVICE_BUF(d_track_sums), DEVICE_BUF(d_track_scratch),
+    DEVICE_BUF(d_tp_scratch), DEVICE_BUF(d_register_keys), DEVICE_BUF(d_volume_scratch), DEVICE_BUF(d_track_sums),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -2320,8 +2320,6 @@ bool sgm_register_spec_raw(const double K[9], const double dist[5], const double
 #pragma weak sgmd_volume_points
 static bool volume_available(void) { return sgmd_volume_scratch_bytes != NULL && sgmd_volume_integrate != NULL && sgmd_volume_points != NULL; }
 
-#define VOLUME_MAX_FRAMES 64    /* the poses travel as kernel arguments */
-
 /* the volume as the kernels take it; false for anything outside the ranges of include/sgm_mi355x.h */
 static bool volume_spec_valid(const sgm_volume_spec* sp, sgmd_volume* v)
 {
@@ -2334,11 +2332,21 @@ static bool volume_spec_valid(const sgm_volume_spec* sp, sgmd_volume* v)
     return true;
 }
 
+static size_t volume_bytes(const sgmd_volume* v) { return (size_t)v->nx * v->ny * v->nz * sizeof(uint32_t); }
+
 size_t sgm_volume_bytes(const sgm_volume_spec* spec)
 {
     sgmd_volume v;
     if (!spec || !volume_spec_valid(spec, &v)) return 0;
-    return (size_t)v.nx * v.ny * v.nz * sizeof(uint32_t);
+    return volume_bytes(&v);
+}
+
+/* every entry of the poses of `frames` frames is finite */
+static bool poses_finite(const char* entry, const float* poses, int frames)
+{
+    for (int i = 0; i < 12 * frames; ++i)
+        if (!isfinite(poses[i])) FAIL("%s: entry %d of the pose of frame %d is not finite", entry, i % 12, i / 12);
+    return true;
 }
 
 bool sgm_volume_integrate(sgm_instance* s, const sgm_volume_spec* spec, const sgm_cloud_spec* src, const float* poses, const float* d_disp,
@@ -2350,14 +2358,13 @@ bool sgm_volume_integrate(sgm_instance* s, const sgm_volume_spec* spec, const sg
     if (!volume_available()) FAIL("the volume is not part of this build");
     if (!volume_spec_valid(spec, &v)) FAIL("sgm_volume_integrate: the volume spec is outside its ranges");
     if (!cloud_spec_valid(src, &c)) FAIL("sgm_volume_integrate: the source spec is outside its ranges");
-    if (c.B > VOLUME_MAX_FRAMES) FAIL("sgm_volume_integrate: %d frames in one call (at most %d)", c.B, VOLUME_MAX_FRAMES);
-    for (int i = 0; i < 12 * c.B; ++i)
-        if (!isfinite(poses[i])) FAIL("sgm_volume_integrate: entry %d of the pose of frame %d is not finite", i % 12, i / 12);
+    if (c.B > SGMD_MAX_POSES) FAIL("sgm_volume_integrate: %d frames in one call (at most %d)", c.B, SGMD_MAX_POSES);
+    if (!poses_finite("sgm_volume_integrate", poses, c.B)) return false;
     if (!aligned_to(d_disp, sizeof(float)) || !aligned_to(d_conf, sizeof(uint16_t)) || !aligned_to(d_voxels, sizeof(uint32_t)))
         FAIL("sgm_volume_integrate: a pointer is not aligned to its element");
     d_disp = source_map(s, &c, d_disp, "sgm_volume_integrate");
     if (!d_disp) return false;
-    const size_t px = (size_t)c.B * c.W * c.H, vol_bytes = (size_t)v.nx * v.ny * v.nz * sizeof(uint32_t);
+    const size_t px = (size_t)c.B * c.W * c.H, vol_bytes = volume_bytes(&v);
     if (ranges_overlap(d_voxels, vol_bytes, d_disp, px * sizeof(float)) || ranges_overlap(d_voxels, vol_bytes, d_mask, px) ||
         ranges_overlap(d_voxels, vol_bytes, d_conf, px * sizeof(uint16_t)))
         FAIL("sgm_volume_integrate: the volume aliases a map");
@@ -2376,7 +2383,7 @@ bool sgm_volume_points(sgm_instance* s, const sgm_volume_spec* spec, const uint3
     if (min_weight < 1u || min_weight > 65535u) FAIL("sgm_volume_points: a min_weight of %u (1..65535)", min_weight);
     if (!aligned_to(d_voxels, sizeof(uint32_t)) || !aligned_to(d_points, sizeof(sgm_surface_point)) || !aligned_to(d_count, sizeof(uint32_t)))
         FAIL("sgm_volume_points: a pointer is not aligned (the points to 16 bytes, the others to their element)");
-    const size_t n = (size_t)v.nx * v.ny * v.nz, vol_bytes = n * sizeof(uint32_t);
+    const size_t vol_bytes = volume_bytes(&v), n = vol_bytes / sizeof(uint32_t);
     /* (no more than three crossings per voxel can be written, whatever the capacity says) */
     const size_t pts_bytes = (capacity < 3 * n ? capacity : 3 * n) * sizeof(sgm_surface_point);
     if (ranges_overlap(d_points, pts_bytes, d_voxels, vol_bytes) || ranges_overlap(d_count, sizeof(uint32_t), d_voxels, vol_bytes) ||
@@ -2393,7 +2400,7 @@ static bool raycast_available(void) { return sgmd_volume_raycast != NULL; }
 /* the view as the kernel takes it; NULL, or what is outside the ranges of include/sgm_mi355x.h */
 static const char* raycast_spec_invalid(const sgm_raycast_spec* sp, sgmd_raycast* r)
 {
-    if (sp->frames < 1 || sp->frames > VOLUME_MAX_FRAMES) return "1..64 frames in one call (the poses travel as kernel arguments)";
+    if (sp->frames < 1 || sp->frames > SGMD_MAX_POSES) return "1..64 frames in one call (the poses travel as kernel arguments)";
     if (!frame_size_valid(sp->width, sp->height, sp->frames)) return "width and height 1..65535, frames*width*height <= 2^31";
     if (!finite_positive(sp->fx) || !finite_positive(sp->fy)) return "fx, fy finite and > 0";
     if (!isfinite(sp->cx) || !isfinite(sp->cy)) return "cx, cy finite";
@@ -2416,11 +2423,10 @@ bool sgm_volume_raycast(sgm_instance* s, const sgm_volume_spec* vol, const sgm_r
     if (!volume_spec_valid(vol, &v)) FAIL("sgm_volume_raycast: the volume spec is outside its ranges");
     const char* why = raycast_spec_invalid(view, &r);
     if (why) FAIL("sgm_volume_raycast: the view is outside its ranges (%s)", why);
-    for (int i = 0; i < 12 * r.B; ++i)
-        if (!isfinite(poses[i])) FAIL("sgm_volume_raycast: entry %d of the pose of frame %d is not finite", i % 12, i / 12);
+    if (!poses_finite("sgm_volume_raycast", poses, r.B)) return false;
     if (!aligned_to(d_voxels, sizeof(uint32_t)) || !aligned_to(d_depth, sizeof(float)) || !aligned_to(d_normal, sizeof(float)))
         FAIL("sgm_volume_raycast: a pointer is not aligned to its element");
-    const size_t vol_bytes = (size_t)v.nx * v.ny * v.nz * sizeof(uint32_t), depth_bytes = (size_t)r.B * r.W * r.H * sizeof(float);
+    const size_t vol_bytes = volume_bytes(&v), depth_bytes = (size_t)r.B * r.W * r.H * sizeof(float);
     if (ranges_overlap(d_depth, depth_bytes, d_voxels, vol_bytes) || ranges_overlap(d_normal, 3 * depth_bytes, d_voxels, vol_bytes) ||
         ranges_overlap(d_normal, 3 * depth_bytes, d_depth, depth_bytes))
         FAIL("sgm_volume_raycast: an output overlaps the volume or the other output");
@@ -2431,18 +2437,9 @@ bool sgm_volume_raycast(sgm_instance* s, const sgm_volume_spec* vol, const sgm_r
 
 /* ------------------------------------------------------------------ frame-to-model tracking (extension) */
 
-/* The launcher of sgm_track.hip and its scratch size, weak symbols of their own: a host built without them keeps the volume and
- * the ray-cast */
-#pragma weak sgmd_track_scratch_bytes
+/* The launcher of sgm_track.hip, a weak symbol of its own: a host built without it keeps the volume and the ray-cast */
 #pragma weak sgmd_track_sums
-static bool track_available(void) { return sgmd_track_scratch_bytes != NULL && sgmd_track_sums != NULL; }
-
-/* the launcher's scratch (b == NULL for a launcher that wants none), reserved at the first call that needs it */
-static sgm_buf* track_scratch(sgm_instance* s, const sgmd_cloud* c, size_t* bytes)
-{
-    *bytes = sgmd_track_scratch_bytes(c->W, c->H, c->B);
-    return *bytes ? &s->d_track_scratch : NULL;
-}
+static bool track_available(void) { return sgmd_track_sums != NULL; }
 
 #define TRACK_SUMS 29
 #define TRACK_MAX_PIXELS (1LL << 24)    /* per frame: a term is at most 2^38, a sum stays at or below 2^62 */
@@ -2554,7 +2551,7 @@ static bool track_ready(sgm_instance* s, const sgm_cloud_spec* src, const sgm_tr
 {
     if (!track_available()) FAIL("%s: tracking is not part of this build", entry);
     if (!cloud_spec_valid(src, c)) FAIL("%s: the source spec is outside its ranges", entry);
-    if (c->B > VOLUME_MAX_FRAMES) FAIL("%s: %d frames in one call (at most %d)", entry, c->B, VOLUME_MAX_FRAMES);
+    if (c->B > SGMD_MAX_POSES) FAIL("%s: %d frames in one call (at most %d)", entry, c->B, SGMD_MAX_POSES);
     if ((long long)c->W * c->H > TRACK_MAX_PIXELS) FAIL("%s: a source of %dx%d pixels (at most 2^24: the sums are 64-bit)", entry, c->W, c->H);
     const char* why = track_spec_invalid(model, t);
     if (why) FAIL("%s: the model is outside its ranges (%s)", entry, why);
@@ -2578,14 +2575,10 @@ bool sgm_track_sums(sgm_instance* s, const sgm_cloud_spec* src, const sgm_track_
     sgmd_track t;
     if (!s || !src || !model || !poses || !d_model_depth || !d_model_normal || !d_sums) FAIL("sgm_track_sums: NULL argument");
     if (!track_ready(s, src, model, &d_disp, d_mask, d_conf, d_model_depth, d_model_normal, d_sums, &c, &t, "sgm_track_sums")) return false;
-    for (int i = 0; i < 12 * c.B; ++i)
-        if (!isfinite(poses[i])) FAIL("sgm_track_sums: entry %d of the pose of frame %d is not finite", i % 12, i / 12);
+    if (!poses_finite("sgm_track_sums", poses, c.B)) return false;
     /* the maps may be the work of a ray-cast on this stream and of a match: the same place in the queue as sgm_volume_raycast */
-    size_t scratch_bytes;
-    sgm_buf* scratch = track_scratch(s, &c, &scratch_bytes);
-    if (!scratch_then_wait(s, scratch, scratch_bytes, "the partial sums of tracking")) return false;
-    return sgmd_track_sums(s->device, s->stream, &c, &t, poses, d_disp, d_mask, d_conf, d_model_depth, d_model_normal,
-                           s->d_track_scratch.p, d_sums) == 0;
+    if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
+    return sgmd_track_sums(s->device, s->stream, &c, &t, poses, d_disp, d_mask, d_conf, d_model_depth, d_model_normal, d_sums) == 0;
 }
 
 bool sgm_track(sgm_instance* s, const sgm_cloud_spec* src, const sgm_track_spec* model, double* poses, const float* d_disp,
@@ -2600,19 +2593,15 @@ bool sgm_track(sgm_instance* s, const sgm_cloud_spec* src, const sgm_track_spec*
         if (!isfinite(poses[i]) || !isfinite((float)poses[i]))
             FAIL("sgm_track: entry %d of the pose of frame %d is not finite as a float", i % 12, i / 12);
     const size_t sum_bytes = (size_t)c.B * TRACK_SUMS * sizeof(int64_t);
-    size_t scratch_bytes;
-    sgm_buf* scratch = track_scratch(s, &c, &scratch_bytes);
-    if (scratch && !reserve(s, scratch, scratch_bytes, 0)) FAIL("device allocation failed for the partial sums of tracking (%zu bytes)", scratch_bytes);
     if (!scratch_then_wait(s, &s->d_track_sums, sum_bytes, "the sums of tracking")) return false;
-    int64_t sums[VOLUME_MAX_FRAMES * TRACK_SUMS];
-    float pose32[VOLUME_MAX_FRAMES * 12];
-    bool out[VOLUME_MAX_FRAMES] = {false};                       /* a frame whose solve failed sits out the remaining rounds */
+    int64_t sums[SGMD_MAX_POSES * TRACK_SUMS];
+    float pose32[SGMD_MAX_POSES * 12];
+    bool out[SGMD_MAX_POSES] = {false};                       /* a frame whose solve failed sits out the remaining rounds */
     for (int f = 0; f < c.B; ++f) stats[f] = (sgm_track_stats){0.0, 0u, 0};
     if (trace_poses) memcpy(trace_poses, poses, (size_t)c.B * 12 * sizeof(double));
     for (int it = 0; it < model->iterations; ++it) {
         for (int i = 0; i < 12 * c.B; ++i) pose32[i] = (float)poses[i];
-        if (sgmd_track_sums(s->device, s->stream, &c, &t, pose32, d_disp, d_mask, d_conf, d_model_depth, d_model_normal, s->d_track_scratch.p,
-                            s->d_track_sums.p) != 0 ||
+        if (sgmd_track_sums(s->device, s->stream, &c, &t, pose32, d_disp, d_mask, d_conf, d_model_depth, d_model_normal, s->d_track_sums.p) != 0 ||
             sgmd_d2h_async(s->device, s->stream, sums, s->d_track_sums.p, sum_bytes) != 0 || sync_streams(s) != 0)
             return false;
         if (trace_sums) memcpy(trace_sums + (size_t)it * c.B * TRACK_SUMS, sums, sum_bytes);

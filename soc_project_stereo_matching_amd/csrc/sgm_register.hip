@@ -27,12 +27,8 @@
 #define REG_QNAN 0x7FC00000u
 #define REG_NONE 0xFFFFFFFFu
 // The pre-check: read the key first (agent scope, relaxed) and skip the atomic when it is already <= this candidate's.  Keys only
-// fall, so a stale read costs one redundant atomic and never a wrong result.  SGM_REGISTER_PRECHECK (make REG_PRECHECK=...): 0 never,
-// 1 at either splat, 2 at splat 2 only -- what was measured to be faster (NOTES.md section 29): at splat 1 a key sees about one
-// candidate and the load is wasted, at splat 2 it sees about four and the later ones are often beaten already.
-#ifndef SGM_REGISTER_PRECHECK
-#define SGM_REGISTER_PRECHECK 2
-#endif
+// fall, so a stale read costs one redundant atomic and never a wrong result.  At splat 2 only (NOTES.md section 29): at splat 1 a key
+// sees about one candidate and the load is wasted, at splat 2 it sees about four and the later ones are often beaten already.
 
 typedef unsigned long long reg_key;
 
@@ -49,7 +45,8 @@ struct RegisterParams {
 template <bool PRECHECK>
 static __device__ __forceinline__ void register_vote(reg_key* __restrict__ keys, const RegisterParams& r, float uf, float vf, reg_key k)
 {
-    // admitted in float, before any conversion to int
+    // admitted in float, before any conversion to int (pinhole_pixel's test, written out here: behind a shared helper the four
+    // votes of splat 2 compiled to another control flow, 6 % slower -- NOTES.md section 36)
     if (!(0.0f <= uf && uf < r.wf && 0.0f <= vf && vf < r.hf)) return;
     reg_key* at = keys + (size_t)(unsigned)vf * r.W + (unsigned)uf;
     if constexpr (PRECHECK) {
@@ -63,9 +60,8 @@ static __device__ __forceinline__ void register_vote(reg_key* __restrict__ keys,
 static __device__ __forceinline__ void register_point(reg_key* __restrict__ keys, const RegisterParams& r, unsigned x, unsigned y,
                                                       float X, float Y, float Z)
 {
-    const float Xp = ((r.R[0] * X + r.R[1] * Y) + r.R[2] * Z) + r.t[0];
-    const float Yp = ((r.R[3] * X + r.R[4] * Y) + r.R[5] * Z) + r.t[1];
-    const float Zp = ((r.R[6] * X + r.R[7] * Y) + r.R[8] * Z) + r.t[2];
+    float Xp, Yp, Zp;
+    pose_move(r.R, r.t, X, Y, Z, Xp, Yp, Zp);
     if (!cloud_finite(Zp)) return;
     if (!(Zp > 0.0f && r.z_min <= Zp && Zp <= r.z_max)) return;
     const float a = Xp / Zp, b = Yp / Zp;
@@ -78,14 +74,14 @@ static __device__ __forceinline__ void register_point(reg_key* __restrict__ keys
     if (!cloud_finite(u) || !cloud_finite(v)) return;
     const reg_key k = ((reg_key)__float_as_uint(Zp) << 32) | (reg_key)((y << 16) | x);
     if (r.splat == 1) {
-        register_vote<SGM_REGISTER_PRECHECK == 1>(keys, r, floorf(u + 0.5f), floorf(v + 0.5f), k);
+        register_vote<false>(keys, r, floorf(u + 0.5f), floorf(v + 0.5f), k);
     } else {
         const float u0 = floorf(u), v0 = floorf(v);
         const float u1 = u0 + 1.0f, v1 = v0 + 1.0f;
-        register_vote<SGM_REGISTER_PRECHECK != 0>(keys, r, u0, v0, k);
-        register_vote<SGM_REGISTER_PRECHECK != 0>(keys, r, u1, v0, k);
-        register_vote<SGM_REGISTER_PRECHECK != 0>(keys, r, u0, v1, k);
-        register_vote<SGM_REGISTER_PRECHECK != 0>(keys, r, u1, v1, k);
+        register_vote<true>(keys, r, u0, v0, k);
+        register_vote<true>(keys, r, u1, v0, k);
+        register_vote<true>(keys, r, u0, v1, k);
+        register_vote<true>(keys, r, u1, v1, k);
     }
 }
 

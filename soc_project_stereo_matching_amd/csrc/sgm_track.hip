@@ -16,45 +16,28 @@
 // the order of addition does not show: the result is the same bytes on every run, and one call over B frames is B calls of one.
 // sums is zeroed on the stream ahead of the launch.
 //
-// SGM_TRACK_FOLD (make TRACK_FOLD=1): 1 ends a workgroup with a plain store of its 29 sums into a partials array (the scratch
-//                sgmd_track_scratch_bytes sizes) and folds that array with a second small launch, sgm_track_fold_k, instead of the
-//                memset and the atomics.  Both were measured (NOTES.md section 35); the default is the winner.
-//
 // (this translation unit is compiled with -fno-honor-nans like the others: "finite" is tested on the bit pattern, before any
 // comparison)
 // ============================================================================================
 
 #define TRACK_THREADS 256
 #define TRACK_WAVES (TRACK_THREADS / 64)
-#define TRACK_MAX_FRAMES 64
 #define TRACK_MAX_BLOCKS 128                                  // per frame: 29 atomics each, the lanes stride beyond
 #define TRACK_SUMS 29
-#ifndef SGM_TRACK_FOLD
-#define SGM_TRACK_FOLD 0
-#endif
-#define FOLD_THREADS 256                                      // 8 parts of 32 lanes, 29 of them at work
 
 struct TrackModel {
     unsigned W, H;
     float wf, hf, fx, fy, cx, cy, gate, dist_max, span;       // gate: dist_max * dist_max rounded once
 };
-struct TrackPoses { float p[TRACK_MAX_FRAMES][12]; };         // 3 KiB of the 4 KiB a kernel's arguments may take
 
 // One kept source pixel with its cloud X, Y, Z.  The parentheses are the contract's.
 static __device__ __forceinline__ void track_pixel(const TrackModel& m, const float* P, const float* __restrict__ depth,
                                                    const float* __restrict__ normal, float X, float Y, float Z,
                                                    long long (&acc)[TRACK_SUMS])
 {
-    const float Px = ((P[0] * X + P[1] * Y) + P[2] * Z) + P[9];
-    const float Py = ((P[3] * X + P[4] * Y) + P[5] * Z) + P[10];
-    const float Pz = ((P[6] * X + P[7] * Y) + P[8] * Z) + P[11];
-    if (!cloud_finite(Pz)) return;
-    if (!(Pz > 0.0f)) return;
-    const float u = m.fx * (Px / Pz) + m.cx, v = m.fy * (Py / Pz) + m.cy;
-    if (!cloud_finite(u) || !cloud_finite(v)) return;
-    const float uf = floorf(u + 0.5f), vf = floorf(v + 0.5f);
-    // admitted in float, before any conversion to int
-    if (!(0.0f <= uf && uf < m.wf && 0.0f <= vf && vf < m.hf)) return;
+    float Px, Py, Pz, uf, vf;
+    pose_move(P, P + 9, X, Y, Z, Px, Py, Pz);
+    if (!pinhole_pixel(m.fx, m.fy, m.cx, m.cy, m.wf, m.hf, Px, Py, Pz, uf, vf)) return;
     const size_t at = (size_t)(unsigned)vf * m.W + (unsigned)uf;
     const float Zm = depth[at];
     if (!cloud_finite(Zm)) return;
@@ -85,11 +68,10 @@ static __device__ __forceinline__ void track_pixel(const TrackModel& m, const fl
 }
 
 template <int V>
-__global__ __launch_bounds__(TRACK_THREADS) void sgm_track_sums_k(CloudParams c, TrackModel m, TrackPoses poses,
+__global__ __launch_bounds__(TRACK_THREADS) void sgm_track_sums_k(CloudParams c, TrackModel m, PoseBlock poses,
                                                                   const float* __restrict__ disp, const uint8_t* __restrict__ mask,
                                                                   const uint16_t* __restrict__ conf, const float* __restrict__ depth,
-                                                                  const float* __restrict__ normal, long long* __restrict__ partials,
-                                                                  long long* __restrict__ sums)
+                                                                  const float* __restrict__ normal, long long* __restrict__ sums)
 {
     __shared__ long long s_wave[TRACK_WAVES][TRACK_SUMS];
     const unsigned f = blockIdx.y;
@@ -130,35 +112,9 @@ __global__ __launch_bounds__(TRACK_THREADS) void sgm_track_sums_k(CloudParams c,
         long long sum = 0;
 #pragma unroll
         for (int w = 0; w < TRACK_WAVES; ++w) sum += s_wave[w][threadIdx.x];
-#if SGM_TRACK_FOLD
-        partials[((size_t)f * gridDim.x + blockIdx.x) * TRACK_SUMS + threadIdx.x] = sum;
-#else
         if (sum != 0) atomicAdd(reinterpret_cast<unsigned long long*>(sums + (size_t)f * TRACK_SUMS + threadIdx.x), (unsigned long long)sum);
-#endif
     }
 }
-
-#if SGM_TRACK_FOLD
-// one workgroup per frame adds the `blocks` partial sums of each of the 29 numbers
-__global__ __launch_bounds__(FOLD_THREADS) void sgm_track_fold_k(const long long* __restrict__ partials, unsigned blocks,
-                                                                 long long* __restrict__ sums)
-{
-    __shared__ long long s_part[FOLD_THREADS / 32][32];
-    const unsigned k = threadIdx.x & 31u, part = threadIdx.x >> 5;
-    const long long* from = partials + (size_t)blockIdx.x * blocks * TRACK_SUMS;
-    long long sum = 0;
-    if (k < TRACK_SUMS)
-        for (unsigned b = part; b < blocks; b += FOLD_THREADS / 32) sum += from[(size_t)b * TRACK_SUMS + k];
-    s_part[part][k] = sum;
-    __syncthreads();
-    if (threadIdx.x < TRACK_SUMS) {
-        long long all = 0;
-#pragma unroll
-        for (int p = 0; p < FOLD_THREADS / 32; ++p) all += s_part[p][threadIdx.x];
-        sums[(size_t)blockIdx.x * TRACK_SUMS + threadIdx.x] = all;
-    }
-}
-#endif
 
 // the workgroups of a frame: one item per lane up to TRACK_MAX_BLOCKS, the lanes stride beyond
 static unsigned track_blocks(size_t items)
@@ -169,18 +125,10 @@ static unsigned track_blocks(size_t items)
 
 extern "C" {
 
-// the partials of SGM_TRACK_FOLD: 29 int64 per workgroup, for the one-pixel-per-lane path, which has the most workgroups
-size_t sgmd_track_scratch_bytes(int W, int H, int B)
-{
-    if (!SGM_TRACK_FOLD || W < 1 || H < 1 || B < 1) return 0;
-    return (size_t)B * track_blocks((size_t)W * H) * TRACK_SUMS * sizeof(long long);
-}
-
 int sgmd_track_sums(int ord, void* stream, const sgmd_cloud* c, const sgmd_track* t, const float* poses, const void* disp,
-                    const void* mask, const void* conf, const void* model_depth, const void* model_normal, void* scratch, void* sums)
+                    const void* mask, const void* conf, const void* model_depth, const void* model_normal, void* sums)
 {
-    if ((SGM_TRACK_FOLD && (!scratch || (uintptr_t)scratch % 8 != 0)) ||
-        !cloud_shape_ok(c) || !t || !poses || !disp || !model_depth || !model_normal || !sums || c->B > TRACK_MAX_FRAMES ||
+    if (!cloud_shape_ok(c) || !t || !poses || !disp || !model_depth || !model_normal || !sums || c->B > SGMD_MAX_POSES ||
         (unsigned long long)c->W * c->H > (1ull << 24) || t->W < 1 || t->H < 1 || t->W > 65535 || t->H > 65535 ||
         (uintptr_t)disp % 4 != 0 || (uintptr_t)conf % 2 != 0 || (uintptr_t)model_depth % 4 != 0 || (uintptr_t)model_normal % 4 != 0 ||
         (uintptr_t)sums % 8 != 0) {
@@ -195,27 +143,19 @@ int sgmd_track_sums(int ord, void* stream, const sgmd_cloud* c, const sgmd_track
     m.fx = t->fx; m.fy = t->fy; m.cx = t->cx; m.cy = t->cy;
     m.gate = t->dist_max * t->dist_max;
     m.dist_max = t->dist_max; m.span = t->span;
-    TrackPoses pose;
-    memset(&pose, 0, sizeof pose);
-    memcpy(pose.p, poses, (size_t)c->B * 12 * sizeof(float));
+    const PoseBlock pose = pose_block(poses, c->B);
     const hipStream_t st = (hipStream_t)stream;
-#if !SGM_TRACK_FOLD
     HIP_TRY(hipMemsetAsync(sums, 0, (size_t)c->B * TRACK_SUMS * sizeof(long long), st));
-#endif
     const bool vec = cloud_vector(c, disp, mask, conf);
     const unsigned blocks = track_blocks(((size_t)q.npx + (vec ? 3 : 0)) / (vec ? 4 : 1));
     const dim3 grid(blocks, (unsigned)c->B);
     if (vec)
         hipLaunchKernelGGL(sgm_track_sums_k<4>, grid, dim3(TRACK_THREADS), 0, st, q, m, pose, (const float*)disp, (const uint8_t*)mask,
-                           (const uint16_t*)conf, (const float*)model_depth, (const float*)model_normal, (long long*)scratch, (long long*)sums);
+                           (const uint16_t*)conf, (const float*)model_depth, (const float*)model_normal, (long long*)sums);
     else
         hipLaunchKernelGGL(sgm_track_sums_k<1>, grid, dim3(TRACK_THREADS), 0, st, q, m, pose, (const float*)disp, (const uint8_t*)mask,
-                           (const uint16_t*)conf, (const float*)model_depth, (const float*)model_normal, (long long*)scratch, (long long*)sums);
+                           (const uint16_t*)conf, (const float*)model_depth, (const float*)model_normal, (long long*)sums);
     HIP_TRY(hipGetLastError());
-#if SGM_TRACK_FOLD
-    hipLaunchKernelGGL(sgm_track_fold_k, dim3((unsigned)c->B), dim3(FOLD_THREADS), 0, st, (const long long*)scratch, blocks, (long long*)sums);
-    HIP_TRY(hipGetLastError());
-#endif
     return 0;
 }
 

@@ -24,11 +24,6 @@
 // ============================================================================================
 
 #define VOL_THREADS 256                                       // the integration's; the surface list's kernels run TILE_THREADS
-#define VOL_MAX_FRAMES 64
-// SGM_VOLUME_VEC (make VOL_VEC=0): 0 sends every volume down the one-voxel-per-lane path -- the measurement of NOTES.md section 31
-#ifndef SGM_VOLUME_VEC
-#define SGM_VOLUME_VEC 1
-#endif
 
 struct VolumeParams {
     unsigned nx, ny, nz;
@@ -36,7 +31,6 @@ struct VolumeParams {
     float voxel, ox, oy, oz, trunc;
     unsigned max_weight;
 };
-struct VolumePoses { float p[VOL_MAX_FRAMES][12]; };          // 3 KiB of the 4 KiB a kernel's arguments may take
 
 // the source image as the integration needs it beside CloudParams
 struct VolumeSource { float wf, hf; unsigned frames; };
@@ -60,16 +54,9 @@ static __device__ __forceinline__ bool volume_update(const VolumeParams& v, cons
                                                      const uint8_t* __restrict__ mask, const uint16_t* __restrict__ conf, float px,
                                                      float py, float pz, int& tq, unsigned& w)
 {
-    const float Xp = ((P[0] * px + P[1] * py) + P[2] * pz) + P[9];
-    const float Yp = ((P[3] * px + P[4] * py) + P[5] * pz) + P[10];
-    const float Zp = ((P[6] * px + P[7] * py) + P[8] * pz) + P[11];
-    if (!cloud_finite(Zp)) return false;
-    if (!(Zp > 0.0f)) return false;
-    const float u = c.fx * (Xp / Zp) + c.cx, vv = c.fy * (Yp / Zp) + c.cy;
-    if (!cloud_finite(u) || !cloud_finite(vv)) return false;
-    const float uf = floorf(u + 0.5f), vf = floorf(vv + 0.5f);
-    // admitted in float, before any conversion to int
-    if (!(0.0f <= uf && uf < s.wf && 0.0f <= vf && vf < s.hf)) return false;
+    float Xp, Yp, Zp, uf, vf;
+    pose_move(P, P + 9, px, py, pz, Xp, Yp, Zp);
+    if (!pinhole_pixel(c.fx, c.fy, c.cx, c.cy, s.wf, s.hf, Xp, Yp, Zp, uf, vf)) return false;
     const size_t at = frame_base + (size_t)(unsigned)vf * c.W + (unsigned)uf;
     float Z;
     if (!cloud_kept(c, disp[at], mask ? mask[at] : 1u, conf ? conf[at] : 65535u, Z)) return false;
@@ -86,7 +73,7 @@ static __device__ __forceinline__ bool volume_update(const VolumeParams& v, cons
 }
 
 template <int V>
-__global__ __launch_bounds__(VOL_THREADS) void sgm_volume_integrate_k(VolumeParams v, CloudParams c, VolumeSource s, VolumePoses poses,
+__global__ __launch_bounds__(VOL_THREADS) void sgm_volume_integrate_k(VolumeParams v, CloudParams c, VolumeSource s, PoseBlock poses,
                                                                       const float* __restrict__ disp, const uint8_t* __restrict__ mask,
                                                                       const uint16_t* __restrict__ conf, unsigned* __restrict__ voxels)
 {
@@ -227,25 +214,11 @@ __global__ __launch_bounds__(TILE_THREADS) void sgm_volume_emit_k(VolumeParams v
 // restates it).  One lane per pixel, one launch for all frames (blockIdx.z: the frame, whose pose is read from the kernel
 // arguments with scalar loads), no LDS, no atomics and no dependence between lanes: a lane marches its ray in Z, reads one word
 // per sample, and at a front hit 16 words for the two trilinear values and 48 for the normal.
-//
-// SGM_RAYCAST_TILE (make RAY_TILE=0 | 1): how a wave covers the image -- 1: an 8 x 8 pixel tile, whose rays stay together in the
-//                  volume; 0: a 64 x 1 row segment, whose stores coalesce.
-// SGM_RAYCAST_SKIP (make RAY_SKIP=0 | 1): 1 starts and ends the march at the volume's box (ray_box below); 0 marches z_min..z_max.
-// Both were measured (NOTES.md section 34); the defaults are the winners.
+// A wave covers an 8 x 8 pixel tile, whose rays stay together in the volume, and the march starts and ends at the volume's box
+// (ray_box below).
 #define RAY_THREADS 256
-#ifndef SGM_RAYCAST_TILE
-#define SGM_RAYCAST_TILE 1
-#endif
-#ifndef SGM_RAYCAST_SKIP
-#define SGM_RAYCAST_SKIP 1
-#endif
-#if SGM_RAYCAST_TILE
 #define RAY_BLOCK_W 32                                        // four 8 x 8 tiles side by side
 #define RAY_BLOCK_H 8
-#else
-#define RAY_BLOCK_W RAY_THREADS                               // four row segments of 64 in a row
-#define RAY_BLOCK_H 1
-#endif
 
 struct RaycastView {
     unsigned W, H;
@@ -324,16 +297,12 @@ static __device__ __forceinline__ void ray_box(const VolumeParams& v, const Rayc
 }
 
 template <bool NORMALS>
-__global__ __launch_bounds__(RAY_THREADS) void sgm_volume_raycast_k(VolumeParams v, RaycastView r, VolumePoses poses,
+__global__ __launch_bounds__(RAY_THREADS) void sgm_volume_raycast_k(VolumeParams v, RaycastView r, PoseBlock poses,
                                                                     const unsigned* __restrict__ voxels, float* __restrict__ depth,
                                                                     float* __restrict__ normal)
 {
-#if SGM_RAYCAST_TILE
     const unsigned lane = threadIdx.x & 63u;
     const unsigned x = blockIdx.x * RAY_BLOCK_W + (threadIdx.x >> 6) * 8u + (lane & 7u), y = blockIdx.y * RAY_BLOCK_H + (lane >> 3);
-#else
-    const unsigned x = blockIdx.x * RAY_BLOCK_W + threadIdx.x, y = blockIdx.y;
-#endif
     if (x >= r.W || y >= r.H) return;
     const float* P = poses.p[blockIdx.z];                     // R row-major, then t: world -> camera
     const float a = ((float)x - r.cx) / r.fx, b = ((float)y - r.cy) / r.fy;
@@ -348,9 +317,7 @@ __global__ __launch_bounds__(RAY_THREADS) void sgm_volume_raycast_k(VolumeParams
     }
     unsigned k = 0;
     float z_end = r.z_max;
-#if SGM_RAYCAST_SKIP
     ray_box(v, r, go, gd, k, z_end);
-#endif
     const float nan = __uint_as_float(0x7FC00000u);
     float Z = nan, nrm[3] = {nan, nan, nan};
     unsigned prev = 0;
@@ -440,7 +407,7 @@ size_t sgmd_volume_scratch_bytes(int nx, int ny, int nz)
 int sgmd_volume_integrate(int ord, void* stream, const sgmd_volume* v, const sgmd_cloud* c, const float* poses, const void* disp,
                           const void* mask, const void* conf, void* voxels)
 {
-    if (!volume_ok(v) || !cloud_shape_ok(c) || !poses || !disp || !voxels || c->B > VOL_MAX_FRAMES || (uintptr_t)voxels % 4 != 0 ||
+    if (!volume_ok(v) || !cloud_shape_ok(c) || !poses || !disp || !voxels || c->B > SGMD_MAX_POSES || (uintptr_t)voxels % 4 != 0 ||
         (uintptr_t)disp % 4 != 0 || (uintptr_t)conf % 2 != 0) {
         fprintf(stderr, "sgm_mi355x: sgmd_volume_integrate: bad arguments\n");
         return -1;
@@ -451,11 +418,9 @@ int sgmd_volume_integrate(int ord, void* stream, const sgmd_volume* v, const sgm
     VolumeSource s;
     s.wf = (float)c->W; s.hf = (float)c->H;
     s.frames = (unsigned)c->B;
-    VolumePoses pose;
-    memset(&pose, 0, sizeof pose);
-    memcpy(pose.p, poses, (size_t)c->B * 12 * sizeof(float));
+    const PoseBlock pose = pose_block(poses, c->B);
     const hipStream_t st = (hipStream_t)stream;
-    if (SGM_VOLUME_VEC && p.nx % 4 == 0 && (uintptr_t)voxels % 16 == 0)
+    if (p.nx % 4 == 0 && (uintptr_t)voxels % 16 == 0)
         hipLaunchKernelGGL(sgm_volume_integrate_k<4>, dim3((p.n / 4 + VOL_THREADS - 1) / VOL_THREADS), dim3(VOL_THREADS), 0, st, p, q, s,
                            pose, (const float*)disp, (const uint8_t*)mask, (const uint16_t*)conf, (unsigned*)voxels);
     else
@@ -493,7 +458,7 @@ int sgmd_volume_raycast(int ord, void* stream, const sgmd_volume* v, const sgmd_
                         void* depth, void* normal)
 {
     if (!volume_ok(v) || !r || !poses || !voxels || !depth || r->W < 1 || r->H < 1 || r->W > 65535 || r->H > 65535 || r->B < 1 ||
-        r->B > VOL_MAX_FRAMES || (unsigned long long)r->W * r->H * r->B > (1ull << 31) || r->min_weight < 1 || r->min_weight > 65535 ||
+        r->B > SGMD_MAX_POSES || (unsigned long long)r->W * r->H * r->B > (1ull << 31) || r->min_weight < 1 || r->min_weight > 65535 ||
         (uintptr_t)voxels % 4 != 0 || (uintptr_t)depth % 4 != 0 || (uintptr_t)normal % 4 != 0) {
         fprintf(stderr, "sgm_mi355x: sgmd_volume_raycast: bad arguments\n");
         return -1;
@@ -504,9 +469,7 @@ int sgmd_volume_raycast(int ord, void* stream, const sgmd_volume* v, const sgmd_
     q.W = (unsigned)r->W; q.H = (unsigned)r->H;
     q.fx = r->fx; q.fy = r->fy; q.cx = r->cx; q.cy = r->cy; q.z_min = r->z_min; q.z_max = r->z_max; q.step = r->step;
     q.min_weight = r->min_weight;
-    VolumePoses pose;
-    memset(&pose, 0, sizeof pose);
-    memcpy(pose.p, poses, (size_t)r->B * 12 * sizeof(float));
+    const PoseBlock pose = pose_block(poses, r->B);
     const dim3 grid((q.W + RAY_BLOCK_W - 1) / RAY_BLOCK_W, (q.H + RAY_BLOCK_H - 1) / RAY_BLOCK_H, (unsigned)r->B);
     const hipStream_t st = (hipStream_t)stream;
     if (normal)

@@ -14,12 +14,11 @@
 #include <string.h>
 
 #define RAY_LOG_MAX 256
-#define RAY_FRAMES_MAX 64
 #define CAP ((size_t)1 << 20)
 static struct {
     sgmd_volume v;
     sgmd_raycast r;
-    float poses[RAY_FRAMES_MAX * 12];
+    float poses[SGMD_MAX_POSES * 12];
     const void* p[4];
 } g_calls[RAY_LOG_MAX];
 static int g_calls_n, g_refuse_countdown = -1;
@@ -109,7 +108,7 @@ int sgmd_volume_raycast(int o, void* st, const sgmd_volume* v, const sgmd_raycas
         memset(&g_calls[g_calls_n], 0, sizeof g_calls[0]);
         g_calls[g_calls_n].v = *v;
         g_calls[g_calls_n].r = *r;
-        if (poses && r->B >= 1 && r->B <= RAY_FRAMES_MAX) memcpy(g_calls[g_calls_n].poses, poses, (size_t)r->B * 12 * sizeof(float));
+        if (poses && r->B >= 1 && r->B <= SGMD_MAX_POSES) memcpy(g_calls[g_calls_n].poses, poses, (size_t)r->B * 12 * sizeof(float));
         const void* p[4] = {voxels_, depth_, normal_, poses};
         memcpy(g_calls[g_calls_n++].p, p, sizeof p);
     }

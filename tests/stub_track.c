@@ -14,23 +14,18 @@
 #include <string.h>
 
 #define TRACK_LOG_MAX 256
-#define TRACK_FRAMES_MAX 64
 static struct {
     sgmd_cloud c;
     sgmd_track t;
-    float poses[TRACK_FRAMES_MAX * 12];
-    const void* p[8];
+    float poses[SGMD_MAX_POSES * 12];
+    const void* p[7];
 } g_calls[TRACK_LOG_MAX];
 static int g_calls_n, g_total, g_refuse_countdown = -1;           /* g_total: every call, also those past the log's end */
-static size_t g_scratch_bytes;                                    /* what the launcher says it wants: 0, as the default build */
 
-void stub_track_clear(void) { g_calls_n = g_total = 0; g_refuse_countdown = -1; g_scratch_bytes = 0; }
+void stub_track_clear(void) { g_calls_n = g_total = 0; g_refuse_countdown = -1; }
 int stub_track_count(void) { return g_total; }
-/* which: 0 disp, 1 mask, 2 conf, 3 model depth, 4 model normal, 5 sums, 6 the poses as given, 7 scratch */
-const void* stub_track_ptr(int call, int which) { return (call >= 0 && call < g_calls_n && which >= 0 && which < 8) ? g_calls[call].p[which] : NULL; }
-/* a launcher that wants scratch, as a build with make TRACK_FOLD=1 */
-void stub_track_scratch(size_t bytes) { g_scratch_bytes = bytes; }
-size_t sgmd_track_scratch_bytes(int W, int H, int B) { (void)W; (void)H; (void)B; return g_scratch_bytes; }
+/* which: 0 disp, 1 mask, 2 conf, 3 model depth, 4 model normal, 5 sums, 6 the poses as given */
+const void* stub_track_ptr(int call, int which) { return (call >= 0 && call < g_calls_n && which >= 0 && which < 7) ? g_calls[call].p[which] : NULL; }
 const sgmd_cloud* stub_track_source(int call) { return (call >= 0 && call < g_calls_n) ? &g_calls[call].c : NULL; }
 const sgmd_track* stub_track_model(int call) { return (call >= 0 && call < g_calls_n) ? &g_calls[call].t : NULL; }
 const float* stub_track_poses(int call) { return (call >= 0 && call < g_calls_n) ? g_calls[call].poses : NULL; }
@@ -45,7 +40,7 @@ static int finite_bits(float v)
 }
 
 int sgmd_track_sums(int o, void* st, const sgmd_cloud* c, const sgmd_track* t, const float* poses, const void* disp_, const void* mask_,
-                    const void* conf_, const void* depth_, const void* normal_, void* scratch_, void* sums_)
+                    const void* conf_, const void* depth_, const void* normal_, void* sums_)
 {
     (void)o; (void)st;
     ++g_total;
@@ -53,12 +48,11 @@ int sgmd_track_sums(int o, void* st, const sgmd_cloud* c, const sgmd_track* t, c
         memset(&g_calls[g_calls_n], 0, sizeof g_calls[0]);
         g_calls[g_calls_n].c = *c;
         g_calls[g_calls_n].t = *t;
-        if (poses && c->B >= 1 && c->B <= TRACK_FRAMES_MAX) memcpy(g_calls[g_calls_n].poses, poses, (size_t)c->B * 12 * sizeof(float));
-        const void* p[8] = {disp_, mask_, conf_, depth_, normal_, sums_, poses, scratch_};
+        if (poses && c->B >= 1 && c->B <= SGMD_MAX_POSES) memcpy(g_calls[g_calls_n].poses, poses, (size_t)c->B * 12 * sizeof(float));
+        const void* p[7] = {disp_, mask_, conf_, depth_, normal_, sums_, poses};
         memcpy(g_calls[g_calls_n++].p, p, sizeof p);
     }
     if (g_refuse_countdown >= 0 && g_refuse_countdown-- == 0) return 719;
-    if (g_scratch_bytes) memset(scratch_, 0x5C, g_scratch_bytes);  /* (a sanitizer build sees the whole of it) */
     const float* disp = (const float*)disp_;
     const uint8_t* mask = (const uint8_t*)mask_;
     const uint16_t* conf = (const uint16_t*)conf_;

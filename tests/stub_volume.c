@@ -15,7 +15,6 @@
 #include <string.h>
 
 #define VOL_LOG_MAX 256
-#define VOL_FRAMES_MAX 64
 #define CAP ((size_t)1 << 20)
 #define TILE 2048
 static struct {
@@ -24,7 +23,7 @@ static struct {
     size_t capacity;
     sgmd_volume v;
     sgmd_cloud c;
-    float poses[VOL_FRAMES_MAX * 12];
+    float poses[SGMD_MAX_POSES * 12];
     const void* p[6];
 } g_calls[VOL_LOG_MAX];
 static int g_calls_n, g_refuse_countdown = -1;
@@ -52,7 +51,7 @@ static int note(int kind, const sgmd_volume* v, const sgmd_cloud* c, const float
         g_calls[g_calls_n].capacity = capacity;
         g_calls[g_calls_n].v = *v;
         if (c) g_calls[g_calls_n].c = *c;
-        if (c && poses && c->B >= 1 && c->B <= VOL_FRAMES_MAX) memcpy(g_calls[g_calls_n].poses, poses, (size_t)c->B * 12 * sizeof(float));
+        if (c && poses && c->B >= 1 && c->B <= SGMD_MAX_POSES) memcpy(g_calls[g_calls_n].poses, poses, (size_t)c->B * 12 * sizeof(float));
         memcpy(g_calls[g_calls_n++].p, p, (size_t)np * sizeof *p);
     }
     return (g_refuse_countdown >= 0 && g_refuse_countdown-- == 0) ? 719 : 0;

@@ -473,8 +473,7 @@ def _sign(L):
     for name, (res, args) in {"sgm_track_sums": (_b, [_p] * 10), "sgm_track": (_b, [_p] * 12), "sgm_track_solve": (_b, [_p] * 5),
                               "stub_track_clear": (None, []), "stub_track_count": (_i, []), "stub_track_ptr": (_p, [_i, _i]),
                               "stub_track_source": (C.POINTER(DeviceCloud), [_i]), "stub_track_model": (C.POINTER(DeviceTrack), [_i]),
-                              "stub_track_poses": (C.POINTER(C.c_float), [_i]), "stub_track_fail_at": (None, [_i]),
-                              "stub_track_scratch": (None, [C.c_size_t])}.items():
+                              "stub_track_poses": (C.POINTER(C.c_float), [_i]), "stub_track_fail_at": (None, [_i])}.items():
         if hasattr(L, name):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
     return L
@@ -594,34 +593,18 @@ def test_sgm_track_on_the_stand_in_equals_the_restatement_round_by_round(host):
     L.sgm_destroy(inst)
 
 
-def test_a_launcher_that_wants_scratch_gets_it_reserved_once(host):
-    """what a build with make TRACK_FOLD=1 asks of the host: sgmd_track_scratch_bytes > 0"""
+def test_a_refused_allocation_fails_sgm_track_before_anything_is_queued(host, capfd):
+    """the one buffer tracking reserves: sgm_track's own sums"""
     L = host
     inst = L.sgm_create(0)
     s, disp, m, poses, depth, normal, mask, conf = noisy_case()
-    b = Maps(s, disp, depth, normal, mask, conf)
-    want = TR.sums(disp, s, m, poses, depth, normal, mask, conf).tolist()
     L.stub_clear(); L.stub_track_clear()
-    assert L.stub_track_ptr(0, 7) is None
-    L.stub_track_scratch(4096)
-    assert sums_call(L, inst, c_source(s), c_model(m), poses, b) and b.sums().tolist() == want
-    allocs = [e for e in standin.log(L) if e.name == "alloc"]
-    assert len(allocs) == 1 and allocs[0].arg == 4 and L.stub_track_ptr(0, 7) is not None        # (the log counts KiB)
-    cm = c_model(m)
-    cm.iterations = 2
-    ok, _, _, t_sums, _ = track_call(L, inst, c_source(s), cm, poses.astype(np.float64), b)
-    assert ok and t_sums[0].tolist() == want
-    allocs = [e.arg for e in standin.log(L) if e.name == "alloc"]
-    assert allocs == [4, 232 * s.frames >> 10] and {L.stub_track_ptr(k, 7) for k in range(3)} == {L.stub_track_ptr(0, 7)}
-    # and a refused allocation fails the call before anything is queued
-    inst2 = L.sgm_create(0)
-    L.stub_clear(); L.stub_track_clear()
-    L.stub_track_scratch(4096)
     L.stub_fail_at(b"alloc", 0)
-    assert not sums_call(L, inst2, c_source(s), c_model(m), poses, Maps(s, disp, depth, normal)) and L.stub_track_count() == 0
-    L.stub_track_clear()
+    ok, got, _, _, _ = track_call(L, inst, c_source(s), c_model(m), poses.astype(np.float64), Maps(s, disp, depth, normal))
+    assert not ok and L.stub_track_count() == 0 and got.tobytes() == poses.astype(np.float64).tobytes()
+    assert "device allocation failed for the sums of tracking" in capfd.readouterr().err
+    assert "d2h" not in [e.name for e in standin.log(L)]
     L.sgm_destroy(inst)
-    L.sgm_destroy(inst2)
 
 
 def refused(L, inst, cs, cm, poses, b, capfd, entry="sgm_track_sums", **kw):
@@ -759,7 +742,7 @@ def test_the_kernel_compiles_without_scratch_and_the_committed_table_is_this_bui
     for block in out.stderr.split("Function Name: ")[1:]:
         name = block.split()[0]
         num = lambda pat: int(re.search(pat + r": (\d+)", block).group(1))
-        assert "sgm_track_sums_k" in name, name                   # (the fold kernel belongs to make TRACK_FOLD=1 alone)
+        assert "sgm_track_sums_k" in name, name
         got["sgm_track_sums_k<4>" if "ILi4E" in name else "sgm_track_sums_k<1>"] = [
             num(r"TotalSGPRs"), num(r" VGPRs"), num(r"ScratchSize \[bytes/lane\]"), num(r"LDS Size \[bytes/block\]"),
             num(r"Occupancy \[waves/SIMD\]"), num(r"SGPRs Spill"), num(r"VGPRs Spill")]

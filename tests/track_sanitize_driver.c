@@ -16,7 +16,6 @@
 
 int stub_track_count(void);
 void stub_track_fail_at(int nth);
-void stub_track_scratch(size_t bytes);
 
 static SGMOption options(int d)
 {
@@ -130,12 +129,6 @@ int main(void)
     CHECK(s);
     for (size_t i = 0; i < sizeof shapes / sizeof shapes[0]; ++i)
         if (run(s, shapes[i][0], shapes[i][1], shapes[i][2], shapes[i][3], shapes[i][4]) != 0) return 1;
-    /* a launcher that wants scratch, as a build that folds partial sums: reserved by the host, grown, freed with the instance */
-    stub_track_scratch(1000);
-    if (run(s, 24, 16, 24, 16, 2) != 0) return 1;
-    stub_track_scratch(70000);
-    if (run(s, 70, 33, 40, 24, 3) != 0) return 1;
-    stub_track_scratch(0);
     /* refusals queue nothing */
     {
         float disp[4] = {20, 20, 20, 20}, depth[4] = {2, 2, 2, 2}, normal[12] = {0, 0, -1, 0, 0, -1, 0, 0, -1, 0, 0, -1}, poses32[65 * 12];

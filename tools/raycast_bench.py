@@ -10,8 +10,7 @@ met), and as yardsticks sgm_volume_integrate B = 1, sgm_volume_points and sgm_cl
 and call `warmup` calls, then `calls` calls queued back to back between two HIP events on the instance's stream; time per call =
 elapsed / calls.  Median, minimum and maximum over the rounds.  Beside the render: the pixels that meet the surface and the samples
 per pixel the contract's march takes (from the depth map: up to the hit, or all of them), i.e. without the box skip.  Prints one JSON
-line per call.  --label names the build: the wave mapping and the box skip are compile-time switches (make RAY_TILE=0 / RAY_SKIP=0
-through tools/build_variant.sh; SGM_LIBRARY_PATH points at the variant)."""
+line per call.  --label names the build in the output (SGM_LIBRARY_PATH may point at the library of another commit)."""
 import argparse, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -9,7 +9,8 @@ sgm_cloud_points.  Per round and call: `warmup` calls, then `calls` calls queued
 instance's stream; time per call = elapsed / calls.  Median, minimum and maximum over the rounds.  Beside every registration: the
 atomic candidates a call issues (counted by the restatement tests/register_ref.py on the same map) and the byte rate they imply, 8 B
 each, over the whole call (clear and resolve included: a lower bound of the scatter's own rate).  Prints one JSON line per call and
-the match's own time per batch.  --label names the build (SGM_LIBRARY_PATH may point at a variant, tools/build_variant.sh)."""
+the match's own time per batch.  --label names the build in the output (SGM_LIBRARY_PATH may point at the
+library of another commit)."""
 import argparse, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

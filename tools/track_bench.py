@@ -1,6 +1,6 @@
 """What frame-to-model tracking costs a call (NOTES.md section 35) -- needs an MI355X.
 
-    python tools/track_bench.py [--rounds 9] [--calls 40] [--warmup 5] [--label atomics | fold]
+    python tools/track_bench.py [--rounds 9] [--calls 40] [--warmup 5] [--label atomics]
 
 The set-up of tools/raycast_bench.py: KITTI 1242x375, D = 128, batch 8, device-resident, the disparity maps of a real match of
 SGM_SynthPair frames fused (sgm_volume_integrate, B = 8) into 512 x 128 x 512 voxels of 0.1 m (134 MB) in front of the rig, eight
@@ -10,7 +10,7 @@ yardsticks sgm_volume_raycast of one view with normals and sgm_cloud_organized. 
 `warmup` calls, then `calls` calls queued back to back between two HIP events on the instance's stream; time per call = elapsed /
 calls.  sgm_track blocks (per round: a launch, a copy of 232 bytes per frame, a wait, the solve), so it is timed with the host's
 clock over `calls` calls of 1 and of 4 rounds.  Median, minimum and maximum over the rounds.  Prints one JSON line per call.
---label names the build: how a workgroup ends is a compile-time switch (make TRACK_FOLD=1; SGM_LIBRARY_PATH points at the variant)."""
+--label names the build in the output (SGM_LIBRARY_PATH may point at the library of another commit)."""
 import argparse, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -10,7 +10,7 @@ section 29: per round and call `warmup` calls, then `calls` calls queued back to
 stream; time per call = elapsed / calls.  Median, minimum and maximum over the rounds.  Beside the integration: the voxels a call
 updates and stores, the bytes it moves (every word read once, the stored ones written once) and the rate that is, against one read
 plus one write of the updated voxels alone.  Prints one JSON line per call and the match's own time per batch.  --label names the
-build (SGM_LIBRARY_PATH may point at a variant, tools/build_variant.sh)."""
+build in the output (SGM_LIBRARY_PATH may point at the library of another commit)."""
 import argparse, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
