@@ -610,9 +610,9 @@ bool   sgm_register_spec_raw(const double K[9], const double dist[5], const doub
  * travel as kernel arguments); a non-finite pose entry; a min_weight outside 1..65535; a pointer not aligned as said; a d_voxels
  * that aliases a map (d_points or d_count that alias the volume or each other); a build without the kernels.  The extraction
  * keeps 8 bytes of scratch per tile of 2048 voxels, reserved at its first call: an instance that never calls these entry points
- * allocates and launches exactly what it did before.  Not part of it: meshing (ray-casting the volume into a view is
- * sgm_volume_raycast below), confidence-weighted updates, colour, voxel hashing or a moving volume, estimating the poses (sgm_track
- * below does that against a ray-cast), row tiles, sgm_match_planes. */
+ * allocates and launches exactly what it did before.  Not part of it: meshing and ray-casting the volume into a view, which are
+ * entry points of their own (sgm_volume_mesh and sgm_volume_raycast below), confidence-weighted updates, colour, voxel hashing or
+ * a moving volume, estimating the poses (sgm_track below does that against a ray-cast), row tiles, sgm_match_planes. */
 typedef struct {            /* 36 bytes, every field 4 bytes, no padding */
     int32_t  nx, ny, nz;    /* 1..1024 each, nx*ny*nz <= 2^30; voxel n = (k*ny + j)*nx + i, x fastest */
     float    voxel;         /* edge length, units of baseline; finite, > 0 */
@@ -627,6 +627,57 @@ bool   sgm_volume_integrate(sgm_instance* s, const sgm_volume_spec* spec, const 
                             const float* d_disp, const uint8_t* d_mask, const uint16_t* d_conf, uint32_t* d_voxels);
 bool   sgm_volume_points(sgm_instance* s, const sgm_volume_spec* spec, const uint32_t* d_voxels, uint32_t min_weight /* 1..65535 */,
                          sgm_surface_point* d_points /* 16-byte aligned */, size_t capacity, uint32_t* d_count);
+
+/* ---- the TSDF volume as a triangle mesh: marching tetrahedra on the device ----
+ * Extension, "parity unpinned by the reference"; defined here and restated by tests/mesh_ref.py.  sgm_volume_points hands back an
+ * unconnected list of crossings; a viewer, a collision checker or a texture step needs connectivity.  Takes a volume as
+ * sgm_volume_integrate leaves it and writes an indexed triangle mesh: a vertex list and a triangle list.  Marching tetrahedra, not
+ * cubes: 16 cases per tetrahedron, none ambiguous, so the mesh is closed wherever the cells around it are meshed.  All float
+ * arithmetic follows sgm_volume_points: float32, every operation rounded on its own, no contraction.
+ *
+ * Size limit.  A spec sgm_volume_integrate accepts with, in addition, nx*ny*nz <= 2^27: then n*8 + e, at most 7 vertices per voxel
+ * and at most 12 triangles per cell all fit uint32.  A larger volume is refused by this entry point only.
+ * Edges.  Edge kind e of voxel n = (i,j,k) runs to the voxel at (i+dx, j+dy, k+dz):
+ *   e = 0: (1,0,0)   1: (0,1,0)   2: (0,0,1)   3: (1,1,0)   4: (1,0,1)   5: (0,1,1)   6: (1,1,1)
+ * and exists when that far voxel is inside the grid.  Kinds 0..2 are the axes of sgm_volume_points.
+ * Vertices.  Edge (n, e) with far voxel m carries a vertex iff w[n] >= min_weight && w[m] >= min_weight && (tq[n] < 0) != (tq[m] < 0),
+ * the crossing rule of sgm_volume_points (zero counts as non-negative).  s = (float)tq[n] / ((float)tq[n] - (float)tq[m]); each
+ * coordinate in which the edge steps is centre + s * voxel, the others are the centre of voxel n (px, py, pz of the volume
+ * contract); id = n*8 + e.  The list is sorted by id and holds every such edge, whether or not a triangle uses it; its records
+ * with e < 3 are exactly the records of sgm_volume_points with the same min_weight (same x, y, z; id n*4 + a <-> n*8 + a).
+ * Cells and tetrahedra.  Cell n = (i,j,k) exists iff i+1 < nx, j+1 < ny and k+1 < nz, and is meshed iff all eight corners have
+ * w >= min_weight.  It is cut into the six tetrahedra around its body diagonal: tetrahedron t has corners p0 = (0,0,0),
+ * p1 = p0 + axis a, p2 = p1 + axis b, p3 = (1,1,1) for (a,b,c) = the permutations (x,y,z), (x,z,y), (y,x,z), (y,z,x), (z,x,y),
+ * (z,y,x), t = 0..5.  Every tetrahedron edge is one of the seven kinds above, taken from its lower corner, so neighbouring cells
+ * agree on their shared face diagonals.
+ * Triangles of a tetrahedron.  N is the set of corner indices 0..3 with tq < 0, ascending; P the rest, ascending.
+ *   |N| = 0 or 4: no triangle
+ *   |N| = 1, N = {a}:           one triangle on edges (a,P0), (a,P1), (a,P2)
+ *   |N| = 3, P = {c}:           one triangle on edges (c,N0), (c,N1), (c,N2)
+ *   |N| = 2, N = {a,b}, P = {c,d}: two triangles, (ac, ad, bd) then (ac, bd, bc)
+ * Winding, a constant of (t, sign mask) independent of the data: with each vertex at the midpoint of its edge in the unit cell, the
+ * order above is kept if ((v1-v0) x (v2-v0)) . (centroid(P) - centroid(N)) > 0 and the last two vertices are swapped otherwise (the
+ * product is a non-zero integer in all 6 x 14 cases).  Normals therefore point towards free space, as the ray-cast's do.
+ * Order of the triangle list: by cell n, then t, then first triangle before second.  v[] are ranks in the full vertex list;
+ * cell = n.  Triangles with coincident vertices (tq == 0 gives s == 0) are emitted as any other: they keep the mesh closed.
+ * Outputs.  d_counts[0] always receives the full vertex count and d_counts[1] the full triangle count.  Vertex records with index
+ * >= vertex_capacity are not written.  Triangle records are written only if the vertex count <= vertex_capacity (a truncated
+ * vertex list would make the indices meaningless), and only those with index < triangle_capacity.  Nothing else is written.
+ * Capacity 0 with a NULL array asks for the counts only.  The result is the same bytes on every run: no atomic decides a place
+ * (count per tile, one scan, the vertices, the triangles; a triangle finds its vertices' ranks by binary search of their ids).
+ *
+ * false, nothing queued and one "sgm_mi355x: sgm_volume_mesh: ..." line on stderr: a NULL s, spec, d_voxels or d_counts; an array
+ * that is NULL with a capacity > 0; a spec outside the ranges (the limit above included); a min_weight outside 1..65535; an array
+ * not 16-byte aligned, or d_voxels / d_counts not 4-byte aligned; outputs that overlap the volume or each other; a build without
+ * the kernels.  Asynchronous on sgm_stream(s) and ordered as sgm_volume_points is.  It keeps 16 bytes of scratch per tile of 2048
+ * voxels, reserved at its first call: an instance that never calls it allocates and launches exactly what it did before.  Not part
+ * of it: vertex normals, colour, decimation, welding of coincident positions, row tiles. */
+typedef struct { float x, y, z; uint32_t id; } sgm_mesh_vertex;      /* 16 bytes; id = n*8 + e */
+typedef struct { uint32_t v[3]; uint32_t cell; } sgm_mesh_triangle;  /* 16 bytes; v = indices into the vertex list */
+bool sgm_volume_mesh(sgm_instance* s, const sgm_volume_spec* spec, const uint32_t* d_voxels, uint32_t min_weight /* 1..65535 */,
+                     sgm_mesh_vertex* d_vertices /* 16-byte aligned */, size_t vertex_capacity,
+                     sgm_mesh_triangle* d_triangles /* 16-byte aligned */, size_t triangle_capacity,
+                     uint32_t* d_counts /* [2]: vertices, triangles */);
 
 /* ---- the TSDF volume ray-cast into depth and normal maps of any view ----
  * Extension, "parity unpinned by the reference"; defined here and restated by tests/raycast_ref.py.  The third step of spatial

@@ -333,6 +333,17 @@ typedef struct {
 int sgmd_volume_raycast(int ord, void* stream, const sgmd_volume* v, const sgmd_raycast* r, const float* poses, const void* voxels,
                         void* depth, void* normal);
 
+/* The volume as a triangle mesh, marching tetrahedra (include/sgm_mi355x.h, sgm_volume_mesh); sgm_mesh.hip.  v: the volume as the
+ * host validated it, at most 2^27 voxels.  Four launches (count per tile, one scan, the vertices, the triangles; the last two only
+ * where their capacity is not 0) that use scratch, sgmd_mesh_scratch_bytes(nx, ny, nz) bytes -- two sets of tile words -- which
+ * must not be shared with a call still in flight.  vertices, triangles: 16-byte records, those at index >= their capacity not
+ * written, and no triangle unless the whole vertex list was; counts[0], counts[1]: the full numbers of vertices and triangles.
+ * sgm_host.c references both weakly, on their own: a host built without them answers false to sgm_volume_mesh and keeps the rest
+ * of the volume. */
+size_t sgmd_mesh_scratch_bytes(int nx, int ny, int nz);
+int sgmd_volume_mesh(int ord, void* stream, const sgmd_volume* v, const void* voxels, unsigned min_weight, void* scratch,
+                     void* vertices, size_t vertex_capacity, void* triangles, size_t triangle_capacity, void* counts);
+
 /* Extension (parity unpinned by the reference), the sums of frame-to-model tracking (include/sgm_mi355x.h, sgm_track_spec);
  * sgm_track.hip.  c: the source as the host validated it (c->B <= 64 frames, one pose each, c->W * c->H <= 2^24); t: the model view.
  * poses: HOST, [c->B][12], source camera -> model camera, read before it returns.  model_depth f32 [B][t->H][t->W], model_normal

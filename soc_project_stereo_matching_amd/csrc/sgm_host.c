@@ -162,6 +162,8 @@ struct sgm_instance {
     sgm_buf d_register_keys;
     /* TSDF volume (sgm_volume_points; allocated at the first such call): the tile counts and bases of the surface list's three launches */
     sgm_buf d_volume_scratch;
+    /* the volume's mesh (sgm_volume_mesh; allocated at the first such call): the two sets of tile words of its four launches */
+    sgm_buf d_mesh_scratch;
     /* tracking (allocated at the first such call): the sums of a round of sgm_track, 29 int64 per frame, and whatever scratch the
      * launcher asks for (none in the default build) */
     sgm_buf d_track_sums;
@@ -216,7 +218,7 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     DEVICE_BUF(d_sc_small_l), DEVICE_BUF(d_sc_small_r), DEVICE_BUF(d_sc_census_l), DEVICE_BUF(d_sc_census_r), DEVICE_BUF(d_sc_g8_l),
     DEVICE_BUF(d_sc_g8_r), DEVICE_BUF(d_sc_full_l), DEVICE_BUF(d_sc_full_r), DEVICE_BUF(d_sc_disp), PINNED_BUF(h_sc_l), PINNED_BUF(h_sc_r),
     PINNED_BUF(h_sc_disp), DEVICE_BUF(d_tp_value), DEVICE_BUF(d_tp_bits), DEVICE_BUF(d_tp_stats), DEVICE_BUF(d_tp_pre),
-    DEVICE_BUF(d_tp_scratch), DEVICE_BUF(d_register_keys), DEVICE_BUF(d_volume_scratch), DEVICE_BUF(d_track_sums),
+    DEVICE_BUF(d_tp_scratch), DEVICE_BUF(d_register_keys), DEVICE_BUF(d_volume_scratch), DEVICE_BUF(d_mesh_scratch), DEVICE_BUF(d_track_sums),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -2391,6 +2393,41 @@ bool sgm_volume_points(sgm_instance* s, const sgm_volume_spec* spec, const uint3
         FAIL("sgm_volume_points: an output aliases the volume or the other output");
     if (!scratch_then_wait(s, &s->d_volume_scratch, sgmd_volume_scratch_bytes(v.nx, v.ny, v.nz), "the surface list's tiles")) return false;
     return sgmd_volume_points(s->device, s->stream, &v, d_voxels, min_weight, s->d_volume_scratch.p, d_points, capacity, d_count) == 0;
+}
+
+/* The mesh's launchers, weak symbols of their own: a host built with the volume but without them keeps the volume */
+#pragma weak sgmd_mesh_scratch_bytes
+#pragma weak sgmd_volume_mesh
+static bool mesh_available(void) { return sgmd_mesh_scratch_bytes != NULL && sgmd_volume_mesh != NULL; }
+
+#define MESH_MAX_VOXELS ((size_t)1 << 27)       /* n*8 + kind, 7 vertices per voxel and 12 triangles per cell fit 32 bits */
+
+bool sgm_volume_mesh(sgm_instance* s, const sgm_volume_spec* spec, const uint32_t* d_voxels, uint32_t min_weight,
+                     sgm_mesh_vertex* d_vertices, size_t vertex_capacity, sgm_mesh_triangle* d_triangles, size_t triangle_capacity,
+                     uint32_t* d_counts)
+{
+    sgmd_volume v;
+    if (!s || !spec || !d_voxels || !d_counts || (!d_vertices && vertex_capacity) || (!d_triangles && triangle_capacity))
+        FAIL("sgm_volume_mesh: NULL argument");
+    if (!mesh_available()) FAIL("sgm_volume_mesh: the mesh is not part of this build");
+    if (!volume_spec_valid(spec, &v)) FAIL("sgm_volume_mesh: the volume spec is outside its ranges");
+    const size_t vol_bytes = volume_bytes(&v), n = vol_bytes / sizeof(uint32_t);
+    if (n > MESH_MAX_VOXELS) FAIL("sgm_volume_mesh: %zu voxels (at most 2^27: ids and counts are 32 bits)", n);
+    if (min_weight < 1u || min_weight > 65535u) FAIL("sgm_volume_mesh: a min_weight of %u (1..65535)", min_weight);
+    if (!aligned_to(d_voxels, sizeof(uint32_t)) || !aligned_to(d_vertices, sizeof(sgm_mesh_vertex)) ||
+        !aligned_to(d_triangles, sizeof(sgm_mesh_triangle)) || !aligned_to(d_counts, sizeof(uint32_t)))
+        FAIL("sgm_volume_mesh: a pointer is not aligned (the vertices and triangles to 16 bytes, the others to their element)");
+    /* (no more than seven vertices per voxel and twelve triangles per cell can be written, whatever the capacities say) */
+    const size_t vtx_bytes = (vertex_capacity < 7 * n ? vertex_capacity : 7 * n) * sizeof(sgm_mesh_vertex);
+    const size_t tri_bytes = (triangle_capacity < 12 * n ? triangle_capacity : 12 * n) * sizeof(sgm_mesh_triangle);
+    const size_t cnt_bytes = 2 * sizeof(uint32_t);
+    if (ranges_overlap(d_vertices, vtx_bytes, d_voxels, vol_bytes) || ranges_overlap(d_triangles, tri_bytes, d_voxels, vol_bytes) ||
+        ranges_overlap(d_counts, cnt_bytes, d_voxels, vol_bytes) || ranges_overlap(d_vertices, vtx_bytes, d_triangles, tri_bytes) ||
+        ranges_overlap(d_counts, cnt_bytes, d_vertices, vtx_bytes) || ranges_overlap(d_counts, cnt_bytes, d_triangles, tri_bytes))
+        FAIL("sgm_volume_mesh: an output overlaps the volume or another output");
+    if (!scratch_then_wait(s, &s->d_mesh_scratch, sgmd_mesh_scratch_bytes(v.nx, v.ny, v.nz), "the mesh's tiles")) return false;
+    return sgmd_volume_mesh(s->device, s->stream, &v, d_voxels, min_weight, s->d_mesh_scratch.p, d_vertices, vertex_capacity, d_triangles,
+                            triangle_capacity, d_counts) == 0;
 }
 
 /* The ray-cast's launcher, a weak symbol of its own: a host built with the volume but without it keeps the volume */

@@ -36,6 +36,9 @@
  *                             (units of BASELINE) and truncation distance TRUNC -- sgm_volume_integrate of the one frame with the
  *                             identity pose -- and the volume's surface points (sgm_volume_points, min_weight 1) as a PLY like
  *                             --cloud's, coloured with the grey at the pixel a point projects to.  --cloud-z-max cuts it too
+ *            [--volume-mesh OUT.ply]   extension: with --volume, the volume as a triangle mesh (sgm_volume_mesh, marching tetrahedra,
+ *                             the min_weight of --volume-ply): a binary little-endian PLY with the elements vertex (x y z float) and
+ *                             face (a list of three vertex indices, uchar count and uint indices); prints the two counts
  *            [--volume-view ZMIN,ZMAX,STEP[,MINWEIGHT] [--volume-depth OUT.f32] [--volume-normals OUT.f32]]   extension: with
  *                             --volume, the volume rendered back into the frame's own camera after the frame is integrated
  *                             (sgm_volume_raycast: the --pinhole intrinsics, the identity pose, the image's size), marched at
@@ -244,10 +247,43 @@ static int volume_render(sgm_instance* s, const sgm_volume_spec* vol, const volu
     return rc;
 }
 
+/* --volume-mesh: the volume as a triangle mesh, sized by a counts-only call, written as a binary little-endian PLY */
+static int volume_mesh_ply(sgm_instance* s, const sgm_volume_spec* vol, const uint32_t* d_voxels, uint32_t min_weight, const char* path)
+{
+    uint32_t* d_counts = (uint32_t*)sgm_host_alloc(s, 2 * sizeof(uint32_t));
+    sgm_mesh_vertex* d_vertices = NULL;
+    sgm_mesh_triangle* d_triangles = NULL;
+    int rc = -1;
+    if (d_counts && sgm_volume_mesh(s, vol, d_voxels, min_weight, NULL, 0, NULL, 0, d_counts) && sgm_synchronize(s)) {
+        const size_t nv = d_counts[0], nt = d_counts[1];
+        d_vertices = nv ? (sgm_mesh_vertex*)sgm_host_alloc(s, nv * sizeof(sgm_mesh_vertex)) : NULL;
+        d_triangles = nt ? (sgm_mesh_triangle*)sgm_host_alloc(s, nt * sizeof(sgm_mesh_triangle)) : NULL;
+        if ((d_vertices || !nv) && (d_triangles || !nt) &&
+            sgm_volume_mesh(s, vol, d_voxels, min_weight, d_vertices, nv, d_triangles, nt, d_counts) && sgm_synchronize(s) &&
+            d_counts[0] == nv && d_counts[1] == nt) {
+            printf("volume mesh: %zu vertices, %zu triangles\n", nv, nt);
+            FILE* f = fopen(path, "wb");
+            if (f) {
+                fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+                           "element face %zu\nproperty list uchar uint vertex_indices\nend_header\n", nv, nt);
+                size_t put = 0;
+                for (size_t i = 0; i < nv; ++i) put += fwrite(&d_vertices[i], sizeof(float), 3, f) == 3;
+                for (size_t i = 0; i < nt; ++i) put += fputc(3, f) == 3 && fwrite(d_triangles[i].v, sizeof(uint32_t), 3, f) == 3;
+                rc = (fclose(f) == 0 && put == nv + nt) ? 0 : -1;
+            }
+        }
+    }
+    sgm_host_free(s, d_counts);
+    sgm_host_free(s, d_vertices);
+    sgm_host_free(s, d_triangles);
+    return rc;
+}
+
 /* --volume: the map fused into a TSDF volume with the identity pose, and the surface points read back, as sgm_point records whose
- * pixel is the one the point projects to (clamped to the image), for write_ply; with view != NULL the volume rendered as well.
+ * pixel is the one the point projects to (clamped to the image), for write_ply; with view != NULL the volume rendered as well, with
+ * mesh_path != NULL its mesh written there.
  * Page-locked buffers of an instance of its own, as above.  *out: malloc'ed, *n records. */
-static int volume_surface(const sgm_volume_spec* vol, const volume_view* view, int device, int w, int h, const float* pinhole, float z_max,
+static int volume_surface(const sgm_volume_spec* vol, const volume_view* view, const char* mesh_path, int device, int w, int h, const float* pinhole, float z_max,
                           const float* disp, sgm_point** out, size_t* n)
 {
     const sgm_cloud_spec src = {w, h, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], pinhole[4], pinhole[5], 0.0f, z_max, 0};
@@ -289,6 +325,7 @@ static int volume_surface(const sgm_volume_spec* vol, const volume_view* view, i
                 }
                 *n = count;
                 rc = view ? volume_render(s, vol, view, w, h, pinhole, d_voxels, &src, d_disp) : 0;
+                if (rc == 0 && mesh_path) rc = volume_mesh_ply(s, vol, d_voxels, 1, mesh_path);
             }
         }
     }
@@ -358,6 +395,7 @@ int main(int argc, char** argv)
     int have_pinhole = 0;
     const char* register_path = NULL;
     const char* volume_path = NULL;
+    const char* mesh_path = NULL;
     sgm_volume_spec volume = {0, 0, 0, 0.0f, {0.0f, 0.0f, 0.0f}, 0.0f, 65535};
     int have_volume = 0;
     volume_view view = {0.0f, 0.0f, 0.0f, 1, NULL, NULL, 0, 0.0f, {0.0f, 0.0f, 0.0f}};
@@ -409,6 +447,7 @@ int main(int argc, char** argv)
             ++i;
         }
         else if (v && !strcmp(a, "--volume-ply")) { volume_path = v; ++i; }
+        else if (v && !strcmp(a, "--volume-mesh")) { mesh_path = v; ++i; }
         else if (v && !strcmp(a, "--volume-view")) {
             const int got = sscanf(v, "%f,%f,%f,%u", &view.z_min, &view.z_max, &view.step, &view.min_weight);
             if (got != 3 && got != 4) { fprintf(stderr, "--volume-view wants ZMIN,ZMAX,STEP[,MINWEIGHT]\n"); return 2; }
@@ -480,6 +519,7 @@ int main(int argc, char** argv)
         fprintf(stderr, "--volume-view, --volume-depth and --volume-normals need --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n");
         return 2;
     }
+    if (mesh_path && !have_volume) { fprintf(stderr, "--volume-mesh needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n"); return 2; }
     if (have_track && (!have_volume || !have_view)) {
         fprintf(stderr, "--volume-track needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC and --volume-view ZMIN,ZMAX,STEP[,MINWEIGHT]\n");
         return 2;
@@ -619,8 +659,8 @@ int main(int argc, char** argv)
     if (volume_path) {
         sgm_point* pts = NULL;
         size_t n = 0;
-        if (volume_surface(&volume, have_view ? &view : NULL, device, w1, h1, pinhole, cloud_z_max, disp, &pts, &n) != 0) {
-            printf("volume unavailable or --volume / --volume-view / --pinhole / --cloud-z-max out of range\n");
+        if (volume_surface(&volume, have_view ? &view : NULL, mesh_path, device, w1, h1, pinhole, cloud_z_max, disp, &pts, &n) != 0) {
+            printf("volume unavailable or --volume / --volume-view / --volume-mesh / --pinhole / --cloud-z-max out of range\n");
             rc = -1;
         } else {
             uint8_t* rect = NULL;

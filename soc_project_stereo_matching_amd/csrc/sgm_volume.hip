@@ -1,5 +1,6 @@
 #include "sgm_common.hpp"
 #include "sgm_cloud_common.hpp"
+#include "sgm_volume_common.hpp"
 
 // ============================================================================================
 // Extension (parity unpinned by the reference): depth maps with known poses fused into a truncated signed distance volume
@@ -25,26 +26,8 @@
 
 #define VOL_THREADS 256                                       // the integration's; the surface list's kernels run TILE_THREADS
 
-struct VolumeParams {
-    unsigned nx, ny, nz;
-    unsigned n;                // voxels
-    float voxel, ox, oy, oz, trunc;
-    unsigned max_weight;
-};
-
 // the source image as the integration needs it beside CloudParams
 struct VolumeSource { float wf, hf; unsigned frames; };
-
-static __device__ __forceinline__ float volume_centre(float o, unsigned i, float voxel) { return o + ((float)i + 0.5f) * voxel; }
-
-// n -> (i, j, k)
-static __device__ __forceinline__ void volume_ijk(const VolumeParams& v, unsigned n, unsigned& i, unsigned& j, unsigned& k)
-{
-    const unsigned row = n / v.nx;
-    i = n - row * v.nx;
-    k = row / v.ny;
-    j = row - k * v.ny;
-}
 
 // ---- integration ---------------------------------------------------------------------------------------------------------------
 
@@ -376,22 +359,6 @@ __global__ __launch_bounds__(RAY_THREADS) void sgm_volume_raycast_k(VolumeParams
         normal[3 * at + 1] = nrm[1];
         normal[3 * at + 2] = nrm[2];
     }
-}
-
-static bool volume_ok(const sgmd_volume* v)
-{
-    return v && v->nx >= 1 && v->ny >= 1 && v->nz >= 1 && v->nx <= 1024 && v->ny <= 1024 && v->nz <= 1024 &&
-           (unsigned long long)v->nx * v->ny * v->nz <= (1ull << 30) && v->max_weight >= 1 && v->max_weight <= 65535;
-}
-
-static VolumeParams volume_params(const sgmd_volume* v)
-{
-    VolumeParams p;
-    p.nx = (unsigned)v->nx; p.ny = (unsigned)v->ny; p.nz = (unsigned)v->nz;
-    p.n = p.nx * p.ny * p.nz;
-    p.voxel = v->voxel; p.ox = v->origin[0]; p.oy = v->origin[1]; p.oz = v->origin[2]; p.trunc = v->trunc;
-    p.max_weight = v->max_weight;
-    return p;
 }
 
 extern "C" {

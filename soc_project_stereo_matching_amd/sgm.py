@@ -126,6 +126,18 @@ class SGMVolumeSpec(C.Structure):
 SURFACE_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32), ("id", np.uint32)])   # sgm_surface_point
 
 
+MESH_VERTEX_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32), ("id", np.uint32)])    # sgm_mesh_vertex
+MESH_TRIANGLE_DTYPE = np.dtype([("v", np.uint32, (3,)), ("cell", np.uint32)])                                   # sgm_mesh_triangle
+
+
+class SGMMeshVertex(C.Structure):                                 # ctypes mirror of sgm_mesh_vertex
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("id", C.c_uint32)]
+
+
+class SGMMeshTriangle(C.Structure):                               # ctypes mirror of sgm_mesh_triangle
+    _fields_ = [("v", C.c_uint32 * 3), ("cell", C.c_uint32)]
+
+
 def volume_spec(nx, ny, nz, voxel, origin, trunc, max_weight=64) -> SGMVolumeSpec:
     """A sgm_volume_spec: nx x ny x nz voxels of edge `voxel` (units of baseline), the corner of voxel (0, 0, 0) at `origin` in the
     world, truncation distance `trunc`, weights capped at max_weight (1..65535)."""
@@ -404,6 +416,9 @@ def _load() -> C.CDLL:
         L.sgm_volume_integrate.restype = C.c_bool
         L.sgm_volume_points.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
         L.sgm_volume_points.restype = C.c_bool
+    if hasattr(L, "sgm_volume_mesh"):         # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_volume_mesh.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sgm_volume_mesh.restype = C.c_bool
     if hasattr(L, "sgm_volume_raycast"):      # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_volume_raycast.argtypes = [C.c_void_p] * 7
         L.sgm_volume_raycast.restype = C.c_bool
@@ -1270,6 +1285,14 @@ class SGMInstance(_StageReader):
         room for `capacity` records; None with capacity 0) and their full number into d_count[0].  Asynchronous on `stream`."""
         return bool(self.lib.sgm_volume_points(self.handle, C.byref(spec), d_voxels, int(min_weight), d_points or None, int(capacity),
                                                d_count))
+
+    def volume_mesh(self, spec: SGMVolumeSpec, d_voxels: int, min_weight: int, d_vertices, vertex_capacity: int, d_triangles,
+                    triangle_capacity: int, d_counts: int) -> bool:
+        """sgm_volume_mesh: the volume as an indexed triangle mesh, marching tetrahedra: MESH_VERTEX_DTYPE records sorted by id into
+        d_vertices and MESH_TRIANGLE_DTYPE records into d_triangles (both 16-byte aligned, may be None with capacity 0), the full
+        numbers of vertices and triangles in d_counts[0], d_counts[1]; triangles only where the whole vertex list fitted"""
+        return bool(self.lib.sgm_volume_mesh(self.handle, C.byref(spec), d_voxels, int(min_weight), d_vertices or None, int(vertex_capacity),
+                                             d_triangles or None, int(triangle_capacity), d_counts))
 
     def volume_raycast(self, vol: SGMVolumeSpec, view: SGMRaycastSpec, poses, d_voxels: int, d_depth: int, d_normal=None) -> bool:
         """sgm_volume_raycast: the volume at d_voxels rendered into view.frames depth maps [frames][height][width] float32 at d_depth
