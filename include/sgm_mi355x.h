@@ -845,6 +845,79 @@ bool sgm_track(sgm_instance* s, const sgm_cloud_spec* src, const sgm_track_spec*
                double* trace_poses /* HOST [iterations + 1][frames][12], or NULL */);
 bool sgm_track_world_pose(const float model_pose[12], const double rel[12], float out[12]);   /* host only */
 
+/* ---- colour in the TSDF volume: fused with the depth, ray-cast with it, given to the mesh ----
+ * Extension, "parity unpinned by the reference"; defined here and restated by tests/color_ref.py.  The entry points above carry
+ * geometry only; these three carry the reference camera's image along, so that the fused model is the left image on the surface: a
+ * rendered preview that looks like a picture, a mesh a viewer shows in colour.  Each is the twin of a plain entry point and leaves
+ * that one's outputs exactly as the plain call leaves them.  Float arithmetic follows the sections above: float32, every operation
+ * rounded on its own, no contraction, "finite" tested on the bit pattern; the averages are exact integers; no atomics, the same
+ * bytes on every run.
+ *
+ * The colour volume.  A second caller-owned device array of nx * ny * nz uint32 words, indexed like the TSDF words, each
+ *   (cw << 24) | (b << 16) | (g << 8) | r
+ * with cw an 8-bit weight of its own.  All-zero bytes mean "no colour anywhere"; its size is sgm_volume_bytes(spec); there is no
+ * clear entry point (hipMemset it, as for the TSDF words).
+ *
+ * sgm_volume_integrate_color.  d_image is the reference camera's image, registered to the disparity map, [frames][height][width]:
+ * channels == 1: uint8 grey, taken as r = g = b;  channels == 4: uint32 per pixel, r | g << 8 | b << 16, the top byte ignored,
+ * the pointer 4-byte aligned.  d_voxels is updated exactly as sgm_volume_integrate updates it, word for word (d_disp == NULL: the
+ * instance's last final map, under the same rules).  For voxel and frame f the colour word changes iff frame f updated the voxel's
+ * TSDF word under every rule of the volume contract AND sdf <= trunc (tested in float: a voxel far in front of the surface gets
+ * distance but no colour).  Then, with p the channel value of the source pixel (f, vf, uf) that gave Z, per channel
+ *   c = floor_div(2*(c*cw + p) + (cw + 1), 2*(cw + 1))       (all operands non-negative, below 2^31: rounded, halves up)
+ * and then
+ *   cw = min(cw + 1, min(max_weight, 255))
+ * Frames take effect in order; one call over B frames equals B calls of one frame, bit for bit, in both arrays; a launch reads and
+ * writes each word of either array at most once (the lane that owns a voxel owns its colour word; it stores the colour words only
+ * where one changed).  Both arrays are accessed 16 bytes at a time where nx % 4 == 0 and both pointers allow it, else one voxel per
+ * lane, with the same results.
+ *
+ * sgm_volume_raycast_color.  d_depth and d_normal (may be NULL) receive exactly the bytes sgm_volume_raycast writes.  d_rgba is
+ * uint32 [frames][height][width]: 0 for an empty pixel; at a hit, with g* = go + Z* * gd, the first of these rules that applies:
+ *   trilinear   the eight voxels of F(g*): h = g* - 0.5f, i0 = floorf(h), f = h - i0, the same in-grid test in float.  Valid iff
+ *               all eight colour words have cw >= 1 (the TSDF weight is not asked again).  Per channel, on (float)c,
+ *               lerp(p, q, s) = p + s*(q - p) along x, then y, then z;   v = (unsigned)rintf(fminf(fmaxf(value, 0), 255));
+ *               the pixel is 0xFF000000 | b << 16 | g << 8 | r
+ *   nearest     the voxel (floorf g*_x, floorf g*_y, floorf g*_z), where all three g*_i are finite and 0 <= g*_i < (float)n_i (the
+ *               march's own admission test, in float): if its cw >= 1, its colour with alpha 0xFF
+ *   else        0
+ *
+ * sgm_volume_colors: colours for a list the volume produced.  d_records are 16-byte records with the id in the last word:
+ * id_kinds == 8: sgm_mesh_vertex, id = n*8 + e, edge kinds 0..6;  id_kinds == 4: sgm_surface_point, id = n*4 + a, axes 0..2.
+ * Only the id is read.  Record r is handled iff r < capacity and (d_count == NULL or r < d_count[0]); nothing is written for the
+ * other records, so the call can be queued straight behind sgm_volume_mesh (d_count = its d_counts) or sgm_volume_points without
+ * reading the count back.  d_rgba is uint32 [capacity].  The edge (n, e) of a record, with far voxel m (the (dx,dy,dz) table of
+ * the mesh contract), is valid iff n < nx*ny*nz, e names a kind and m is inside the grid; otherwise d_rgba[r] = 0.  Else
+ *   den = (float)tq[n] - (float)tq[m];   s = den != 0 ? fminf(fmaxf((float)tq[n] / den, 0), 1) : 0
+ *   both ends have cw >= 1:      per channel rintf(lerp(c_n, c_m, s)), alpha 0xFF
+ *   exactly one end has colour:  that end's colour, alpha 0xFF
+ *   neither:                     0
+ * One launch, one lane per record, no scratch.
+ *
+ * All three: poses is a HOST pointer as in the plain twins; the others are device pointers.  Asynchronous on sgm_stream(s), behind
+ * the last match also with sgm_set_overlap_post, as their twins.  false, nothing queued and one "sgm_mi355x: <entry point>: ..."
+ * line on stderr: everything the plain twin refuses (sgm_volume_colors: a NULL s, spec, d_voxels or d_colors; a spec outside the
+ * volume's ranges; with id_kinds 8 a spec over the mesh's 2^27 voxels; a capacity above 2^32); a NULL d_image, d_colors or d_rgba
+ * (sgm_volume_colors: a NULL d_records or d_rgba with capacity > 0); channels other than 1 or 4; id_kinds other than 4 or 8; a
+ * d_image (with channels 4), d_colors, d_rgba or d_count that is not 4-byte aligned, d_records not 16-byte aligned; d_colors that
+ * overlaps d_voxels, the image or a map (integration); d_rgba that overlaps the volume, the colours or another output (ray-cast);
+ * an output that overlaps an input (sgm_volume_colors); a build without the kernel.  capacity == 0 is a successful no-op.  An
+ * instance that never calls these entry points allocates and launches exactly what it did before.  Not part of it: colour spaces
+ * and gamma (the bytes are averaged as they are), shading, textures and texture atlases, per-triangle colour, a second camera's
+ * image (register it first: sgm_register_gather), row tiles, sgm_match_planes. */
+bool sgm_volume_integrate_color(sgm_instance* s, const sgm_volume_spec* spec, const sgm_cloud_spec* src,
+                                const float* poses /* HOST, [src->frames][12], as sgm_volume_integrate */,
+                                const float* d_disp, const uint8_t* d_mask, const uint16_t* d_conf,
+                                const void* d_image /* [frames][height][width] u8 or u32 */, int channels /* 1 or 4 */,
+                                uint32_t* d_voxels, uint32_t* d_colors);
+bool sgm_volume_raycast_color(sgm_instance* s, const sgm_volume_spec* vol, const sgm_raycast_spec* view,
+                              const float* poses /* HOST [frames][12], as sgm_volume_raycast */,
+                              const uint32_t* d_voxels, const uint32_t* d_colors, float* d_depth /* [frames][height][width] */,
+                              float* d_normal /* [frames][height][width][3], may be NULL */, uint32_t* d_rgba /* [frames][height][width] */);
+bool sgm_volume_colors(sgm_instance* s, const sgm_volume_spec* spec, const uint32_t* d_voxels, const uint32_t* d_colors,
+                       const void* d_records /* 16-byte records, id in the last word */, size_t capacity,
+                       const uint32_t* d_count /* device u32, may be NULL */, int id_kinds /* 8 or 4 */, uint32_t* d_rgba /* u32 [capacity] */);
+
 /* ---- matching at half or quarter scale, re-search at full resolution ----
  * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/scaled_ref.py.  A match at
  * 1/f scale pays for f^3 fewer cells of W x H x D for the same metric range; the result is brought back to the full grid by a guided

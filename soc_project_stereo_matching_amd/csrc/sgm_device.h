@@ -333,6 +333,20 @@ typedef struct {
 int sgmd_volume_raycast(int ord, void* stream, const sgmd_volume* v, const sgmd_raycast* r, const float* poses, const void* voxels,
                         void* depth, void* normal);
 
+/* Colour in the volume (include/sgm_mi355x.h, the colour section); sgm_volume.hip.  colors: u32 [nz][ny][nx] beside the voxels,
+ * (cw << 24) | (b << 16) | (g << 8) | r.  sgmd_volume_integrate_color: sgmd_volume_integrate with the source's image (u8 grey with
+ * channels 1, u32 r | g << 8 | b << 16 with channels 4, [B][c->H][c->W]) fused into colors by the same launch.
+ * sgmd_volume_raycast_color: sgmd_volume_raycast with rgba u32 [B][H][W] written beside depth and normal (NULL: not written).
+ * sgmd_volume_colors: one launch, no scratch: rgba[r] for every 16-byte record r < capacity (and < count[0] where count, a device
+ * word, is not NULL) whose last word is the id n * id_kinds + e of a mesh vertex (id_kinds 8) or of a surface point (4).
+ * sgm_host.c references each weakly, on its own: a host built without one answers false to its entry point and keeps the rest. */
+int sgmd_volume_integrate_color(int ord, void* stream, const sgmd_volume* v, const sgmd_cloud* c, const float* poses, const void* disp,
+                                const void* mask, const void* conf, const void* image, int channels, void* voxels, void* colors);
+int sgmd_volume_raycast_color(int ord, void* stream, const sgmd_volume* v, const sgmd_raycast* r, const float* poses, const void* voxels,
+                              const void* colors, void* depth, void* normal, void* rgba);
+int sgmd_volume_colors(int ord, void* stream, const sgmd_volume* v, const void* voxels, const void* colors, const void* records,
+                       size_t capacity, const void* count, int id_kinds, void* rgba);
+
 /* The volume as a triangle mesh, marching tetrahedra (include/sgm_mi355x.h, sgm_volume_mesh); sgm_mesh.hip.  v: the volume as the
  * host validated it, at most 2^27 voxels.  Four launches (count per tile, one scan, the vertices, the triangles; the last two only
  * where their capacity is not 0) that use scratch, sgmd_mesh_scratch_bytes(nx, ny, nz) bytes -- two sets of tile words -- which

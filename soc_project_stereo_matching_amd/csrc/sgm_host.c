@@ -2472,6 +2472,97 @@ bool sgm_volume_raycast(sgm_instance* s, const sgm_volume_spec* vol, const sgm_r
     return sgmd_volume_raycast(s->device, s->stream, &v, &r, poses, d_voxels, d_depth, d_normal) == 0;
 }
 
+/* ------------------------------------------------------------------ colour in the volume (extension) */
+
+/* The coloured launchers of sgm_volume.hip, weak symbols each on its own: a host built without one refuses its entry point and keeps
+ * the rest of the volume */
+#pragma weak sgmd_volume_integrate_color
+#pragma weak sgmd_volume_raycast_color
+#pragma weak sgmd_volume_colors
+
+bool sgm_volume_integrate_color(sgm_instance* s, const sgm_volume_spec* spec, const sgm_cloud_spec* src, const float* poses,
+                                const float* d_disp, const uint8_t* d_mask, const uint16_t* d_conf, const void* d_image, int channels,
+                                uint32_t* d_voxels, uint32_t* d_colors)
+{
+    sgmd_volume v;
+    sgmd_cloud c;
+    if (!s || !spec || !src || !poses || !d_voxels || !d_image || !d_colors) FAIL("sgm_volume_integrate_color: NULL argument");
+    if (sgmd_volume_integrate_color == NULL) FAIL("sgm_volume_integrate_color: the coloured integration is not part of this build");
+    if (!volume_spec_valid(spec, &v)) FAIL("sgm_volume_integrate_color: the volume spec is outside its ranges");
+    if (!cloud_spec_valid(src, &c)) FAIL("sgm_volume_integrate_color: the source spec is outside its ranges");
+    if (c.B > SGMD_MAX_POSES) FAIL("sgm_volume_integrate_color: %d frames in one call (at most %d)", c.B, SGMD_MAX_POSES);
+    if (channels != 1 && channels != 4) FAIL("sgm_volume_integrate_color: %d channels (1: u8 grey, 4: u32 r | g << 8 | b << 16)", channels);
+    if (!poses_finite("sgm_volume_integrate_color", poses, c.B)) return false;
+    if (!aligned_to(d_disp, sizeof(float)) || !aligned_to(d_conf, sizeof(uint16_t)) || !aligned_to(d_voxels, sizeof(uint32_t)) ||
+        !aligned_to(d_colors, sizeof(uint32_t)) || !aligned_to(d_image, (size_t)channels))
+        FAIL("sgm_volume_integrate_color: a pointer is not aligned to its element");
+    d_disp = source_map(s, &c, d_disp, "sgm_volume_integrate_color");
+    if (!d_disp) return false;
+    const size_t px = (size_t)c.B * c.W * c.H, vol_bytes = volume_bytes(&v);
+    const void* const maps[] = {d_disp, d_mask, d_conf, d_image};
+    const size_t map_bytes[] = {px * sizeof(float), px, px * sizeof(uint16_t), px * (size_t)channels};
+    for (int i = 0; i < 4; ++i) {
+        if (ranges_overlap(d_voxels, vol_bytes, maps[i], map_bytes[i])) FAIL("sgm_volume_integrate_color: the volume aliases a map");
+        if (ranges_overlap(d_colors, vol_bytes, maps[i], map_bytes[i])) FAIL("sgm_volume_integrate_color: the colours overlap a map or the image");
+    }
+    if (ranges_overlap(d_colors, vol_bytes, d_voxels, vol_bytes)) FAIL("sgm_volume_integrate_color: the colours overlap the volume");
+    /* the map may be the result of a match whose last stages run on a stream of their own, as in sgm_volume_integrate */
+    if (wait_for_result(s, s->stream) != 0) return false;
+    return sgmd_volume_integrate_color(s->device, s->stream, &v, &c, poses, d_disp, d_mask, d_conf, d_image, channels, d_voxels, d_colors) == 0;
+}
+
+bool sgm_volume_raycast_color(sgm_instance* s, const sgm_volume_spec* vol, const sgm_raycast_spec* view, const float* poses,
+                              const uint32_t* d_voxels, const uint32_t* d_colors, float* d_depth, float* d_normal, uint32_t* d_rgba)
+{
+    sgmd_volume v;
+    sgmd_raycast r;
+    if (!s || !vol || !view || !poses || !d_voxels || !d_colors || !d_depth || !d_rgba) FAIL("sgm_volume_raycast_color: NULL argument");
+    if (sgmd_volume_raycast_color == NULL) FAIL("sgm_volume_raycast_color: the coloured ray-cast is not part of this build");
+    if (!volume_spec_valid(vol, &v)) FAIL("sgm_volume_raycast_color: the volume spec is outside its ranges");
+    const char* why = raycast_spec_invalid(view, &r);
+    if (why) FAIL("sgm_volume_raycast_color: the view is outside its ranges (%s)", why);
+    if (!poses_finite("sgm_volume_raycast_color", poses, r.B)) return false;
+    if (!aligned_to(d_voxels, sizeof(uint32_t)) || !aligned_to(d_colors, sizeof(uint32_t)) || !aligned_to(d_depth, sizeof(float)) ||
+        !aligned_to(d_normal, sizeof(float)) || !aligned_to(d_rgba, sizeof(uint32_t)))
+        FAIL("sgm_volume_raycast_color: a pointer is not aligned to its element");
+    const size_t vol_bytes = volume_bytes(&v), depth_bytes = (size_t)r.B * r.W * r.H * sizeof(float);
+    void* const outs[] = {d_depth, d_normal, d_rgba};
+    const size_t out_bytes[] = {depth_bytes, 3 * depth_bytes, depth_bytes};
+    for (int i = 0; i < 3; ++i) {
+        if (ranges_overlap(outs[i], out_bytes[i], d_voxels, vol_bytes) || ranges_overlap(outs[i], out_bytes[i], d_colors, vol_bytes))
+            FAIL("sgm_volume_raycast_color: an output overlaps the volume or the colours");
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(outs[i], out_bytes[i], outs[j], out_bytes[j])) FAIL("sgm_volume_raycast_color: an output overlaps another output");
+    }
+    /* the same place in the queue as sgm_volume_raycast */
+    if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
+    return sgmd_volume_raycast_color(s->device, s->stream, &v, &r, poses, d_voxels, d_colors, d_depth, d_normal, d_rgba) == 0;
+}
+
+bool sgm_volume_colors(sgm_instance* s, const sgm_volume_spec* spec, const uint32_t* d_voxels, const uint32_t* d_colors,
+                       const void* d_records, size_t capacity, const uint32_t* d_count, int id_kinds, uint32_t* d_rgba)
+{
+    sgmd_volume v;
+    if (!s || !spec || !d_voxels || !d_colors || (capacity && (!d_records || !d_rgba))) FAIL("sgm_volume_colors: NULL argument");
+    if (sgmd_volume_colors == NULL) FAIL("sgm_volume_colors: the colours of a list are not part of this build");
+    if (!volume_spec_valid(spec, &v)) FAIL("sgm_volume_colors: the volume spec is outside its ranges");
+    if (id_kinds != 4 && id_kinds != 8) FAIL("sgm_volume_colors: id_kinds of %d (8: sgm_mesh_vertex, 4: sgm_surface_point)", id_kinds);
+    const size_t vol_bytes = volume_bytes(&v), n = vol_bytes / sizeof(uint32_t);
+    if (id_kinds == 8 && n > MESH_MAX_VOXELS) FAIL("sgm_volume_colors: %zu voxels (at most 2^27 for the ids of a mesh)", n);
+    if (!aligned_to(d_voxels, sizeof(uint32_t)) || !aligned_to(d_colors, sizeof(uint32_t)) || !aligned_to(d_records, 16) ||
+        !aligned_to(d_count, sizeof(uint32_t)) || !aligned_to(d_rgba, sizeof(uint32_t)))
+        FAIL("sgm_volume_colors: a pointer is not aligned (the records to 16 bytes, the others to their element)");
+    if (capacity > ((size_t)1 << 32)) FAIL("sgm_volume_colors: a capacity of %zu records (ids are 32 bits: at most 2^32)", capacity);
+    const void* const ins[] = {d_voxels, d_colors, d_records, d_count};
+    const size_t in_bytes[] = {vol_bytes, vol_bytes, capacity * 16, sizeof(uint32_t)};
+    for (int i = 0; i < 4; ++i)
+        if (ranges_overlap(d_rgba, capacity * sizeof(uint32_t), ins[i], in_bytes[i])) FAIL("sgm_volume_colors: the output overlaps an input");
+    if (capacity == 0) return true;
+    /* behind the list's own call on this stream, and behind the last match as that call is */
+    if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
+    return sgmd_volume_colors(s->device, s->stream, &v, d_voxels, d_colors, d_records, capacity, d_count, id_kinds, d_rgba) == 0;
+}
+
 /* ------------------------------------------------------------------ frame-to-model tracking (extension) */
 
 /* The launcher of sgm_track.hip, a weak symbol of its own: a host built without it keeps the volume and the ray-cast */

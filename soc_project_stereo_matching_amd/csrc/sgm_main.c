@@ -44,6 +44,12 @@
  *                             (sgm_volume_raycast: the --pinhole intrinsics, the identity pose, the image's size), marched at
  *                             Z = ZMIN + k * STEP up to ZMAX over voxels of weight MINWEIGHT (default 1) or more: the depth as raw
  *                             float32 [H][W] like --raw, the unit normals as raw float32 [H][W][3], NaN where no surface is met
+ *            [--volume-color [--volume-image OUT.pgm]]   extension: with --volume, the frame fused with its own grey image (the one
+ *                             --volume-ply takes its colours from) into a colour volume beside the TSDF words
+ *                             (sgm_volume_integrate_color, channels 1); --volume-mesh then gains uchar red green blue per vertex
+ *                             (sgm_volume_colors), and --volume-image, with --volume-view, writes the red channel of the coloured
+ *                             ray-cast (sgm_volume_raycast_color) as a PGM, 0 where no surface is met.  Without it every output
+ *                             file is what it was
  *            [--volume-track ITER,DISTMAX[,TX,TY,TZ]]   extension: with --volume and --volume-view, the frame tracked against that
  *                             render (sgm_track: ITER rounds, gate DISTMAX, span the middle of the march (ZMIN + ZMAX) / 2, at least
  *                             6 pixels, pivots above 1e-6) from the identity displaced by the translation TX,TY,TZ (default 0,0,0);
@@ -188,6 +194,7 @@ typedef struct {
     const char* normals_path;
     int track_iterations;          /* --volume-track: 0 without it */
     float track_dist_max, track_t[3];
+    const char* image_path;        /* --volume-image (with --volume-color) */
 } volume_view;
 
 static int write_floats(const char* path, const float* v, size_t n)
@@ -221,9 +228,10 @@ static int volume_track(sgm_instance* s, const volume_view* view, const sgm_clou
 }
 
 /* the volume rendered into the frame's own camera with the identity pose, and the maps written; with --volume-track the frame
- * (src, d_disp) tracked against that render, which then has normals whether they are written or not */
+ * (src, d_disp) tracked against that render, which then has normals whether they are written or not.  d_colors != NULL
+ * (--volume-color): the coloured ray-cast, whose red channel --volume-image writes as a PGM, 0 where the pixel is empty */
 static int volume_render(sgm_instance* s, const sgm_volume_spec* vol, const volume_view* view, int w, int h, const float* pinhole,
-                         const uint32_t* d_voxels, const sgm_cloud_spec* src, const float* d_disp)
+                         const uint32_t* d_voxels, const uint32_t* d_colors, const sgm_cloud_spec* src, const float* d_disp)
 {
     static const float identity[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
     const sgm_raycast_spec spec = {w, h, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], view->z_min, view->z_max, view->step, view->min_weight};
@@ -231,8 +239,11 @@ static int volume_render(sgm_instance* s, const sgm_volume_spec* vol, const volu
     float* d_depth = (float*)sgm_host_alloc(s, px * sizeof(float));
     const int normals = view->normals_path || view->track_iterations;
     float* d_normal = normals ? (float*)sgm_host_alloc(s, 3 * px * sizeof(float)) : NULL;
+    uint32_t* d_rgba = d_colors ? (uint32_t*)sgm_host_alloc(s, px * sizeof(uint32_t)) : NULL;
     int rc = -1;
-    if (d_depth && (d_normal || !normals) && sgm_volume_raycast(s, vol, &spec, identity, d_voxels, d_depth, d_normal) &&
+    if (d_depth && (d_normal || !normals) && (d_rgba || !d_colors) &&
+        (d_colors ? sgm_volume_raycast_color(s, vol, &spec, identity, d_voxels, d_colors, d_depth, d_normal, d_rgba)
+                  : sgm_volume_raycast(s, vol, &spec, identity, d_voxels, d_depth, d_normal)) &&
         sgm_synchronize(s)) {
         size_t hits = 0;
         for (size_t i = 0; i < px; ++i) hits += d_depth[i] == d_depth[i];
@@ -240,34 +251,51 @@ static int volume_render(sgm_instance* s, const sgm_volume_spec* vol, const volu
         rc = 0;
         if (view->depth_path && write_floats(view->depth_path, d_depth, px) != 0) rc = -1;
         if (view->normals_path && write_floats(view->normals_path, d_normal, 3 * px) != 0) rc = -1;
+        if (view->image_path) {
+            uint8_t* red = (uint8_t*)malloc(px);
+            for (size_t i = 0; red && i < px; ++i) red[i] = (uint8_t)(d_rgba[i] & 0xFFu);
+            if (!red || sgm_write_pgm(view->image_path, red, w, h) != 0) rc = -1;
+            free(red);
+        }
         if (rc == 0 && view->track_iterations) rc = volume_track(s, view, src, d_disp, d_depth, d_normal);
     }
     sgm_host_free(s, d_depth);
     sgm_host_free(s, d_normal);
+    sgm_host_free(s, d_rgba);
     return rc;
 }
 
-/* --volume-mesh: the volume as a triangle mesh, sized by a counts-only call, written as a binary little-endian PLY */
-static int volume_mesh_ply(sgm_instance* s, const sgm_volume_spec* vol, const uint32_t* d_voxels, uint32_t min_weight, const char* path)
+/* --volume-mesh: the volume as a triangle mesh, sized by a counts-only call, written as a binary little-endian PLY.  d_colors !=
+ * NULL (--volume-color): sgm_volume_colors of the vertices, queued behind the mesh with its counts, as uchar red green blue */
+static int volume_mesh_ply(sgm_instance* s, const sgm_volume_spec* vol, const uint32_t* d_voxels, const uint32_t* d_colors,
+                           uint32_t min_weight, const char* path)
 {
     uint32_t* d_counts = (uint32_t*)sgm_host_alloc(s, 2 * sizeof(uint32_t));
     sgm_mesh_vertex* d_vertices = NULL;
     sgm_mesh_triangle* d_triangles = NULL;
+    uint32_t* d_rgba = NULL;
     int rc = -1;
     if (d_counts && sgm_volume_mesh(s, vol, d_voxels, min_weight, NULL, 0, NULL, 0, d_counts) && sgm_synchronize(s)) {
         const size_t nv = d_counts[0], nt = d_counts[1];
         d_vertices = nv ? (sgm_mesh_vertex*)sgm_host_alloc(s, nv * sizeof(sgm_mesh_vertex)) : NULL;
         d_triangles = nt ? (sgm_mesh_triangle*)sgm_host_alloc(s, nt * sizeof(sgm_mesh_triangle)) : NULL;
-        if ((d_vertices || !nv) && (d_triangles || !nt) &&
-            sgm_volume_mesh(s, vol, d_voxels, min_weight, d_vertices, nv, d_triangles, nt, d_counts) && sgm_synchronize(s) &&
+        d_rgba = (d_colors && nv) ? (uint32_t*)sgm_host_alloc(s, nv * sizeof(uint32_t)) : NULL;
+        if ((d_vertices || !nv) && (d_triangles || !nt) && (d_rgba || !d_colors || !nv) &&
+            sgm_volume_mesh(s, vol, d_voxels, min_weight, d_vertices, nv, d_triangles, nt, d_counts) &&
+            (!d_colors || sgm_volume_colors(s, vol, d_voxels, d_colors, d_vertices, nv, d_counts, 8, d_rgba)) && sgm_synchronize(s) &&
             d_counts[0] == nv && d_counts[1] == nt) {
             printf("volume mesh: %zu vertices, %zu triangles\n", nv, nt);
             FILE* f = fopen(path, "wb");
             if (f) {
-                fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
-                           "element face %zu\nproperty list uchar uint vertex_indices\nend_header\n", nv, nt);
+                fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n%s"
+                           "element face %zu\nproperty list uchar uint vertex_indices\nend_header\n", nv,
+                        d_colors ? "property uchar red\nproperty uchar green\nproperty uchar blue\n" : "", nt);
                 size_t put = 0;
-                for (size_t i = 0; i < nv; ++i) put += fwrite(&d_vertices[i], sizeof(float), 3, f) == 3;
+                for (size_t i = 0; i < nv; ++i) {
+                    const uint8_t rgb[3] = {(uint8_t)(d_colors ? d_rgba[i] : 0u), (uint8_t)(d_colors ? d_rgba[i] >> 8 : 0u),
+                                            (uint8_t)(d_colors ? d_rgba[i] >> 16 : 0u)};
+                    put += fwrite(&d_vertices[i], sizeof(float), 3, f) == 3 && (!d_colors || fwrite(rgb, 1, 3, f) == 3);
+                }
                 for (size_t i = 0; i < nt; ++i) put += fputc(3, f) == 3 && fwrite(d_triangles[i].v, sizeof(uint32_t), 3, f) == 3;
                 rc = (fclose(f) == 0 && put == nv + nt) ? 0 : -1;
             }
@@ -276,15 +304,17 @@ static int volume_mesh_ply(sgm_instance* s, const sgm_volume_spec* vol, const ui
     sgm_host_free(s, d_counts);
     sgm_host_free(s, d_vertices);
     sgm_host_free(s, d_triangles);
+    sgm_host_free(s, d_rgba);
     return rc;
 }
 
 /* --volume: the map fused into a TSDF volume with the identity pose, and the surface points read back, as sgm_point records whose
  * pixel is the one the point projects to (clamped to the image), for write_ply; with view != NULL the volume rendered as well, with
- * mesh_path != NULL its mesh written there.
+ * mesh_path != NULL its mesh written there.  grey != NULL (--volume-color): the frame fused with that image, its own grey, into a
+ * colour volume beside the TSDF words (sgm_volume_integrate_color, channels 1), which the render and the mesh then take.
  * Page-locked buffers of an instance of its own, as above.  *out: malloc'ed, *n records. */
-static int volume_surface(const sgm_volume_spec* vol, const volume_view* view, const char* mesh_path, int device, int w, int h, const float* pinhole, float z_max,
-                          const float* disp, sgm_point** out, size_t* n)
+static int volume_surface(const sgm_volume_spec* vol, const volume_view* view, const char* mesh_path, const uint8_t* grey, int device, int w, int h,
+                          const float* pinhole, float z_max, const float* disp, sgm_point** out, size_t* n)
 {
     const sgm_cloud_spec src = {w, h, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], pinhole[4], pinhole[5], 0.0f, z_max, 0};
     static const float identity[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
@@ -301,13 +331,20 @@ static int volume_surface(const sgm_volume_spec* vol, const volume_view* view, c
     uint32_t* d_voxels = (uint32_t*)sgm_host_alloc(s, bytes);
     uint32_t* d_count = (uint32_t*)sgm_host_alloc(s, sizeof(uint32_t));
     sgm_surface_point* d_points = NULL;
+    uint8_t* d_image = grey ? (uint8_t*)sgm_host_alloc(s, px) : NULL;
+    uint32_t* d_colors = grey ? (uint32_t*)sgm_host_alloc(s, bytes) : NULL;
     int rc = -1;
     *out = NULL;
     *n = 0;
-    if (d_disp && d_voxels && d_count) {
+    if (d_disp && d_voxels && d_count && (!grey || (d_image && d_colors))) {
         memcpy(d_disp, disp, px * sizeof(float));
         memset(d_voxels, 0, bytes);                               /* the empty volume */
-        if (sgm_volume_integrate(s, vol, &src, identity, d_disp, NULL, NULL, d_voxels) &&
+        if (grey) {
+            memcpy(d_image, grey, px);
+            memset(d_colors, 0, bytes);                           /* no colour anywhere */
+        }
+        if ((grey ? sgm_volume_integrate_color(s, vol, &src, identity, d_disp, NULL, NULL, d_image, 1, d_voxels, d_colors)
+                  : sgm_volume_integrate(s, vol, &src, identity, d_disp, NULL, NULL, d_voxels)) &&
             sgm_volume_points(s, vol, d_voxels, 1, NULL, 0, d_count) && sgm_synchronize(s)) {
             const size_t count = *d_count;
             size_t seen = 0;
@@ -324,11 +361,13 @@ static int volume_surface(const sgm_volume_spec* vol, const volume_view* view, c
                     (*out)[i] = (sgm_point){q.x, q.y, q.z, ((uint32_t)v << 16) | (uint32_t)u};
                 }
                 *n = count;
-                rc = view ? volume_render(s, vol, view, w, h, pinhole, d_voxels, &src, d_disp) : 0;
-                if (rc == 0 && mesh_path) rc = volume_mesh_ply(s, vol, d_voxels, 1, mesh_path);
+                rc = view ? volume_render(s, vol, view, w, h, pinhole, d_voxels, d_colors, &src, d_disp) : 0;
+                if (rc == 0 && mesh_path) rc = volume_mesh_ply(s, vol, d_voxels, d_colors, 1, mesh_path);
             }
         }
     }
+    sgm_host_free(s, d_image);
+    sgm_host_free(s, d_colors);
     sgm_host_free(s, d_disp);
     sgm_host_free(s, d_voxels);
     sgm_host_free(s, d_count);
@@ -398,8 +437,8 @@ int main(int argc, char** argv)
     const char* mesh_path = NULL;
     sgm_volume_spec volume = {0, 0, 0, 0.0f, {0.0f, 0.0f, 0.0f}, 0.0f, 65535};
     int have_volume = 0;
-    volume_view view = {0.0f, 0.0f, 0.0f, 1, NULL, NULL, 0, 0.0f, {0.0f, 0.0f, 0.0f}};
-    int have_track = 0;
+    volume_view view = {0.0f, 0.0f, 0.0f, 1, NULL, NULL, 0, 0.0f, {0.0f, 0.0f, 0.0f}, NULL};
+    int have_track = 0, volume_color = 0;
     int have_view = 0;
     int register_splat = 2, register_splat_set = 0;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
@@ -456,6 +495,8 @@ int main(int argc, char** argv)
         }
         else if (v && !strcmp(a, "--volume-depth")) { view.depth_path = v; ++i; }
         else if (v && !strcmp(a, "--volume-normals")) { view.normals_path = v; ++i; }
+        else if (v && !strcmp(a, "--volume-image")) { view.image_path = v; ++i; }
+        else if (!strcmp(a, "--volume-color")) volume_color = 1;
         else if (v && !strcmp(a, "--volume-track")) {
             const int got = sscanf(v, "%d,%f,%f,%f,%f", &view.track_iterations, &view.track_dist_max, &view.track_t[0], &view.track_t[1],
                                    &view.track_t[2]);
@@ -524,7 +565,12 @@ int main(int argc, char** argv)
         fprintf(stderr, "--volume-track needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC and --volume-view ZMIN,ZMAX,STEP[,MINWEIGHT]\n");
         return 2;
     }
-    if (have_view != (view.depth_path || view.normals_path || have_track)) {
+    if (volume_color && !have_volume) { fprintf(stderr, "--volume-color needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n"); return 2; }
+    if (view.image_path && (!have_view || !volume_color)) {
+        fprintf(stderr, "--volume-image OUT.pgm needs --volume-view ZMIN,ZMAX,STEP[,MINWEIGHT] and --volume-color\n");
+        return 2;
+    }
+    if (have_view != (view.depth_path || view.normals_path || have_track || view.image_path)) {
         fprintf(stderr, "--volume-view ZMIN,ZMAX,STEP[,MINWEIGHT] and --volume-depth / --volume-normals OUT.f32 come together\n");
         return 2;
     }
@@ -659,15 +705,18 @@ int main(int argc, char** argv)
     if (volume_path) {
         sgm_point* pts = NULL;
         size_t n = 0;
-        if (volume_surface(&volume, have_view ? &view : NULL, mesh_path, device, w1, h1, pinhole, cloud_z_max, disp, &pts, &n) != 0) {
+        uint8_t* rect = NULL;
+        const uint8_t* grey = NULL;
+        if (volume_color) grey = reference_grey(left, right, right_ref, calib_path != NULL, bits, (size_t)w1 * h1, &rect);
+        if ((volume_color && !grey) ||
+            volume_surface(&volume, have_view ? &view : NULL, mesh_path, grey, device, w1, h1, pinhole, cloud_z_max, disp, &pts, &n) != 0) {
             printf("volume unavailable or --volume / --volume-view / --volume-mesh / --pinhole / --cloud-z-max out of range\n");
             rc = -1;
         } else {
-            uint8_t* rect = NULL;
-            const uint8_t* grey = reference_grey(left, right, right_ref, calib_path != NULL, bits, (size_t)w1 * h1, &rect);
+            if (!grey) grey = reference_grey(left, right, right_ref, calib_path != NULL, bits, (size_t)w1 * h1, &rect);
             if (!grey || write_ply(volume_path, pts, n, grey, w1) != 0) rc = -1;
-            free(rect);
         }
+        free(rect);
         free(pts);
     }
     SGM_Shutdown();

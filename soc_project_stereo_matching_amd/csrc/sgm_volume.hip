@@ -19,6 +19,10 @@
 //               decides a place: the list is sorted by id and the same on every run.
 // Ray-cast      the volume rendered into depth and normal maps of a view (sgm_raycast_spec; tests/raycast_ref.py): one lane per
 //               pixel, one launch for all frames; see the block further down.
+// Colour        a second array of words beside the volume's, (cw << 24) | (b << 16) | (g << 8) | r (include/sgm_mi355x.h, the
+//               colour section; tests/color_ref.py): the COLOR instantiations of the integration and of the ray-cast carry it along
+//               -- the lane that owns a voxel owns its colour word, a hit reads eight more words -- and sgm_volume_colors_k gives a
+//               colour to every record of a surface list or of a mesh's vertex list, one lane per record.
 //
 // (this translation unit is compiled with -fno-honor-nans like the others: "finite" is tested on the bit pattern, before any
 // comparison)
@@ -31,11 +35,23 @@ struct VolumeSource { float wf, hf; unsigned frames; };
 
 // ---- integration ---------------------------------------------------------------------------------------------------------------
 
+// the image of the coloured integration: u8 grey (channels 1) or u32 r | g << 8 | b << 16 (channels 4), registered to the map
+struct VolumeImage { const void* pixels; unsigned channels; };
+
+// c = (c*cw + p) / (cw + 1) rounded, halves up: every operand is below 2^17
+static __device__ __forceinline__ unsigned color_average(unsigned c, unsigned cw, unsigned p)
+{
+    return (2u * (c * cw + p) + (cw + 1u)) / (2u * (cw + 1u));
+}
+
 // One frame's say on one voxel whose centre is (px, py, pz); true when the voxel was updated.  The parentheses are the contract's.
+// COLOR: col is the voxel's colour word, which takes the source pixel's colour where the update has sdf <= trunc (coloured: it did).
+template <bool COLOR>
 static __device__ __forceinline__ bool volume_update(const VolumeParams& v, const CloudParams& c, const VolumeSource& s,
                                                      const float* P, size_t frame_base, const float* __restrict__ disp,
                                                      const uint8_t* __restrict__ mask, const uint16_t* __restrict__ conf, float px,
-                                                     float py, float pz, int& tq, unsigned& w)
+                                                     float py, float pz, int& tq, unsigned& w, const VolumeImage& image, unsigned& col,
+                                                     bool& coloured)
 {
     float Xp, Yp, Zp, uf, vf;
     pose_move(P, P + 9, px, py, pz, Xp, Yp, Zp);
@@ -52,24 +68,47 @@ static __device__ __forceinline__ bool volume_update(const VolumeParams& v, cons
     if (rem < 0) { rem += den; --quot; }
     tq = quot + (2 * rem >= den ? 1 : 0);
     w = min(w + 1u, v.max_weight);
+    if constexpr (COLOR) {
+        if (sdf <= v.trunc) {                                     // far in front of the surface: distance, no colour
+            unsigned p;
+            if (image.channels == 4u) {
+                p = static_cast<const unsigned*>(image.pixels)[at] & 0xFFFFFFu;
+            } else {
+                p = static_cast<const uint8_t*>(image.pixels)[at];
+                p |= (p << 8) | (p << 16);
+            }
+            const unsigned cw = col >> 24;
+            const unsigned r = color_average(col & 0xFFu, cw, p & 0xFFu), g = color_average((col >> 8) & 0xFFu, cw, (p >> 8) & 0xFFu),
+                           b = color_average((col >> 16) & 0xFFu, cw, p >> 16);
+            col = (min(cw + 1u, min(v.max_weight, 255u)) << 24) | (b << 16) | (g << 8) | r;
+            coloured = true;
+        }
+    }
     return true;
 }
 
-template <int V>
+template <int V, bool COLOR>
 __global__ __launch_bounds__(VOL_THREADS) void sgm_volume_integrate_k(VolumeParams v, CloudParams c, VolumeSource s, PoseBlock poses,
                                                                       const float* __restrict__ disp, const uint8_t* __restrict__ mask,
-                                                                      const uint16_t* __restrict__ conf, unsigned* __restrict__ voxels)
+                                                                      const uint16_t* __restrict__ conf, unsigned* __restrict__ voxels,
+                                                                      VolumeImage image, unsigned* __restrict__ colors)
 {
     const unsigned g = (blockIdx.x * VOL_THREADS + threadIdx.x) * V;             // V == 4: nx % 4 == 0, the four share a row
     if (g >= v.n) return;
     unsigned i, j, k;
     volume_ijk(v, g, i, j, k);
-    unsigned word[V];
+    unsigned word[V], col[V];
     if constexpr (V == 4) {
         const uint4 t = *reinterpret_cast<const uint4*>(voxels + g);
         word[0] = t.x; word[1] = t.y; word[2] = t.z; word[3] = t.w;
     } else {
         word[0] = voxels[g];
+    }
+    if constexpr (COLOR && V == 4) {
+        const uint4 t = *reinterpret_cast<const uint4*>(colors + g);
+        col[0] = t.x; col[1] = t.y; col[2] = t.z; col[3] = t.w;
+    } else if constexpr (COLOR) {
+        col[0] = colors[g];
     }
     int tq[V];
     unsigned w[V];
@@ -81,12 +120,13 @@ __global__ __launch_bounds__(VOL_THREADS) void sgm_volume_integrate_k(VolumePara
         px[e] = volume_centre(v.ox, i + e, v.voxel);
     }
     const float py = volume_centre(v.oy, j, v.voxel), pz = volume_centre(v.oz, k, v.voxel);
-    bool touched = false;
+    bool touched = false, coloured = false;
     for (unsigned f = 0; f < s.frames; ++f) {                                   // frames take effect in order
         const float* P = poses.p[f];
         const size_t frame_base = (size_t)f * c.npx;
 #pragma unroll
-        for (int e = 0; e < V; ++e) touched |= volume_update(v, c, s, P, frame_base, disp, mask, conf, px[e], py, pz, tq[e], w[e]);
+        for (int e = 0; e < V; ++e)
+            touched |= volume_update<COLOR>(v, c, s, P, frame_base, disp, mask, conf, px[e], py, pz, tq[e], w[e], image, col[e], coloured);
     }
     if (!touched) return;
 #pragma unroll
@@ -95,6 +135,13 @@ __global__ __launch_bounds__(VOL_THREADS) void sgm_volume_integrate_k(VolumePara
         *reinterpret_cast<uint4*>(voxels + g) = make_uint4(word[0], word[1], word[2], word[3]);
     else
         voxels[g] = word[0];
+    if constexpr (COLOR) {
+        if (!coloured) return;
+        if constexpr (V == 4)
+            *reinterpret_cast<uint4*>(colors + g) = make_uint4(col[0], col[1], col[2], col[3]);
+        else
+            colors[g] = col[0];
+    }
 }
 
 // ---- surface points ------------------------------------------------------------------------------------------------------------
@@ -279,10 +326,66 @@ static __device__ __forceinline__ void ray_box(const VolumeParams& v, const Rayc
     }
 }
 
-template <bool NORMALS>
+// ---- colour ---------------------------------------------------------------------------------------------------------------------
+// A colour word is (cw << 24) | (b << 16) | (g << 8) | r; cw == 0: the voxel has none.
+
+// the three channels of p and q blended at s, each rounded to the nearest integer (halves to even), alpha 0xFF; clamp: to 0..255
+// first (a blend of three lerps can leave the range by a rounding, one lerp with 0 <= s <= 1 cannot)
+template <bool CLAMP, typename F>
+static __device__ __forceinline__ unsigned color_pack(F channel)
+{
+    unsigned out = 0xFF000000u;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        float value = channel(8 * ch);
+        if constexpr (CLAMP) value = fminf(fmaxf(value, 0.0f), 255.0f);
+        out |= (unsigned)rintf(value) << (8 * ch);
+    }
+    return out;
+}
+
+// The colour at g: trilinear over the eight words of F(g)'s cell where all eight have a colour, else the word of the voxel g lies
+// in, else 0
+static __device__ __forceinline__ unsigned ray_color(const VolumeParams& v, const unsigned* __restrict__ colors, float gx, float gy,
+                                                     float gz)
+{
+    const float hx = gx - 0.5f, hy = gy - 0.5f, hz = gz - 0.5f;
+    if (cloud_finite(hx) && cloud_finite(hy) && cloud_finite(hz)) {
+        const float ix = floorf(hx), iy = floorf(hy), iz = floorf(hz);
+        if (0.0f <= ix && ix + 1.0f < (float)v.nx && 0.0f <= iy && iy + 1.0f < (float)v.ny && 0.0f <= iz && iz + 1.0f < (float)v.nz) {
+            const float fx = hx - ix, fy = hy - iy, fz = hz - iz;
+            const unsigned* at = colors + (((unsigned)iz * v.ny + (unsigned)iy) * v.nx + (unsigned)ix);
+            const unsigned sy = v.nx, sz = v.nx * v.ny;
+            unsigned word[8];
+            bool all = true;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                word[e] = at[(e & 1) + ((e >> 1) & 1) * sy + (e >> 2) * sz];
+                all = all && (word[e] >> 24) != 0u;
+            }
+            if (all)
+                return color_pack<true>([&](int shift) {
+                    float t[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) t[e] = (float)((word[e] >> shift) & 0xFFu);
+                    const float c00 = ray_lerp(t[0], t[1], fx), c10 = ray_lerp(t[2], t[3], fx), c01 = ray_lerp(t[4], t[5], fx),
+                                c11 = ray_lerp(t[6], t[7], fx);
+                    return ray_lerp(ray_lerp(c00, c10, fy), ray_lerp(c01, c11, fy), fz);
+                });
+        }
+    }
+    // the march's admission of a sample, in float before any conversion
+    if (!cloud_finite(gx) || !cloud_finite(gy) || !cloud_finite(gz)) return 0u;
+    if (!(0.0f <= gx && gx < (float)v.nx && 0.0f <= gy && gy < (float)v.ny && 0.0f <= gz && gz < (float)v.nz)) return 0u;
+    const unsigned word = colors[((unsigned)gz * v.ny + (unsigned)gy) * v.nx + (unsigned)gx];
+    return (word >> 24) != 0u ? (0xFF000000u | word) : 0u;
+}
+
+template <bool NORMALS, bool COLOR>
 __global__ __launch_bounds__(RAY_THREADS) void sgm_volume_raycast_k(VolumeParams v, RaycastView r, PoseBlock poses,
                                                                     const unsigned* __restrict__ voxels, float* __restrict__ depth,
-                                                                    float* __restrict__ normal)
+                                                                    float* __restrict__ normal, const unsigned* __restrict__ colors,
+                                                                    unsigned* __restrict__ rgba)
 {
     const unsigned lane = threadIdx.x & 63u;
     const unsigned x = blockIdx.x * RAY_BLOCK_W + (threadIdx.x >> 6) * 8u + (lane & 7u), y = blockIdx.y * RAY_BLOCK_H + (lane >> 3);
@@ -303,7 +406,7 @@ __global__ __launch_bounds__(RAY_THREADS) void sgm_volume_raycast_k(VolumeParams
     ray_box(v, r, go, gd, k, z_end);
     const float nan = __uint_as_float(0x7FC00000u);
     float Z = nan, nrm[3] = {nan, nan, nan};
-    unsigned prev = 0;
+    unsigned prev = 0, color = 0;                             // (color: of the COLOR instantiations; an empty pixel gets 0)
     float Zp = 0.0f;
     bool front = false;
     for (;; ++k) {
@@ -325,6 +428,7 @@ __global__ __launch_bounds__(RAY_THREADS) void sgm_volume_raycast_k(VolumeParams
             if (den > 0.0f) {
                 const float s = fminf(fmaxf(Fp / den, 0.0f), 1.0f);
                 Z = Zp + s * r.step;
+                if constexpr (COLOR) color = ray_color(v, colors, go[0] + Z * gd[0], go[1] + Z * gd[1], go[2] + Z * gd[2]);
                 if constexpr (NORMALS) {
                     const float g[3] = {go[0] + Z * gd[0], go[1] + Z * gd[1], go[2] + Z * gd[2]};
                     float nw[3];
@@ -359,6 +463,42 @@ __global__ __launch_bounds__(RAY_THREADS) void sgm_volume_raycast_k(VolumeParams
         normal[3 * at + 1] = nrm[1];
         normal[3 * at + 2] = nrm[2];
     }
+    if constexpr (COLOR) rgba[at] = color;
+}
+
+// ---- the colours of a surface list or of a mesh's vertices ----------------------------------------------------------------------
+// One lane per record; only the id, the record's last word, is read.  shift: 3 for ids n*8 + e (sgm_mesh_vertex, kinds 0..6), 2 for
+// n*4 + a (sgm_surface_point, axes 0..2).  count (may be NULL) is the list's length as the call before left it on the device, so the
+// launch can follow the list's on the stream; records at or beyond it are not written.
+__global__ __launch_bounds__(VOL_THREADS) void sgm_volume_colors_k(VolumeParams v, const unsigned* __restrict__ voxels,
+                                                                   const unsigned* __restrict__ colors, const uint4* __restrict__ records,
+                                                                   size_t capacity, const unsigned* __restrict__ count, unsigned shift,
+                                                                   unsigned* __restrict__ rgba)
+{
+    const size_t r = (size_t)blockIdx.x * VOL_THREADS + threadIdx.x;
+    if (r >= capacity || (count && r >= count[0])) return;
+    const unsigned id = records[r].w, n = id >> shift, e = id & ((1u << shift) - 1u);
+    unsigned out = 0;
+    if (n < v.n && e < (shift == 3u ? 7u : 3u)) {
+        unsigned i, j, k;
+        volume_ijk(v, n, i, j, k);
+        const unsigned c = MESH_CORNER_OF(e);
+        if (i + (c & 1u) < v.nx && j + ((c >> 1) & 1u) < v.ny && k + (c >> 2) < v.nz) {
+            const unsigned m = n + (c & 1u) + ((c >> 1) & 1u) * v.nx + (c >> 2) * (v.nx * v.ny);
+            const unsigned cn = colors[n], cm = colors[m];
+            if ((cn >> 24) != 0u && (cm >> 24) != 0u) {
+                const float tn = (float)(int)(short)(voxels[n] & 0xFFFFu), tm = (float)(int)(short)(voxels[m] & 0xFFFFu);
+                const float den = tn - tm;
+                const float s = den != 0.0f ? fminf(fmaxf(tn / den, 0.0f), 1.0f) : 0.0f;
+                out = color_pack<false>([&](int sh) { return ray_lerp((float)((cn >> sh) & 0xFFu), (float)((cm >> sh) & 0xFFu), s); });
+            } else if ((cn >> 24) != 0u) {
+                out = 0xFF000000u | cn;
+            } else if ((cm >> 24) != 0u) {
+                out = 0xFF000000u | cm;
+            }
+        }
+    }
+    rgba[r] = out;
 }
 
 extern "C" {
@@ -371,12 +511,16 @@ size_t sgmd_volume_scratch_bytes(int nx, int ny, int nz)
     return tile_scratch_bytes((n + TILE_MAX - 1) / TILE_MAX);
 }
 
-int sgmd_volume_integrate(int ord, void* stream, const sgmd_volume* v, const sgmd_cloud* c, const float* poses, const void* disp,
-                          const void* mask, const void* conf, void* voxels)
+// the integration, plain (image, colors NULL) or coloured
+static int volume_integrate(const char* entry, int ord, void* stream, const sgmd_volume* v, const sgmd_cloud* c, const float* poses,
+                            const void* disp, const void* mask, const void* conf, void* voxels, const void* image, int channels,
+                            void* colors)
 {
+    const bool color = colors != nullptr;
     if (!volume_ok(v) || !cloud_shape_ok(c) || !poses || !disp || !voxels || c->B > SGMD_MAX_POSES || (uintptr_t)voxels % 4 != 0 ||
-        (uintptr_t)disp % 4 != 0 || (uintptr_t)conf % 2 != 0) {
-        fprintf(stderr, "sgm_mi355x: sgmd_volume_integrate: bad arguments\n");
+        (uintptr_t)disp % 4 != 0 || (uintptr_t)conf % 2 != 0 ||
+        (color && (!image || (channels != 1 && channels != 4) || (uintptr_t)colors % 4 != 0 || (channels == 4 && (uintptr_t)image % 4 != 0)))) {
+        fprintf(stderr, "sgm_mi355x: %s: bad arguments\n", entry);
         return -1;
     }
     HIP_TRY(hipSetDevice(ord));
@@ -387,14 +531,38 @@ int sgmd_volume_integrate(int ord, void* stream, const sgmd_volume* v, const sgm
     s.frames = (unsigned)c->B;
     const PoseBlock pose = pose_block(poses, c->B);
     const hipStream_t st = (hipStream_t)stream;
-    if (p.nx % 4 == 0 && (uintptr_t)voxels % 16 == 0)
-        hipLaunchKernelGGL(sgm_volume_integrate_k<4>, dim3((p.n / 4 + VOL_THREADS - 1) / VOL_THREADS), dim3(VOL_THREADS), 0, st, p, q, s,
-                           pose, (const float*)disp, (const uint8_t*)mask, (const uint16_t*)conf, (unsigned*)voxels);
-    else
-        hipLaunchKernelGGL(sgm_volume_integrate_k<1>, dim3((p.n + VOL_THREADS - 1) / VOL_THREADS), dim3(VOL_THREADS), 0, st, p, q, s, pose,
-                           (const float*)disp, (const uint8_t*)mask, (const uint16_t*)conf, (unsigned*)voxels);
+    VolumeImage im;
+    im.pixels = image; im.channels = (unsigned)channels;
+    // four voxels per lane where a row is a whole number of them and every array of words can be accessed 16 bytes at a time
+    const bool four = p.nx % 4 == 0 && (uintptr_t)voxels % 16 == 0 && (uintptr_t)colors % 16 == 0;
+    const dim3 grid(((four ? p.n / 4 : p.n) + VOL_THREADS - 1) / VOL_THREADS);
+#define VOL_LAUNCH(V, COLOR)                                                                                                             \
+    hipLaunchKernelGGL((sgm_volume_integrate_k<V, COLOR>), grid, dim3(VOL_THREADS), 0, st, p, q, s, pose, (const float*)disp,            \
+                       (const uint8_t*)mask, (const uint16_t*)conf, (unsigned*)voxels, im, (unsigned*)colors)
+    if (color) {
+        if (four) VOL_LAUNCH(4, true); else VOL_LAUNCH(1, true);
+    } else {
+        if (four) VOL_LAUNCH(4, false); else VOL_LAUNCH(1, false);
+    }
+#undef VOL_LAUNCH
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int sgmd_volume_integrate(int ord, void* stream, const sgmd_volume* v, const sgmd_cloud* c, const float* poses, const void* disp,
+                          const void* mask, const void* conf, void* voxels)
+{
+    return volume_integrate("sgmd_volume_integrate", ord, stream, v, c, poses, disp, mask, conf, voxels, nullptr, 0, nullptr);
+}
+
+int sgmd_volume_integrate_color(int ord, void* stream, const sgmd_volume* v, const sgmd_cloud* c, const float* poses, const void* disp,
+                                const void* mask, const void* conf, const void* image, int channels, void* voxels, void* colors)
+{
+    if (!colors) {
+        fprintf(stderr, "sgm_mi355x: sgmd_volume_integrate_color: bad arguments\n");
+        return -1;
+    }
+    return volume_integrate("sgmd_volume_integrate_color", ord, stream, v, c, poses, disp, mask, conf, voxels, image, channels, colors);
 }
 
 int sgmd_volume_points(int ord, void* stream, const sgmd_volume* v, const void* voxels, unsigned min_weight, void* scratch, void* points,
@@ -421,13 +589,15 @@ int sgmd_volume_points(int ord, void* stream, const sgmd_volume* v, const void* 
     return 0;
 }
 
-int sgmd_volume_raycast(int ord, void* stream, const sgmd_volume* v, const sgmd_raycast* r, const float* poses, const void* voxels,
-                        void* depth, void* normal)
+// the ray-cast, plain (colors, rgba NULL) or coloured
+static int volume_raycast(const char* entry, int ord, void* stream, const sgmd_volume* v, const sgmd_raycast* r, const float* poses,
+                          const void* voxels, void* depth, void* normal, const void* colors, void* rgba)
 {
     if (!volume_ok(v) || !r || !poses || !voxels || !depth || r->W < 1 || r->H < 1 || r->W > 65535 || r->H > 65535 || r->B < 1 ||
         r->B > SGMD_MAX_POSES || (unsigned long long)r->W * r->H * r->B > (1ull << 31) || r->min_weight < 1 || r->min_weight > 65535 ||
-        (uintptr_t)voxels % 4 != 0 || (uintptr_t)depth % 4 != 0 || (uintptr_t)normal % 4 != 0) {
-        fprintf(stderr, "sgm_mi355x: sgmd_volume_raycast: bad arguments\n");
+        (uintptr_t)voxels % 4 != 0 || (uintptr_t)depth % 4 != 0 || (uintptr_t)normal % 4 != 0 || (colors == nullptr) != (rgba == nullptr) ||
+        (uintptr_t)colors % 4 != 0 || (uintptr_t)rgba % 4 != 0) {
+        fprintf(stderr, "sgm_mi355x: %s: bad arguments\n", entry);
         return -1;
     }
     HIP_TRY(hipSetDevice(ord));
@@ -439,12 +609,51 @@ int sgmd_volume_raycast(int ord, void* stream, const sgmd_volume* v, const sgmd_
     const PoseBlock pose = pose_block(poses, r->B);
     const dim3 grid((q.W + RAY_BLOCK_W - 1) / RAY_BLOCK_W, (q.H + RAY_BLOCK_H - 1) / RAY_BLOCK_H, (unsigned)r->B);
     const hipStream_t st = (hipStream_t)stream;
-    if (normal)
-        hipLaunchKernelGGL(sgm_volume_raycast_k<true>, grid, dim3(RAY_THREADS), 0, st, p, q, pose, (const unsigned*)voxels, (float*)depth,
-                           (float*)normal);
-    else
-        hipLaunchKernelGGL(sgm_volume_raycast_k<false>, grid, dim3(RAY_THREADS), 0, st, p, q, pose, (const unsigned*)voxels, (float*)depth,
-                           (float*)nullptr);
+#define RAY_LAUNCH(NORMALS, COLOR)                                                                                                       \
+    hipLaunchKernelGGL((sgm_volume_raycast_k<NORMALS, COLOR>), grid, dim3(RAY_THREADS), 0, st, p, q, pose, (const unsigned*)voxels,      \
+                       (float*)depth, (float*)normal, (const unsigned*)colors, (unsigned*)rgba)
+    if (rgba) {
+        if (normal) RAY_LAUNCH(true, true); else RAY_LAUNCH(false, true);
+    } else {
+        if (normal) RAY_LAUNCH(true, false); else RAY_LAUNCH(false, false);
+    }
+#undef RAY_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sgmd_volume_raycast(int ord, void* stream, const sgmd_volume* v, const sgmd_raycast* r, const float* poses, const void* voxels,
+                        void* depth, void* normal)
+{
+    return volume_raycast("sgmd_volume_raycast", ord, stream, v, r, poses, voxels, depth, normal, nullptr, nullptr);
+}
+
+int sgmd_volume_raycast_color(int ord, void* stream, const sgmd_volume* v, const sgmd_raycast* r, const float* poses, const void* voxels,
+                              const void* colors, void* depth, void* normal, void* rgba)
+{
+    if (!colors || !rgba) {
+        fprintf(stderr, "sgm_mi355x: sgmd_volume_raycast_color: bad arguments\n");
+        return -1;
+    }
+    return volume_raycast("sgmd_volume_raycast_color", ord, stream, v, r, poses, voxels, depth, normal, colors, rgba);
+}
+
+int sgmd_volume_colors(int ord, void* stream, const sgmd_volume* v, const void* voxels, const void* colors, const void* records,
+                       size_t capacity, const void* count, int id_kinds, void* rgba)
+{
+    if (!volume_ok(v) || !voxels || !colors || (capacity && (!records || !rgba)) || (id_kinds != 4 && id_kinds != 8) ||
+        (id_kinds == 8 && (unsigned long long)v->nx * v->ny * v->nz > (1ull << 27)) || capacity > ((size_t)1 << 32) ||
+        (uintptr_t)voxels % 4 != 0 || (uintptr_t)colors % 4 != 0 || (uintptr_t)records % 16 != 0 || (uintptr_t)count % 4 != 0 ||
+        (uintptr_t)rgba % 4 != 0) {
+        fprintf(stderr, "sgm_mi355x: sgmd_volume_colors: bad arguments\n");
+        return -1;
+    }
+    if (capacity == 0) return 0;
+    HIP_TRY(hipSetDevice(ord));
+    const VolumeParams p = volume_params(v);
+    hipLaunchKernelGGL(sgm_volume_colors_k, dim3((unsigned)((capacity + VOL_THREADS - 1) / VOL_THREADS)), dim3(VOL_THREADS), 0,
+                       (hipStream_t)stream, p, (const unsigned*)voxels, (const unsigned*)colors, (const uint4*)records, capacity,
+                       (const unsigned*)count, id_kinds == 8 ? 3u : 2u, (unsigned*)rgba);
     HIP_TRY(hipGetLastError());
     return 0;
 }

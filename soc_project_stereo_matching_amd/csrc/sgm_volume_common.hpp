@@ -20,6 +20,10 @@ static __device__ __forceinline__ void volume_ijk(const VolumeParams& v, unsigne
     j = row - k * v.ny;
 }
 
+// Corner c = dx | dy << 1 | dz << 2 of the cell whose corner 0 is voxel n; the edge of kind e (the mesh contract's table, whose
+// kinds 0..2 are the axes of the surface list) runs from corner 0 to corner MESH_CORNER_OF(e)
+#define MESH_CORNER_OF(e) ((e) == 0 ? 1 : (e) == 1 ? 2 : (e) == 2 ? 4 : (e) == 3 ? 3 : (e) == 4 ? 5 : (e) == 5 ? 6 : 7)
+
 static bool volume_ok(const sgmd_volume* v)
 {
     return v && v->nx >= 1 && v->ny >= 1 && v->nz >= 1 && v->nx <= 1024 && v->ny <= 1024 && v->nz <= 1024 &&

@@ -422,6 +422,13 @@ def _load() -> C.CDLL:
     if hasattr(L, "sgm_volume_raycast"):      # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_volume_raycast.argtypes = [C.c_void_p] * 7
         L.sgm_volume_raycast.restype = C.c_bool
+    if hasattr(L, "sgm_volume_colors"):       # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_volume_integrate_color.argtypes = [C.c_void_p] * 8 + [C.c_int, C.c_void_p, C.c_void_p]
+        L.sgm_volume_integrate_color.restype = C.c_bool
+        L.sgm_volume_raycast_color.argtypes = [C.c_void_p] * 9
+        L.sgm_volume_raycast_color.restype = C.c_bool
+        L.sgm_volume_colors.argtypes = [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]
+        L.sgm_volume_colors.restype = C.c_bool
     if hasattr(L, "sgm_track_sums"):          # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_track_sums.argtypes = [C.c_void_p] * 10
         L.sgm_track_sums.restype = C.c_bool
@@ -1303,6 +1310,37 @@ class SGMInstance(_StageReader):
             raise ValueError("volume_raycast: one pose of 12 floats (R row-major, then t) per frame")
         return bool(self.lib.sgm_volume_raycast(self.handle, C.byref(vol), C.byref(view), poses.ctypes.data, d_voxels, d_depth,
                                                 d_normal or None))
+
+    # ---- colour in the TSDF volume (include/sgm_mi355x.h, the colour section); device pointers as ints, None = NULL ----
+    def volume_integrate_color(self, spec: SGMVolumeSpec, src: SGMCloudSpec, poses, d_disp, d_mask, d_conf, d_image: int, channels: int,
+                               d_voxels: int, d_colors: int) -> bool:
+        """sgm_volume_integrate_color: volume_integrate with the reference camera's image ([frames][height][width]: uint8 grey with
+        channels 1, uint32 r | g << 8 | b << 16 with channels 4) fused into the colour words at d_colors (volume_bytes(spec) bytes,
+        all zero when empty) by the same launch.  Asynchronous on `stream`."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1)
+        if poses.size != 12 * src.frames:
+            raise ValueError("volume_integrate_color: one pose of 12 floats (R row-major, then t) per frame")
+        return bool(self.lib.sgm_volume_integrate_color(self.handle, C.byref(spec), C.byref(src), poses.ctypes.data, d_disp or None,
+                                                        d_mask or None, d_conf or None, d_image or None, int(channels), d_voxels,
+                                                        d_colors or None))
+
+    def volume_raycast_color(self, vol: SGMVolumeSpec, view: SGMRaycastSpec, poses, d_voxels: int, d_colors: int, d_depth: int,
+                             d_normal, d_rgba: int) -> bool:
+        """sgm_volume_raycast_color: volume_raycast with the colour at every hit, 0xFF000000 | b << 16 | g << 8 | r, into d_rgba
+        (uint32 [frames][height][width]; 0 for an empty pixel or a hit without colour).  Asynchronous on `stream`."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1)
+        if poses.size != 12 * view.frames:
+            raise ValueError("volume_raycast_color: one pose of 12 floats (R row-major, then t) per frame")
+        return bool(self.lib.sgm_volume_raycast_color(self.handle, C.byref(vol), C.byref(view), poses.ctypes.data, d_voxels,
+                                                      d_colors or None, d_depth, d_normal or None, d_rgba or None))
+
+    def volume_colors(self, spec: SGMVolumeSpec, d_voxels: int, d_colors: int, d_records, capacity: int, d_count, id_kinds: int,
+                      d_rgba) -> bool:
+        """sgm_volume_colors: a colour (uint32 into d_rgba[r]) for each of the first `capacity` records at d_records -- the vertices
+        of volume_mesh (id_kinds 8) or the points of volume_points (id_kinds 4) -- and, with d_count (a device uint32, e.g. the
+        d_counts of volume_mesh), only for those below d_count[0].  Asynchronous on `stream`."""
+        return bool(self.lib.sgm_volume_colors(self.handle, C.byref(spec), d_voxels, d_colors or None, d_records or None, int(capacity),
+                                               d_count or None, int(id_kinds), d_rgba or None))
 
     # ---- frame-to-model tracking (include/sgm_mi355x.h, sgm_track_spec); device pointers as ints, None = NULL ----
     def track_sums(self, src: SGMCloudSpec, model: SGMTrackSpec, poses, d_disp, d_mask, d_conf, d_model_depth: int, d_model_normal: int,
