@@ -611,8 +611,9 @@ bool   sgm_register_spec_raw(const double K[9], const double dist[5], const doub
  * that aliases a map (d_points or d_count that alias the volume or each other); a build without the kernels.  The extraction
  * keeps 8 bytes of scratch per tile of 2048 voxels, reserved at its first call: an instance that never calls these entry points
  * allocates and launches exactly what it did before.  Not part of it: meshing and ray-casting the volume into a view, which are
- * entry points of their own (sgm_volume_mesh and sgm_volume_raycast below), confidence-weighted updates, colour, voxel hashing or
- * a moving volume, estimating the poses (sgm_track below does that against a ray-cast), row tiles, sgm_match_planes. */
+ * entry points of their own (sgm_volume_mesh and sgm_volume_raycast below), confidence-weighted updates, colour, voxel hashing (a
+ * volume that moves with the rig is made of windows: sgm_volume_window below), estimating the poses (sgm_track below does that
+ * against a ray-cast), row tiles, sgm_match_planes. */
 typedef struct {            /* 36 bytes, every field 4 bytes, no padding */
     int32_t  nx, ny, nz;    /* 1..1024 each, nx*ny*nz <= 2^30; voxel n = (k*ny + j)*nx + i, x fastest */
     float    voxel;         /* edge length, units of baseline; finite, > 0 */
@@ -917,6 +918,74 @@ bool sgm_volume_raycast_color(sgm_instance* s, const sgm_volume_spec* vol, const
 bool sgm_volume_colors(sgm_instance* s, const sgm_volume_spec* spec, const uint32_t* d_voxels, const uint32_t* d_colors,
                        const void* d_records /* 16-byte records, id in the last word */, size_t capacity,
                        const uint32_t* d_count /* device u32, may be NULL */, int id_kinds /* 8 or 4 */, uint32_t* d_rgba /* u32 [capacity] */);
+
+/* ---- a window of the TSDF volume: a volume that follows the rig and streams out what leaves ----
+ * Extension, "parity unpinned by the reference"; defined here and restated by tests/window_ref.py.  A volume is a dense array with a
+ * fixed origin: at 5 cm voxels the largest box is 51 m long, and a car crosses it in seconds.  Every entry point above takes the
+ * volume spec per call, so one primitive makes the volume move: copy a box of the voxel lattice into another volume array at an
+ * integer voxel offset, zero-filling what was never observed.  Shifting the volume so that the rig stays centred is one call, what
+ * is about to fall off the edge is handed out as a small volume of its own by one call per slab, and the same call grows, crops or
+ * re-allocates a volume without losing it.  Tolerance 0: words are copied.
+ *
+ * sgm_volume_window.  The destination is a volume of dims[0] x dims[1] x dims[2] voxels, indexed like every volume.
+ *   copy rule   destination voxel (i, j, k), 0 <= i < dims[0], 0 <= j < dims[1], 0 <= k < dims[2], receives the source word of
+ *               (i + offset[0], j + offset[1], k + offset[2]) if that lies inside the source grid, otherwise 0, the empty voxel
+ *   colours     with d_src_colors and d_dst_colors (both or neither) the colour words travel the same way in the same launch
+ *   writes      every destination word is written exactly once; nothing else is written; the source is only read
+ *   the spec    voxel, trunc and max_weight are the source's;  nx, ny, nz = dims;
+ *               origin_a = src.origin_a + (float)offset_a * src.voxel        (float32: the product, then the sum, each rounded once)
+ *               It is written to *dst_out (HOST, may be NULL) and is what sgm_volume_window_spec (host only) gives.
+ * The consequence of the origin's rule: if voxel is a power of two and the origin a multiple of it (and the numbers stay within
+ * float32's 24 bits), every origin made this way is exact, the voxel centres of source and window are the same floats, and whatever
+ * is computed in the window -- an integration, a mesh, a ray-cast -- is word for word what it would have been in the source.
+ * Otherwise the centres agree to rounding, and results computed in the window may differ from the source's in isolated words.
+ * One launch, no scratch, no atomics: the same bytes on every run.  Four voxels per lane and 16-byte stores where dims[0] % 4 == 0
+ * and the destination arrays can be accessed 16 bytes at a time, 16-byte loads where src->nx % 4 == 0, offset[0] % 4 == 0 and
+ * the source arrays allow it; else element by element, with the same bytes.  Asynchronous on sgm_stream(s), behind the last match
+ * also with sgm_set_overlap_post, as sgm_volume_points.  false, nothing queued and one "sgm_mi355x: sgm_volume_window: ..." line
+ * on stderr: a NULL s, src, offset, dims, d_src_voxels or d_dst_voxels; exactly one of the two colour arrays NULL; a source spec
+ * that sgm_volume_integrate refuses; dims that do not make a spec it accepts (1..1024 each, product <= 2^30); |offset_a| > 2^20; a
+ * resulting origin that is not finite; a pointer that is not 4-byte aligned; a destination array that overlaps any other of the
+ * four arrays (so there is no in-place call: keep two arrays and alternate); a build without the kernel.  An instance that never
+ * calls it allocates and launches exactly what it did before.
+ *
+ * sgm_volume_follow (host only): the shift, in voxels, that brings the rig back to the middle of the volume.  In double, every
+ * operation on its own, sums left to right; pose is world -> camera (R row-major, then t):
+ *   the point to keep centred is (0, 0, focus_z) in camera coordinates: the camera centre for 0, or the middle of the viewed depths
+ *   P_i     = (R[0][i]*(0 - t0) + R[1][i]*(0 - t1)) + R[2][i]*(focus_z - t2)                  (the point in the world)
+ *   g_a     = (P_a - origin_a) / voxel - n_a / 2                                              (n_a / 2 in double: 16.5 for 33)
+ *   shift_a = 0 if |g_a| <= margin, else granule * floor(g_a / granule + 0.5)
+ * false and a line on stderr: a NULL argument, a spec outside the volume's ranges, granule < 1, margin < 0, a pose entry or focus_z
+ * that is not finite, |g_a| >= 2^20, a shift that rounds to more than 2^20.  A granule that is a multiple of 4 keeps offset[0], and
+ * with nx % 4 == 0 the whole shift, on the window's 16-byte load path.
+ *
+ * sgm_volume_leaving (host only): the parts of the volume that the shift drops, as at most three boxes to hand to sgm_volume_window.
+ * Per axis a, with c = n_a - 1 the cells on that axis (a cell is the cube between eight neighbouring voxels) and s = shift_a:
+ *   s > 0:  the cells [0, min(s, c)) leave and [min(s, c), c) stay
+ *   s < 0:  the cells [max(c + s, 0), c) leave and [0, max(c + s, 0)) stay
+ *   s = 0:  none leave and [0, c) stay
+ * Box a is the stay range on the axes before a, the leave range on a, and all cells on the axes after; it exists iff all three
+ * ranges are non-empty.  It is reported in voxels: lo holds the range starts and n the lengths + 1, so that its last cells are
+ * whole.  The boxes come in axis order, absent ones skipped; the return value is their number, 0..3, or -1 (and a line on stderr)
+ * for a NULL argument or a refused spec.  The boxes are disjoint in cells, and together with the stay ranges they cover every cell
+ * of the volume exactly once: the meshes of what leaves and of what stays tile the mesh of the whole, without gaps or duplicates.
+ *
+ * The caller's loop, with two arrays A and B of sgm_volume_bytes(spec) (and two of colours) that alternate:
+ *   1. sgm_volume_follow(spec, pose, focus_z, granule, margin, shift);  all zero: nothing to do
+ *   2. for each box of sgm_volume_leaving(spec, shift, boxes): sgm_volume_window(s, spec, box.lo, box.n, A, ..., small, ..., &part)
+ *   3. sgm_volume_mesh / sgm_volume_colors (or sgm_volume_points) on each small array under its spec `part`: the streamed surface
+ *   4. sgm_volume_window(s, spec, shift, (nx, ny, nz), A, ..., B, ..., &spec);  swap A and B;  integrate the next frames into A
+ * Not part of it: ring-buffer addressing inside the kernels above, shifting in place, voxel hashing, welding the seams between
+ * streamed meshes (vertices on a shared face appear in both parts, with equal positions), loop closure. */
+typedef struct { int32_t lo[3]; int32_t n[3]; } sgm_volume_box;      /* voxels: a box of n cells-plus-one starting at lo; 24 bytes */
+bool sgm_volume_window(sgm_instance* s, const sgm_volume_spec* src, const int32_t offset[3], const int32_t dims[3],
+                       const uint32_t* d_src_voxels, const uint32_t* d_src_colors /* or NULL */,
+                       uint32_t* d_dst_voxels, uint32_t* d_dst_colors /* NULL iff d_src_colors is */,
+                       sgm_volume_spec* dst_out /* HOST, may be NULL */);
+bool sgm_volume_window_spec(const sgm_volume_spec* src, const int32_t offset[3], const int32_t dims[3], sgm_volume_spec* dst); /* host only */
+bool sgm_volume_follow(const sgm_volume_spec* spec, const float pose[12] /* world -> camera */, float focus_z,
+                       int32_t granule /* >= 1 */, int32_t margin /* >= 0, voxels */, int32_t shift[3]);
+int  sgm_volume_leaving(const sgm_volume_spec* spec, const int32_t shift[3], sgm_volume_box boxes[3]);   /* 0..3, -1 refused */
 
 /* ---- matching at half or quarter scale, re-search at full resolution ----
  * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/scaled_ref.py.  A match at

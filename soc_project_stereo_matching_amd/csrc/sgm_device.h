@@ -347,7 +347,15 @@ int sgmd_volume_raycast_color(int ord, void* stream, const sgmd_volume* v, const
 int sgmd_volume_colors(int ord, void* stream, const sgmd_volume* v, const void* voxels, const void* colors, const void* records,
                        size_t capacity, const void* count, int id_kinds, void* rgba);
 
-/* The volume as a triangle mesh, marching tetrahedra (include/sgm_mi355x.h, sgm_volume_mesh); sgm_mesh.hip.  v: the volume as the
+/* A window of the volume (include/sgm_mi355x.h, the moving-volume section); sgm_window.hip.  One launch, no scratch: destination
+ * voxel (i, j, k) of the dims[0] x dims[1] x dims[2] grid receives the source word of (i + offset[0], j + offset[1], k + offset[2])
+ * where that lies inside src's grid, else 0; the colour words alike where src_colors / dst_colors are given (both or neither).
+ * src: the source volume as the host validated it; dims 1..1024 each and at most 2^30 voxels, |offset| <= 2^20; the arrays 4-byte
+ * aligned and, the destination's against all others, disjoint.  sgm_host.c references it weakly, on its own. */
+int sgmd_volume_window(int ord, void* stream, const sgmd_volume* src, const int* offset, const int* dims, const void* src_voxels,
+                       const void* src_colors, void* dst_voxels, void* dst_colors);
+
+/* The volume as a triangle mesh, marching tetrahedra (include/sgm_mi355x.h, sgm_volume_mesh); sgm_mesh.hip. v: the volume as the
  * host validated it, at most 2^27 voxels.  Four launches (count per tile, one scan, the vertices, the triangles; the last two only
  * where their capacity is not 0) that use scratch, sgmd_mesh_scratch_bytes(nx, ny, nz) bytes -- two sets of tile words -- which
  * must not be shared with a call still in flight.  vertices, triangles: 16-byte records, those at index >= their capacity not

@@ -2563,6 +2563,131 @@ bool sgm_volume_colors(sgm_instance* s, const sgm_volume_spec* spec, const uint3
     return sgmd_volume_colors(s->device, s->stream, &v, d_voxels, d_colors, d_records, capacity, d_count, id_kinds, d_rgba) == 0;
 }
 
+/* ------------------------------------------------------------------ a window of the volume, and a volume that follows the rig (extension) */
+
+/* The launcher of sgm_window.hip, a weak symbol of its own: a host built without it keeps the volume and refuses the window */
+#pragma weak sgmd_volume_window
+
+#define WINDOW_MAX_OFFSET (1 << 20)
+
+/* The spec of a window, dims[] voxels of src's lattice from offset[] on: NULL and *v, *dst filled, or what is wrong with it */
+static const char* window_spec_invalid(const sgm_volume_spec* src, const int32_t offset[3], const int32_t dims[3], sgmd_volume* v,
+                                       sgm_volume_spec* dst)
+{
+    if (!volume_spec_valid(src, v)) return "the source spec is outside the volume's ranges";
+    *dst = *src;
+    dst->nx = dims[0]; dst->ny = dims[1]; dst->nz = dims[2];
+    for (int a = 0; a < 3; ++a) {
+        if (offset[a] < -WINDOW_MAX_OFFSET || offset[a] > WINDOW_MAX_OFFSET) return "an offset beyond 2^20 voxels";
+        const float step = (float)offset[a] * src->voxel;     /* float32: the product, then the sum, each rounded once */
+        dst->origin[a] = src->origin[a] + step;
+    }
+    sgmd_volume w;
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || dims[0] > 1024 || dims[1] > 1024 || dims[2] > 1024 ||
+        (long long)dims[0] * dims[1] * dims[2] > (1LL << 30))
+        return "dims outside the volume's ranges (1..1024 each, at most 2^30 voxels)";
+    if (!volume_spec_valid(dst, &w)) return "the window's origin is not finite";
+    return NULL;
+}
+
+bool sgm_volume_window_spec(const sgm_volume_spec* src, const int32_t offset[3], const int32_t dims[3], sgm_volume_spec* dst)
+{
+    sgmd_volume v;
+    sgm_volume_spec out;
+    if (!src || !offset || !dims || !dst) FAIL("sgm_volume_window_spec: NULL argument");
+    const char* why = window_spec_invalid(src, offset, dims, &v, &out);
+    if (why) FAIL("sgm_volume_window_spec: %s", why);
+    *dst = out;
+    return true;
+}
+
+bool sgm_volume_window(sgm_instance* s, const sgm_volume_spec* src, const int32_t offset[3], const int32_t dims[3],
+                       const uint32_t* d_src_voxels, const uint32_t* d_src_colors, uint32_t* d_dst_voxels, uint32_t* d_dst_colors,
+                       sgm_volume_spec* dst_out)
+{
+    sgmd_volume v;
+    sgm_volume_spec dst;
+    if (!s || !src || !offset || !dims || !d_src_voxels || !d_dst_voxels) FAIL("sgm_volume_window: NULL argument");
+    if ((d_src_colors == NULL) != (d_dst_colors == NULL)) FAIL("sgm_volume_window: one colour array without the other");
+    if (sgmd_volume_window == NULL) FAIL("sgm_volume_window: the window is not part of this build");
+    const char* why = window_spec_invalid(src, offset, dims, &v, &dst);
+    if (why) FAIL("sgm_volume_window: %s", why);
+    if (!aligned_to(d_src_voxels, sizeof(uint32_t)) || !aligned_to(d_src_colors, sizeof(uint32_t)) ||
+        !aligned_to(d_dst_voxels, sizeof(uint32_t)) || !aligned_to(d_dst_colors, sizeof(uint32_t)))
+        FAIL("sgm_volume_window: a pointer is not aligned to its element");
+    const size_t src_bytes = volume_bytes(&v), dst_bytes = (size_t)dims[0] * dims[1] * dims[2] * sizeof(uint32_t);
+    if (ranges_overlap(d_dst_voxels, dst_bytes, d_src_voxels, src_bytes) || ranges_overlap(d_dst_voxels, dst_bytes, d_src_colors, src_bytes) ||
+        ranges_overlap(d_dst_colors, dst_bytes, d_src_voxels, src_bytes) || ranges_overlap(d_dst_colors, dst_bytes, d_src_colors, src_bytes) ||
+        ranges_overlap(d_dst_voxels, dst_bytes, d_dst_colors, dst_bytes))
+        FAIL("sgm_volume_window: a destination array overlaps another array (the window is not made in place)");
+    /* the source may be the work of an integration that read a match's result: the same place in the queue as sgm_volume_points */
+    if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
+    if (sgmd_volume_window(s->device, s->stream, &v, offset, dims, d_src_voxels, d_src_colors, d_dst_voxels, d_dst_colors) != 0) return false;
+    if (dst_out) *dst_out = dst;
+    return true;
+}
+
+bool sgm_volume_follow(const sgm_volume_spec* spec, const float pose[12], float focus_z, int32_t granule, int32_t margin, int32_t shift[3])
+{
+    sgmd_volume v;
+    int32_t out[3];
+    if (!spec || !pose || !shift) FAIL("sgm_volume_follow: NULL argument");
+    if (!volume_spec_valid(spec, &v)) FAIL("sgm_volume_follow: the volume spec is outside its ranges");
+    if (granule < 1 || margin < 0) FAIL("sgm_volume_follow: a granule of %d (>= 1) or a margin of %d (>= 0)", granule, margin);
+    for (int i = 0; i < 12; ++i)
+        if (!isfinite(pose[i])) FAIL("sgm_volume_follow: entry %d of the pose is not finite", i);
+    if (!isfinite(focus_z)) FAIL("sgm_volume_follow: focus_z is not finite");
+    /* in double, every operation on its own (-ffp-contract=off), sums left to right */
+    const double c[3] = {0.0 - (double)pose[9], 0.0 - (double)pose[10], (double)focus_z - (double)pose[11]};
+    const int n[3] = {v.nx, v.ny, v.nz};
+    for (int a = 0; a < 3; ++a) {
+        const double P = ((double)pose[a] * c[0] + (double)pose[3 + a] * c[1]) + (double)pose[6 + a] * c[2];
+        const double g = (P - (double)spec->origin[a]) / (double)spec->voxel - (double)n[a] / 2.0;
+        if (!(fabs(g) < (double)WINDOW_MAX_OFFSET)) FAIL("sgm_volume_follow: the focus is 2^20 voxels or more from the volume's centre");
+        const double sh = fabs(g) <= (double)margin ? 0.0 : (double)granule * floor(g / (double)granule + 0.5);
+        if (fabs(sh) > (double)WINDOW_MAX_OFFSET) FAIL("sgm_volume_follow: the shift rounds to more than 2^20 voxels");
+        out[a] = (int32_t)sh;
+    }
+    memcpy(shift, out, sizeof out);
+    return true;
+}
+
+int sgm_volume_leaving(const sgm_volume_spec* spec, const int32_t shift[3], sgm_volume_box boxes[3])
+{
+    sgmd_volume v;
+    if (!spec || !shift || !boxes || !volume_spec_valid(spec, &v)) {
+        fprintf(stderr, "sgm_mi355x: sgm_volume_leaving: %s\n", (!spec || !shift || !boxes) ? "NULL argument" : "the volume spec is outside its ranges");
+        return -1;
+    }
+    const int n[3] = {v.nx, v.ny, v.nz};
+    int32_t leave[3][2], stay[3][2];                          /* [begin, end) in cells */
+    for (int a = 0; a < 3; ++a) {
+        const int64_t c = n[a] - 1, sh = shift[a];
+        const int64_t cut = sh > 0 ? (sh < c ? sh : c) : (c + sh > 0 ? c + sh : 0);
+        if (sh > 0) {
+            leave[a][0] = 0; leave[a][1] = (int32_t)cut; stay[a][0] = (int32_t)cut; stay[a][1] = (int32_t)c;
+        } else if (sh < 0) {
+            leave[a][0] = (int32_t)cut; leave[a][1] = (int32_t)c; stay[a][0] = 0; stay[a][1] = (int32_t)cut;
+        } else {
+            leave[a][0] = leave[a][1] = 0; stay[a][0] = 0; stay[a][1] = (int32_t)c;
+        }
+    }
+    int count = 0;
+    for (int a = 0; a < 3; ++a) {
+        sgm_volume_box b;
+        bool whole = true;
+        for (int i = 0; i < 3; ++i) {
+            const int32_t lo = i < a ? stay[i][0] : i == a ? leave[i][0] : 0;
+            const int32_t hi = i < a ? stay[i][1] : i == a ? leave[i][1] : n[i] - 1;
+            b.lo[i] = lo;
+            b.n[i] = hi - lo + 1;                             /* voxels: the cells and one more, so that the last cells are whole */
+            whole = whole && hi > lo;
+        }
+        if (whole) boxes[count++] = b;
+    }
+    return count;
+}
+
 /* ------------------------------------------------------------------ frame-to-model tracking (extension) */
 
 /* The launcher of sgm_track.hip, a weak symbol of its own: a host built without it keeps the volume and the ray-cast */

@@ -50,6 +50,9 @@
  *                             (sgm_volume_colors), and --volume-image, with --volume-view, writes the red channel of the coloured
  *                             ray-cast (sgm_volume_raycast_color) as a PGM, 0 where no surface is met.  Without it every output
  *                             file is what it was
+ *            [--volume-window OX,OY,OZ,NX,NY,NZ]   extension: with --volume, after the frame is fused (and coloured) the volume is
+ *                             replaced by the window of NX x NY x NZ voxels that starts OX,OY,OZ voxels into it (sgm_volume_window:
+ *                             zero where the volume has nothing, the origin moved along); every --volume-* output is the window's
  *            [--volume-track ITER,DISTMAX[,TX,TY,TZ]]   extension: with --volume and --volume-view, the frame tracked against that
  *                             render (sgm_track: ITER rounds, gate DISTMAX, span the middle of the march (ZMIN + ZMAX) / 2, at least
  *                             6 pixels, pivots above 1e-6) from the identity displaced by the translation TX,TY,TZ (default 0,0,0);
@@ -312,13 +315,16 @@ static int volume_mesh_ply(sgm_instance* s, const sgm_volume_spec* vol, const ui
  * pixel is the one the point projects to (clamped to the image), for write_ply; with view != NULL the volume rendered as well, with
  * mesh_path != NULL its mesh written there.  grey != NULL (--volume-color): the frame fused with that image, its own grey, into a
  * colour volume beside the TSDF words (sgm_volume_integrate_color, channels 1), which the render and the mesh then take.
+ * window != NULL (--volume-window: offset, then dims): after the frame is fused the volume is replaced by that window of itself
+ * (sgm_volume_window into a second allocation; the first is freed), and everything that is written is the window's.
  * Page-locked buffers of an instance of its own, as above.  *out: malloc'ed, *n records. */
-static int volume_surface(const sgm_volume_spec* vol, const volume_view* view, const char* mesh_path, const uint8_t* grey, int device, int w, int h,
-                          const float* pinhole, float z_max, const float* disp, sgm_point** out, size_t* n)
+static int volume_surface(const sgm_volume_spec* vol, const int32_t* window, const volume_view* view, const char* mesh_path, const uint8_t* grey,
+                          int device, int w, int h, const float* pinhole, float z_max, const float* disp, sgm_point** out, size_t* n)
 {
     const sgm_cloud_spec src = {w, h, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], pinhole[4], pinhole[5], 0.0f, z_max, 0};
     static const float identity[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-    const size_t bytes = sgm_volume_bytes(vol);
+    size_t bytes = sgm_volume_bytes(vol);
+    sgm_volume_spec windowed;
     if (!bytes) return -1;
     if (device < 0) {
         const char* e = getenv("SGM_DEVICE");
@@ -343,9 +349,30 @@ static int volume_surface(const sgm_volume_spec* vol, const volume_view* view, c
             memcpy(d_image, grey, px);
             memset(d_colors, 0, bytes);                           /* no colour anywhere */
         }
-        if ((grey ? sgm_volume_integrate_color(s, vol, &src, identity, d_disp, NULL, NULL, d_image, 1, d_voxels, d_colors)
-                  : sgm_volume_integrate(s, vol, &src, identity, d_disp, NULL, NULL, d_voxels)) &&
-            sgm_volume_points(s, vol, d_voxels, 1, NULL, 0, d_count) && sgm_synchronize(s)) {
+        bool fused = grey ? sgm_volume_integrate_color(s, vol, &src, identity, d_disp, NULL, NULL, d_image, 1, d_voxels, d_colors)
+                          : sgm_volume_integrate(s, vol, &src, identity, d_disp, NULL, NULL, d_voxels);
+        if (fused && window) {                                    /* the volume becomes the window: a second allocation, the first freed */
+            fused = sgm_volume_window_spec(vol, window, window + 3, &windowed);
+            const size_t win_bytes = fused ? sgm_volume_bytes(&windowed) : 0;
+            uint32_t* d_win = win_bytes ? (uint32_t*)sgm_host_alloc(s, win_bytes) : NULL;
+            uint32_t* d_win_colors = (win_bytes && grey) ? (uint32_t*)sgm_host_alloc(s, win_bytes) : NULL;
+            fused = fused && d_win && (d_win_colors || !grey) &&
+                    sgm_volume_window(s, vol, window, window + 3, d_voxels, d_colors, d_win, d_win_colors, NULL) && sgm_synchronize(s);
+            if (fused) {
+                sgm_host_free(s, d_voxels);
+                sgm_host_free(s, d_colors);
+                d_voxels = d_win;
+                d_colors = d_win_colors;
+                vol = &windowed;
+                bytes = win_bytes;
+                printf("volume window: %d x %d x %d voxels from (%d, %d, %d), origin (%.9g, %.9g, %.9g)\n", windowed.nx, windowed.ny, windowed.nz,
+                       window[0], window[1], window[2], windowed.origin[0], windowed.origin[1], windowed.origin[2]);
+            } else {
+                sgm_host_free(s, d_win);
+                sgm_host_free(s, d_win_colors);
+            }
+        }
+        if (fused && sgm_volume_points(s, vol, d_voxels, 1, NULL, 0, d_count) && sgm_synchronize(s)) {
             const size_t count = *d_count;
             size_t seen = 0;
             for (size_t i = 0; i < bytes / sizeof(uint32_t); ++i) seen += (d_voxels[i] >> 16) != 0;
@@ -439,6 +466,8 @@ int main(int argc, char** argv)
     int have_volume = 0;
     volume_view view = {0.0f, 0.0f, 0.0f, 1, NULL, NULL, 0, 0.0f, {0.0f, 0.0f, 0.0f}, NULL};
     int have_track = 0, volume_color = 0;
+    int32_t volume_window[6] = {0, 0, 0, 0, 0, 0};
+    int have_window = 0;
     int have_view = 0;
     int register_splat = 2, register_splat_set = 0;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
@@ -497,6 +526,15 @@ int main(int argc, char** argv)
         else if (v && !strcmp(a, "--volume-normals")) { view.normals_path = v; ++i; }
         else if (v && !strcmp(a, "--volume-image")) { view.image_path = v; ++i; }
         else if (!strcmp(a, "--volume-color")) volume_color = 1;
+        else if (v && !strcmp(a, "--volume-window")) {
+            if (sscanf(v, "%d,%d,%d,%d,%d,%d", &volume_window[0], &volume_window[1], &volume_window[2], &volume_window[3], &volume_window[4],
+                       &volume_window[5]) != 6) {
+                fprintf(stderr, "--volume-window wants OX,OY,OZ,NX,NY,NZ\n");
+                return 2;
+            }
+            have_window = 1;
+            ++i;
+        }
         else if (v && !strcmp(a, "--volume-track")) {
             const int got = sscanf(v, "%d,%f,%f,%f,%f", &view.track_iterations, &view.track_dist_max, &view.track_t[0], &view.track_t[1],
                                    &view.track_t[2]);
@@ -566,6 +604,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (volume_color && !have_volume) { fprintf(stderr, "--volume-color needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n"); return 2; }
+    if (have_window && !have_volume) { fprintf(stderr, "--volume-window needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n"); return 2; }
     if (view.image_path && (!have_view || !volume_color)) {
         fprintf(stderr, "--volume-image OUT.pgm needs --volume-view ZMIN,ZMAX,STEP[,MINWEIGHT] and --volume-color\n");
         return 2;
@@ -709,8 +748,9 @@ int main(int argc, char** argv)
         const uint8_t* grey = NULL;
         if (volume_color) grey = reference_grey(left, right, right_ref, calib_path != NULL, bits, (size_t)w1 * h1, &rect);
         if ((volume_color && !grey) ||
-            volume_surface(&volume, have_view ? &view : NULL, mesh_path, grey, device, w1, h1, pinhole, cloud_z_max, disp, &pts, &n) != 0) {
-            printf("volume unavailable or --volume / --volume-view / --volume-mesh / --pinhole / --cloud-z-max out of range\n");
+            volume_surface(&volume, have_window ? volume_window : NULL, have_view ? &view : NULL, mesh_path, grey, device, w1, h1, pinhole,
+                           cloud_z_max, disp, &pts, &n) != 0) {
+            printf("volume unavailable or --volume / --volume-window / --volume-view / --volume-mesh / --pinhole / --cloud-z-max out of range\n");
             rc = -1;
         } else {
             if (!grey) grey = reference_grey(left, right, right_ref, calib_path != NULL, bits, (size_t)w1 * h1, &rect);

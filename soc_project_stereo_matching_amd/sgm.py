@@ -152,6 +152,46 @@ def volume_bytes(spec: SGMVolumeSpec) -> int:
     return int(load_library().sgm_volume_bytes(C.byref(spec)))
 
 
+class SGMVolumeBox(C.Structure):
+    """Field-for-field sgm_volume_box of include/sgm_mi355x.h: a box of n voxels (its cells and one more) starting at lo; 24 bytes."""
+    _fields_ = [("lo", C.c_int32 * 3), ("n", C.c_int32 * 3)]
+
+
+def _int3(values, what):
+    values = [int(x) for x in values]
+    if len(values) != 3:
+        raise ValueError(what + ": three integers")
+    return (C.c_int32 * 3)(*values)
+
+
+def volume_window_spec(src: SGMVolumeSpec, offset, dims):
+    """sgm_volume_window_spec (host only): the spec of the window of `dims` voxels that starts `offset` voxels into `src`; None
+    where sgm_volume_window would refuse the three."""
+    dst = SGMVolumeSpec()
+    ok = load_library().sgm_volume_window_spec(C.byref(src), _int3(offset, "volume_window_spec"), _int3(dims, "volume_window_spec"), C.byref(dst))
+    return dst if ok else None
+
+
+def volume_follow(spec: SGMVolumeSpec, pose, focus_z=0.0, granule=4, margin=0):
+    """sgm_volume_follow (host only): the shift (sx, sy, sz) in voxels, a multiple of `granule` per axis, that brings the point
+    (0, 0, focus_z) of the camera with the world -> camera `pose` back to the middle of the volume; 0 on an axis where it is within
+    `margin` voxels of the middle.  None where the call refuses."""
+    pose = np.ascontiguousarray(pose, np.float32).reshape(-1)
+    if pose.size != 12:
+        raise ValueError("volume_follow: one pose of 12 floats (R row-major, then t)")
+    shift = (C.c_int32 * 3)()
+    ok = load_library().sgm_volume_follow(C.byref(spec), pose.ctypes.data, float(focus_z), int(granule), int(margin), shift)
+    return tuple(shift) if ok else None
+
+
+def volume_leaving(spec: SGMVolumeSpec, shift):
+    """sgm_volume_leaving (host only): the boxes [(lo, n), ...] of voxels, at most three, that `shift` drops from the volume, each
+    to be handed to volume_window as (offset, dims); None where the call refuses."""
+    boxes = (SGMVolumeBox * 3)()
+    count = load_library().sgm_volume_leaving(C.byref(spec), _int3(shift, "volume_leaving"), boxes)
+    return None if count < 0 else [(tuple(b.lo), tuple(b.n)) for b in boxes[:count]]
+
+
 class SGMRaycastSpec(C.Structure):
     """Field-for-field sgm_raycast_spec of include/sgm_mi355x.h: 44 bytes, every field 4 bytes."""
     _fields_ = [
@@ -429,6 +469,15 @@ def _load() -> C.CDLL:
         L.sgm_volume_raycast_color.restype = C.c_bool
         L.sgm_volume_colors.argtypes = [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]
         L.sgm_volume_colors.restype = C.c_bool
+    if hasattr(L, "sgm_volume_window"):       # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_volume_window.argtypes = [C.c_void_p] * 9
+        L.sgm_volume_window.restype = C.c_bool
+        L.sgm_volume_window_spec.argtypes = [C.c_void_p] * 4
+        L.sgm_volume_window_spec.restype = C.c_bool
+        L.sgm_volume_follow.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p]
+        L.sgm_volume_follow.restype = C.c_bool
+        L.sgm_volume_leaving.argtypes = [C.c_void_p] * 3
+        L.sgm_volume_leaving.restype = C.c_int
     if hasattr(L, "sgm_track_sums"):          # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_track_sums.argtypes = [C.c_void_p] * 10
         L.sgm_track_sums.restype = C.c_bool
@@ -1341,6 +1390,16 @@ class SGMInstance(_StageReader):
         d_counts of volume_mesh), only for those below d_count[0].  Asynchronous on `stream`."""
         return bool(self.lib.sgm_volume_colors(self.handle, C.byref(spec), d_voxels, d_colors or None, d_records or None, int(capacity),
                                                d_count or None, int(id_kinds), d_rgba or None))
+
+    # ---- a window of the volume (include/sgm_mi355x.h, the window section); device pointers as ints, None = NULL ----
+    def volume_window(self, src: SGMVolumeSpec, offset, dims, d_src_voxels: int, d_src_colors, d_dst_voxels: int, d_dst_colors=None):
+        """sgm_volume_window: the `dims` voxels of `src` from `offset` on copied into the volume at d_dst_voxels (and the colour
+        words into d_dst_colors where both colour arrays are given), 0 where the source has nothing.  Returns the window's spec,
+        None where the call was refused.  Asynchronous on `stream`."""
+        dst = SGMVolumeSpec()
+        ok = self.lib.sgm_volume_window(self.handle, C.byref(src), _int3(offset, "volume_window"), _int3(dims, "volume_window"),
+                                        d_src_voxels or None, d_src_colors or None, d_dst_voxels or None, d_dst_colors or None, C.byref(dst))
+        return dst if ok else None
 
     # ---- frame-to-model tracking (include/sgm_mi355x.h, sgm_track_spec); device pointers as ints, None = NULL ----
     def track_sums(self, src: SGMCloudSpec, model: SGMTrackSpec, poses, d_disp, d_mask, d_conf, d_model_depth: int, d_model_normal: int,
