@@ -987,6 +987,64 @@ bool sgm_volume_follow(const sgm_volume_spec* spec, const float pose[12] /* worl
                        int32_t granule /* >= 1 */, int32_t margin /* >= 0, voxels */, int32_t shift[3]);
 int  sgm_volume_leaving(const sgm_volume_spec* spec, const int32_t shift[3], sgm_volume_box boxes[3]);   /* 0..3, -1 refused */
 
+/* ---- the distance field of the TSDF volume: the exact Euclidean distance transform of its voxel lattice ----
+ * Extension, "parity unpinned by the reference"; defined here and restated by tests/distance_ref.py.  What a planner reads from a map
+ * is the clearance of a voxel: its distance to the nearest obstacle.  The stored tq cannot serve: it is projective along the camera's
+ * Z, truncated at trunc, and undefined where no frame looked.  sgm_volume_distance computes, per voxel, the squared Euclidean distance
+ * in voxels to the nearest site of the lattice -- exact integers, tolerance 0 -- and sgm_volume_distance_field turns the words of one
+ * or both sides into a metric, optionally signed, float field.
+ *
+ * Sites.  For a voxel word, w = word >> 16 and tq = (int16_t)word.
+ *   observed    w >= min_weight
+ *   occupied    observed and tq < 0   (the sign rule of sgm_volume_points; zero counts as non-negative)
+ *   O           the obstacle set: the occupied voxels, and with unknown == 1 the voxels that are not observed
+ *   side 0      the sites are O;   side 1: the sites are every voxel of the grid that is not in O
+ * Nothing exists outside the grid: there are no sites there, on either side.
+ *
+ * sgm_volume_distance.  d_dist2 holds one uint16_t per voxel, indexed like the volume.  For voxel p = (pi, pj, pk)
+ *   m = min over sites q of (pi-qi)^2 + (pj-qj)^2 + (pk-qk)^2                                         (an exact integer)
+ *   the word written is m if a site exists and m <= r*r, otherwise SGM_DISTANCE_FAR; a site gets 0
+ * Every word of d_dist2 is written exactly once per call as far as a reader can tell (the result does not depend on what it held),
+ * nothing else is written, the volume is only read, and the result is the same bytes on every run.  The transform is separable --
+ * along x the nearest site of the row, then along y and along z out[j] = min over |o| <= r of g[j+o] + o*o -- and runs as three
+ * passes over d_dist2 itself: a workgroup owns whole lines, holds them in LDS and stores them in place.  An intermediate above r*r
+ * can never become a result and is FAR at once, so every value fits 16 bits.  The call allocates nothing: no instance scratch and
+ * no second array.  No atomics.
+ *
+ * sgm_volume_distance_field.  float32, every operation rounded on its own, sqrtf correctly rounded (as the ray-cast needs it).  With
+ * o the word of side 0 (d_out2) and i the word of side 1 (d_in2, which may be NULL: an unsigned field):
+ *   o == FAR                              +INFINITY
+ *   o > 0                                 spec->voxel * sqrtf((float)o)
+ *   o == 0 and (d_in2 == NULL or i == 0)  0.0f
+ *   o == 0 and i == FAR                   -INFINITY
+ *   o == 0 otherwise                      -(spec->voxel * sqrtf((float)i))
+ * Distances are between voxel centres: the surface lies between an occupied voxel and its free neighbour, so against the true
+ * surface the field is biased by up to half a voxel (the outside reads too far, the inside too deep, each by half a voxel along an
+ * axis); a planner that needs a bound subtracts voxel * sqrt(3) / 2.  One launch, one lane per voxel, or four with a 16-byte store
+ * where nx % 4 == 0 and the pointers allow it; no scratch, no atomics.
+ *
+ * Both calls are asynchronous on sgm_stream(s), behind the last match also with sgm_set_overlap_post, as sgm_volume_points.  false,
+ * nothing queued and one "sgm_mi355x: sgm_volume_distance: ..." (or "sgm_volume_distance_field: ...") line on stderr: a NULL s, spec,
+ * dist, d_voxels, d_dist2, d_out2 or d_field; a volume spec that sgm_volume_integrate refuses; a min_weight outside 1..65535; a radius
+ * outside 1..255; a side or unknown other than 0 or 1; a pointer that is not aligned to its element; an output that overlaps any
+ * input; a build without the kernels.  It composes with the window: sgm_volume_window crops the region of interest first (a window
+ * with a margin of r voxels around a box gives, on that box, the source's distances), and a moving volume recomputes its field after
+ * a shift.  An instance that never calls these allocates and launches exactly what it did before.
+ * Not part of it: incremental update of a field after an integration, the identity of the nearest site, a radius above 255, 2-D
+ * cost maps, queries at arbitrary points (interpolation is the caller's). */
+#define SGM_DISTANCE_FAR 0xFFFFu
+typedef struct {            /* 16 bytes, every field 4 bytes, no padding */
+    uint32_t min_weight;    /* 1..65535: a voxel is observed iff w >= min_weight */
+    int32_t  radius;        /* r, voxels, 1..255: r*r <= 65025 < SGM_DISTANCE_FAR */
+    int32_t  side;          /* 0: distance to the obstacle set; 1: distance to its complement */
+    int32_t  unknown;       /* 0: unobserved voxels are not obstacles; 1: they are */
+} sgm_distance_spec;
+size_t sgm_volume_distance_bytes(const sgm_volume_spec* spec);   /* host only; 2 * nx*ny*nz, 0 for a refused spec */
+bool sgm_volume_distance(sgm_instance* s, const sgm_volume_spec* spec, const sgm_distance_spec* dist,
+                         const uint32_t* d_voxels, uint16_t* d_dist2);
+bool sgm_volume_distance_field(sgm_instance* s, const sgm_volume_spec* spec,
+                               const uint16_t* d_out2, const uint16_t* d_in2 /* or NULL */, float* d_field);
+
 /* ---- matching at half or quarter scale, re-search at full resolution ----
  * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/scaled_ref.py.  A match at
  * 1/f scale pays for f^3 fewer cells of W x H x D for the same metric range; the result is brought back to the full grid by a guided

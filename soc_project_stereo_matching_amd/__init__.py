@@ -12,6 +12,7 @@ from .sgm import (SGM, SGMInstance, SGMOption, default_option, library_path, loa
                   register_spec, register_spec_raw,
                   SGMVolumeSpec, SURFACE_DTYPE, MESH_VERTEX_DTYPE, MESH_TRIANGLE_DTYPE, SGMMeshVertex, SGMMeshTriangle, volume_spec, volume_bytes, SGMRaycastSpec, raycast_spec,
                   SGMVolumeBox, volume_window_spec, volume_follow, volume_leaving,
+                  SGMDistanceSpec, DISTANCE_FAR, distance_spec, volume_distance_bytes,
                   SGMTrackSpec, SGMTrackStats, track_spec, track_solve, track_world_pose,
                   rectify_valid_mask, STAGE_NARROW_LEFT, STAGE_NARROW_RIGHT, SGMScaleSpec, scale_spec, scaled_shape,
                   SGMTemporalSpec, temporal_spec, TEMPORAL_CLASSES, STAGE_TEMPORAL_IN, STAGE_TEMPORAL_VALUE, STAGE_TEMPORAL_BITS,
@@ -23,6 +24,7 @@ __all__ = ["SGM", "SGMInstance", "SGMOption", "default_option", "library_path", 
            "STAGE_RECT_LEFT", "STAGE_RECT_RIGHT", "SGMCloudSpec", "POINT_DTYPE", "cloud_spec", "SGMRegisterSpec", "REGISTER_NONE",
            "register_spec", "register_spec_raw", "SGMVolumeSpec", "SURFACE_DTYPE", "MESH_VERTEX_DTYPE", "MESH_TRIANGLE_DTYPE", "SGMMeshVertex", "SGMMeshTriangle", "volume_spec", "volume_bytes", "SGMRaycastSpec", "raycast_spec",
            "SGMVolumeBox", "volume_window_spec", "volume_follow", "volume_leaving",
+           "SGMDistanceSpec", "DISTANCE_FAR", "distance_spec", "volume_distance_bytes",
            "SGMTrackSpec", "SGMTrackStats", "track_spec", "track_solve", "track_world_pose",
            "rectify_valid_mask",
            "STAGE_NARROW_LEFT", "STAGE_NARROW_RIGHT", "SGMScaleSpec", "scale_spec", "scaled_shape", "SGMTemporalSpec", "temporal_spec",

@@ -355,6 +355,15 @@ int sgmd_volume_colors(int ord, void* stream, const sgmd_volume* v, const void* 
 int sgmd_volume_window(int ord, void* stream, const sgmd_volume* src, const int* offset, const int* dims, const void* src_voxels,
                        const void* src_colors, void* dst_voxels, void* dst_colors);
 
+/* The distance field of the volume (include/sgm_mi355x.h, the distance section); sgm_distance.hip.  v: the volume as the host validated
+ * it; min_weight 1..65535, radius 1..255, side and unknown 0 or 1.  sgmd_volume_distance: dist2 u16 [nz][ny][nx], 2-byte aligned and
+ * disjoint from voxels, every word written; up to three launches (the x pass, then y and z in place where those axes are longer than
+ * one voxel), no scratch.  sgmd_volume_distance_field: field f32 [nz][ny][nx] from the side-0 words out2 and the side-1 words in2 (or
+ * NULL), one launch, no scratch.  sgm_host.c references both weakly, on their own. */
+int sgmd_volume_distance(int ord, void* stream, const sgmd_volume* v, unsigned min_weight, int radius, int side, int unknown,
+                         const void* voxels, void* dist2);
+int sgmd_volume_distance_field(int ord, void* stream, const sgmd_volume* v, const void* out2, const void* in2, void* field);
+
 /* The volume as a triangle mesh, marching tetrahedra (include/sgm_mi355x.h, sgm_volume_mesh); sgm_mesh.hip. v: the volume as the
  * host validated it, at most 2^27 voxels.  Four launches (count per tile, one scan, the vertices, the triangles; the last two only
  * where their capacity is not 0) that use scratch, sgmd_mesh_scratch_bytes(nx, ny, nz) bytes -- two sets of tile words -- which

@@ -2688,6 +2688,54 @@ int sgm_volume_leaving(const sgm_volume_spec* spec, const int32_t shift[3], sgm_
     return count;
 }
 
+/* ------------------------------------------------------------------ the distance field of the volume (extension) */
+
+/* The launchers of sgm_distance.hip, weak symbols of their own: a host built without them keeps the volume and refuses the two calls */
+#pragma weak sgmd_volume_distance
+#pragma weak sgmd_volume_distance_field
+
+size_t sgm_volume_distance_bytes(const sgm_volume_spec* spec)
+{
+    sgmd_volume v;
+    if (!spec || !volume_spec_valid(spec, &v)) return 0;
+    return volume_bytes(&v) / sizeof(uint32_t) * sizeof(uint16_t);
+}
+
+bool sgm_volume_distance(sgm_instance* s, const sgm_volume_spec* spec, const sgm_distance_spec* dist, const uint32_t* d_voxels,
+                         uint16_t* d_dist2)
+{
+    sgmd_volume v;
+    if (!s || !spec || !dist || !d_voxels || !d_dist2) FAIL("sgm_volume_distance: NULL argument");
+    if (sgmd_volume_distance == NULL) FAIL("sgm_volume_distance: the distance field is not part of this build");
+    if (!volume_spec_valid(spec, &v)) FAIL("sgm_volume_distance: the volume spec is outside its ranges");
+    if (dist->min_weight < 1u || dist->min_weight > 65535u) FAIL("sgm_volume_distance: a min_weight of %u (1..65535)", dist->min_weight);
+    if (dist->radius < 1 || dist->radius > 255) FAIL("sgm_volume_distance: a radius of %d (1..255)", dist->radius);
+    if (dist->side < 0 || dist->side > 1 || dist->unknown < 0 || dist->unknown > 1)
+        FAIL("sgm_volume_distance: side %d and unknown %d (0 or 1 each)", dist->side, dist->unknown);
+    if (!aligned_to(d_voxels, sizeof(uint32_t)) || !aligned_to(d_dist2, sizeof(uint16_t)))
+        FAIL("sgm_volume_distance: a pointer is not aligned to its element");
+    const size_t vol_bytes = volume_bytes(&v);
+    if (ranges_overlap(d_dist2, vol_bytes / 2, d_voxels, vol_bytes)) FAIL("sgm_volume_distance: the output overlaps the volume");
+    /* the volume may be the work of an integration that read a match's result: the same place in the queue as sgm_volume_points */
+    if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
+    return sgmd_volume_distance(s->device, s->stream, &v, dist->min_weight, dist->radius, dist->side, dist->unknown, d_voxels, d_dist2) == 0;
+}
+
+bool sgm_volume_distance_field(sgm_instance* s, const sgm_volume_spec* spec, const uint16_t* d_out2, const uint16_t* d_in2, float* d_field)
+{
+    sgmd_volume v;
+    if (!s || !spec || !d_out2 || !d_field) FAIL("sgm_volume_distance_field: NULL argument");
+    if (sgmd_volume_distance_field == NULL) FAIL("sgm_volume_distance_field: the distance field is not part of this build");
+    if (!volume_spec_valid(spec, &v)) FAIL("sgm_volume_distance_field: the volume spec is outside its ranges");
+    if (!aligned_to(d_out2, sizeof(uint16_t)) || !aligned_to(d_in2, sizeof(uint16_t)) || !aligned_to(d_field, sizeof(float)))
+        FAIL("sgm_volume_distance_field: a pointer is not aligned to its element");
+    const size_t vol_bytes = volume_bytes(&v);
+    if (ranges_overlap(d_field, vol_bytes, d_out2, vol_bytes / 2) || ranges_overlap(d_field, vol_bytes, d_in2, vol_bytes / 2))
+        FAIL("sgm_volume_distance_field: the output overlaps an input");
+    if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
+    return sgmd_volume_distance_field(s->device, s->stream, &v, d_out2, d_in2, d_field) == 0;
+}
+
 /* ------------------------------------------------------------------ frame-to-model tracking (extension) */
 
 /* The launcher of sgm_track.hip, a weak symbol of its own: a host built without it keeps the volume and the ray-cast */

@@ -53,6 +53,11 @@
  *            [--volume-window OX,OY,OZ,NX,NY,NZ]   extension: with --volume, after the frame is fused (and coloured) the volume is
  *                             replaced by the window of NX x NY x NZ voxels that starts OX,OY,OZ voxels into it (sgm_volume_window:
  *                             zero where the volume has nothing, the origin moved along); every --volume-* output is the window's
+ *            [--volume-distance R[,UNKNOWN] --volume-field OUT.f32]   extension: with --volume, the signed distance field of the
+ *                             fused volume (of the window, with --volume-window): sgm_volume_distance with radius R voxels on both
+ *                             sides (min_weight 1, as --volume-ply; UNKNOWN 1 counts unobserved voxels as obstacles, default 0),
+ *                             then sgm_volume_distance_field, written as raw float32, x fastest, behind 16 bytes of header: nx, ny,
+ *                             nz as int32 and voxel as float32.  Without it every output file is what it was
  *            [--volume-track ITER,DISTMAX[,TX,TY,TZ]]   extension: with --volume and --volume-view, the frame tracked against that
  *                             render (sgm_track: ITER rounds, gate DISTMAX, span the middle of the march (ZMIN + ZMAX) / 2, at least
  *                             6 pixels, pivots above 1e-6) from the identity displaced by the translation TX,TY,TZ (default 0,0,0);
@@ -311,15 +316,47 @@ static int volume_mesh_ply(sgm_instance* s, const sgm_volume_spec* vol, const ui
     return rc;
 }
 
+/* --volume-distance / --volume-field: both sides of the distance transform (min_weight 1, as the surface points), the signed field,
+ * and the file: nx, ny, nz as int32 and voxel as float32, then the floats, x fastest.  distance: the radius, then unknown.  0 or -1 */
+static int volume_field_file(sgm_instance* s, const sgm_volume_spec* vol, const uint32_t* d_voxels, const int32_t* distance, const char* path)
+{
+    const size_t n = sgm_volume_bytes(vol) / sizeof(uint32_t), half = sgm_volume_distance_bytes(vol);
+    uint16_t* d_out2 = half ? (uint16_t*)sgm_host_alloc(s, half) : NULL;
+    uint16_t* d_in2 = half ? (uint16_t*)sgm_host_alloc(s, half) : NULL;
+    float* d_field = half ? (float*)sgm_host_alloc(s, n * sizeof(float)) : NULL;
+    const sgm_distance_spec outside = {1, distance[0], 0, distance[1]}, inside = {1, distance[0], 1, distance[1]};
+    int rc = -1;
+    if (d_out2 && d_in2 && d_field && sgm_volume_distance(s, vol, &outside, d_voxels, d_out2) &&
+        sgm_volume_distance(s, vol, &inside, d_voxels, d_in2) && sgm_volume_distance_field(s, vol, d_out2, d_in2, d_field) && sgm_synchronize(s)) {
+        size_t obstacles = 0, near = 0;
+        for (size_t i = 0; i < n; ++i) {
+            obstacles += d_out2[i] == 0;
+            near += d_out2[i] != 0 && d_out2[i] != SGM_DISTANCE_FAR;
+        }
+        printf("volume field: radius %d, unknown %d: %zu obstacle voxels, %zu within the radius\n", distance[0], distance[1], obstacles, near);
+        const int32_t dims[3] = {vol->nx, vol->ny, vol->nz};
+        FILE* f = fopen(path, "wb");
+        if (f && fwrite(dims, sizeof dims, 1, f) == 1 && fwrite(&vol->voxel, sizeof(float), 1, f) == 1 && fwrite(d_field, sizeof(float), n, f) == n)
+            rc = 0;
+        if (f && fclose(f) != 0) rc = -1;
+        if (rc != 0) fprintf(stderr, "cannot write %s\n", path);
+    }
+    sgm_host_free(s, d_out2);
+    sgm_host_free(s, d_in2);
+    sgm_host_free(s, d_field);
+    return rc;
+}
+
 /* --volume: the map fused into a TSDF volume with the identity pose, and the surface points read back, as sgm_point records whose
  * pixel is the one the point projects to (clamped to the image), for write_ply; with view != NULL the volume rendered as well, with
  * mesh_path != NULL its mesh written there.  grey != NULL (--volume-color): the frame fused with that image, its own grey, into a
  * colour volume beside the TSDF words (sgm_volume_integrate_color, channels 1), which the render and the mesh then take.
  * window != NULL (--volume-window: offset, then dims): after the frame is fused the volume is replaced by that window of itself
  * (sgm_volume_window into a second allocation; the first is freed), and everything that is written is the window's.
+ * distance != NULL (--volume-distance: the radius, then unknown): the signed distance field of that volume written to field_path.
  * Page-locked buffers of an instance of its own, as above.  *out: malloc'ed, *n records. */
-static int volume_surface(const sgm_volume_spec* vol, const int32_t* window, const volume_view* view, const char* mesh_path, const uint8_t* grey,
-                          int device, int w, int h, const float* pinhole, float z_max, const float* disp, sgm_point** out, size_t* n)
+static int volume_surface(const sgm_volume_spec* vol, const int32_t* window, const int32_t* distance, const char* field_path,
+                          const volume_view* view, const char* mesh_path, const uint8_t* grey, int device, int w, int h, const float* pinhole, float z_max, const float* disp, sgm_point** out, size_t* n)
 {
     const sgm_cloud_spec src = {w, h, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], pinhole[4], pinhole[5], 0.0f, z_max, 0};
     static const float identity[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
@@ -390,6 +427,7 @@ static int volume_surface(const sgm_volume_spec* vol, const int32_t* window, con
                 *n = count;
                 rc = view ? volume_render(s, vol, view, w, h, pinhole, d_voxels, d_colors, &src, d_disp) : 0;
                 if (rc == 0 && mesh_path) rc = volume_mesh_ply(s, vol, d_voxels, d_colors, 1, mesh_path);
+                if (rc == 0 && distance) rc = volume_field_file(s, vol, d_voxels, distance, field_path);
             }
         }
     }
@@ -468,6 +506,9 @@ int main(int argc, char** argv)
     int have_track = 0, volume_color = 0;
     int32_t volume_window[6] = {0, 0, 0, 0, 0, 0};
     int have_window = 0;
+    int32_t volume_distance[2] = {0, 0};
+    int have_distance = 0;
+    const char* field_path = NULL;
     int have_view = 0;
     int register_splat = 2, register_splat_set = 0;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
@@ -535,6 +576,15 @@ int main(int argc, char** argv)
             have_window = 1;
             ++i;
         }
+        else if (v && !strcmp(a, "--volume-distance")) {
+            if (sscanf(v, "%d,%d", &volume_distance[0], &volume_distance[1]) < 1) {
+                fprintf(stderr, "--volume-distance wants R[,UNKNOWN]\n");
+                return 2;
+            }
+            have_distance = 1;
+            ++i;
+        }
+        else if (v && !strcmp(a, "--volume-field")) { field_path = v; ++i; }
         else if (v && !strcmp(a, "--volume-track")) {
             const int got = sscanf(v, "%d,%f,%f,%f,%f", &view.track_iterations, &view.track_dist_max, &view.track_t[0], &view.track_t[1],
                                    &view.track_t[2]);
@@ -605,6 +655,8 @@ int main(int argc, char** argv)
     }
     if (volume_color && !have_volume) { fprintf(stderr, "--volume-color needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n"); return 2; }
     if (have_window && !have_volume) { fprintf(stderr, "--volume-window needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n"); return 2; }
+    if ((have_distance || field_path) && !have_volume) { fprintf(stderr, "--volume-distance needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n"); return 2; }
+    if (have_distance != (field_path != NULL)) { fprintf(stderr, "--volume-distance and --volume-field OUT.f32 go together\n"); return 2; }
     if (view.image_path && (!have_view || !volume_color)) {
         fprintf(stderr, "--volume-image OUT.pgm needs --volume-view ZMIN,ZMAX,STEP[,MINWEIGHT] and --volume-color\n");
         return 2;
@@ -748,9 +800,9 @@ int main(int argc, char** argv)
         const uint8_t* grey = NULL;
         if (volume_color) grey = reference_grey(left, right, right_ref, calib_path != NULL, bits, (size_t)w1 * h1, &rect);
         if ((volume_color && !grey) ||
-            volume_surface(&volume, have_window ? volume_window : NULL, have_view ? &view : NULL, mesh_path, grey, device, w1, h1, pinhole,
-                           cloud_z_max, disp, &pts, &n) != 0) {
-            printf("volume unavailable or --volume / --volume-window / --volume-view / --volume-mesh / --pinhole / --cloud-z-max out of range\n");
+            volume_surface(&volume, have_window ? volume_window : NULL, have_distance ? volume_distance : NULL, field_path,
+                           have_view ? &view : NULL, mesh_path, grey, device, w1, h1, pinhole, cloud_z_max, disp, &pts, &n) != 0) {
+            printf("volume unavailable or --volume / --volume-window / --volume-distance / --volume-view / --volume-mesh / --pinhole / --cloud-z-max out of range\n");
             rc = -1;
         } else {
             if (!grey) grey = reference_grey(left, right, right_ref, calib_path != NULL, bits, (size_t)w1 * h1, &rect);

@@ -192,6 +192,26 @@ def volume_leaving(spec: SGMVolumeSpec, shift):
     return None if count < 0 else [(tuple(b.lo), tuple(b.n)) for b in boxes[:count]]
 
 
+DISTANCE_FAR = 0xFFFF
+
+
+class SGMDistanceSpec(C.Structure):
+    """Field-for-field sgm_distance_spec of include/sgm_mi355x.h: 16 bytes, every field 4 bytes."""
+    _fields_ = [("min_weight", C.c_uint32), ("radius", C.c_int32), ("side", C.c_int32), ("unknown", C.c_int32)]
+
+
+def distance_spec(min_weight, radius, side=0, unknown=0) -> SGMDistanceSpec:
+    """The sites and the radius of sgm_volume_distance: a voxel is observed iff its weight >= min_weight (1..65535); the obstacle
+    set is the observed voxels with tq < 0, and with unknown == 1 the unobserved ones; side 0 measures to the obstacle set, side 1
+    to its complement; radius 1..255 voxels, beyond which a voxel reads DISTANCE_FAR.  The library validates the values."""
+    return SGMDistanceSpec(int(min_weight), int(radius), int(side), int(unknown))
+
+
+def volume_distance_bytes(spec: SGMVolumeSpec) -> int:
+    """sgm_volume_distance_bytes: 2 * nx * ny * nz, 0 for a spec the library refuses"""
+    return int(load_library().sgm_volume_distance_bytes(C.byref(spec)))
+
+
 class SGMRaycastSpec(C.Structure):
     """Field-for-field sgm_raycast_spec of include/sgm_mi355x.h: 44 bytes, every field 4 bytes."""
     _fields_ = [
@@ -478,6 +498,13 @@ def _load() -> C.CDLL:
         L.sgm_volume_follow.restype = C.c_bool
         L.sgm_volume_leaving.argtypes = [C.c_void_p] * 3
         L.sgm_volume_leaving.restype = C.c_int
+    if hasattr(L, "sgm_volume_distance"):     # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        L.sgm_volume_distance_bytes.argtypes = [C.c_void_p]
+        L.sgm_volume_distance_bytes.restype = C.c_size_t
+        L.sgm_volume_distance.argtypes = [C.c_void_p] * 5
+        L.sgm_volume_distance.restype = C.c_bool
+        L.sgm_volume_distance_field.argtypes = [C.c_void_p] * 5
+        L.sgm_volume_distance_field.restype = C.c_bool
     if hasattr(L, "sgm_track_sums"):          # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_track_sums.argtypes = [C.c_void_p] * 10
         L.sgm_track_sums.restype = C.c_bool
@@ -1400,6 +1427,17 @@ class SGMInstance(_StageReader):
         ok = self.lib.sgm_volume_window(self.handle, C.byref(src), _int3(offset, "volume_window"), _int3(dims, "volume_window"),
                                         d_src_voxels or None, d_src_colors or None, d_dst_voxels or None, d_dst_colors or None, C.byref(dst))
         return dst if ok else None
+
+    # ---- the distance field of the volume (include/sgm_mi355x.h, the distance section); device pointers as ints, None = NULL ----
+    def volume_distance(self, spec: SGMVolumeSpec, dist: SGMDistanceSpec, d_voxels: int, d_dist2: int) -> bool:
+        """sgm_volume_distance: per voxel the squared distance, in voxels, to the nearest site of `dist` as uint16 into d_dist2
+        (volume_distance_bytes(spec) bytes), DISTANCE_FAR beyond the radius.  Asynchronous on `stream`."""
+        return bool(self.lib.sgm_volume_distance(self.handle, C.byref(spec), C.byref(dist), d_voxels or None, d_dist2 or None))
+
+    def volume_distance_field(self, spec: SGMVolumeSpec, d_out2: int, d_in2, d_field: int) -> bool:
+        """sgm_volume_distance_field: the metric field, float32 per voxel, from the side-0 words at d_out2 and, for the sign, the
+        side-1 words at d_in2 (None: unsigned).  Asynchronous on `stream`."""
+        return bool(self.lib.sgm_volume_distance_field(self.handle, C.byref(spec), d_out2 or None, d_in2 or None, d_field or None))
 
     # ---- frame-to-model tracking (include/sgm_mi355x.h, sgm_track_spec); device pointers as ints, None = NULL ----
     def track_sums(self, src: SGMCloudSpec, model: SGMTrackSpec, poses, d_disp, d_mask, d_conf, d_model_depth: int, d_model_normal: int,
