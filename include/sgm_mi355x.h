@@ -1045,6 +1045,135 @@ bool sgm_volume_distance(sgm_instance* s, const sgm_volume_spec* spec, const sgm
 bool sgm_volume_distance_field(sgm_instance* s, const sgm_volume_spec* spec,
                                const uint16_t* d_out2, const uint16_t* d_in2 /* or NULL */, float* d_field);
 
+/* ---- planes in a point list: exact votes on the device, an integer fit ----
+ * Extension, "parity unpinned by the reference"; defined here and restated by tests/plane_ref.py.  Everything above stops at raw
+ * geometry; this answers the first question asked of it: where is the floor, where are the walls, which points stand on them.
+ * A point list is what sgm_cloud_points, sgm_volume_points and sgm_volume_mesh (its vertices) write: 16-byte records
+ * { float x, y, z; uint32 tag } -- sgm_point, sgm_surface_point, sgm_mesh_vertex; the tag is never read -- with an optional device
+ * count word, so that a call can be queued behind the list's own call without reading the count back.  Throughout,
+ *   n = min(capacity, d_count[0])     (capacity where d_count == NULL)
+ * and a record r < n TAKES PART iff x, y, z are finite and it is unlabelled (d_labels == NULL || d_labels[r] == 0).
+ *
+ * All device arithmetic is float32, every operation rounded on its own (no contraction; divide and sqrt correctly rounded); the
+ * parentheses are the contract; "finite" is tested on the bit pattern, before any comparison.
+ * A plane (sgm_plane) is normal . (P - anchor) = 0 with offset = -(normal . anchor) carried along; a VOID plane has an all-zero
+ * normal (either sign of zero) and, as the entry points write it, 32 zero bytes.  A void plane has no inliers.
+ * The vote rule.  A record that takes part is an INLIER of a non-void plane iff
+ *   s = ((n0*(x - a0) + n1*(y - a1)) + n2*(z - a2))     is finite and |s| <= dist
+ *
+ * Candidates (sgm_plane_votes).  Candidate k = 0 .. hypotheses-1 takes the records i_j = ((uint64)h(seed, k, j) * n) >> 32,
+ * j = 0, 1, 2, with the uint32 mix (every operation modulo 2^32; no modulo by n, no float)
+ *   h(seed, k, j):  x = (seed ^ (k * 0x9E3779B9)) ^ ((j + 1) * 0x85EBCA6B)
+ *                   x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16
+ * It is void where two of the three indices coincide (so always for n < 3; no record is read then) or a chosen record does not
+ * take part.  Else, with P0, P1, P2 the records:
+ *   u = P1 - P0,  v = P2 - P0                                   (per coordinate)
+ *   c0 = u1*v2 - u2*v1,  c1 = u2*v0 - u0*v2,  c2 = u0*v1 - u1*v0
+ *   len2 = (c0*c0 + c1*c1) + c2*c2;   void unless len2 is finite and len2 > 0
+ *   len = sqrtf(len2);   n_i = c_i / len;   void unless every n_i is finite and not all are zero
+ *   t = (n0*P0x + n1*P0y) + n2*P0z;   void unless t is finite
+ *   with a prior (axis not all zero):  d = (n0*axis0 + n1*axis1) + n2*axis2;  void unless d is finite;
+ *                                      if d < 0: n = -n, t = -t, d = -d;   void unless d >= thr,
+ *                                      thr = min_cos * sqrtf((axis0*axis0 + axis1*axis1) + axis2*axis2)     (float32, as written)
+ *   without:                           if t > 0: n = -n, t = -t                                            (so that offset >= 0)
+ *   normal = n,  offset = 0.0f - t,  anchor = P0,  votes = 0
+ * The candidates are written to d_planes by a small launch of their own; the vote launch that follows adds to their votes.
+ * Votes.  votes of a non-void candidate = the number of its inliers among the records r < n, exact (modulo 2^32, which only
+ * n = 2^32 can reach).  A void candidate keeps its 32 zero bytes.  Integer sums: the same bytes on every run.
+ * Best (sgm_plane_best).  d_best receives the non-void candidate with the most votes, ties to the smallest k; a void plane where
+ * every candidate is void.
+ * Sums (sgm_plane_sums).  Over the inliers of *d_plane, per coordinate i:
+ *   e_i = (P_i - anchor_i) / span;   skip the record unless every e_i is finite and |e_i| <= 8.0f
+ *   q_i = (int32)rintf(e_i * 65536.0f)                        (the product is exact; round half to even; |q_i| <= 2^19)
+ * d_sums[0..9] is the upper triangle of the 4 x 4 moment matrix of (q_x, q_y, q_z, 1) in row-major order: sum of q_x*q_x, q_x*q_y,
+ * q_x*q_z, q_x, q_y*q_y, q_y*q_z, q_y, q_z*q_z, q_z, 1; the last is the number of records that were not skipped.  Bound: a term
+ * is at most 2^38 and the entry points refuse capacity > 2^24, so a sum stays at or below 2^62 and no addition overflows int64;
+ * exact integers, so the order of addition does not show.
+ * Labels (sgm_plane_label).  d_labels[r] = label for every inlier of *d_plane (an inlier is unlabelled by definition); no other
+ * byte is written.  Label the floor, vote again: the second plane.  The records still 0 afterwards are the obstacle points.
+ *
+ * The fit step (sgm_plane_solve; host only, double, every operation rounded on its own, no contraction, no libm beyond sqrt).
+ * Sxx .. N name the ten sums in their order (Sxx Sxy Sxz Sx Syy Syz Sy Szz Sz N) as doubles, M the symmetric 3 x 3 matrix of the
+ * second moments and m = (Sx, Sy, Sz).  status 1 (too few inliers) if N < min_inliers.  Else, from plane_in (n, A as doubles):
+ *   w = n / sqrt((n0*n0 + n1*n1) + n2*n2)
+ *   e = the unit vector of the axis with the smallest |w_i|, ties to the lowest index
+ *   t1 = c / sqrt((c0*c0 + c1*c1) + c2*c2),  c = w x e;     t2 = w x t1        (p x r = (p1*r2 - p2*r1, p2*r0 - p0*r2, p0*r1 - p1*r0))
+ *   M(p, r) = (p0*Mr_0 + p1*Mr_1) + p2*Mr_2,  Mr_i = (M_i0*r0 + M_i1*r1) + M_i2*r2;      m(p) = (p0*Sx + p1*Sy) + p2*Sz
+ * (t1, t2, w) is an orthonormal frame; with u = t1.q, v = t2.q, s = w.q the moments in that frame are exact integers rotated:
+ *   Su = m(t1), Sv = m(t2), Ss = m(w), Suu = M(t1,t1), Suv = M(t1,t2), Svv = M(t2,t2), Sus = M(t1,w), Svs = M(t2,w), Sss = M(w,w)
+ * The regression s = c + a*u + b*v has the normal equations A x = y, x = (c, a, b), in this order of unknowns:
+ *   A = [N Su Sv; Su Suu Suv; Sv Suv Svv],   y = (Ss, Sus, Svs)
+ * solved by LDL^T without square roots, columns j = 0..2 left to right, every inner sum starting at 0.0 in index order:
+ *   D_j  = A_jj - sum_{k<j} (L_jk*L_jk)*D_k
+ *   status 2 (degenerate) unless D_j is finite and D_j > min_pivot * A_jj
+ *   L_ij = (A_ij - sum_{k<j} (L_ik*L_jk)*D_k) / D_j                for i = j+1..2
+ * then  z_i = y_i - sum_{k<i} L_ik*z_k   (i = 0..2),   x_i = z_i / D_i - sum_{k=i+1..2} L_ki*x_k   (i = 2..0).
+ * With the constant first, D_1 and D_2 are the centred second moments: identical inliers fail at D_1, collinear ones at D_1 or D_2.
+ *   g = (w - a*t1) - b*t2;   lg = sqrt((g0*g0 + g1*g1) + g2*g2);   nn = g / lg          the stepped unit normal
+ *   gq = (Sx/N, Sy/N, Sz/N)                                                              the centroid, in q units
+ *   d  = c/lg - ((nn0*gq0 + nn1*gq1) + nn2*gq2);   pq = gq + d*nn                        the centroid lifted onto the new plane
+ *   unit = span / 65536;   anchor_i = (float)(A_i + pq_i*unit);   normal_i = (float)nn_i  each rounded to float once
+ *   t = (N0*a0 + N1*a1) + N2*a2    on the rounded normal N and anchor a, as doubles
+ *   with a prior:  if (N0*axis0 + N1*axis1) + N2*axis2 < 0: N = -N, t = -t;     without:  if t > 0: N = -N, t = -t
+ *   offset = (float)(0.0 - t);   votes = N (the count)
+ *   SSR = Sss - ((c*Ss + a*Sus) + b*Svs), taken as 0 if negative;   rms = unit * sqrt(SSR / N)      in the units of span
+ * status 2 as well if x, lg (which must be > 0) or an output is not finite.  With status 0 plane_out is the stepped plane; else
+ * plane_out = plane_in and rms = 0.  stats->inliers = N in every case.  Regressing the offset along the current normal on the
+ * in-plane coordinates has total least squares as its fixed point: where the step leaves the normal unchanged, a = b = 0, the
+ * in-plane coordinates are uncorrelated with the residual, and the normal is an eigenvector of the inliers' covariance; iterated
+ * from a candidate near the plane it converges to the eigenvector of the smallest eigenvalue, the orthogonal-distance fit.
+ *
+ * sgm_plane_fit (blocking).  First sgm_plane_votes into candidates of the instance's own, sgm_plane_best into a 32-byte device
+ * word of the instance's own, and that word copied to the host; a void best plane is status 1 and ends the call.  Then up to
+ * spec->iterations rounds, each of which
+ *   1. copies the current plane to that device word (from the second round on: in the first it is there already),
+ *   2. queues sgm_plane_sums at it into 80 bytes of the instance's own,
+ *   3. copies those 80 bytes to the host and waits for them,
+ *   4. steps the plane with sgm_plane_solve.
+ * The first status other than 0 ends the rounds, and the plane stays the last good one.  *plane
+ * and *stats are HOST outputs: the last plane and the stats of the last solve.  trace_sums (HOST, int64 [iterations][10], or
+ * NULL) receives the sums of every round made, trace_planes (HOST, sgm_plane [iterations + 1], or NULL) the best candidate and
+ * the plane after every round made; rounds not made leave their entries as they were.
+ *
+ * The device entry points are asynchronous on sgm_stream(s) and ordered as sgm_volume_points is (behind the last match also with
+ * sgm_set_overlap_post; a list queued before them on the same instance is finished when they read it).  d_records is 16-byte
+ * aligned; d_planes, d_best and d_plane are 16-byte aligned; d_sums is 8-byte aligned and zeroed on the stream inside the call;
+ * d_count is 4-byte aligned; d_labels needs no alignment.  No scratch, except the 32 KiB + 112 bytes sgm_plane_fit reserves at
+ * its first call: an instance that never calls these entry points allocates and launches exactly what it did before.
+ * false, nothing queued and one "sgm_mi355x: <entry point>: ..." line on stderr: a NULL pointer other than d_count, d_labels
+ * (sgm_plane_label needs its d_labels) and the traces; a spec outside the ranges below; a label outside 1..255; a K outside 1..1024
+ * (sgm_plane_best); a pointer not aligned as said; capacity > 2^32 (> 2^24 for sgm_plane_sums and sgm_plane_fit); an output that
+ * overlaps an input or another output; a plane_in that is not finite or is void, or a sums[9] outside 0..2^24
+ * (sgm_plane_solve); a build without the kernels.  Not part of it: several planes in one call, plane extents and polygons, a
+ * plane at a clicked pixel, region growing on normals, a floor-aligned pose helper, row tiles. */
+typedef struct { float normal[3]; float offset; float anchor[3]; uint32_t votes; } sgm_plane;   /* 32 bytes */
+typedef struct {            /* 44 bytes, every field 4 bytes, no padding */
+    int32_t  hypotheses;    /* K, 1..1024: candidate planes of a vote */
+    uint32_t seed;          /* of the hash that picks the candidates' records */
+    float    dist;          /* finite, > 0: the inlier half-thickness, units of the records */
+    float    axis[3];       /* the orientation prior; all zero: none.  Else finite, with a finite length > 0 as a float */
+    float    min_cos;       /* finite, 0..1: with a prior a candidate is kept only if |normal . axis| >= min_cos * |axis| */
+    float    span;          /* finite, > 0: the length that normalises coordinates before they are quantised; about the scene size */
+    int32_t  iterations;    /* 1..64: rounds of sgm_plane_fit */
+    uint32_t min_inliers;   /* at least 3: fewer are status 1 */
+    float    min_pivot;     /* finite, >= 0: a pivot D_j <= min_pivot * A_jj is status 2 */
+} sgm_plane_spec;
+typedef struct { double rms; uint32_t inliers; int32_t status; } sgm_plane_stats;   /* 16 bytes; status 0 ok, 1 too few inliers, 2 degenerate */
+bool sgm_plane_votes(sgm_instance* s, const sgm_plane_spec* spec, const void* d_records /* 16-byte records */, size_t capacity,
+                     const uint32_t* d_count /* device u32, or NULL */, const uint8_t* d_labels /* device u8 [capacity], or NULL */,
+                     sgm_plane* d_planes /* device, [hypotheses], 16-byte aligned */);
+bool sgm_plane_best(sgm_instance* s, const sgm_plane* d_planes, int K /* 1..1024 */, sgm_plane* d_best /* device, 16-byte aligned */);
+bool sgm_plane_sums(sgm_instance* s, const sgm_plane_spec* spec, const void* d_records, size_t capacity, const uint32_t* d_count,
+                    const uint8_t* d_labels, const sgm_plane* d_plane /* device, one plane */,
+                    int64_t* d_sums /* device, [10], 8-byte aligned */);
+bool sgm_plane_label(sgm_instance* s, const sgm_plane_spec* spec, const void* d_records, size_t capacity, const uint32_t* d_count,
+                     const sgm_plane* d_plane, int label /* 1..255 */, uint8_t* d_labels /* device u8 [capacity] */);
+bool sgm_plane_solve(const sgm_plane_spec* spec, const int64_t sums[10], const sgm_plane* plane_in, sgm_plane* plane_out,
+                     sgm_plane_stats* stats);                                        /* host only */
+bool sgm_plane_fit(sgm_instance* s, const sgm_plane_spec* spec, const void* d_records, size_t capacity, const uint32_t* d_count,
+                   const uint8_t* d_labels, sgm_plane* plane /* HOST out */, sgm_plane_stats* stats /* HOST out */,
+                   int64_t* trace_sums /* HOST [iterations][10], or NULL */, sgm_plane* trace_planes /* HOST [iterations + 1], or NULL */);
+
 /* ---- matching at half or quarter scale, re-search at full resolution ----
  * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/scaled_ref.py.  A match at
  * 1/f scale pays for f^3 fewer cells of W x H x D for the same metric range; the result is brought back to the full grid by a guided

@@ -14,6 +14,7 @@ from .sgm import (SGM, SGMInstance, SGMOption, default_option, library_path, loa
                   SGMVolumeBox, volume_window_spec, volume_follow, volume_leaving,
                   SGMDistanceSpec, DISTANCE_FAR, distance_spec, volume_distance_bytes,
                   SGMTrackSpec, SGMTrackStats, track_spec, track_solve, track_world_pose,
+                  SGMPlane, SGMPlaneSpec, SGMPlaneStats, PLANE_DTYPE, plane_spec, plane_solve,
                   rectify_valid_mask, STAGE_NARROW_LEFT, STAGE_NARROW_RIGHT, SGMScaleSpec, scale_spec, scaled_shape,
                   SGMTemporalSpec, temporal_spec, TEMPORAL_CLASSES, STAGE_TEMPORAL_IN, STAGE_TEMPORAL_VALUE, STAGE_TEMPORAL_BITS,
                   debug_guard_check)
@@ -26,6 +27,7 @@ __all__ = ["SGM", "SGMInstance", "SGMOption", "default_option", "library_path", 
            "SGMVolumeBox", "volume_window_spec", "volume_follow", "volume_leaving",
            "SGMDistanceSpec", "DISTANCE_FAR", "distance_spec", "volume_distance_bytes",
            "SGMTrackSpec", "SGMTrackStats", "track_spec", "track_solve", "track_world_pose",
+           "SGMPlane", "SGMPlaneSpec", "SGMPlaneStats", "PLANE_DTYPE", "plane_spec", "plane_solve",
            "rectify_valid_mask",
            "STAGE_NARROW_LEFT", "STAGE_NARROW_RIGHT", "SGMScaleSpec", "scale_spec", "scaled_shape", "SGMTemporalSpec", "temporal_spec",
            "TEMPORAL_CLASSES", "STAGE_TEMPORAL_IN", "STAGE_TEMPORAL_VALUE", "STAGE_TEMPORAL_BITS", "debug_guard_check", "SGMStream", "frames_of_rank", "match_sharded"]

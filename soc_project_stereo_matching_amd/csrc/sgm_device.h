@@ -388,6 +388,26 @@ typedef struct {
 int sgmd_track_sums(int ord, void* stream, const sgmd_cloud* c, const sgmd_track* t, const float* poses, const void* disp,
                     const void* mask, const void* conf, const void* model_depth, const void* model_normal, void* sums);
 
+/* Extension (parity unpinned by the reference), planes in a point list (include/sgm_mi355x.h, sgm_plane_spec); sgm_plane.hip.
+ * p: the spec as the host validated it (threshold = min_cos * |axis| as the header rounds it, prior = the axis is not all zero).
+ * records: 16-byte records {x, y, z, tag}, 16-byte aligned, capacity <= 2^32 of them (2^24 for the sums); count: a device u32 or
+ * NULL; labels: device u8 [capacity] or NULL (sgmd_plane_label: never NULL); planes / plane / best: device sgm_plane, 16-byte
+ * aligned; sums: int64 [10], 8-byte aligned, zeroed on the stream and then added to with integer atomics.  sgmd_plane_votes: two
+ * launches (the candidates, the vote); the others one each; no scratch.  sgm_host.c references each weakly, on its own. */
+typedef struct {
+    int hypotheses;
+    unsigned seed;
+    float dist, axis[3], threshold, span;
+    int prior;
+} sgmd_plane;
+int sgmd_plane_votes(int ord, void* stream, const sgmd_plane* p, const void* records, size_t capacity, const void* count,
+                     const void* labels, void* planes);
+int sgmd_plane_best(int ord, void* stream, const void* planes, int K, void* best);
+int sgmd_plane_sums(int ord, void* stream, const sgmd_plane* p, const void* records, size_t capacity, const void* count,
+                    const void* labels, const void* plane, void* sums);
+int sgmd_plane_label(int ord, void* stream, const sgmd_plane* p, const void* records, size_t capacity, const void* count,
+                     const void* plane, int label, void* labels);
+
 /* Extension (parity unpinned by the reference), matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); sgm_scale.hip.
  * c: the spec as the host validated it (W, H: FULL resolution; the low resolution is W / f x H / f).  sgmd_downscale: the f x f box
  * mean with rounding of one image stack, u8 (bits == 8) or u16 [B][H][W] -> [B][H / f][W / f]; trailing rows and columns are not

@@ -167,6 +167,9 @@ struct sgm_instance {
     /* tracking (allocated at the first such call): the sums of a round of sgm_track, 29 int64 per frame, and whatever scratch the
      * launcher asks for (none in the default build) */
     sgm_buf d_track_sums;
+    /* planes in a point list (sgm_plane_fit; allocated at its first call): 1024 candidates, the plane that travels between the
+     * rounds and the ten sums of a round */
+    sgm_buf d_plane_work;
     /* matching at 1/f scale (sgm_match_scaled; allocated at its first use): the downscaled views, the census planes of the
      * FULL-resolution views with the narrowed images sgmd_census16 writes beside them, and for the host-pointer form the full
      * images, the full map and their page-locked staging */
@@ -219,6 +222,7 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     DEVICE_BUF(d_sc_g8_r), DEVICE_BUF(d_sc_full_l), DEVICE_BUF(d_sc_full_r), DEVICE_BUF(d_sc_disp), PINNED_BUF(h_sc_l), PINNED_BUF(h_sc_r),
     PINNED_BUF(h_sc_disp), DEVICE_BUF(d_tp_value), DEVICE_BUF(d_tp_bits), DEVICE_BUF(d_tp_stats), DEVICE_BUF(d_tp_pre),
     DEVICE_BUF(d_tp_scratch), DEVICE_BUF(d_register_keys), DEVICE_BUF(d_volume_scratch), DEVICE_BUF(d_mesh_scratch), DEVICE_BUF(d_track_sums),
+    DEVICE_BUF(d_plane_work),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -2917,6 +2921,281 @@ bool sgm_track(sgm_instance* s, const sgm_cloud_spec* src, const sgm_track_spec*
         }
         if (trace_poses) memcpy(trace_poses + (size_t)(it + 1) * c.B * 12, poses, (size_t)c.B * 12 * sizeof(double));
     }
+    return true;
+}
+
+/* ------------------------------------------------------------------ planes in a point list (extension) */
+
+/* The launchers of sgm_plane.hip, weak symbols each on its own: a host built without one refuses its entry point and keeps the rest */
+#pragma weak sgmd_plane_votes
+#pragma weak sgmd_plane_best
+#pragma weak sgmd_plane_sums
+#pragma weak sgmd_plane_label
+
+#define PLANE_SUMS 10
+#define PLANE_MAX_K 1024
+#define PLANE_MAX_RECORDS ((size_t)1 << 32)
+#define PLANE_MAX_SUMMED ((size_t)1 << 24)     /* a term is at most 2^38, a sum stays at or below 2^62 */
+#define RECORD_BYTES 16
+
+/* the spec as the kernels take it; NULL, or what is outside the ranges of include/sgm_mi355x.h */
+static const char* plane_spec_invalid(const sgm_plane_spec* sp, sgmd_plane* p)
+{
+    if (sp->hypotheses < 1 || sp->hypotheses > PLANE_MAX_K) return "hypotheses 1..1024";
+    if (!finite_positive(sp->dist)) return "dist finite and > 0";
+    if (!isfinite(sp->axis[0]) || !isfinite(sp->axis[1]) || !isfinite(sp->axis[2])) return "axis finite";
+    const int prior = sp->axis[0] != 0.0f || sp->axis[1] != 0.0f || sp->axis[2] != 0.0f;
+    const float len = sqrtf((sp->axis[0] * sp->axis[0] + sp->axis[1] * sp->axis[1]) + sp->axis[2] * sp->axis[2]);
+    if (prior && !finite_positive(len)) return "an axis with a finite length > 0 as a float";
+    if (!isfinite(sp->min_cos) || !(sp->min_cos >= 0.0f) || !(sp->min_cos <= 1.0f)) return "min_cos 0..1";
+    if (!finite_positive(sp->span)) return "span finite and > 0";
+    if (sp->iterations < 1 || sp->iterations > 64) return "iterations 1..64";
+    if (sp->min_inliers < 3u) return "min_inliers at least 3";
+    if (!isfinite(sp->min_pivot) || !(sp->min_pivot >= 0.0f)) return "min_pivot finite and >= 0";
+    if (p) *p = (sgmd_plane){sp->hypotheses, sp->seed, sp->dist, {sp->axis[0], sp->axis[1], sp->axis[2]}, sp->min_cos * len, sp->span, prior};
+    return NULL;
+}
+
+/* What the device entry points check of a list before they queue anything */
+static bool plane_list_ready(const sgm_plane_spec* spec, const void* d_records, size_t capacity, size_t max_records, const uint32_t* d_count,
+                             sgmd_plane* p, const char* entry)
+{
+    const char* why = plane_spec_invalid(spec, p);
+    if (why) FAIL("%s: the spec is outside its ranges (%s)", entry, why);
+    if (capacity > max_records) FAIL("%s: a capacity of %zu records (at most 2^%d)", entry, capacity, max_records == PLANE_MAX_RECORDS ? 32 : 24);
+    if (!aligned_to(d_records, RECORD_BYTES) || !aligned_to(d_count, sizeof(uint32_t)))
+        FAIL("%s: a pointer is not aligned (records and planes to 16 bytes, the sums to 8, the count to 4)", entry);
+    return true;
+}
+
+/* an output of `bytes` at out against the list (labels: NULL, or the byte per record that is an input here) */
+static bool plane_output_clear(const void* out, size_t bytes, const void* d_records, size_t capacity, const uint32_t* d_count,
+                               const uint8_t* d_labels, const char* entry)
+{
+    if (ranges_overlap(out, bytes, d_records, capacity * RECORD_BYTES) || ranges_overlap(out, bytes, d_count, sizeof(uint32_t)) ||
+        ranges_overlap(out, bytes, d_labels, capacity))
+        FAIL("%s: an output overlaps an input", entry);
+    return true;
+}
+
+bool sgm_plane_votes(sgm_instance* s, const sgm_plane_spec* spec, const void* d_records, size_t capacity, const uint32_t* d_count,
+                     const uint8_t* d_labels, sgm_plane* d_planes)
+{
+    sgmd_plane p;
+    if (!s || !spec || !d_records || !d_planes) FAIL("sgm_plane_votes: NULL argument");
+    if (sgmd_plane_votes == NULL) FAIL("sgm_plane_votes: the planes of a list are not part of this build");
+    if (!plane_list_ready(spec, d_records, capacity, PLANE_MAX_RECORDS, d_count, &p, "sgm_plane_votes")) return false;
+    if (!aligned_to(d_planes, 16)) FAIL("sgm_plane_votes: a pointer is not aligned (records and planes to 16 bytes, the count to 4)");
+    if (!plane_output_clear(d_planes, (size_t)p.hypotheses * sizeof(sgm_plane), d_records, capacity, d_count, d_labels, "sgm_plane_votes"))
+        return false;
+    /* behind the list's own call on this stream, and behind the last match as that call is */
+    if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
+    return sgmd_plane_votes(s->device, s->stream, &p, d_records, capacity, d_count, d_labels, d_planes) == 0;
+}
+
+bool sgm_plane_best(sgm_instance* s, const sgm_plane* d_planes, int K, sgm_plane* d_best)
+{
+    if (!s || !d_planes || !d_best) FAIL("sgm_plane_best: NULL argument");
+    if (sgmd_plane_best == NULL) FAIL("sgm_plane_best: the planes of a list are not part of this build");
+    if (K < 1 || K > PLANE_MAX_K) FAIL("sgm_plane_best: %d candidates (1..1024)", K);
+    if (!aligned_to(d_planes, 16) || !aligned_to(d_best, 16)) FAIL("sgm_plane_best: a pointer is not aligned (planes to 16 bytes)");
+    if (ranges_overlap(d_best, sizeof(sgm_plane), d_planes, (size_t)K * sizeof(sgm_plane))) FAIL("sgm_plane_best: the output overlaps the candidates");
+    if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
+    return sgmd_plane_best(s->device, s->stream, d_planes, K, d_best) == 0;
+}
+
+bool sgm_plane_sums(sgm_instance* s, const sgm_plane_spec* spec, const void* d_records, size_t capacity, const uint32_t* d_count,
+                    const uint8_t* d_labels, const sgm_plane* d_plane, int64_t* d_sums)
+{
+    sgmd_plane p;
+    if (!s || !spec || !d_records || !d_plane || !d_sums) FAIL("sgm_plane_sums: NULL argument");
+    if (sgmd_plane_sums == NULL) FAIL("sgm_plane_sums: the planes of a list are not part of this build");
+    if (!plane_list_ready(spec, d_records, capacity, PLANE_MAX_SUMMED, d_count, &p, "sgm_plane_sums")) return false;
+    if (!aligned_to(d_plane, 16) || !aligned_to(d_sums, sizeof(int64_t)))
+        FAIL("sgm_plane_sums: a pointer is not aligned (records and planes to 16 bytes, the sums to 8, the count to 4)");
+    const size_t sum_bytes = PLANE_SUMS * sizeof(int64_t);
+    if (ranges_overlap(d_sums, sum_bytes, d_plane, sizeof(sgm_plane))) FAIL("sgm_plane_sums: an output overlaps an input");
+    if (!plane_output_clear(d_sums, sum_bytes, d_records, capacity, d_count, d_labels, "sgm_plane_sums")) return false;
+    if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
+    return sgmd_plane_sums(s->device, s->stream, &p, d_records, capacity, d_count, d_labels, d_plane, d_sums) == 0;
+}
+
+bool sgm_plane_label(sgm_instance* s, const sgm_plane_spec* spec, const void* d_records, size_t capacity, const uint32_t* d_count,
+                     const sgm_plane* d_plane, int label, uint8_t* d_labels)
+{
+    sgmd_plane p;
+    if (!s || !spec || !d_records || !d_plane || !d_labels) FAIL("sgm_plane_label: NULL argument");
+    if (sgmd_plane_label == NULL) FAIL("sgm_plane_label: the planes of a list are not part of this build");
+    if (!plane_list_ready(spec, d_records, capacity, PLANE_MAX_RECORDS, d_count, &p, "sgm_plane_label")) return false;
+    if (label < 1 || label > 255) FAIL("sgm_plane_label: a label of %d (1..255)", label);
+    if (!aligned_to(d_plane, 16)) FAIL("sgm_plane_label: a pointer is not aligned (records and planes to 16 bytes, the count to 4)");
+    if (ranges_overlap(d_labels, capacity, d_plane, sizeof(sgm_plane))) FAIL("sgm_plane_label: an output overlaps an input");
+    if (!plane_output_clear(d_labels, capacity, d_records, capacity, d_count, NULL, "sgm_plane_label")) return false;
+    if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
+    return sgmd_plane_label(s->device, s->stream, &p, d_records, capacity, d_count, d_plane, label, d_labels) == 0;
+}
+
+static void plane_cross(const double* p, const double* r, double* out)
+{
+    out[0] = p[1] * r[2] - p[2] * r[1];
+    out[1] = p[2] * r[0] - p[0] * r[2];
+    out[2] = p[0] * r[1] - p[1] * r[0];
+}
+
+static double plane_dot(const double* p, const double* r) { return (p[0] * r[0] + p[1] * r[1]) + p[2] * r[2]; }
+
+/* M(p, r) of the header for the symmetric matrix M */
+static double plane_moment(const double M[3][3], const double* p, const double* r)
+{
+    const double Mr[3] = {plane_dot(M[0], r), plane_dot(M[1], r), plane_dot(M[2], r)};
+    return plane_dot(p, Mr);
+}
+
+bool sgm_plane_solve(const sgm_plane_spec* spec, const int64_t sums[10], const sgm_plane* plane_in, sgm_plane* plane_out, sgm_plane_stats* stats)
+{
+    if (!spec || !sums || !plane_in || !plane_out || !stats) FAIL("sgm_plane_solve: NULL argument");
+    sgmd_plane rule;
+    const char* why = plane_spec_invalid(spec, &rule);
+    if (why) FAIL("sgm_plane_solve: the spec is outside its ranges (%s)", why);
+    const double n[3] = {plane_in->normal[0], plane_in->normal[1], plane_in->normal[2]};
+    const double A[3] = {plane_in->anchor[0], plane_in->anchor[1], plane_in->anchor[2]};
+    for (int i = 0; i < 3; ++i)
+        if (!isfinite(n[i]) || !isfinite(A[i])) FAIL("sgm_plane_solve: the plane is not finite");
+    if (n[0] == 0.0 && n[1] == 0.0 && n[2] == 0.0) FAIL("sgm_plane_solve: the plane is void");
+    if (sums[9] < 0 || sums[9] > (int64_t)PLANE_MAX_SUMMED) FAIL("sgm_plane_solve: %lld inliers (0..2^24)", (long long)sums[9]);
+    sgm_plane out = *plane_in;
+    stats->inliers = (uint32_t)sums[9];
+    stats->rms = 0.0;
+    stats->status = 0;
+    if ((uint64_t)sums[9] < spec->min_inliers) stats->status = 1;
+    if (stats->status == 0) {
+        const double N = (double)sums[9];
+        const double M[3][3] = {{(double)sums[0], (double)sums[1], (double)sums[2]},
+                                {(double)sums[1], (double)sums[4], (double)sums[5]},
+                                {(double)sums[2], (double)sums[5], (double)sums[7]}};
+        const double m[3] = {(double)sums[3], (double)sums[6], (double)sums[8]};
+        const double ln = sqrt(plane_dot(n, n));
+        const double w[3] = {n[0] / ln, n[1] / ln, n[2] / ln};
+        int axis = 0;
+        for (int i = 1; i < 3; ++i)
+            if (fabs(w[i]) < fabs(w[axis])) axis = i;
+        double e[3] = {0.0, 0.0, 0.0}, c[3], t1[3], t2[3];
+        e[axis] = 1.0;
+        plane_cross(w, e, c);
+        const double lc = sqrt(plane_dot(c, c));
+        for (int i = 0; i < 3; ++i) t1[i] = c[i] / lc;
+        plane_cross(w, t1, t2);
+        const double Su = plane_dot(t1, m), Sv = plane_dot(t2, m), Ss = plane_dot(w, m);
+        const double Suu = plane_moment(M, t1, t1), Suv = plane_moment(M, t1, t2), Svv = plane_moment(M, t2, t2);
+        const double Sus = plane_moment(M, t1, w), Svs = plane_moment(M, t2, w), Sss = plane_moment(M, w, w);
+        const double Am[3][3] = {{N, Su, Sv}, {Su, Suu, Suv}, {Sv, Suv, Svv}};
+        const double y[3] = {Ss, Sus, Svs};
+        double L[3][3], D[3], z[3], x[3];
+        memset(L, 0, sizeof L);
+        for (int j = 0; j < 3 && stats->status == 0; ++j) {
+            double acc = 0.0;
+            for (int k = 0; k < j; ++k) acc += (L[j][k] * L[j][k]) * D[k];
+            D[j] = Am[j][j] - acc;
+            if (!isfinite(D[j]) || !(D[j] > (double)spec->min_pivot * Am[j][j])) { stats->status = 2; break; }
+            for (int i = j + 1; i < 3; ++i) {
+                acc = 0.0;
+                for (int k = 0; k < j; ++k) acc += (L[i][k] * L[j][k]) * D[k];
+                L[i][j] = (Am[i][j] - acc) / D[j];
+            }
+        }
+        if (stats->status == 0) {
+            for (int i = 0; i < 3; ++i) {
+                double acc = 0.0;
+                for (int k = 0; k < i; ++k) acc += L[i][k] * z[k];
+                z[i] = y[i] - acc;
+            }
+            for (int i = 2; i >= 0; --i) {
+                double acc = 0.0;
+                for (int k = i + 1; k < 3; ++k) acc += L[k][i] * x[k];
+                x[i] = z[i] / D[i] - acc;
+            }
+            for (int i = 0; i < 3; ++i)
+                if (!isfinite(x[i])) stats->status = 2;
+        }
+        if (stats->status == 0) {
+            const double g[3] = {(w[0] - x[1] * t1[0]) - x[2] * t2[0], (w[1] - x[1] * t1[1]) - x[2] * t2[1], (w[2] - x[1] * t1[2]) - x[2] * t2[2]};
+            const double lg = sqrt(plane_dot(g, g));
+            if (!isfinite(lg) || !(lg > 0.0)) stats->status = 2;
+            else {
+                const double nn[3] = {g[0] / lg, g[1] / lg, g[2] / lg};
+                const double gq[3] = {m[0] / N, m[1] / N, m[2] / N};
+                const double d = x[0] / lg - plane_dot(nn, gq);
+                const double unit = (double)spec->span / 65536.0;
+                double Nf[3], af[3];
+                for (int i = 0; i < 3; ++i) {
+                    out.anchor[i] = (float)(A[i] + (gq[i] + d * nn[i]) * unit);
+                    out.normal[i] = (float)nn[i];
+                    Nf[i] = (double)out.normal[i];
+                    af[i] = (double)out.anchor[i];
+                }
+                double t = plane_dot(Nf, af);
+                const double ax[3] = {spec->axis[0], spec->axis[1], spec->axis[2]};
+                if (rule.prior ? plane_dot(Nf, ax) < 0.0 : t > 0.0) {
+                    for (int i = 0; i < 3; ++i) out.normal[i] = -out.normal[i];
+                    t = -t;
+                }
+                out.offset = (float)(0.0 - t);
+                out.votes = (uint32_t)sums[9];
+                double ssr = Sss - ((x[0] * Ss + x[1] * Sus) + x[2] * Svs);
+                if (!(ssr >= 0.0)) ssr = 0.0;
+                stats->rms = unit * sqrt(ssr / N);
+                bool ok = isfinite(out.offset) && isfinite(stats->rms) && (out.normal[0] != 0.0f || out.normal[1] != 0.0f || out.normal[2] != 0.0f);
+                for (int i = 0; i < 3; ++i) ok = ok && isfinite(out.normal[i]) && isfinite(out.anchor[i]);
+                if (!ok) stats->status = 2;
+            }
+        }
+        if (stats->status != 0) {
+            out = *plane_in;
+            stats->rms = 0.0;
+        }
+    }
+    *plane_out = out;
+    return true;
+}
+
+bool sgm_plane_fit(sgm_instance* s, const sgm_plane_spec* spec, const void* d_records, size_t capacity, const uint32_t* d_count,
+                   const uint8_t* d_labels, sgm_plane* plane, sgm_plane_stats* stats, int64_t* trace_sums, sgm_plane* trace_planes)
+{
+    sgmd_plane p;
+    if (!s || !spec || !d_records || !plane || !stats) FAIL("sgm_plane_fit: NULL argument");
+    if (sgmd_plane_votes == NULL || sgmd_plane_best == NULL || sgmd_plane_sums == NULL) FAIL("sgm_plane_fit: the planes of a list are not part of this build");
+    if (!plane_list_ready(spec, d_records, capacity, PLANE_MAX_SUMMED, d_count, &p, "sgm_plane_fit")) return false;
+    /* the instance's own: the candidates, the plane that travels, the sums of a round */
+    const size_t cand_bytes = (size_t)PLANE_MAX_K * sizeof(sgm_plane), sum_bytes = PLANE_SUMS * sizeof(int64_t);
+    if (!scratch_then_wait(s, &s->d_plane_work, cand_bytes + sizeof(sgm_plane) + sum_bytes, "the planes of a fit")) return false;
+    char* work = (char*)s->d_plane_work.p;
+    void *d_cand = work, *d_plane = work + cand_bytes, *d_sums = work + cand_bytes + sizeof(sgm_plane);
+    sgm_plane cur;
+    if (sgmd_plane_votes(s->device, s->stream, &p, d_records, capacity, d_count, d_labels, d_cand) != 0 ||
+        sgmd_plane_best(s->device, s->stream, d_cand, p.hypotheses, d_plane) != 0 ||
+        sgmd_d2h_async(s->device, s->stream, &cur, d_plane, sizeof cur) != 0 || sync_streams(s) != 0)
+        return false;
+    if (trace_planes) trace_planes[0] = cur;
+    *plane = cur;
+    *stats = (sgm_plane_stats){0.0, 0u, 0};
+    if (cur.normal[0] == 0.0f && cur.normal[1] == 0.0f && cur.normal[2] == 0.0f) {
+        stats->status = 1;
+        return true;
+    }
+    for (int it = 0; it < spec->iterations; ++it) {
+        int64_t sums[PLANE_SUMS];
+        sgm_plane next;
+        if ((it > 0 && sgmd_h2d_async(s->device, s->stream, d_plane, &cur, sizeof cur) != 0) ||
+            sgmd_plane_sums(s->device, s->stream, &p, d_records, capacity, d_count, d_labels, d_plane, d_sums) != 0 ||
+            sgmd_d2h_async(s->device, s->stream, sums, d_sums, sum_bytes) != 0 || sync_streams(s) != 0)
+            return false;
+        if (trace_sums) memcpy(trace_sums + (size_t)it * PLANE_SUMS, sums, sum_bytes);
+        if (!sgm_plane_solve(spec, sums, &cur, &next, stats)) return false;
+        cur = next;
+        if (trace_planes) trace_planes[it + 1] = cur;
+        if (stats->status != 0) break;
+    }
+    *plane = cur;
     return true;
 }
 

@@ -63,6 +63,14 @@
  *                             6 pixels, pivots above 1e-6) from the identity displaced by the translation TX,TY,TZ (default 0,0,0);
  *                             prints the status, the associated pixels, the rms and the estimated pose source -> model camera, and
  *                             the world -> camera pose sgm_track_world_pose makes of it
+ *            [--plane K,DIST[,SEED[,AX,AY,AZ,MINCOS]] [--plane-labels OUT.pgm]]   extension: with --pinhole, the dominant plane of the
+ *                             frame's cloud list (SGM_ReadCloud's records; --cloud-z-max cuts it too) or, with --volume, of the
+ *                             volume's surface points: sgm_plane_fit with K candidates, half-thickness DIST, the hash seed SEED
+ *                             (default 0), the orientation prior AX,AY,AZ with MINCOS (default none), 4 rounds, at least 3 inliers,
+ *                             pivots above 1e-9, span a quarter of the largest finite |coordinate| of the list; prints the status,
+ *                             the inliers, the rms, the normal and the offset.  --plane-labels (not with --volume) writes a PGM of
+ *                             the image's size, 255 at the cloud pixels sgm_plane_label marks as the plane's.  Without --plane every
+ *                             output file and line is what it was
  *            [--bits N]       extension: images of N = 9..16 bits per sample (SGM_SetPixelBits): LEFT and RIGHT are loaded with
  *                             sgm_load_gray16 (binary PGM with maxval up to 65535, PNG grey of depth 16; 8-bit files are widened
  *                             unshifted) and matched on all their bits.  --bits 0: the smallest N >= 8 that holds the files' maxval.
@@ -441,6 +449,62 @@ static int volume_surface(const sgm_volume_spec* vol, const int32_t* window, con
     return rc;
 }
 
+/* --plane: the dominant plane of a list of n records (sgm_plane_fit) printed, and with labels_path (the records are the cloud's: the
+ * tag names the pixel) the pixels sgm_plane_label marks written as a w x h PGM.  k, seed: K and SEED; opt: -, DIST, -, AX, AY, AZ, MINCOS.  An instance
+ * and page-locked buffers of its own, as above. */
+static int plane_report(int device, const sgm_point* pts, size_t n, int k, uint32_t seed, const float* opt, const char* labels_path, int w, int h)
+{
+    if (device < 0) {
+        const char* e = getenv("SGM_DEVICE");
+        device = (e && *e) ? atoi(e) : 0;
+    }
+    float reach = 0.0f;
+    for (size_t i = 0; i < n; ++i) {
+        const float c[3] = {fabsf(pts[i].x), fabsf(pts[i].y), fabsf(pts[i].z)};
+        for (int k = 0; k < 3; ++k)
+            if (isfinite(c[k]) && c[k] > reach) reach = c[k];
+    }
+    const sgm_plane_spec spec = {k, seed, opt[1], {opt[3], opt[4], opt[5]}, opt[6], reach > 0.0f ? reach / 4.0f : 1.0f,
+                                 4, 3u, 1e-9f};
+    sgm_instance* s = sgm_create(device);
+    if (!s) return -1;
+    sgm_point* d_records = (sgm_point*)sgm_host_alloc(s, (n ? n : 1) * sizeof(sgm_point));
+    uint8_t* d_labels = labels_path ? (uint8_t*)sgm_host_alloc(s, n ? n : 1) : NULL;
+    sgm_plane* d_plane = labels_path ? (sgm_plane*)sgm_host_alloc(s, sizeof(sgm_plane)) : NULL;
+    sgm_plane plane;
+    sgm_plane_stats stats;
+    int rc = -1;
+    if (d_records && (!labels_path || (d_labels && d_plane))) {
+        if (n) memcpy(d_records, pts, n * sizeof(sgm_point));
+        if (sgm_plane_fit(s, &spec, d_records, n, NULL, NULL, &plane, &stats, NULL, NULL)) {
+            printf("plane: status %d, %u inliers, rms %.9g, normal (%.9g, %.9g, %.9g), offset %.9g\n", stats.status, stats.inliers, stats.rms,
+                   plane.normal[0], plane.normal[1], plane.normal[2], plane.offset);
+            rc = 0;
+            if (labels_path) {
+                uint8_t* image = (uint8_t*)calloc((size_t)w * h, 1);
+                memset(d_labels, 0, n ? n : 1);
+                *d_plane = plane;
+                rc = -1;
+                if (image && sgm_plane_label(s, &spec, d_records, n, NULL, d_plane, 1, d_labels) && sgm_synchronize(s)) {
+                    size_t marked = 0;
+                    for (size_t i = 0; i < n; ++i) {
+                        const uint32_t x = pts[i].pixel & 0xFFFFu, y = pts[i].pixel >> 16;
+                        if (d_labels[i] && x < (uint32_t)w && y < (uint32_t)h) { image[(size_t)y * w + x] = 255; ++marked; }
+                    }
+                    printf("plane labels: %zu pixels\n", marked);
+                    rc = sgm_write_pgm(labels_path, image, w, h) == 0 ? 0 : -1;
+                }
+                free(image);
+            }
+        }
+    }
+    sgm_host_free(s, d_records);
+    sgm_host_free(s, d_labels);
+    sgm_host_free(s, d_plane);
+    sgm_destroy(s);
+    return rc;
+}
+
 /* the 8-bit image the map's pixels are those of: the reference view's, as the match saw it (stage 19 / 20 with --rectify, the
  * narrowed image, stage 21 / 22, with more than 8 bits); *owned: what to free afterwards.  NULL: not available */
 static const uint8_t* reference_grey(const uint8_t* left, const uint8_t* right, int right_ref, int rectified, int bits, size_t px,
@@ -507,6 +571,11 @@ int main(int argc, char** argv)
     int32_t volume_window[6] = {0, 0, 0, 0, 0, 0};
     int have_window = 0;
     int32_t volume_distance[2] = {0, 0};
+    float plane_opt[7] = {0, 0, 0, 0, 0, 0, 0};                   /* --plane: -, DIST, -, AX, AY, AZ, MINCOS */
+    int plane_k = 0;
+    uint32_t plane_seed = 0;
+    int have_plane = 0;
+    const char* plane_labels = NULL;
     int have_distance = 0;
     const char* field_path = NULL;
     int have_view = 0;
@@ -585,6 +654,28 @@ int main(int argc, char** argv)
             ++i;
         }
         else if (v && !strcmp(a, "--volume-field")) { field_path = v; ++i; }
+        else if (v && !strcmp(a, "--plane")) {
+            int k = 0;
+            long long seed = 0;                                   /* K and SEED are integers: 64.7 or a seed past 32 bits is refused, not rounded */
+            int got = 0, used = -1;                               /* the fields of the form that takes the whole argument */
+            if (sscanf(v, "%d,%f,%lld,%f,%f,%f,%f%n", &k, &plane_opt[1], &seed, &plane_opt[3], &plane_opt[4], &plane_opt[5], &plane_opt[6], &used) == 7 &&
+                used >= 0 && v[used] == '\0')
+                got = 7;
+            else if (used = -1, sscanf(v, "%d,%f,%lld%n", &k, &plane_opt[1], &seed, &used) == 3 && used >= 0 && v[used] == '\0')
+                got = 3;
+            else if (used = -1, seed = 0, sscanf(v, "%d,%f%n", &k, &plane_opt[1], &used) == 2 && used >= 0 && v[used] == '\0')
+                got = 2;
+            if (got != 7) plane_opt[3] = plane_opt[4] = plane_opt[5] = plane_opt[6] = 0.0f;
+            plane_k = k;
+            plane_seed = (uint32_t)seed;
+            if ((got != 2 && got != 3 && got != 7) || k < 1 || k > 1024 || seed < 0 || seed > 0xFFFFFFFFLL) {
+                fprintf(stderr, "--plane wants K,DIST[,SEED[,AX,AY,AZ,MINCOS]] with integers K 1..1024 and SEED 0..2^32-1\n");
+                return 2;
+            }
+            have_plane = 1;
+            ++i;
+        }
+        else if (v && !strcmp(a, "--plane-labels")) { plane_labels = v; ++i; }
         else if (v && !strcmp(a, "--volume-track")) {
             const int got = sscanf(v, "%d,%f,%f,%f,%f", &view.track_iterations, &view.track_dist_max, &view.track_t[0], &view.track_t[1],
                                    &view.track_t[2]);
@@ -665,6 +756,9 @@ int main(int argc, char** argv)
         fprintf(stderr, "--volume-view ZMIN,ZMAX,STEP[,MINWEIGHT] and --volume-depth / --volume-normals OUT.f32 come together\n");
         return 2;
     }
+    if (have_plane && !have_pinhole) { fprintf(stderr, "--plane needs --pinhole FX,FY,CX,CY,BASELINE,DOFFS\n"); return 2; }
+    if (plane_labels && (!have_plane || volume_path)) { fprintf(stderr, "--plane-labels OUT.pgm needs --plane and is the cloud's: not with --volume\n"); return 2; }
+    if (have_plane && scale) { fprintf(stderr, "--scale does not combine with --plane\n"); return 2; }
     if (volume_path && !have_pinhole) { fprintf(stderr, "--volume needs --pinhole FX,FY,CX,CY,BASELINE,DOFFS\n"); return 2; }
     if (scale && volume_path) { fprintf(stderr, "--scale does not combine with --volume\n"); return 2; }
     if (scale && register_path) { fprintf(stderr, "--scale does not combine with --register-raw (it needs --rectify)\n"); return 2; }
@@ -789,6 +883,21 @@ int main(int argc, char** argv)
         }
         free(pts);
     }
+    if (have_plane && !volume_path) {                             /* the plane of the frame's cloud list */
+        const sgm_cloud_spec spec = {w1, h1, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], pinhole[4], pinhole[5], 0.0f, cloud_z_max, 0};
+        uint32_t offsets[2] = {0, 0};
+        sgm_point* pts = NULL;
+        bool ok = SGM_ReadCloud(&spec, NULL, 0, offsets);
+        if (!ok && offsets[1] > 0) {
+            pts = (sgm_point*)malloc(sizeof(sgm_point) * offsets[1]);
+            ok = pts && SGM_ReadCloud(&spec, pts, offsets[1], offsets);
+        }
+        if (!ok || plane_report(device, pts, offsets[1], plane_k, plane_seed, plane_opt, plane_labels, w1, h1) != 0) {
+            printf("plane unavailable or --plane / --pinhole / --cloud-z-max out of range\n");
+            rc = -1;
+        }
+        free(pts);
+    }
     if (register_path && register_raw(register_path, calib_path, right_ref, device, w1, h1, pinhole, cloud_z_max, register_splat, disp) != 0) {
         printf("registration unavailable, a bad calibration file or --pinhole / --cloud-z-max out of range\n");
         rc = -1;
@@ -807,6 +916,10 @@ int main(int argc, char** argv)
         } else {
             if (!grey) grey = reference_grey(left, right, right_ref, calib_path != NULL, bits, (size_t)w1 * h1, &rect);
             if (!grey || write_ply(volume_path, pts, n, grey, w1) != 0) rc = -1;
+            if (have_plane && plane_report(device, pts, n, plane_k, plane_seed, plane_opt, NULL, w1, h1) != 0) {       /* the plane of the surface points */
+                printf("plane unavailable or --plane out of range\n");
+                rc = -1;
+            }
         }
         free(rect);
         free(pts);

@@ -276,6 +276,52 @@ def track_world_pose(model_pose, rel):
     return out
 
 
+class SGMPlane(C.Structure):
+    """sgm_plane of include/sgm_mi355x.h: 32 bytes; normal . (P - anchor) = 0, offset = -(normal . anchor); all-zero normal: void."""
+    _fields_ = [("normal", C.c_float * 3), ("offset", C.c_float), ("anchor", C.c_float * 3), ("votes", C.c_uint32)]
+
+
+PLANE_DTYPE = np.dtype([("normal", np.float32, (3,)), ("offset", np.float32), ("anchor", np.float32, (3,)), ("votes", np.uint32)])
+
+
+class SGMPlaneSpec(C.Structure):
+    """Field-for-field sgm_plane_spec of include/sgm_mi355x.h: 44 bytes, every field 4 bytes."""
+    _fields_ = [
+        ("hypotheses", C.c_int32), ("seed", C.c_uint32), ("dist", C.c_float), ("axis", C.c_float * 3), ("min_cos", C.c_float),
+        ("span", C.c_float), ("iterations", C.c_int32), ("min_inliers", C.c_uint32), ("min_pivot", C.c_float),
+    ]
+
+
+class SGMPlaneStats(C.Structure):
+    """sgm_plane_stats of include/sgm_mi355x.h: 16 bytes; status 0 ok, 1 too few inliers, 2 degenerate."""
+    _fields_ = [("rms", C.c_double), ("inliers", C.c_uint32), ("status", C.c_int32)]
+
+
+def plane_spec(hypotheses, dist, span, seed=0, axis=(0.0, 0.0, 0.0), min_cos=0.0, iterations=1, min_inliers=3, min_pivot=0.0) -> SGMPlaneSpec:
+    """A sgm_plane_spec: the number of candidate planes of a vote and the seed of the hash that picks them, the inlier half-thickness
+    dist, the orientation prior (axis all zero: none), the length `span` that normalises coordinates before they are quantised, the
+    rounds of SGMInstance.plane_fit and the two thresholds of the solve."""
+    return SGMPlaneSpec(int(hypotheses), int(seed) & 0xFFFFFFFF, dist, (C.c_float * 3)(*axis), min_cos, span, int(iterations),
+                        int(min_inliers), min_pivot)
+
+
+def _plane_record(pl: SGMPlane) -> np.ndarray:
+    return np.frombuffer(bytes(pl), PLANE_DTYPE)[0].copy()
+
+
+def plane_solve(spec: SGMPlaneSpec, sums, plane):
+    """sgm_plane_solve (host only): one round of the fit from the ten sums -> (the stepped plane, a PLANE_DTYPE record, or `plane`
+    where the status is not 0; a dict of inliers, rms and status).  None for a refused call."""
+    sums = np.ascontiguousarray(sums, np.int64).reshape(-1)
+    plane = np.ascontiguousarray(plane, PLANE_DTYPE).reshape(-1)
+    if sums.size != 10 or plane.size != 1:
+        raise ValueError("plane_solve: 10 sums and one plane")
+    out, st = SGMPlane(), SGMPlaneStats()
+    if not load_library().sgm_plane_solve(C.byref(spec), sums.ctypes.data, plane.ctypes.data, C.byref(out), C.byref(st)):
+        return None
+    return _plane_record(out), dict(inliers=int(st.inliers), rms=float(st.rms), status=int(st.status))
+
+
 class SGMScaleSpec(C.Structure):
     """Field-for-field sgm_scale_spec of include/sgm_mi355x.h: 36 bytes, every field 4 bytes."""
     _fields_ = [
@@ -505,6 +551,16 @@ def _load() -> C.CDLL:
         L.sgm_volume_distance.restype = C.c_bool
         L.sgm_volume_distance_field.argtypes = [C.c_void_p] * 5
         L.sgm_volume_distance_field.restype = C.c_bool
+    if hasattr(L, "sgm_plane_votes"):
+        _vp, _sz = C.c_void_p, C.c_size_t
+        L.sgm_plane_votes.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _vp]
+        L.sgm_plane_best.argtypes = [_vp, _vp, C.c_int, _vp]
+        L.sgm_plane_sums.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]
+        L.sgm_plane_label.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, C.c_int, _vp]
+        L.sgm_plane_solve.argtypes = [_vp] * 5
+        L.sgm_plane_fit.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]
+        for name in ("votes", "best", "sums", "label", "solve", "fit"):
+            getattr(L, "sgm_plane_" + name).restype = C.c_bool
     if hasattr(L, "sgm_track_sums"):          # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
         L.sgm_track_sums.argtypes = [C.c_void_p] * 10
         L.sgm_track_sums.restype = C.c_bool
@@ -1470,6 +1526,44 @@ class SGMInstance(_StageReader):
             return None
         out = [dict(pixels=int(st.pixels), rms=float(st.rms), status=int(st.status)) for st in stats]
         return (poses.reshape(src.frames, 12), out, t_sums, t_poses) if trace else (poses.reshape(src.frames, 12), out)
+
+    # ---- planes in a point list (include/sgm_mi355x.h, sgm_plane_spec); device pointers as ints, None = NULL ----
+    def plane_votes(self, spec: SGMPlaneSpec, d_records: int, capacity: int, d_count, d_labels, d_planes: int) -> bool:
+        """sgm_plane_votes: spec.hypotheses candidate planes from hashed triples of the 16-byte records at d_records (the first
+        min(capacity, d_count[0]) of them; d_count None: capacity) and, for each, the exact number of its inliers, into d_planes
+        (sgm_plane [hypotheses], 16-byte aligned).  d_labels (u8 per record, None: none) takes labelled records out.  Asynchronous
+        on `stream`."""
+        return bool(self.lib.sgm_plane_votes(self.handle, C.byref(spec), d_records or None, int(capacity), d_count or None, d_labels or None,
+                                             d_planes or None))
+
+    def plane_best(self, d_planes: int, k: int, d_best: int) -> bool:
+        """sgm_plane_best: the candidate with the most votes (ties: the smallest index; all void: a void plane) into d_best."""
+        return bool(self.lib.sgm_plane_best(self.handle, d_planes or None, int(k), d_best or None))
+
+    def plane_sums(self, spec: SGMPlaneSpec, d_records: int, capacity: int, d_count, d_labels, d_plane: int, d_sums: int) -> bool:
+        """sgm_plane_sums: the ten int64 moments of the inliers of the plane at d_plane into d_sums (8-byte aligned).  Asynchronous."""
+        return bool(self.lib.sgm_plane_sums(self.handle, C.byref(spec), d_records or None, int(capacity), d_count or None, d_labels or None,
+                                            d_plane or None, d_sums or None))
+
+    def plane_label(self, spec: SGMPlaneSpec, d_records: int, capacity: int, d_count, d_plane: int, label: int, d_labels: int) -> bool:
+        """sgm_plane_label: `label` (1..255) into d_labels[r] of every unlabelled inlier of the plane at d_plane.  Asynchronous."""
+        return bool(self.lib.sgm_plane_label(self.handle, C.byref(spec), d_records or None, int(capacity), d_count or None, d_plane or None,
+                                             int(label), d_labels or None))
+
+    def plane_fit(self, spec: SGMPlaneSpec, d_records: int, capacity: int, d_count=None, d_labels=None, trace: bool = False):
+        """sgm_plane_fit (blocking): vote, take the best candidate, refine it in spec.iterations rounds -> (the plane, a PLANE_DTYPE
+        record; a dict of inliers, rms and status), with trace=True also the sums of every round (int64 [iterations][10]) and the
+        planes before and after every round (PLANE_DTYPE [iterations + 1]).  None for a refused or failed call."""
+        n = max(int(spec.iterations), 0)
+        plane, st = SGMPlane(), SGMPlaneStats()
+        t_sums = np.zeros((n, 10), np.int64) if trace else None
+        t_planes = np.zeros(n + 1, PLANE_DTYPE) if trace else None
+        if not self.lib.sgm_plane_fit(self.handle, C.byref(spec), d_records or None, int(capacity), d_count or None, d_labels or None,
+                                      C.addressof(plane), C.addressof(st), t_sums.ctypes.data if trace else None,
+                                      t_planes.ctypes.data if trace else None):
+            return None
+        out = _plane_record(plane), dict(inliers=int(st.inliers), rms=float(st.rms), status=int(st.status))
+        return out + (t_sums, t_planes) if trace else out
 
     # ---- matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); device pointers as ints, None = NULL ----
     def downscale(self, spec: SGMScaleSpec, d_in: int, d_out: int) -> bool:
