@@ -397,7 +397,12 @@ int           sgm_fused_sweep_rows(const sgm_instance* s);
 /* Batches: after sgm_set_batch(s, n) and the next sgm_initialize / sgm_reset, every sgm_match /
  * sgm_match_device call processes n frames of the same shape stored back to back ([n][H][W] for the
  * images and the disparity output) -- each kernel of the pipeline covers all n frames in one launch,
- * which is how one GPU is filled when frames are small.  n = 1 (default) is the reference behaviour. */
+ * which is how one GPU is filled when frames are small.  n = 1 (default) is the reference behaviour.
+ * n is 1 to 1024; anything else returns false and changes nothing.  The limits of sgm_initialize hold per frame and are unchanged
+ * by the batch (width * height below 2^31, width * height * the padded range below 2^32 - 1); the totals of a batch may pass 2^32
+ * cells, pixels times frames included: every frame base is 64-bit arithmetic, and only device memory bounds the batch
+ * (8 bytes per padded cell of the batch for the path planes, 3 more where S and the cost volume exist).  The entry points that
+ * return both views, and the two-view temporal filter, run their post pass on 2 n maps. */
 bool          sgm_set_batch(sgm_instance* s, int frames);
 /* which frame of the batch sgm_read_stage returns (default 0) */
 void          sgm_select_frame(sgm_instance* s, int frame);

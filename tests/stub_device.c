@@ -17,9 +17,10 @@
 #include <stdlib.h>
 #include <string.h>
 
-/* a log entry: the launcher's name, an int the tests look at, up to two of its pointers, one float (the refinement's L_t[0]) */
+/* a log entry: the launcher's name, an int the tests look at, up to two of its pointers, one float (the refinement's L_t[0]);
+ * allocations, fills and copies also with their whole byte count (the int holds KiB, or the low 32 bits) */
 #define LOG_MAX 4096
-static struct { char name[40]; int arg; const void *a, *b; float f; } g_log[LOG_MAX];
+static struct { char name[40]; int arg; const void *a, *b; float f; size_t bytes; } g_log[LOG_MAX];
 static int g_n;
 static char g_fail_name[40];
 static int g_fail_countdown = -1;
@@ -30,6 +31,7 @@ const char* stub_log_name(int i) { return (i >= 0 && i < g_n) ? g_log[i].name : 
 int stub_log_arg(int i) { return (i >= 0 && i < g_n) ? g_log[i].arg : -1; }
 const void* stub_log_ptr(int i, int second) { return (i >= 0 && i < g_n) ? (second ? g_log[i].b : g_log[i].a) : NULL; }
 float stub_log_float(int i) { return (i >= 0 && i < g_n) ? g_log[i].f : -1.0f; }
+size_t stub_log_bytes(int i) { return (i >= 0 && i < g_n) ? g_log[i].bytes : 0; }
 /* the nth (0-based) call of launcher `name` from now on returns an error */
 void stub_fail_at(const char* name, int nth) { snprintf(g_fail_name, sizeof g_fail_name, "%s", name); g_fail_countdown = nth; }
 
@@ -42,19 +44,26 @@ static int refused_locked(const char* name)
     }
     return 0;
 }
-static int note_locked(const char* name, int arg, const void* a, const void* b, float f)
+static int note_locked(const char* name, int arg, const void* a, const void* b, float f, size_t bytes)
 {
     if (g_n < LOG_MAX) {
         snprintf(g_log[g_n].name, sizeof g_log[g_n].name, "%s", name);
-        g_log[g_n].arg = arg; g_log[g_n].a = a; g_log[g_n].b = b; g_log[g_n].f = f;
+        g_log[g_n].arg = arg; g_log[g_n].a = a; g_log[g_n].b = b; g_log[g_n].f = f; g_log[g_n].bytes = bytes;
         ++g_n;
     }
     return refused_locked(name);
 }
+static int note_bytes(const char* name, size_t bytes, const void* a, const void* b)
+{
+    pthread_mutex_lock(&g_mu);
+    const int rc = note_locked(name, (int)bytes, a, b, 0.0f, bytes);
+    pthread_mutex_unlock(&g_mu);
+    return rc;
+}
 static int note_ptrs(const char* name, int arg, const void* a, const void* b, float f)
 {
     pthread_mutex_lock(&g_mu);
-    const int rc = note_locked(name, arg, a, b, f);
+    const int rc = note_locked(name, arg, a, b, f, 0);
     pthread_mutex_unlock(&g_mu);
     return rc;
 }
@@ -84,7 +93,7 @@ int stub_alloc_count(void) { return g_alloc_count; }
 static int note_alloc(const char* name, size_t n, int logged)
 {
     pthread_mutex_lock(&g_mu);
-    const int rc = logged ? note_locked(name, (int)(n >> 10), NULL, NULL, 0.0f) : refused_locked(name);
+    const int rc = logged ? note_locked(name, (int)(n >> 10), NULL, NULL, 0.0f, n) : refused_locked(name);
     ++g_alloc_count;
     const int refused = g_alloc_countdown >= 0 && g_alloc_countdown-- == 0;
     pthread_mutex_unlock(&g_mu);
@@ -108,10 +117,10 @@ int sgmd_host_is_pinned(int o, const void* p, size_t n)
         if (p && g_pinned[i] == p) return 1;
     return 0;
 }
-int sgmd_h2d_async(int o, void* st, void* d, const void* s, size_t n) { (void)o; (void)st; if (n <= (1u << 20)) memcpy(d, s, n); return note("h2d", (int)n); }
+int sgmd_h2d_async(int o, void* st, void* d, const void* s, size_t n) { (void)o; (void)st; if (n <= (1u << 20)) memcpy(d, s, n); return note_bytes("h2d", n, NULL, NULL); }
 /* (logged with its destination and source: the tests follow a staged result from the staging buffer to the caller) */
 int sgmd_d2h_async(int o, void* st, void* d, const void* s, size_t n)
-{ (void)o; (void)st; if (n <= (1u << 20)) memcpy(d, s, n); return note_ptrs("d2h", (int)n, d, s, 0.0f); }
+{ (void)o; (void)st; if (n <= (1u << 20)) memcpy(d, s, n); return note_bytes("d2h", n, d, s); }
 int sgmd_plane_rows_copy(int o, void* st, void* planes, size_t pb, size_t ro, size_t rb, const int* dirs, int nd, int frames, void* buf, int to_buf)
 {
     (void)o; (void)st;
@@ -125,17 +134,17 @@ int sgmd_plane_rows_copy(int o, void* st, void* planes, size_t pb, size_t ro, si
             }
     return note(to_buf ? "rows_out" : "rows_in", nd * frames);
 }
-int sgmd_d2d_async(int o, void* st, void* d, const void* s, size_t n) { (void)o; (void)st; if (n <= (1u << 20)) memmove(d, s, n); return note("d2d", (int)n); }
+int sgmd_d2d_async(int o, void* st, void* d, const void* s, size_t n) { (void)o; (void)st; if (n <= (1u << 20)) memmove(d, s, n); return note_bytes("d2d", n, NULL, NULL); }
 int sgmd_d2d_2d_async(int o, void* st, void* d, size_t dp, const void* s, size_t sp, size_t w, size_t rows)
 {
     (void)o; (void)st;
     if ((rows ? (rows - 1) * (dp > sp ? dp : sp) : 0) + w <= (1u << 20))
         for (size_t r = 0; r < rows; ++r) memmove((char*)d + r * dp, (const char*)s + r * sp, w);
-    return note("d2d_2d", (int)(w * rows));
+    return note_bytes("d2d_2d", w * rows, NULL, NULL);
 }
 /* (logged with its destination: the tests look for the fill that covers a given buffer) */
 int sgmd_memset_async(int o, void* st, void* d, int v, size_t n)
-{ (void)o; (void)st; if (n <= (1u << 20)) memset(d, v, n); return note_ptrs("memset", (int)n, d, NULL, 0.0f); }
+{ (void)o; (void)st; if (n <= (1u << 20)) memset(d, v, n); return note_bytes("memset", n, d, NULL); }
 
 int sgmd_timer_create(int o, void** t, int n) { (void)o; (void)n; *t = malloc(8); return 0; }
 void sgmd_timer_destroy(int o, void* t) { (void)o; free(t); }
