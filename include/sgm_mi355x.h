@@ -1179,6 +1179,96 @@ bool sgm_plane_fit(sgm_instance* s, const sgm_plane_spec* spec, const void* d_re
                    const uint8_t* d_labels, sgm_plane* plane /* HOST out */, sgm_plane_stats* stats /* HOST out */,
                    int64_t* trace_sums /* HOST [iterations][10], or NULL */, sgm_plane* trace_planes /* HOST [iterations + 1], or NULL */);
 
+/* ---- objects in the TSDF volume: connected components of its voxel lattice ----
+ * Extension, "parity unpinned by the reference"; defined here and restated by tests/components_ref.py.  The plane section ends with the
+ * obstacle points; what a planner, a tracker or a viewer asks next is which of them belong together: how many objects stand on the
+ * floor, where they are and how large, which mesh vertices belong to which, whether one free cell can be reached from another.
+ * sgm_volume_components labels the connected components of a set of voxels and lists them; sgm_volume_component_of carries the
+ * result to a list the volume produced.  Exact integers throughout, tolerance 0, the same bytes on every run.
+ *
+ * The set.  For a voxel word, w = word >> 16 and tq = (int16_t)word, as in the distance section; a voxel is observed iff
+ * w >= min_weight.  A voxel is IN THE SET iff no plane excludes it (below) and
+ *   set == 0 (occupied)   it is observed and tq < 0,   or
+ *   set == 1 (free)       it is observed and tq >= 0,  or
+ *   unknown == 1          it is not observed           (with either set)
+ * Plane exclusion: how the floor sgm_plane_fit found is taken out, so that the things standing on it fall apart.  The spec carries
+ * `planes` (0..4) host sgm_plane values and a clearance each.  Per axis the voxel centre is C = o + ((float)i + 0.5f) * voxel, the float
+ * the integration uses, and
+ *   s = ((n0*(Cx - a0) + n1*(Cy - a1)) + n2*(Cz - a2))       the plane section's vote arithmetic: float32, no contraction
+ * A non-void plane excludes the voxel iff s is finite (by its bits) and s <= clearance: the plane's slab and everything behind it.
+ * A void plane (an all-zero normal, either sign of zero) excludes nothing.
+ * Neighbours.  connectivity 6: the voxels one step away along one axis; 26: along one, two or three axes.  Neighbours exist inside
+ * the grid only.  The components are the classes of the symmetric relation "neighbours, both in the set".
+ *
+ * Outputs, with n the voxel index of the volume.
+ *   d_labels   one uint32_t per voxel.  With `first` the smallest voxel index of the voxel's component and `size` its number of
+ *              voxels, the word is first + 1 if the voxel is in the set and size >= min_voxels, and 0 otherwise.  Every word is
+ *              written whatever the array held.
+ *   d_objects  sgm_component records, one per surviving component (size >= min_voxels) in increasing order of first; only the first
+ *              `capacity` records are written and nothing beyond min(C, capacity) records.  lo and hi are the inclusive box of the
+ *              component in i, j, k; sum holds the sums of i, of j and of k over its voxels.
+ *   d_counts   [0] = C, the surviving components, also where C > capacity; [1] = the components before the min_voxels filter.
+ * capacity == 0 with d_objects == NULL asks for labels and counts alone.
+ *
+ * sgm_volume_component_of.  d_records are 16-byte records with the id in the last word; id_kinds 4 (sgm_surface_point, id = n*4 + a)
+ * or 8 (sgm_mesh_vertex, id = n*8 + e) as in sgm_volume_colors, and record r is handled iff r < records_capacity and
+ * (d_records_count == NULL or r < d_records_count[0]); nothing is written for the others.  The label of a record is that of its voxel
+ * n; where that is 0, the label of the other end of its edge (the (dx,dy,dz) table of the mesh contract), where that voxel is inside
+ * the grid.  A record whose n is outside the volume or whose kind does not exist has label 0.  d_index[r] is 1 plus the position in
+ * d_objects[0 .. min(C, capacity)) of the object whose first + 1 equals the label -- found by binary search, the list is sorted --
+ * and 0 where the label is 0 or the object was not written.  d_labels, d_objects, capacity and d_counts are those of the components
+ * call, so it can be queued straight behind sgm_volume_mesh and sgm_volume_components with their device count words.
+ * sgm_component_metric (host only).  lo[a] = origin[a] + (float)obj->lo[a] * voxel and hi[a] = origin[a] + (float)(obj->hi[a] + 1) *
+ * voxel, float32 as written; centroid[a] = (float)(origin[a] + (sum[a] / voxels + 0.5) * voxel) computed in double (the quotient of
+ * the two integers as doubles) and rounded once.  Only spec->voxel and spec->origin are read; an output that is NULL is left out, and
+ * with voxels == 0 (no record the device writes) the quotient is taken as 0.
+ * sgm_volume_components_bytes (host only): the size of d_labels, 4 * nx*ny*nz, 0 for a refused spec.
+ *
+ * How it runs.  Union-find over d_labels itself, which serves the call as its working array: a workgroup labels a tile of 64 x 8 x 8
+ * voxels in LDS (one wave per x-row: runs come from a ballot, unions only between the runs of neighbouring rows), voxels on tile
+ * faces union roots across tiles in global memory (parents only ever decrease, so every find ends), then the sizes, the filter, the
+ * ordered compaction of the surviving roots (count per tile, one scan, emit) and a statistics pass that reduces a tile on chip
+ * before it touches a record.  Integer atomics only; no workgroup waits for another.
+ * Scratch: 4 * nx*ny*nz + 12 * ceil(nx*ny*nz / 2048) + 24 * min(capacity, nx*ny*nz) bytes of the instance's own, reserved at the
+ * first call and grown when a later call needs more; it depends on the arguments alone, never on a value read back, and the call
+ * does not block.  An instance that never calls these entry points allocates and launches exactly what it did before.
+ *
+ * The device calls are asynchronous on sgm_stream(s) and ordered as sgm_volume_points is.  false, nothing queued and one
+ * "sgm_mi355x: <entry point>: ..." line on stderr: a NULL pointer other than d_objects with capacity 0 and d_records_count; a volume
+ * spec that sgm_volume_integrate refuses; min_weight outside 1..65535; set or unknown other than 0 or 1; connectivity other than 6 or
+ * 26; min_voxels < 1; planes outside 0..4; a plane (normal, offset, anchor) or clearance that is not finite; id_kinds other than 4 or
+ * 8, and with 8 a volume over the mesh's 2^27 voxels; records_capacity above 2^32; a pointer that is not aligned (records 16 bytes,
+ * objects 8, words 4); an output that overlaps an input or another output; a build without the kernels.  records_capacity == 0 is a
+ * successful no-op.
+ * Not part of it: 18-connectivity, incremental relabelling after an integration, tracking object identities across frames or window
+ * shifts, oriented boxes, clustering of unorganised point lists. */
+typedef struct {            /* 168 bytes, every field 4 bytes, no padding */
+    uint32_t  min_weight;   /* 1..65535: a voxel is observed iff w >= min_weight */
+    int32_t   set;          /* 0: the occupied voxels; 1: the free ones */
+    int32_t   unknown;      /* 1: unobserved voxels belong to the set as well */
+    int32_t   connectivity; /* 6 or 26 */
+    uint32_t  min_voxels;   /* >= 1: smaller components get label 0 and no record */
+    int32_t   planes;       /* 0..4: how many of plane[] and clearance[] are in effect */
+    sgm_plane plane[4];     /* finite; only normal and anchor take part; a void plane excludes nothing */
+    float     clearance[4]; /* finite: a voxel with s <= clearance is excluded */
+} sgm_component_spec;
+typedef struct {            /* 48 bytes */
+    uint32_t first;         /* the smallest voxel index of the component: its label is first + 1 */
+    uint32_t voxels;
+    uint16_t lo[3], hi[3];  /* the inclusive box in i, j, k */
+    uint32_t reserved;      /* 0 */
+    uint64_t sum[3];        /* the sums of i, j, k over the component's voxels */
+} sgm_component;
+size_t sgm_volume_components_bytes(const sgm_volume_spec* spec);   /* host only; 4 * nx*ny*nz, 0 for a refused spec */
+bool sgm_volume_components(sgm_instance* s, const sgm_volume_spec* spec, const sgm_component_spec* comp, const uint32_t* d_voxels,
+                           uint32_t* d_labels, sgm_component* d_objects /* 8-byte aligned, or NULL */, size_t capacity,
+                           uint32_t* d_counts /* [2]: surviving components, all components */);
+bool sgm_volume_component_of(sgm_instance* s, const sgm_volume_spec* spec, const uint32_t* d_labels, const sgm_component* d_objects,
+                             size_t capacity, const uint32_t* d_counts, const void* d_records /* 16-byte records, id in the last word */,
+                             size_t records_capacity, const uint32_t* d_records_count /* device u32, may be NULL */,
+                             int id_kinds /* 8 or 4 */, uint32_t* d_index /* u32 [records_capacity] */);
+void sgm_component_metric(const sgm_volume_spec* spec, const sgm_component* obj, float lo[3], float hi[3], float centroid[3]); /* host only */
+
 /* ---- matching at half or quarter scale, re-search at full resolution ----
  * Extension, "parity unpinned by the reference" (it has no such step); defined here and restated by tests/scaled_ref.py.  A match at
  * 1/f scale pays for f^3 fewer cells of W x H x D for the same metric range; the result is brought back to the full grid by a guided

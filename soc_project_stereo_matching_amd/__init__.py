@@ -15,6 +15,7 @@ from .sgm import (SGM, SGMInstance, SGMOption, default_option, library_path, loa
                   SGMDistanceSpec, DISTANCE_FAR, distance_spec, volume_distance_bytes,
                   SGMTrackSpec, SGMTrackStats, track_spec, track_solve, track_world_pose,
                   SGMPlane, SGMPlaneSpec, SGMPlaneStats, PLANE_DTYPE, plane_spec, plane_solve,
+                  SGMComponentSpec, SGMComponent, COMPONENT_DTYPE, component_spec, volume_components_bytes, component_metric,
                   rectify_valid_mask, STAGE_NARROW_LEFT, STAGE_NARROW_RIGHT, SGMScaleSpec, scale_spec, scaled_shape,
                   SGMTemporalSpec, temporal_spec, TEMPORAL_CLASSES, STAGE_TEMPORAL_IN, STAGE_TEMPORAL_VALUE, STAGE_TEMPORAL_BITS,
                   debug_guard_check)
@@ -28,6 +29,7 @@ __all__ = ["SGM", "SGMInstance", "SGMOption", "default_option", "library_path", 
            "SGMDistanceSpec", "DISTANCE_FAR", "distance_spec", "volume_distance_bytes",
            "SGMTrackSpec", "SGMTrackStats", "track_spec", "track_solve", "track_world_pose",
            "SGMPlane", "SGMPlaneSpec", "SGMPlaneStats", "PLANE_DTYPE", "plane_spec", "plane_solve",
+           "SGMComponentSpec", "SGMComponent", "COMPONENT_DTYPE", "component_spec", "volume_components_bytes", "component_metric",
            "rectify_valid_mask",
            "STAGE_NARROW_LEFT", "STAGE_NARROW_RIGHT", "SGMScaleSpec", "scale_spec", "scaled_shape", "SGMTemporalSpec", "temporal_spec",
            "TEMPORAL_CLASSES", "STAGE_TEMPORAL_IN", "STAGE_TEMPORAL_VALUE", "STAGE_TEMPORAL_BITS", "debug_guard_check", "SGMStream", "frames_of_rank", "match_sharded"]

@@ -408,6 +408,28 @@ int sgmd_plane_sums(int ord, void* stream, const sgmd_plane* p, const void* reco
 int sgmd_plane_label(int ord, void* stream, const sgmd_plane* p, const void* records, size_t capacity, const void* count,
                      const void* plane, int label, void* labels);
 
+/* Extension (parity unpinned by the reference), connected components of the volume's voxel lattice (include/sgm_mi355x.h, the
+ * components section); sgm_components.hip.  v: the volume as the host validated it; cs: the spec as the host validated it (the planes
+ * as normal, anchor and clearance; a void plane is skipped).  sgmd_volume_components: labels u32 [nz][ny][nx], the call's working array
+ * and its result; objects: 48-byte records, 8-byte aligned, or NULL with capacity 0; counts u32 [2]; scratch:
+ * sgmd_components_scratch_bytes(nx, ny, nz, capacity) bytes, 8-byte aligned, which must not be shared with a call still in flight.
+ * Five launches for labels and counts (three where the volume is one tile), three more for the records.  sgmd_volume_component_of: one
+ * launch, no scratch: index[r] for every 16-byte record r < records_capacity (and < records_count[0] where that device word is
+ * given).  sgm_host.c references all three weakly, on their own. */
+typedef struct {
+    unsigned min_weight;
+    int set, unknown, connectivity;
+    unsigned min_voxels;
+    int planes;
+    float normal[4][3], anchor[4][3], clearance[4];
+} sgmd_components;
+size_t sgmd_components_scratch_bytes(int nx, int ny, int nz, size_t capacity);
+int sgmd_volume_components(int ord, void* stream, const sgmd_volume* v, const sgmd_components* cs, const void* voxels, void* scratch,
+                           void* labels, void* objects, size_t capacity, void* counts);
+int sgmd_volume_component_of(int ord, void* stream, const sgmd_volume* v, const void* labels, const void* objects, size_t capacity,
+                             const void* counts, const void* records, size_t records_capacity, const void* records_count, int id_kinds,
+                             void* index);
+
 /* Extension (parity unpinned by the reference), matching at 1/f scale (include/sgm_mi355x.h, sgm_scale_spec); sgm_scale.hip.
  * c: the spec as the host validated it (W, H: FULL resolution; the low resolution is W / f x H / f).  sgmd_downscale: the f x f box
  * mean with rounding of one image stack, u8 (bits == 8) or u16 [B][H][W] -> [B][H / f][W / f]; trailing rows and columns are not

@@ -170,6 +170,9 @@ struct sgm_instance {
     /* planes in a point list (sgm_plane_fit; allocated at its first call): 1024 candidates, the plane that travels between the
      * rounds and the ten sums of a round */
     sgm_buf d_plane_work;
+    /* connected components of the volume (sgm_volume_components; allocated at its first call): the sizes, the compaction's tile words
+     * and the boxes of the objects */
+    sgm_buf d_components_scratch;
     /* matching at 1/f scale (sgm_match_scaled; allocated at its first use): the downscaled views, the census planes of the
      * FULL-resolution views with the narrowed images sgmd_census16 writes beside them, and for the host-pointer form the full
      * images, the full map and their page-locked staging */
@@ -222,7 +225,7 @@ static const struct { size_t offset; bool pinned; } k_buffers[] = {
     DEVICE_BUF(d_sc_g8_r), DEVICE_BUF(d_sc_full_l), DEVICE_BUF(d_sc_full_r), DEVICE_BUF(d_sc_disp), PINNED_BUF(h_sc_l), PINNED_BUF(h_sc_r),
     PINNED_BUF(h_sc_disp), DEVICE_BUF(d_tp_value), DEVICE_BUF(d_tp_bits), DEVICE_BUF(d_tp_stats), DEVICE_BUF(d_tp_pre),
     DEVICE_BUF(d_tp_scratch), DEVICE_BUF(d_register_keys), DEVICE_BUF(d_volume_scratch), DEVICE_BUF(d_mesh_scratch), DEVICE_BUF(d_track_sums),
-    DEVICE_BUF(d_plane_work),
+    DEVICE_BUF(d_plane_work), DEVICE_BUF(d_components_scratch),
 };
 #define UPSUM_DEFAULT 0       /* the fused last sweep is opt-in (SGM_UPSUM=1) until it beats the separate kernels in the timed pipeline */
 #define RESULT_CHUNKS 4
@@ -2738,6 +2741,103 @@ bool sgm_volume_distance_field(sgm_instance* s, const sgm_volume_spec* spec, con
         FAIL("sgm_volume_distance_field: the output overlaps an input");
     if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
     return sgmd_volume_distance_field(s->device, s->stream, &v, d_out2, d_in2, d_field) == 0;
+}
+
+/* ------------------------------------------------------------------ connected components of the volume (extension) */
+
+/* The launchers of sgm_components.hip, weak symbols of their own: a host built without them keeps the volume and refuses the calls */
+#pragma weak sgmd_components_scratch_bytes
+#pragma weak sgmd_volume_components
+#pragma weak sgmd_volume_component_of
+
+size_t sgm_volume_components_bytes(const sgm_volume_spec* spec)
+{
+    sgmd_volume v;
+    if (!spec || !volume_spec_valid(spec, &v)) return 0;
+    return volume_bytes(&v);
+}
+
+bool sgm_volume_components(sgm_instance* s, const sgm_volume_spec* spec, const sgm_component_spec* comp, const uint32_t* d_voxels,
+                           uint32_t* d_labels, sgm_component* d_objects, size_t capacity, uint32_t* d_counts)
+{
+    sgmd_volume v;
+    sgmd_components c;
+    if (!s || !spec || !comp || !d_voxels || !d_labels || !d_counts || (!d_objects && capacity)) FAIL("sgm_volume_components: NULL argument");
+    if (sgmd_volume_components == NULL || sgmd_components_scratch_bytes == NULL)
+        FAIL("sgm_volume_components: the components are not part of this build");
+    if (!volume_spec_valid(spec, &v)) FAIL("sgm_volume_components: the volume spec is outside its ranges");
+    if (comp->min_weight < 1u || comp->min_weight > 65535u) FAIL("sgm_volume_components: a min_weight of %u (1..65535)", comp->min_weight);
+    if (comp->set < 0 || comp->set > 1 || comp->unknown < 0 || comp->unknown > 1)
+        FAIL("sgm_volume_components: set %d and unknown %d (0 or 1 each)", comp->set, comp->unknown);
+    if (comp->connectivity != 6 && comp->connectivity != 26) FAIL("sgm_volume_components: a connectivity of %d (6 or 26)", comp->connectivity);
+    if (comp->min_voxels < 1u) FAIL("sgm_volume_components: min_voxels of 0 (at least 1)");
+    if (comp->planes < 0 || comp->planes > 4) FAIL("sgm_volume_components: %d planes (0..4)", comp->planes);
+    c = (sgmd_components){comp->min_weight, comp->set, comp->unknown, comp->connectivity, comp->min_voxels, comp->planes, {{0}}, {{0}}, {0}};
+    for (int q = 0; q < comp->planes; ++q) {
+        const sgm_plane* pl = &comp->plane[q];
+        bool finite = isfinite(pl->offset) && isfinite(comp->clearance[q]);
+        for (int a = 0; a < 3; ++a) finite = finite && isfinite(pl->normal[a]) && isfinite(pl->anchor[a]);
+        if (!finite) FAIL("sgm_volume_components: plane %d or its clearance is not finite", q);
+        for (int a = 0; a < 3; ++a) { c.normal[q][a] = pl->normal[a]; c.anchor[q][a] = pl->anchor[a]; }
+        c.clearance[q] = comp->clearance[q];
+    }
+    if (!aligned_to(d_voxels, sizeof(uint32_t)) || !aligned_to(d_labels, sizeof(uint32_t)) || !aligned_to(d_counts, sizeof(uint32_t)) ||
+        !aligned_to(d_objects, 8))
+        FAIL("sgm_volume_components: a pointer is not aligned (the objects to 8 bytes, the others to their element)");
+    const size_t vol_bytes = volume_bytes(&v), n = vol_bytes / sizeof(uint32_t);
+    /* (no more than one object per voxel can be written, whatever the capacity says) */
+    const size_t obj_bytes = (capacity < n ? capacity : n) * sizeof(sgm_component), cnt_bytes = 2 * sizeof(uint32_t);
+    if (ranges_overlap(d_labels, vol_bytes, d_voxels, vol_bytes) || ranges_overlap(d_objects, obj_bytes, d_voxels, vol_bytes) ||
+        ranges_overlap(d_counts, cnt_bytes, d_voxels, vol_bytes) || ranges_overlap(d_objects, obj_bytes, d_labels, vol_bytes) ||
+        ranges_overlap(d_counts, cnt_bytes, d_labels, vol_bytes) || ranges_overlap(d_counts, cnt_bytes, d_objects, obj_bytes))
+        FAIL("sgm_volume_components: an output overlaps the volume or another output");
+    if (!scratch_then_wait(s, &s->d_components_scratch, sgmd_components_scratch_bytes(v.nx, v.ny, v.nz, capacity), "the components' scratch"))
+        return false;
+    return sgmd_volume_components(s->device, s->stream, &v, &c, d_voxels, s->d_components_scratch.p, d_labels, d_objects, capacity,
+                                  d_counts) == 0;
+}
+
+bool sgm_volume_component_of(sgm_instance* s, const sgm_volume_spec* spec, const uint32_t* d_labels, const sgm_component* d_objects,
+                             size_t capacity, const uint32_t* d_counts, const void* d_records, size_t records_capacity,
+                             const uint32_t* d_records_count, int id_kinds, uint32_t* d_index)
+{
+    sgmd_volume v;
+    if (!s || !spec || !d_labels || !d_counts || (!d_objects && capacity) || (records_capacity && (!d_records || !d_index)))
+        FAIL("sgm_volume_component_of: NULL argument");
+    if (sgmd_volume_component_of == NULL) FAIL("sgm_volume_component_of: the components are not part of this build");
+    if (!volume_spec_valid(spec, &v)) FAIL("sgm_volume_component_of: the volume spec is outside its ranges");
+    if (id_kinds != 4 && id_kinds != 8) FAIL("sgm_volume_component_of: id_kinds of %d (8: sgm_mesh_vertex, 4: sgm_surface_point)", id_kinds);
+    const size_t vol_bytes = volume_bytes(&v), n = vol_bytes / sizeof(uint32_t);
+    if (id_kinds == 8 && n > MESH_MAX_VOXELS) FAIL("sgm_volume_component_of: %zu voxels (at most 2^27 for the ids of a mesh)", n);
+    if (!aligned_to(d_labels, sizeof(uint32_t)) || !aligned_to(d_objects, 8) || !aligned_to(d_counts, sizeof(uint32_t)) ||
+        !aligned_to(d_records, 16) || !aligned_to(d_records_count, sizeof(uint32_t)) || !aligned_to(d_index, sizeof(uint32_t)))
+        FAIL("sgm_volume_component_of: a pointer is not aligned (the records to 16 bytes, the objects to 8, the others to their element)");
+    if (records_capacity > ((size_t)1 << 32))
+        FAIL("sgm_volume_component_of: a capacity of %zu records (ids are 32 bits: at most 2^32)", records_capacity);
+    const void* const ins[] = {d_labels, d_objects, d_counts, d_records, d_records_count};
+    const size_t in_bytes[] = {vol_bytes, (capacity < n ? capacity : n) * sizeof(sgm_component), 2 * sizeof(uint32_t), records_capacity * 16,
+                               sizeof(uint32_t)};
+    for (int i = 0; i < 5; ++i)
+        if (ranges_overlap(d_index, records_capacity * sizeof(uint32_t), ins[i], in_bytes[i]))
+            FAIL("sgm_volume_component_of: the output overlaps an input");
+    if (records_capacity == 0) return true;
+    /* behind the list's own call and the components call on this stream, and behind the last match as those calls are */
+    if (!scratch_then_wait(s, NULL, 0, NULL)) return false;
+    return sgmd_volume_component_of(s->device, s->stream, &v, d_labels, d_objects, capacity, d_counts, d_records, records_capacity,
+                                    d_records_count, id_kinds, d_index) == 0;
+}
+
+void sgm_component_metric(const sgm_volume_spec* spec, const sgm_component* obj, float lo[3], float hi[3], float centroid[3])
+{
+    if (!spec || !obj) return;
+    for (int a = 0; a < 3; ++a) {
+        if (lo) lo[a] = spec->origin[a] + (float)obj->lo[a] * spec->voxel;
+        if (hi) hi[a] = spec->origin[a] + (float)(obj->hi[a] + 1) * spec->voxel;
+        if (centroid) {
+            const double mean = obj->voxels ? (double)obj->sum[a] / (double)obj->voxels : 0.0;
+            centroid[a] = (float)((double)spec->origin[a] + (mean + 0.5) * (double)spec->voxel);
+        }
+    }
 }
 
 /* ------------------------------------------------------------------ frame-to-model tracking (extension) */

@@ -58,6 +58,14 @@
  *                             sides (min_weight 1, as --volume-ply; UNKNOWN 1 counts unobserved voxels as obstacles, default 0),
  *                             then sgm_volume_distance_field, written as raw float32, x fastest, behind 16 bytes of header: nx, ny,
  *                             nz as int32 and voxel as float32.  Without it every output file is what it was
+ *            [--volume-objects MINVOXELS[,CONN[,CLEARANCE]]]   extension: with --volume, the objects of the fused volume (of the
+ *                             window, with --volume-window): sgm_volume_components on the occupied voxels (min_weight 1, as
+ *                             --volume-ply) with CONN 6 (default) or 26 neighbours, components below MINVOXELS voxels dropped.  With
+ *                             --plane the plane it fits to the surface points is excluded first, with CLEARANCE (default 0, units of
+ *                             BASELINE): the floor goes and what stands on it falls apart.  Prints the counts and one line per object
+ *                             with its voxels, metric box and centroid (sgm_component_metric); --volume-mesh then gains one more
+ *                             vertex property, uint object: 1 + the object's line, 0 for none (sgm_volume_component_of).  Without it
+ *                             every output file and line is what it was
  *            [--volume-track ITER,DISTMAX[,TX,TY,TZ]]   extension: with --volume and --volume-view, the frame tracked against that
  *                             render (sgm_track: ITER rounds, gate DISTMAX, span the middle of the march (ZMIN + ZMAX) / 2, at least
  *                             6 pixels, pivots above 1e-6) from the identity displaced by the translation TX,TY,TZ (default 0,0,0);
@@ -283,9 +291,12 @@ static int volume_render(sgm_instance* s, const sgm_volume_spec* vol, const volu
 
 /* --volume-mesh: the volume as a triangle mesh, sized by a counts-only call, written as a binary little-endian PLY.  d_colors !=
  * NULL (--volume-color): sgm_volume_colors of the vertices, queued behind the mesh with its counts, as uchar red green blue */
+typedef struct { uint32_t* d_labels; sgm_component* d_objects; size_t capacity; uint32_t* d_counts; } object_list;
+
 static int volume_mesh_ply(sgm_instance* s, const sgm_volume_spec* vol, const uint32_t* d_voxels, const uint32_t* d_colors,
-                           uint32_t min_weight, const char* path)
+                           uint32_t min_weight, const object_list* objects, const char* path)
 {
+    uint32_t* d_index = NULL;
     uint32_t* d_counts = (uint32_t*)sgm_host_alloc(s, 2 * sizeof(uint32_t));
     sgm_mesh_vertex* d_vertices = NULL;
     sgm_mesh_triangle* d_triangles = NULL;
@@ -296,21 +307,25 @@ static int volume_mesh_ply(sgm_instance* s, const sgm_volume_spec* vol, const ui
         d_vertices = nv ? (sgm_mesh_vertex*)sgm_host_alloc(s, nv * sizeof(sgm_mesh_vertex)) : NULL;
         d_triangles = nt ? (sgm_mesh_triangle*)sgm_host_alloc(s, nt * sizeof(sgm_mesh_triangle)) : NULL;
         d_rgba = (d_colors && nv) ? (uint32_t*)sgm_host_alloc(s, nv * sizeof(uint32_t)) : NULL;
-        if ((d_vertices || !nv) && (d_triangles || !nt) && (d_rgba || !d_colors || !nv) &&
+        d_index = (objects && nv) ? (uint32_t*)sgm_host_alloc(s, nv * sizeof(uint32_t)) : NULL;
+        if ((d_vertices || !nv) && (d_triangles || !nt) && (d_rgba || !d_colors || !nv) && (d_index || !objects || !nv) &&
             sgm_volume_mesh(s, vol, d_voxels, min_weight, d_vertices, nv, d_triangles, nt, d_counts) &&
-            (!d_colors || sgm_volume_colors(s, vol, d_voxels, d_colors, d_vertices, nv, d_counts, 8, d_rgba)) && sgm_synchronize(s) &&
+            (!d_colors || sgm_volume_colors(s, vol, d_voxels, d_colors, d_vertices, nv, d_counts, 8, d_rgba)) &&
+            (!objects || sgm_volume_component_of(s, vol, objects->d_labels, objects->d_objects, objects->capacity, objects->d_counts,
+                                                 d_vertices, nv, d_counts, 8, d_index)) && sgm_synchronize(s) &&
             d_counts[0] == nv && d_counts[1] == nt) {
             printf("volume mesh: %zu vertices, %zu triangles\n", nv, nt);
             FILE* f = fopen(path, "wb");
             if (f) {
-                fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n%s"
+                fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n%s%s"
                            "element face %zu\nproperty list uchar uint vertex_indices\nend_header\n", nv,
-                        d_colors ? "property uchar red\nproperty uchar green\nproperty uchar blue\n" : "", nt);
+                        d_colors ? "property uchar red\nproperty uchar green\nproperty uchar blue\n" : "", objects ? "property uint object\n" : "", nt);
                 size_t put = 0;
                 for (size_t i = 0; i < nv; ++i) {
                     const uint8_t rgb[3] = {(uint8_t)(d_colors ? d_rgba[i] : 0u), (uint8_t)(d_colors ? d_rgba[i] >> 8 : 0u),
                                             (uint8_t)(d_colors ? d_rgba[i] >> 16 : 0u)};
-                    put += fwrite(&d_vertices[i], sizeof(float), 3, f) == 3 && (!d_colors || fwrite(rgb, 1, 3, f) == 3);
+                    put += fwrite(&d_vertices[i], sizeof(float), 3, f) == 3 && (!d_colors || fwrite(rgb, 1, 3, f) == 3) &&
+                           (!objects || fwrite(&d_index[i], sizeof(uint32_t), 1, f) == 1);
                 }
                 for (size_t i = 0; i < nt; ++i) put += fputc(3, f) == 3 && fwrite(d_triangles[i].v, sizeof(uint32_t), 3, f) == 3;
                 rc = (fclose(f) == 0 && put == nv + nt) ? 0 : -1;
@@ -321,7 +336,73 @@ static int volume_mesh_ply(sgm_instance* s, const sgm_volume_spec* vol, const ui
     sgm_host_free(s, d_vertices);
     sgm_host_free(s, d_triangles);
     sgm_host_free(s, d_rgba);
+    sgm_host_free(s, d_index);
     return rc;
+}
+
+/* the spec of --plane for a list of n 16-byte records {x, y, z, tag}: K and SEED; opt: -, DIST, -, AX, AY, AZ, MINCOS; 4 rounds, at
+ * least 3 inliers, pivots above 1e-9, span a quarter of the largest finite |coordinate| */
+static sgm_plane_spec plane_spec_for(const void* records, size_t n, int k, uint32_t seed, const float* opt)
+{
+    float reach = 0.0f;
+    for (size_t i = 0; i < n; ++i) {
+        const float* p = (const float*)records + 4 * i;
+        for (int a = 0; a < 3; ++a)
+            if (isfinite(p[a]) && fabsf(p[a]) > reach) reach = fabsf(p[a]);
+    }
+    const sgm_plane_spec spec = {k, seed, opt[1], {opt[3], opt[4], opt[5]}, opt[6], reach > 0.0f ? reach / 4.0f : 1.0f, 4, 3u, 1e-9f};
+    return spec;
+}
+
+/* --volume-objects: MINVOXELS, CONN, CLEARANCE and, with --plane, what that option was given */
+typedef struct { uint32_t min_voxels; int connectivity; float clearance; int have_plane, plane_k; uint32_t plane_seed; const float* plane_opt; } volume_objects;
+
+/* The objects of the volume: the components of its occupied voxels (min_weight 1), with the plane of the n surface points at
+ * d_points -- the plane --plane reports: the same records, the same spec -- excluded first where one was asked for and found; sized
+ * by a counts-only call, printed one line each.  *list: the arrays the mesh looks its vertices up in, page-locked, the caller's to
+ * free.  0 or -1 */
+static int volume_objects_report(sgm_instance* s, const sgm_volume_spec* vol, const uint32_t* d_voxels, const volume_objects* o,
+                                 const sgm_surface_point* d_points, size_t n, object_list* list)
+{
+    sgm_component_spec comp;
+    memset(&comp, 0, sizeof comp);
+    comp.min_weight = 1; comp.connectivity = o->connectivity; comp.min_voxels = o->min_voxels;
+    if (o->have_plane) {
+        const sgm_plane_spec spec = plane_spec_for(d_points, n, o->plane_k, o->plane_seed, o->plane_opt);
+        sgm_plane plane;
+        sgm_plane_stats stats;
+        if (!sgm_plane_fit(s, &spec, d_points, n, NULL, NULL, &plane, &stats, NULL, NULL)) return -1;
+        if (stats.status == 0) {
+            comp.planes = 1;
+            comp.plane[0] = plane;
+            comp.clearance[0] = o->clearance;
+        }
+    }
+    list->d_labels = (uint32_t*)sgm_host_alloc(s, sgm_volume_components_bytes(vol));
+    list->d_counts = (uint32_t*)sgm_host_alloc(s, 2 * sizeof(uint32_t));
+    list->d_objects = NULL;
+    list->capacity = 0;
+    if (!list->d_labels || !list->d_counts ||
+        !sgm_volume_components(s, vol, &comp, d_voxels, list->d_labels, NULL, 0, list->d_counts) || !sgm_synchronize(s))
+        return -1;
+    const size_t count = list->d_counts[0];
+    if (count) {
+        list->d_objects = (sgm_component*)sgm_host_alloc(s, count * sizeof(sgm_component));
+        list->capacity = count;
+        if (!list->d_objects ||
+            !sgm_volume_components(s, vol, &comp, d_voxels, list->d_labels, list->d_objects, count, list->d_counts) || !sgm_synchronize(s) ||
+            list->d_counts[0] != count)
+            return -1;
+    }
+    printf("volume objects: %zu of %u components have at least %u voxels (connectivity %d%s)\n", count, list->d_counts[1], o->min_voxels,
+           o->connectivity, comp.planes ? ", the plane excluded" : o->have_plane ? ", no plane found" : "");
+    for (size_t i = 0; i < count; ++i) {
+        float lo[3], hi[3], c[3];
+        sgm_component_metric(vol, &list->d_objects[i], lo, hi, c);
+        printf("volume object %zu: %u voxels, box (%.9g, %.9g, %.9g) to (%.9g, %.9g, %.9g), centroid (%.9g, %.9g, %.9g)\n", i + 1,
+               list->d_objects[i].voxels, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], c[0], c[1], c[2]);
+    }
+    return 0;
 }
 
 /* --volume-distance / --volume-field: both sides of the distance transform (min_weight 1, as the surface points), the signed field,
@@ -362,9 +443,10 @@ static int volume_field_file(sgm_instance* s, const sgm_volume_spec* vol, const 
  * window != NULL (--volume-window: offset, then dims): after the frame is fused the volume is replaced by that window of itself
  * (sgm_volume_window into a second allocation; the first is freed), and everything that is written is the window's.
  * distance != NULL (--volume-distance: the radius, then unknown): the signed distance field of that volume written to field_path.
+ * objects != NULL (--volume-objects): the objects of that volume printed, ahead of the mesh, whose vertices then carry theirs.
  * Page-locked buffers of an instance of its own, as above.  *out: malloc'ed, *n records. */
 static int volume_surface(const sgm_volume_spec* vol, const int32_t* window, const int32_t* distance, const char* field_path,
-                          const volume_view* view, const char* mesh_path, const uint8_t* grey, int device, int w, int h, const float* pinhole, float z_max, const float* disp, sgm_point** out, size_t* n)
+                          const volume_objects* objects, const volume_view* view, const char* mesh_path, const uint8_t* grey, int device, int w, int h, const float* pinhole, float z_max, const float* disp, sgm_point** out, size_t* n)
 {
     const sgm_cloud_spec src = {w, h, 1, pinhole[0], pinhole[1], pinhole[2], pinhole[3], pinhole[4], pinhole[5], 0.0f, z_max, 0};
     static const float identity[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
@@ -434,7 +516,12 @@ static int volume_surface(const sgm_volume_spec* vol, const int32_t* window, con
                 }
                 *n = count;
                 rc = view ? volume_render(s, vol, view, w, h, pinhole, d_voxels, d_colors, &src, d_disp) : 0;
-                if (rc == 0 && mesh_path) rc = volume_mesh_ply(s, vol, d_voxels, d_colors, 1, mesh_path);
+                object_list list = {NULL, NULL, 0, NULL};
+                if (rc == 0 && objects) rc = volume_objects_report(s, vol, d_voxels, objects, d_points, count, &list);
+                if (rc == 0 && mesh_path) rc = volume_mesh_ply(s, vol, d_voxels, d_colors, 1, objects ? &list : NULL, mesh_path);
+                sgm_host_free(s, list.d_labels);
+                sgm_host_free(s, list.d_objects);
+                sgm_host_free(s, list.d_counts);
                 if (rc == 0 && distance) rc = volume_field_file(s, vol, d_voxels, distance, field_path);
             }
         }
@@ -458,14 +545,7 @@ static int plane_report(int device, const sgm_point* pts, size_t n, int k, uint3
         const char* e = getenv("SGM_DEVICE");
         device = (e && *e) ? atoi(e) : 0;
     }
-    float reach = 0.0f;
-    for (size_t i = 0; i < n; ++i) {
-        const float c[3] = {fabsf(pts[i].x), fabsf(pts[i].y), fabsf(pts[i].z)};
-        for (int k = 0; k < 3; ++k)
-            if (isfinite(c[k]) && c[k] > reach) reach = c[k];
-    }
-    const sgm_plane_spec spec = {k, seed, opt[1], {opt[3], opt[4], opt[5]}, opt[6], reach > 0.0f ? reach / 4.0f : 1.0f,
-                                 4, 3u, 1e-9f};
+    const sgm_plane_spec spec = plane_spec_for(pts, n, k, seed, opt);
     sgm_instance* s = sgm_create(device);
     if (!s) return -1;
     sgm_point* d_records = (sgm_point*)sgm_host_alloc(s, (n ? n : 1) * sizeof(sgm_point));
@@ -578,6 +658,8 @@ int main(int argc, char** argv)
     const char* plane_labels = NULL;
     int have_distance = 0;
     const char* field_path = NULL;
+    volume_objects objects = {0, 6, 0.0f, 0, 0, 0, NULL};
+    int have_objects = 0;
     int have_view = 0;
     int register_splat = 2, register_splat_set = 0;
     int repeat = 1, device = -1, census_w = 0, census_h = 0, right_ref = 0, fill_holes = 0, refine = 0;
@@ -654,6 +736,16 @@ int main(int argc, char** argv)
             ++i;
         }
         else if (v && !strcmp(a, "--volume-field")) { field_path = v; ++i; }
+        else if (v && !strcmp(a, "--volume-objects")) {
+            long long m = 0;
+            if (sscanf(v, "%lld,%d,%f", &m, &objects.connectivity, &objects.clearance) < 1 || m < 1 || m > 0xFFFFFFFFLL) {
+                fprintf(stderr, "--volume-objects wants MINVOXELS[,CONN[,CLEARANCE]] with MINVOXELS >= 1\n");
+                return 2;
+            }
+            objects.min_voxels = (uint32_t)m;
+            have_objects = 1;
+            ++i;
+        }
         else if (v && !strcmp(a, "--plane")) {
             int k = 0;
             long long seed = 0;                                   /* K and SEED are integers: 64.7 or a seed past 32 bits is refused, not rounded */
@@ -747,6 +839,7 @@ int main(int argc, char** argv)
     if (volume_color && !have_volume) { fprintf(stderr, "--volume-color needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n"); return 2; }
     if (have_window && !have_volume) { fprintf(stderr, "--volume-window needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n"); return 2; }
     if ((have_distance || field_path) && !have_volume) { fprintf(stderr, "--volume-distance needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n"); return 2; }
+    if (have_objects && !have_volume) { fprintf(stderr, "--volume-objects needs --volume NX,NY,NZ,VOXEL,OX,OY,OZ,TRUNC\n"); return 2; }
     if (have_distance != (field_path != NULL)) { fprintf(stderr, "--volume-distance and --volume-field OUT.f32 go together\n"); return 2; }
     if (view.image_path && (!have_view || !volume_color)) {
         fprintf(stderr, "--volume-image OUT.pgm needs --volume-view ZMIN,ZMAX,STEP[,MINWEIGHT] and --volume-color\n");
@@ -907,11 +1000,12 @@ int main(int argc, char** argv)
         size_t n = 0;
         uint8_t* rect = NULL;
         const uint8_t* grey = NULL;
+        objects.have_plane = have_plane; objects.plane_k = plane_k; objects.plane_seed = plane_seed; objects.plane_opt = plane_opt;
         if (volume_color) grey = reference_grey(left, right, right_ref, calib_path != NULL, bits, (size_t)w1 * h1, &rect);
         if ((volume_color && !grey) ||
             volume_surface(&volume, have_window ? volume_window : NULL, have_distance ? volume_distance : NULL, field_path,
-                           have_view ? &view : NULL, mesh_path, grey, device, w1, h1, pinhole, cloud_z_max, disp, &pts, &n) != 0) {
-            printf("volume unavailable or --volume / --volume-window / --volume-distance / --volume-view / --volume-mesh / --pinhole / --cloud-z-max out of range\n");
+                           have_objects ? &objects : NULL, have_view ? &view : NULL, mesh_path, grey, device, w1, h1, pinhole, cloud_z_max, disp, &pts, &n) != 0) {
+            printf("volume unavailable or --volume / --volume-window / --volume-distance / --volume-objects / --volume-view / --volume-mesh / --pinhole / --cloud-z-max out of range\n");
             rc = -1;
         } else {
             if (!grey) grey = reference_grey(left, right, right_ref, calib_path != NULL, bits, (size_t)w1 * h1, &rect);

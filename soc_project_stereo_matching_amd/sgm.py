@@ -305,6 +305,55 @@ def plane_spec(hypotheses, dist, span, seed=0, axis=(0.0, 0.0, 0.0), min_cos=0.0
                         int(min_inliers), min_pivot)
 
 
+class SGMComponentSpec(C.Structure):
+    """Field-for-field sgm_component_spec of include/sgm_mi355x.h: 168 bytes, every field 4 bytes."""
+    _fields_ = [("min_weight", C.c_uint32), ("set", C.c_int32), ("unknown", C.c_int32), ("connectivity", C.c_int32),
+                ("min_voxels", C.c_uint32), ("planes", C.c_int32), ("plane", SGMPlane * 4), ("clearance", C.c_float * 4)]
+
+
+class SGMComponent(C.Structure):
+    """sgm_component of include/sgm_mi355x.h: 48 bytes."""
+    _fields_ = [("first", C.c_uint32), ("voxels", C.c_uint32), ("lo", C.c_uint16 * 3), ("hi", C.c_uint16 * 3), ("reserved", C.c_uint32),
+                ("sum", C.c_uint64 * 3)]
+
+
+COMPONENT_DTYPE = np.dtype([("first", np.uint32), ("voxels", np.uint32), ("lo", np.uint16, (3,)), ("hi", np.uint16, (3,)),
+                            ("reserved", np.uint32), ("sum", np.uint64, (3,))])
+assert COMPONENT_DTYPE.itemsize == 48 and C.sizeof(SGMComponent) == 48 and C.sizeof(SGMComponentSpec) == 168
+
+
+def component_spec(min_weight, set=0, unknown=0, connectivity=6, min_voxels=1, planes=(), clearance=()) -> SGMComponentSpec:
+    """A sgm_component_spec: the set whose components are labelled (set 0: observed voxels with tq < 0, 1: observed with tq >= 0;
+    unknown 1: the unobserved ones as well), the connectivity (6 or 26), the smallest component that keeps its label, and up to four
+    planes (PLANE_DTYPE records) with a clearance each: a voxel whose centre lies at or below clearance along a plane's normal is
+    taken out of the set.  The library validates the values; more than four planes are passed on by their number and refused."""
+    planes = np.ascontiguousarray(planes, PLANE_DTYPE).reshape(-1) if len(planes) else np.zeros(0, PLANE_DTYPE)
+    clearance = np.ascontiguousarray(clearance, np.float32).reshape(-1)
+    if planes.size != clearance.size:
+        raise ValueError("component_spec: one clearance per plane")
+    sp = SGMComponentSpec(int(min_weight), int(set), int(unknown), int(connectivity), int(min_voxels), int(planes.size))
+    for q in range(min(planes.size, 4)):
+        sp.plane[q] = SGMPlane.from_buffer_copy(planes[q].tobytes())
+        sp.clearance[q] = float(clearance[q])
+    return sp
+
+
+def volume_components_bytes(spec: SGMVolumeSpec) -> int:
+    """sgm_volume_components_bytes: 4 * nx * ny * nz, the label array, 0 for a spec the library refuses"""
+    return int(load_library().sgm_volume_components_bytes(C.byref(spec)))
+
+
+def component_metric(spec: SGMVolumeSpec, obj):
+    """sgm_component_metric (host only): the box corners and the centroid of one COMPONENT_DTYPE record in world units ->
+    (lo, hi, centroid), float32 [3] each."""
+    obj = np.ascontiguousarray(obj, COMPONENT_DTYPE).reshape(-1)
+    if obj.size != 1:
+        raise ValueError("component_metric: one record")
+    out = np.zeros((3, 3), np.float32)
+    load_library().sgm_component_metric(C.byref(spec), obj.ctypes.data, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data)
+    return out[0], out[1], out[2]
+
+
 def _plane_record(pl: SGMPlane) -> np.ndarray:
     return np.frombuffer(bytes(pl), PLANE_DTYPE)[0].copy()
 
@@ -551,6 +600,16 @@ def _load() -> C.CDLL:
         L.sgm_volume_distance.restype = C.c_bool
         L.sgm_volume_distance_field.argtypes = [C.c_void_p] * 5
         L.sgm_volume_distance_field.restype = C.c_bool
+    if hasattr(L, "sgm_volume_components"):   # (SGM_LIBRARY_PATH may point an A/B run at a build of older sources)
+        _vp, _sz = C.c_void_p, C.c_size_t
+        L.sgm_volume_components_bytes.argtypes = [_vp]
+        L.sgm_volume_components_bytes.restype = _sz
+        L.sgm_volume_components.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+        L.sgm_volume_components.restype = C.c_bool
+        L.sgm_volume_component_of.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, C.c_int, _vp]
+        L.sgm_volume_component_of.restype = C.c_bool
+        L.sgm_component_metric.argtypes = [_vp] * 5
+        L.sgm_component_metric.restype = None
     if hasattr(L, "sgm_plane_votes"):
         _vp, _sz = C.c_void_p, C.c_size_t
         L.sgm_plane_votes.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _vp]
@@ -1494,6 +1553,25 @@ class SGMInstance(_StageReader):
         """sgm_volume_distance_field: the metric field, float32 per voxel, from the side-0 words at d_out2 and, for the sign, the
         side-1 words at d_in2 (None: unsigned).  Asynchronous on `stream`."""
         return bool(self.lib.sgm_volume_distance_field(self.handle, C.byref(spec), d_out2 or None, d_in2 or None, d_field or None))
+
+    # ---- connected components of the volume (include/sgm_mi355x.h, the components section); device pointers as ints, None = NULL ----
+    def volume_components(self, spec: SGMVolumeSpec, comp: SGMComponentSpec, d_voxels: int, d_labels: int, d_objects, capacity: int,
+                          d_counts: int) -> bool:
+        """sgm_volume_components: per voxel the label of its component (uint32 into d_labels, volume_components_bytes(spec) bytes:
+        the smallest voxel index of the component plus 1, or 0), the first `capacity` surviving components as COMPONENT_DTYPE
+        records into d_objects (None with capacity 0: labels and counts alone) and into d_counts the numbers of surviving and of all
+        components.  Asynchronous on `stream`."""
+        return bool(self.lib.sgm_volume_components(self.handle, C.byref(spec), C.byref(comp), d_voxels or None, d_labels or None,
+                                                   d_objects or None, int(capacity), d_counts or None))
+
+    def volume_component_of(self, spec: SGMVolumeSpec, d_labels: int, d_objects, capacity: int, d_counts: int, d_records, records_capacity: int,
+                            d_records_count, id_kinds: int, d_index) -> bool:
+        """sgm_volume_component_of: for each of the first `records_capacity` records at d_records (and d_records_count[0], where
+        given) -- the vertices of volume_mesh with id_kinds 8, the points of volume_points with 4 -- 1 plus the position of its
+        object in the list volume_components wrote, or 0, as uint32 into d_index.  Asynchronous on `stream`."""
+        return bool(self.lib.sgm_volume_component_of(self.handle, C.byref(spec), d_labels or None, d_objects or None, int(capacity),
+                                                     d_counts or None, d_records or None, int(records_capacity), d_records_count or None,
+                                                     int(id_kinds), d_index or None))
 
     # ---- frame-to-model tracking (include/sgm_mi355x.h, sgm_track_spec); device pointers as ints, None = NULL ----
     def track_sums(self, src: SGMCloudSpec, model: SGMTrackSpec, poses, d_disp, d_mask, d_conf, d_model_depth: int, d_model_normal: int,
